@@ -2,7 +2,7 @@
 """Throughput of the assembly hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c1|c5|tiny] [--algo auto|sumfact|entrywise]
-                    [--weak] [--emulate R/W] [--op matrix|rhs|entries]
+                    [--weak] [--emulate R/W] [--op matrix|rhs|entries] [--dump-outputs DIR]
 
 Workload (BASELINE.json): stiffness assembly of a tensor-product B-spline patch over the NURBS quarter-annulus
 cylinder; default C4 = 3D, p=4, 128^3 spans (2.1 M elements, 1.59 G nonzeros).  One "step" = one complete assembly of
@@ -277,6 +277,53 @@ def api_call(args, kvs, geo, kind, nnz):
     return round(dt, 3)
 
 
+DUMP_MAX_ENTRIES = 1 << 21     # --dump-outputs: 3 float64 arrays of at most 2^21 entries = 48 MiB
+DUMP_RUN = 4096                # a larger result is sampled as seeded runs of this many consecutive CSR entries
+
+
+def _device_csr_reader(patch):
+    """(row_lo, local indptr, read(which, lo, n)) of the CSR result resident on the device: the values of the most recent
+    assembly (igx_d_csr_data, what assemble(to_host=True) would have copied) and the pattern (igx_pattern builds it on the
+    device if no call has yet)."""
+    import ctypes as C
+    from pyiga_amd import _lib
+    lib = _lib.load()
+    lo, hi = patch.row_range
+    indptr = np.empty(hi - lo + 1, dtype=np.int32)
+    _lib.check(lib.igx_pattern(patch.handle, indptr.ctypes.data_as(C.POINTER(C.c_int32)), None), 'igx_pattern')
+    src = {'values': (lib.igx_d_csr_data(patch.handle), np.float64), 'cols': (lib.igx_d_csr_indices(patch.handle), np.int32)}
+    nnz = patch.nnz
+
+    def read(which, k, n):
+        ptr, dtype = src[which]
+        assert ptr and 0 <= k and k + n <= nnz, (which, k, n, nnz)
+        out = np.empty(n, dtype=dtype)
+        _lib.check(lib.igx_dev_download(patch.ctx.handle, out.ctypes.data, ptr + k * out.itemsize, out.nbytes), 'igx_dev_download')
+        return out
+    return lo, indptr, read
+
+
+def dump_outputs(directory, patch, reader, prefix='', max_entries=DUMP_MAX_ENTRIES):
+    """Write the CSR matrix the timed path left on the device as <prefix>csr_values / csr_rows / csr_cols .npy (float64;
+    rows and columns are global ids): every entry if there are at most `max_entries`, otherwise the entries of a fixed
+    sample (seed 0) of whole runs of DUMP_RUN consecutive entries -- the same entries for the same arguments."""
+    row_lo, indptr, read = reader
+    nnz = int(patch.nnz)
+    if nnz <= max_entries:
+        starts, run = np.array([0], dtype=np.int64), nnz
+    else:
+        run = DUMP_RUN
+        starts = np.sort(np.random.default_rng(0).choice(nnz // run, max(1, max_entries // run), replace=False)).astype(np.int64) * run
+    pos = (starts[:, None] + np.arange(run, dtype=np.int64)).ravel()
+    values = np.concatenate([read('values', int(k), run) for k in starts]) if run else np.empty(0)
+    cols = np.concatenate([read('cols', int(k), run) for k in starts]) if run else np.empty(0, dtype=np.int32)
+    rows = row_lo + np.searchsorted(indptr.astype(np.int64), pos, side='right') - 1
+    os.makedirs(directory, exist_ok=True)
+    for name, a in (('csr_values', values), ('csr_rows', rows), ('csr_cols', cols)):
+        np.save(os.path.join(directory, prefix + name + '.npy'), np.asarray(a, dtype=np.float64))
+    return {'dir': directory, 'entries': int(pos.size), 'nnz': nnz, 'sampled': bool(pos.size < nnz)}
+
+
 def flush_c_stdio():
     # RCCL writes its banner through C stdio, which is block-buffered on a pipe: flush it so that the result is the LAST line
     try:
@@ -375,7 +422,15 @@ def main():
     ap.add_argument('--placement-tries', type=int, default=1,
                     help='candidate buffers for the CSR values, timed under the mirror pass at the FIRST assembly (outside the timed region; '
                          'IGX_PLACEMENT_TRIES: the pass follows where the driver put the buffer); 1: plain allocation')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps write the CSR matrix of the last one to DIR/csr_{values,rows,cols}.npy (float64; '
+                         'at most %d entries, a fixed seeded sample of a larger matrix; each rank of a multi-rank run its slab, '
+                         'prefixed rank<r>_); --op matrix / form' % DUMP_MAX_ENTRIES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.op not in ('matrix', 'form'):
+        ap.error('--dump-outputs writes the matrix of --op matrix / form')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if world == 1 and args.gpus > 1 and 'RANK' not in os.environ:
@@ -468,7 +523,12 @@ def main():
     def barrier():
         if dist is not None:
             import torch
-            dist.barrier()
+            if os.environ.get('BENCH_SHARE_GPU'):
+                # gloo: dist.barrier() probes for an accelerator (and so opens the GPU even in a rank that never uses it);
+                # an all-reduce of a host tensor synchronises the ranks just the same
+                dist.all_reduce(torch.zeros(1, dtype=torch.float64))
+            else:
+                dist.barrier()
             if not os.environ.get('BENCH_PATCH_STUB'):
                 torch.cuda.synchronize()
         patch.ctx.sync()
@@ -500,6 +560,11 @@ def main():
         algo_used = tm['algo_used']
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:        # outside the timed region; the device values are those of the last timed step
+        reader = patch.dump_csr_reader() if stub else _device_csr_reader(patch)
+        dumped = dump_outputs(args.dump_outputs, patch, reader, prefix='rank%d_' % rank if world > 1 else '',
+                              max_entries=DUMP_MAX_ENTRIES // world)
     slab_ms = [float(np.median(steps_ms))]
     if dist is not None:
         import torch
@@ -616,6 +681,8 @@ def main():
     }
     if cpu is not None:
         out['cpu_baseline'] = cpu
+    if dumped is not None:
+        out['dump_outputs'] = dumped
     if dist is not None:
         dist.destroy_process_group()        # before the result line: anything RCCL prints comes first
     flush_c_stdio()

@@ -34,3 +34,13 @@ class DevicePatch:
 
     def close(self):
         pass
+
+    def dump_csr_reader(self):
+        """bench.py --dump-outputs: a made-up CSR of the slab (rows of nearly equal length, values a function of the position)."""
+        nrows = self.shape[0]
+        indptr = np.round(np.linspace(0, self.nnz, nrows + 1)).astype(np.int32)
+
+        def read(which, k, n):
+            pos = np.arange(k, k + n, dtype=np.int64)
+            return np.sin(pos + 1.0) if which == 'values' else (pos % self.shape[1]).astype(np.int32)
+        return self.row0[0] * (self.shape[0] // (self.row0[1] - self.row0[0])), indptr, read

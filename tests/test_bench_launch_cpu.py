@@ -54,3 +54,57 @@ def test_self_launch_eight_ranks():
     N, p = 14, 2
     S = sum(min(i + p, N - 1) + 1 - max(i - p, 0) for i in range(N))
     assert d['config']['nnz'] == S ** 3 and 'scaling_model' in d
+
+
+def test_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs DIR: the CSR of the last timed step as float64 .npy files (at most 64 MB), the same for the same arguments;
+    --steps sets the number of timed steps and the line carries ms_per_step."""
+    import numpy as np
+    files = {}
+    for run in ('a', 'b'):
+        d = tmp_path / run
+        r = _run(['--steps', '3', '--warmup', '1', '--config', 'tiny', '--no-cpu-baseline', '--no-api-call', '--dump-outputs', str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.rstrip().splitlines()[-1])
+        assert line['steps'] == 3 and line['ms_per_step'] > 0
+        assert line['dump_outputs']['entries'] == line['config']['nnz'] and not line['dump_outputs']['sampled']
+        files[run] = {p.name: np.load(p) for p in sorted(d.iterdir())}
+    assert sorted(files['a']) == ['csr_cols.npy', 'csr_rows.npy', 'csr_values.npy']
+    assert sum(a.nbytes for a in files['a'].values()) <= 64 << 20
+    for name, a in files['a'].items():
+        assert a.dtype == np.float64 and a.shape == (262144,)
+        assert np.array_equal(a, files['b'][name])
+    assert _run(['--steps', '0', '--config', 'tiny', '--no-cpu-baseline']).returncode != 0
+
+
+def test_dump_outputs_of_two_ranks(tmp_path):
+    r = _run(['--gpus', '2', '--steps', '2', '--warmup', '0', '--config', 'tiny', '--no-cpu-baseline', '--dump-outputs', str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == sorted('rank%d_csr_%s.npy' % (k, a) for k in range(2) for a in ('cols', 'rows', 'values'))
+
+
+def test_dump_outputs_sample_of_a_large_matrix(tmp_path):
+    """A matrix above the entry budget is written as a fixed seeded sample of whole runs of consecutive entries."""
+    import numpy as np
+    import bench
+
+    class Patch:
+        nnz = 50 * bench.DUMP_RUN + 123
+    indptr = np.arange(0, Patch.nnz + 1, 7, dtype=np.int32)
+    indptr[-1] = Patch.nnz
+    calls = []
+
+    def read(which, k, n):
+        calls.append((which, k, n))
+        assert 0 <= k and k + n <= Patch.nnz
+        pos = np.arange(k, k + n)
+        return pos * 0.5 if which == 'values' else (pos % 11).astype(np.int32)
+    out = [bench.dump_outputs(str(tmp_path / s), Patch(), (100, indptr, read), max_entries=8 * bench.DUMP_RUN) for s in 'ab']
+    assert out[0]['sampled'] and out[0]['entries'] == 8 * bench.DUMP_RUN and out[0]['nnz'] == Patch.nnz
+    v, rows, cols = (np.load(tmp_path / 'a' / ('csr_%s.npy' % n)) for n in ('values', 'rows', 'cols'))
+    pos = (v * 2).astype(np.int64)
+    assert np.array_equal(rows, 100 + np.searchsorted(indptr, pos, side='right') - 1) and np.array_equal(cols, pos % 11)
+    assert np.all(pos % bench.DUMP_RUN == np.tile(np.arange(bench.DUMP_RUN), 8))
+    for n in ('values', 'rows', 'cols'):
+        assert np.array_equal(np.load(tmp_path / 'a' / ('csr_%s.npy' % n)), np.load(tmp_path / 'b' / ('csr_%s.npy' % n)))
