@@ -779,11 +779,9 @@ int igx_patch_set_form(igx_patch *pt, const double *const coef[16])
 // resident Gauss points and the arrays take the way of igx_patch_set_form_d.
 // The physical coefficient table of a form given as expressions, as the fast chain wants it: constants told from expressions
 // (a constant is a number, possibly in parentheses: pyiga_amd.symbolic writes them so), equal entries found by their text.
-static void capture_form_table(igx_patch *pt, const char *const expr[16])
+static igx_patch::FormTable capture_form_table(const char *const expr[16])
 {
-    igx_patch::FormTable &T = pt->ftab;
-    T = igx_patch::FormTable();
-    (void)hipFree(pt->ftab_arr); pt->ftab_arr = nullptr; pt->ftab_ready = false;
+    igx_patch::FormTable T;
     for (int k = 0; k < 16; ++k) {
         T.arr_of[k] = -1;
         if (!expr[k]) continue;
@@ -828,6 +826,18 @@ static void capture_form_table(igx_patch *pt, const char *const expr[16])
         if (T.arr_of[k] < 0) T.arr_of[k] = T.narr++;
     }
     T.valid = true;
+    return T;
+}
+
+// ... committed to the patch (and its twin) only when the form itself has been set: until then the fast chain and the other
+// algorithms go on describing the previous form
+static void commit_form_table(igx_patch *pt, const igx_patch::FormTable &T)
+{
+    for (igx_patch *q : {pt, pt->twin}) {
+        if (!q) continue;
+        q->ftab = T;
+        (void)hipFree(q->ftab_arr); q->ftab_arr = nullptr; q->ftab_ready = false;
+    }
 }
 
 int igx_patch_set_form_expr(igx_patch *pt, const char *const expr[16], int *cache_hit)
@@ -844,10 +854,9 @@ int igx_patch_set_form_expr(igx_patch *pt, const char *const expr[16], int *cach
         for (int s = 0; s < 4; ++s)
             if (expr[4 * r + s] && (r >= nj || s >= nj)) { set_error("igx_patch_set_form_expr: coefficient (%d,%d) does not exist in %dD", r, s, pt->dim); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(pt->ctx->device));
-    capture_form_table(pt, expr);
     // (the table is one of PHYSICAL coefficients in physical coordinates: the twin of a patch with repeated knots on its last axis
     // -- igx_patch::twin -- takes it as it is and samples its functions on its own Gauss grid when its chain first runs)
-    if (pt->twin) capture_form_table(pt->twin, expr);
+    const igx_patch::FormTable T = capture_form_table(expr);
     if (form_fields_applicable(pt)) {
         int form_ab[16];
         const int nt = form_terms(pt->dim, expr, form_ab);
@@ -861,6 +870,7 @@ int igx_patch_set_form_expr(igx_patch *pt, const char *const expr[16], int *cach
         pt->dev.form_n = nt;
         pt->dev.form_par = 0;
         pt->fields_kind = -1;
+        commit_form_table(pt, T);
         return IGX_OK;
     }
     const size_t npts = (size_t)pt->dev.npts_loc;
@@ -874,6 +884,7 @@ int igx_patch_set_form_expr(igx_patch *pt, const char *const expr[16], int *cach
         rc = set_form_impl(pt, d_coef, true, "igx_patch_set_form_expr");
     }
     (void)hipFree(buf);
+    if (!rc) commit_form_table(pt, T);
     return rc;
 }
 

@@ -13,6 +13,7 @@ import pytest
 import scipy.sparse
 
 from conftest import GOLDEN, golden_csr, rel_maxdiff, form_inputs, form_tables, FORMS, form2d_cases, PFORMS2, PFORMS3, pform_inputs2
+import _bf3_cases as bc
 
 pytestmark = pytest.mark.gpu
 
@@ -2523,7 +2524,8 @@ def test_fused_stage_with_unequal_degrees_and_repeated_knots(iga, monkeypatch):
     """Round 5: k_bf3 serves every symmetric 3D patch with single knots on the LAST axis -- degrees of the swept and the last
     axis one below nqp = max degree + 1 (pyiga/assemblers.pyx:1338), repeated knots on the swept axis (equal degrees) and on
     axis 0.  Against the entry-wise kernels (the reference's loop nest), exactly symmetric, every value written, the fused
-    stage really ran, and row slabs reproduce the patch bit for bit."""
+    stage really ran, and row slabs reproduce the patch bit for bit.  (Every instantiation of k_bf3, one case each:
+    tests/_bf3_cases.py, test_every_bf3_instantiation_vs_oracle.)"""
     mk = iga.bspline.make_knots
     monkeypatch.setenv('IGX_DEBUG_POISON', '1')
 
@@ -2571,3 +2573,161 @@ def test_fused_stage_with_unequal_degrees_and_repeated_knots(iga, monkeypatch):
                     parts.append(sl.assemble(kind, algo='sumfact', to_host=True).copy())
                     sl.close()
             assert np.array_equal(np.concatenate(parts), A.data), tag
+
+
+# ---------------------------------------------------------------------------------------------
+# every compiled k_bf3 instantiation (tests/_bf3_cases.py; tests/test_bf3_coverage_cpu.py ties the table to fused3.hip)
+def _bf3_coeff(x, y, z):
+    return 1.0 + x * x + 0.5 * z
+
+
+def _bf3_patch_kvs(iga, axes):
+    return tuple(iga.bspline.KnotVector(bc.axis_knots(a), a[0]) for a in axes)
+
+
+def _bf3_oracle(kind, kvs, gname):
+    from oracle import iga_oracle as orc
+    okvs = tuple(orc.KnotVector(np.asarray(kv.kv), kv.p) for kv in kvs)
+    geo = orc.geo_cylinder() if gname == 'cylinder' else orc.geo_twisted_box()
+    if kind == 'convdiff':
+        return orc.assemble_nonsymmetric('convdiff', okvs, geo, coeff=_bf3_coeff, nthreads=8)
+    return orc.assemble(kind, okvs, geo, nthreads=8)
+
+
+def _bf3_assemble(iga, kind, kvs, gname, algo, row0=None):
+    """(CSR matrix, last_path) of one patch or row slab."""
+    geo = _geo(iga, gname)
+    if kind == 'convdiff':
+        asm = iga.assemblers.ConvDiffAssembler3D(kvs, geo, _bf3_coeff, row0=row0)
+        A = asm.assemble_csr(algo=algo)
+        path = asm.patch.last_path()
+        asm.patch.close()
+        return A, path
+    patch = iga.assemblers.DevicePatch(kvs, geo, row0=row0)
+    A = patch.csr(kind, algo=algo)
+    path = patch.last_path()
+    patch.close()
+    return A, path
+
+
+def _bf3_check_vs_oracle(A, R, kvs, kind, tag):
+    """Every value written, exact symmetry, the reference's pattern, the oracle's values.  The pattern is the structural one
+    (MLStructure, oracle.full_pattern): the oracle's matrix is a sum of two scipy matrices, which drops entries that are
+    exactly zero -- those of two functions whose supports share only an empty-width span, as make_knots makes for some n
+    (bspline.make_knots: n = 49 gives a last interior knot of 1 - 1e-16)."""
+    from oracle import iga_oracle as orc
+    assert not np.isnan(A.data).any(), tag                    # every value written (IGX_DEBUG_POISON)
+    if kind != 'convdiff':
+        assert abs(A - A.T).max() == 0.0, tag
+    I, J = orc.full_pattern(tuple(orc.KnotVector(np.asarray(kv.kv), kv.p) for kv in kvs))
+    P = scipy.sparse.csr_matrix((np.ones(len(I)), (I, J)), shape=R.shape)
+    P.sort_indices()
+    assert A.shape == R.shape and np.array_equal(A.indptr, P.indptr) and np.array_equal(A.indices, P.indices), tag
+    assert rel_maxdiff(A, R) <= RTOL, (tag, rel_maxdiff(A, R))
+
+
+@pytest.mark.parametrize('case', bc.BF3_CASES, ids=[c.id for c in bc.BF3_CASES])
+def test_every_bf3_instantiation_vs_oracle(iga, case, monkeypatch):
+    """Every k_bf3 instantiation launch_bf3 can pick -- 27 (P1, P2, Q) x {mass, stiffness}, the convection-diffusion form at
+    equal degrees, repeated knots on the swept axis (MULT) and on the last axis (TR, the twin) for the three forms -- on a small
+    patch shaped for the edges (tests/_bf3_cases.py): the intended kernel ran (not a fallback), every value written, exact
+    symmetry, the pattern and the values of the CPU oracle (the reference's loop nest), the entry-wise kernels, and -- one case
+    per (P1, P2, Q) -- row slabs of axis 0 bit for bit."""
+    monkeypatch.setenv('IGX_DEBUG_POISON', '1')
+    kind, key = case.kind, case.key
+    kvs = _bf3_patch_kvs(iga, case.axes)
+    A, path = _bf3_assemble(iga, kind, kvs, case.geo, 'sumfact')
+    tag = (case.id, key, sorted(path))
+    assert 'bf3' in path and ('twin' in path) == key.tr, tag
+    if kind != 'convdiff':
+        assert 'both' in path, tag
+    _bf3_check_vs_oracle(A, _bf3_oracle(kind, kvs, case.geo), kvs, kind, tag)
+    E, _ = _bf3_assemble(iga, kind, kvs, case.geo, 'entrywise')
+    assert rel_maxdiff(A, E) <= RTOL, (tag, rel_maxdiff(A, E))
+    if not case.slabs:
+        return
+    N0 = kvs[0].numdofs
+    cuts = sorted(set([0, 1, N0 // 2, N0]))
+    parts = []
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        S, spath = _bf3_assemble(iga, kind, kvs, case.geo, 'sumfact', row0=(lo, hi))
+        assert 'bf3' in spath and ('twin' in spath) == key.tr, (tag, lo, hi, sorted(spath))
+        parts.append(S)
+    V = scipy.sparse.vstack(parts).tocsr()
+    assert np.array_equal(V.indptr, A.indptr) and np.array_equal(V.indices, A.indices) and np.array_equal(V.data, A.data), (tag, 'slabs')
+
+
+@pytest.mark.parametrize('axes01,p2,gname,kind', bc.EDGE_SWEEPS, ids=['%s-p%d%d%d' % (s[3], s[0][0][0], s[0][1][0], s[1]) for s in bc.EDGE_SWEEPS])
+def test_bf3_tile_edges_along_the_last_axis(iga, axes01, p2, gname, kind, monkeypatch):
+    """k_bf3 cuts the last axis into tiles of RMAX rows (BF3Geom::rmax, fused3.hip): the dof count of the last axis runs over
+    2 p + 1 .. 2 RMAX + 2 -- one, two and three tiles, every position of the last tile's edge -- against the CPU oracle, every
+    value written."""
+    monkeypatch.setenv('IGX_DEBUG_POISON', '1')
+    spans, rmax = bc.edge_sweep_sizes(axes01, p2, kind)
+    keys = set()
+    for n2 in spans:
+        axes = tuple(axes01) + ((p2, n2, 1),)
+        key = bc.bf3_key(axes, kind)
+        keys.add(key)
+        kvs = _bf3_patch_kvs(iga, axes)
+        A, path = _bf3_assemble(iga, kind, kvs, gname, 'sumfact')
+        tag = (kind, key, kvs[2].numdofs, rmax, sorted(path))
+        assert key is not None and 'bf3' in path and 'twin' not in path, tag
+        _bf3_check_vs_oracle(A, _bf3_oracle(kind, kvs, gname), kvs, kind, tag)
+    assert len(keys) == 1 and kvs[2].numdofs >= 2 * rmax + 2
+
+
+@pytest.mark.parametrize('last_rep', [1, 2], ids=['single-knots', 'twin'])
+def test_failed_set_form_expr_keeps_the_previous_form(iga, last_rep, monkeypatch, tmp_path):
+    """A call of igx_patch_set_form_expr that fails (the expressions do not compile: IGX_ERR_COMPILE; no run-time compiler:
+    IGX_ERR_NORTC) leaves the previous form in place for EVERY algorithm: the fast chain's coefficient table (of the patch and
+    of its axis-exchanged twin) as well as the field kernel of the entry-wise path."""
+    import ctypes
+    from pyiga_amd import _lib
+    mk = iga.bspline.make_knots
+    kvs = (mk(2, 0., 1., 3), mk(3, 0., 1., 4), iga.bspline.KnotVector(bc.axis_knots((3, 5, last_rep)), 3))
+    patch = iga.assemblers.DevicePatch(kvs, _geo(iga, 'cylinder'))
+
+    def table(c0, c1, bad=None):
+        t = [[None] * 4 for _ in range(4)]
+        t[0][0] = c0
+        for k in range(1, 4):
+            t[k][k] = c1
+        if bad:
+            t[1][1] = bad
+        return t
+
+    def set_raw(t):
+        exprs = (ctypes.c_char_p * 16)()
+        for r in range(4):
+            for s in range(4):
+                if t[r][s] is not None:
+                    exprs[4 * r + s] = t[r][s].encode()
+        hit = ctypes.c_int(0)
+        return _lib.load().igx_patch_set_form_expr(patch.handle, exprs, ctypes.byref(hit))
+
+    def both():
+        A = patch.csr('form', algo='sumfact')
+        path = patch.last_path()
+        assert 'bf3' in path and ('twin' in path) == (last_rep > 1), sorted(path)
+        return A, patch.csr('form', algo='entrywise')
+
+    patch.set_form_expr(table('1.0', '2.0'))
+    A_old, E_old = both()
+    assert rel_maxdiff(A_old, E_old) <= RTOL
+    # no run-time compiler: a table of constants the fast chain could take without compiling anything
+    monkeypatch.setenv('IGX_NO_HIPRTC', '1')
+    monkeypatch.setenv('IGX_CACHE_DIR', str(tmp_path / 'empty_cache'))
+    assert set_raw(table('3.25', '0.5')) == _lib.IGX_ERR_NORTC
+    A, E = both()
+    assert rel_maxdiff(A, A_old) <= RTOL and rel_maxdiff(E, A_old) <= RTOL, (rel_maxdiff(A, A_old), rel_maxdiff(E, A_old))
+    monkeypatch.delenv('IGX_NO_HIPRTC')
+    # an expression that does not compile
+    assert set_raw(table('3.25', '0.5', bad='x + undefined_name')) == _lib.IGX_ERR_COMPILE
+    A, E = both()
+    assert rel_maxdiff(A, A_old) <= RTOL and rel_maxdiff(E, A_old) <= RTOL, (rel_maxdiff(A, A_old), rel_maxdiff(E, A_old))
+    # ... and the next call that succeeds takes effect for both algorithms
+    assert set_raw(table('3.25', '0.5')) == _lib.IGX_OK
+    A, E = both()
+    assert rel_maxdiff(A, E) <= RTOL and rel_maxdiff(A, A_old) > 1e-3
+    patch.close()
