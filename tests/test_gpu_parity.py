@@ -14,6 +14,7 @@ import scipy.sparse
 
 from conftest import GOLDEN, golden_csr, rel_maxdiff, form_inputs, form_tables, FORMS, form2d_cases, PFORMS2, PFORMS3, pform_inputs2
 import _bf3_cases as bc
+import _geoa_cases as gc
 
 pytestmark = pytest.mark.gpu
 
@@ -2610,14 +2611,14 @@ def _bf3_assemble(iga, kind, kvs, gname, algo, row0=None):
     return A, path
 
 
-def _bf3_check_vs_oracle(A, R, kvs, kind, tag):
+def _bf3_check_vs_oracle(A, R, kvs, kind, tag, symmetric=None):
     """Every value written, exact symmetry, the reference's pattern, the oracle's values.  The pattern is the structural one
     (MLStructure, oracle.full_pattern): the oracle's matrix is a sum of two scipy matrices, which drops entries that are
     exactly zero -- those of two functions whose supports share only an empty-width span, as make_knots makes for some n
     (bspline.make_knots: n = 49 gives a last interior knot of 1 - 1e-16)."""
     from oracle import iga_oracle as orc
     assert not np.isnan(A.data).any(), tag                    # every value written (IGX_DEBUG_POISON)
-    if kind != 'convdiff':
+    if (kind != 'convdiff') if symmetric is None else symmetric:
         assert abs(A - A.T).max() == 0.0, tag
     I, J = orc.full_pattern(tuple(orc.KnotVector(np.asarray(kv.kv), kv.p) for kv in kvs))
     P = scipy.sparse.csr_matrix((np.ones(len(I)), (I, J)), shape=R.shape)
@@ -2731,3 +2732,126 @@ def test_failed_set_form_expr_keeps_the_previous_form(iga, last_rep, monkeypatch
     A, E = both()
     assert rel_maxdiff(A, E) <= RTOL and rel_maxdiff(A, A_old) > 1e-3
     patch.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# every compiled k_geoA instantiation (tests/_geoa_cases.py; tests/test_geoa_coverage_cpu.py ties the table to geoa.hip)
+def _geoa_coeff(x, y, z):
+    return 1.0 + x * x + 0.5 * z
+
+
+_GEOA_AFFINE = (1.0, 0.5, -0.25, 0.125)
+
+
+def _geoa_assemble(iga, axes, geo, kind, table, coeff, algo, monkeypatch, row0=None):
+    """(CSR matrix, last_path) of one patch or row slab of a case."""
+    kvs = _bf3_patch_kvs(iga, axes)
+    g = gc.product_geo(iga, geo, len(axes))
+    if kind == 'convdiff':
+        if coeff == 'affine':
+            asm = iga.assemblers.ConvDiffAssembler3D(kvs, g, iga.assemblers.AffineCoefficient(*_GEOA_AFFINE), row0=row0)
+        else:
+            with monkeypatch.context() as m:
+                if coeff == 'sampled':
+                    m.setenv('IGX_FORM_RTC', '0')                  # sampled on the host, read per point
+                asm = iga.assemblers.ConvDiffAssembler3D(kvs, g, _geoa_coeff, row0=row0)
+        A = asm.assemble_csr(algo=algo)
+        path = asm.patch.last_path()
+        asm.patch.close()
+        return A, path
+    patch = iga.assemblers.DevicePatch(kvs, g, row0=row0)
+    if table is not None:
+        patch.set_form_expr(gc.TABLES[table])
+    A = patch.csr('form' if table is not None else kind, algo=algo)
+    path = patch.last_path()
+    patch.close()
+    return A, path
+
+
+def _geoa_oracle(axes, geo, kind, table, coeff):
+    from oracle import iga_oracle as orc
+    okvs = tuple(orc.KnotVector(bc.axis_knots(a), a[0]) for a in axes)
+    ogeo = gc.oracle_geo(orc, geo, len(axes))
+    if kind == 'convdiff':
+        c = _geoa_coeff if coeff != 'affine' else (lambda x, y, z: _GEOA_AFFINE[0] + _GEOA_AFFINE[1] * x + _GEOA_AFFINE[2] * y + _GEOA_AFFINE[3] * z)
+        return orc.assemble_nonsymmetric('convdiff', okvs, ogeo, coeff=c, nthreads=8)
+    if table is not None:
+        return orc.assemble_nonsymmetric('form', okvs, ogeo, table=gc.table_oracle(gc.TABLES[table]), nthreads=8)
+    return orc.assemble(kind, okvs, ogeo, nthreads=8)
+
+
+def _geoa_slabs(iga, axes, geo, kind, table, coeff, cuts, monkeypatch, key, twin):
+    """The row slabs [cuts[k], cuts[k + 1]) of axis 0, stacked; each ran k_geoA (and the twin) like the whole patch."""
+    parts = []
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        S, spath = _geoa_assemble(iga, axes, geo, kind, table, coeff, 'sumfact', monkeypatch, row0=(lo, hi))
+        assert ('geoA' in spath) == (key is not None) and ('twin' in spath) == twin, (lo, hi, sorted(spath))
+        parts.append(S)
+    return scipy.sparse.vstack(parts).tocsr()
+
+
+def _geoa_check(iga, axes, geo, kind, table, coeff, key, twin, bf3, tag, monkeypatch):
+    """The whole patch: the intended chain ran, against the oracle and the entry-wise kernels; returns it."""
+    A, path = _geoa_assemble(iga, axes, geo, kind, table, coeff, 'sumfact', monkeypatch)
+    tag = (tag, key, sorted(path))
+    assert ('geoA' in path) == (key is not None) and ('twin' in path) == twin, tag
+    if bf3 is not None:
+        assert ('bf3' in path) == bf3, tag
+    sym = kind in ('mass', 'stiffness', 'form_sym')
+    R = _geoa_oracle(axes, geo, kind, table, coeff)
+    _bf3_check_vs_oracle(A, R, _bf3_patch_kvs(iga, axes), kind, tag, symmetric=sym)
+    E, _ = _geoa_assemble(iga, axes, geo, kind, table, coeff, 'entrywise', monkeypatch)
+    assert rel_maxdiff(A, E) <= RTOL, (tag, rel_maxdiff(A, E))
+    return A
+
+
+@pytest.mark.parametrize('case', gc.GEOA_CASES, ids=[c.id for c in gc.GEOA_CASES])
+def test_every_geoa_instantiation_vs_oracle(iga, case, monkeypatch):
+    """Every (k_geoA instantiation, form) launch_geoA can pick -- mass and stiffness at P = 2 .. 6 (one sweep wave for the mass
+    form at P = 6), the matrix-core sweep, the convection-diffusion form, symmetric and non-symmetric coefficient tables, the 2D
+    chain; geometry maps of degree 1 and 2 along axis 0 with spans not nested in the space mesh, B-spline and NURBS -- on a patch
+    shaped for the edges (tests/_geoa_cases.py), and the decision edges where k_geoA must not run: the intended kernels ran
+    (k_geoA, k_bf3, the twin, as restated), every value written, exact symmetry for the symmetric forms, the pattern and the values
+    of the CPU oracle from the same control net, the entry-wise kernels, and -- one case per (P, P0G, NC, FORM, D2) -- row slabs
+    of axis 0 bit for bit."""
+    monkeypatch.setenv('IGX_DEBUG_POISON', '1')
+    if case.mfma:
+        monkeypatch.setenv('IGX_GEOA', 'mfma')                 # (knobs are read when a patch is created)
+    bf3 = None if case.key is None else case.bf3
+    A = _geoa_check(iga, case.axes, case.geo, case.kind, case.table, case.coeff, case.key, case.twin, bf3, case.id, monkeypatch)
+    if not case.slabs:
+        return
+    N0 = bc.numdofs(case.axes[0])
+    cuts = sorted(set([0, 1, N0 // 2, N0]))
+    V = _geoa_slabs(iga, case.axes, case.geo, case.kind, case.table, case.coeff, cuts, monkeypatch, case.key, case.twin)
+    assert np.array_equal(V.indptr, A.indptr) and np.array_equal(V.indices, A.indices) and np.array_equal(V.data, A.data), (case.id, 'slabs')
+
+
+@pytest.mark.parametrize('sweep', gc.CHUNK_SWEEPS, ids=[s[0] for s in gc.CHUNK_SWEEPS])
+def test_geoa_axis0_chunks(iga, sweep, monkeypatch):
+    """k_geoA splits the axis-0 sweep of a patch with a small cross-section into blockIdx.y chunks (sumfact.hip: sweep_chunks,
+    geoa2d_min_chunk); each chunk re-walks P - 1 warm-up spans.  Axis 0 runs over sizes that give 1, 2, 3 and 4 chunks and every
+    remainder of the last chunk, with a C^0 knot and a geometry span boundary inside the warm-up spans before a chunk start:
+    against the oracle and the entry-wise kernels, and -- for the sizes of 3 and 4 chunks with no remainder -- row slabs cut just
+    before, at and after a chunk boundary reproduce the whole patch bit for bit (a slab has fewer spans and a chunking of its
+    own)."""
+    name, ml, p0, (deg0, nurbs), kind, extra = sweep
+    monkeypatch.setenv('IGX_DEBUG_POISON', '1')
+    table = extra if kind.startswith('form') else None
+    coeff = extra if kind == 'convdiff' else None
+    seen = set()
+    for n0 in gc.chunk_sweep_sizes(ml, p0):
+        a0, gk, length, nch = gc.chunk_axis0(ml, p0, n0)
+        axes = (a0,) + tuple(ml)
+        geo = gc.Geo(deg0, gk, nurbs, 300 + n0)
+        key, twin = gc.geoa_route(axes, geo, kind, gc.TABLES[table] if table else None)
+        tag = (name, n0, length, nch)
+        assert key is not None and not twin, tag
+        A = _geoa_check(iga, axes, geo, kind, table, coeff, key, False, gc.expect_bf3(axes, kind, key), tag, monkeypatch)
+        if nch in (3, 4) and n0 % nch == 0 and nch not in seen:
+            seen.add(nch)
+            b = length * (1 if nch == 3 else 2)                # a chunk start (in spans = in dofs of its first function)
+            cuts = [0, b - 1, b, b + 1, bc.numdofs(a0)]
+            V = _geoa_slabs(iga, axes, geo, kind, table, coeff, cuts, monkeypatch, key, False)
+            assert np.array_equal(V.indptr, A.indptr) and np.array_equal(V.indices, A.indices) and np.array_equal(V.data, A.data), (tag, 'slabs')
+    assert seen == {3, 4}
