@@ -33,6 +33,8 @@
  *                                         pyiga/genericasm.pxi:438-456,762-778
  *   igx_assemble                       <- assemble_entries(asm, symmetric=True)
  *                                         pyiga/assemble.py:703-754 (multi_entries + COO->CSR + mirror)
+ *   igx_multipatch_*                   <- Multipatch.assemble_system: A += X_p @ A_p @ X_p.T, b += X_p @ b_p
+ *                                         pyiga/assemble.py:1340-1370 (global pattern and sums on the device)
  */
 #ifndef IGX_H
 #define IGX_H
@@ -51,6 +53,7 @@ extern "C" {
 
 typedef struct igx_ctx igx_ctx;       /* one per GPU: device id + HIP stream */
 typedef struct igx_patch igx_patch;   /* device-resident state of one assembler */
+typedef struct igx_multipatch igx_multipatch;   /* global CSR of several patches glued at their interfaces */
 
 enum { IGX_MASS = 0, IGX_STIFFNESS = 1,
        /* (inner(c*grad(u),grad(v)) + inner((x[1],-x[0],1.0),grad(u))*v)*dx -- the custom (vform) case of
@@ -352,6 +355,45 @@ int igx_patch_placement(const igx_patch *patch, int *tried, float *best_ms, floa
    (c0max * S_mid * S_last values) and one slice of the sweep intermediate (G_mid * G_last values) below 2^31 bytes.
    (No counterpart in the reference: its index type is size_t throughout, pyiga/assemble_tools_cy.pyx:44-49.) */
 int igx_fused_stage_fits(int64_t c0max, int64_t S_mid, int64_t S_last, int64_t G_mid, int64_t G_last);
+
+/* --- multipatch: sum_p X_p A_p X_p^T on the device (pyiga/assemble.py:1103-1389) -------------------------------------------
+   X_p is the 0/1 matrix of the local-to-global map l2g[p] (Multipatch.patch_to_global_idx, pyiga/assemble.py:1276-1293).  The
+   handle does NOT own the patches: they are read by the calls that take them and may be destroyed afterwards. */
+typedef struct {
+    int32_t npatches;
+    int32_t injective;         /* 1 if every map l2g[p] is injective (else the sums are formed with atomics: correct to rounding) */
+    int64_t nrows;             /* global dofs */
+    int64_t nnz;               /* entries of the global pattern */
+    int64_t entries[4];        /* local entries over all patches by scatter class: direct store, store through a position,
+                                  read-add-write, atomic add */
+    int64_t zero_from;         /* igx_multipatch_zero clears the values from this position on */
+} igx_multipatch_info;
+
+/* Builds the canonical CSR pattern (sorted, unique int32 columns per row) of sum_p X_p S_p X_p^T from the device pattern S_p
+   of every patch (igx_pattern; built here if missing) and l2g[p] (host, nrows_total of patch p entries in [0, nglobal)),
+   entirely on the device, and the scatter plan of every patch.  Entries whose values sum to 0 stay in the pattern (scipy
+   would drop them).  Whole patches only (no row slab, no span box).  A global nnz of 2^31 or more: IGX_ERR_UNSUPPORTED
+   (igx_last_error).  NULL on failure.  <- Multipatch.finalize + the pattern of A += X @ A_p @ X.T (pyiga/assemble.py:1264-1270,
+   1340-1370) */
+igx_multipatch *igx_multipatch_create(igx_ctx *ctx, int npatches, igx_patch *const *patches, const int32_t *const *l2g, int64_t nglobal);
+void igx_multipatch_destroy(igx_multipatch *mp);
+int  igx_multipatch_get_info(const igx_multipatch *mp, igx_multipatch_info *info);
+/* Global pattern to host: indptr has nrows + 1 entries, indices nnz.  Either may be NULL.  <- (A.indptr, A.indices) */
+int  igx_multipatch_pattern(const igx_multipatch *mp, int32_t *indptr, int32_t *indices);
+/* Start a new sum: A = 0, b = 0 (the reference's  A = csr_matrix((n, n)); b = zeros(n)).  Rows that one local row reaches are
+   overwritten by its scatter; only the rows of interface dofs are cleared. */
+int  igx_multipatch_zero(igx_multipatch *mp);
+/* A += X_p A_p X_p^T with the values A_p that `src` holds on the device after igx_assemble(src, ..., data_out = NULL) -- nothing
+   goes through the host.  `src` must have patch p's shape and nnz (IGX_ERR_ARG otherwise).  One pass on the context's stream,
+   read-add-write in the rows of interface dofs: calls in patch order sum as ((0 + a_0) + a_1) + ..., bit for bit the
+   reference's order.  Returns when the pass is done (`src` may then be destroyed).  <- A += X @ A_p @ X.T */
+int  igx_multipatch_scatter_patch(igx_multipatch *mp, int p, const igx_patch *src);
+/* The same with the nnz values of patch p in its canonical CSR order given on the host. */
+int  igx_multipatch_scatter_host(igx_multipatch *mp, int p, const double *vals);
+/* b += X_p b_p, b_p host (nrows_total of patch p values).  <- b += X @ b_p */
+int  igx_multipatch_scatter_vector(igx_multipatch *mp, int p, const double *b);
+/* Global values (nnz, in the order of igx_multipatch_pattern) and vector (nrows) to host.  Either may be NULL. */
+int  igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec);
 
 #ifdef __cplusplus
 }

@@ -37,3 +37,5 @@ from . import assemblers      # noqa: F401
 from . import assemble        # noqa: F401
 from . import utils           # noqa: F401
 from . import distributed     # noqa: F401
+from . import approx          # noqa: F401
+from . import multipatch      # noqa: F401

@@ -43,6 +43,13 @@ class PatchInfo(C.Structure):
     ]
 
 
+class MultipatchInfo(C.Structure):
+    _fields_ = [
+        ('npatches', C.c_int32), ('injective', C.c_int32), ('nrows', C.c_int64), ('nnz', C.c_int64),
+        ('entries', C.c_int64 * 4), ('zero_from', C.c_int64),
+    ]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ('total_ms', C.c_float), ('fields_ms', C.c_float), ('stage0_ms', C.c_float),
@@ -109,6 +116,15 @@ SYMBOLS = [
     ('igx_dev_free', None, [C.c_void_p, C.c_void_p]),
     ('igx_dev_upload', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     ('igx_dev_download', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    ('igx_multipatch_create', C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_int32)), C.c_int64]),
+    ('igx_multipatch_destroy', None, [C.c_void_p]),
+    ('igx_multipatch_get_info', C.c_int, [C.c_void_p, C.POINTER(MultipatchInfo)]),
+    ('igx_multipatch_pattern', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ('igx_multipatch_zero', C.c_int, [C.c_void_p]),
+    ('igx_multipatch_scatter_patch', C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ('igx_multipatch_scatter_host', C.c_int, [C.c_void_p, C.c_int, _dp]),
+    ('igx_multipatch_scatter_vector', C.c_int, [C.c_void_p, C.c_int, _dp]),
+    ('igx_multipatch_download', C.c_int, [C.c_void_p, _dp, _dp]),
 ]
 
 _lib = None

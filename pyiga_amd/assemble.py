@@ -21,6 +21,8 @@ from . import bspline
 from . import assemblers
 from . import _lib
 from .quadrature import make_iterated_quadrature
+from .multipatch import (slice_indices, boundary_dofs, combine_bcs, compute_dirichlet_bc, compute_dirichlet_bcs,  # noqa: F401
+                         detect_interfaces, Multipatch)
 
 ################################################################################
 # 1D matrices (pyiga/assemble.py:125-190): per-span dense blocks f1 @ (f2*w)^T

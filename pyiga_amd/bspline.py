@@ -91,6 +91,15 @@ class KnotVector:
         return self.first_active(self.findspan(u))
 
     # ---- value semantics
+    def greville(self):
+        """Greville abscissae: averages of p consecutive interior knots, clamped to the support (pyiga/bspline.py:164-174);
+        cell midpoints for p = 0."""
+        kv, p = self.kv, self.p
+        if p == 0:
+            return (kv[1:] + kv[:-1]) / 2
+        g = np.convolve(kv, np.ones(p) / p)[p:-p]
+        return np.clip(g, kv[0], kv[-1])
+
     def copy(self):
         return KnotVector(self.kv.copy(), self.p)
 
@@ -297,6 +306,18 @@ class _BaseSplineFunc:
     def support(self):
         return tuple(kv.support() for kv in self.kvs)
 
+    def bounding_box(self, grid=1):
+        """(lower, upper) per component (x first) of the image of the grid with `grid` + 1 points per axis -- the corners by
+        default (pyiga/bspline.py:752-765)."""
+        X = np.asarray(self.grid_eval([np.linspace(a, b, grid + 1) for a, b in self.support])).reshape(-1, self.dim)
+        return tuple((X[:, d].min(), X[:, d].max()) for d in range(self.dim))
+
+    def rotate_2d(self, angle):
+        """The map rotated by `angle` about the origin (``dim == 2``)."""
+        assert self.dim == 2, 'Must be 2D vector function'
+        c, s = np.cos(angle), np.sin(angle)
+        return self.apply_matrix(np.array([[c, -s], [s, c]]))
+
 
 class BSplineFunc(_BaseSplineFunc):
     """Function given by tensor-product B-spline coefficients (pyiga/bspline.py:820-921).
@@ -366,6 +387,19 @@ class BSplineFunc(_BaseSplineFunc):
         axis, side = parse_bdspec(bdspec, self.sdim)
         layer = np.take(self.coeffs, 0 if side == 0 else -1, axis=axis)
         return BSplineFunc(self.kvs[:axis] + self.kvs[axis + 1:], layer)
+
+    def translate(self, offset):
+        """The function with `offset` added to every control point."""
+        return BSplineFunc(self.kvs, self.coeffs + offset)
+
+    def scale(self, factor):
+        """Every control point scaled by a scalar or componentwise by a vector."""
+        return BSplineFunc(self.kvs, self.coeffs * factor)
+
+    def apply_matrix(self, A):
+        """`A` (one matrix, or one per control point; numpy broadcasting) applied to every control point."""
+        assert self.is_vector(), 'Can only apply matrices to vector-valued functions'
+        return BSplineFunc(self.kvs, np.matmul(A, self.coeffs[..., None])[..., 0])
 
     def as_nurbs(self):
         from .geometry import NurbsFunc

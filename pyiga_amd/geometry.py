@@ -105,6 +105,23 @@ class NurbsFunc(_BaseSplineFunc):
         layer = np.take(self.coeffs, 0 if side == 0 else -1, axis=axis)
         return NurbsFunc(self.kvs[:axis] + self.kvs[axis + 1:], layer.copy(), None, premultiplied=True)
 
+    # rigid and linear maps of the control points; the weights stay as they are
+    def translate(self, offset):
+        """The function with `offset` added to every (de-homogenised) control point."""
+        C, W = self.coeffs_weights()
+        return NurbsFunc(self.kvs, C + offset, W)
+
+    def scale(self, factor):
+        """Every control point scaled by a scalar or componentwise by a vector."""
+        C, W = self.coeffs_weights()
+        return NurbsFunc(self.kvs, C * factor, W)
+
+    def apply_matrix(self, A):
+        """`A` (one matrix, or one per control point; numpy broadcasting) applied to every control point."""
+        assert self.is_vector(), 'Can only apply matrices to vector-valued functions'
+        C, W = self.coeffs_weights()
+        return NurbsFunc(self.kvs, np.matmul(A, C[..., None])[..., 0], W)
+
     def as_nurbs(self):
         return self
 
@@ -218,6 +235,13 @@ def line_segment(x0, x1, support=(0.0, 1.0), intervals=1):
     S = np.linspace(0.0, 1.0, intervals + 1).reshape((intervals + 1, 1))
     coeffs = (1 - S) * x0 + S * x1
     return BSplineFunc(bspline.make_knots(1, support[0], support[1], intervals), coeffs)
+
+
+def identity(extents):
+    """Identity map of the box given by (min, max) pairs or ``KnotVector`` s (their supports), one per axis, as linear
+    splines over those supports (pyiga/geometry.py:542-555)."""
+    extents = [ex.support() if isinstance(ex, bspline.KnotVector) else ex for ex in extents]
+    return functools.reduce(tensor_product, (line_segment(ex[0], ex[1], support=ex) for ex in extents))
 
 
 def _split_control_net(G):
