@@ -35,6 +35,9 @@
  *                                         pyiga/assemble.py:703-754 (multi_entries + COO->CSR + mirror)
  *   igx_multipatch_*                   <- Multipatch.assemble_system: A += X_p @ A_p @ X_p.T, b += X_p @ b_p
  *                                         pyiga/assemble.py:1340-1370 (global pattern and sums on the device)
+ *   igx_solver_* / igx_kron_apply_d    <- RestrictedLinearSystem + make_solver / cg, fastdiag_solver, KroneckerOperator
+ *                                         pyiga/assemble.py:571-652, pyiga/solvers.py:17-42, pyiga/operators.py:60-86,
+ *                                         pyiga/approx.py:62-96 (one patch, matrix values never leave the device)
  */
 #ifndef IGX_H
 #define IGX_H
@@ -394,6 +397,67 @@ int  igx_multipatch_scatter_host(igx_multipatch *mp, int p, const double *vals);
 int  igx_multipatch_scatter_vector(igx_multipatch *mp, int p, const double *b);
 /* Global values (nnz, in the order of igx_multipatch_pattern) and vector (nrows) to host.  Either may be NULL. */
 int  igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec);
+
+/* --- Dirichlet problems of one patch on the device: preconditioned CG (pyiga/assemble.py:571-652, pyiga/solvers.py:17-42) ----
+   The solver reads the CSR values that the patch holds on the device after an assembly with data_out = NULL, in the patch's own
+   structured layout (no index arrays).  Dirichlet dofs are handled with a dof mask: every vector is full-length with zeros at the
+   fixed dofs, and the restricted matrix R A R^T never exists.  The handle does NOT own the patch: the patch must outlive it. */
+typedef struct igx_solver igx_solver;
+enum { IGX_PRECOND_NONE = 0, IGX_PRECOND_JACOBI = 1, IGX_PRECOND_KRON = 2 };
+/* how the per-axis eigenvalues lam_k form the diagonal D of a Kronecker preconditioner  (x)U_k . D^-1 . (x)U_k^T */
+enum { IGX_KRON_SUM = 1,       /* D = sum_k 1 (x) .. (x) lam_k (x) .. (x) 1: fast diagonalization of sum_k K_k (x) M_rest (Sangalli-Tani) */
+       IGX_KRON_PRODUCT = 2 }; /* D = (x)_k lam_k: with U_k, lam_k the eigenpairs of M_k this is (x) M_k^-1 */
+
+typedef struct {
+    int32_t iterations;        /* CG iterations done */
+    int32_t converged;         /* 1 if ||r|| <= tol * ||R (b - A ext(g))|| was reached */
+    double relres;             /* final ||r|| / ||R (b - A ext(g))|| */
+    int64_t n_free;            /* free dofs */
+    float spmv_ms, precond_ms, vector_ms;   /* device time summed over the iterations (solve with timed != 0, else 0) */
+    float total_ms;            /* device time of the whole solve, transfers included */
+} igx_solve_info;
+
+/* A solver for the matrix of `kind` (IGX_MASS or IGX_STIFFNESS only -- CG needs a symmetric positive definite matrix; any other
+   kind: IGX_ERR_UNSUPPORTED) that the patch holds on the device now (else IGX_ERR_ARG).  fixed[0..nfixed): the eliminated dofs
+   (ravelled indices; the order of the values given to the solve).  Whole patches only: a row slab or a span box is
+   IGX_ERR_UNSUPPORTED.  *out receives the handle (NULL on failure). */
+int  igx_solver_create(igx_patch *patch, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out);
+void igx_solver_destroy(igx_solver *solver);
+/* Preconditioner of the following solves.  IGX_PRECOND_NONE; IGX_PRECOND_JACOBI: the diagonal, gathered from the device values;
+   IGX_PRECOND_KRON: (x)U_k . D^-1 . (x)U_k^T on the free box box_lo[k] <= i_k < box_hi[k], which must be exactly the free dofs.
+   U[k] (host, n_k x n_k row-major, n_k = box_hi[k] - box_lo[k]) and lam[k] (host, n_k) per axis, lam_mode IGX_KRON_*.  The
+   other arguments may be NULL for NONE and JACOBI. */
+int igx_solver_set_precond(igx_solver *solver, int precond, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                           const double *const *lam, int lam_mode);
+/* d_y = R A R^T d_x on the device (full-length vectors; the fixed entries of d_x are ignored, those of d_y are 0). */
+int igx_solver_spmv_d(igx_solver *solver, const double *d_x, double *d_y);
+/* Solves  R A R^T x = R (b - A ext(g))  by CG and returns the full vector u = x + ext(g) (host, nrows_total).  b: host load
+   vector (nrows_total); g: host values of the fixed dofs (in the order of `fixed`); x0: host initial guess (nrows_total, only
+   its free entries are used) or NULL.  Stops when ||r|| <= tol * ||R (b - A ext(g))|| or after maxiter iterations; the residual
+   norm is read back every check_every iterations (alpha and beta stay on the device).  timed != 0: events between the phases
+   of every iteration (info->spmv_ms etc.).  The solve is deterministic: the same inputs give bit-identical u.  Refused
+   (IGX_ERR_ARG) if the patch's values have been overwritten by an assembly of another kind since the solver was made. */
+int igx_solver_solve(igx_solver *solver, const double *b, const double *g, const double *x0, double tol, int maxiter,
+                     int check_every, int timed, double *u, igx_solve_info *info);
+
+/* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers.  The factors are dense, row-major, m[k] x n[k]
+   (rectangular allowed).  x and y are tensors of shape (n_0, .., n_{dim-1}, batch) and (m_0, .., batch), addressed through an
+   element offset and four strides (axis 3 = the trailing batch axis), so a sub-box of a longer vector can be read or written.
+   D: lam_mode 0 none, IGX_KRON_SUM / IGX_KRON_PRODUCT of d_lam[k] (m[k] each) at the output index.  d_work: 2 * W doubles with
+   W = max over k < dim - 1 of batch * m_0 .. m_k * n_{k+1} .. n_{dim-1}, or NULL (allocated for the call).  x and y must not
+   overlap.  Returns when the result is in y. */
+typedef struct {
+    int32_t dim;                       /* 1..3 factors */
+    int32_t m[3], n[3];
+    const double *d_B[3];
+    int64_t batch;                     /* >= 1 */
+    int64_t x_off, x_stride[4];        /* x(i_0, .., t) = d_x[x_off + sum_k i_k x_stride[k] + t x_stride[3]] */
+    int64_t y_off, y_stride[4];
+    int32_t lam_mode;
+    int32_t reserved;
+    const double *d_lam[3];
+} igx_kron_desc;
+int igx_kron_apply_d(igx_ctx *ctx, const igx_kron_desc *desc, const double *d_x, double *d_y, double *d_work, int64_t work_len);
 
 #ifdef __cplusplus
 }

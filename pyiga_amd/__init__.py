@@ -39,3 +39,5 @@ from . import utils           # noqa: F401
 from . import distributed     # noqa: F401
 from . import approx          # noqa: F401
 from . import multipatch      # noqa: F401
+from . import operators       # noqa: F401
+from . import solvers         # noqa: F401

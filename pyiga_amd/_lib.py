@@ -61,6 +61,29 @@ class Timing(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+IGX_PRECOND_NONE, IGX_PRECOND_JACOBI, IGX_PRECOND_KRON = 0, 1, 2
+IGX_KRON_SUM, IGX_KRON_PRODUCT = 1, 2
+PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'kron': IGX_PRECOND_KRON}
+
+
+class SolveInfo(C.Structure):
+    _fields_ = [
+        ('iterations', C.c_int32), ('converged', C.c_int32), ('relres', C.c_double), ('n_free', C.c_int64),
+        ('spmv_ms', C.c_float), ('precond_ms', C.c_float), ('vector_ms', C.c_float), ('total_ms', C.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class KronDesc(C.Structure):
+    _fields_ = [
+        ('dim', C.c_int32), ('m', C.c_int32 * 3), ('n', C.c_int32 * 3), ('d_B', C.c_void_p * 3),
+        ('batch', C.c_int64), ('x_off', C.c_int64), ('x_stride', C.c_int64 * 4), ('y_off', C.c_int64), ('y_stride', C.c_int64 * 4),
+        ('lam_mode', C.c_int32), ('reserved', C.c_int32), ('d_lam', C.c_void_p * 3),
+    ]
+
+
 # every symbol include/igx.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ('igx_version', C.c_int, []),
@@ -125,6 +148,12 @@ SYMBOLS = [
     ('igx_multipatch_scatter_host', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_multipatch_scatter_vector', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_multipatch_download', C.c_int, [C.c_void_p, _dp, _dp]),
+    ('igx_solver_create', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_destroy', None, [C.c_void_p]),
+    ('igx_solver_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
+    ('igx_solver_spmv_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('igx_solver_solve', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(SolveInfo)]),
+    ('igx_kron_apply_d', C.c_int, [C.c_void_p, C.POINTER(KronDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
 ]
 
 _lib = None

@@ -35,3 +35,41 @@ def interpolate(kvs, f, geo=None, nodes=None):
         shape = Y.shape
         X = np.moveaxis(lu.solve(np.ascontiguousarray(Y.reshape(shape[0], -1))).reshape(shape), 0, ax)
     return X
+
+
+def project_L2(kvs, f, f_physical=False, geo=None):
+    """Coefficients of the L2 projection of `f` into the tensor-product B-spline basis `kvs` (pyiga/approx.py:62-96).
+
+    `f` is given in the parameter domain, or in physical coordinates with ``f_physical=True`` (needs `geo`).  Without `geo` the
+    load vector is multiplied by ``(x) M_k^-1`` with the device Kronecker apply (trailing value axes of a vector-valued `f`
+    allowed).  With `geo` the mass matrix is assembled and solved on the device by CG with the Kronecker product of the 1D
+    inverse mass matrices as preconditioner (relative tolerance 1e-12, at most 100 iterations, as the reference).
+    Hierarchical spaces are not supported.
+    """
+    import sys
+    import scipy.linalg
+    from . import _lib, assemble
+    from .solvers import KronDiagOperator, PatchSystem
+    if isinstance(kvs, bspline.KnotVector):
+        kvs = (kvs,)
+    if not isinstance(kvs, (tuple, list)):
+        raise NotImplementedError('project_L2: only tensor-product spaces (a sequence of KnotVector)')
+    kvs = tuple(kvs)
+    rhs = assemble.inner_products(kvs, f, f_physical=f_physical, geo=geo)
+    if geo is None:
+        assert not f_physical, 'Cannot use physical coordinates without geometry'
+        EV = [scipy.linalg.eigh(assemble.bsp_mass_1d(kv).toarray()) for kv in kvs]
+        op = KronDiagOperator([U for _, U in EV], [lam for lam, _ in EV], _lib.IGX_KRON_PRODUCT)
+        n = int(np.prod([kv.numdofs for kv in kvs]))
+        return op.matmat(np.reshape(rhs, (n, -1))).reshape(rhs.shape)
+    b = np.ravel(rhs)
+    n = int(np.prod([kv.numdofs for kv in kvs]))
+    assert b.shape[0] == n, 'L2 projection with geometry only implemented for scalar functions'
+    S = PatchSystem(kvs, geo, b, None, kind='mass')
+    try:
+        x = S.solve(tol=1e-12, maxiter=100, precond='kron')
+        if not S.info['converged']:
+            print('WARNING: L2 projection - CG did not converge:', S.info['iterations'], file=sys.stderr)
+    finally:
+        S.close()
+    return x.reshape(rhs.shape)

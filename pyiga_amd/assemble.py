@@ -543,3 +543,70 @@ def mass_fast(kvs, geo=None, tol=1e-10, maxiter=100, skipcount=3, tolcount=3, ve
 def stiffness_fast(kvs, geo=None, tol=1e-10, maxiter=100, skipcount=3, tolcount=3, verbose=2):
     """See :func:`mass_fast` (pyiga/assemble.py:1083-1101)."""
     return _fast('stiffness', kvs, geo, tol, maxiter, skipcount, tolcount, verbose)
+
+
+################################################################################
+# Eliminating dofs from a linear system (pyiga/assemble.py:571-652)
+################################################################################
+
+def _selection(n, rows):
+    """The 0/1 matrix that picks the entries `rows` (in this order) of a vector of length n."""
+    rows = np.asarray(rows, dtype=np.int64)
+    return scipy.sparse.csr_matrix((np.ones(rows.size), (np.arange(rows.size), rows)), shape=(rows.size, n))
+
+
+class RestrictedLinearSystem:
+    """A linear system with some of its dofs eliminated -- the host class of the reference, on scipy matrices.
+
+    `A`: the full matrix; `b`: the right-hand side (a scalar is broadcast); `bcs`: ``(indices, values)`` of the dofs to
+    eliminate (a scalar value is broadcast).  `elim_rows`: the equations to drop when they differ from the eliminated dofs
+    (Petrov-Galerkin).  The values are assigned to the eliminated dofs in increasing index order, as the reference does.
+
+    Attributes ``A`` (restricted matrix) and ``b`` (restricted right-hand side, with the eliminated dofs moved over).
+    For the device-resident solve of one patch see :class:`pyiga_amd.solvers.PatchSystem`.
+    """
+
+    def __init__(self, A, b, bcs, elim_rows=None):
+        indices, values = bcs
+        nrow, ncol = A.shape
+        if np.isscalar(b):
+            b = np.broadcast_to(b, nrow)
+        indices = np.asarray(indices)
+        if np.isscalar(values):
+            values = np.broadcast_to(values, indices.shape[0])
+        self.values = values
+        elim = np.zeros(ncol, dtype=bool)
+        elim[np.asarray(indices, dtype=np.int64)] = True
+        self.R_free = _selection(ncol, np.flatnonzero(~elim))
+        self.R_elim = _selection(ncol, np.flatnonzero(elim))
+        if elim_rows is None:
+            self.R_free_v, self.R_elim_v = self.R_free, self.R_elim
+        else:
+            drop = np.zeros(nrow, dtype=bool)
+            drop[np.asarray(elim_rows, dtype=np.int64)] = True
+            self.R_free_v = _selection(nrow, np.flatnonzero(~drop))
+            self.R_elim_v = _selection(nrow, np.flatnonzero(drop))
+        self.A = self.restrict_matrix(A)
+        self.b = self.restrict_rhs(b - A.dot(self.R_elim.T.dot(values)))
+
+    def restrict(self, u):
+        """The free dofs of a vector `u` of all dofs."""
+        return self.R_free.dot(u)
+
+    def restrict_rhs(self, f):
+        """The non-eliminated rows of a right-hand side `f` (equal to :meth:`restrict` without `elim_rows`)."""
+        return self.R_free_v.dot(f)
+
+    def restrict_matrix(self, B):
+        """The restriction of a matrix `B` on all dofs to the free dofs (rows: the non-eliminated equations)."""
+        if not scipy.sparse.issparse(B):
+            B = scipy.sparse.csr_matrix(B)
+        return self.R_free_v.dot(B).dot(self.R_free.T)
+
+    def extend(self, u):
+        """A vector of the free dofs padded with zeros to all dofs."""
+        return self.R_free.T.dot(u)
+
+    def complete(self, u):
+        """A solution `u` of the restricted system completed with the values of the eliminated dofs."""
+        return self.extend(u) + self.R_elim.T.dot(self.values)

@@ -981,6 +981,7 @@ int igx_assemble(igx_patch *pt, int kind, int algo, double *data_out)
             }
         }
     }
+    pt->values_kind = -1;                           // (set again when the values are complete)
     if (pt->knobs.poison)                         // every value must be written exactly once
         IGX_HIP(hipMemsetAsync(pt->d_data, 0xFF, (size_t)pt->nnz * sizeof(double), st));
     memset(&pt->timing, 0, sizeof(pt->timing));
@@ -1022,6 +1023,7 @@ int igx_assemble(igx_patch *pt, int kind, int algo, double *data_out)
         if (e != hipSuccess) { set_error("igx_assemble: kernel failure: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
     }
     (void)hipEventElapsedTime(&pt->timing.total_ms, ev[0], ev[5]);
+    pt->values_kind = kind;
     if (one_launch) pt->timing.stage1_ms = pt->timing.total_ms;
     if (!staged) {                              // only the whole interval was timed
     } else if (algo == IGX_ALGO_SUMFACT) {
@@ -1067,6 +1069,7 @@ int igx_assemble_kron3(igx_patch *p3, igx_patch *p2, int kind, const double *m0,
         const size_t bytes = ((size_t)std::max(p3->nnz, p3->nnz_ext) + IGX_DUMP_PAD) * sizeof(double);
         if (hipMalloc((void **)&p3->d_data, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("hipMalloc of %.2f GB for CSR values failed", p3->nnz * 8.0 / 1e9); return IGX_ERR_NOMEM; }
     }
+    p3->values_kind = -1;
     if (p3->knobs.poison) IGX_HIP(hipMemsetAsync(p3->d_data, 0xFF, (size_t)p3->nnz * sizeof(double), st));
     // 2D matrices of the cross-section: the regular 2D path (mass first: its values move aside, the stiffness values stay in
     // the patch's own buffer)
@@ -1104,6 +1107,7 @@ int igx_assemble_kron3(igx_patch *p3, igx_patch *p2, int kind, const double *m0,
     p3->timing.final_ms = p3->timing.total_ms;
     p3->timing.n_launches = 1;
     p3->last_path = IGX_PATH_KRON;
+    p3->values_kind = kind;
     if (data_out) {
         IGX_HIP(hipMemcpyAsync(data_out, p3->d_data, (size_t)p3->nnz * sizeof(double), hipMemcpyDeviceToHost, st));
         IGX_HIP(hipStreamSynchronize(st));

@@ -186,6 +186,8 @@ struct igx_patch {
     double *d_data = nullptr;
     int32_t *d_indices = nullptr, *d_indptr = nullptr;
     bool have_pattern = false;
+    int values_kind = -1;                     // IGX_* kind d_data holds (igx_assemble / igx_assemble_kron3 done), -1: none or overwritten
+                                              // (read by the solver of solve.hip: it refuses values of another kind)
     // sum factorisation workspaces
     bool sumfact_ok = false;
     int *d_pl0 = nullptr;                     // [npairs0][2] processed lower pairs (i0,j0) of axis 0

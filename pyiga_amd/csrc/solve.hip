@@ -1,0 +1,844 @@
+// Dirichlet problems of one patch solved on the device: preconditioned CG on the values igx_assemble left in HBM
+// (igx_solver_*, igx_kron_apply_d; include/igx.h).
+//
+// Replaces the host steps of the reference's workflow  RestrictedLinearSystem -> make_solver / cg  (pyiga/assemble.py:571-652,
+// pyiga/solvers.py:17-42, pyiga/approx.py:62-96) for a single patch.  Three kinds of kernels:
+//   k_spmv     y = R A R^T x  (and  b - A ext(g)): reads the CSR values in the patch's structured layout
+//              -- positions from the per-axis tables rp / jlo / jhi, no indices / indptr: 8 bytes per nonzero.  One group of GW
+//              lanes per row; rows of fixed dofs are not read and come out as 0.
+//   k_kron     one contraction  Y[.., i, ..] = sum_j B[i][j] X[.., j, ..]  of a Kronecker product through LDS tiles (FP64 VALU);
+//              strided input / output, so the fast-diagonalization preconditioner (Sangalli-Tani) works on the free box of a
+//              full-length vector.  The last contraction can divide by the eigenvalue sums / products (D^-1).
+//   vector     fused CG updates and fixed-order two-pass dot products (fixed grid, fixed trees): two solves of the same
+//              system give bit-identical results.  alpha and beta stay in device memory.
+#include "igx_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+using namespace igx;
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int NB_VEC = 1024;             // blocks of the vector kernels (and most partial sums of a dot product)
+constexpr int NB_SPMV_MAX = 8192;        // blocks of the SpMV (grid-stride over rows): what is resident at once, at most this
+enum { SC_PQ = 0, SC_RZ, SC_RR, SC_ALPHA, SC_BETA, SC_N = 8 };
+enum { FIN_ALPHA = 0, FIN_BETA = 1, FIN_INIT = 2 };
+
+// per-axis tables of the value layout; a 2D patch is a 3D one with a one-dof outer axis
+struct Geom {
+    int N[3];
+    const int *jlo[3], *jhi[3], *rp[3];
+    long long S1, S2;
+    long long nrows;
+};
+
+__device__ __forceinline__ double block_sum(double v, double *sh)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    const double s = sh[0];
+    __syncthreads();
+    return s;
+}
+
+// what a row needs from the per-axis tables: loaded one row ahead, while the values of the current row are in flight
+struct RowHdr {
+    int fr, l0, l1, l2, c0, c1, c2, r0, r1, r2;
+};
+
+__device__ __forceinline__ RowHdr row_hdr(const Geom &g, const uint8_t *freem, long long I)
+{
+    RowHdr h;
+    const int i2 = (int)(I % g.N[2]);
+    const long long t = I / g.N[2];
+    const int i1 = (int)(t % g.N[1]), i0 = (int)(t / g.N[1]);
+    h.fr = freem[I];
+    h.l0 = g.jlo[0][i0]; h.l1 = g.jlo[1][i1]; h.l2 = g.jlo[2][i2];
+    h.c0 = g.jhi[0][i0]; h.c1 = g.jhi[1][i1]; h.c2 = g.jhi[2][i2];
+    h.r0 = g.rp[0][i0]; h.r1 = g.rp[1][i1]; h.r2 = g.rp[2][i2];
+    return h;
+}
+
+// y[I] = free[I] ? (b ? b[I] : 0) + s * (A x)[I] : 0 ;  part[block] = sum of pd[I] * y[I] over the rows of the block (optional)
+// (U batches of GW values per lane are loaded before they are summed: enough bytes in flight to stream HBM; the values are read
+// once, non-temporally, so that x stays in the caches)
+template <int GW, int U>
+__global__ void __launch_bounds__(BLOCK) k_spmv(const Geom g, const double *__restrict__ vals, const uint8_t *__restrict__ freem,
+                                                const double *__restrict__ x, const double *b, double s, double *y,
+                                                const double *__restrict__ pd, double *part)
+{
+    __shared__ double sh[BLOCK];
+    const int lane = threadIdx.x % GW;
+    const long long ngroups = (long long)gridDim.x * (BLOCK / GW);
+    const int N1 = g.N[1], N2 = g.N[2];
+    const int N12 = N1 * N2;
+    double dot = 0.0;
+    long long I = (long long)blockIdx.x * (BLOCK / GW) + threadIdx.x / GW;
+    RowHdr h{};
+    if (I < g.nrows) h = row_hdr(g, freem, I);
+    for (; I < g.nrows; I += ngroups) {
+        const RowHdr cur = h;
+        if (I + ngroups < g.nrows) h = row_hdr(g, freem, I + ngroups);
+        if (!cur.fr) {                               // (uniform over the group)
+            if (lane == 0) y[I] = 0.0;
+            continue;
+        }
+        const int c0 = cur.c0 - cur.l0, c1 = cur.c1 - cur.l1, c2 = cur.c2 - cur.l2;
+        const int len = c0 * c1 * c2;
+        const long long row = igx_rowptr3(&cur.r0, &cur.r1, &cur.r2, g.S1, g.S2, c0, c1, 0, 0, 0);
+        const int xbase = (cur.l0 * N1 + cur.l1) * N2 + cur.l2;
+        // lane's entry k = (a c1 + bb) c2 + c, advanced by GW = (da c1 + db) c2 + dc per step
+        int c = lane % c2, bb = (lane / c2) % c1, a = lane / (c1 * c2);
+        const int dc = GW % c2, db = (GW / c2) % c1, da = GW / (c1 * c2);
+        double acc = 0.0;
+        for (int k0 = lane; k0 < len; k0 += U * GW) {
+            double v[U], xv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k0 + u * GW < len;
+                v[u] = in ? __builtin_nontemporal_load(vals + row + k0 + u * GW) : 0.0;
+                xv[u] = in ? x[xbase + a * N12 + bb * N2 + c] : 0.0;
+                c += dc; bb += db; a += da;
+                if (c >= c2) { c -= c2; ++bb; }
+                if (bb >= c1) { bb -= c1; ++a; }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc += v[u] * xv[u];
+        }
+#pragma unroll
+        for (int off = GW / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, GW);
+        if (lane == 0) {
+            const double v = (b ? b[I] : 0.0) + s * acc;
+            y[I] = v;
+            if (pd) dot += pd[I] * v;
+        }
+    }
+    if (part) {
+        const double v = block_sum(dot, sh);
+        if (threadIdx.x == 0) part[blockIdx.x] = v;
+    }
+}
+
+// dinv[I] = free[I] ? 1 / A[I][I] : 0  (the diagonal gathered from the structured layout)
+__global__ void k_diag(const Geom g, const double *__restrict__ vals, const uint8_t *__restrict__ freem, double *dinv)
+{
+    const long long I = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= g.nrows) return;
+    if (!freem[I]) { dinv[I] = 0.0; return; }
+    const int N1 = g.N[1], N2 = g.N[2];
+    const int i2 = (int)(I % N2);
+    const long long t = I / N2;
+    const int i1 = (int)(t % N1), i0 = (int)(t / N1);
+    const int l0 = g.jlo[0][i0], l1 = g.jlo[1][i1], l2 = g.jlo[2][i2];
+    const int c0 = g.jhi[0][i0] - l0, c1 = g.jhi[1][i1] - l1, c2 = g.jhi[2][i2] - l2;
+    const long long row = igx_rowptr3(g.rp[0], g.rp[1], g.rp[2], g.S1, g.S2, c0, c1, i0, i1, i2);
+    dinv[I] = 1.0 / vals[row + ((long long)(i0 - l0) * c1 + (i1 - l1)) * c2 + (i2 - l2)];
+}
+
+__global__ void k_mask_copy(long long n, const uint8_t *freem, const double *x, double *y)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = freem[i] ? x[i] : 0.0;
+}
+
+// partA[block] = sum a1 b1, partB[block] = sum a2 b2 (a2 may be null)
+__global__ void __launch_bounds__(BLOCK) k_dot2(long long n, const double *a1, const double *b1, const double *a2, const double *b2,
+                                                double *partA, double *partB)
+{
+    __shared__ double sh[BLOCK];
+    double s1 = 0.0, s2 = 0.0;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
+        s1 += a1[i] * b1[i];
+        if (a2) s2 += a2[i] * b2[i];
+    }
+    s1 = block_sum(s1, sh);
+    if (threadIdx.x == 0) partA[blockIdx.x] = s1;
+    if (a2) {
+        s2 = block_sum(s2, sh);
+        if (threadIdx.x == 0) partB[blockIdx.x] = s2;
+    }
+}
+
+// one block: sums of the partials in a fixed order, then the CG scalars
+__global__ void __launch_bounds__(BLOCK) k_fin(const double *partA, const double *partB, int nb, double *sc, int op)
+{
+    __shared__ double sh[BLOCK];
+    double a = 0.0, bsum = 0.0;
+    for (int k = threadIdx.x; k < nb; k += BLOCK) {
+        a += partA[k];
+        if (partB) bsum += partB[k];
+    }
+    a = block_sum(a, sh);
+    if (partB) bsum = block_sum(bsum, sh);
+    if (threadIdx.x != 0) return;
+    if (op == FIN_ALPHA) {                            // a = p.q
+        sc[SC_PQ] = a;
+        sc[SC_ALPHA] = a != 0.0 ? sc[SC_RZ] / a : 0.0;
+    } else {                                          // a = r.r, bsum = r.z (no preconditioner: z = r)
+        const double rz = partB ? bsum : a;
+        sc[SC_RR] = a;
+        sc[SC_BETA] = (op == FIN_BETA && sc[SC_RZ] != 0.0) ? rz / sc[SC_RZ] : 0.0;
+        sc[SC_RZ] = rz;
+    }
+}
+
+// x += alpha p; r -= alpha q; (Jacobi: z = dinv r); partials of r.r and r.z
+__global__ void __launch_bounds__(BLOCK) k_update(long long n, double *x, double *r, const double *p, const double *q,
+                                                  const double *dinv, double *z, const double *sc, double *partA, double *partB)
+{
+    __shared__ double sh[BLOCK];
+    const double alpha = sc[SC_ALPHA];
+    double rr = 0.0, rz = 0.0;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
+        x[i] += alpha * p[i];
+        const double ri = r[i] - alpha * q[i];
+        r[i] = ri;
+        rr += ri * ri;
+        if (dinv) {
+            const double zi = dinv[i] * ri;
+            z[i] = zi;
+            rz += ri * zi;
+        }
+    }
+    rr = block_sum(rr, sh);
+    if (threadIdx.x == 0) partA[blockIdx.x] = rr;
+    if (dinv) {
+        rz = block_sum(rz, sh);
+        if (threadIdx.x == 0) partB[blockIdx.x] = rz;
+    }
+}
+
+__global__ void k_pupdate(long long n, const double *z, double *p, const double *sc)
+{
+    const double beta = sc[SC_BETA];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        p[i] = z[i] + beta * p[i];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Kronecker contraction of tensor dim kd (of 4: three spatial axes + a trailing batch axis):
+//     Y[..., i, ...] = (sum_j B[i][j] X[..., j, ...]) [ / D(i0, i1, i2) ]
+// A GEMM of B (m x n) with the matrix X whose columns are the other three tensor indices (C order).  Tile 64 x 64 of (i, column),
+// TK values of j per LDS step (the next step's tile is loaded into registers meanwhile), 4 x 4 results per thread.
+constexpr int TM = 64, TN = 64, TK = 32, LPT = TK * TN / 256;     // LPT: values of each tile every thread loads
+
+struct KStep {
+    const double *B;
+    int m, n, kd;
+    int ext[4];                          // extents of the other dims (ext[kd] unused)
+    long long sx[4], sy[4], xoff, yoff;
+    long long ncol;
+    int lam_mode;                        // 0: none, 1: divide by sum_k lam[k][i_k], 2: by the product
+    const double *lam[3];
+};
+
+__device__ __forceinline__ void col_index(const KStep &S, long long col, int idx[4])
+{
+#pragma unroll
+    for (int d = 3; d >= 0; --d) {
+        if (d == S.kd) { idx[d] = 0; continue; }
+        idx[d] = (int)(col % S.ext[d]);
+        col /= S.ext[d];
+    }
+}
+
+template <bool JFAST>
+__global__ void __launch_bounds__(256) k_kron(const KStep S, const double *__restrict__ X, double *__restrict__ Y)
+{
+    __shared__ double Bs[TK][TM + 1];
+    __shared__ double Xs[TK][TN + 1];
+    const int t = threadIdx.x, tx = t % 16, ty = t / 16;
+    const long long c0 = (long long)blockIdx.x * TN;
+    const int i0 = blockIdx.y * TM;
+    const long long sxk = S.sx[S.kd];
+    // tile element l of this thread: B (kb, ib) and X (kx, cx).  JFAST (unit stride along j): LPT columns, one j each; else one
+    // column, LPT values of j
+    long long loff[LPT];
+    bool lok[LPT];
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) {
+        const long long col = c0 + (JFAST ? (t / TK + (256 / TK) * l) : (t % TN));
+        int idx[4];
+        lok[l] = col < S.ncol;
+        col_index(S, lok[l] ? col : 0, idx);
+        loff[l] = S.xoff + idx[0] * S.sx[0] + idx[1] * S.sx[1] + idx[2] * S.sx[2] + idx[3] * S.sx[3];
+    }
+    double rb[LPT], rx[LPT];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) {
+            const int i = i0 + t / TK + (256 / TK) * l, j = k0 + t % TK;
+            rb[l] = (i < S.m && j < S.n) ? S.B[(long long)i * S.n + j] : 0.0;
+            const int jx = k0 + (JFAST ? t % TK : t / TN + (256 / TN) * l);
+            rx[l] = (lok[l] && jx < S.n) ? X[loff[l] + jx * sxk] : 0.0;
+        }
+    };
+    double acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
+    load(0);
+    for (int k0 = 0; k0 < S.n; k0 += TK) {
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) {
+            Bs[t % TK][t / TK + (256 / TK) * l] = rb[l];
+            if (JFAST) Xs[t % TK][t / TK + (256 / TK) * l] = rx[l];
+            else Xs[t / TN + (256 / TN) * l][t % TN] = rx[l];
+        }
+        __syncthreads();
+        if (k0 + TK < S.n) load(k0 + TK);             // the next tile is in flight while this one is used
+#pragma unroll 8
+        for (int k = 0; k < TK; ++k) {
+            double a[4], bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = Bs[k][ty + 16 * r];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) bv[c] = Xs[k][tx + 16 * c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[r][c] = fma(a[r], bv[c], acc[r][c]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const long long col = c0 + tx + 16 * c;
+        if (col >= S.ncol) continue;
+        int idx[4];
+        col_index(S, col, idx);
+        const long long yo = S.yoff + idx[0] * S.sy[0] + idx[1] * S.sy[1] + idx[2] * S.sy[2] + idx[3] * S.sy[3];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + ty + 16 * r;
+            if (i >= S.m) continue;
+            double v = acc[r][c];
+            if (S.lam_mode) {
+                double d = S.lam_mode == 1 ? 0.0 : 1.0;
+                for (int e = 0; e < 3; ++e) {
+                    if (!S.lam[e]) continue;
+                    const double l = S.lam[e][e == S.kd ? i : idx[e]];
+                    d = S.lam_mode == 1 ? d + l : d * l;
+                }
+                v /= d;
+            }
+            Y[yo + (long long)i * S.sy[S.kd]] = v;
+        }
+    }
+}
+
+// the contractions of a whole Kronecker product: x (strided) -> work -> ... -> y (strided)
+struct KronPlan {
+    int dim;
+    int m[3], n[3];
+    const double *B[3];
+    long long batch;
+    long long x_off, x_stride[4], y_off, y_stride[4];
+    int lam_mode;
+    const double *lam[3];
+};
+
+long long kron_work_len(const KronPlan &P)         // doubles of ONE of the two work buffers
+{
+    long long mx = 0;
+    for (int k = 0; k + 1 < P.dim; ++k) {
+        long long s = P.batch;
+        for (int e = 0; e < P.dim; ++e) s *= e <= k ? P.m[e] : P.n[e];
+        mx = std::max(mx, s);
+    }
+    return mx;
+}
+
+// work: two buffers of kron_work_len doubles; with dim >= 2 step k writes W[k % 2], so the last step reads W[dim % 2]
+int launch_kron_plan(hipStream_t st, const KronPlan &P, const double *x, double *y, double *const W[2])
+{
+    int cur[4] = {1, 1, 1, (int)P.batch};           // extents of the current tensor
+    for (int e = 0; e < P.dim; ++e) cur[e] = P.n[e];
+    for (int k = 0; k < P.dim; ++k) {
+        KStep S{};
+        S.B = P.B[k]; S.m = P.m[k]; S.n = P.n[k]; S.kd = k;
+        for (int e = 0; e < 4; ++e) S.ext[e] = cur[e];
+        S.ncol = 1;
+        for (int e = 0; e < 4; ++e)
+            if (e != k) S.ncol *= cur[e];
+        const bool first = k == 0, last = k == P.dim - 1;
+        // compact C-order strides of an intermediate (input: extents cur, output: cur with m[k] at k)
+        long long cs_in[4], cs_out[4];
+        {
+            int out[4] = {cur[0], cur[1], cur[2], cur[3]};
+            out[k] = P.m[k];
+            long long a = 1, b = 1;
+            for (int e = 3; e >= 0; --e) { cs_in[e] = a; a *= cur[e]; cs_out[e] = b; b *= out[e]; }
+        }
+        const double *src = first ? x : W[(k - 1) % 2];
+        double *dst = last ? y : W[k % 2];
+        for (int e = 0; e < 4; ++e) {
+            S.sx[e] = first ? P.x_stride[e] : cs_in[e];
+            S.sy[e] = last ? P.y_stride[e] : cs_out[e];
+        }
+        S.xoff = first ? P.x_off : 0;
+        S.yoff = last ? P.y_off : 0;
+        S.lam_mode = last ? P.lam_mode : 0;
+        for (int e = 0; e < 3; ++e) S.lam[e] = (last && e < P.dim) ? P.lam[e] : nullptr;
+        if (S.ncol > 0 && S.m > 0) {
+            const long long gx = (S.ncol + TN - 1) / TN;
+            if (gx > 0x7fffffffLL) { set_error("Kronecker apply: %lld column tiles", gx); return IGX_ERR_UNSUPPORTED; }
+            dim3 grid((unsigned)gx, (unsigned)((S.m + TM - 1) / TM));
+            if (S.sx[k] == 1) k_kron<true><<<grid, 256, 0, st>>>(S, src, dst);
+            else k_kron<false><<<grid, 256, 0, st>>>(S, src, dst);
+            IGX_HIP(hipGetLastError());
+        }
+        cur[k] = P.m[k];
+    }
+    return IGX_OK;
+}
+
+int spmv_gw(long long maxlen)
+{
+    return maxlen >= 192 ? 64 : maxlen >= 96 ? 32 : maxlen >= 48 ? 16 : maxlen >= 24 ? 8 : 4;
+}
+
+} // namespace
+
+// ---------------------------------------------------------------------------------------------
+struct igx_solver {
+    igx_patch *pt = nullptr;
+    int kind = 0;
+    int dim = 0;
+    int N[3] = {1, 1, 1};                    // dofs per axis of the patch (dim of them)
+    long long n = 0;
+    Geom g{};
+    int gw = 64;
+    int nb_spmv = 1;                          // SpMV blocks resident on the device at once (fixed per solver: fixed summation order)
+    int *d_tab = nullptr;
+    uint8_t *d_mask = nullptr;
+    std::vector<uint8_t> h_free;
+    std::vector<long long> fixed;
+    double *d_vec = nullptr;                  // x | r | p | q | z | b | w | dinv, n each
+    double *x = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *z = nullptr, *b = nullptr, *w = nullptr, *dinv = nullptr;
+    double *d_part = nullptr;                 // 2 x NB_SPMV_MAX partial sums
+    double *d_sc = nullptr;                   // SC_N scalars
+    int precond = IGX_PRECOND_NONE;
+    KronPlan kl{}, kr{};                      // (x) U_k^T with D^-1, then (x) U_k
+    double *d_kron = nullptr;                 // U_k^T | U_k | lam_k
+    double *d_W = nullptr;                    // two work buffers
+    long long wlen = 0;
+    hipEvent_t ev[6] = {};
+    bool have_ev = false;
+};
+
+namespace {
+
+int check_values(const igx_solver *s, const char *what)
+{
+    if (s->pt->values_kind != s->kind || !s->pt->d_data) {
+        set_error("%s: the patch no longer holds the values of the solver's matrix (another kind was assembled since, or an "
+                  "assembly failed): assemble it again", what);
+        return IGX_ERR_ARG;
+    }
+    return IGX_OK;
+}
+
+unsigned spmv_blocks(const igx_solver *s)
+{
+    const long long groups = BLOCK / s->gw;
+    return (unsigned)std::max<long long>(1, std::min<long long>(s->nb_spmv, (s->n + groups - 1) / groups));
+}
+
+int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
+{
+    const unsigned nb = spmv_blocks(s);
+    const double *v = s->pt->d_data;
+    switch (s->gw) {
+    case 64: k_spmv<64, 12><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
+    case 32: k_spmv<32, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
+    case 16: k_spmv<16, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
+    case 8: k_spmv<8, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
+    default: k_spmv<4, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
+    }
+    IGX_HIP(hipGetLastError());
+    return IGX_OK;
+}
+
+unsigned vec_blocks(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(NB_VEC, (n + BLOCK - 1) / BLOCK)); }
+
+// z = P r on the free box (kron), or nothing (none / Jacobi: z is formed by k_update or is r itself)
+int apply_kron(hipStream_t st, igx_solver *s, const double *r, double *z)
+{
+    double *W[2] = {s->d_W, s->d_W + s->wlen};
+    double *t = W[(s->dim - 1) % 2];             // the compact result of the first product (not read by its last step)
+    if (int rc = launch_kron_plan(st, s->kl, r, t, W)) return rc;
+    double *W2[2] = {W[s->dim % 2], t};          // step 0 must not write t, which it reads
+    return launch_kron_plan(st, s->kr, t, z, W2);
+}
+
+void free_solver(igx_solver *s)
+{
+    (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
+    (void)hipFree(s->d_kron); (void)hipFree(s->d_W);
+    if (s->have_ev)
+        for (auto &e : s->ev) (void)hipEventDestroy(e);
+    delete s;
+}
+
+} // namespace
+
+extern "C" {
+
+int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    if (!out) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
+    *out = nullptr;
+    if (!pt || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
+    if (kind != IGX_MASS && kind != IGX_STIFFNESS) {
+        set_error("igx_solver_create: CG needs a symmetric positive definite matrix (IGX_MASS or IGX_STIFFNESS), kind %d", kind);
+        return IGX_ERR_UNSUPPORTED;
+    }
+    if (pt->boxed || pt->row_lo != 0 || pt->row_hi != pt->nrows_total) {
+        set_error("igx_solver_create: whole patches only (no row slab, no span box)");
+        return IGX_ERR_UNSUPPORTED;
+    }
+    if (pt->values_kind != kind || !pt->d_data) {
+        set_error("igx_solver_create: assemble the patch with this kind first (igx_assemble, data_out may be NULL)");
+        return IGX_ERR_ARG;
+    }
+    if (hipSetDevice(pt->ctx->device) != hipSuccess) { set_error("igx_solver_create: hipSetDevice failed"); return IGX_ERR_HIP; }
+    igx_solver *s = new igx_solver;
+    s->pt = pt; s->kind = kind; s->dim = pt->dim; s->n = pt->nrows_total;
+    for (int k = 0; k < pt->dim; ++k) s->N[k] = pt->ax[k].N;
+    s->h_free.assign((size_t)s->n, 1);
+    for (int64_t k = 0; k < nfixed; ++k) {
+        if (fixed[k] < 0 || fixed[k] >= s->n) { set_error("igx_solver_create: fixed dof %lld out of range", (long long)fixed[k]); delete s; return IGX_ERR_ARG; }
+        if (!s->h_free[fixed[k]]) { set_error("igx_solver_create: fixed dof %lld given twice", (long long)fixed[k]); delete s; return IGX_ERR_ARG; }
+        s->h_free[fixed[k]] = 0;
+        s->fixed.push_back(fixed[k]);
+    }
+    // per-axis tables as a 3D layout (2D: a one-dof outer axis in front)
+    const int off = 3 - pt->dim;
+    std::vector<int> tab;
+    size_t pos[3][3];
+    long long maxlen = 1;
+    for (int a = 0; a < 3; ++a) {
+        std::vector<int> lo, hi, rp;
+        if (a < off) { lo = {0}; hi = {1}; rp = {0, 1}; s->g.N[a] = 1; }
+        else {
+            const igx::Axis &A = pt->ax[a - off];
+            lo = A.jlo; hi = A.jhi; rp = A.rp; s->g.N[a] = A.N;
+            int mc = 0;
+            for (int i = 0; i < A.N; ++i) mc = std::max(mc, A.jhi[i] - A.jlo[i]);
+            maxlen *= mc;
+        }
+        pos[a][0] = tab.size(); tab.insert(tab.end(), lo.begin(), lo.end());
+        pos[a][1] = tab.size(); tab.insert(tab.end(), hi.begin(), hi.end());
+        pos[a][2] = tab.size(); tab.insert(tab.end(), rp.begin(), rp.end());
+    }
+    s->gw = spmv_gw(maxlen);
+    {
+        int per_cu = 0;
+        hipError_t eo;
+        switch (s->gw) {
+        case 64: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<64, 12>, BLOCK, 0); break;
+        case 32: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<32, 4>, BLOCK, 0); break;
+        case 16: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<16, 4>, BLOCK, 0); break;
+        case 8: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<8, 4>, BLOCK, 0); break;
+        default: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<4, 4>, BLOCK, 0); break;
+        }
+        if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
+        s->nb_spmv = (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, pt->ctx->ncu));
+    }
+    const size_t n = (size_t)s->n;
+    bool ok = hipMalloc((void **)&s->d_tab, tab.size() * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&s->d_mask, n) == hipSuccess &&
+              hipMalloc((void **)&s->d_vec, 8 * n * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&s->d_part, 2 * (size_t)NB_SPMV_MAX * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&s->d_sc, SC_N * sizeof(double)) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); set_error("igx_solver_create: out of device memory (%.3f GB)", 8.0 * 8 * n / 1e9); free_solver(s); return IGX_ERR_NOMEM; }
+    hipStream_t st = pt->ctx->stream;
+    hipError_t e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_mask, s->h_free.data(), n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_vec, 0, 8 * n * sizeof(double), st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("igx_solver_create: %s", hipGetErrorString(e)); free_solver(s); return IGX_ERR_HIP; }
+    for (int a = 0; a < 3; ++a) { s->g.jlo[a] = s->d_tab + pos[a][0]; s->g.jhi[a] = s->d_tab + pos[a][1]; s->g.rp[a] = s->d_tab + pos[a][2]; }
+    s->g.S1 = tab[pos[1][2] + s->g.N[1]];
+    s->g.S2 = tab[pos[2][2] + s->g.N[2]];
+    s->g.nrows = s->n;
+    double *v = s->d_vec;
+    s->x = v; s->r = v + n; s->p = v + 2 * n; s->q = v + 3 * n; s->z = v + 4 * n; s->b = v + 5 * n; s->w = v + 6 * n; s->dinv = v + 7 * n;
+    for (auto &ev : s->ev)
+        if (hipEventCreate(&ev) != hipSuccess) { set_error("igx_solver_create: hipEventCreate failed"); free_solver(s); return IGX_ERR_HIP; }
+    s->have_ev = true;
+    *out = s;
+    return IGX_OK;
+}
+
+void igx_solver_destroy(igx_solver *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->pt->ctx->device);
+    (void)hipStreamSynchronize(s->pt->ctx->stream);
+    free_solver(s);
+}
+
+int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                           const double *const *lam, int lam_mode)
+{
+    if (!s) { set_error("igx_solver_set_precond: null solver"); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->pt->ctx->device));
+    hipStream_t st = s->pt->ctx->stream;
+    if (precond == IGX_PRECOND_NONE) { s->precond = precond; return IGX_OK; }
+    if (precond == IGX_PRECOND_JACOBI) {
+        if (int rc = check_values(s, "igx_solver_set_precond")) return rc;
+        k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pt->d_data, s->d_mask, s->dinv);
+        IGX_HIP(hipGetLastError());
+        IGX_HIP(hipStreamSynchronize(st));
+        s->precond = precond;
+        return IGX_OK;
+    }
+    if (precond != IGX_PRECOND_KRON) { set_error("igx_solver_set_precond: unknown preconditioner %d", precond); return IGX_ERR_ARG; }
+    if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_precond: null argument"); return IGX_ERR_ARG; }
+    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_precond: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
+    const int d = s->dim;
+    int nb[3] = {1, 1, 1};
+    for (int k = 0; k < d; ++k) {
+        if (box_lo[k] < 0 || box_hi[k] > s->N[k] || box_lo[k] >= box_hi[k] || !U[k] || !lam[k]) {
+            set_error("igx_solver_set_precond: bad free box [%d, %d) on axis %d", box_lo[k], box_hi[k], k);
+            return IGX_ERR_ARG;
+        }
+        nb[k] = box_hi[k] - box_lo[k];
+    }
+    // the box must be exactly the free dofs: the preconditioner leaves everything outside it at 0
+    {
+        long long I = 0;
+        int i[3] = {0, 0, 0};
+        for (i[0] = 0; i[0] < s->N[0]; ++i[0])
+            for (i[1] = 0; i[1] < (d > 1 ? s->N[1] : 1); ++i[1])
+                for (i[2] = 0; i[2] < (d > 2 ? s->N[2] : 1); ++i[2], ++I) {
+                    bool in = true;
+                    for (int k = 0; k < d; ++k) in = in && i[k] >= box_lo[k] && i[k] < box_hi[k];
+                    if (in != (s->h_free[I] != 0)) {
+                        set_error("igx_solver_set_precond: the free dofs are not the box given (dof %lld)", I);
+                        return IGX_ERR_ARG;
+                    }
+                }
+    }
+    size_t tot = 0;
+    for (int k = 0; k < d; ++k) tot += 2 * (size_t)nb[k] * nb[k] + nb[k];
+    std::vector<double> h(tot);
+    size_t o = 0;
+    size_t oUt[3], oU[3], oL[3];
+    for (int k = 0; k < d; ++k) {
+        const int m = nb[k];
+        oUt[k] = o;
+        for (int a = 0; a < m; ++a)
+            for (int b2 = 0; b2 < m; ++b2) h[o + (size_t)a * m + b2] = U[k][(size_t)b2 * m + a];
+        o += (size_t)m * m;
+        oU[k] = o;
+        std::memcpy(&h[o], U[k], (size_t)m * m * sizeof(double));
+        o += (size_t)m * m;
+        oL[k] = o;
+        std::memcpy(&h[o], lam[k], (size_t)m * sizeof(double));
+        o += m;
+    }
+    (void)hipFree(s->d_kron); s->d_kron = nullptr;
+    (void)hipFree(s->d_W); s->d_W = nullptr;
+    s->precond = IGX_PRECOND_NONE;
+    IGX_HIP(hipMalloc((void **)&s->d_kron, tot * sizeof(double)));
+    IGX_HIP(hipMemcpyAsync(s->d_kron, h.data(), tot * sizeof(double), hipMemcpyHostToDevice, st));
+    KronPlan L{}, R{};
+    L.dim = R.dim = d;
+    L.batch = R.batch = 1;
+    long long full_stride[3] = {1, 1, 1}, off = 0;
+    for (int k = d - 1; k >= 0; --k) full_stride[k] = k == d - 1 ? 1 : full_stride[k + 1] * s->N[k + 1];
+    for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
+    // (x) U_k^T reads the box of the full-length r, (x) U_k writes it into z; in between compact box vectors
+    long long box_stride[3] = {1, 1, 1};
+    for (int k = d - 2; k >= 0; --k) box_stride[k] = box_stride[k + 1] * nb[k + 1];
+    for (int k = 0; k < 4; ++k) {
+        L.x_stride[k] = R.y_stride[k] = k < d ? full_stride[k] : 1;
+        L.y_stride[k] = R.x_stride[k] = k < d ? box_stride[k] : 1;
+    }
+    L.x_off = R.y_off = off;
+    L.y_off = R.x_off = 0;
+    for (int k = 0; k < d; ++k) {
+        L.m[k] = L.n[k] = R.m[k] = R.n[k] = nb[k];
+        L.B[k] = s->d_kron + oUt[k];
+        R.B[k] = s->d_kron + oU[k];
+        L.lam[k] = s->d_kron + oL[k];
+    }
+    L.lam_mode = lam_mode;
+    s->kl = L; s->kr = R;
+    s->wlen = std::max<long long>(1, (long long)nb[0] * nb[1] * nb[2]);
+    IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)s->wlen * sizeof(double)));
+    IGX_HIP(hipStreamSynchronize(st));
+    s->precond = IGX_PRECOND_KRON;
+    return IGX_OK;
+}
+
+int igx_solver_spmv_d(igx_solver *s, const double *d_x, double *d_y)
+{
+    if (!s || !d_x || !d_y) { set_error("igx_solver_spmv_d: null argument"); return IGX_ERR_ARG; }
+    if (int rc = check_values(s, "igx_solver_spmv_d")) return rc;
+    IGX_HIP(hipSetDevice(s->pt->ctx->device));
+    hipStream_t st = s->pt->ctx->stream;
+    k_mask_copy<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->n, s->d_mask, d_x, s->w);
+    IGX_HIP(hipGetLastError());
+    if (int rc = spmv(st, s, s->w, nullptr, 1.0, d_y, nullptr, nullptr)) return rc;
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
+int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const double *x0, double tol, int maxiter, int check_every,
+                     int timed, double *u, igx_solve_info *info)
+{
+    if (!s || !b || (!gvals && !s->fixed.empty()) || !u) { set_error("igx_solver_solve: null argument"); return IGX_ERR_ARG; }
+    if (!(tol >= 0.0) || maxiter < 0) { set_error("igx_solver_solve: tol must be >= 0 and maxiter >= 0"); return IGX_ERR_ARG; }
+    if (int rc = check_values(s, "igx_solver_solve")) return rc;
+    if (check_every < 1) check_every = 1;
+    IGX_HIP(hipSetDevice(s->pt->ctx->device));
+    hipStream_t st = s->pt->ctx->stream;
+    const long long n = s->n;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    igx_solve_info inf{};
+    // ext(g) (+ the free part of x0): the vector the lifted right-hand side is formed with
+    std::vector<double> w((size_t)n, 0.0);
+    for (size_t k = 0; k < s->fixed.size(); ++k) w[s->fixed[k]] = gvals[k];
+    IGX_HIP(hipEventRecord(s->ev[5], st));
+    IGX_HIP(hipMemcpyAsync(s->b, b, nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(s->w, w.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemsetAsync(s->x, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->p, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->q, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->z, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st));
+    const unsigned nbv = vec_blocks(n), nbs = spmv_blocks(s);
+    double *pA = s->d_part, *pB = s->d_part + NB_SPMV_MAX;
+    // r = R (b - A ext(g)); its norm is the reference of the relative residual
+    if (int rc = spmv(st, s, s->w, s->b, -1.0, s->r, nullptr, nullptr)) return rc;
+    k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
+    k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbv, s->d_sc, FIN_INIT);
+    double h_rr = 0.0;
+    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    const double bnorm = std::sqrt(h_rr);
+    if (x0) {
+        for (long long i = 0; i < n; ++i) w[i] = s->h_free[i] ? x0[i] : 0.0;
+        IGX_HIP(hipMemcpyAsync(s->x, w.data(), nbytes, hipMemcpyHostToDevice, st));
+        if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
+    }
+    const bool kron = s->precond == IGX_PRECOND_KRON, jac = s->precond == IGX_PRECOND_JACOBI;
+    // z = P r, rz, rr; p = z
+    const double *zz = (kron || jac) ? s->z : s->r;
+    if (jac) {
+        IGX_HIP(hipMemsetAsync(s->d_sc + SC_ALPHA, 0, sizeof(double), st));   // k_update with alpha = 0: z = dinv r and the dots
+        k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, s->dinv, s->z, s->d_sc, pA, pB);
+    } else {
+        if (kron && (apply_kron(st, s, s->r, s->z) != IGX_OK)) return IGX_ERR_HIP;
+        k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, kron ? s->r : nullptr, s->z, pA, pB);
+    }
+    k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_INIT);
+    k_pupdate<<<nbv, BLOCK, 0, st>>>(n, zz, s->p, s->d_sc);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    const double stop = tol * bnorm;
+    bool conv = std::sqrt(h_rr) <= stop;
+    int it = 0;
+    while (!conv && it < maxiter) {
+        ++it;
+        if (timed) IGX_HIP(hipEventRecord(s->ev[0], st));
+        if (int rc = spmv(st, s, s->p, nullptr, 1.0, s->q, s->p, pA)) return rc;
+        if (timed) IGX_HIP(hipEventRecord(s->ev[1], st));
+        k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbs, s->d_sc, FIN_ALPHA);
+        k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, jac ? s->dinv : nullptr, s->z, s->d_sc, pA, pB);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(s->ev[2], st));
+        if (kron) {
+            if (int rc = apply_kron(st, s, s->r, s->z)) return rc;
+        }
+        if (timed) IGX_HIP(hipEventRecord(s->ev[3], st));
+        if (kron) k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->z, nullptr, nullptr, pB, nullptr);
+        k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_BETA);
+        k_pupdate<<<nbv, BLOCK, 0, st>>>(n, zz, s->p, s->d_sc);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(s->ev[4], st));
+        if (timed || it % check_every == 0 || it == maxiter) {
+            IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+            IGX_HIP(hipStreamSynchronize(st));
+            conv = std::sqrt(h_rr) <= stop;
+            if (timed) {
+                float a = 0, b2 = 0, c = 0, d2 = 0;
+                (void)hipEventElapsedTime(&a, s->ev[0], s->ev[1]);
+                (void)hipEventElapsedTime(&b2, s->ev[1], s->ev[2]);
+                (void)hipEventElapsedTime(&c, s->ev[2], s->ev[3]);
+                (void)hipEventElapsedTime(&d2, s->ev[3], s->ev[4]);
+                inf.spmv_ms += a; inf.precond_ms += c; inf.vector_ms += b2 + d2;
+            }
+        }
+    }
+    IGX_HIP(hipMemcpyAsync(u, s->x, nbytes, hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipEventRecord(s->ev[4], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("igx_solver_solve: kernel failure: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
+    }
+    (void)hipEventElapsedTime(&inf.total_ms, s->ev[5], s->ev[4]);
+    for (size_t k = 0; k < s->fixed.size(); ++k) u[s->fixed[k]] = gvals[k];
+    inf.iterations = it;
+    inf.converged = conv ? 1 : 0;
+    inf.relres = bnorm > 0.0 ? std::sqrt(h_rr) / bnorm : 0.0;
+    inf.n_free = n - (long long)s->fixed.size();
+    if (info) *info = inf;
+    return IGX_OK;
+}
+
+int igx_kron_apply_d(igx_ctx *ctx, const igx_kron_desc *d, const double *d_x, double *d_y, double *d_work, int64_t work_len)
+{
+    if (!ctx || !d || !d_x || !d_y) { set_error("igx_kron_apply_d: null argument"); return IGX_ERR_ARG; }
+    if (d->dim < 1 || d->dim > 3 || d->batch < 1) { set_error("igx_kron_apply_d: dim must be 1..3 and batch >= 1"); return IGX_ERR_ARG; }
+    if (d->lam_mode < 0 || d->lam_mode > IGX_KRON_PRODUCT) { set_error("igx_kron_apply_d: unknown lam_mode %d", d->lam_mode); return IGX_ERR_ARG; }
+    KronPlan P{};
+    P.dim = d->dim;
+    P.batch = d->batch;
+    for (int k = 0; k < d->dim; ++k) {
+        if (d->m[k] < 1 || d->n[k] < 1 || !d->d_B[k] || (d->lam_mode && !d->d_lam[k])) {
+            set_error("igx_kron_apply_d: factor %d is empty or missing", k);
+            return IGX_ERR_ARG;
+        }
+        P.m[k] = d->m[k]; P.n[k] = d->n[k]; P.B[k] = d->d_B[k]; P.lam[k] = d->d_lam[k];
+    }
+    for (int k = 0; k < 4; ++k) { P.x_stride[k] = d->x_stride[k]; P.y_stride[k] = d->y_stride[k]; }
+    P.x_off = d->x_off; P.y_off = d->y_off;
+    P.lam_mode = d->lam_mode;
+    const long long need = kron_work_len(P);
+    IGX_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    double *own = nullptr;
+    if (need > 0 && !d_work) {
+        IGX_HIP(hipMalloc((void **)&own, 2 * (size_t)need * sizeof(double)));
+        d_work = own;
+    } else if (need > 0 && work_len < 2 * need) {
+        set_error("igx_kron_apply_d: work buffer of %lld doubles, %lld needed", (long long)work_len, 2 * need);
+        return IGX_ERR_ARG;
+    }
+    double *W[2] = {d_work, d_work ? d_work + need : nullptr};
+    int rc = launch_kron_plan(st, P, d_x, d_y, W);
+    hipError_t e = hipStreamSynchronize(st);
+    (void)hipFree(own);
+    if (rc) return rc;
+    if (e != hipSuccess) { set_error("igx_kron_apply_d: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
+    return IGX_OK;
+}
+
+} // extern "C"
