@@ -392,6 +392,7 @@ igx_patch *igx_patch_create(igx_ctx *ctx, const igx_patch_desc *d)
         if (const char *e = getenv("IGX_ENTRIES")) k.entries_thread = !strcmp(e, "thread");
         k.poison = getenv("IGX_DEBUG_POISON") != nullptr;
         if (const char *e = getenv("IGX_BF")) k.bf = atoi(e);
+        k.no_twin = getenv("IGX_NO_TWIN") != nullptr;
         if (const char *e = getenv("IGX_PLACEMENT_TRIES")) k.placement_tries = std::max(1, std::min(16, atoi(e)));
         if (const char *e = getenv("IGX_STAGE_EVENTS")) k.stage_events = strcmp(e, "0") != 0;
     }
@@ -516,7 +517,7 @@ igx_patch *igx_patch_create(igx_ctx *ctx, const igx_patch_desc *d)
     // the mass and the stiffness matrix are assembled (igx_internal.h, igx_patch::twin).  The twin is an ordinary patch -- same
     // parameter domain, same map, |det| of the Jacobian unchanged -- only its values land in THIS patch's CSR layout.  A twin that
     // cannot be created or whose fast chain does not serve the patch is dropped: the stage kernels take such a patch as before.
-    if (dim == 3 && !pt->boxed && pt->sumfact_ok && pt->ax[1].simple && !pt->ax[2].simple && d->ctrl &&
+    if (dim == 3 && !pt->boxed && pt->sumfact_ok && !pt->knobs.no_twin && pt->ax[1].simple && !pt->ax[2].simple && d->ctrl &&
         (d->geo_kind == IGX_GEO_BSPLINE || d->geo_kind == IGX_GEO_NURBS)) {
         igx_patch_desc e = *d;
         const int perm[3] = {0, 2, 1};
@@ -951,6 +952,8 @@ int igx_assemble(igx_patch *pt, int kind, int algo, double *data_out)
     if (algo == IGX_ALGO_SUMFACT && !sumfact_supports_kind(pt, kind)) { set_error("igx_assemble: sum factorisation does not support this form yet"); return IGX_ERR_UNSUPPORTED; }
     if (algo == IGX_ALGO_SUMFACT && !pt->sumfact_ok) { set_error("igx_assemble: sum factorisation does not support this patch (degree > %d)", IGX_MAX_SF_DEGREE); return IGX_ERR_UNSUPPORTED; }
     if (algo != IGX_ALGO_SUMFACT && algo != IGX_ALGO_ENTRYWISE) { set_error("igx_assemble: unknown algo %d", algo); return IGX_ERR_ARG; }
+    Plan plan;
+    if (algo == IGX_ALGO_SUMFACT) sumfact_plan(pt, kind, plan);
     if (!pt->d_data) {
         const size_t bytes = ((size_t)std::max(pt->nnz, pt->nnz_ext) + IGX_DUMP_PAD) * sizeof(double);   // + halo rows of the mirror pass / dump slots of masked stores
         hipError_t e = hipMalloc((void **)&pt->d_data, bytes);
@@ -958,13 +961,13 @@ int igx_assemble(igx_patch *pt, int kind, int algo, double *data_out)
         // opt-in (IGX_PLACEMENT_TRIES): keep the candidate buffer on which the mirror pass of this patch runs fastest.  The
         // candidates are alive together (the driver must not hand the same pages out again); a failed allocation or probe ends
         // the search with what there is.
-        if (pt->knobs.placement_tries > 1 && pt->knobs.bf == 2 && algo == IGX_ALGO_SUMFACT && igx_kind_symmetric(kind) && pt->sumfact_ok) {   // (only the chain with the mirror pass: IGX_BF=2)
+        if (pt->knobs.placement_tries > 1 && pt->knobs.bf == 2 && algo == IGX_ALGO_SUMFACT) {   // (only the chain with the mirror pass: IGX_BF=2)
             std::vector<double *> cand(1, pt->d_data);
-            std::vector<float> ms(1, sumfact_probe_mirror(pt, pt->d_data));
+            std::vector<float> ms(1, sumfact_probe_mirror(pt, plan, pt->d_data));
             for (int k = 1; k < pt->knobs.placement_tries && ms[0] >= 0.0f; ++k) {
                 double *b = nullptr;
                 if (hipMalloc((void **)&b, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-                const float t = sumfact_probe_mirror(pt, b);
+                const float t = sumfact_probe_mirror(pt, plan, b);
                 if (t < 0.0f) { (void)hipFree(b); break; }
                 cand.push_back(b); ms.push_back(t);
             }
@@ -991,15 +994,14 @@ int igx_assemble(igx_patch *pt, int kind, int algo, double *data_out)
     pt->fields_kind = -1;                           // the timed path always recomputes the fields
     pt->last_path = 0;
     int rc = IGX_OK;
-    if (algo != IGX_ALGO_SUMFACT || sumfact_needs_fields(pt, kind)) rc = ensure_fields(pt, kind);
+    if (algo != IGX_ALGO_SUMFACT || plan.needs_fields) rc = ensure_fields(pt, kind);
     if (rc) return rc;
     pt->timing.n_launches = 1;
     // k_single2d: first and last event only (one launch); a chain without stage events likewise
-    const bool one_launch = algo == IGX_ALGO_SUMFACT && pt->dim == 2 && sumfact_single_launch(pt, kind);
-    const bool staged = !one_launch && pt->knobs.stage_events;
+    const bool staged = !plan.one_launch && pt->knobs.stage_events;
     if (staged) IGX_HIP(hipEventRecord(ev[1], st));
     if (algo == IGX_ALGO_SUMFACT) {
-        rc = sumfact_assemble(pt, kind, pt->d_data);
+        rc = sumfact_assemble(pt, plan, pt->d_data);
         if (rc == IGX_ERR_UNSUPPORTED && was_auto) {
             // a shape the stage kernels refuse (a limit of their staging buffers): with IGX_ALGO_AUTO the entry-wise kernels take
             // over -- same device, same matrix; an explicit IGX_ALGO_SUMFACT keeps the error
@@ -1024,7 +1026,7 @@ int igx_assemble(igx_patch *pt, int kind, int algo, double *data_out)
     }
     (void)hipEventElapsedTime(&pt->timing.total_ms, ev[0], ev[5]);
     pt->values_kind = kind;
-    if (one_launch) pt->timing.stage1_ms = pt->timing.total_ms;
+    if (plan.one_launch) pt->timing.stage1_ms = pt->timing.total_ms;
     if (!staged) {                              // only the whole interval was timed
     } else if (algo == IGX_ALGO_SUMFACT) {
         (void)hipEventElapsedTime(&pt->timing.fields_ms, ev[0], ev[1]);

@@ -102,8 +102,6 @@ struct GeoAxis {                              // geometry basis restricted to th
     int *d_fa = nullptr;                      // [G] first active control index at node g
 };
 
-struct Plan;                                   // sum-factorisation plan (sumfact.hip)
-
 } // namespace igx
 
 struct igx_ctx {
@@ -124,6 +122,7 @@ struct igx_knobs {
     int entries_thread = 0;                   // IGX_ENTRIES=thread: one thread per entry (the reference's summation order)
     int poison = 0;                           // IGX_DEBUG_POISON: NaN-fill the CSR values before an assembly (tests)
     int bf = 0;                               // IGX_BF=2: symmetric 3D forms through k_bf2 + the mirror pass (the chain of rounds 3-4) instead of k_bf3
+    int no_twin = 0;                          // IGX_NO_TWIN: no twin patch (repeated knots on the last axis: the stage kernels, as before round 6)
     int placement_tries = 1;                  // IGX_PLACEMENT_TRIES=n (opt-in, 3D symmetric forms): the CSR value buffer is the fastest of n
                                               // allocations under the mirror pass, timed once at its first assembly
     int stage_events = -1;                    // IGX_STAGE_EVENTS: events between the kernels of a chain (per-kernel device times in
@@ -166,7 +165,8 @@ struct igx_patch {
     // Repeated knots on the LAST axis only (round 6): k_bf3 contracts an axis of single knots and sweeps one that may have repeated
     // ones, so such a patch is assembled through its TWIN -- the same patch with mid and last axis exchanged (knot vectors, control
     // net), created with it -- whose k_bf3 stores straight into the CSR layout of this patch (fused3.hip, TR).  twin_kinds: bit per
-    // IGX_* kind the twin's fast chain serves; is_twin: this patch is one (its values belong to its owner's layout).
+    // IGX_* kind whose plan on the twin is k_geoA -> k_bf3 (sumfact_twin_kinds); is_twin: this patch is one (its values belong to
+    // its owner's layout).
     igx_patch *twin = nullptr;
     int twin_kinds = 0;
     bool is_twin = false;
@@ -203,7 +203,6 @@ struct igx_patch {
     bool desc_built = false;
     int *d_ldesc = nullptr;                   // [n_ldesc][4] line descriptors of the final stage
     int n_ldesc = 0;
-    bool ldesc_ok = false;
     int *d_steps = nullptr;                   // flush-step tables of the sweeps (one allocation)
     const int *stepA_ptr = nullptr, *stepA_rec = nullptr, *stepB_ptr = nullptr, *stepB_rec = nullptr;
     float placement_ms_best = 0, placement_ms_worst = 0;   // IGX_PLACEMENT_TRIES: mirror pass on the kept / the slowest candidate
@@ -339,14 +338,55 @@ int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *
                 double *const *slot_out, long long slice_stride, int chunk_len, int nchunks, const int *slot_xfield = nullptr, const int *slot_xtype = nullptr,
                 const GeoAForm *form = nullptr);
 bool geoA_form_supported(const igx_patch *pt);
-bool sumfact_needs_fields(const igx_patch *pt, int kind);
+
+// The kernel chain of one sum-factorised assembly: sumfact_plan decides all of it from the patch, its knobs and the kind (no HIP
+// calls), sumfact_assemble runs it.  The chains:
+//   FORM_TABLE  k_geoA<FORM = 2 | 3> -> k_bf3                   a coefficient table (form_table_plan)
+//   SINGLE2D    k_single2d                                      small 2D patches
+//   FUSED2D     the field arrays -> k_bf3, or k_bf2 + k_mirror2  (IGX_PATH=fused in 2D)
+//   STAGES      k_geoA or k_stageA -> k_bf3, or k_bf2 (+ k_mirror2), or k_stageB / k_combine -> k_final_mfma, k_final_q or k_final
+// twin: the plan is that of pt->twin (repeated knots on the last axis only), whose values land in the patch's layout.
+struct Term;                                  // sumfact_stages.h
+struct XA { int t0, f, slot, key, xt0, xf, alias; };   // stage-A array: axis-0 type, field (+ second source of a merged slot)
+struct FormPlan {
+    bool ok = false, sym = false;
+    GeoAForm g;
+    int narr = 0;
+    int slot_arr[4][4];                       // (last-axis type y, mid-axis type t1) -> K1 array, or -1
+    bool mass_only = false;
+};
+struct Plan {
+    enum Chain { FORM_TABLE, SINGLE2D, FUSED2D, STAGES };
+    enum Fused { NO_FUSED, BF3, BF2 };
+    enum Final { FINAL_VALU, FINAL_Q, FINAL_MFMA };
+    int kind = 0;
+    bool sym = false, twin = false;
+    Chain chain = STAGES;
+    bool needs_fields = false;                // the chain reads the field arrays (igx_assemble computes them first)
+    bool one_launch = false;                  // no stage events (k_single2d)
+    // K1 arrays of the stage chain (the field arrays in FUSED2D): terms of the form, their stage-A arrays X, term -> X.  merged
+    // (non-symmetric 3D forms into the fused stage): one array per fused-stage slot, an alias shares an earlier slot's array
+    std::vector<Term> terms;
+    std::vector<XA> X;
+    std::vector<int> term_x;
+    bool merged = false;
+    int nX = 0;
+    bool geoA = false;                        // stage 0: k_geoA, else k_stageA
+    Fused fused = NO_FUSED;
+    int slot_n[4][4] = {}, slot_arr[4][4][2]; // fused-stage inputs per (last-axis type, mid-axis type): count, array index
+    Final fin = FINAL_VALU;
+    int mfma_nch = 0;                         // k_final_mfma: 8-point chunks of the Gauss window
+    FormPlan form;
+    Plan();                                   // (out of line: Term is complete in sumfact.hip)
+    ~Plan();
+};
+void sumfact_plan(const igx_patch *pt, int kind, Plan &pl);
 int sumfact_twin_kinds(const igx_patch *tw);                    // IGX_* kinds (bit mask) the fast chain of an axis-exchanged twin serves
-bool sumfact_single_launch(const igx_patch *pt, int kind);     // the 2D single-launch kernel will run (no stage events inside)
-// device time of the mirror pass of this patch on `buf` (access pattern only: the values are whatever the buffer holds);
-// < 0 when the patch has no such pass
-float sumfact_probe_mirror(igx_patch *pt, double *buf);
+// device time of the mirror pass of this plan on `buf` (access pattern only: the values are whatever the buffer holds);
+// < 0 when the plan has no such pass
+float sumfact_probe_mirror(igx_patch *pt, const Plan &pl, double *buf);
 int sumfact_supported(const igx_patch *pt);
 int sumfact_prepare(igx_patch *pt);
 int sumfact_supports_kind(const igx_patch *pt, int kind);
-int sumfact_assemble(igx_patch *pt, int kind, double *d_data);
+int sumfact_assemble(igx_patch *pt, const Plan &pl, double *d_data);
 } // namespace igx

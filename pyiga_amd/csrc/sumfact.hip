@@ -564,6 +564,9 @@ static int build_qdesc(igx_patch *pt, const std::vector<int> &pl, bool sym, int 
     return IGX_OK;
 }
 
+// the line field of a k_final_mfma descriptor has 28 bits
+static bool ldesc_fits(const igx_patch *pt) { return (long long)pt->npairs0 * (pt->dim == 3 ? pt->ax[1].S : 1) < (1LL << 28); }
+
 // Line descriptors of the stage-kernel final (k_final_q / k_final_mfma): ~0.8 M descriptors (25 MB) at C4, built on
 // the host.  The default 3D chain (k_geoA, k_bf, k_mirror) never reads them, so they are made on first use.
 static int ensure_line_descriptors(igx_patch *pt)
@@ -606,7 +609,6 @@ static int ensure_line_descriptors(igx_patch *pt)
             }
         }
         pt->n_ldesc = (int)(ld.size() / 4);
-        pt->ldesc_ok = (long long)pt->npairs0 * (dim == 3 ? A1.S : 1) < (1LL << 28);
         if (pt->d_ldesc) { (void)hipFree(pt->d_ldesc); pt->d_ldesc = nullptr; }     // (a retry after a failed build: no leak)
         IGX_HIP(hipMalloc(&pt->d_ldesc, std::max<size_t>(1, ld.size()) * sizeof(int)));
         IGX_HIP(hipMemcpyAsync(pt->d_ldesc, ld.data(), ld.size() * sizeof(int), hipMemcpyHostToDevice, pt->ctx->stream));
@@ -789,6 +791,10 @@ static int geoa2d_min_chunk(int P)
     case 6: { constexpr int PP = 6; CALL; } break;             \
     default: set_error("sum factorisation: degree %d unsupported", (Pv) - 1); return IGX_ERR_UNSUPPORTED; }
 
+// ---------------------------------------------------------------------------------------------
+// The plan: which chain runs (igx_internal.h, Plan).  Every test of the knobs and of the kernels' limits that chooses a path is
+// made here, before anything is launched; the executors below only run what the plan says.
+//
 // The fused sweep + final stage (fused.hip) needs single interior knots, equal degrees and q = p + 1 on the swept and
 // the last axis.  It is the default in 3D (C4: 12.1 + 3.7 ms against 6.9 + 9.4..10.7 ms for stage B + final, K2 never in
 // HBM); in 2D the unfused kernels are faster (C2: 0.105 against 0.141 ms) and stay the default.  IGX_PATH=fused / unfused
@@ -799,8 +805,6 @@ static bool geoA_wanted(const igx_patch *pt, int kind, int nslots)
     if (!pt->knobs.geoa) return false;
     return (igx_kind_symmetric(kind) || kind == IGX_CONVDIFF) && geoA_supported(pt, kind, nslots);
 }
-static bool fused_applicable(const igx_patch *pt);
-static bool fused3_axes(const igx_patch *pt, bool sym);
 
 // The single launch beats the stage-kernel chain while its grid is one resident round of tiles of at most 6 x 6 rows
 // (a block's duration grows with its tile: 14 us at 2 x 4 rows, 27 us at 6 x 6, 39 us at 8 x 8 against 28-34 us of
@@ -818,43 +822,6 @@ static bool single2d_wanted(const igx_patch *pt, int kind)
     int rows = 0;
     const long long nb = single2d_blocks(pt, kind, &rows, true);
     return nb >= 0 && nb <= SINGLE2D_MAX_BLOCKS && rows <= SINGLE2D_MAX_TILE;
-}
-
-bool form_on_fast_chain(const igx_patch *pt);
-bool sumfact_single_launch(const igx_patch *pt, int kind) { return single2d_wanted(pt, kind); }
-// Repeated knots on the last axis only: the patch is assembled through its axis-exchanged twin (igx_internal.h, igx_patch::twin),
-// whose fast chain serves the kinds of twin_kinds (sumfact_twin_kinds, asked once when the twin is created).
-static bool twin_route(const igx_patch *pt, int kind)
-{
-    if (!pt->twin || pt->is_twin) return false;
-    // a form given as a table of expressions (igx_patch_set_form_expr hands it to the twin as well): where the twin's fast chain takes it
-    if (kind == IGX_FORM) return pt->twin->ftab.valid && pt->ftab.valid && !pt->dev.form_par && form_on_fast_chain(pt->twin);
-    return kind >= 0 && kind < 31 && ((pt->twin_kinds >> kind) & 1);
-}
-int sumfact_twin_kinds(const igx_patch *tw)
-{
-    if (tw->dim != 3 || !tw->sumfact_ok || tw->knobs.path == 2 || tw->knobs.final_sel || tw->knobs.bf == 2) return 0;
-    if (getenv("IGX_NO_TWIN")) return 0;                 // (experiments: the stage kernels for such patches, as before round 6)
-    const Axis &AM = tw->ax[1], &AL = tw->ax[2];
-    if (!fused3_axes(tw, true) || !fused3_tr_fits(tw->ax[0].p, AM.p, AL.p, AM.S, AL.S)) return 0;
-    int kinds = 0;
-    if (geoA_wanted(tw, IGX_MASS, 1)) kinds |= 1 << IGX_MASS;
-    if (geoA_wanted(tw, IGX_STIFFNESS, 8)) kinds |= 1 << IGX_STIFFNESS;
-    // the convection-diffusion form: its coefficient follows the patch's (igx_api.hip, twin_coeff)
-    if (fused3_axes(tw, false) && geoA_wanted(tw, IGX_CONVDIFF, 8)) kinds |= 1 << IGX_CONVDIFF;
-    return kinds;
-}
-
-bool sumfact_needs_fields(const igx_patch *pt, int kind)
-{
-    if (twin_route(pt, kind)) return false;
-    if (single2d_wanted(pt, kind)) return false;
-    if (kind == IGX_FORM && pt->dim == 3 && form_on_fast_chain(pt)) return false;
-    if (pt->dim == 2) return !(igx_kind_symmetric(kind) && pt->knobs.path != 1 && geoA_wanted(pt, kind, kind == IGX_MASS ? 1 : 4));
-    if (pt->dim != 3) return true;
-    // the convection-diffusion form: its eight merged slots exist where the fused stage runs (sumfact_assemble)
-    if (!igx_kind_symmetric(kind)) return !(kind == IGX_CONVDIFF && (fused_applicable(pt) || fused3_axes(pt, false)) && geoA_wanted(pt, kind, 8));
-    return !geoA_wanted(pt, kind, kind == IGX_MASS ? 1 : 8);
 }
 
 // k_bf3 (fused3.hip): single knots on the LAST axis only; the swept axis may have repeated knots; the two degrees may differ
@@ -883,88 +850,6 @@ static bool fused_applicable(const igx_patch *pt)
     return fused_offsets_fit(dim == 3 ? 2 * pt->ax[0].p + 1 : 1, AM.S, AL.S, AM.G, AL.G);
 }
 
-// slot table of the fused stage: input array `ptr` enters the sweep with mid-axis type t1 and last-axis type y
-static bool bf_add_slot(BFInputs &in, int y, int t1, const double *ptr)
-{
-    int &n = in.slot_n[y][t1];
-    if (n >= 2) return false;
-    in.slot_ptr[y][t1][n++] = ptr;
-    return true;
-}
-
-static int run_fused(igx_patch *pt, BFInputs &in, bool sym, double *d_data, bool use3)
-{
-    hipStream_t st = pt->ctx->stream;
-    const int dim = pt->dim;
-    const Axis &A0 = pt->ax[0];
-    in.mid = &pt->ax[dim - 2]; in.last = &pt->ax[dim - 1];
-    in.zeros = pt->d_zeros; in.sym = sym ? 1 : 0;
-    if (dim == 3) { in.rp0 = A0.dev.rp; in.jlo0 = A0.dev.jlo; in.jhi0 = A0.dev.jhi; }
-    else { in.pl0 = pt->d_triv; in.npairs = 1; in.rp0 = pt->d_triv + 2; in.jlo0 = pt->d_triv + 4; in.jhi0 = pt->d_triv + 5; }
-    int i1_lo = 0, i1_hi = in.mid->N;
-    if (dim == 3) { in.mid_lo = 0; in.mid_hi = in.mid->N; in.span_hi = in.mid->n; }
-    else {
-        // 2D: the swept axis carries the row slab; symmetric forms also produce the lower entries of the p halo rows
-        // above it (mirror sources), as far as the resident spans reach
-        i1_lo = pt->r0_lo; i1_hi = pt->r0_hi;
-        in.mid_lo = pt->r0_lo; in.mid_hi = sym ? std::min(pt->r0_hi + A0.p, A0.N) : pt->r0_hi; in.span_hi = pt->s0_hi;
-    }
-    // k_bf3 (fused3.hip): symmetric forms get their upper triangle from the same registers as the lower one -- no mirror pass
-    in.tr = pt->is_twin ? 1 : 0;
-    if (pt->is_twin && !use3) { set_error("internal: the axis-exchanged twin of a patch left k_bf3"); return IGX_ERR_UNSUPPORTED; }
-    if (use3) {
-        if (dim == 2 && sym) in.mid_hi = pt->r0_hi;      // (no mirror sources above the slab)
-        if (int rc = launch_bf3(st, pt, in, d_data)) return rc;
-        pt->last_path |= IGX_PATH_FUSED | IGX_PATH_BF3 | (sym ? IGX_PATH_BOTH : 0);
-        pt->timing.n_launches++;
-        stage_event(pt, 3, st);
-        stage_event(pt, 4, st);
-        return IGX_OK;
-    }
-    if (int rc = launch_bf(st, pt, in, d_data)) return rc;
-    pt->last_path |= IGX_PATH_FUSED;
-    pt->timing.n_launches++;
-    stage_event(pt, 3, st);
-#ifdef IGX_ABLATE
-    if (sym && !getenv("IGX_NO_MIRROR")) {
-#else
-    if (sym) {
-#endif
-        MirrorInputs mi{};
-        mi.mid = in.mid; mi.last = in.last; mi.rp0 = in.rp0; mi.jlo0 = in.jlo0; mi.jhi0 = in.jhi0;
-        mi.tpairs = pt->d_tpairs; mi.ntp = pt->ntp; mi.i1_lo = i1_lo; mi.i1_hi = i1_hi;
-        if (int rc = launch_mirror(st, pt, mi, d_data)) return rc;
-        pt->last_path |= IGX_PATH_MIRROR;
-        pt->timing.n_launches++;
-    }
-    stage_event(pt, 4, st);
-    return IGX_OK;
-}
-
-// The mirror pass gathers 72-byte runs all over the CSR values and takes 3.3 - 4.2 ms at C4 depending on where the driver put
-// the 12.75 GB physically -- a property of the BUFFER, stable over its life (DESIGN.md section 4).  A caller that opts in
-// (IGX_PLACEMENT_TRIES) lets the first assembly time the pass on a few candidate buffers and keep the fastest.
-float sumfact_probe_mirror(igx_patch *pt, double *buf)
-{
-    if (pt->dim != 3 || !fused_applicable(pt) || pt->ntp == 0) return -1.0f;
-    hipStream_t st = pt->ctx->stream;
-    const Axis &A0 = pt->ax[0];
-    MirrorInputs mi{};
-    mi.mid = &pt->ax[1]; mi.last = &pt->ax[2]; mi.rp0 = A0.dev.rp; mi.jlo0 = A0.dev.jlo; mi.jhi0 = A0.dev.jhi;
-    mi.tpairs = pt->d_tpairs; mi.ntp = pt->ntp; mi.i1_lo = 0; mi.i1_hi = pt->ax[1].N;
-    hipEvent_t *ev = pt->ctx->ev;
-    float best = -1.0f;
-    for (int rep = 0; rep < 3; ++rep) {                  // (the first launch also pages the buffer in)
-        if (hipEventRecord(ev[6], st) != hipSuccess) return -1.0f;
-        if (launch_mirror(st, pt, mi, buf)) return -1.0f;
-        if (hipEventRecord(ev[7], st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1.0f;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev[6], ev[7]) != hipSuccess) return -1.0f;
-        if (rep > 0 && (best < 0.0f || ms < best)) best = ms;
-    }
-    return best;
-}
-
 // ---------------------------------------------------------------------------------------------
 // General first-order forms on the fast chain (round 6).  A form given as a coefficient table (igx_patch_set_form_expr: constants
 // and expressions in the physical coordinates) needs no field arrays: k_geoA<FORM = 2 | 3> evaluates F = W T P T^T at every point
@@ -973,14 +858,6 @@ float sumfact_probe_mirror(igx_patch *pt, double *buf)
 // slot into ONE K1 array, which is what k_bf3 wants.  A symmetric table takes the symmetric chain: lower pairs of axis 0, both
 // triangles from k_bf3<SYM = 2>, exactly symmetric result -- half the work of the reference's default for such a form.
 // Reference: pyiga/vform.py:705-731 (finalize), pyiga/codegen/cython.py:325-387 (the generated combine), assemble.py:837-897.
-struct FormPlan {
-    bool ok = false, sym = false;
-    GeoAForm g;
-    int narr = 0;
-    int slot_arr[4][4];                                  // (last-axis type y, mid-axis type t1) -> K1 array, or -1
-    bool mass_only = false;
-};
-
 static FormPlan form_table_plan(const igx_patch *pt)
 {
     FormPlan fp;
@@ -1054,113 +931,85 @@ static FormPlan form_table_plan(const igx_patch *pt)
     return fp;
 }
 
-bool form_on_fast_chain(const igx_patch *pt) { return form_table_plan(pt).ok; }
+Plan::Plan() = default;
+Plan::~Plan() = default;
 
-static int run_fused(igx_patch *pt, BFInputs &in, bool sym, double *d_data, bool use3);
-static int assemble_form_table(igx_patch *pt, FormPlan &fp, double *d_data)
+// the table chain: one K1 array per slot of k_bf3
+static void plan_form_slots(Plan &pl)
 {
-    hipStream_t st = pt->ctx->stream;
-    const Axis &A0 = pt->ax[0], &A1 = pt->ax[1], &A2 = pt->ax[2];
-    const long long NPL = (long long)A1.G * A2.G;
-    const bool sym = fp.sym;
-    if (!sym && prepare_nonsym(pt)) return IGX_ERR_HIP;
-    const int np0 = sym ? pt->npairs0 : pt->npairs0n;
-    const int *d_pl0 = sym ? pt->d_pl0 : pt->d_pl0n;
-    if (np0 == 0) return IGX_OK;
-    // the entries of the table that are functions: sampled once per patch by the generated coefficient kernel
-    igx_patch::FormTable &T = pt->ftab;
-    const size_t npts = (size_t)pt->dev.npts_loc;
-    if (T.narr > 0 && !pt->ftab_ready) {
-        std::vector<const char *> list((size_t)T.narr, nullptr);
-        for (int k = 0; k < 16; ++k)
-            if (T.arr_of[k] >= 0 && !list[(size_t)T.arr_of[k]]) list[(size_t)T.arr_of[k]] = T.expr[k].c_str();
-        if (!pt->ftab_arr && hipMalloc((void **)&pt->ftab_arr, std::max<size_t>(1, (size_t)T.narr * npts) * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError(); pt->ftab_arr = nullptr;
-            set_error("hipMalloc of %.2f GB for the sampled coefficients of the form failed", T.narr * npts * 8.0 / 1e9);
-            return IGX_ERR_NOMEM;
-        }
-        int hit = 0;
-        if (int rc = launch_form_exprs(st, pt, T.narr, list.data(), pt->ftab_arr, &hit)) return rc;
-        pt->ftab_ready = true;
-    }
-    for (int k = 0; k < 16; ++k) fp.g.pa[k] = T.arr_of[k] >= 0 ? pt->ftab_arr + (size_t)T.arr_of[k] * npts : nullptr;
-    if (ensure(st, &pt->d_K1, &pt->K1_cap, (size_t)fp.narr * np0 * NPL)) return IGX_ERR_NOMEM;
-    stage_event(pt, 1, st);
-    double *so[8];
-    for (int x = 0; x < fp.narr; ++x) so[x] = pt->d_K1 + (size_t)x * np0 * NPL;
-    const SweepChunks ch = sweep_chunks((NPL + 63) / 64, pt->s0_hi - pt->s0_lo, A0.P);
-    if (int rc = launch_geoA(st, pt, IGX_FORM, fp.narr, nullptr, nullptr, so, NPL, ch.len, ch.nchunks, nullptr, nullptr, &fp.g)) return rc;
-    pt->last_path |= IGX_PATH_GEOA;
-    pt->timing.n_launches++;
-    stage_event(pt, 2, st);
-    BFInputs in{};
-    bool ok = true;
+    pl.chain = Plan::FORM_TABLE;
+    pl.sym = pl.form.sym;
     for (int y = 0; y < 4; ++y)
         for (int t1 = 0; t1 < 4; ++t1)
-            if (fp.slot_arr[y][t1] >= 0) ok = ok && bf_add_slot(in, y, t1, pt->d_K1 + (size_t)fp.slot_arr[y][t1] * np0 * NPL);
-    in.sym = sym ? 1 : 0;
-    in.pad_stiff3 = fp.mass_only ? 0 : 1;
-    if (!ok || !fused3_supported(in)) { set_error("internal: the slots of the form do not fit the fused stage"); return IGX_ERR_UNSUPPORTED; }
-    in.slice_stride = NPL; in.gmid_lo = 0; in.pl0 = d_pl0; in.npairs = np0;
-    return run_fused(pt, in, sym, d_data, true);
+            if (pl.form.slot_arr[y][t1] >= 0) pl.slot_arr[y][t1][pl.slot_n[y][t1]++] = pl.form.slot_arr[y][t1];
 }
 
-int sumfact_assemble(igx_patch *pt, int kind, double *d_data)
+void sumfact_plan(const igx_patch *pt, int kind, Plan &pl)
 {
-    hipStream_t st = pt->ctx->stream;
     const int dim = pt->dim;
-    const PatchDev &pd = pt->dev;
-    if (twin_route(pt, kind)) {                           // repeated knots on the last axis: the twin's chain, values to THIS layout
-        igx_patch *tw = pt->twin;
-        memset(&tw->timing, 0, sizeof(tw->timing));
-        tw->last_path = 0;
-        const int rc = sumfact_assemble(tw, kind, d_data);
-        pt->last_path |= tw->last_path | IGX_PATH_TWIN;
-        pt->timing.n_launches += tw->timing.n_launches;
-        return rc;
+    const bool sym = igx_kind_symmetric(kind);
+    pl.kind = kind;
+    pl.sym = sym;
+    // repeated knots on the last axis only: the twin's chain for the kinds of twin_kinds, and for a coefficient table
+    // (igx_patch_set_form_expr hands it to the twin as well) where the twin's table chain takes it
+    if (pt->twin && !pt->is_twin) {
+        if (kind != IGX_FORM && ((pt->twin_kinds >> kind) & 1)) {
+            sumfact_plan(pt->twin, kind, pl);
+            pl.twin = true;
+            return;
+        }
+        if (kind == IGX_FORM && pt->ftab.valid && !pt->dev.form_par) {
+            pl.form = form_table_plan(pt->twin);
+            if (pl.form.ok) { plan_form_slots(pl); pl.twin = true; return; }
+        }
     }
     if (kind == IGX_FORM && dim == 3) {                   // a coefficient table on the fast chain: no field arrays
-        FormPlan fp = form_table_plan(pt);
-        if (fp.ok) return assemble_form_table(pt, fp, d_data);
+        pl.form = form_table_plan(pt);
+        if (pl.form.ok) { plan_form_slots(pl); return; }
     }
-    std::vector<Term> terms = form_terms(dim, kind, &pd);
-    const Axis &A0 = pt->ax[0], &A1 = pt->ax[1], &A2 = pt->ax[2];
-    const long long NPL = (long long)A1.G * (dim == 3 ? A2.G : 1);
-    const bool sym = igx_kind_symmetric(kind);
-    if (!sym && prepare_nonsym(pt)) return IGX_ERR_HIP;
-    const int np0 = sym ? pt->npairs0 : pt->npairs0n;
-    const int *d_pl0 = sym ? pt->d_pl0 : pt->d_pl0n;
-    if (np0 == 0) return IGX_OK;
     if (single2d_wanted(pt, kind)) {
         // one launch between the caller's first and last event: no stage events (a marker costs a few microseconds of
         // stream time, as much as this kernel on a small patch); igx_assemble reports the whole interval as stage 1
-        if (int rc = launch_single2d(st, pt, kind, d_data)) return rc;
-        pt->last_path |= IGX_PATH_SINGLE;
-        return IGX_OK;
+        pl.chain = Plan::SINGLE2D;
+        pl.one_launch = true;
+        return;
     }
-    const bool axes3 = fused3_axes(pt, sym);
-    const bool fused = fused_applicable(pt) || axes3;
+    pl.terms = form_terms(dim, kind, &pt->dev);
+    const std::vector<Term> &terms = pl.terms;
+    std::vector<XA> &X = pl.X;
+    std::vector<int> &term_x = pl.term_x;
+    term_x.assign(terms.size(), 0);
+    const bool axes3 = fused3_axes(pt, sym), fused2 = fused_applicable(pt), fused = axes3 || fused2;
+    // the fused stage takes the slot table (input array `a` enters the sweep with mid-axis type t1 and last-axis type y) where a
+    // kernel is compiled for it: k_bf3 (on a twin: where the exchanged-axes store fits), else k_bf2
+    bool slots_ok = true;
+    auto add_slot = [&](int y, int t1, int a) {
+        int &n = pl.slot_n[y][t1];
+        if (n >= 2) slots_ok = false;
+        else pl.slot_arr[y][t1][n++] = a;
+    };
+    auto fused_kernel = [&]() {
+        BFInputs probe{};
+        memcpy(probe.slot_n, pl.slot_n, sizeof(probe.slot_n));
+        probe.sym = sym ? 1 : 0;
+        const Axis &AM = pt->ax[dim - 2], &AL = pt->ax[dim - 1];
+        if (!slots_ok) return Plan::NO_FUSED;
+        if (axes3 && fused3_supported(probe) && (!pt->is_twin || fused3_tr_fits(pt->ax[0].p, AM.p, AL.p, AM.S, AL.S))) return Plan::BF3;
+        return fused2 && fused_supported(probe) ? Plan::BF2 : Plan::NO_FUSED;
+    };
     if (fused && dim == 2) {
         // 2D: the fields ARE the sweep input (axis 0 swept, axis 1 contracted by the contractors): one kernel + mirror
-        BFInputs in{};
-        bool ok = true;
-        for (const Term &t : terms)
-            ok = ok && bf_add_slot(in, kind == IGX_MASS ? 0 : t.t[1], t.t[0], pt->d_fields + (size_t)t.f * pd.npts_loc);
-        in.sym = sym ? 1 : 0;
-        const bool can3 = ok && axes3 && fused3_supported(in), can2 = ok && fused_applicable(pt) && fused_supported(in);
-        if (can3 || can2) {
-            in.slice_stride = 0; in.gmid_lo = pd.g0_lo;
-            stage_event(pt, 1, st);
-            stage_event(pt, 2, st);
-            return run_fused(pt, in, sym, d_data, can3);
+        for (const Term &t : terms) add_slot(kind == IGX_MASS ? 0 : t.t[1], t.t[0], t.f);
+        pl.fused = fused_kernel();
+        if (pl.fused != Plan::NO_FUSED) {
+            pl.chain = Plan::FUSED2D;
+            pl.needs_fields = true;
+            return;
         }
     }
 
     // ---- stage-A arrays X = unique (t0, f).  In 2D the final stage wants the arrays ordered by
     // the last-axis type of their (single) consuming term; in 3D any order works.
-    struct XA { int t0, f, slot, key, xt0, xf, alias; };
-    std::vector<XA> X;
-    std::vector<int> term_x(terms.size());
     // Fused stage with the stage-A kernel (non-symmetric 3D forms): one K1 array per SLOT (last-axis type, mid-axis type) of the
     // sweep, holding the sum of the (at most two) terms of the slot -- the later stages cannot tell them apart.  Fewer arrays
     // than unique (t0, field) pairs when terms collide (convection-diffusion: 9 instead of 11), and one input per slot.
@@ -1224,102 +1073,264 @@ int sumfact_assemble(igx_patch *pt, int kind, double *d_data)
     int nX = 0;                                          // K1 arrays (aliases of the merged slots do not count)
     for (const XA &x : X) nX = std::max(nX, x.slot + 1);
     if (!merged || dim == 2) nX = (int)X.size();
-    // K1 slice stride: padded when both producer (geoA) and consumer (k_bf) take a stride (experiment: IGX_K1PAD doubles)
-    const bool use_geoA = (sym || merged) && geoA_wanted(pt, kind, nX);
-    long long NPLs = NPL;
-#ifdef IGX_ABLATE
-    if (use_geoA && fused && dim == 3) { const char *e = getenv("IGX_K1PAD"); NPLs = NPL + (e ? atoi(e) : 0); }
-#endif
-    if (ensure(st, &pt->d_K1, &pt->K1_cap, (size_t)nX * np0 * NPLs)) return IGX_ERR_NOMEM;
+    pl.merged = merged;
+    pl.nX = nX;
+    pl.geoA = (sym || merged) && geoA_wanted(pt, kind, nX);
+    pl.needs_fields = !pl.geoA;
 
-    const int nF = igx_num_fields(dim, kind, pd.form_n);
+    if (fused && dim == 3) {
+        if (merged)
+            for (const XA &x : X) add_slot(x.key >> 2, x.key & 3, x.slot);
+        else
+            for (size_t i = 0; i < terms.size(); ++i) add_slot(kind == IGX_MASS ? 0 : terms[i].t[2], terms[i].t[1], X[term_x[i]].slot);
+        pl.fused = fused_kernel();
+        if (pl.fused != Plan::NO_FUSED) return;
+    }
+    // ---- final stage: the matrix-core kernel on request (IGX_FINAL=mfma), the quadrature-lane kernel for single interior knots
+    // and q == P on the last axis (instantiated for P <= 6), k_final for everything else
+    const Axis &AL = pt->ax[dim - 1];
+    if (pt->knobs.final_sel == 3 && sym && AL.G >= 2 && ldesc_fits(pt)) {
+        const int W = 2 * AL.P - 1;
+        const int ntile = (AL.N * W + 15) / 16;
+        int wmax = 0;
+        for (int t = 0; t < ntile; ++t) {
+            const int i_first = std::min(AL.N - 1, (t * 16) / W), i_last = std::min(AL.N - 1, (t * 16 + 15) / W);
+            wmax = std::max(wmax, (AL.mshi[i_last] - AL.mslo[i_first]) * AL.q);
+        }
+        pl.mfma_nch = (wmax + 7) / 8;
+        if (pl.mfma_nch >= 1 && pl.mfma_nch <= 6) pl.fin = Plan::FINAL_MFMA;
+    }
+    if (pl.fin != Plan::FINAL_MFMA && pt->knobs.final_sel != 2 && AL.q == AL.P && AL.simple && AL.P <= 6) pl.fin = Plan::FINAL_Q;
+}
+
+// Repeated knots on the last axis only: the patch is assembled through its axis-exchanged twin (igx_internal.h, igx_patch::twin),
+// which serves the kinds whose plan on the twin is k_geoA -> k_bf3 (no field arrays: nobody computes the twin's).  Asked once,
+// when the twin is created.
+int sumfact_twin_kinds(const igx_patch *tw)
+{
+    if (!tw->sumfact_ok) return 0;
+    int kinds = 0;
+    for (const int kind : {IGX_MASS, IGX_STIFFNESS, IGX_CONVDIFF}) {
+        Plan pl;
+        sumfact_plan(tw, kind, pl);
+        if (pl.chain == Plan::STAGES && pl.geoA && pl.fused == Plan::BF3) kinds |= 1 << kind;
+    }
+    return kinds;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The executors: each runs its part of the plan.
+static int run_fused(igx_patch *pt, BFInputs &in, bool sym, double *d_data, bool use3)
+{
+    hipStream_t st = pt->ctx->stream;
+    const int dim = pt->dim;
+    const Axis &A0 = pt->ax[0];
+    in.mid = &pt->ax[dim - 2]; in.last = &pt->ax[dim - 1];
+    in.zeros = pt->d_zeros; in.sym = sym ? 1 : 0;
+    if (dim == 3) { in.rp0 = A0.dev.rp; in.jlo0 = A0.dev.jlo; in.jhi0 = A0.dev.jhi; }
+    else { in.pl0 = pt->d_triv; in.npairs = 1; in.rp0 = pt->d_triv + 2; in.jlo0 = pt->d_triv + 4; in.jhi0 = pt->d_triv + 5; }
+    int i1_lo = 0, i1_hi = in.mid->N;
+    if (dim == 3) { in.mid_lo = 0; in.mid_hi = in.mid->N; in.span_hi = in.mid->n; }
+    else {
+        // 2D: the swept axis carries the row slab; symmetric forms also produce the lower entries of the p halo rows
+        // above it (mirror sources), as far as the resident spans reach
+        i1_lo = pt->r0_lo; i1_hi = pt->r0_hi;
+        in.mid_lo = pt->r0_lo; in.mid_hi = sym ? std::min(pt->r0_hi + A0.p, A0.N) : pt->r0_hi; in.span_hi = pt->s0_hi;
+    }
+    // k_bf3 (fused3.hip): symmetric forms get their upper triangle from the same registers as the lower one -- no mirror pass
+    in.tr = pt->is_twin ? 1 : 0;
+    if (pt->is_twin && !use3) { set_error("internal: the axis-exchanged twin of a patch left k_bf3"); return IGX_ERR_UNSUPPORTED; }
+    if (use3) {
+        if (dim == 2 && sym) in.mid_hi = pt->r0_hi;      // (no mirror sources above the slab)
+        if (int rc = launch_bf3(st, pt, in, d_data)) return rc;
+        pt->last_path |= IGX_PATH_FUSED | IGX_PATH_BF3 | (sym ? IGX_PATH_BOTH : 0);
+        pt->timing.n_launches++;
+        stage_event(pt, 3, st);
+        stage_event(pt, 4, st);
+        return IGX_OK;
+    }
+    if (int rc = launch_bf(st, pt, in, d_data)) return rc;
+    pt->last_path |= IGX_PATH_FUSED;
+    pt->timing.n_launches++;
+    stage_event(pt, 3, st);
+#ifdef IGX_ABLATE
+    if (sym && !getenv("IGX_NO_MIRROR")) {
+#else
+    if (sym) {
+#endif
+        MirrorInputs mi{};
+        mi.mid = in.mid; mi.last = in.last; mi.rp0 = in.rp0; mi.jlo0 = in.jlo0; mi.jhi0 = in.jhi0;
+        mi.tpairs = pt->d_tpairs; mi.ntp = pt->ntp; mi.i1_lo = i1_lo; mi.i1_hi = i1_hi;
+        if (int rc = launch_mirror(st, pt, mi, d_data)) return rc;
+        pt->last_path |= IGX_PATH_MIRROR;
+        pt->timing.n_launches++;
+    }
+    stage_event(pt, 4, st);
+    return IGX_OK;
+}
+
+// the inputs of the fused stage: the plan's slot table over the arrays base + a * stride
+static BFInputs bf_inputs(const Plan &pl, const double *base, size_t stride)
+{
+    BFInputs in{};
+    for (int y = 0; y < 4; ++y)
+        for (int t1 = 0; t1 < 4; ++t1) {
+            in.slot_n[y][t1] = pl.slot_n[y][t1];
+            for (int i = 0; i < pl.slot_n[y][t1]; ++i) in.slot_ptr[y][t1][i] = base + (size_t)pl.slot_arr[y][t1][i] * stride;
+        }
+    in.sym = pl.sym ? 1 : 0;
+    return in;
+}
+
+// The mirror pass gathers 72-byte runs all over the CSR values and takes 3.3 - 4.2 ms at C4 depending on where the driver put
+// the 12.75 GB physically -- a property of the BUFFER, stable over its life (DESIGN.md section 4).  A caller that opts in
+// (IGX_PLACEMENT_TRIES) lets the first assembly time the pass on a few candidate buffers and keep the fastest.
+float sumfact_probe_mirror(igx_patch *pt, const Plan &pl, double *buf)
+{
+    if (pl.twin || pl.chain != Plan::STAGES || pl.fused != Plan::BF2 || !pl.sym || pt->ntp == 0) return -1.0f;
+    hipStream_t st = pt->ctx->stream;
+    const Axis &A0 = pt->ax[0];
+    MirrorInputs mi{};
+    mi.mid = &pt->ax[1]; mi.last = &pt->ax[2]; mi.rp0 = A0.dev.rp; mi.jlo0 = A0.dev.jlo; mi.jhi0 = A0.dev.jhi;
+    mi.tpairs = pt->d_tpairs; mi.ntp = pt->ntp; mi.i1_lo = 0; mi.i1_hi = pt->ax[1].N;
+    hipEvent_t *ev = pt->ctx->ev;
+    float best = -1.0f;
+    for (int rep = 0; rep < 3; ++rep) {                  // (the first launch also pages the buffer in)
+        if (hipEventRecord(ev[6], st) != hipSuccess) return -1.0f;
+        if (launch_mirror(st, pt, mi, buf)) return -1.0f;
+        if (hipEventRecord(ev[7], st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1.0f;
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev[6], ev[7]) != hipSuccess) return -1.0f;
+        if (rep > 0 && (best < 0.0f || ms < best)) best = ms;
+    }
+    return best;
+}
+
+// FORM_TABLE: k_geoA<FORM = 2 | 3> -> k_bf3
+static int assemble_form_table(igx_patch *pt, const Plan &pl, double *d_data)
+{
+    const FormPlan &fp = pl.form;
+    hipStream_t st = pt->ctx->stream;
+    const Axis &A0 = pt->ax[0], &A1 = pt->ax[1], &A2 = pt->ax[2];
+    const long long NPL = (long long)A1.G * A2.G;
+    const bool sym = fp.sym;
+    if (!sym && prepare_nonsym(pt)) return IGX_ERR_HIP;
+    const int np0 = sym ? pt->npairs0 : pt->npairs0n;
+    const int *d_pl0 = sym ? pt->d_pl0 : pt->d_pl0n;
+    if (np0 == 0) return IGX_OK;
+    // the entries of the table that are functions: sampled once per patch by the generated coefficient kernel
+    igx_patch::FormTable &T = pt->ftab;
+    const size_t npts = (size_t)pt->dev.npts_loc;
+    if (T.narr > 0 && !pt->ftab_ready) {
+        std::vector<const char *> list((size_t)T.narr, nullptr);
+        for (int k = 0; k < 16; ++k)
+            if (T.arr_of[k] >= 0 && !list[(size_t)T.arr_of[k]]) list[(size_t)T.arr_of[k]] = T.expr[k].c_str();
+        if (!pt->ftab_arr && hipMalloc((void **)&pt->ftab_arr, std::max<size_t>(1, (size_t)T.narr * npts) * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError(); pt->ftab_arr = nullptr;
+            set_error("hipMalloc of %.2f GB for the sampled coefficients of the form failed", T.narr * npts * 8.0 / 1e9);
+            return IGX_ERR_NOMEM;
+        }
+        int hit = 0;
+        if (int rc = launch_form_exprs(st, pt, T.narr, list.data(), pt->ftab_arr, &hit)) return rc;
+        pt->ftab_ready = true;
+    }
+    GeoAForm g = fp.g;
+    for (int k = 0; k < 16; ++k) g.pa[k] = T.arr_of[k] >= 0 ? pt->ftab_arr + (size_t)T.arr_of[k] * npts : nullptr;
+    if (ensure(st, &pt->d_K1, &pt->K1_cap, (size_t)fp.narr * np0 * NPL)) return IGX_ERR_NOMEM;
     stage_event(pt, 1, st);
-    if (use_geoA) {
+    double *so[8];
+    for (int x = 0; x < fp.narr; ++x) so[x] = pt->d_K1 + (size_t)x * np0 * NPL;
+    const SweepChunks ch = sweep_chunks((NPL + 63) / 64, pt->s0_hi - pt->s0_lo, A0.P);
+    if (int rc = launch_geoA(st, pt, IGX_FORM, fp.narr, nullptr, nullptr, so, NPL, ch.len, ch.nchunks, nullptr, nullptr, &g)) return rc;
+    pt->last_path |= IGX_PATH_GEOA;
+    pt->timing.n_launches++;
+    stage_event(pt, 2, st);
+    BFInputs in = bf_inputs(pl, pt->d_K1, (size_t)np0 * NPL);
+    in.pad_stiff3 = fp.mass_only ? 0 : 1;
+    if (!fused3_supported(in)) { set_error("internal: the slots of the form do not fit the fused stage"); return IGX_ERR_UNSUPPORTED; }
+    in.slice_stride = NPL; in.gmid_lo = 0; in.pl0 = d_pl0; in.npairs = np0;
+    return run_fused(pt, in, sym, d_data, true);
+}
+
+// stage 0 of the stage chain: the axis-0 sweep into the K1 arrays
+static int run_stage0(igx_patch *pt, const Plan &pl, int np0, long long NPL, long long NPLs)
+{
+    hipStream_t st = pt->ctx->stream;
+    const int dim = pt->dim;
+    const bool sym = pl.sym;
+    const Axis &A0 = pt->ax[0];
+    const PatchDev &pd = pt->dev;
+    const std::vector<XA> &X = pl.X;
+    if (pl.geoA) {
         // geometry evaluated inside the sweep: no field arrays (geoa.hip)
         int sf[8], stp[8], sxf[8], sxt[8];
         double *so[8];
         for (const XA &xa : X) {
             if (xa.alias) continue;                      // (merged slots with identical sources share one array)
-            const int x = merged ? xa.slot : (int)(&xa - X.data());
+            const int x = pl.merged ? xa.slot : (int)(&xa - X.data());
             sf[x] = xa.f; stp[x] = xa.t0; sxf[x] = xa.xf; sxt[x] = xa.xt0 < 0 ? 0 : xa.xt0;
             so[x] = pt->d_K1 + (size_t)xa.slot * np0 * NPLs;
         }
         const SweepChunks ch = sweep_chunks((NPL + 63) / 64, pt->s0_hi - pt->s0_lo, A0.P, dim == 2 ? geoa2d_min_chunk(A0.P) : 0);
-        int rc = launch_geoA(st, pt, kind, nX, sf, stp, so, NPLs, ch.len, ch.nchunks, sxf, sxt);
-        if (rc) return rc;
+        if (int rc = launch_geoA(st, pt, pl.kind, pl.nX, sf, stp, so, NPLs, ch.len, ch.nchunks, sxf, sxt)) return rc;
         pt->last_path |= IGX_PATH_GEOA;
         pt->timing.n_launches++;
-    } else
-    // one launch for all fields (blockIdx.y); the types of a field share the field load
-    {
-        StageAArgs A{};
-        int ng = 0;
-        const bool one_type = !sym && A0.P >= 5 && A0.q == A0.P;      // register budget of the full pair window (k_stageA)
-        for (int f = 0; f < nF; ++f) {
-            StageAGroup g{};
-            for (size_t x = 0; x < X.size(); ++x)
-                if (X[x].f == f && !X[x].alias) {
-                    if (g.nt == 2) { set_error("internal: more than two stage-A types per field"); return IGX_ERR_UNSUPPORTED; }
-                    double *o = pt->d_K1 + (size_t)X[x].slot * np0 * NPL;
-                    if (g.nt == 0) { g.t0 = X[x].t0; g.out0 = o; } else { g.t1 = X[x].t0; g.out1 = o; }
-                    if (X[x].xf >= 0) { g.xfield[g.nt] = pt->d_fields + (size_t)X[x].xf * pd.npts_loc; g.xt[g.nt] = X[x].xt0; }
-                    g.nt++;
-                }
-            if (g.nt == 0) continue;
-            g.field = pt->d_fields + (size_t)f * pd.npts_loc;
-            if (one_type && g.nt == 2) {                 // two groups of one type each (see k_stageA)
-                StageAGroup g1 = g;
-                g1.t0 = g.t1; g1.out0 = g.out1; g1.xfield[0] = g.xfield[1]; g1.xt[0] = g.xt[1];
-                g1.nt = g.nt = 1; g1.xfield[1] = g.xfield[1] = nullptr;
-                if (ng >= 15) { set_error("internal: too many stage-A groups"); return IGX_ERR_UNSUPPORTED; }
-                A.grp[ng++] = g1;
+        return IGX_OK;
+    }
+    // k_stageA: one launch for all fields (blockIdx.y); the types of a field share the field load
+    const int nF = igx_num_fields(dim, pl.kind, pd.form_n);
+    StageAArgs A{};
+    int ng = 0;
+    const bool one_type = !sym && A0.P >= 5 && A0.q == A0.P;      // register budget of the full pair window (k_stageA)
+    for (int f = 0; f < nF; ++f) {
+        StageAGroup g{};
+        for (size_t x = 0; x < X.size(); ++x)
+            if (X[x].f == f && !X[x].alias) {
+                if (g.nt == 2) { set_error("internal: more than two stage-A types per field"); return IGX_ERR_UNSUPPORTED; }
+                double *o = pt->d_K1 + (size_t)X[x].slot * np0 * NPL;
+                if (g.nt == 0) { g.t0 = X[x].t0; g.out0 = o; } else { g.t1 = X[x].t0; g.out1 = o; }
+                if (X[x].xf >= 0) { g.xfield[g.nt] = pt->d_fields + (size_t)X[x].xf * pd.npts_loc; g.xt[g.nt] = X[x].xt0; }
+                g.nt++;
             }
-            if (ng >= 16) { set_error("internal: too many stage-A groups"); return IGX_ERR_UNSUPPORTED; }
-            A.grp[ng++] = g;
+        if (g.nt == 0) continue;
+        g.field = pt->d_fields + (size_t)f * pd.npts_loc;
+        if (one_type && g.nt == 2) {                     // two groups of one type each (see k_stageA)
+            StageAGroup g1 = g;
+            g1.t0 = g.t1; g1.out0 = g.out1; g1.xfield[0] = g.xfield[1]; g1.xt[0] = g.xt[1];
+            g1.nt = g.nt = 1; g1.xfield[1] = g.xfield[1] = nullptr;
+            if (ng >= 15) { set_error("internal: too many stage-A groups"); return IGX_ERR_UNSUPPORTED; }
+            A.grp[ng++] = g1;
         }
-        A.PI0 = A0.d_PI; A.step_ptr = pt->stepA_ptr; A.steps = sym ? pt->stepA_rec : pt->d_stepsn;
-        A.s_lo = pt->s0_lo; A.s_hi = pt->s0_hi; A.n0 = A0.n; A.N0 = A0.N; A.q = A0.q; A.g0_lo = pd.g0_lo;
-        A.NPL = NPL;
-        const int bsA = 256;
-        const long long bx = (NPL + bsA - 1) / bsA;
-        const SweepChunks ch = sweep_chunks(bx * ng, pt->s0_hi - pt->s0_lo, A0.P, dim == 2 ? A0.P : 0);
-        A.chunk_len = ch.len;
-        const size_t ldsA = (size_t)2 * A0.q * 4 * ((A0.P * A0.P + 1) & ~1) * sizeof(double);
-        if ((size_t)A0.q * 4 * A0.P * A0.P > (size_t)SWEEP_MAX_STAGE * bsA) { set_error("stage A: coefficient slice too large"); return IGX_ERR_UNSUPPORTED; }
-        dim3 block(bsA), grid((unsigned)bx, ng, ch.nchunks);
-        if (A0.P >= 7) stageA_hi(A0.P, st, A, A0.q == A0.P, sym, one_type, dim == 2, grid, block, ldsA);
-        else DISPATCH_P(A0.P, launch_stageA<PP>(st, A, A0.q == A0.P, sym, one_type, dim == 2, grid, block, ldsA));
-        IGX_HIP(hipGetLastError());
-        pt->timing.n_launches++;
+        if (ng >= 16) { set_error("internal: too many stage-A groups"); return IGX_ERR_UNSUPPORTED; }
+        A.grp[ng++] = g;
     }
-    stage_event(pt, 2, st);
+    A.PI0 = A0.d_PI; A.step_ptr = pt->stepA_ptr; A.steps = sym ? pt->stepA_rec : pt->d_stepsn;
+    A.s_lo = pt->s0_lo; A.s_hi = pt->s0_hi; A.n0 = A0.n; A.N0 = A0.N; A.q = A0.q; A.g0_lo = pd.g0_lo;
+    A.NPL = NPL;
+    const int bsA = 256;
+    const long long bx = (NPL + bsA - 1) / bsA;
+    const SweepChunks ch = sweep_chunks(bx * ng, pt->s0_hi - pt->s0_lo, A0.P, dim == 2 ? A0.P : 0);
+    A.chunk_len = ch.len;
+    const size_t ldsA = (size_t)2 * A0.q * 4 * ((A0.P * A0.P + 1) & ~1) * sizeof(double);
+    if ((size_t)A0.q * 4 * A0.P * A0.P > (size_t)SWEEP_MAX_STAGE * bsA) { set_error("stage A: coefficient slice too large"); return IGX_ERR_UNSUPPORTED; }
+    dim3 block(bsA), grid((unsigned)bx, ng, ch.nchunks);
+    if (A0.P >= 7) stageA_hi(A0.P, st, A, A0.q == A0.P, sym, one_type, dim == 2, grid, block, ldsA);
+    else DISPATCH_P(A0.P, launch_stageA<PP>(st, A, A0.q == A0.P, sym, one_type, dim == 2, grid, block, ldsA));
+    IGX_HIP(hipGetLastError());
+    pt->timing.n_launches++;
+    return IGX_OK;
+}
 
-    if (fused && dim == 3) {
-        BFInputs in{};
-        bool ok = true;
-        if (merged) {
-            for (const XA &x : X) ok = ok && bf_add_slot(in, x.key >> 2, x.key & 3, pt->d_K1 + (size_t)x.slot * np0 * NPLs);
-        } else
-        for (size_t i = 0; i < terms.size(); ++i)
-            ok = ok && bf_add_slot(in, kind == IGX_MASS ? 0 : terms[i].t[2], terms[i].t[1],
-                                   pt->d_K1 + (size_t)X[term_x[i]].slot * np0 * NPLs);
-        in.sym = sym ? 1 : 0;
-        const bool can3 = ok && axes3 && fused3_supported(in), can2 = ok && fused_applicable(pt) && fused_supported(in);
-        if (can3 || can2) {
-            in.slice_stride = NPLs; in.gmid_lo = 0; in.pl0 = d_pl0; in.npairs = np0;
-            return run_fused(pt, in, sym, d_data, can3);
-        }
-    }
-    if (pt->is_twin) { set_error("internal: the axis-exchanged twin of a patch left the fused chain"); return IGX_ERR_UNSUPPORTED; }
-
-    if (int rc = ensure_line_descriptors(pt)) return rc;
-    // ---- final-stage input
-    FinalArgs F{};
-    const Axis &AL = (dim == 3) ? A2 : A1;
-    int NY;
-    const double *Kfinal = nullptr;
-    long long ngroups = 0;
-    if (dim == 3) {
+// the input of the final stage: K2 from stage B (3D), the stage-A arrays summed per last-axis type (2D general forms) or K1 itself
+static int run_mid(igx_patch *pt, const Plan &pl, int np0, const int *d_pl0, long long NPL, FinalArgs &F, const double *&Kfinal, int &NY)
+{
+    hipStream_t st = pt->ctx->stream;
+    const int kind = pl.kind;
+    const Axis &A1 = pt->ax[1], &A2 = pt->ax[2];
+    const std::vector<Term> &terms = pl.terms;
+    const std::vector<XA> &X = pl.X;
+    const std::vector<int> &term_x = pl.term_x;
+    if (pt->dim == 3) {
         // stage B groups by the last-axis type y = t2
         StageBArgs B{};
         int ymax = 0;
@@ -1339,7 +1350,7 @@ int sumfact_assemble(igx_patch *pt, int kind, double *d_data)
             if (B.grp[y].nterm == 0)
                 IGX_HIP(hipMemsetAsync(pt->d_K2 + (size_t)y * np0 * A1.S * A2.G, 0, (size_t)np0 * A1.S * A2.G * sizeof(double), st));
         B.PI1 = A1.d_PI;
-        B.step_ptr = pt->stepB_ptr; B.steps = pt->stepB_rec; B.pl0 = d_pl0; B.symmetric = sym;
+        B.step_ptr = pt->stepB_ptr; B.steps = pt->stepB_rec; B.pl0 = d_pl0; B.symmetric = pl.sym;
         B.n1 = A1.n; B.N1 = A1.N; B.q = A1.q; B.G1 = A1.G; B.G2 = A2.G; B.S1 = A1.S; B.npairs0 = np0;
         const int bs = A1.P >= 7 ? 256 : 128;            // (a span's coefficient slice is staged by the block: q * 4 * P * P values)
         const long long bxB = (A2.G + bs - 1) / bs;
@@ -1356,36 +1367,45 @@ int sumfact_assemble(igx_patch *pt, int kind, double *d_data)
         Kfinal = pt->d_K2;
         F.nlines = (long long)np0 * A1.S;
         F.N1 = A1.N; F.S1 = A1.S; F.Smid = A1.S; F.Slast = A2.S;
-        ngroups = (long long)np0 * A1.N;
-    } else {
-        NY = (kind == IGX_MASS) ? 1 : 4;
-        Kfinal = pt->d_K1;
-        if (kind == IGX_FORM) {
-            // general 2D form: several terms share a last-axis type; their stage-A arrays are summed into the
-            // array of that type (2D intermediates are small: one extra pass over them)
-            int ymax = 0;
-            for (const Term &t : terms) ymax = std::max(ymax, t.t[1]);
-            NY = (ymax == 0) ? 1 : 4;
-            const size_t per = (size_t)np0 * NPL;
-            if (ensure(st, &pt->d_K2, &pt->K2_cap, (size_t)NY * per)) return IGX_ERR_NOMEM;
-            for (int y = 0; y < NY; ++y) {
-                CombineArgs C{};
-                for (size_t i = 0; i < terms.size(); ++i)
-                    if (terms[i].t[1] == y) C.src[C.n++] = pt->d_K1 + (size_t)X[term_x[i]].slot * per;
-                C.dst = pt->d_K2 + (size_t)y * per;
-                C.len = (long long)per;
-                k_combine<<<dim3((unsigned)std::min<size_t>((per + 255) / 256, 65535u * 16u)), 256, 0, st>>>(C);
-            }
-            IGX_HIP(hipGetLastError());
-            pt->timing.n_launches += NY;
-            Kfinal = pt->d_K2;
-        }
-        F.nlines = np0;
-        F.N1 = 1; F.S1 = 1; F.Smid = 1; F.Slast = A1.S;
-        ngroups = np0;
+        F.ngroups = (long long)np0 * A1.N;
+        return IGX_OK;
     }
-    stage_event(pt, 3, st);
+    NY = (kind == IGX_MASS) ? 1 : 4;
+    Kfinal = pt->d_K1;
+    if (kind == IGX_FORM) {
+        // general 2D form: several terms share a last-axis type; their stage-A arrays are summed into the
+        // array of that type (2D intermediates are small: one extra pass over them)
+        int ymax = 0;
+        for (const Term &t : terms) ymax = std::max(ymax, t.t[1]);
+        NY = (ymax == 0) ? 1 : 4;
+        const size_t per = (size_t)np0 * NPL;
+        if (ensure(st, &pt->d_K2, &pt->K2_cap, (size_t)NY * per)) return IGX_ERR_NOMEM;
+        for (int y = 0; y < NY; ++y) {
+            CombineArgs C{};
+            for (size_t i = 0; i < terms.size(); ++i)
+                if (terms[i].t[1] == y) C.src[C.n++] = pt->d_K1 + (size_t)X[term_x[i]].slot * per;
+            C.dst = pt->d_K2 + (size_t)y * per;
+            C.len = (long long)per;
+            k_combine<<<dim3((unsigned)std::min<size_t>((per + 255) / 256, 65535u * 16u)), 256, 0, st>>>(C);
+        }
+        IGX_HIP(hipGetLastError());
+        pt->timing.n_launches += NY;
+        Kfinal = pt->d_K2;
+    }
+    F.nlines = np0;
+    F.N1 = 1; F.S1 = 1; F.Smid = 1; F.Slast = A1.S;
+    F.ngroups = np0;
+    return IGX_OK;
+}
 
+// the final stage: contraction of the last axis into the CSR values
+static int run_final(igx_patch *pt, const Plan &pl, const int *d_pl0, FinalArgs &F, const double *Kfinal, int NY, double *d_data)
+{
+    hipStream_t st = pt->ctx->stream;
+    const int dim = pt->dim;
+    const bool sym = pl.sym;
+    const Axis &A0 = pt->ax[0], &A1 = pt->ax[1];
+    const Axis &AL = pt->ax[dim - 1];
     F.V = AL.d_V; F.fa = AL.dev.fa; F.mslo = AL.dev.mslo; F.mshi = AL.dev.mshi;
     F.jlo = AL.dev.jlo; F.jhi = AL.dev.jhi; F.rp = AL.dev.rp;
     F.N = AL.N; F.q = AL.q; F.G = AL.G;
@@ -1393,155 +1413,202 @@ int sumfact_assemble(igx_patch *pt, int kind, double *d_data)
     F.rp0 = A0.dev.rp; F.jlo0 = A0.dev.jlo; F.jhi0 = A0.dev.jhi;
     F.rp1 = A1.dev.rp; F.jlo1 = A1.dev.jlo; F.jhi1 = A1.dev.jhi;
     F.r0_lo = pt->r0_lo; F.r0_hi = pt->r0_hi; F.nnz_off = pt->nnz_off;
-    {
+    if (pl.fin == Plan::FINAL_MFMA) {
         // ---- matrix-core path (opt-in, IGX_FINAL=mfma): banded FP64 GEMM, see k_final_mfma.  Correct and
         // tested, but at 2 waves/SIMD its load->MFMA loop is latency-bound (MFMA pipe 25 % busy,
         // 13.7 ms vs 11.0 ms for the VALU kernel at C4); it needs an LDS-DMA staged A operand to pay off.
-        {
-            const int W = 2 * AL.P - 1;
-            const int ntile = (AL.N * W + 15) / 16;
-            int wmax = 0;
-            for (int t = 0; t < ntile; ++t) {
-                const int i_first = std::min(AL.N - 1, (t * 16) / W), i_last = std::min(AL.N - 1, (t * 16 + 15) / W);
-                wmax = std::max(wmax, (AL.mshi[i_last] - AL.mslo[i_first]) * AL.q);
-            }
-            const int nch = (wmax + 7) / 8;
-            const bool want_mfma = pt->knobs.final_sel == 3;
-            if (want_mfma && sym && nch >= 1 && nch <= 6 && pt->ldesc_ok && AL.G >= 2) {
-                FinalMArgs M{};
-                M.desc = (const int4 *)pt->d_ldesc; M.nl = pt->n_ldesc; M.nlines = F.nlines;
-                M.V = AL.d_V; M.fa = AL.dev.fa; M.mslo = AL.dev.mslo; M.mshi = AL.dev.mshi;
-                M.jlo = AL.dev.jlo; M.jhi = AL.dev.jhi; M.rp = AL.dev.rp;
-                M.N = AL.N; M.P = AL.P; M.q = AL.q; M.G = AL.G; M.W = W; M.ntile = ntile;
-                int LC = 256;
-#ifdef IGX_ABLATE
-                if (const char *e = getenv("IGX_FINAL_LC")) LC = std::max(16, (atoi(e) / 16) * 16);
-#endif
-                M.LC = LC; M.debug = 0;
-                M.nchunk_blocks = (M.nl + LC - 1) / LC;
-                const long long nblocks = (long long)((ntile + 3) / 4) * M.nchunk_blocks;
-                if (nblocks > 0x7fffffffLL) { set_error("final stage: too many blocks"); return IGX_ERR_UNSUPPORTED; }
-                dim3 block(256), grid((unsigned)nblocks);
-#define LAUNCH_M(NYV, NCHV) k_final_mfma<NYV, NCHV><<<grid, block, 0, st>>>(Kfinal, d_data, M)
-                if (NY == 1) {
-                    switch (nch) { case 1: LAUNCH_M(1, 1); break; case 2: LAUNCH_M(1, 2); break; case 3: LAUNCH_M(1, 3); break;
-                                   case 4: LAUNCH_M(1, 4); break; case 5: LAUNCH_M(1, 5); break; default: LAUNCH_M(1, 6); break; }
-                } else {
-                    switch (nch) { case 1: LAUNCH_M(4, 1); break; case 2: LAUNCH_M(4, 2); break; case 3: LAUNCH_M(4, 3); break;
-                                   case 4: LAUNCH_M(4, 4); break; case 5: LAUNCH_M(4, 5); break; default: LAUNCH_M(4, 6); break; }
-                }
-#undef LAUNCH_M
-                IGX_HIP(hipGetLastError());
-                pt->timing.n_launches++;
-                stage_event(pt, 4, st);
-                return IGX_OK;
-            }
-        }
-        // ---- quadrature-lane kernel: single interior knots and q == P on the last axis
-        {
-            const bool want_q = pt->knobs.final_sel != 2;
-            if (want_q && AL.q == AL.P && AL.simple && AL.P <= 6) {       // (k_final_q is instantiated for P <= 6: higher degrees take k_final)
-                FinalQArgs Q{};
-                Q.V = AL.d_V; Q.fa = AL.dev.fa; Q.mslo = AL.dev.mslo; Q.mshi = AL.dev.mshi;
-                Q.jlo = AL.dev.jlo; Q.jhi = AL.dev.jhi; Q.rp = AL.dev.rp;
-                Q.N = AL.N; Q.G = AL.G; Q.nlines = F.nlines;
-                Q.desc = (const LineDesc *)(sym ? pt->d_qdesc : pt->d_qdescn);
-                Q.ndesc = sym ? pt->n_qdesc : pt->n_qdescn;
-                Q.dump = pt->nnz;
-                const int R = 64 / AL.P;
-                Q.nchunks = (AL.N + R - 1) / R;
-                // ~8 waves per CU and a few rounds; at least 16 lines per wave to amortise its set-up
-                long long target_waves = 8192;
-#ifdef IGX_ABLATE
-                if (const char *e = getenv("IGX_FINALQ_WAVES")) target_waves = std::max(1, atoi(e));
-#endif
-                Q.nsuper = (Q.nchunks + FINALQ_WAVES - 1) / FINALQ_WAVES;
-                Q.lpw = (int)std::max<long long>(16, (Q.ndesc * Q.nsuper * FINALQ_WAVES + target_waves - 1) / target_waves);
-                // a launch of less than one resident round (2 blocks per CU: a 2D patch): as few lines per wave as one
-                // round allows -- the lines of a wave are worked through in sequence
-                const long long slots = 2 * 256, per_super = slots / Q.nsuper;
-                if (per_super > 0 && ((Q.ndesc + 15) / 16) * Q.nsuper <= slots)
-                    Q.lpw = (int)std::max<long long>(4, (Q.ndesc + per_super - 1) / per_super);
-                const long long nblocks = ((Q.ndesc + Q.lpw - 1) / Q.lpw) * Q.nsuper;
-                if (nblocks > 0x7fffffffLL) { set_error("final stage: too many blocks"); return IGX_ERR_UNSUPPORTED; }
-                dim3 block(64 * FINALQ_WAVES), grid((unsigned)nblocks);
-#define LAUNCH_Q(PV) { if (NY == 1) k_final_q<PV, 1><<<grid, block, 0, st>>>(Kfinal, d_data, Q); \
-                       else k_final_q<PV, 4><<<grid, block, 0, st>>>(Kfinal, d_data, Q); }
-                switch (AL.P) {
-                case 2: LAUNCH_Q(2); break;
-                case 3: LAUNCH_Q(3); break;
-                case 4: LAUNCH_Q(4); break;
-                case 5: LAUNCH_Q(5); break;
-                default: LAUNCH_Q(6); break;
-                }
-#undef LAUNCH_Q
-                IGX_HIP(hipGetLastError());
-                pt->timing.n_launches++;
-                stage_event(pt, 4, st);
-                return IGX_OK;
-            }
-        }
-        // wave tasks: chunks of CR <= 64 consecutive rows; NW waves share the staged basis-table
-        // segment of a row tile (the whole axis when it fits in ~64 KB of LDS)
         const int W = 2 * AL.P - 1;
-        F.SSTR = (AL.q * AL.P * 2) | 1;
-        F.KSTR = AL.q | 1;
-        int ntiles = 1, tile_rows, CR, tsp_max, trow_max, nsp_max;
-        // rows per wave task: at most 64 (one lane per row), and few enough that the K window of the task -- the Gauss points
-        // under its rows: (rows + p) spans with single knots -- fits the 8 x 64 prefetch slots (degree 7 with q = 8: 56 rows)
-        const int crmax = std::max(1, std::min(64, 512 / std::max(AL.q, 1) - AL.p));
-        for (;; ++ntiles) {
-            const int rows_per_tile = (AL.N + ntiles - 1) / ntiles;
-            const int nch = (rows_per_tile + crmax - 1) / crmax;
-            CR = (rows_per_tile + nch - 1) / nch;
-            tile_rows = CR * nch;
-            tsp_max = trow_max = nsp_max = 0;
-            for (int lo = 0; lo < AL.N; lo += tile_rows) {
-                const int hi = std::min(lo + tile_rows, AL.N);
-                tsp_max = std::max(tsp_max, AL.mshi[hi - 1] - AL.mslo[lo]);
-                trow_max = std::max(trow_max, AL.jhi[hi - 1] - AL.jlo[lo]);
-                for (int cl = lo; cl < hi; cl += CR)
-                    nsp_max = std::max(nsp_max, AL.mshi[std::min(cl + CR, hi) - 1] - AL.mslo[cl]);
-            }
-            if ((size_t)tsp_max * F.SSTR * sizeof(double) <= 64 * 1024 || tile_rows <= crmax) break;
-        }
-        ntiles = (AL.N + tile_rows - 1) / tile_rows;
-        const int kpy = (nsp_max * AL.q + 63) / 64;
-        if (kpy > 8) { set_error("final stage: K window does not fit the prefetch registers"); return IGX_ERR_UNSUPPORTED; }
-        F.CR = CR; F.tile_rows = tile_rows; F.ntiles = ntiles; F.tsp_max = tsp_max; F.trow_max = trow_max;
-        F.nsp_max = nsp_max; F.ngroups = ngroups;
-        const size_t vbytes = (size_t)tsp_max * F.SSTR * sizeof(double);
-        const size_t kslot = std::max((size_t)NY * nsp_max * F.KSTR, (size_t)CR * W) * sizeof(double);
-        const size_t tbytes = ((size_t)5 * trow_max + tsp_max) * sizeof(int);
-        if (vbytes + kslot + tbytes > 160 * 1024) { set_error("final stage: basis table segment (%zu B) does not fit LDS", vbytes); return IGX_ERR_UNSUPPORTED; }
-        const bool fast = AL.q == AL.P && AL.simple && AL.P < 7;      // (P >= 7: generic instantiation only, launch_final)
-        const int max_waves = fast ? 12 : 6;
-        int NW = (int)std::min<size_t>(max_waves, (160 * 1024 - vbytes - tbytes) / kslot);
+        const int ntile = (AL.N * W + 15) / 16;
+        FinalMArgs M{};
+        M.desc = (const int4 *)pt->d_ldesc; M.nl = pt->n_ldesc; M.nlines = F.nlines;
+        M.V = AL.d_V; M.fa = AL.dev.fa; M.mslo = AL.dev.mslo; M.mshi = AL.dev.mshi;
+        M.jlo = AL.dev.jlo; M.jhi = AL.dev.jhi; M.rp = AL.dev.rp;
+        M.N = AL.N; M.P = AL.P; M.q = AL.q; M.G = AL.G; M.W = W; M.ntile = ntile;
+        int LC = 256;
 #ifdef IGX_ABLATE
-        if (const char *e = getenv("IGX_FINAL_NW")) NW = std::max(1, std::min(NW, atoi(e)));
+        if (const char *e = getenv("IGX_FINAL_LC")) LC = std::max(16, (atoi(e) / 16) * 16);
 #endif
-        int max_lines = 1;
-        if (dim == 3)
-            for (int i = 0; i < A1.N; ++i) max_lines = std::max(max_lines, A1.jhi[i] - A1.jlo[i]);
-        // row groups per block: enough tasks for ~8 rounds per wave
-        int GPB = std::max(1, (8 * NW) / std::max(1, max_lines * (tile_rows / CR)));
-#ifdef IGX_ABLATE
-        if (const char *e = getenv("IGX_FINAL_GPB")) GPB = std::max(1, atoi(e));
-#endif
-        F.NW = NW; F.GPB = GPB;
-        const size_t lds = vbytes + (size_t)NW * kslot + tbytes;
-        const long long nblocks = ((ngroups + GPB - 1) / GPB) * ntiles;
+        M.LC = LC; M.debug = 0;
+        M.nchunk_blocks = (M.nl + LC - 1) / LC;
+        const long long nblocks = (long long)((ntile + 3) / 4) * M.nchunk_blocks;
         if (nblocks > 0x7fffffffLL) { set_error("final stage: too many blocks"); return IGX_ERR_UNSUPPORTED; }
-        dim3 block(64 * NW), grid((unsigned)nblocks);
-        int rc = IGX_OK;
-        if (AL.P >= 7) rc = final_hi(AL.P, st, Kfinal, d_data, F, NY, fast, kpy, grid, block, lds);
-        else DISPATCH_P(AL.P, rc = launch_final<PP>(st, Kfinal, d_data, F, NY, fast, kpy, grid, block, lds));
-        if (rc) return rc;
+        dim3 block(256), grid((unsigned)nblocks);
+#define LAUNCH_M(NYV, NCHV) k_final_mfma<NYV, NCHV><<<grid, block, 0, st>>>(Kfinal, d_data, M)
+        if (NY == 1) {
+            switch (pl.mfma_nch) { case 1: LAUNCH_M(1, 1); break; case 2: LAUNCH_M(1, 2); break; case 3: LAUNCH_M(1, 3); break;
+                                   case 4: LAUNCH_M(1, 4); break; case 5: LAUNCH_M(1, 5); break; default: LAUNCH_M(1, 6); break; }
+        } else {
+            switch (pl.mfma_nch) { case 1: LAUNCH_M(4, 1); break; case 2: LAUNCH_M(4, 2); break; case 3: LAUNCH_M(4, 3); break;
+                                   case 4: LAUNCH_M(4, 4); break; case 5: LAUNCH_M(4, 5); break; default: LAUNCH_M(4, 6); break; }
+        }
+#undef LAUNCH_M
         IGX_HIP(hipGetLastError());
         pt->timing.n_launches++;
+        return IGX_OK;
     }
+    if (pl.fin == Plan::FINAL_Q) {
+        // ---- quadrature-lane kernel: single interior knots and q == P on the last axis
+        FinalQArgs Q{};
+        Q.V = AL.d_V; Q.fa = AL.dev.fa; Q.mslo = AL.dev.mslo; Q.mshi = AL.dev.mshi;
+        Q.jlo = AL.dev.jlo; Q.jhi = AL.dev.jhi; Q.rp = AL.dev.rp;
+        Q.N = AL.N; Q.G = AL.G; Q.nlines = F.nlines;
+        Q.desc = (const LineDesc *)(sym ? pt->d_qdesc : pt->d_qdescn);
+        Q.ndesc = sym ? pt->n_qdesc : pt->n_qdescn;
+        Q.dump = pt->nnz;
+        const int R = 64 / AL.P;
+        Q.nchunks = (AL.N + R - 1) / R;
+        // ~8 waves per CU and a few rounds; at least 16 lines per wave to amortise its set-up
+        long long target_waves = 8192;
+#ifdef IGX_ABLATE
+        if (const char *e = getenv("IGX_FINALQ_WAVES")) target_waves = std::max(1, atoi(e));
+#endif
+        Q.nsuper = (Q.nchunks + FINALQ_WAVES - 1) / FINALQ_WAVES;
+        Q.lpw = (int)std::max<long long>(16, (Q.ndesc * Q.nsuper * FINALQ_WAVES + target_waves - 1) / target_waves);
+        // a launch of less than one resident round (2 blocks per CU: a 2D patch): as few lines per wave as one
+        // round allows -- the lines of a wave are worked through in sequence
+        const long long slots = 2 * 256, per_super = slots / Q.nsuper;
+        if (per_super > 0 && ((Q.ndesc + 15) / 16) * Q.nsuper <= slots)
+            Q.lpw = (int)std::max<long long>(4, (Q.ndesc + per_super - 1) / per_super);
+        const long long nblocks = ((Q.ndesc + Q.lpw - 1) / Q.lpw) * Q.nsuper;
+        if (nblocks > 0x7fffffffLL) { set_error("final stage: too many blocks"); return IGX_ERR_UNSUPPORTED; }
+        dim3 block(64 * FINALQ_WAVES), grid((unsigned)nblocks);
+#define LAUNCH_Q(PV) { if (NY == 1) k_final_q<PV, 1><<<grid, block, 0, st>>>(Kfinal, d_data, Q); \
+                       else k_final_q<PV, 4><<<grid, block, 0, st>>>(Kfinal, d_data, Q); }
+        switch (AL.P) {
+        case 2: LAUNCH_Q(2); break;
+        case 3: LAUNCH_Q(3); break;
+        case 4: LAUNCH_Q(4); break;
+        case 5: LAUNCH_Q(5); break;
+        default: LAUNCH_Q(6); break;
+        }
+#undef LAUNCH_Q
+        IGX_HIP(hipGetLastError());
+        pt->timing.n_launches++;
+        return IGX_OK;
+    }
+    // wave tasks: chunks of CR <= 64 consecutive rows; NW waves share the staged basis-table
+    // segment of a row tile (the whole axis when it fits in ~64 KB of LDS)
+    const int W = 2 * AL.P - 1;
+    F.SSTR = (AL.q * AL.P * 2) | 1;
+    F.KSTR = AL.q | 1;
+    int ntiles = 1, tile_rows, CR, tsp_max, trow_max, nsp_max;
+    // rows per wave task: at most 64 (one lane per row), and few enough that the K window of the task -- the Gauss points
+    // under its rows: (rows + p) spans with single knots -- fits the 8 x 64 prefetch slots (degree 7 with q = 8: 56 rows)
+    const int crmax = std::max(1, std::min(64, 512 / std::max(AL.q, 1) - AL.p));
+    for (;; ++ntiles) {
+        const int rows_per_tile = (AL.N + ntiles - 1) / ntiles;
+        const int nch = (rows_per_tile + crmax - 1) / crmax;
+        CR = (rows_per_tile + nch - 1) / nch;
+        tile_rows = CR * nch;
+        tsp_max = trow_max = nsp_max = 0;
+        for (int lo = 0; lo < AL.N; lo += tile_rows) {
+            const int hi = std::min(lo + tile_rows, AL.N);
+            tsp_max = std::max(tsp_max, AL.mshi[hi - 1] - AL.mslo[lo]);
+            trow_max = std::max(trow_max, AL.jhi[hi - 1] - AL.jlo[lo]);
+            for (int cl = lo; cl < hi; cl += CR)
+                nsp_max = std::max(nsp_max, AL.mshi[std::min(cl + CR, hi) - 1] - AL.mslo[cl]);
+        }
+        if ((size_t)tsp_max * F.SSTR * sizeof(double) <= 64 * 1024 || tile_rows <= crmax) break;
+    }
+    ntiles = (AL.N + tile_rows - 1) / tile_rows;
+    const int kpy = (nsp_max * AL.q + 63) / 64;
+    if (kpy > 8) { set_error("final stage: K window does not fit the prefetch registers"); return IGX_ERR_UNSUPPORTED; }
+    F.CR = CR; F.tile_rows = tile_rows; F.ntiles = ntiles; F.tsp_max = tsp_max; F.trow_max = trow_max;
+    F.nsp_max = nsp_max;
+    const size_t vbytes = (size_t)tsp_max * F.SSTR * sizeof(double);
+    const size_t kslot = std::max((size_t)NY * nsp_max * F.KSTR, (size_t)CR * W) * sizeof(double);
+    const size_t tbytes = ((size_t)5 * trow_max + tsp_max) * sizeof(int);
+    if (vbytes + kslot + tbytes > 160 * 1024) { set_error("final stage: basis table segment (%zu B) does not fit LDS", vbytes); return IGX_ERR_UNSUPPORTED; }
+    const bool fast = AL.q == AL.P && AL.simple && AL.P < 7;      // (P >= 7: generic instantiation only, launch_final)
+    const int max_waves = fast ? 12 : 6;
+    int NW = (int)std::min<size_t>(max_waves, (160 * 1024 - vbytes - tbytes) / kslot);
+#ifdef IGX_ABLATE
+    if (const char *e = getenv("IGX_FINAL_NW")) NW = std::max(1, std::min(NW, atoi(e)));
+#endif
+    int max_lines = 1;
+    if (dim == 3)
+        for (int i = 0; i < A1.N; ++i) max_lines = std::max(max_lines, A1.jhi[i] - A1.jlo[i]);
+    // row groups per block: enough tasks for ~8 rounds per wave
+    int GPB = std::max(1, (8 * NW) / std::max(1, max_lines * (tile_rows / CR)));
+#ifdef IGX_ABLATE
+    if (const char *e = getenv("IGX_FINAL_GPB")) GPB = std::max(1, atoi(e));
+#endif
+    F.NW = NW; F.GPB = GPB;
+    const size_t lds = vbytes + (size_t)NW * kslot + tbytes;
+    const long long nblocks = ((F.ngroups + GPB - 1) / GPB) * ntiles;
+    if (nblocks > 0x7fffffffLL) { set_error("final stage: too many blocks"); return IGX_ERR_UNSUPPORTED; }
+    dim3 block(64 * NW), grid((unsigned)nblocks);
+    int rc = IGX_OK;
+    if (AL.P >= 7) rc = final_hi(AL.P, st, Kfinal, d_data, F, NY, fast, kpy, grid, block, lds);
+    else DISPATCH_P(AL.P, rc = launch_final<PP>(st, Kfinal, d_data, F, NY, fast, kpy, grid, block, lds));
+    if (rc) return rc;
+    IGX_HIP(hipGetLastError());
+    pt->timing.n_launches++;
+    return IGX_OK;
+}
+
+// the plan on this patch (a twin's plan on the twin)
+static int run_plan(igx_patch *pt, const Plan &pl, double *d_data)
+{
+    if (pl.chain == Plan::FORM_TABLE) return assemble_form_table(pt, pl, d_data);
+    const bool sym = pl.sym;
+    if (!sym && prepare_nonsym(pt)) return IGX_ERR_HIP;
+    const int np0 = sym ? pt->npairs0 : pt->npairs0n;
+    const int *d_pl0 = sym ? pt->d_pl0 : pt->d_pl0n;
+    if (np0 == 0) return IGX_OK;
+    hipStream_t st = pt->ctx->stream;
+    if (pl.chain == Plan::SINGLE2D) {
+        if (int rc = launch_single2d(st, pt, pl.kind, d_data)) return rc;
+        pt->last_path |= IGX_PATH_SINGLE;
+        return IGX_OK;
+    }
+    if (pl.chain == Plan::FUSED2D) {
+        BFInputs in = bf_inputs(pl, pt->d_fields, (size_t)pt->dev.npts_loc);
+        in.slice_stride = 0; in.gmid_lo = pt->dev.g0_lo;
+        stage_event(pt, 1, st);
+        stage_event(pt, 2, st);
+        return run_fused(pt, in, sym, d_data, pl.fused == Plan::BF3);
+    }
+    // STAGES: stage 0, then the fused stage, or stage B / k_combine and the final stage
+    const Axis &A1 = pt->ax[1], &A2 = pt->ax[2];
+    const long long NPL = (long long)A1.G * (pt->dim == 3 ? A2.G : 1);
+    // K1 slice stride: padded when both producer (geoA) and consumer (k_bf) take a stride (experiment: IGX_K1PAD doubles)
+    long long NPLs = NPL;
+#ifdef IGX_ABLATE
+    if (pl.geoA && pl.fused != Plan::NO_FUSED) { const char *e = getenv("IGX_K1PAD"); NPLs = NPL + (e ? atoi(e) : 0); }
+#endif
+    if (ensure(st, &pt->d_K1, &pt->K1_cap, (size_t)pl.nX * np0 * NPLs)) return IGX_ERR_NOMEM;
+    stage_event(pt, 1, st);
+    if (int rc = run_stage0(pt, pl, np0, NPL, NPLs)) return rc;
+    stage_event(pt, 2, st);
+    if (pl.fused != Plan::NO_FUSED) {
+        BFInputs in = bf_inputs(pl, pt->d_K1, (size_t)np0 * NPLs);
+        in.slice_stride = NPLs; in.gmid_lo = 0; in.pl0 = d_pl0; in.npairs = np0;
+        return run_fused(pt, in, sym, d_data, pl.fused == Plan::BF3);
+    }
+    if (pt->is_twin) { set_error("internal: the axis-exchanged twin of a patch left the fused chain"); return IGX_ERR_UNSUPPORTED; }
+    if (int rc = ensure_line_descriptors(pt)) return rc;
+    FinalArgs F{};
+    const double *Kfinal = nullptr;
+    int NY = 1;
+    if (int rc = run_mid(pt, pl, np0, d_pl0, NPL, F, Kfinal, NY)) return rc;
+    stage_event(pt, 3, st);
+    if (int rc = run_final(pt, pl, d_pl0, F, Kfinal, NY, d_data)) return rc;
     stage_event(pt, 4, st);
     return IGX_OK;
+}
+
+int sumfact_assemble(igx_patch *pt, const Plan &pl, double *d_data)
+{
+    if (!pl.twin) return run_plan(pt, pl, d_data);
+    // repeated knots on the last axis: the twin's chain, values to THIS layout
+    igx_patch *tw = pt->twin;
+    memset(&tw->timing, 0, sizeof(tw->timing));
+    tw->last_path = 0;
+    const int rc = run_plan(tw, pl, d_data);
+    pt->last_path |= tw->last_path | IGX_PATH_TWIN;
+    pt->timing.n_launches += tw->timing.n_launches;
+    return rc;
 }
 
 } // namespace igx
