@@ -403,7 +403,8 @@ int  igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec
    structured layout (no index arrays).  Dirichlet dofs are handled with a dof mask: every vector is full-length with zeros at the
    fixed dofs, and the restricted matrix R A R^T never exists.  The handle does NOT own the patch: the patch must outlive it. */
 typedef struct igx_solver igx_solver;
-enum { IGX_PRECOND_NONE = 0, IGX_PRECOND_JACOBI = 1, IGX_PRECOND_KRON = 2 };
+enum { IGX_PRECOND_NONE = 0, IGX_PRECOND_JACOBI = 1, IGX_PRECOND_KRON = 2,
+       IGX_PRECOND_SCHWARZ = 3 };   /* multipatch solvers only: set up by igx_solver_set_schwarz */
 /* how the per-axis eigenvalues lam_k form the diagonal D of a Kronecker preconditioner  (x)U_k . D^-1 . (x)U_k^T */
 enum { IGX_KRON_SUM = 1,       /* D = sum_k 1 (x) .. (x) lam_k (x) .. (x) 1: fast diagonalization of sum_k K_k (x) M_rest (Sangalli-Tani) */
        IGX_KRON_PRODUCT = 2 }; /* D = (x)_k lam_k: with U_k, lam_k the eigenpairs of M_k this is (x) M_k^-1 */
@@ -422,6 +423,13 @@ typedef struct {
    (ravelled indices; the order of the values given to the solve).  Whole patches only: a row slab or a span box is
    IGX_ERR_UNSUPPORTED.  *out receives the handle (NULL on failure). */
 int  igx_solver_create(igx_patch *patch, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out);
+/* A solver for the global sum sum_p X_p A_p X_p^T that `mp` holds now (after igx_multipatch_zero and the scatters), in its
+   CSR pattern on the device.  fixed[0..nfixed): eliminated global dofs (Multipatch.compute_dirichlet_bcs).  The matrix must be
+   symmetric positive definite on the free dofs (CG).  The handle does NOT own `mp`: the multipatch must outlive it.  Once
+   igx_multipatch_zero has restarted the sums, every call that reads them returns IGX_ERR_ARG.  Preconditioners: NONE, JACOBI,
+   SCHWARZ (igx_solver_set_schwarz); IGX_PRECOND_KRON: IGX_ERR_UNSUPPORTED.  The solve takes b = NULL: the multipatch's summed
+   vector on the device. */
+int  igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64_t nfixed, igx_solver **out);
 void igx_solver_destroy(igx_solver *solver);
 /* Preconditioner of the following solves.  IGX_PRECOND_NONE; IGX_PRECOND_JACOBI: the diagonal, gathered from the device values;
    IGX_PRECOND_KRON: (x)U_k . D^-1 . (x)U_k^T on the free box box_lo[k] <= i_k < box_hi[k], which must be exactly the free dofs.
@@ -429,6 +437,17 @@ void igx_solver_destroy(igx_solver *solver);
    other arguments may be NULL for NONE and JACOBI. */
 int igx_solver_set_precond(igx_solver *solver, int precond, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
                            const double *const *lam, int lam_mode);
+/* Additive Schwarz preconditioner of a multipatch solver (and selects it; afterwards igx_solver_set_precond(IGX_PRECOND_SCHWARZ)
+   selects it again):  z = sum_p X_p M_p B_p M_p X_p^T r,  M_p the mask of the free dofs, B_p = (x)U_k . D^-1 . (x)U_k^T the
+   fast-diagonalization inverse of patch p on the box box_lo[p*3+k] <= i_k < box_hi[p*3+k] of its local dofs (a patch with an
+   empty box takes no part).  U[p*3+k] (host, n_k x n_k row-major) and lam[p*3+k] (host, n_k) per patch and axis (axes beyond
+   the patch's dimension are not read), lam_mode IGX_KRON_*.  Patch solvers, or a multipatch whose maps are not all injective:
+   IGX_ERR_UNSUPPORTED. */
+int igx_solver_set_schwarz(igx_solver *solver, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                           const double *const *lam, int lam_mode);
+/* d_z = P d_r on the device with the current preconditioner P (full-length vectors; NONE: the free entries of d_r).  d_r and
+   d_z must not overlap (d_z is cleared before d_r is read); the same buffer for both is refused with IGX_ERR_ARG. */
+int igx_solver_precond_d(igx_solver *solver, const double *d_r, double *d_z);
 /* d_y = R A R^T d_x on the device (full-length vectors; the fixed entries of d_x are ignored, those of d_y are 0). */
 int igx_solver_spmv_d(igx_solver *solver, const double *d_x, double *d_y);
 /* Solves  R A R^T x = R (b - A ext(g))  by CG and returns the full vector u = x + ext(g) (host, nrows_total).  b: host load
@@ -436,7 +455,8 @@ int igx_solver_spmv_d(igx_solver *solver, const double *d_x, double *d_y);
    its free entries are used) or NULL.  Stops when ||r|| <= tol * ||R (b - A ext(g))|| or after maxiter iterations; the residual
    norm is read back every check_every iterations (alpha and beta stay on the device).  timed != 0: events between the phases
    of every iteration (info->spmv_ms etc.).  The solve is deterministic: the same inputs give bit-identical u.  Refused
-   (IGX_ERR_ARG) if the patch's values have been overwritten by an assembly of another kind since the solver was made. */
+   (IGX_ERR_ARG) if the patch's values have been overwritten by an assembly of another kind since the solver was made.  A
+   multipatch solver takes b = NULL: the right-hand side is then the multipatch's device vector. */
 int igx_solver_solve(igx_solver *solver, const double *b, const double *g, const double *x0, double tol, int maxiter,
                      int check_every, int timed, double *u, igx_solve_info *info);
 

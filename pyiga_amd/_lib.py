@@ -61,9 +61,10 @@ class Timing(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-IGX_PRECOND_NONE, IGX_PRECOND_JACOBI, IGX_PRECOND_KRON = 0, 1, 2
+IGX_PRECOND_NONE, IGX_PRECOND_JACOBI, IGX_PRECOND_KRON, IGX_PRECOND_SCHWARZ = 0, 1, 2, 3
 IGX_KRON_SUM, IGX_KRON_PRODUCT = 1, 2
 PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'kron': IGX_PRECOND_KRON}
+MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ}
 
 
 class SolveInfo(C.Structure):
@@ -149,8 +150,11 @@ SYMBOLS = [
     ('igx_multipatch_scatter_vector', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_multipatch_download', C.c_int, [C.c_void_p, _dp, _dp]),
     ('igx_solver_create', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_create_multipatch', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
     ('igx_solver_destroy', None, [C.c_void_p]),
     ('igx_solver_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
+    ('igx_solver_set_schwarz', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
+    ('igx_solver_precond_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_spmv_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_solve', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(SolveInfo)]),
     ('igx_kron_apply_d', C.c_int, [C.c_void_p, C.POINTER(KronDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -390,3 +390,35 @@ int sumfact_prepare(igx_patch *pt);
 int sumfact_supports_kind(const igx_patch *pt, int kind);
 int sumfact_assemble(igx_patch *pt, const Plan &pl, double *d_data);
 } // namespace igx
+
+// ---------------------------------------------------------------------------------------------
+// multipatch handle (multipatch.hip); also read by the multipatch solver (solve.hip)
+namespace igx {
+struct RowInfo {                             // per local row of a patch: the scatter plan (16 bytes)
+    int32_t kstart, len, base, mode;         // base: delta (DIRECT) or offset of the row in the compacted position array
+};
+} // namespace igx
+
+struct igx_multipatch {
+    igx_ctx *ctx = nullptr;
+    int np = 0;
+    long long nglobal = 0, nnz = 0;
+    bool injective = true;
+    long long zero_from = 0;                   // igx_multipatch_zero clears values [zero_from, nnz): the rows more than one local row reaches
+    long long vzero_from = 0;                  // ... and vector entries [vzero_from, nglobal)
+    unsigned long long generation = 0;         // bumped by igx_multipatch_zero: a solver made over older sums refuses to run
+    int32_t *d_indptr = nullptr, *d_indices = nullptr, *d_contrib = nullptr;
+    double *d_vals = nullptr, *d_vec = nullptr, *d_stage = nullptr;
+    size_t stage_len = 0;
+    long long counts[4] = {0, 0, 0, 0};        // local entries per scatter class
+    int max_row = 0;                           // longest global row (entries)
+    struct Patch {
+        int n = 0;
+        int dim = 0, N[3] = {1, 1, 1};         // tensor-product shape of the patch's dofs
+        long long nnz = 0;
+        int32_t *d_l2g = nullptr;
+        igx::RowInfo *d_info = nullptr;
+        int32_t *d_cpos = nullptr;
+    };
+    std::vector<Patch> pp;
+};

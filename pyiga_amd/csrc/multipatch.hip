@@ -29,9 +29,6 @@ constexpr int WAVE = 64;
 constexpr int SORT_TILE = 1024;          // longest raw global row sorted in the LDS of one wave; longer rows: k_sort_long
 enum { MODE_DIRECT = 0, MODE_STORE = 1, MODE_RMW = 2, MODE_ATOMIC = 3 };
 
-struct RowInfo {                         // per local row of a patch: the scatter plan (16 bytes)
-    int32_t kstart, len, base, mode;     // base: delta (DIRECT) or offset of the row in the compacted position array
-};
 
 __device__ __forceinline__ unsigned long long lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
 
@@ -307,26 +304,6 @@ unsigned waves_grid(long long nwaves, int block = 256) { return (unsigned)((nwav
 
 } // namespace
 
-struct igx_multipatch {
-    igx_ctx *ctx = nullptr;
-    int np = 0;
-    long long nglobal = 0, nnz = 0;
-    bool injective = true;
-    long long zero_from = 0;                   // igx_multipatch_zero clears values [zero_from, nnz): the rows more than one local row reaches
-    long long vzero_from = 0;                  // ... and vector entries [vzero_from, nglobal)
-    int32_t *d_indptr = nullptr, *d_indices = nullptr, *d_contrib = nullptr;
-    double *d_vals = nullptr, *d_vec = nullptr, *d_stage = nullptr;
-    size_t stage_len = 0;
-    long long counts[4] = {0, 0, 0, 0};        // local entries per scatter class
-    struct Patch {
-        int n = 0;
-        long long nnz = 0;
-        int32_t *d_l2g = nullptr;
-        RowInfo *d_info = nullptr;
-        int32_t *d_cpos = nullptr;
-    };
-    std::vector<Patch> pp;
-};
 
 namespace {
 
@@ -479,6 +456,7 @@ int mp_build(igx_multipatch *mp, igx_patch *const *patches, const int32_t *const
     if (!mp->injective || !tail) first_multi = 0;
     mp->vzero_from = first_multi;
     mp->zero_from = gptr32[first_multi];
+    for (long long r = 0; r < G; ++r) mp->max_row = std::max(mp->max_row, gptr32[r + 1] - gptr32[r]);
     MP_KEEP(mp->d_vals, nnz, "global values");
     MP_KEEP(mp->d_vec, G, "global vector");
     IGX_HIP(hipMemsetAsync(mp->d_vals, 0, std::max<long long>(1, nnz) * sizeof(double), st));
@@ -544,6 +522,8 @@ igx_multipatch *igx_multipatch_create(igx_ctx *ctx, int npatches, igx_patch *con
         auto &P = mp->pp[p];
         P.n = (int)patches[p]->nrows_total;
         P.nnz = patches[p]->nnz;
+        P.dim = patches[p]->dim;
+        for (int k = 0; k < P.dim; ++k) P.N[k] = patches[p]->ax[k].N;
         std::vector<int32_t> s(l2g[p], l2g[p] + P.n);
         for (int32_t g : s)
             if (g < 0 || g >= nglobal) { set_error("igx_multipatch_create: patch %d maps a dof to %d, outside [0, %lld)", p, g, (long long)nglobal); delete mp; return nullptr; }
@@ -589,6 +569,7 @@ int igx_multipatch_zero(igx_multipatch *mp)
     if (!mp) { set_error("igx_multipatch_zero: null handle"); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(mp->ctx->device));
     hipStream_t st = mp->ctx->stream;
+    ++mp->generation;
     // rows one local row reaches are overwritten by every scatter; only the sums need a zero to start from
     if (mp->nnz > mp->zero_from)
         IGX_HIP(hipMemsetAsync(mp->d_vals + mp->zero_from, 0, (mp->nnz - mp->zero_from) * sizeof(double), st));

@@ -1,5 +1,5 @@
-// Dirichlet problems of one patch solved on the device: preconditioned CG on the values igx_assemble left in HBM
-// (igx_solver_*, igx_kron_apply_d; include/igx.h).
+// Dirichlet problems solved on the device: preconditioned CG on the values igx_assemble left in HBM (one patch), or on the
+// global sums igx_multipatch_* formed there (several patches) (igx_solver_*, igx_kron_apply_d; include/igx.h).
 //
 // Replaces the host steps of the reference's workflow  RestrictedLinearSystem -> make_solver / cg  (pyiga/assemble.py:571-652,
 // pyiga/solvers.py:17-42, pyiga/approx.py:62-96) for a single patch.  Three kinds of kernels:
@@ -9,6 +9,10 @@
 //   k_kron     one contraction  Y[.., i, ..] = sum_j B[i][j] X[.., j, ..]  of a Kronecker product through LDS tiles (FP64 VALU);
 //              strided input / output, so the fast-diagonalization preconditioner (Sangalli-Tani) works on the free box of a
 //              full-length vector.  The last contraction can divide by the eigenvalue sums / products (D^-1).
+//   k_csr_spmv the same product over the general CSR pattern of a multipatch (indptr / indices / values: 12 bytes per
+//              nonzero), k_csr_diag its diagonal; the additive Schwarz preconditioner gathers the box of every patch
+//              (k_box_gather), applies the patch's fast-diagonalization inverse with the k_kron steps and adds it back
+//              (k_box_scatter), patch after patch.
 //   vector     fused CG updates and fixed-order two-pass dot products (fixed grid, fixed trees): two solves of the same
 //              system give bit-identical results.  alpha and beta stay in device memory.
 #include "igx_internal.h"
@@ -141,6 +145,116 @@ __global__ void k_diag(const Geom g, const double *__restrict__ vals, const uint
     const int c0 = g.jhi[0][i0] - l0, c1 = g.jhi[1][i1] - l1, c2 = g.jhi[2][i2] - l2;
     const long long row = igx_rowptr3(g.rp[0], g.rp[1], g.rp[2], g.S1, g.S2, c0, c1, i0, i1, i2);
     dinv[I] = 1.0 / vals[row + ((long long)(i0 - l0) * c1 + (i1 - l1)) * c2 + (i2 - l2)];
+}
+
+// the contract of k_spmv over the general CSR pattern of a multipatch: y[I] = free[I] ? (b ? b[I] : 0) + s * (A x)[I] : 0,
+// part[block] = sum of pd[I] * y[I] over the rows of the block (optional).  Values and indices are streamed once
+// (non-temporal), x is gathered through the caches.  Offsets into values / indices are 64-bit.
+template <int GW, int U>
+__global__ void __launch_bounds__(BLOCK) k_csr_spmv(long long nrows, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                    const double *__restrict__ vals, const uint8_t *__restrict__ freem,
+                                                    const double *__restrict__ x, const double *b, double s, double *y,
+                                                    const double *__restrict__ pd, double *part)
+{
+    __shared__ double sh[BLOCK];
+    const int lane = threadIdx.x % GW;
+    const long long ngroups = (long long)gridDim.x * (BLOCK / GW);
+    double dot = 0.0;
+    long long I = (long long)blockIdx.x * (BLOCK / GW) + threadIdx.x / GW;
+    // row header loaded one row ahead
+    long long nk0 = 0, nk1 = 0;
+    int nfr = 0;
+    if (I < nrows) { nfr = freem[I]; nk0 = indptr[I]; nk1 = indptr[I + 1]; }
+    for (; I < nrows; I += ngroups) {
+        const long long k0 = nk0, k1 = nk1;
+        const int fr = nfr;
+        if (I + ngroups < nrows) { nfr = freem[I + ngroups]; nk0 = indptr[I + ngroups]; nk1 = indptr[I + ngroups + 1]; }
+        if (!fr) {                                   // (uniform over the group)
+            if (lane == 0) y[I] = 0.0;
+            continue;
+        }
+        double acc = 0.0;
+        for (long long k = k0 + lane; k < k1; k += U * GW) {
+            double v[U], xv[U];
+            int c[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k + u * GW < k1;
+                v[u] = in ? __builtin_nontemporal_load(vals + k + u * GW) : 0.0;
+                c[u] = in ? __builtin_nontemporal_load(indices + k + u * GW) : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) xv[u] = c[u] >= 0 ? x[c[u]] : 0.0;
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc += v[u] * xv[u];
+        }
+#pragma unroll
+        for (int off = GW / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, GW);
+        if (lane == 0) {
+            const double v = (b ? b[I] : 0.0) + s * acc;
+            y[I] = v;
+            if (pd) dot += pd[I] * v;
+        }
+    }
+    if (part) {
+        const double v = block_sum(dot, sh);
+        if (threadIdx.x == 0) part[blockIdx.x] = v;
+    }
+}
+
+// dinv[I] = free[I] ? 1 / A[I][I] : 0, the diagonal found by binary search in the sorted row
+__global__ void k_csr_diag(long long nrows, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                           const double *__restrict__ vals, const uint8_t *__restrict__ freem, double *dinv)
+{
+    const long long I = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= nrows) return;
+    if (!freem[I]) { dinv[I] = 0.0; return; }
+    const long long end = indptr[I + 1];
+    long long lo = indptr[I], hi = end;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (indices[mid] < I) lo = mid + 1; else hi = mid;
+    }
+    dinv[I] = (lo < end && indices[lo] == I) ? 1.0 / vals[lo] : 0.0;
+}
+
+// the box of one patch in its local dofs (3D; a 2D patch has a one-dof outer axis) and its local-to-global map
+struct BoxMap {
+    int lo[3], nb[3], N[3];
+    long long nbox;
+    const int32_t *l2g;
+};
+
+__device__ __forceinline__ int box_global(const BoxMap &m, long long i)
+{
+    const int c2 = (int)(i % m.nb[2]);
+    const long long t = i / m.nb[2];
+    const int c1 = (int)(t % m.nb[1]), c0 = (int)(t / m.nb[1]);
+    return m.l2g[((long long)(m.lo[0] + c0) * m.N[1] + (m.lo[1] + c1)) * m.N[2] + (m.lo[2] + c2)];
+}
+
+// rp[i] = free[g] ? r[g] : 0, g the global dof of box entry i
+__global__ void k_box_gather(const BoxMap m, const uint8_t *__restrict__ freem, const double *__restrict__ r, double *__restrict__ rp)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m.nbox) return;
+    const int g = box_global(m, i);
+    rp[i] = freem[g] ? r[g] : 0.0;
+}
+
+// z[g] += zp[i] on the free g (the map of a patch is injective: no two entries of one pass meet)
+__global__ void k_box_scatter(const BoxMap m, const uint8_t *__restrict__ freem, const double *__restrict__ zp, double *z)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m.nbox) return;
+    const int g = box_global(m, i);
+    if (freem[g]) z[g] += zp[i];
+}
+
+__global__ void k_scale(long long n, const double *d, const double *x, double *y)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = d[i] * x[i];
 }
 
 __global__ void k_mask_copy(long long n, const uint8_t *freem, const double *x, double *y)
@@ -410,8 +524,18 @@ int spmv_gw(long long maxlen)
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
+// one patch of the Schwarz preconditioner: its box and the contractions of its fast-diagonalization inverse (compact box vectors)
+struct SwPatch {
+    BoxMap map;
+    int patch, dim;
+    KronPlan kl, kr;
+};
+
 struct igx_solver {
-    igx_patch *pt = nullptr;
+    igx_ctx *ctx = nullptr;
+    igx_patch *pt = nullptr;                  // the patch of a patch solver, or
+    igx_multipatch *mp = nullptr;             // the global sums of a multipatch solver
+    unsigned long long gen = 0;               // mp->generation the solver was made over
     int kind = 0;
     int dim = 0;
     int N[3] = {1, 1, 1};                    // dofs per axis of the patch (dim of them)
@@ -429,9 +553,11 @@ struct igx_solver {
     double *d_sc = nullptr;                   // SC_N scalars
     int precond = IGX_PRECOND_NONE;
     KronPlan kl{}, kr{};                      // (x) U_k^T with D^-1, then (x) U_k
-    double *d_kron = nullptr;                 // U_k^T | U_k | lam_k
+    double *d_kron = nullptr;                 // U_k^T | U_k | lam_k (Schwarz: of every patch)
     double *d_W = nullptr;                    // two work buffers
     long long wlen = 0;
+    std::vector<SwPatch> sw;                  // Schwarz: the patches with a non-empty box
+    double *d_box = nullptr;                  // Schwarz: one patch's box (gathered residual, then the local correction)
     hipEvent_t ev[6] = {};
     bool have_ev = false;
 };
@@ -440,6 +566,14 @@ namespace {
 
 int check_values(const igx_solver *s, const char *what)
 {
+    if (s->mp) {
+        if (s->mp->generation != s->gen) {
+            set_error("%s: the multipatch's sums were restarted (igx_multipatch_zero) since the solver was made: make a new solver "
+                      "over the new sums", what);
+            return IGX_ERR_ARG;
+        }
+        return IGX_OK;
+    }
     if (s->pt->values_kind != s->kind || !s->pt->d_data) {
         set_error("%s: the patch no longer holds the values of the solver's matrix (another kind was assembled since, or an "
                   "assembly failed): assemble it again", what);
@@ -454,8 +588,25 @@ unsigned spmv_blocks(const igx_solver *s)
     return (unsigned)std::max<long long>(1, std::min<long long>(s->nb_spmv, (s->n + groups - 1) / groups));
 }
 
+int csr_spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
+{
+    const unsigned nb = spmv_blocks(s);
+    const igx_multipatch *m = s->mp;
+    const long long n = s->n;
+    switch (s->gw) {
+    case 64: k_csr_spmv<64, 8><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
+    case 32: k_csr_spmv<32, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
+    case 16: k_csr_spmv<16, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
+    case 8: k_csr_spmv<8, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
+    default: k_csr_spmv<4, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
+    }
+    IGX_HIP(hipGetLastError());
+    return IGX_OK;
+}
+
 int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
 {
+    if (s->mp) return csr_spmv(st, s, x, b, sign, y, pd, part);
     const unsigned nb = spmv_blocks(s);
     const double *v = s->pt->d_data;
     switch (s->gw) {
@@ -481,13 +632,99 @@ int apply_kron(hipStream_t st, igx_solver *s, const double *r, double *z)
     return launch_kron_plan(st, s->kr, t, z, W2);
 }
 
+// z = sum_p X_p M_p B_p M_p X_p^T r: per patch, in patch order, gather the box, the two Kronecker products, add back on the free dofs
+int apply_schwarz(hipStream_t st, igx_solver *s, const double *r, double *z)
+{
+    IGX_HIP(hipMemsetAsync(z, 0, (size_t)s->n * sizeof(double), st));
+    double *W[2] = {s->d_W, s->d_W + s->wlen};
+    for (const SwPatch &P : s->sw) {
+        const unsigned nb = (unsigned)((P.map.nbox + 255) / 256);
+        k_box_gather<<<nb, 256, 0, st>>>(P.map, s->d_mask, r, s->d_box);
+        IGX_HIP(hipGetLastError());
+        double *t = W[(P.dim - 1) % 2];
+        if (int rc = launch_kron_plan(st, P.kl, s->d_box, t, W)) return rc;
+        double *W2[2] = {W[P.dim % 2], t};
+        if (int rc = launch_kron_plan(st, P.kr, t, s->d_box, W2)) return rc;
+        k_box_scatter<<<nb, 256, 0, st>>>(P.map, s->d_mask, s->d_box, z);
+        IGX_HIP(hipGetLastError());
+    }
+    return IGX_OK;
+}
+
+// the preconditioners applied by kernels of their own (Kronecker, Schwarz); Jacobi is fused into k_update
+int apply_dense(hipStream_t st, igx_solver *s, const double *r, double *z)
+{
+    return s->precond == IGX_PRECOND_SCHWARZ ? apply_schwarz(st, s, r, z) : apply_kron(st, s, r, z);
+}
+
+int spmv_occupancy(const igx_solver *s)
+{
+    int per_cu = 0;
+    hipError_t eo;
+    if (s->mp) {
+        switch (s->gw) {
+        case 64: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<64, 8>, BLOCK, 0); break;
+        case 32: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<32, 4>, BLOCK, 0); break;
+        case 16: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<16, 4>, BLOCK, 0); break;
+        case 8: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<8, 4>, BLOCK, 0); break;
+        default: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<4, 4>, BLOCK, 0); break;
+        }
+    } else {
+        switch (s->gw) {
+        case 64: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<64, 12>, BLOCK, 0); break;
+        case 32: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<32, 4>, BLOCK, 0); break;
+        case 16: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<16, 4>, BLOCK, 0); break;
+        case 8: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<8, 4>, BLOCK, 0); break;
+        default: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<4, 4>, BLOCK, 0); break;
+        }
+    }
+    if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
+    return (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, s->ctx->ncu));
+}
+
 void free_solver(igx_solver *s)
 {
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
-    (void)hipFree(s->d_kron); (void)hipFree(s->d_W);
+    (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
     if (s->have_ev)
         for (auto &e : s->ev) (void)hipEventDestroy(e);
     delete s;
+}
+
+// the dof mask from the fixed list (s->n set); false with igx_last_error on a bad list
+bool set_fixed(igx_solver *s, const int64_t *fixed, int64_t nfixed, const char *what)
+{
+    s->h_free.assign((size_t)s->n, 1);
+    for (int64_t k = 0; k < nfixed; ++k) {
+        if (fixed[k] < 0 || fixed[k] >= s->n) { set_error("%s: fixed dof %lld out of range", what, (long long)fixed[k]); return false; }
+        if (!s->h_free[fixed[k]]) { set_error("%s: fixed dof %lld given twice", what, (long long)fixed[k]); return false; }
+        s->h_free[fixed[k]] = 0;
+        s->fixed.push_back(fixed[k]);
+    }
+    return true;
+}
+
+// the dof mask on the device, the CG vectors, partial sums, scalars and events (s->n, s->h_free set)
+int init_vectors(igx_solver *s, const char *what)
+{
+    const size_t n = (size_t)s->n;
+    bool ok = hipMalloc((void **)&s->d_mask, n) == hipSuccess &&
+              hipMalloc((void **)&s->d_vec, 8 * n * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&s->d_part, 2 * (size_t)NB_SPMV_MAX * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&s->d_sc, SC_N * sizeof(double)) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); set_error("%s: out of device memory (%.3f GB)", what, 8.0 * 8 * n / 1e9); return IGX_ERR_NOMEM; }
+    hipStream_t st = s->ctx->stream;
+    hipError_t e = hipMemcpyAsync(s->d_mask, s->h_free.data(), n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_vec, 0, 8 * n * sizeof(double), st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
+    double *v = s->d_vec;
+    s->x = v; s->r = v + n; s->p = v + 2 * n; s->q = v + 3 * n; s->z = v + 4 * n; s->b = v + 5 * n; s->w = v + 6 * n; s->dinv = v + 7 * n;
+    for (auto &ev : s->ev)
+        if (hipEventCreate(&ev) != hipSuccess) { set_error("%s: hipEventCreate failed", what); return IGX_ERR_HIP; }
+    s->have_ev = true;
+    return IGX_OK;
 }
 
 } // namespace
@@ -513,15 +750,9 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
     }
     if (hipSetDevice(pt->ctx->device) != hipSuccess) { set_error("igx_solver_create: hipSetDevice failed"); return IGX_ERR_HIP; }
     igx_solver *s = new igx_solver;
-    s->pt = pt; s->kind = kind; s->dim = pt->dim; s->n = pt->nrows_total;
+    s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->n = pt->nrows_total;
     for (int k = 0; k < pt->dim; ++k) s->N[k] = pt->ax[k].N;
-    s->h_free.assign((size_t)s->n, 1);
-    for (int64_t k = 0; k < nfixed; ++k) {
-        if (fixed[k] < 0 || fixed[k] >= s->n) { set_error("igx_solver_create: fixed dof %lld out of range", (long long)fixed[k]); delete s; return IGX_ERR_ARG; }
-        if (!s->h_free[fixed[k]]) { set_error("igx_solver_create: fixed dof %lld given twice", (long long)fixed[k]); delete s; return IGX_ERR_ARG; }
-        s->h_free[fixed[k]] = 0;
-        s->fixed.push_back(fixed[k]);
-    }
+    if (!set_fixed(s, fixed, nfixed, "igx_solver_create")) { delete s; return IGX_ERR_ARG; }
     // per-axis tables as a 3D layout (2D: a one-dof outer axis in front)
     const int off = 3 - pt->dim;
     std::vector<int> tab;
@@ -542,42 +773,34 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
         pos[a][2] = tab.size(); tab.insert(tab.end(), rp.begin(), rp.end());
     }
     s->gw = spmv_gw(maxlen);
-    {
-        int per_cu = 0;
-        hipError_t eo;
-        switch (s->gw) {
-        case 64: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<64, 12>, BLOCK, 0); break;
-        case 32: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<32, 4>, BLOCK, 0); break;
-        case 16: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<16, 4>, BLOCK, 0); break;
-        case 8: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<8, 4>, BLOCK, 0); break;
-        default: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<4, 4>, BLOCK, 0); break;
-        }
-        if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
-        s->nb_spmv = (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, pt->ctx->ncu));
-    }
+    s->nb_spmv = spmv_occupancy(s);
     const size_t n = (size_t)s->n;
-    bool ok = hipMalloc((void **)&s->d_tab, tab.size() * sizeof(int)) == hipSuccess &&
-              hipMalloc((void **)&s->d_mask, n) == hipSuccess &&
-              hipMalloc((void **)&s->d_vec, 8 * n * sizeof(double)) == hipSuccess &&
-              hipMalloc((void **)&s->d_part, 2 * (size_t)NB_SPMV_MAX * sizeof(double)) == hipSuccess &&
-              hipMalloc((void **)&s->d_sc, SC_N * sizeof(double)) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); set_error("igx_solver_create: out of device memory (%.3f GB)", 8.0 * 8 * n / 1e9); free_solver(s); return IGX_ERR_NOMEM; }
-    hipStream_t st = pt->ctx->stream;
-    hipError_t e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_mask, s->h_free.data(), n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_vec, 0, 8 * n * sizeof(double), st);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (hipMalloc((void **)&s->d_tab, tab.size() * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError(); set_error("igx_solver_create: out of device memory (%.3f GB)", 8.0 * 8 * n / 1e9); free_solver(s); return IGX_ERR_NOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, pt->ctx->stream);
     if (e != hipSuccess) { set_error("igx_solver_create: %s", hipGetErrorString(e)); free_solver(s); return IGX_ERR_HIP; }
+    if (int rc = init_vectors(s, "igx_solver_create")) { free_solver(s); return rc; }
     for (int a = 0; a < 3; ++a) { s->g.jlo[a] = s->d_tab + pos[a][0]; s->g.jhi[a] = s->d_tab + pos[a][1]; s->g.rp[a] = s->d_tab + pos[a][2]; }
     s->g.S1 = tab[pos[1][2] + s->g.N[1]];
     s->g.S2 = tab[pos[2][2] + s->g.N[2]];
     s->g.nrows = s->n;
-    double *v = s->d_vec;
-    s->x = v; s->r = v + n; s->p = v + 2 * n; s->q = v + 3 * n; s->z = v + 4 * n; s->b = v + 5 * n; s->w = v + 6 * n; s->dinv = v + 7 * n;
-    for (auto &ev : s->ev)
-        if (hipEventCreate(&ev) != hipSuccess) { set_error("igx_solver_create: hipEventCreate failed"); free_solver(s); return IGX_ERR_HIP; }
-    s->have_ev = true;
+    *out = s;
+    return IGX_OK;
+}
+
+int igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    if (!out) { set_error("igx_solver_create_multipatch: null argument"); return IGX_ERR_ARG; }
+    *out = nullptr;
+    if (!mp || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create_multipatch: null argument"); return IGX_ERR_ARG; }
+    if (hipSetDevice(mp->ctx->device) != hipSuccess) { set_error("igx_solver_create_multipatch: hipSetDevice failed"); return IGX_ERR_HIP; }
+    igx_solver *s = new igx_solver;
+    s->ctx = mp->ctx; s->mp = mp; s->gen = mp->generation; s->kind = -1; s->n = mp->nglobal;
+    if (!set_fixed(s, fixed, nfixed, "igx_solver_create_multipatch")) { delete s; return IGX_ERR_ARG; }
+    s->gw = spmv_gw(mp->max_row);
+    s->nb_spmv = spmv_occupancy(s);
+    if (int rc = init_vectors(s, "igx_solver_create_multipatch")) { free_solver(s); return rc; }
     *out = s;
     return IGX_OK;
 }
@@ -585,8 +808,8 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
 void igx_solver_destroy(igx_solver *s)
 {
     if (!s) return;
-    (void)hipSetDevice(s->pt->ctx->device);
-    (void)hipStreamSynchronize(s->pt->ctx->stream);
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
     free_solver(s);
 }
 
@@ -594,18 +817,26 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
                            const double *const *lam, int lam_mode)
 {
     if (!s) { set_error("igx_solver_set_precond: null solver"); return IGX_ERR_ARG; }
-    IGX_HIP(hipSetDevice(s->pt->ctx->device));
-    hipStream_t st = s->pt->ctx->stream;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
     if (precond == IGX_PRECOND_NONE) { s->precond = precond; return IGX_OK; }
     if (precond == IGX_PRECOND_JACOBI) {
         if (int rc = check_values(s, "igx_solver_set_precond")) return rc;
-        k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pt->d_data, s->d_mask, s->dinv);
+        if (s->mp) k_csr_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->n, s->mp->d_indptr, s->mp->d_indices, s->mp->d_vals, s->d_mask, s->dinv);
+        else k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pt->d_data, s->d_mask, s->dinv);
         IGX_HIP(hipGetLastError());
         IGX_HIP(hipStreamSynchronize(st));
         s->precond = precond;
         return IGX_OK;
     }
+    if (precond == IGX_PRECOND_SCHWARZ) {
+        if (!s->mp) { set_error("igx_solver_set_precond: the Schwarz preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
+        if (s->sw.empty() || !s->d_W) { set_error("igx_solver_set_precond: set the Schwarz factors up first (igx_solver_set_schwarz)"); return IGX_ERR_ARG; }
+        s->precond = precond;
+        return IGX_OK;
+    }
     if (precond != IGX_PRECOND_KRON) { set_error("igx_solver_set_precond: unknown preconditioner %d", precond); return IGX_ERR_ARG; }
+    if (s->mp) { set_error("igx_solver_set_precond: IGX_PRECOND_KRON needs a patch solver (multipatch: IGX_PRECOND_SCHWARZ)"); return IGX_ERR_UNSUPPORTED; }
     if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_precond: null argument"); return IGX_ERR_ARG; }
     if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_precond: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
     const int d = s->dim;
@@ -685,12 +916,137 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     return IGX_OK;
 }
 
+int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                           const double *const *lam, int lam_mode)
+{
+    if (!s) { set_error("igx_solver_set_schwarz: null solver"); return IGX_ERR_ARG; }
+    if (!s->mp) { set_error("igx_solver_set_schwarz: the Schwarz preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
+    const igx_multipatch *mp = s->mp;
+    if (!mp->injective) {
+        set_error("igx_solver_set_schwarz: a local-to-global map is not injective (two dofs of one patch share a global dof); "
+                  "use IGX_PRECOND_JACOBI");
+        return IGX_ERR_UNSUPPORTED;
+    }
+    if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_schwarz: null argument"); return IGX_ERR_ARG; }
+    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_schwarz: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
+    // host layout of the factors: per patch with a non-empty box, per axis  U_k^T | U_k | lam_k
+    std::vector<SwPatch> sw;
+    std::vector<size_t> oUt, oU, oL;               // (per patch, 3 axes)
+    size_t tot = 0;
+    long long wlen = 1;
+    for (int p = 0; p < mp->np; ++p) {
+        const auto &P = mp->pp[p];
+        bool empty = false;
+        for (int k = 0; k < P.dim; ++k) {
+            const int lo = box_lo[p * 3 + k], hi = box_hi[p * 3 + k];
+            if (lo < 0 || hi > P.N[k] || lo > hi) {
+                set_error("igx_solver_set_schwarz: patch %d: bad box [%d, %d) on axis %d of %d dofs", p, lo, hi, k, P.N[k]);
+                return IGX_ERR_ARG;
+            }
+            empty = empty || lo == hi;
+        }
+        if (empty) continue;
+        SwPatch W{};
+        W.dim = P.dim;
+        const int off = 3 - P.dim;
+        for (int a = 0; a < 3; ++a) { W.map.lo[a] = 0; W.map.nb[a] = 1; W.map.N[a] = 1; }
+        W.map.nbox = 1;
+        for (int k = 0; k < P.dim; ++k) {
+            const int m = box_hi[p * 3 + k] - box_lo[p * 3 + k];
+            if (!U[p * 3 + k] || !lam[p * 3 + k]) { set_error("igx_solver_set_schwarz: patch %d: factor of axis %d missing", p, k); return IGX_ERR_ARG; }
+            W.map.lo[off + k] = box_lo[p * 3 + k]; W.map.nb[off + k] = m; W.map.N[off + k] = P.N[k];
+            W.map.nbox *= m;
+            oUt.push_back(tot); tot += (size_t)m * m;
+            oU.push_back(tot); tot += (size_t)m * m;
+            oL.push_back(tot); tot += m;
+        }
+        for (int k = P.dim; k < 3; ++k) { oUt.push_back(0); oU.push_back(0); oL.push_back(0); }
+        W.map.l2g = P.d_l2g;
+        W.patch = p;
+        wlen = std::max(wlen, W.map.nbox);
+        sw.push_back(W);
+    }
+    if (sw.empty()) { set_error("igx_solver_set_schwarz: every patch box is empty"); return IGX_ERR_ARG; }
+    std::vector<double> h(std::max<size_t>(1, tot));
+    for (size_t j = 0; j < sw.size(); ++j) {
+        const int p = sw[j].patch;
+        for (int k = 0; k < sw[j].dim; ++k) {
+            const int m = box_hi[p * 3 + k] - box_lo[p * 3 + k];
+            const double *Uk = U[p * 3 + k];
+            double *ut = &h[oUt[j * 3 + k]];
+            for (int a = 0; a < m; ++a)
+                for (int b2 = 0; b2 < m; ++b2) ut[(size_t)a * m + b2] = Uk[(size_t)b2 * m + a];
+            std::memcpy(&h[oU[j * 3 + k]], Uk, (size_t)m * m * sizeof(double));
+            std::memcpy(&h[oL[j * 3 + k]], lam[p * 3 + k], (size_t)m * sizeof(double));
+        }
+    }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    IGX_HIP(hipStreamSynchronize(st));
+    (void)hipFree(s->d_kron); s->d_kron = nullptr;
+    (void)hipFree(s->d_W); s->d_W = nullptr;
+    (void)hipFree(s->d_box); s->d_box = nullptr;
+    s->sw.clear();
+    if (s->precond == IGX_PRECOND_SCHWARZ) s->precond = IGX_PRECOND_NONE;
+    IGX_HIP(hipMalloc((void **)&s->d_kron, h.size() * sizeof(double)));
+    IGX_HIP(hipMemcpyAsync(s->d_kron, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMalloc((void **)&s->d_box, (size_t)wlen * sizeof(double)));
+    IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)wlen * sizeof(double)));
+    for (size_t j = 0; j < sw.size(); ++j) {
+        SwPatch &W = sw[j];
+        const int d = W.dim, off = 3 - d;
+        KronPlan L{}, R{};
+        L.dim = R.dim = d;
+        L.batch = R.batch = 1;
+        long long stride[4] = {1, 1, 1, 1};             // compact box vectors in and out
+        for (int k = d - 2; k >= 0; --k) stride[k] = stride[k + 1] * W.map.nb[off + k + 1];
+        for (int k = 0; k < 4; ++k) L.x_stride[k] = L.y_stride[k] = R.x_stride[k] = R.y_stride[k] = k < d ? stride[k] : 1;
+        for (int k = 0; k < d; ++k) {
+            L.m[k] = L.n[k] = R.m[k] = R.n[k] = W.map.nb[off + k];
+            L.B[k] = s->d_kron + oUt[j * 3 + k];
+            R.B[k] = s->d_kron + oU[j * 3 + k];
+            L.lam[k] = s->d_kron + oL[j * 3 + k];
+        }
+        L.lam_mode = lam_mode;
+        W.kl = L; W.kr = R;
+    }
+    IGX_HIP(hipStreamSynchronize(st));
+    s->sw = std::move(sw);
+    s->wlen = wlen;
+    s->precond = IGX_PRECOND_SCHWARZ;
+    return IGX_OK;
+}
+
+int igx_solver_precond_d(igx_solver *s, const double *d_r, double *d_z)
+{
+    if (!s || !d_r || !d_z) { set_error("igx_solver_precond_d: null argument"); return IGX_ERR_ARG; }
+    if (d_r == d_z) { set_error("igx_solver_precond_d: d_r and d_z must be different buffers (z is cleared before r is read)"); return IGX_ERR_ARG; }
+    if (int rc = check_values(s, "igx_solver_precond_d")) return rc;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const unsigned nb = (unsigned)((s->n + 255) / 256);
+    switch (s->precond) {
+    case IGX_PRECOND_JACOBI: k_scale<<<nb, 256, 0, st>>>(s->n, s->dinv, d_r, d_z); break;
+    case IGX_PRECOND_KRON:
+        IGX_HIP(hipMemsetAsync(d_z, 0, (size_t)s->n * sizeof(double), st));
+        if (int rc = apply_kron(st, s, d_r, d_z)) return rc;
+        break;
+    case IGX_PRECOND_SCHWARZ:
+        if (int rc = apply_schwarz(st, s, d_r, d_z)) return rc;
+        break;
+    default: k_mask_copy<<<nb, 256, 0, st>>>(s->n, s->d_mask, d_r, d_z); break;
+    }
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
 int igx_solver_spmv_d(igx_solver *s, const double *d_x, double *d_y)
 {
     if (!s || !d_x || !d_y) { set_error("igx_solver_spmv_d: null argument"); return IGX_ERR_ARG; }
     if (int rc = check_values(s, "igx_solver_spmv_d")) return rc;
-    IGX_HIP(hipSetDevice(s->pt->ctx->device));
-    hipStream_t st = s->pt->ctx->stream;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
     k_mask_copy<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->n, s->d_mask, d_x, s->w);
     IGX_HIP(hipGetLastError());
     if (int rc = spmv(st, s, s->w, nullptr, 1.0, d_y, nullptr, nullptr)) return rc;
@@ -701,12 +1057,12 @@ int igx_solver_spmv_d(igx_solver *s, const double *d_x, double *d_y)
 int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const double *x0, double tol, int maxiter, int check_every,
                      int timed, double *u, igx_solve_info *info)
 {
-    if (!s || !b || (!gvals && !s->fixed.empty()) || !u) { set_error("igx_solver_solve: null argument"); return IGX_ERR_ARG; }
+    if (!s || (!b && !s->mp) || (!gvals && !s->fixed.empty()) || !u) { set_error("igx_solver_solve: null argument"); return IGX_ERR_ARG; }
     if (!(tol >= 0.0) || maxiter < 0) { set_error("igx_solver_solve: tol must be >= 0 and maxiter >= 0"); return IGX_ERR_ARG; }
     if (int rc = check_values(s, "igx_solver_solve")) return rc;
     if (check_every < 1) check_every = 1;
-    IGX_HIP(hipSetDevice(s->pt->ctx->device));
-    hipStream_t st = s->pt->ctx->stream;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
     const long long n = s->n;
     const size_t nbytes = (size_t)n * sizeof(double);
     igx_solve_info inf{};
@@ -714,7 +1070,8 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
     std::vector<double> w((size_t)n, 0.0);
     for (size_t k = 0; k < s->fixed.size(); ++k) w[s->fixed[k]] = gvals[k];
     IGX_HIP(hipEventRecord(s->ev[5], st));
-    IGX_HIP(hipMemcpyAsync(s->b, b, nbytes, hipMemcpyHostToDevice, st));
+    if (b) IGX_HIP(hipMemcpyAsync(s->b, b, nbytes, hipMemcpyHostToDevice, st));
+    else IGX_HIP(hipMemcpyAsync(s->b, s->mp->d_vec, nbytes, hipMemcpyDeviceToDevice, st));      // the multipatch's summed vector
     IGX_HIP(hipMemcpyAsync(s->w, w.data(), nbytes, hipMemcpyHostToDevice, st));
     IGX_HIP(hipMemsetAsync(s->x, 0, nbytes, st));
     IGX_HIP(hipMemsetAsync(s->p, 0, nbytes, st));
@@ -736,14 +1093,14 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
         IGX_HIP(hipMemcpyAsync(s->x, w.data(), nbytes, hipMemcpyHostToDevice, st));
         if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
     }
-    const bool kron = s->precond == IGX_PRECOND_KRON, jac = s->precond == IGX_PRECOND_JACOBI;
+    const bool kron = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ, jac = s->precond == IGX_PRECOND_JACOBI;
     // z = P r, rz, rr; p = z
     const double *zz = (kron || jac) ? s->z : s->r;
     if (jac) {
         IGX_HIP(hipMemsetAsync(s->d_sc + SC_ALPHA, 0, sizeof(double), st));   // k_update with alpha = 0: z = dinv r and the dots
         k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, s->dinv, s->z, s->d_sc, pA, pB);
     } else {
-        if (kron && (apply_kron(st, s, s->r, s->z) != IGX_OK)) return IGX_ERR_HIP;
+        if (kron && (apply_dense(st, s, s->r, s->z) != IGX_OK)) return IGX_ERR_HIP;
         k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, kron ? s->r : nullptr, s->z, pA, pB);
     }
     k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_INIT);
@@ -764,7 +1121,7 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
         IGX_HIP(hipGetLastError());
         if (timed) IGX_HIP(hipEventRecord(s->ev[2], st));
         if (kron) {
-            if (int rc = apply_kron(st, s, s->r, s->z)) return rc;
+            if (int rc = apply_dense(st, s, s->r, s->z)) return rc;
         }
         if (timed) IGX_HIP(hipEventRecord(s->ev[3], st));
         if (kron) k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->z, nullptr, nullptr, pB, nullptr);

@@ -4,11 +4,13 @@
 The dof numbering is the reference's: the non-shared dofs of patch p get ``M_ofs[p]`` plus their rank in tensor-product
 order, shared dof ``sd`` gets ``M_ofs[-1] + sd`` in the order ``join_dofs`` creates them.  The global matrix
 ``sum_p X_p A_p X_p^T`` is formed on the device (``igx_multipatch_*``, pyiga_amd/csrc/multipatch.hip): its pattern once per
-``Multipatch``, then one scatter pass per patch straight from the patch's device values.  Scalar problems only.
+``Multipatch``, then one scatter pass per patch straight from the patch's device values.  Scalar problems only.  The sums can
+also stay on the device and be solved there: ``pyiga_amd.solvers.MultipatchSystem``.
 """
 import ctypes as C
 import itertools
 import time
+import weakref
 
 import numpy as np
 import scipy.sparse
@@ -169,7 +171,9 @@ class Multipatch:
         self.shared_per_patch = [dict() for _ in self.patches]
         self.shared_dofs = []
         self._handle = None
+        self._ctx = None                          # the context the handle lives on
         self._pattern = None
+        self._solvers = weakref.WeakSet()         # live device solvers over the sums of the handle (destroyed before it)
         self.last_sources, self.last_paths, self.timings = [], [], {}
         if automatch:
             connected, interfaces = detect_interfaces(self.patches)
@@ -262,9 +266,11 @@ class Multipatch:
 
     # -- device side
     def _drop_device(self):
+        for solver in list(getattr(self, '_solvers', ())):
+            solver._release()
         if self._handle:
             _lib.load().igx_multipatch_destroy(self._handle)
-        self._handle, self._pattern = None, None
+        self._handle, self._ctx, self._pattern = None, None, None
 
     def close(self):
         """Free the device pattern and sums (rebuilt on the next assembly)."""
@@ -294,7 +300,7 @@ class Multipatch:
             h = lib.igx_multipatch_create(dps[0].ctx.handle, self.numpatches, handles, ptrs, self.numdofs)
             if not h:
                 raise _lib.IgxError('igx_multipatch_create failed: ' + _lib.last_error())
-            self._handle = h
+            self._handle, self._ctx = h, dps[0].ctx
         finally:
             for d in dps:
                 d.close()
@@ -349,13 +355,25 @@ class Multipatch:
         all patches (arguments as for :func:`pyiga_amd.assemble.assemble`).  Each patch is assembled in turn and scattered
         into the global sums on the device -- from the patch's device values when the assembler leaves them there -- and
         its device memory is freed before the next one.  The pattern keeps entries whose values sum to 0."""
-        from . import assemble as asm_mod
-        from .assemblers import _DeviceAssembler, _ParametricFormAssembler
         if bfuns is not None:
             raise NotImplementedError('vector-valued multipatch problems are not supported')
+        h = self._sum_system(problem, rhs, args, symmetric, format, layout, kwargs)
+        indptr, indices = self.pattern()
+        data = np.empty(indices.shape[0])
+        b = np.empty(self.numdofs)
+        _lib.check(_lib.load().igx_multipatch_download(h, _lib.dptr(data), _lib.dptr(b)), 'igx_multipatch_download')
+        A = scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(self.numdofs, self.numdofs))
+        return A.asformat(format), b
+
+    def _sum_system(self, problem, rhs, args, symmetric, format, layout, kwargs, on_assembler=None):
+        """Restart the device sums and add every patch's matrix and right-hand side to them (the loop of
+        :meth:`assemble_system`); returns the handle, the sums left on the device.  `on_assembler(p, asm)` is called with each
+        patch's assembler before it assembles."""
+        from . import assemble as asm_mod
+        from .assemblers import _DeviceAssembler, _ParametricFormAssembler
         lib = _lib.load()
         h = self._device()
-        indptr, indices = self.pattern()
+        self.pattern()
         args = dict(args or {})
         args.update(kwargs)
         _lib.check(lib.igx_multipatch_zero(h), 'igx_multipatch_zero')
@@ -369,6 +387,8 @@ class Multipatch:
             device = (isinstance(asm, _DeviceAssembler) and not isinstance(asm, _ParametricFormAssembler) and layout == 'blocked'
                       and not (symmetric and not getattr(asm, '_symmetric_form', True)))
             try:
+                if on_assembler is not None:
+                    on_assembler(p, asm)
                 if device:
                     asm.patch.assemble(asm._kind, to_host=False)
                     self.last_paths.append(asm.patch.last_path())
@@ -391,9 +411,5 @@ class Multipatch:
             if b_p.shape[0] != self.N[p]:
                 raise ValueError('patch %d: right-hand side has %d entries, expected %d' % (p, b_p.shape[0], self.N[p]))
             _lib.check(lib.igx_multipatch_scatter_vector(h, p, _lib.dptr(b_p)), 'igx_multipatch_scatter_vector')
-        data = np.empty(indices.shape[0])
-        b = np.empty(self.numdofs)
-        _lib.check(lib.igx_multipatch_download(h, _lib.dptr(data), _lib.dptr(b)), 'igx_multipatch_download')
         self.timings.update(assemble_ms=t_asm, scatter_ms=t_sc)
-        A = scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(self.numdofs, self.numdofs))
-        return A.asformat(format), b
+        return h

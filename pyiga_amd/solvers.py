@@ -8,6 +8,11 @@ pairs ``(K_k, M_k)`` are solved on the host (setup); the application ``(x)U_k . 
 Dirichlet problem there by preconditioned CG (``igx_solver_*``, pyiga_amd/csrc/solve.hip).  The matrix never leaves the
 device; only the solution vector comes back.  What the reference does with ``RestrictedLinearSystem`` and ``make_solver`` /
 ``cg`` on a host matrix.
+
+``MultipatchSystem(MP, problem, rhs, bcs)``: the same for the global system of a ``Multipatch``.  The sums
+``sum_p X_p A_p X_p^T`` and ``sum_p X_p b_p`` are formed on the device and solved there (CSR SpMV over the global pattern;
+Jacobi or an additive Schwarz preconditioner of one fast-diagonalization solve per patch); only the Dirichlet values go up
+and only the solution comes down.
 """
 import ctypes as C
 
@@ -209,3 +214,207 @@ class PatchSystem:
         d_y = DeviceArray(self.patch.ctx, self.n)
         _lib.check(_lib.load().igx_solver_spmv_d(self.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d')
         return d_y.download()
+
+
+################################################################################
+# Multi-patch Dirichlet problems on the device
+################################################################################
+
+def schwarz_boxes(shapes, maps, fixed):
+    """The box of every patch for the Schwarz preconditioner: ``[(lo, hi), ...]`` with ``lo[k] <= i_k < hi[k]``.
+
+    `shapes`: dofs per axis of each patch; `maps`: the local-to-global index of each patch (``patch_to_global_idx``); `fixed`:
+    the fixed global dofs.  Axis k of patch p drops its first index if the whole side ``(k, 0)`` of the patch is fixed and its
+    last index if the whole side ``(k, 1)`` is.  Other fixed local dofs stay in the box (the device masks them)."""
+    nglobal = max([int(np.max(m)) + 1 for m in maps if len(m)] + [0])
+    fixed = np.asarray(fixed, dtype=np.int64).ravel()
+    mask = np.zeros(max(nglobal, int(fixed.max()) + 1 if fixed.size else 0), dtype=bool)
+    mask[fixed] = True
+    boxes = []
+    for shape, l2g in zip(shapes, maps):
+        shape = tuple(int(n) for n in shape)
+        loc = mask[np.asarray(l2g, dtype=np.int64)].reshape(shape)
+        lo, hi = [], []
+        for k, n in enumerate(shape):
+            a = 1 if np.take(loc, 0, axis=k).all() else 0
+            b = n - 1 if np.take(loc, n - 1, axis=k).all() else n
+            lo.append(a)
+            hi.append(max(a, b))
+        boxes.append((tuple(lo), tuple(hi)))
+    return boxes
+
+
+def schwarz_factors(kvs_list, boxes, kind='stiffness', mats1d=None):
+    """Per patch and axis the eigenvectors ``U`` and eigenvalues ``lam`` of the 1D matrices on the box range, and the
+    ``IGX_KRON_*`` mode: ``eigh(K_k, M_k)`` with ``IGX_KRON_SUM`` for stiffness, ``eigh(M_k)`` with ``IGX_KRON_PRODUCT`` for
+    mass (as :class:`PatchSystem`).  A floating stiffness patch -- no wholly fixed side, ``sum lam`` has a zero -- gets
+    ``sigma / d`` added to every ``lam_k``, ``sigma = min_k lam_k[1]``: the inverse of the fast diagonalization of
+    ``K + sigma M``, symmetric positive definite.  `mats1d(kv)`: ``(K, M)`` of a knot vector (default: the device's
+    ``bsp_stiffness_1d`` / ``bsp_mass_1d``)."""
+    if kind not in ('mass', 'stiffness'):
+        raise ValueError('the Schwarz preconditioner has a Kronecker set-up for mass and stiffness only, not %r' % (kind,))
+    if mats1d is None:
+        from .assemble import bsp_mass_1d, bsp_stiffness_1d
+
+        def mats1d(kv):
+            return (bsp_stiffness_1d(kv) if kind == 'stiffness' else None), bsp_mass_1d(kv)
+    U, lam = [], []
+    for kvs, (lo, hi) in zip(kvs_list, boxes):
+        Up, Lp = [], []
+        for kv, a, b in zip(kvs, lo, hi):
+            K, M = mats1d(kv)
+            M = _dense(M)[a:b, a:b]
+            if kind == 'stiffness':
+                w, V = scipy.linalg.eigh(_dense(K)[a:b, a:b], M)
+            else:
+                w, V = scipy.linalg.eigh(M)
+            Up.append(np.ascontiguousarray(V))
+            Lp.append(np.ascontiguousarray(w))
+        floating = all(a == 0 for a in lo) and all(b == kv.numdofs for b, kv in zip(hi, kvs))
+        if kind == 'stiffness' and floating and all(len(l) > 1 for l in Lp):
+            sigma = min(l[1] for l in Lp)
+            Lp = [l + sigma / len(Lp) for l in Lp]
+        U.append(Up)
+        lam.append(Lp)
+    return U, lam, (_lib.IGX_KRON_SUM if kind == 'stiffness' else _lib.IGX_KRON_PRODUCT)
+
+
+class MultipatchSystem:
+    """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, of the global system of the multipatch `MP`, summed and
+    solved on the device.
+
+    `problem`, `rhs`, `args` / `kwargs`: as for ``MP.assemble_system`` (the same per-patch assemblies and scatters; the sums stay
+    on the device).  The form must be symmetric (CG): a form whose assembler declares ``_symmetric_form = False`` is refused.
+    `bcs`: ``(indices, values)`` as ``MP.compute_dirichlet_bcs`` returns them, or None.  ``solve(...)`` returns the completed
+    global vector and leaves the solver's statistics in ``info``.  The system reads the sums `MP` holds: a later
+    ``MP.assemble_system`` restarts them (a solve then raises), and ``MP.close()`` destroys the system's device solver.
+    """
+
+    def __init__(self, MP, problem, rhs, bcs=None, args=None, **kwargs):
+        self.handle = None
+        self.MP = MP
+        kinds = []
+
+        def inspect(p, asm):
+            if not getattr(asm, '_symmetric_form', True):
+                raise ValueError('MultipatchSystem solves by CG and needs a form known to be symmetric; the assembler of patch %d '
+                                 '(%s) cannot show that its form is (general form strings never can).  Accepted: the built-in '
+                                 "mass and stiffness forms ('u*v*dx', 'inner(grad(u),grad(v))*dx') and assemblers that do not "
+                                 'declare _symmetric_form = False' % (p, type(asm).__name__))
+            kinds.append(getattr(asm, '_kind', None))
+        h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect)
+        self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
+        self.n = MP.numdofs
+        if bcs is None:
+            idx, vals = np.zeros(0, dtype=np.int64), np.zeros(0)
+        else:
+            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
+            vals = np.broadcast_to(np.asarray(bcs[1], dtype=np.float64), idx.shape)
+            idx, first = np.unique(idx, return_index=True)
+            vals = vals[first]
+        self.bc_indices, self.bc_values = idx, np.ascontiguousarray(vals)
+        self._precond = None
+        self._schwarz = False
+        self.info = None
+        out = C.c_void_p()
+        _lib.check(_lib.load().igx_solver_create_multipatch(h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, C.byref(out)),
+                   'igx_solver_create_multipatch')
+        self.handle = out.value
+        self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
+        MP._solvers.add(self)
+
+    def _release(self):
+        if getattr(self, 'handle', None):
+            _lib.load().igx_solver_destroy(self.handle)
+            self.handle = None
+
+    def close(self):
+        self._release()
+        MP = getattr(self, 'MP', None)
+        if MP is not None:
+            MP._solvers.discard(self)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.handle:
+            raise _lib.IgxError('MultipatchSystem: the solver was closed (or its Multipatch was closed or re-joined)')
+        return self.handle
+
+    def schwarz_setup(self):
+        """Boxes, factors and mode of the Schwarz preconditioner (host set-up)."""
+        MP = self.MP
+        shapes = [tuple(kv.numdofs for kv in kvs) for kvs, _ in MP.patches]
+        maps = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
+        boxes = schwarz_boxes(shapes, maps, self.bc_indices)
+        U, lam, mode = schwarz_factors([tuple(kvs) for kvs, _ in MP.patches], boxes, self.kind)
+        return boxes, U, lam, mode
+
+    def set_precond(self, precond):
+        key = precond if precond is not None else 'none'
+        if key not in _lib.MP_PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        if key == self._precond:
+            return
+        lib = _lib.load()
+        if key == 'schwarz' and not self._schwarz:
+            boxes, U, lam, mode = self.schwarz_setup()
+            P = len(boxes)
+            lo = (C.c_int32 * (3 * P))(*[b[0][k] if k < len(b[0]) else 0 for b in boxes for k in range(3)])
+            hi = (C.c_int32 * (3 * P))(*[b[1][k] if k < len(b[1]) else 0 for b in boxes for k in range(3)])
+            Up = (_lib._dp * (3 * P))(*[_lib.dptr(u[k]) if k < len(u) else None for u in U for k in range(3)])
+            Lp = (_lib._dp * (3 * P))(*[_lib.dptr(l[k]) if k < len(l) else None for l in lam for k in range(3)])
+            _lib.check(lib.igx_solver_set_schwarz(h, lo, hi, Up, Lp, mode), 'igx_solver_set_schwarz')
+            self._schwarz = True
+        else:
+            _lib.check(lib.igx_solver_set_precond(h, _lib.MP_PRECONDS[key], None, None, None, None, 0), 'igx_solver_set_precond')
+        self._precond = key
+
+    def solve(self, tol=1e-8, maxiter=1000, precond='jacobi', x0=None, check_every=1, timed=False, b=None):
+        """CG to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the global solution vector (the Dirichlet values included).
+        The right-hand side is the summed vector on the device unless a host vector `b` is given.
+
+        `precond`: 'jacobi' (default), 'schwarz' or None.  Schwarz takes far fewer iterations, but each of them applies one
+        fast-diagonalization solve per patch, a few small GEMMs that leave most of the device idle on 2D patches: on the 2D
+        notebook domain (p = 3, n = 256) it takes 2.7x fewer iterations and 4x the time of Jacobi.  It pays in 3D and on
+        ill-conditioned systems."""
+        self.set_precond(precond)
+        u = np.empty(self.n)
+        x0a = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).ravel()
+        if x0a is not None and x0a.size != self.n:
+            raise ValueError('x0 has the wrong size')
+        ba = None if b is None else np.ascontiguousarray(b, dtype=np.float64).ravel()
+        if ba is not None and ba.size != self.n:
+            raise ValueError('b has the wrong size')
+        info = _lib.SolveInfo()
+        _lib.check(_lib.load().igx_solver_solve(self._live(), None if ba is None else _lib.dptr(ba), _lib.dptr(self.bc_values),
+                                                None if x0a is None else _lib.dptr(x0a), float(tol), int(maxiter),
+                                                int(check_every), 1 if timed else 0, _lib.dptr(u), C.byref(info)),
+                   'igx_solver_solve')
+        self.info = dict(info.as_dict(), converged=bool(info.converged), precond=self._precond)
+        return u
+
+    def _device_op(self, fn, what, x):
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if x.size != self.n:
+            raise ValueError('vector of %d entries, the system has %d' % (x.size, self.n))
+        h = self._live()
+        d_x = DeviceArray.from_host(self._ctx, x)
+        d_y = DeviceArray(self._ctx, self.n)
+        _lib.check(fn(h, d_x.ptr, d_y.ptr), what)
+        return d_y.download()
+
+    def spmv(self, x):
+        """``R A R^T x`` on the device (global vectors in and out)."""
+        return self._device_op(_lib.load().igx_solver_spmv_d, 'igx_solver_spmv_d', x)
+
+    def apply_precond(self, r, precond=None):
+        """``z = P r`` on the device with the preconditioner of the last solve, or `precond` if given."""
+        if precond is not None:
+            self.set_precond(precond)
+        return self._device_op(_lib.load().igx_solver_precond_d, 'igx_solver_precond_d', r)
