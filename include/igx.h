@@ -460,6 +460,29 @@ int igx_solver_spmv_d(igx_solver *solver, const double *d_x, double *d_y);
 int igx_solver_solve(igx_solver *solver, const double *b, const double *g, const double *x0, double tol, int maxiter,
                      int check_every, int timed, double *u, igx_solve_info *info);
 
+/* --- Non-symmetric Dirichlet problems: right-preconditioned BiCGStab (van der Vorst; the "Templates" variant that
+   scipy.sparse.linalg.bicgstab runs).  r stays the true residual, so the stopping rule is CG's.  Two SpMVs and two applies of the
+   preconditioner per iteration; its scalars stay on the device.  When rho = r^.r has cancelled to below eps^2 times the sum of
+   the magnitudes of its terms, the iteration restarts with r^ = p = r.  The solve stops without converging (info->converged = 0)
+   on a breakdown: rho vanishing again right after a restart, a step 1e-13 |alpha| ||v|| > ||r|| (r^.v vanished), t.t = 0 or
+   omega = 0, or a non-finite scalar.  u is then the last finite iterate.  A solve that has stopped leaves x and r as they are, so
+   check_every does not change u; info->iterations counts the iterations entered. */
+enum { IGX_METHOD_CG = 0, IGX_METHOD_BICGSTAB = 1 };
+enum { IGX_BREAKDOWN_RHO = 1,        /* rho = r^.r vanished twice in a row (the restart with r^ = r did not help) */
+       IGX_BREAKDOWN_ALPHA = 2,      /* r^.v vanished: the step alpha v would exceed 1e13 ||r|| */
+       IGX_BREAKDOWN_OMEGA = 3,      /* t.t = 0 or omega = 0: the half step x + alpha p^ is kept */
+       IGX_BREAKDOWN_NONFINITE = 4 };/* a scalar was not finite */
+/* As igx_solver_create, for any kind the patch holds on the device (IGX_MASS, IGX_STIFFNESS, IGX_CONVDIFF, IGX_FORM; another
+   value: IGX_ERR_ARG), with the same refusals (row slabs and span boxes, values not assembled or stale).  Starts in
+   IGX_METHOD_BICGSTAB.  The patch's values must be the whole matrix of the form (a parametric jet form assembled in passes
+   leaves only the last pass on the device). */
+int  igx_solver_create_general(igx_patch *patch, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out);
+/* The method of the following solves, on any solver.  IGX_METHOD_CG on a patch solver of a kind other than IGX_MASS /
+   IGX_STIFFNESS: IGX_ERR_UNSUPPORTED.  IGX_METHOD_BICGSTAB allocates its four extra vectors once (a CG solver has none). */
+int  igx_solver_set_method(igx_solver *solver, int method);
+/* IGX_BREAKDOWN_* of the last solve, 0 if it did not break down (and for CG). */
+int  igx_solver_last_breakdown(const igx_solver *solver);
+
 /* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers.  The factors are dense, row-major, m[k] x n[k]
    (rectangular allowed).  x and y are tensors of shape (n_0, .., n_{dim-1}, batch) and (m_0, .., batch), addressed through an
    element offset and four strides (axis 3 = the trailing batch axis), so a sub-box of a longer vector can be read or written.

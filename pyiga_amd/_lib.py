@@ -65,6 +65,11 @@ IGX_PRECOND_NONE, IGX_PRECOND_JACOBI, IGX_PRECOND_KRON, IGX_PRECOND_SCHWARZ = 0,
 IGX_KRON_SUM, IGX_KRON_PRODUCT = 1, 2
 PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'kron': IGX_PRECOND_KRON}
 MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ}
+IGX_METHOD_CG, IGX_METHOD_BICGSTAB = 0, 1
+METHODS = {'cg': IGX_METHOD_CG, 'bicgstab': IGX_METHOD_BICGSTAB}
+IGX_BREAKDOWN_RHO, IGX_BREAKDOWN_ALPHA, IGX_BREAKDOWN_OMEGA, IGX_BREAKDOWN_NONFINITE = 1, 2, 3, 4
+BREAKDOWNS = {0: None, IGX_BREAKDOWN_RHO: 'rho', IGX_BREAKDOWN_ALPHA: 'alpha', IGX_BREAKDOWN_OMEGA: 'omega',
+              IGX_BREAKDOWN_NONFINITE: 'nonfinite'}
 
 
 class SolveInfo(C.Structure):
@@ -150,6 +155,9 @@ SYMBOLS = [
     ('igx_multipatch_scatter_vector', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_multipatch_download', C.c_int, [C.c_void_p, _dp, _dp]),
     ('igx_solver_create', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_create_general', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_set_method', C.c_int, [C.c_void_p, C.c_int]),
+    ('igx_solver_last_breakdown', C.c_int, [C.c_void_p]),
     ('igx_solver_create_multipatch', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
     ('igx_solver_destroy', None, [C.c_void_p]),
     ('igx_solver_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),

@@ -15,6 +15,9 @@
 //              (k_box_scatter), patch after patch.
 //   vector     fused CG updates and fixed-order two-pass dot products (fixed grid, fixed trees): two solves of the same
 //              system give bit-identical results.  alpha and beta stay in device memory.
+//   BiCGStab   for non-symmetric matrices (igx_solver_create_general / igx_solver_set_method): the same SpMVs and
+//              preconditioners, fused p / s / x-r updates that emit their dot partials, and k_fin_bicg for rho, alpha, omega,
+//              the stop and breakdown on the device.
 #include "igx_internal.h"
 
 #include <algorithm>
@@ -338,6 +341,157 @@ __global__ void k_pupdate(long long n, const double *z, double *p, const double 
 }
 
 // ---------------------------------------------------------------------------------------------
+// BiCGStab (right-preconditioned, the "Templates" variant).  Its scalars live in a block of their own (BS_*)
+// that only k_fin_bicg writes.  BS_DONE freezes the solve: every update kernel returns at once when it is set, so iterations run
+// past the stop (check_every > 1) change neither x nor r.  BS_LAST marks the x / r update of this iteration as the final one
+// (||s|| small enough, or omega broke down: x += alpha p^, r = s); the next FB_RHO then sets BS_DONE.  BS_RESTART makes k_bicg_p
+// start afresh from the current residual (r^ = p = r).
+enum { BS_RHO = 0, BS_RHO_OLD, BS_ALPHA, BS_OMEGA, BS_BETA, BS_RR, BS_IT, BS_DONE, BS_LAST, BS_CONV, BS_REASON, BS_RESTART,
+       BS_RESTART_IT, BS_NRESTART, BS_N = 16 };
+enum { FB_INIT = 0, FB_RHO, FB_ALPHA, FB_S, FB_OMEGA };
+// Breakdown.  rho = r^.r is zero once it has cancelled to below BICG_EPS_RHO times the sum of the magnitudes of its terms (scipy's
+// eps^2, made independent of the scale): the iteration restarts with r^ = p = r, and stops (IGX_BREAKDOWN_RHO) only if rho
+// vanishes again in the iteration right after a restart.  r^.v is zero when the step it gives is absurd:
+// BICG_EPS_ALPHA |alpha| ||v|| > ||r||.
+// (Near-breakdowns that BiCGStab survives -- r^.v cancelled to 1e-16 of its terms with a step of 200 ||r|| on the convection-
+// dominated notebook problem -- pass; a skew-symmetric R A R^T, where r0.A r0 = 0, stops in its first iteration.)
+constexpr double BICG_EPS_RHO = 2.220446049250313e-16 * 2.220446049250313e-16;
+constexpr double BICG_EPS_ALPHA = 1e-13;
+
+__device__ __forceinline__ bool is_fin(double v) { return v - v == 0.0; }
+
+// one block: sums of the partials in a fixed order (partA: nA of them, partB and partC: nB), then the BiCGStab scalars of step `op`
+__global__ void __launch_bounds__(BLOCK) k_fin_bicg(const double *partA, int nA, const double *partB, int nB, const double *partC,
+                                                    double *sc, int op, double stop)
+{
+    __shared__ double sh[BLOCK];
+    if (sc[BS_DONE] != 0.0) return;                               // (uniform: nothing below changes once stopped)
+    double a = 0.0, bsum = 0.0, csum = 0.0;
+    for (int k = threadIdx.x; k < nA; k += BLOCK) a += partA[k];
+    for (int k = threadIdx.x; k < nB; k += BLOCK) {
+        bsum += partB[k];
+        if (partC) csum += partC[k];
+    }
+    a = block_sum(a, sh);
+    if (partB) bsum = block_sum(bsum, sh);
+    if (partC) csum = block_sum(csum, sh);
+    if (threadIdx.x != 0) return;
+    auto halt = [&](int conv, int reason) { sc[BS_DONE] = 1.0; sc[BS_CONV] = conv; if (reason) sc[BS_REASON] = reason; };
+    switch (op) {
+    case FB_INIT:                                                 // a = r.r (r^ = r)
+        bsum = csum = a;
+        [[fallthrough]];
+    case FB_RHO: {                                                // a = r.r, bsum = r^.r, csum = sum |r^_i r_i|
+        const double rr = a, rho = bsum;
+        sc[BS_RR] = rr;
+        if (sc[BS_LAST] != 0.0) { sc[BS_DONE] = 1.0; return; }   // (BS_CONV / BS_REASON set with BS_LAST)
+        if (!is_fin(rr) || !is_fin(rho)) { halt(0, IGX_BREAKDOWN_NONFINITE); return; }
+        if (sqrt(rr) <= stop) { halt(1, 0); return; }
+        if (fabs(rho) <= BICG_EPS_RHO * csum) {
+            if (sc[BS_NRESTART] > 0.0 && sc[BS_RESTART_IT] == sc[BS_IT] - 1.0) { halt(0, IGX_BREAKDOWN_RHO); return; }
+            sc[BS_RESTART] = 1.0;                                 // r^ = p = r: rho = r.r
+            sc[BS_RESTART_IT] = sc[BS_IT];
+            sc[BS_NRESTART] += 1.0;
+            sc[BS_BETA] = 0.0;
+            sc[BS_RHO] = sc[BS_RHO_OLD] = rr;
+            return;
+        }
+        const double beta = sc[BS_IT] > 0.0 ? (rho / sc[BS_RHO_OLD]) * (sc[BS_ALPHA] / sc[BS_OMEGA]) : 0.0;
+        if (!is_fin(beta)) { halt(0, IGX_BREAKDOWN_NONFINITE); return; }
+        sc[BS_BETA] = beta;
+        sc[BS_RHO] = sc[BS_RHO_OLD] = rho;
+        return;
+    }
+    case FB_ALPHA: {                                              // a = r^.v
+        sc[BS_IT] += 1.0;                                         // an iteration is entered at its first SpMV
+        sc[BS_RESTART] = 0.0;
+        const double alpha = sc[BS_RHO] / a;
+        if (!is_fin(a) || !is_fin(alpha)) { halt(0, a == 0.0 ? IGX_BREAKDOWN_ALPHA : IGX_BREAKDOWN_NONFINITE); return; }
+        sc[BS_ALPHA] = alpha;
+        return;
+    }
+    case FB_S: {                                                  // a = s.s, bsum = v.v
+        if (!is_fin(a) || !is_fin(bsum)) { halt(0, IGX_BREAKDOWN_NONFINITE); return; }
+        if (BICG_EPS_ALPHA * fabs(sc[BS_ALPHA]) * sqrt(bsum) > sqrt(sc[BS_RR])) { halt(0, IGX_BREAKDOWN_ALPHA); return; }
+        if (sqrt(a) <= stop) { sc[BS_LAST] = 1.0; sc[BS_CONV] = 1.0; }
+        return;
+    }
+    default: {                                                    // FB_OMEGA: a = t.s, bsum = t.t
+        if (sc[BS_LAST] != 0.0) { sc[BS_OMEGA] = 0.0; return; }
+        const double omega = a / bsum;
+        if (!is_fin(omega) || omega == 0.0) {                     // (t.t == 0 included) keep the half step x + alpha p^ and stop
+            sc[BS_OMEGA] = 0.0;
+            sc[BS_LAST] = 1.0;
+            sc[BS_REASON] = is_fin(a) && is_fin(bsum) ? IGX_BREAKDOWN_OMEGA : IGX_BREAKDOWN_NONFINITE;
+            return;
+        }
+        sc[BS_OMEGA] = omega;
+        return;
+    }
+    }
+}
+
+// p = r + beta (p - omega v), or r^ = p = r on a restart; (Jacobi: ph = dinv p)
+__global__ void k_bicg_p(long long n, const double *r, double *p, const double *v, const double *dinv, double *ph, double *rh,
+                         const double *sc)
+{
+    if (sc[BS_DONE] != 0.0) return;
+    const double beta = sc[BS_BETA], omega = sc[BS_OMEGA];
+    const bool restart = sc[BS_RESTART] != 0.0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const double pi = restart ? r[i] : r[i] + beta * (p[i] - omega * v[i]);
+        if (restart) rh[i] = pi;
+        p[i] = pi;
+        if (dinv) ph[i] = dinv[i] * pi;
+    }
+}
+
+// s = r - alpha v; (Jacobi: sh = dinv s); partials of s.s and v.v
+__global__ void __launch_bounds__(BLOCK) k_bicg_s(long long n, const double *r, const double *v, double *s, const double *dinv, double *sh_,
+                                                  const double *sc, double *partA, double *partB)
+{
+    __shared__ double sh[BLOCK];
+    if (sc[BS_DONE] != 0.0) return;
+    const double alpha = sc[BS_ALPHA];
+    double ss = 0.0, vv = 0.0;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
+        const double vi = v[i], si = r[i] - alpha * vi;
+        s[i] = si;
+        if (dinv) sh_[i] = dinv[i] * si;
+        ss += si * si;
+        vv += vi * vi;
+    }
+    ss = block_sum(ss, sh);
+    vv = block_sum(vv, sh);
+    if (threadIdx.x == 0) { partA[blockIdx.x] = ss; partB[blockIdx.x] = vv; }
+}
+
+// x += alpha ph [+ omega sh]; r = s [- omega t]; partials of r.r, r^.r and sum |r^_i r_i|
+__global__ void __launch_bounds__(BLOCK) k_bicg_xr(long long n, double *x, double *r, const double *ph, const double *sh_, const double *s,
+                                                   const double *t, const double *rh, const double *sc, double *partA, double *partB,
+                                                   double *partC)
+{
+    __shared__ double sh[BLOCK];
+    if (sc[BS_DONE] != 0.0) return;
+    const double alpha = sc[BS_ALPHA], omega = sc[BS_OMEGA];
+    double rr = 0.0, rhr = 0.0, arhr = 0.0;
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK) {
+        double xi = x[i] + alpha * ph[i], ri = s[i];
+        if (omega != 0.0) { xi += omega * sh_[i]; ri -= omega * t[i]; }     // (omega = 0: the half step; sh, t are not read)
+        x[i] = xi;
+        r[i] = ri;
+        const double q = rh[i] * ri;
+        rr += ri * ri;
+        rhr += q;
+        arhr += fabs(q);
+    }
+    rr = block_sum(rr, sh);
+    rhr = block_sum(rhr, sh);
+    arhr = block_sum(arhr, sh);
+    if (threadIdx.x == 0) { partA[blockIdx.x] = rr; partB[blockIdx.x] = rhr; partC[blockIdx.x] = arhr; }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Kronecker contraction of tensor dim kd (of 4: three spatial axes + a trailing batch axis):
 //     Y[..., i, ...] = (sum_j B[i][j] X[..., j, ...]) [ / D(i0, i1, i2) ]
 // A GEMM of B (m x n) with the matrix X whose columns are the other three tensor indices (C order).  Tile 64 x 64 of (i, column),
@@ -560,6 +714,14 @@ struct igx_solver {
     double *d_box = nullptr;                  // Schwarz: one patch's box (gathered residual, then the local correction)
     hipEvent_t ev[6] = {};
     bool have_ev = false;
+    // BiCGStab (allocated only once a solver is switched to it): v = q, p^ = z; r^ | s | s^ | t in d_bvec, its scalars in d_bsc
+    int method = IGX_METHOD_CG;
+    double *d_bvec = nullptr;
+    double *rh = nullptr, *sv = nullptr, *sh = nullptr, *t = nullptr;
+    double *d_bsc = nullptr;
+    int breakdown = 0;                        // reason of the last BiCGStab solve (IGX_BREAKDOWN_*), 0 if none
+    hipEvent_t bev[8] = {};
+    bool have_bev = false;
 };
 
 namespace {
@@ -686,8 +848,11 @@ void free_solver(igx_solver *s)
 {
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
     (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
+    (void)hipFree(s->d_bvec); (void)hipFree(s->d_bsc);
     if (s->have_ev)
         for (auto &e : s->ev) (void)hipEventDestroy(e);
+    if (s->have_bev)
+        for (auto &e : s->bev) (void)hipEventDestroy(e);
     delete s;
 }
 
@@ -727,32 +892,128 @@ int init_vectors(igx_solver *s, const char *what)
     return IGX_OK;
 }
 
+// the BiCGStab vectors, scalars and events of a solver (once; a CG-only solver never has them)
+int init_bicgstab(igx_solver *s, const char *what)
+{
+    if (s->d_bvec) return IGX_OK;
+    const size_t n = (size_t)s->n;
+    if (hipMalloc((void **)&s->d_bvec, 4 * n * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&s->d_bsc, BS_N * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(s->d_bvec); s->d_bvec = nullptr;
+        set_error("%s: out of device memory (%.3f GB)", what, 4.0 * 8 * n / 1e9);
+        return IGX_ERR_NOMEM;
+    }
+    hipError_t e = hipMemsetAsync(s->d_bvec, 0, 4 * n * sizeof(double), s->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
+    s->rh = s->d_bvec; s->sv = s->d_bvec + n; s->sh = s->d_bvec + 2 * n; s->t = s->d_bvec + 3 * n;
+    for (auto &ev : s->bev)
+        if (hipEventCreate(&ev) != hipSuccess) { set_error("%s: hipEventCreate failed", what); return IGX_ERR_HIP; }
+    s->have_bev = true;
+    return IGX_OK;
+}
+
+// Right-preconditioned BiCGStab on R A R^T x = r0 (r0 = R (b - A ext(g)) - R A R^T x0 in s->r, ||R (b - A ext(g))|| = bnorm).
+// Per iteration: p = r + beta (p - omega v), p^ = M p, v = A p^ (and r^.v), s = r - alpha v (and s.s, v.v; Jacobi: s^ = M s),
+// s^ = M s, t = A s^ (and t.s), t.t, x += alpha p^ + omega s^, r = s - omega t (and r.r, r^.r).  Every scalar is formed on the
+// device by k_fin_bicg; the host reads BS_* back every check_every iterations to decide whether to go on.
+int solve_bicgstab(hipStream_t st, igx_solver *s, double bnorm, double tol, int maxiter, int check_every, int timed, igx_solve_info &inf)
+{
+    const long long n = s->n;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    const unsigned nbv = vec_blocks(n), nbs = spmv_blocks(s);
+    double *pA = s->d_part, *pB = s->d_part + NB_SPMV_MAX;
+    double *pC = pA + NB_VEC;                    // (vector kernels write at most NB_VEC partials into pA: pC follows them)
+    const bool dense = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ, jac = s->precond == IGX_PRECOND_JACOBI;
+    double *v = s->q;
+    double *ph = (dense || jac) ? s->z : s->p, *sh = (dense || jac) ? s->sh : s->sv;
+    const double *dinv = jac ? s->dinv : nullptr;
+    const double stop = tol * bnorm;
+    IGX_HIP(hipMemsetAsync(s->d_bsc, 0, BS_N * sizeof(double), st));
+    IGX_HIP(hipMemsetAsync(s->sh, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->t, 0, nbytes, st));
+    IGX_HIP(hipMemcpyAsync(s->rh, s->r, nbytes, hipMemcpyDeviceToDevice, st));       // r^ = r0
+    k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
+    k_fin_bicg<<<1, BLOCK, 0, st>>>(pA, nbv, nullptr, 0, nullptr, s->d_bsc, FB_INIT, stop);
+    IGX_HIP(hipGetLastError());
+    double h[BS_N] = {};
+    auto readback = [&]() -> int {
+        IGX_HIP(hipMemcpyAsync(h, s->d_bsc, sizeof(h), hipMemcpyDeviceToHost, st));
+        IGX_HIP(hipStreamSynchronize(st));
+        return IGX_OK;
+    };
+    if (int rc = readback()) return rc;
+    hipEvent_t *E = s->bev;
+    for (int it = 0; h[BS_DONE] == 0.0 && it < maxiter;) {
+        ++it;
+        if (timed) IGX_HIP(hipEventRecord(E[0], st));
+        k_bicg_p<<<nbv, BLOCK, 0, st>>>(n, s->r, s->p, v, dinv, ph, s->rh, s->d_bsc);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(E[1], st));
+        if (dense) { if (int rc = apply_dense(st, s, s->p, ph)) return rc; }
+        if (timed) IGX_HIP(hipEventRecord(E[2], st));
+        if (int rc = spmv(st, s, ph, nullptr, 1.0, v, s->rh, pA)) return rc;
+        if (timed) IGX_HIP(hipEventRecord(E[3], st));
+        k_fin_bicg<<<1, BLOCK, 0, st>>>(pA, nbs, nullptr, 0, nullptr, s->d_bsc, FB_ALPHA, stop);
+        k_bicg_s<<<nbv, BLOCK, 0, st>>>(n, s->r, v, s->sv, dinv, sh, s->d_bsc, pA, pB);
+        k_fin_bicg<<<1, BLOCK, 0, st>>>(pA, nbv, pB, nbv, nullptr, s->d_bsc, FB_S, stop);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(E[4], st));
+        if (dense) { if (int rc = apply_dense(st, s, s->sv, sh)) return rc; }
+        if (timed) IGX_HIP(hipEventRecord(E[5], st));
+        if (int rc = spmv(st, s, sh, nullptr, 1.0, s->t, s->sv, pA)) return rc;
+        if (timed) IGX_HIP(hipEventRecord(E[6], st));
+        k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->t, s->t, nullptr, nullptr, pB, nullptr);
+        k_fin_bicg<<<1, BLOCK, 0, st>>>(pA, nbs, pB, nbv, nullptr, s->d_bsc, FB_OMEGA, stop);
+        k_bicg_xr<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, ph, sh, s->sv, s->t, s->rh, s->d_bsc, pA, pB, pC);
+        k_fin_bicg<<<1, BLOCK, 0, st>>>(pA, nbv, pB, nbv, pC, s->d_bsc, FB_RHO, stop);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(E[7], st));
+        if (timed || it % check_every == 0 || it == maxiter) {
+            if (int rc = readback()) return rc;
+            if (timed) {
+                float ms[7] = {};
+                for (int k = 0; k < 7; ++k) (void)hipEventElapsedTime(&ms[k], E[k], E[k + 1]);
+                inf.spmv_ms += ms[2] + ms[5];
+                inf.precond_ms += ms[1] + ms[4];
+                inf.vector_ms += ms[0] + ms[3] + ms[6];
+            }
+        }
+    }
+    inf.iterations = (int)h[BS_IT];
+    inf.converged = h[BS_CONV] != 0.0 ? 1 : 0;
+    inf.relres = bnorm > 0.0 ? std::sqrt(h[BS_RR]) / bnorm : 0.0;
+    s->breakdown = (int)h[BS_REASON];
+    return IGX_OK;
+}
+
 } // namespace
 
 extern "C" {
 
-int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+} // extern "C"
+
+namespace {
+
+bool spd_kind(int kind) { return kind == IGX_MASS || kind == IGX_STIFFNESS; }
+
+// a solver over the values of `kind` the patch holds (the kind itself checked by the caller)
+int create_patch_solver(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what)
 {
-    if (!out) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
-    *out = nullptr;
-    if (!pt || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
-    if (kind != IGX_MASS && kind != IGX_STIFFNESS) {
-        set_error("igx_solver_create: CG needs a symmetric positive definite matrix (IGX_MASS or IGX_STIFFNESS), kind %d", kind);
-        return IGX_ERR_UNSUPPORTED;
-    }
     if (pt->boxed || pt->row_lo != 0 || pt->row_hi != pt->nrows_total) {
-        set_error("igx_solver_create: whole patches only (no row slab, no span box)");
+        set_error("%s: whole patches only (no row slab, no span box)", what);
         return IGX_ERR_UNSUPPORTED;
     }
     if (pt->values_kind != kind || !pt->d_data) {
-        set_error("igx_solver_create: assemble the patch with this kind first (igx_assemble, data_out may be NULL)");
+        set_error("%s: assemble the patch with this kind first (igx_assemble, data_out may be NULL)", what);
         return IGX_ERR_ARG;
     }
-    if (hipSetDevice(pt->ctx->device) != hipSuccess) { set_error("igx_solver_create: hipSetDevice failed"); return IGX_ERR_HIP; }
+    if (hipSetDevice(pt->ctx->device) != hipSuccess) { set_error("%s: hipSetDevice failed", what); return IGX_ERR_HIP; }
     igx_solver *s = new igx_solver;
     s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->n = pt->nrows_total;
     for (int k = 0; k < pt->dim; ++k) s->N[k] = pt->ax[k].N;
-    if (!set_fixed(s, fixed, nfixed, "igx_solver_create")) { delete s; return IGX_ERR_ARG; }
+    if (!set_fixed(s, fixed, nfixed, what)) { delete s; return IGX_ERR_ARG; }
     // per-axis tables as a 3D layout (2D: a one-dof outer axis in front)
     const int off = 3 - pt->dim;
     std::vector<int> tab;
@@ -776,11 +1037,11 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
     s->nb_spmv = spmv_occupancy(s);
     const size_t n = (size_t)s->n;
     if (hipMalloc((void **)&s->d_tab, tab.size() * sizeof(int)) != hipSuccess) {
-        (void)hipGetLastError(); set_error("igx_solver_create: out of device memory (%.3f GB)", 8.0 * 8 * n / 1e9); free_solver(s); return IGX_ERR_NOMEM;
+        (void)hipGetLastError(); set_error("%s: out of device memory (%.3f GB)", what, 8.0 * 8 * n / 1e9); free_solver(s); return IGX_ERR_NOMEM;
     }
     hipError_t e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, pt->ctx->stream);
-    if (e != hipSuccess) { set_error("igx_solver_create: %s", hipGetErrorString(e)); free_solver(s); return IGX_ERR_HIP; }
-    if (int rc = init_vectors(s, "igx_solver_create")) { free_solver(s); return rc; }
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); free_solver(s); return IGX_ERR_HIP; }
+    if (int rc = init_vectors(s, what)) { free_solver(s); return rc; }
     for (int a = 0; a < 3; ++a) { s->g.jlo[a] = s->d_tab + pos[a][0]; s->g.jhi[a] = s->d_tab + pos[a][1]; s->g.rp[a] = s->d_tab + pos[a][2]; }
     s->g.S1 = tab[pos[1][2] + s->g.N[1]];
     s->g.S2 = tab[pos[2][2] + s->g.N[2]];
@@ -788,6 +1049,59 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
     *out = s;
     return IGX_OK;
 }
+
+} // namespace
+
+extern "C" {
+
+int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    if (!out) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
+    *out = nullptr;
+    if (!pt || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
+    if (!spd_kind(kind)) {
+        set_error("igx_solver_create: CG needs a symmetric positive definite matrix (IGX_MASS or IGX_STIFFNESS), kind %d", kind);
+        return IGX_ERR_UNSUPPORTED;
+    }
+    return create_patch_solver(pt, kind, fixed, nfixed, out, "igx_solver_create");
+}
+
+int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    if (!out) { set_error("igx_solver_create_general: null argument"); return IGX_ERR_ARG; }
+    *out = nullptr;
+    if (!pt || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create_general: null argument"); return IGX_ERR_ARG; }
+    if (kind != IGX_MASS && kind != IGX_STIFFNESS && kind != IGX_CONVDIFF && kind != IGX_FORM) {
+        set_error("igx_solver_create_general: unknown kind %d", kind);
+        return IGX_ERR_ARG;
+    }
+    igx_solver *s = nullptr;
+    if (int rc = create_patch_solver(pt, kind, fixed, nfixed, &s, "igx_solver_create_general")) return rc;
+    if (int rc = init_bicgstab(s, "igx_solver_create_general")) { free_solver(s); return rc; }
+    s->method = IGX_METHOD_BICGSTAB;
+    *out = s;
+    return IGX_OK;
+}
+
+int igx_solver_set_method(igx_solver *s, int method)
+{
+    if (!s) { set_error("igx_solver_set_method: null solver"); return IGX_ERR_ARG; }
+    if (method == IGX_METHOD_CG) {
+        if (!s->mp && !spd_kind(s->kind)) {
+            set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; kind %d is not known to be one", s->kind);
+            return IGX_ERR_UNSUPPORTED;
+        }
+        s->method = method;
+        return IGX_OK;
+    }
+    if (method != IGX_METHOD_BICGSTAB) { set_error("igx_solver_set_method: unknown method %d", method); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    if (int rc = init_bicgstab(s, "igx_solver_set_method")) return rc;
+    s->method = method;
+    return IGX_OK;
+}
+
+int igx_solver_last_breakdown(const igx_solver *s) { return s ? s->breakdown : 0; }
 
 int igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64_t nfixed, igx_solver **out)
 {
@@ -1054,6 +1368,31 @@ int igx_solver_spmv_d(igx_solver *s, const double *d_x, double *d_y)
     return IGX_OK;
 }
 
+} // extern "C"
+
+namespace {
+
+// the solution x + ext(g) to the host, the device time of the whole solve (from ev[5]) and the info block
+int finish_solve(hipStream_t st, igx_solver *s, const double *gvals, double *u, igx_solve_info *info, igx_solve_info &inf)
+{
+    IGX_HIP(hipMemcpyAsync(u, s->x, (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipEventRecord(s->ev[4], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("igx_solver_solve: kernel failure: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
+    }
+    (void)hipEventElapsedTime(&inf.total_ms, s->ev[5], s->ev[4]);
+    for (size_t k = 0; k < s->fixed.size(); ++k) u[s->fixed[k]] = gvals[k];
+    inf.n_free = s->n - (long long)s->fixed.size();
+    if (info) *info = inf;
+    return IGX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const double *x0, double tol, int maxiter, int check_every,
                      int timed, double *u, igx_solve_info *info)
 {
@@ -1061,6 +1400,7 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
     if (!(tol >= 0.0) || maxiter < 0) { set_error("igx_solver_solve: tol must be >= 0 and maxiter >= 0"); return IGX_ERR_ARG; }
     if (int rc = check_values(s, "igx_solver_solve")) return rc;
     if (check_every < 1) check_every = 1;
+    s->breakdown = 0;
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     const long long n = s->n;
@@ -1092,6 +1432,10 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
         for (long long i = 0; i < n; ++i) w[i] = s->h_free[i] ? x0[i] : 0.0;
         IGX_HIP(hipMemcpyAsync(s->x, w.data(), nbytes, hipMemcpyHostToDevice, st));
         if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
+    }
+    if (s->method == IGX_METHOD_BICGSTAB) {
+        if (int rc = solve_bicgstab(st, s, bnorm, tol, maxiter, check_every, timed, inf)) return rc;
+        return finish_solve(st, s, gvals, u, info, inf);
     }
     const bool kron = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ, jac = s->precond == IGX_PRECOND_JACOBI;
     // z = P r, rz, rr; p = z
@@ -1143,21 +1487,10 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
             }
         }
     }
-    IGX_HIP(hipMemcpyAsync(u, s->x, nbytes, hipMemcpyDeviceToHost, st));
-    IGX_HIP(hipEventRecord(s->ev[4], st));
-    IGX_HIP(hipStreamSynchronize(st));
-    {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("igx_solver_solve: kernel failure: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
-    }
-    (void)hipEventElapsedTime(&inf.total_ms, s->ev[5], s->ev[4]);
-    for (size_t k = 0; k < s->fixed.size(); ++k) u[s->fixed[k]] = gvals[k];
     inf.iterations = it;
     inf.converged = conv ? 1 : 0;
     inf.relres = bnorm > 0.0 ? std::sqrt(h_rr) / bnorm : 0.0;
-    inf.n_free = n - (long long)s->fixed.size();
-    if (info) *info = inf;
-    return IGX_OK;
+    return finish_solve(st, s, gvals, u, info, inf);
 }
 
 int igx_kron_apply_d(igx_ctx *ctx, const igx_kron_desc *d, const double *d_x, double *d_y, double *d_work, int64_t work_len)

@@ -13,8 +13,14 @@ device; only the solution vector comes back.  What the reference does with ``Res
 ``sum_p X_p A_p X_p^T`` and ``sum_p X_p b_p`` are formed on the device and solved there (CSR SpMV over the global pattern;
 Jacobi or an additive Schwarz preconditioner of one fast-diagonalization solve per patch); only the Dirichlet values go up
 and only the solution comes down.
+
+``FormSystem(problem, kvs, rhs, bcs, args)``: the Dirichlet problem of any form whose values the device assembles (general form
+strings, the convection-diffusion form, ...), solved there by right-preconditioned BiCGStab -- what the reference does with
+``assemble.assemble`` + ``RestrictedLinearSystem`` + ``make_solver`` (a direct LU) on the host.  ``method='bicgstab'`` also
+lets ``PatchSystem`` and ``MultipatchSystem`` solve by BiCGStab; ``MultipatchSystem`` then accepts non-symmetric forms.
 """
 import ctypes as C
+import re
 
 import numpy as np
 import scipy.linalg
@@ -101,6 +107,27 @@ def dirichlet_box(ndofs, indices):
     return tuple(lo), tuple(hi)
 
 
+def _check_method(method):
+    if method not in _lib.METHODS:
+        raise ValueError("unknown method %r: 'cg' or 'bicgstab'" % (method,))
+
+
+def _bcs_arrays(bcs):
+    """Sorted unique fixed dofs and their values (a repeated dof keeps its first value, as combine_bcs)."""
+    if bcs is None:
+        return np.zeros(0, dtype=np.int64), np.zeros(0)
+    idx = np.asarray(bcs[0], dtype=np.int64).ravel()
+    vals = np.broadcast_to(np.asarray(bcs[1], dtype=np.float64), idx.shape)
+    idx, first = np.unique(idx, return_index=True)
+    return idx, np.ascontiguousarray(vals[first])
+
+
+def _info_dict(info, precond, method, handle):
+    reason = _lib.load().igx_solver_last_breakdown(handle)
+    return dict(info.as_dict(), converged=bool(info.converged), precond=precond, method=method,
+                breakdown=_lib.BREAKDOWNS.get(reason, reason))
+
+
 class PatchSystem:
     """The Dirichlet problem ``A u = b`` with ``u = g`` on the dofs of `bcs`, for the mass or stiffness matrix of one patch,
     assembled and solved on the device.
@@ -110,11 +137,12 @@ class PatchSystem:
     None.  ``solve(...)`` returns the completed full vector and leaves the solver's statistics in ``info``.
     """
 
-    def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None):
+    def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None, method='cg'):
         self.kvs = tuple(kvs)
         self.kind = kind
         if kind not in _lib.KINDS:
             raise ValueError('unknown kind %r' % (kind,))
+        _check_method(method)
         self.patch = assemblers.DevicePatch(self.kvs, geo, device=device)
         self.ndofs = self.patch.ndofs
         self.n = int(np.prod(self.ndofs))
@@ -123,25 +151,32 @@ class PatchSystem:
         if callable(rhs):
             from . import assemble
             rhs = assemble.inner_products(self.kvs, rhs, f_physical=True, geo=geo)
+        self._create(rhs, bcs, 'igx_solver_create')
+        self.method = 'cg'
+        self.set_method(method)
+
+    def _create(self, rhs, bcs, create):
+        """Right-hand side, Dirichlet data and the device solver (igx_solver_create or igx_solver_create_general)."""
         self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
         if self.b.size != self.n:
             raise ValueError('right-hand side has %d entries, the space %d' % (self.b.size, self.n))
-        if bcs is None:
-            idx, vals = np.zeros(0, dtype=np.int64), np.zeros(0)
-        else:
-            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
-            vals = np.broadcast_to(np.asarray(bcs[1], dtype=np.float64), idx.shape)
-            idx, first = np.unique(idx, return_index=True)    # (a repeated dof keeps its first value, as combine_bcs)
-            vals = vals[first]
-        self.bc_indices, self.bc_values = idx, np.ascontiguousarray(vals)
+        self.bc_indices, self.bc_values = _bcs_arrays(bcs)
+        idx = self.bc_indices
         self.box = dirichlet_box(self.ndofs, idx)
         self._precond = None
         self.info = None
         h = C.c_void_p()
-        _lib.check(_lib.load().igx_solver_create(self.patch.handle, _lib.KINDS[kind],
-                                                 idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, C.byref(h)),
-                   'igx_solver_create')
+        _lib.check(getattr(_lib.load(), create)(self.patch.handle, _lib.KINDS[self.kind],
+                                                idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, C.byref(h)), create)
         self.handle = h.value
+
+    def set_method(self, method):
+        """'cg' or 'bicgstab' for the following solves.  CG on a matrix that is not known to be symmetric positive definite
+        raises IgxError (IGX_ERR_UNSUPPORTED)."""
+        _check_method(method)
+        if method != self.method:
+            _lib.check(_lib.load().igx_solver_set_method(self.handle, _lib.METHODS[method]), 'igx_solver_set_method')
+            self.method = method
 
     def close(self):
         if getattr(self, 'handle', None):
@@ -160,17 +195,18 @@ class PatchSystem:
         """Per-axis eigenvectors and eigenvalues of the 1D Dirichlet matrices of the free range."""
         from .assemble import bsp_mass_1d, bsp_stiffness_1d
         lo, hi = self.box
+        stiff = self.kind != 'mass'                           # (any other form: the parametric Laplacian of the free box)
         U, lam = [], []
         for kv, a, b in zip(self.kvs, lo, hi):
             M = bsp_mass_1d(kv)[a:b, a:b].toarray()
-            if self.kind == 'stiffness':
+            if stiff:
                 K = bsp_stiffness_1d(kv)[a:b, a:b].toarray()
                 w, V = scipy.linalg.eigh(K, M)
             else:
                 w, V = scipy.linalg.eigh(M)
             U.append(np.ascontiguousarray(V))
             lam.append(np.ascontiguousarray(w))
-        return U, lam, (_lib.IGX_KRON_SUM if self.kind == 'stiffness' else _lib.IGX_KRON_PRODUCT)
+        return U, lam, (_lib.IGX_KRON_SUM if stiff else _lib.IGX_KRON_PRODUCT)
 
     def set_precond(self, precond):
         key = precond if precond is not None else 'none'
@@ -193,7 +229,8 @@ class PatchSystem:
         self._precond = key
 
     def solve(self, tol=1e-8, maxiter=1000, precond='kron', x0=None, check_every=1, timed=False):
-        """CG to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full solution vector (the Dirichlet values included)."""
+        """CG (or BiCGStab, see ``method``) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full solution vector (the
+        Dirichlet values included)."""
         self.set_precond(precond)
         u = np.empty(self.n)
         x0a = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).ravel()
@@ -204,7 +241,7 @@ class PatchSystem:
                                                 None if x0a is None else _lib.dptr(x0a), float(tol), int(maxiter),
                                                 int(check_every), 1 if timed else 0, _lib.dptr(u), C.byref(info)),
                    'igx_solver_solve')
-        self.info = dict(info.as_dict(), converged=bool(info.converged), precond=self._precond)
+        self.info = _info_dict(info, self._precond, self.method, self.handle)
         return u
 
     def spmv(self, x):
@@ -214,6 +251,102 @@ class PatchSystem:
         d_y = DeviceArray(self.patch.ctx, self.n)
         _lib.check(_lib.load().igx_solver_spmv_d(self.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d')
         return d_y.download()
+
+
+_HOST_VALUED = ("FormSystem solves forms whose matrix values the device assembles and keeps; %s leaves its values on the "
+                "host.  Solve it on the device through a one-patch multipatch instead: "
+                "MultipatchSystem(Multipatch([(kvs, geo)]), problem, rhs, bcs, method='bicgstab')")
+
+
+def _check_device_form(problem, kvs, args):
+    """ValueError, before any device work, for a problem whose values would not stay on the device: vector-valued / boundary /
+    surface forms (FormAssembler), forms with second or parametric derivatives (parametric jet forms, assembled in passes),
+    functionals, and assembler classes or objects of other kinds."""
+    from . import assemble, forms
+    from .assemblers import _DeviceAssembler, _ParametricFormAssembler
+    if isinstance(problem, str):
+        geo = args.get('geo')
+        if geo is None:
+            raise ValueError("required input parameter 'geo' missing")
+        if getattr(geo, 'dim', len(kvs)) != len(kvs):
+            raise ValueError(_HOST_VALUED % 'a surface form')
+        if re.search(r'\bds\b', problem):
+            raise ValueError(_HOST_VALUED % 'a boundary form')
+        if assemble._KNOWN_FORMS.get(assemble._normalise_form(problem)) is not None:
+            return
+        try:
+            if forms.arity(problem) != 2:
+                raise ValueError('FormSystem needs a bilinear form, not a linear functional: %r' % (problem,))
+        except NotImplementedError as e:
+            raise ValueError('FormSystem: %s' % e)
+        # the class of the form decided on one host point (inputs that cannot be evaluated there are left to the assembler)
+        d = len(kvs)
+        try:
+            forms.coefficient_table(problem, (1,) * d, np.full((1,) * d + (d,), 0.5), dict(args))
+        except NotImplementedError:
+            raise ValueError(_HOST_VALUED % 'a form with second or parametric derivatives (a parametric jet form)')
+        except Exception:
+            pass
+        return
+    cls = problem if isinstance(problem, type) else type(problem)
+    if not issubclass(cls, _DeviceAssembler) or issubclass(cls, _ParametricFormAssembler):
+        raise ValueError(_HOST_VALUED % cls.__name__)
+
+
+class FormSystem(PatchSystem):
+    """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, for the matrix of `problem` on one patch, assembled and
+    solved on the device by BiCGStab (``method='bicgstab'``; 'cg' for a symmetric positive definite kind).
+
+    `problem`: anything ``assemble.instantiate_assembler`` turns into a device assembler (a form string such as the
+    convection-diffusion form of the reference's notebook, an assembler class or object); `args` / `kwargs`: its inputs,
+    ``geo`` among them.  Forms whose values stay on the host (vector-valued, boundary or surface forms, second or parametric
+    derivatives) raise ValueError.  `rhs`: a vector, a scalar, a function of the physical coordinates (``inner_products``) or
+    a linear form string (``'f*v*dx'``).  ``solve()`` uses the Kronecker preconditioner of the parametric Laplacian on the free
+    box when the Dirichlet dofs are whole sides, else Jacobi.
+    """
+
+    def __init__(self, problem, kvs, rhs, bcs=None, args=None, method='bicgstab', **kwargs):
+        from . import assemble
+        self.handle, self.patch, self._own_patch = None, None, False
+        _check_method(method)
+        args = dict(args or {})
+        args.update(kwargs)
+        self.kvs = tuple(kvs)
+        _check_device_form(problem, self.kvs, args)
+        self.assembler = assemble.instantiate_assembler(problem, self.kvs, args)
+        self._own_patch = self.assembler is not problem
+        self.patch = self.assembler.patch
+        self.kind = self.assembler._kind
+        self.ndofs = self.patch.ndofs
+        self.n = int(np.prod(self.ndofs))
+        self.patch.assemble(self.kind, to_host=False)            # the values stay on the device
+        if isinstance(rhs, str):
+            rhs = assemble.assemble(rhs, self.kvs, args=args)
+        elif callable(rhs):
+            rhs = assemble.inner_products(self.kvs, rhs, f_physical=True, geo=args['geo'])
+        elif np.ndim(rhs) == 0:
+            rhs = np.full(self.n, float(rhs))
+        self._create(rhs, bcs, 'igx_solver_create_general')
+        self.method = 'bicgstab'
+        self.set_method(method)
+
+    @property
+    def default_precond(self):
+        return 'kron' if self.box is not None else 'jacobi'
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            _lib.load().igx_solver_destroy(self.handle)
+            self.handle = None
+        if getattr(self, 'patch', None) is not None and self._own_patch:
+            self.patch.close()
+        self.patch = None
+
+    def solve(self, tol=1e-8, maxiter=1000, precond='auto', x0=None, check_every=1, timed=False):
+        """BiCGStab to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full solution vector.  `precond`: 'auto' (see the
+        class), 'kron', 'jacobi' or None."""
+        return PatchSystem.solve(self, tol=tol, maxiter=maxiter, precond=self.default_precond if precond == 'auto' else precond,
+                                 x0=x0, check_every=check_every, timed=timed)
 
 
 ################################################################################
@@ -284,35 +417,31 @@ class MultipatchSystem:
     solved on the device.
 
     `problem`, `rhs`, `args` / `kwargs`: as for ``MP.assemble_system`` (the same per-patch assemblies and scatters; the sums stay
-    on the device).  The form must be symmetric (CG): a form whose assembler declares ``_symmetric_form = False`` is refused.
+    on the device).  With ``method='cg'`` (the default) the form must be symmetric: a form whose assembler declares
+    ``_symmetric_form = False`` is refused.  ``method='bicgstab'`` solves any form; Schwarz then uses the stiffness factors.
     `bcs`: ``(indices, values)`` as ``MP.compute_dirichlet_bcs`` returns them, or None.  ``solve(...)`` returns the completed
     global vector and leaves the solver's statistics in ``info``.  The system reads the sums `MP` holds: a later
     ``MP.assemble_system`` restarts them (a solve then raises), and ``MP.close()`` destroys the system's device solver.
     """
 
-    def __init__(self, MP, problem, rhs, bcs=None, args=None, **kwargs):
+    def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', **kwargs):
         self.handle = None
         self.MP = MP
+        _check_method(method)
         kinds = []
 
         def inspect(p, asm):
-            if not getattr(asm, '_symmetric_form', True):
+            if method == 'cg' and not getattr(asm, '_symmetric_form', True):
                 raise ValueError('MultipatchSystem solves by CG and needs a form known to be symmetric; the assembler of patch %d '
                                  '(%s) cannot show that its form is (general form strings never can).  Accepted: the built-in '
                                  "mass and stiffness forms ('u*v*dx', 'inner(grad(u),grad(v))*dx') and assemblers that do not "
-                                 'declare _symmetric_form = False' % (p, type(asm).__name__))
+                                 "declare _symmetric_form = False; any other form: method='bicgstab'" % (p, type(asm).__name__))
             kinds.append(getattr(asm, '_kind', None))
         h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect)
         self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
         self.n = MP.numdofs
-        if bcs is None:
-            idx, vals = np.zeros(0, dtype=np.int64), np.zeros(0)
-        else:
-            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
-            vals = np.broadcast_to(np.asarray(bcs[1], dtype=np.float64), idx.shape)
-            idx, first = np.unique(idx, return_index=True)
-            vals = vals[first]
-        self.bc_indices, self.bc_values = idx, np.ascontiguousarray(vals)
+        self.bc_indices, self.bc_values = _bcs_arrays(bcs)
+        idx = self.bc_indices
         self._precond = None
         self._schwarz = False
         self.info = None
@@ -322,6 +451,10 @@ class MultipatchSystem:
         self.handle = out.value
         self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
         MP._solvers.add(self)
+        self.method = 'cg'
+        if method != 'cg':
+            _lib.check(_lib.load().igx_solver_set_method(self.handle, _lib.METHODS[method]), 'igx_solver_set_method')
+            self.method = method
 
     def _release(self):
         if getattr(self, 'handle', None):
@@ -351,7 +484,10 @@ class MultipatchSystem:
         shapes = [tuple(kv.numdofs for kv in kvs) for kvs, _ in MP.patches]
         maps = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
         boxes = schwarz_boxes(shapes, maps, self.bc_indices)
-        U, lam, mode = schwarz_factors([tuple(kvs) for kvs, _ in MP.patches], boxes, self.kind)
+        kind = self.kind
+        if self.method == 'bicgstab' and kind not in ('mass', 'stiffness'):
+            kind = 'stiffness'                    # (a general form: the fast-diagonalization inverse of the Laplacian per patch)
+        U, lam, mode = schwarz_factors([tuple(kvs) for kvs, _ in MP.patches], boxes, kind)
         return boxes, U, lam, mode
 
     def set_precond(self, precond):
@@ -376,7 +512,7 @@ class MultipatchSystem:
         self._precond = key
 
     def solve(self, tol=1e-8, maxiter=1000, precond='jacobi', x0=None, check_every=1, timed=False, b=None):
-        """CG to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the global solution vector (the Dirichlet values included).
+        """CG (or BiCGStab) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the global solution vector (the Dirichlet values included).
         The right-hand side is the summed vector on the device unless a host vector `b` is given.
 
         `precond`: 'jacobi' (default), 'schwarz' or None.  Schwarz takes far fewer iterations, but each of them applies one
@@ -396,7 +532,7 @@ class MultipatchSystem:
                                                 None if x0a is None else _lib.dptr(x0a), float(tol), int(maxiter),
                                                 int(check_every), 1 if timed else 0, _lib.dptr(u), C.byref(info)),
                    'igx_solver_solve')
-        self.info = dict(info.as_dict(), converged=bool(info.converged), precond=self._precond)
+        self.info = _info_dict(info, self._precond, self.method, self.handle)
         return u
 
     def _device_op(self, fn, what, x):
