@@ -134,7 +134,8 @@ class PatchSystem:
 
     `rhs`: the load vector (any shape with ``prod(ndofs)`` entries), or a function of the physical coordinates whose load vector
     is then formed with ``assemble.inner_products``.  `bcs`: ``(indices, values)`` as ``compute_dirichlet_bcs`` returns them, or
-    None.  ``solve(...)`` returns the completed full vector and leaves the solver's statistics in ``info``.
+    None.  ``solve(...)`` returns the completed full vector and leaves the solver's statistics in ``info``.  ``spmv(x)``
+    (``R A R^T x``) and ``apply_precond(r)`` (``z = P r``) run the solver's SpMV and preconditioner alone on the device.
     """
 
     def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None, method='cg'):
@@ -251,6 +252,19 @@ class PatchSystem:
         d_y = DeviceArray(self.patch.ctx, self.n)
         _lib.check(_lib.load().igx_solver_spmv_d(self.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d')
         return d_y.download()
+
+    def apply_precond(self, r, precond=None):
+        """``z = P r`` on the device (full-length vectors in and out) with the preconditioner of the last solve, or `precond`
+        ('kron', 'jacobi' or None) if given."""
+        if precond is not None:
+            self.set_precond(precond)
+        r = np.ascontiguousarray(r, dtype=np.float64).ravel()
+        if r.size != self.n:
+            raise ValueError('vector of %d entries, the system has %d' % (r.size, self.n))
+        d_r = DeviceArray.from_host(self.patch.ctx, r)
+        d_z = DeviceArray(self.patch.ctx, self.n)
+        _lib.check(_lib.load().igx_solver_precond_d(self.handle, d_r.ptr, d_z.ptr), 'igx_solver_precond_d')
+        return d_z.download()
 
 
 _HOST_VALUED = ("FormSystem solves forms whose matrix values the device assembles and keeps; %s leaves its values on the "
