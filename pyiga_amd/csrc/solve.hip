@@ -18,6 +18,10 @@
 //   BiCGStab   for non-symmetric matrices (igx_solver_create_general / igx_solver_set_method): the same SpMVs and
 //              preconditioners, fused p / s / x-r updates that emit their dot partials, and k_fin_bicg for rho, alpha, omega,
 //              the stop and breakdown on the device.
+// Host side: one dispatch table per SpMV family (with_spmv_kernel, with_csr_spmv_kernel) names the instantiations, for the launch
+// and the occupancy query alike; one fast-diagonalization block (FastDiag) is the Kronecker preconditioner of a patch and the
+// local solve of every Schwarz patch; igx_solver_solve forms the lifted right-hand side and hands over to solve_cg or
+// solve_bicgstab.
 #include "igx_internal.h"
 
 #include <algorithm>
@@ -675,14 +679,108 @@ int spmv_gw(long long maxlen)
     return maxlen >= 192 ? 64 : maxlen >= 96 ? 32 : maxlen >= 48 ? 16 : maxlen >= 24 ? 8 : 4;
 }
 
+// f(the instantiation of the structured / CSR SpMV at group width gw): the only place that names one, so that the occupancy
+// query and the launch cannot take different kernels
+template <class F>
+decltype(auto) with_spmv_kernel(int gw, F &&f)
+{
+    switch (gw) {
+    case 64: return f(k_spmv<64, 12>);
+    case 32: return f(k_spmv<32, 4>);
+    case 16: return f(k_spmv<16, 4>);
+    case 8: return f(k_spmv<8, 4>);
+    default: return f(k_spmv<4, 4>);
+    }
+}
+
+template <class F>
+decltype(auto) with_csr_spmv_kernel(int gw, F &&f)
+{
+    switch (gw) {
+    case 64: return f(k_csr_spmv<64, 8>);
+    case 32: return f(k_csr_spmv<32, 4>);
+    case 16: return f(k_csr_spmv<16, 4>);
+    case 8: return f(k_csr_spmv<8, 4>);
+    default: return f(k_csr_spmv<4, 4>);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// the fast-diagonalization inverse  (x) U_k . D^-1 . (x) U_k^T  of one box (m[k] dofs on axis k): x is read and y written at
+// io_off with the strides io_stride, in between compact box vectors.  Its factors, per axis U_k^T | U_k | lam_k, lie in one
+// device buffer (pack_fastdiag).
+struct FastDiag {
+    int dim;
+    KronPlan kl, kr;                     // (x) U_k^T with D^-1, then (x) U_k
+};
+
+// C-order strides of a compact box vector
+void box_strides(int dim, const int *m, long long stride[4])
+{
+    for (int k = 0; k < 4; ++k) stride[k] = 1;
+    for (int k = dim - 2; k >= 0; --k) stride[k] = stride[k + 1] * m[k + 1];
+}
+
+// appends the factors of one box to h (U[k]: m[k] x m[k] row-major, lam[k]: m[k]); returns the offset they start at
+size_t pack_fastdiag(std::vector<double> &h, int dim, const int *m, const double *const *U, const double *const *lam)
+{
+    const size_t at = h.size();
+    for (int k = 0; k < dim; ++k) {
+        const size_t mk = (size_t)m[k], o = h.size();
+        h.resize(o + 2 * mk * mk + mk);
+        for (size_t a = 0; a < mk; ++a)
+            for (size_t b = 0; b < mk; ++b) h[o + a * mk + b] = U[k][b * mk + a];
+        std::memcpy(&h[o + mk * mk], U[k], mk * mk * sizeof(double));
+        std::memcpy(&h[o + 2 * mk * mk], lam[k], mk * sizeof(double));
+    }
+    return at;
+}
+
+// the two plans of a box over its packed factors `fac` (on the device)
+FastDiag make_fastdiag(int dim, const int *m, const double *fac, const long long io_stride[4], long long io_off, int lam_mode)
+{
+    FastDiag F{};
+    F.dim = dim;
+    KronPlan &L = F.kl, &R = F.kr;
+    L.dim = R.dim = dim;
+    L.batch = R.batch = 1;
+    long long box_stride[4];
+    box_strides(dim, m, box_stride);
+    for (int k = 0; k < 4; ++k) {
+        L.x_stride[k] = R.y_stride[k] = k < dim ? io_stride[k] : 1;
+        L.y_stride[k] = R.x_stride[k] = box_stride[k];
+    }
+    L.x_off = R.y_off = io_off;
+    for (int k = 0; k < dim; ++k) {
+        const size_t mk = (size_t)m[k];
+        L.m[k] = L.n[k] = R.m[k] = R.n[k] = m[k];
+        L.B[k] = fac;
+        R.B[k] = fac + mk * mk;
+        L.lam[k] = fac + 2 * mk * mk;
+        fac += 2 * mk * mk + mk;
+    }
+    L.lam_mode = lam_mode;
+    return F;
+}
+
+// y = F x with two work buffers of a box each.  With dim >= 2 step k of a plan writes W[k % 2]: the compact result t of the first
+// product goes where its last step does not write, and the second product alternates between the other buffer and t, so that
+// its step 0 does not write t, which it reads
+int apply_fastdiag(hipStream_t st, const FastDiag &F, const double *x, double *y, double *const W[2])
+{
+    double *t = W[(F.dim - 1) % 2];
+    if (int rc = launch_kron_plan(st, F.kl, x, t, W)) return rc;
+    double *W2[2] = {W[F.dim % 2], t};
+    return launch_kron_plan(st, F.kr, t, y, W2);
+}
+
 } // namespace
 
 // ---------------------------------------------------------------------------------------------
-// one patch of the Schwarz preconditioner: its box and the contractions of its fast-diagonalization inverse (compact box vectors)
+// one patch of the Schwarz preconditioner: its box and its fast-diagonalization inverse (compact box vectors in and out)
 struct SwPatch {
     BoxMap map;
-    int patch, dim;
-    KronPlan kl, kr;
+    FastDiag F;
 };
 
 struct igx_solver {
@@ -706,7 +804,7 @@ struct igx_solver {
     double *d_part = nullptr;                 // 2 x NB_SPMV_MAX partial sums
     double *d_sc = nullptr;                   // SC_N scalars
     int precond = IGX_PRECOND_NONE;
-    KronPlan kl{}, kr{};                      // (x) U_k^T with D^-1, then (x) U_k
+    FastDiag kron{};                          // the Kronecker preconditioner on the free box of the full-length vectors
     double *d_kron = nullptr;                 // U_k^T | U_k | lam_k (Schwarz: of every patch)
     double *d_W = nullptr;                    // two work buffers
     long long wlen = 0;
@@ -750,33 +848,17 @@ unsigned spmv_blocks(const igx_solver *s)
     return (unsigned)std::max<long long>(1, std::min<long long>(s->nb_spmv, (s->n + groups - 1) / groups));
 }
 
-int csr_spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
-{
-    const unsigned nb = spmv_blocks(s);
-    const igx_multipatch *m = s->mp;
-    const long long n = s->n;
-    switch (s->gw) {
-    case 64: k_csr_spmv<64, 8><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
-    case 32: k_csr_spmv<32, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
-    case 16: k_csr_spmv<16, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
-    case 8: k_csr_spmv<8, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
-    default: k_csr_spmv<4, 4><<<nb, BLOCK, 0, st>>>(n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part); break;
-    }
-    IGX_HIP(hipGetLastError());
-    return IGX_OK;
-}
-
+// y = free ? (b ? b : 0) + sign A x : 0 (and the partials of pd.y): k_spmv on a patch's values, k_csr_spmv on a multipatch's sums
 int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
 {
-    if (s->mp) return csr_spmv(st, s, x, b, sign, y, pd, part);
     const unsigned nb = spmv_blocks(s);
-    const double *v = s->pt->d_data;
-    switch (s->gw) {
-    case 64: k_spmv<64, 12><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
-    case 32: k_spmv<32, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
-    case 16: k_spmv<16, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
-    case 8: k_spmv<8, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
-    default: k_spmv<4, 4><<<nb, BLOCK, 0, st>>>(s->g, v, s->d_mask, x, b, sign, y, pd, part); break;
+    if (s->mp) {
+        const igx_multipatch *m = s->mp;
+        with_csr_spmv_kernel(s->gw, [&](auto k) {
+            k<<<nb, BLOCK, 0, st>>>(s->n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part);
+        });
+    } else {
+        with_spmv_kernel(s->gw, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, s->pt->d_data, s->d_mask, x, b, sign, y, pd, part); });
     }
     IGX_HIP(hipGetLastError());
     return IGX_OK;
@@ -788,10 +870,7 @@ unsigned vec_blocks(long long n) { return (unsigned)std::max<long long>(1, std::
 int apply_kron(hipStream_t st, igx_solver *s, const double *r, double *z)
 {
     double *W[2] = {s->d_W, s->d_W + s->wlen};
-    double *t = W[(s->dim - 1) % 2];             // the compact result of the first product (not read by its last step)
-    if (int rc = launch_kron_plan(st, s->kl, r, t, W)) return rc;
-    double *W2[2] = {W[s->dim % 2], t};          // step 0 must not write t, which it reads
-    return launch_kron_plan(st, s->kr, t, z, W2);
+    return apply_fastdiag(st, s->kron, r, z, W);
 }
 
 // z = sum_p X_p M_p B_p M_p X_p^T r: per patch, in patch order, gather the box, the two Kronecker products, add back on the free dofs
@@ -803,10 +882,7 @@ int apply_schwarz(hipStream_t st, igx_solver *s, const double *r, double *z)
         const unsigned nb = (unsigned)((P.map.nbox + 255) / 256);
         k_box_gather<<<nb, 256, 0, st>>>(P.map, s->d_mask, r, s->d_box);
         IGX_HIP(hipGetLastError());
-        double *t = W[(P.dim - 1) % 2];
-        if (int rc = launch_kron_plan(st, P.kl, s->d_box, t, W)) return rc;
-        double *W2[2] = {W[P.dim % 2], t};
-        if (int rc = launch_kron_plan(st, P.kr, t, s->d_box, W2)) return rc;
+        if (int rc = apply_fastdiag(st, P.F, s->d_box, s->d_box, W)) return rc;
         k_box_scatter<<<nb, 256, 0, st>>>(P.map, s->d_mask, s->d_box, z);
         IGX_HIP(hipGetLastError());
     }
@@ -822,24 +898,8 @@ int apply_dense(hipStream_t st, igx_solver *s, const double *r, double *z)
 int spmv_occupancy(const igx_solver *s)
 {
     int per_cu = 0;
-    hipError_t eo;
-    if (s->mp) {
-        switch (s->gw) {
-        case 64: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<64, 8>, BLOCK, 0); break;
-        case 32: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<32, 4>, BLOCK, 0); break;
-        case 16: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<16, 4>, BLOCK, 0); break;
-        case 8: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<8, 4>, BLOCK, 0); break;
-        default: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_csr_spmv<4, 4>, BLOCK, 0); break;
-        }
-    } else {
-        switch (s->gw) {
-        case 64: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<64, 12>, BLOCK, 0); break;
-        case 32: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<32, 4>, BLOCK, 0); break;
-        case 16: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<16, 4>, BLOCK, 0); break;
-        case 8: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<8, 4>, BLOCK, 0); break;
-        default: eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv<4, 4>, BLOCK, 0); break;
-        }
-    }
+    auto occupancy = [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0); };
+    const hipError_t eo = s->mp ? with_csr_spmv_kernel(s->gw, occupancy) : with_spmv_kernel(s->gw, occupancy);
     if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
     return (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, s->ctx->ncu));
 }
@@ -911,6 +971,86 @@ int init_bicgstab(igx_solver *s, const char *what)
     for (auto &ev : s->bev)
         if (hipEventCreate(&ev) != hipSuccess) { set_error("%s: hipEventCreate failed", what); return IGX_ERR_HIP; }
     s->have_bev = true;
+    return IGX_OK;
+}
+
+// the packed fast-diagonalization factors h on the device (s->d_kron) and two work buffers of wlen doubles (s->d_W), in place
+// of the previous ones
+int alloc_fastdiag(igx_solver *s, hipStream_t st, const std::vector<double> &h, long long wlen)
+{
+    (void)hipFree(s->d_kron); s->d_kron = nullptr;
+    (void)hipFree(s->d_W); s->d_W = nullptr;
+    IGX_HIP(hipMalloc((void **)&s->d_kron, h.size() * sizeof(double)));
+    IGX_HIP(hipMemcpyAsync(s->d_kron, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)wlen * sizeof(double)));
+    s->wlen = wlen;
+    return IGX_OK;
+}
+
+// Preconditioned CG on R A R^T x = r0 (r0 in s->r, ||R (b - A ext(g))|| = bnorm).  Per iteration: q = A p (and p.q), alpha,
+// x += alpha p, r -= alpha q (Jacobi: z = dinv r, fused), z = P r (Kronecker / Schwarz), beta, p = z + beta p.  alpha and beta
+// are formed on the device by k_fin; the host reads r.r back every check_every iterations to decide whether to go on.
+int solve_cg(hipStream_t st, igx_solver *s, double bnorm, double tol, int maxiter, int check_every, int timed, igx_solve_info &inf)
+{
+    const long long n = s->n;
+    const unsigned nbv = vec_blocks(n), nbs = spmv_blocks(s);
+    double *pA = s->d_part, *pB = s->d_part + NB_SPMV_MAX;
+    const bool kron = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ, jac = s->precond == IGX_PRECOND_JACOBI;
+    // z = P r, rz, rr; p = z
+    const double *zz = (kron || jac) ? s->z : s->r;
+    if (jac) {
+        IGX_HIP(hipMemsetAsync(s->d_sc + SC_ALPHA, 0, sizeof(double), st));   // k_update with alpha = 0: z = dinv r and the dots
+        k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, s->dinv, s->z, s->d_sc, pA, pB);
+    } else {
+        if (kron) {
+            if (int rc = apply_dense(st, s, s->r, s->z)) return rc;
+        }
+        k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, kron ? s->r : nullptr, s->z, pA, pB);
+    }
+    k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_INIT);
+    k_pupdate<<<nbv, BLOCK, 0, st>>>(n, zz, s->p, s->d_sc);
+    IGX_HIP(hipGetLastError());
+    double h_rr = 0.0;
+    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    const double stop = tol * bnorm;
+    bool conv = std::sqrt(h_rr) <= stop;
+    int it = 0;
+    while (!conv && it < maxiter) {
+        ++it;
+        if (timed) IGX_HIP(hipEventRecord(s->ev[0], st));
+        if (int rc = spmv(st, s, s->p, nullptr, 1.0, s->q, s->p, pA)) return rc;
+        if (timed) IGX_HIP(hipEventRecord(s->ev[1], st));
+        k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbs, s->d_sc, FIN_ALPHA);
+        k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, jac ? s->dinv : nullptr, s->z, s->d_sc, pA, pB);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(s->ev[2], st));
+        if (kron) {
+            if (int rc = apply_dense(st, s, s->r, s->z)) return rc;
+        }
+        if (timed) IGX_HIP(hipEventRecord(s->ev[3], st));
+        if (kron) k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->z, nullptr, nullptr, pB, nullptr);
+        k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_BETA);
+        k_pupdate<<<nbv, BLOCK, 0, st>>>(n, zz, s->p, s->d_sc);
+        IGX_HIP(hipGetLastError());
+        if (timed) IGX_HIP(hipEventRecord(s->ev[4], st));
+        if (timed || it % check_every == 0 || it == maxiter) {
+            IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+            IGX_HIP(hipStreamSynchronize(st));
+            conv = std::sqrt(h_rr) <= stop;
+            if (timed) {
+                float a = 0, b2 = 0, c = 0, d2 = 0;
+                (void)hipEventElapsedTime(&a, s->ev[0], s->ev[1]);
+                (void)hipEventElapsedTime(&b2, s->ev[1], s->ev[2]);
+                (void)hipEventElapsedTime(&c, s->ev[2], s->ev[3]);
+                (void)hipEventElapsedTime(&d2, s->ev[3], s->ev[4]);
+                inf.spmv_ms += a; inf.precond_ms += c; inf.vector_ms += b2 + d2;
+            }
+        }
+    }
+    inf.iterations = it;
+    inf.converged = conv ? 1 : 0;
+    inf.relres = bnorm > 0.0 ? std::sqrt(h_rr) / bnorm : 0.0;
     return IGX_OK;
 }
 
@@ -988,15 +1128,35 @@ int solve_bicgstab(hipStream_t st, igx_solver *s, double bnorm, double tol, int 
     return IGX_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-} // extern "C"
-
-namespace {
-
 bool spd_kind(int kind) { return kind == IGX_MASS || kind == IGX_STIFFNESS; }
+
+// the argument checks of the igx_solver_create* entry points (*out cleared once it can be)
+bool create_args_ok(const void *owner, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what)
+{
+    if (!out) { set_error("%s: null argument", what); return false; }
+    *out = nullptr;
+    if (!owner || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("%s: null argument", what); return false; }
+    return true;
+}
+
+// what patch and multipatch solvers share: s (ctx, n and its matrix set) gets its fixed dofs, the group width of its longest row
+// `maxlen`, its SpMV grid, the per-axis tables `tab` on the device (patch solvers; empty otherwise) and its vectors.  s is freed
+// on failure
+int init_solver(igx_solver *s, const int64_t *fixed, int64_t nfixed, long long maxlen, const std::vector<int> &tab, const char *what)
+{
+    if (!set_fixed(s, fixed, nfixed, what)) { delete s; return IGX_ERR_ARG; }
+    s->gw = spmv_gw(maxlen);
+    s->nb_spmv = spmv_occupancy(s);
+    if (!tab.empty()) {
+        if (hipMalloc((void **)&s->d_tab, tab.size() * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError(); set_error("%s: out of device memory (%.3f GB)", what, 8.0 * 8 * s->n / 1e9); free_solver(s); return IGX_ERR_NOMEM;
+        }
+        hipError_t e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s->ctx->stream);
+        if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); free_solver(s); return IGX_ERR_HIP; }
+    }
+    if (int rc = init_vectors(s, what)) { free_solver(s); return rc; }
+    return IGX_OK;
+}
 
 // a solver over the values of `kind` the patch holds (the kind itself checked by the caller)
 int create_patch_solver(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what)
@@ -1013,7 +1173,6 @@ int create_patch_solver(igx_patch *pt, int kind, const int64_t *fixed, int64_t n
     igx_solver *s = new igx_solver;
     s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->n = pt->nrows_total;
     for (int k = 0; k < pt->dim; ++k) s->N[k] = pt->ax[k].N;
-    if (!set_fixed(s, fixed, nfixed, what)) { delete s; return IGX_ERR_ARG; }
     // per-axis tables as a 3D layout (2D: a one-dof outer axis in front)
     const int off = 3 - pt->dim;
     std::vector<int> tab;
@@ -1033,15 +1192,7 @@ int create_patch_solver(igx_patch *pt, int kind, const int64_t *fixed, int64_t n
         pos[a][1] = tab.size(); tab.insert(tab.end(), hi.begin(), hi.end());
         pos[a][2] = tab.size(); tab.insert(tab.end(), rp.begin(), rp.end());
     }
-    s->gw = spmv_gw(maxlen);
-    s->nb_spmv = spmv_occupancy(s);
-    const size_t n = (size_t)s->n;
-    if (hipMalloc((void **)&s->d_tab, tab.size() * sizeof(int)) != hipSuccess) {
-        (void)hipGetLastError(); set_error("%s: out of device memory (%.3f GB)", what, 8.0 * 8 * n / 1e9); free_solver(s); return IGX_ERR_NOMEM;
-    }
-    hipError_t e = hipMemcpyAsync(s->d_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, pt->ctx->stream);
-    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); free_solver(s); return IGX_ERR_HIP; }
-    if (int rc = init_vectors(s, what)) { free_solver(s); return rc; }
+    if (int rc = init_solver(s, fixed, nfixed, maxlen, tab, what)) return rc;
     for (int a = 0; a < 3; ++a) { s->g.jlo[a] = s->d_tab + pos[a][0]; s->g.jhi[a] = s->d_tab + pos[a][1]; s->g.rp[a] = s->d_tab + pos[a][2]; }
     s->g.S1 = tab[pos[1][2] + s->g.N[1]];
     s->g.S2 = tab[pos[2][2] + s->g.N[2]];
@@ -1056,9 +1207,7 @@ extern "C" {
 
 int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
 {
-    if (!out) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
-    *out = nullptr;
-    if (!pt || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create: null argument"); return IGX_ERR_ARG; }
+    if (!create_args_ok(pt, fixed, nfixed, out, "igx_solver_create")) return IGX_ERR_ARG;
     if (!spd_kind(kind)) {
         set_error("igx_solver_create: CG needs a symmetric positive definite matrix (IGX_MASS or IGX_STIFFNESS), kind %d", kind);
         return IGX_ERR_UNSUPPORTED;
@@ -1068,9 +1217,7 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
 
 int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
 {
-    if (!out) { set_error("igx_solver_create_general: null argument"); return IGX_ERR_ARG; }
-    *out = nullptr;
-    if (!pt || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create_general: null argument"); return IGX_ERR_ARG; }
+    if (!create_args_ok(pt, fixed, nfixed, out, "igx_solver_create_general")) return IGX_ERR_ARG;
     if (kind != IGX_MASS && kind != IGX_STIFFNESS && kind != IGX_CONVDIFF && kind != IGX_FORM) {
         set_error("igx_solver_create_general: unknown kind %d", kind);
         return IGX_ERR_ARG;
@@ -1105,16 +1252,11 @@ int igx_solver_last_breakdown(const igx_solver *s) { return s ? s->breakdown : 0
 
 int igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64_t nfixed, igx_solver **out)
 {
-    if (!out) { set_error("igx_solver_create_multipatch: null argument"); return IGX_ERR_ARG; }
-    *out = nullptr;
-    if (!mp || (nfixed > 0 && !fixed) || nfixed < 0) { set_error("igx_solver_create_multipatch: null argument"); return IGX_ERR_ARG; }
+    if (!create_args_ok(mp, fixed, nfixed, out, "igx_solver_create_multipatch")) return IGX_ERR_ARG;
     if (hipSetDevice(mp->ctx->device) != hipSuccess) { set_error("igx_solver_create_multipatch: hipSetDevice failed"); return IGX_ERR_HIP; }
     igx_solver *s = new igx_solver;
     s->ctx = mp->ctx; s->mp = mp; s->gen = mp->generation; s->kind = -1; s->n = mp->nglobal;
-    if (!set_fixed(s, fixed, nfixed, "igx_solver_create_multipatch")) { delete s; return IGX_ERR_ARG; }
-    s->gw = spmv_gw(mp->max_row);
-    s->nb_spmv = spmv_occupancy(s);
-    if (int rc = init_vectors(s, "igx_solver_create_multipatch")) { free_solver(s); return rc; }
+    if (int rc = init_solver(s, fixed, nfixed, mp->max_row, {}, "igx_solver_create_multipatch")) return rc;
     *out = s;
     return IGX_OK;
 }
@@ -1177,54 +1319,15 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
                     }
                 }
     }
-    size_t tot = 0;
-    for (int k = 0; k < d; ++k) tot += 2 * (size_t)nb[k] * nb[k] + nb[k];
-    std::vector<double> h(tot);
-    size_t o = 0;
-    size_t oUt[3], oU[3], oL[3];
-    for (int k = 0; k < d; ++k) {
-        const int m = nb[k];
-        oUt[k] = o;
-        for (int a = 0; a < m; ++a)
-            for (int b2 = 0; b2 < m; ++b2) h[o + (size_t)a * m + b2] = U[k][(size_t)b2 * m + a];
-        o += (size_t)m * m;
-        oU[k] = o;
-        std::memcpy(&h[o], U[k], (size_t)m * m * sizeof(double));
-        o += (size_t)m * m;
-        oL[k] = o;
-        std::memcpy(&h[o], lam[k], (size_t)m * sizeof(double));
-        o += m;
-    }
-    (void)hipFree(s->d_kron); s->d_kron = nullptr;
-    (void)hipFree(s->d_W); s->d_W = nullptr;
+    std::vector<double> h;
+    pack_fastdiag(h, d, nb, U, lam);
     s->precond = IGX_PRECOND_NONE;
-    IGX_HIP(hipMalloc((void **)&s->d_kron, tot * sizeof(double)));
-    IGX_HIP(hipMemcpyAsync(s->d_kron, h.data(), tot * sizeof(double), hipMemcpyHostToDevice, st));
-    KronPlan L{}, R{};
-    L.dim = R.dim = d;
-    L.batch = R.batch = 1;
-    long long full_stride[3] = {1, 1, 1}, off = 0;
-    for (int k = d - 1; k >= 0; --k) full_stride[k] = k == d - 1 ? 1 : full_stride[k + 1] * s->N[k + 1];
+    if (int rc = alloc_fastdiag(s, st, h, std::max<long long>(1, (long long)nb[0] * nb[1] * nb[2]))) return rc;
+    // (x) U_k^T reads the box of the full-length r, (x) U_k writes it into z
+    long long full_stride[4], off = 0;
+    box_strides(d, s->N, full_stride);
     for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
-    // (x) U_k^T reads the box of the full-length r, (x) U_k writes it into z; in between compact box vectors
-    long long box_stride[3] = {1, 1, 1};
-    for (int k = d - 2; k >= 0; --k) box_stride[k] = box_stride[k + 1] * nb[k + 1];
-    for (int k = 0; k < 4; ++k) {
-        L.x_stride[k] = R.y_stride[k] = k < d ? full_stride[k] : 1;
-        L.y_stride[k] = R.x_stride[k] = k < d ? box_stride[k] : 1;
-    }
-    L.x_off = R.y_off = off;
-    L.y_off = R.x_off = 0;
-    for (int k = 0; k < d; ++k) {
-        L.m[k] = L.n[k] = R.m[k] = R.n[k] = nb[k];
-        L.B[k] = s->d_kron + oUt[k];
-        R.B[k] = s->d_kron + oU[k];
-        L.lam[k] = s->d_kron + oL[k];
-    }
-    L.lam_mode = lam_mode;
-    s->kl = L; s->kr = R;
-    s->wlen = std::max<long long>(1, (long long)nb[0] * nb[1] * nb[2]);
-    IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)s->wlen * sizeof(double)));
+    s->kron = make_fastdiag(d, nb, s->d_kron, full_stride, off, lam_mode);
     IGX_HIP(hipStreamSynchronize(st));
     s->precond = IGX_PRECOND_KRON;
     return IGX_OK;
@@ -1243,10 +1346,10 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
     }
     if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_schwarz: null argument"); return IGX_ERR_ARG; }
     if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_schwarz: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
-    // host layout of the factors: per patch with a non-empty box, per axis  U_k^T | U_k | lam_k
+    // per patch with a non-empty box its map and, per axis, U_k^T | U_k | lam_k at fac[j] in h
     std::vector<SwPatch> sw;
-    std::vector<size_t> oUt, oU, oL;               // (per patch, 3 axes)
-    size_t tot = 0;
+    std::vector<size_t> fac;
+    std::vector<double> h;
     long long wlen = 1;
     for (int p = 0; p < mp->np; ++p) {
         const auto &P = mp->pp[p];
@@ -1261,7 +1364,6 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
         }
         if (empty) continue;
         SwPatch W{};
-        W.dim = P.dim;
         const int off = 3 - P.dim;
         for (int a = 0; a < 3; ++a) { W.map.lo[a] = 0; W.map.nb[a] = 1; W.map.N[a] = 1; }
         W.map.nbox = 1;
@@ -1270,63 +1372,31 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
             if (!U[p * 3 + k] || !lam[p * 3 + k]) { set_error("igx_solver_set_schwarz: patch %d: factor of axis %d missing", p, k); return IGX_ERR_ARG; }
             W.map.lo[off + k] = box_lo[p * 3 + k]; W.map.nb[off + k] = m; W.map.N[off + k] = P.N[k];
             W.map.nbox *= m;
-            oUt.push_back(tot); tot += (size_t)m * m;
-            oU.push_back(tot); tot += (size_t)m * m;
-            oL.push_back(tot); tot += m;
         }
-        for (int k = P.dim; k < 3; ++k) { oUt.push_back(0); oU.push_back(0); oL.push_back(0); }
         W.map.l2g = P.d_l2g;
-        W.patch = p;
+        W.F.dim = P.dim;
+        fac.push_back(pack_fastdiag(h, P.dim, W.map.nb + off, U + p * 3, lam + p * 3));
         wlen = std::max(wlen, W.map.nbox);
         sw.push_back(W);
     }
     if (sw.empty()) { set_error("igx_solver_set_schwarz: every patch box is empty"); return IGX_ERR_ARG; }
-    std::vector<double> h(std::max<size_t>(1, tot));
-    for (size_t j = 0; j < sw.size(); ++j) {
-        const int p = sw[j].patch;
-        for (int k = 0; k < sw[j].dim; ++k) {
-            const int m = box_hi[p * 3 + k] - box_lo[p * 3 + k];
-            const double *Uk = U[p * 3 + k];
-            double *ut = &h[oUt[j * 3 + k]];
-            for (int a = 0; a < m; ++a)
-                for (int b2 = 0; b2 < m; ++b2) ut[(size_t)a * m + b2] = Uk[(size_t)b2 * m + a];
-            std::memcpy(&h[oU[j * 3 + k]], Uk, (size_t)m * m * sizeof(double));
-            std::memcpy(&h[oL[j * 3 + k]], lam[p * 3 + k], (size_t)m * sizeof(double));
-        }
-    }
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     IGX_HIP(hipStreamSynchronize(st));
-    (void)hipFree(s->d_kron); s->d_kron = nullptr;
-    (void)hipFree(s->d_W); s->d_W = nullptr;
     (void)hipFree(s->d_box); s->d_box = nullptr;
     s->sw.clear();
     if (s->precond == IGX_PRECOND_SCHWARZ) s->precond = IGX_PRECOND_NONE;
-    IGX_HIP(hipMalloc((void **)&s->d_kron, h.size() * sizeof(double)));
-    IGX_HIP(hipMemcpyAsync(s->d_kron, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (int rc = alloc_fastdiag(s, st, h, wlen)) return rc;
     IGX_HIP(hipMalloc((void **)&s->d_box, (size_t)wlen * sizeof(double)));
-    IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)wlen * sizeof(double)));
     for (size_t j = 0; j < sw.size(); ++j) {
-        SwPatch &W = sw[j];
-        const int d = W.dim, off = 3 - d;
-        KronPlan L{}, R{};
-        L.dim = R.dim = d;
-        L.batch = R.batch = 1;
-        long long stride[4] = {1, 1, 1, 1};             // compact box vectors in and out
-        for (int k = d - 2; k >= 0; --k) stride[k] = stride[k + 1] * W.map.nb[off + k + 1];
-        for (int k = 0; k < 4; ++k) L.x_stride[k] = L.y_stride[k] = R.x_stride[k] = R.y_stride[k] = k < d ? stride[k] : 1;
-        for (int k = 0; k < d; ++k) {
-            L.m[k] = L.n[k] = R.m[k] = R.n[k] = W.map.nb[off + k];
-            L.B[k] = s->d_kron + oUt[j * 3 + k];
-            R.B[k] = s->d_kron + oU[j * 3 + k];
-            L.lam[k] = s->d_kron + oL[j * 3 + k];
-        }
-        L.lam_mode = lam_mode;
-        W.kl = L; W.kr = R;
+        const int d = sw[j].F.dim;
+        const int *m = sw[j].map.nb + (3 - d);
+        long long stride[4];                            // compact box vectors in and out
+        box_strides(d, m, stride);
+        sw[j].F = make_fastdiag(d, m, s->d_kron + fac[j], stride, 0, lam_mode);
     }
     IGX_HIP(hipStreamSynchronize(st));
     s->sw = std::move(sw);
-    s->wlen = wlen;
     s->precond = IGX_PRECOND_SCHWARZ;
     return IGX_OK;
 }
@@ -1418,8 +1488,8 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
     IGX_HIP(hipMemsetAsync(s->q, 0, nbytes, st));
     IGX_HIP(hipMemsetAsync(s->z, 0, nbytes, st));
     IGX_HIP(hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st));
-    const unsigned nbv = vec_blocks(n), nbs = spmv_blocks(s);
-    double *pA = s->d_part, *pB = s->d_part + NB_SPMV_MAX;
+    const unsigned nbv = vec_blocks(n);
+    double *pA = s->d_part;
     // r = R (b - A ext(g)); its norm is the reference of the relative residual
     if (int rc = spmv(st, s, s->w, s->b, -1.0, s->r, nullptr, nullptr)) return rc;
     k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
@@ -1433,63 +1503,9 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
         IGX_HIP(hipMemcpyAsync(s->x, w.data(), nbytes, hipMemcpyHostToDevice, st));
         if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
     }
-    if (s->method == IGX_METHOD_BICGSTAB) {
-        if (int rc = solve_bicgstab(st, s, bnorm, tol, maxiter, check_every, timed, inf)) return rc;
-        return finish_solve(st, s, gvals, u, info, inf);
-    }
-    const bool kron = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ, jac = s->precond == IGX_PRECOND_JACOBI;
-    // z = P r, rz, rr; p = z
-    const double *zz = (kron || jac) ? s->z : s->r;
-    if (jac) {
-        IGX_HIP(hipMemsetAsync(s->d_sc + SC_ALPHA, 0, sizeof(double), st));   // k_update with alpha = 0: z = dinv r and the dots
-        k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, s->dinv, s->z, s->d_sc, pA, pB);
-    } else {
-        if (kron && (apply_dense(st, s, s->r, s->z) != IGX_OK)) return IGX_ERR_HIP;
-        k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, kron ? s->r : nullptr, s->z, pA, pB);
-    }
-    k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_INIT);
-    k_pupdate<<<nbv, BLOCK, 0, st>>>(n, zz, s->p, s->d_sc);
-    IGX_HIP(hipGetLastError());
-    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-    IGX_HIP(hipStreamSynchronize(st));
-    const double stop = tol * bnorm;
-    bool conv = std::sqrt(h_rr) <= stop;
-    int it = 0;
-    while (!conv && it < maxiter) {
-        ++it;
-        if (timed) IGX_HIP(hipEventRecord(s->ev[0], st));
-        if (int rc = spmv(st, s, s->p, nullptr, 1.0, s->q, s->p, pA)) return rc;
-        if (timed) IGX_HIP(hipEventRecord(s->ev[1], st));
-        k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbs, s->d_sc, FIN_ALPHA);
-        k_update<<<nbv, BLOCK, 0, st>>>(n, s->x, s->r, s->p, s->q, jac ? s->dinv : nullptr, s->z, s->d_sc, pA, pB);
-        IGX_HIP(hipGetLastError());
-        if (timed) IGX_HIP(hipEventRecord(s->ev[2], st));
-        if (kron) {
-            if (int rc = apply_dense(st, s, s->r, s->z)) return rc;
-        }
-        if (timed) IGX_HIP(hipEventRecord(s->ev[3], st));
-        if (kron) k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->z, nullptr, nullptr, pB, nullptr);
-        k_fin<<<1, BLOCK, 0, st>>>(pA, (kron || jac) ? pB : nullptr, nbv, s->d_sc, FIN_BETA);
-        k_pupdate<<<nbv, BLOCK, 0, st>>>(n, zz, s->p, s->d_sc);
-        IGX_HIP(hipGetLastError());
-        if (timed) IGX_HIP(hipEventRecord(s->ev[4], st));
-        if (timed || it % check_every == 0 || it == maxiter) {
-            IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-            IGX_HIP(hipStreamSynchronize(st));
-            conv = std::sqrt(h_rr) <= stop;
-            if (timed) {
-                float a = 0, b2 = 0, c = 0, d2 = 0;
-                (void)hipEventElapsedTime(&a, s->ev[0], s->ev[1]);
-                (void)hipEventElapsedTime(&b2, s->ev[1], s->ev[2]);
-                (void)hipEventElapsedTime(&c, s->ev[2], s->ev[3]);
-                (void)hipEventElapsedTime(&d2, s->ev[3], s->ev[4]);
-                inf.spmv_ms += a; inf.precond_ms += c; inf.vector_ms += b2 + d2;
-            }
-        }
-    }
-    inf.iterations = it;
-    inf.converged = conv ? 1 : 0;
-    inf.relres = bnorm > 0.0 ? std::sqrt(h_rr) / bnorm : 0.0;
+    const int rc = s->method == IGX_METHOD_BICGSTAB ? solve_bicgstab(st, s, bnorm, tol, maxiter, check_every, timed, inf)
+                                                    : solve_cg(st, s, bnorm, tol, maxiter, check_every, timed, inf);
+    if (rc) return rc;
     return finish_solve(st, s, gvals, u, info, inf);
 }
 

@@ -122,13 +122,138 @@ def _bcs_arrays(bcs):
     return idx, np.ascontiguousarray(vals[first])
 
 
-def _info_dict(info, precond, method, handle):
-    reason = _lib.load().igx_solver_last_breakdown(handle)
-    return dict(info.as_dict(), converged=bool(info.converged), precond=precond, method=method,
-                breakdown=_lib.BREAKDOWNS.get(reason, reason))
+def fastdiag_factors(kvs, lo, hi, stiff, mats1d=None):
+    """Per axis of the box ``lo[k] <= i_k < hi[k]`` the eigenvectors ``U_k`` and eigenvalues ``lam_k`` of the 1D matrices on the
+    box range, and the ``IGX_KRON_*`` mode of the fast-diagonalization inverse: ``eigh(K_k, M_k)`` with ``IGX_KRON_SUM`` if
+    `stiff`, else ``eigh(M_k)`` with ``IGX_KRON_PRODUCT``.  `mats1d(kv)`: ``(K, M)`` of a knot vector (default: the device's
+    ``bsp_stiffness_1d`` / ``bsp_mass_1d``; K is not used, and may be None, unless `stiff`)."""
+    if mats1d is None:
+        from .assemble import bsp_mass_1d, bsp_stiffness_1d
+
+        def mats1d(kv):
+            return (bsp_stiffness_1d(kv) if stiff else None), bsp_mass_1d(kv)
+    U, lam = [], []
+    for kv, a, b in zip(kvs, lo, hi):
+        K, M = mats1d(kv)
+        M = _dense(M)[a:b, a:b]
+        w, V = scipy.linalg.eigh(_dense(K)[a:b, a:b], M) if stiff else scipy.linalg.eigh(M)
+        U.append(np.ascontiguousarray(V))
+        lam.append(np.ascontiguousarray(w))
+    return U, lam, (_lib.IGX_KRON_SUM if stiff else _lib.IGX_KRON_PRODUCT)
 
 
-class PatchSystem:
+class _DeviceSystem:
+    """What the device-resident Dirichlet problems share: the solver handle (``igx_solver_*``) and its lifecycle, the method, the
+    preconditioner, the solve and the solver's SpMV and preconditioner alone.
+
+    A subclass sets ``PRECONDS`` (preconditioner names -> ``IGX_PRECOND_*``), ``_ctx`` (the context of the device vectors) and
+    ``n``, creates the handle with ``_attach``, and implements ``_set_factors(handle)`` (the preconditioner ``FACTORED`` that
+    needs a host set-up) and ``_drop_owner()`` (what ``close()`` releases besides the handle).  ``_factors_set``: the set-up is
+    done once and kept (else it runs whenever ``FACTORED`` is chosen)."""
+    PRECONDS = _lib.PRECONDS
+    FACTORED = 'kron'
+    handle = None
+    _factors_set = False
+
+    def _attach(self, create, args, bcs, method, initial):
+        """The device solver made by `create` (``igx_solver_create*``, leading arguments `args`) with the fixed dofs of `bcs`;
+        its method is `initial`, then `method`."""
+        self.bc_indices, self.bc_values = _bcs_arrays(bcs)
+        idx = self.bc_indices
+        self._precond = None
+        self.info = None
+        h = C.c_void_p()
+        _lib.check(getattr(_lib.load(), create)(*args, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, C.byref(h)), create)
+        self.handle = h.value
+        self.method = initial
+        self.set_method(method)
+
+    def _live(self):
+        if not self.handle:
+            raise _lib.IgxError('%s: the solver was closed (that of a MultipatchSystem also when its Multipatch is closed or '
+                                're-joined)' % type(self).__name__)
+        return self.handle
+
+    def set_method(self, method):
+        """'cg' or 'bicgstab' for the following solves.  CG on a matrix that is not known to be symmetric positive definite
+        raises IgxError (IGX_ERR_UNSUPPORTED)."""
+        _check_method(method)
+        if method != self.method:
+            _lib.check(_lib.load().igx_solver_set_method(self._live(), _lib.METHODS[method]), 'igx_solver_set_method')
+            self.method = method
+
+    def set_precond(self, precond):
+        key = precond if precond is not None else 'none'
+        if key not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        if key == self._precond:
+            return
+        if key == self.FACTORED and not self._factors_set:
+            self._set_factors(h)
+        else:
+            _lib.check(_lib.load().igx_solver_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_set_precond')
+        self._precond = key
+
+    def _release(self):
+        if self.handle:
+            _lib.load().igx_solver_destroy(self.handle)
+            self.handle = None
+
+    def close(self):
+        self._release()
+        self._drop_owner()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _solve(self, b, tol, maxiter, precond, x0, check_every, timed):
+        """The solve with the host right-hand side `b`, or with the vector the device holds (multipatch sums) if None."""
+        self.set_precond(precond)
+        u = np.empty(self.n)
+        x0a = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).ravel()
+        if x0a is not None and x0a.size != self.n:
+            raise ValueError('x0 has the wrong size')
+        ba = None if b is None else np.ascontiguousarray(b, dtype=np.float64).ravel()
+        if ba is not None and ba.size != self.n:
+            raise ValueError('b has the wrong size')
+        lib = _lib.load()
+        info = _lib.SolveInfo()
+        _lib.check(lib.igx_solver_solve(self._live(), None if ba is None else _lib.dptr(ba), _lib.dptr(self.bc_values),
+                                        None if x0a is None else _lib.dptr(x0a), float(tol), int(maxiter), int(check_every),
+                                        1 if timed else 0, _lib.dptr(u), C.byref(info)),
+                   'igx_solver_solve')
+        reason = lib.igx_solver_last_breakdown(self.handle)
+        self.info = dict(info.as_dict(), converged=bool(info.converged), precond=self._precond, method=self.method,
+                         breakdown=_lib.BREAKDOWNS.get(reason, reason))
+        return u
+
+    def _device_op(self, fn, what, x):
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if x.size != self.n:
+            raise ValueError('vector of %d entries, the system has %d' % (x.size, self.n))
+        h = self._live()
+        d_x = DeviceArray.from_host(self._ctx, x)
+        d_y = DeviceArray(self._ctx, self.n)
+        _lib.check(fn(h, d_x.ptr, d_y.ptr), what)
+        return d_y.download()
+
+    def spmv(self, x):
+        """``R A R^T x`` on the device (vectors of all dofs in and out)."""
+        return self._device_op(_lib.load().igx_solver_spmv_d, 'igx_solver_spmv_d', x)
+
+    def apply_precond(self, r, precond=None):
+        """``z = P r`` on the device (vectors of all dofs in and out) with the preconditioner of the last solve, or `precond`
+        (a name of ``PRECONDS``, or None) if given."""
+        if precond is not None:
+            self.set_precond(precond)
+        return self._device_op(_lib.load().igx_solver_precond_d, 'igx_solver_precond_d', r)
+
+
+class PatchSystem(_DeviceSystem):
     """The Dirichlet problem ``A u = b`` with ``u = g`` on the dofs of `bcs`, for the mass or stiffness matrix of one patch,
     assembled and solved on the device.
 
@@ -137,6 +262,7 @@ class PatchSystem:
     None.  ``solve(...)`` returns the completed full vector and leaves the solver's statistics in ``info``.  ``spmv(x)``
     (``R A R^T x``) and ``apply_precond(r)`` (``z = P r``) run the solver's SpMV and preconditioner alone on the device.
     """
+    _own_patch = True
 
     def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None, method='cg'):
         self.kvs = tuple(kvs)
@@ -152,119 +278,41 @@ class PatchSystem:
         if callable(rhs):
             from . import assemble
             rhs = assemble.inner_products(self.kvs, rhs, f_physical=True, geo=geo)
-        self._create(rhs, bcs, 'igx_solver_create')
-        self.method = 'cg'
-        self.set_method(method)
+        self._create(rhs, bcs, 'igx_solver_create', 'cg', method)
 
-    def _create(self, rhs, bcs, create):
+    def _create(self, rhs, bcs, create, initial, method):
         """Right-hand side, Dirichlet data and the device solver (igx_solver_create or igx_solver_create_general)."""
         self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
         if self.b.size != self.n:
             raise ValueError('right-hand side has %d entries, the space %d' % (self.b.size, self.n))
-        self.bc_indices, self.bc_values = _bcs_arrays(bcs)
-        idx = self.bc_indices
-        self.box = dirichlet_box(self.ndofs, idx)
-        self._precond = None
-        self.info = None
-        h = C.c_void_p()
-        _lib.check(getattr(_lib.load(), create)(self.patch.handle, _lib.KINDS[self.kind],
-                                                idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, C.byref(h)), create)
-        self.handle = h.value
+        self._ctx = self.patch.ctx
+        self._attach(create, (self.patch.handle, _lib.KINDS[self.kind]), bcs, method, initial)
+        self.box = dirichlet_box(self.ndofs, self.bc_indices)
 
-    def set_method(self, method):
-        """'cg' or 'bicgstab' for the following solves.  CG on a matrix that is not known to be symmetric positive definite
-        raises IgxError (IGX_ERR_UNSUPPORTED)."""
-        _check_method(method)
-        if method != self.method:
-            _lib.check(_lib.load().igx_solver_set_method(self.handle, _lib.METHODS[method]), 'igx_solver_set_method')
-            self.method = method
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            _lib.load().igx_solver_destroy(self.handle)
-            self.handle = None
-        if getattr(self, 'patch', None) is not None:
+    def _drop_owner(self):
+        if getattr(self, 'patch', None) is not None and self._own_patch:
             self.patch.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.patch = None
 
     def _kron_factors(self):
         """Per-axis eigenvectors and eigenvalues of the 1D Dirichlet matrices of the free range."""
-        from .assemble import bsp_mass_1d, bsp_stiffness_1d
-        lo, hi = self.box
         stiff = self.kind != 'mass'                           # (any other form: the parametric Laplacian of the free box)
-        U, lam = [], []
-        for kv, a, b in zip(self.kvs, lo, hi):
-            M = bsp_mass_1d(kv)[a:b, a:b].toarray()
-            if stiff:
-                K = bsp_stiffness_1d(kv)[a:b, a:b].toarray()
-                w, V = scipy.linalg.eigh(K, M)
-            else:
-                w, V = scipy.linalg.eigh(M)
-            U.append(np.ascontiguousarray(V))
-            lam.append(np.ascontiguousarray(w))
-        return U, lam, (_lib.IGX_KRON_SUM if stiff else _lib.IGX_KRON_PRODUCT)
+        return fastdiag_factors(self.kvs, self.box[0], self.box[1], stiff)
 
-    def set_precond(self, precond):
-        key = precond if precond is not None else 'none'
-        if key not in _lib.PRECONDS:
-            raise ValueError('unknown preconditioner %r' % (precond,))
-        if key == self._precond:
-            return
-        lib = _lib.load()
-        if key == 'kron':
-            if self.box is None:
-                raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch")
-            U, lam, mode = self._kron_factors()
-            lo = (C.c_int32 * 3)(*self.box[0])
-            hi = (C.c_int32 * 3)(*self.box[1])
-            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
-            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
-            _lib.check(lib.igx_solver_set_precond(self.handle, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_set_precond')
-        else:
-            _lib.check(lib.igx_solver_set_precond(self.handle, _lib.PRECONDS[key], None, None, None, None, 0), 'igx_solver_set_precond')
-        self._precond = key
+    def _set_factors(self, h):
+        if self.box is None:
+            raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch")
+        U, lam, mode = self._kron_factors()
+        lo = (C.c_int32 * 3)(*self.box[0])
+        hi = (C.c_int32 * 3)(*self.box[1])
+        Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
+        Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+        _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_set_precond')
 
     def solve(self, tol=1e-8, maxiter=1000, precond='kron', x0=None, check_every=1, timed=False):
         """CG (or BiCGStab, see ``method``) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full solution vector (the
         Dirichlet values included)."""
-        self.set_precond(precond)
-        u = np.empty(self.n)
-        x0a = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).ravel()
-        if x0a is not None and x0a.size != self.n:
-            raise ValueError('x0 has the wrong size')
-        info = _lib.SolveInfo()
-        _lib.check(_lib.load().igx_solver_solve(self.handle, _lib.dptr(self.b), _lib.dptr(self.bc_values),
-                                                None if x0a is None else _lib.dptr(x0a), float(tol), int(maxiter),
-                                                int(check_every), 1 if timed else 0, _lib.dptr(u), C.byref(info)),
-                   'igx_solver_solve')
-        self.info = _info_dict(info, self._precond, self.method, self.handle)
-        return u
-
-    def spmv(self, x):
-        """``R A R^T x`` on the device (full-length vectors in and out)."""
-        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
-        d_x = DeviceArray.from_host(self.patch.ctx, x)
-        d_y = DeviceArray(self.patch.ctx, self.n)
-        _lib.check(_lib.load().igx_solver_spmv_d(self.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d')
-        return d_y.download()
-
-    def apply_precond(self, r, precond=None):
-        """``z = P r`` on the device (full-length vectors in and out) with the preconditioner of the last solve, or `precond`
-        ('kron', 'jacobi' or None) if given."""
-        if precond is not None:
-            self.set_precond(precond)
-        r = np.ascontiguousarray(r, dtype=np.float64).ravel()
-        if r.size != self.n:
-            raise ValueError('vector of %d entries, the system has %d' % (r.size, self.n))
-        d_r = DeviceArray.from_host(self.patch.ctx, r)
-        d_z = DeviceArray(self.patch.ctx, self.n)
-        _lib.check(_lib.load().igx_solver_precond_d(self.handle, d_r.ptr, d_z.ptr), 'igx_solver_precond_d')
-        return d_z.download()
+        return self._solve(self.b, tol, maxiter, precond, x0, check_every, timed)
 
 
 _HOST_VALUED = ("FormSystem solves forms whose matrix values the device assembles and keeps; %s leaves its values on the "
@@ -321,7 +369,6 @@ class FormSystem(PatchSystem):
 
     def __init__(self, problem, kvs, rhs, bcs=None, args=None, method='bicgstab', **kwargs):
         from . import assemble
-        self.handle, self.patch, self._own_patch = None, None, False
         _check_method(method)
         args = dict(args or {})
         args.update(kwargs)
@@ -340,27 +387,16 @@ class FormSystem(PatchSystem):
             rhs = assemble.inner_products(self.kvs, rhs, f_physical=True, geo=args['geo'])
         elif np.ndim(rhs) == 0:
             rhs = np.full(self.n, float(rhs))
-        self._create(rhs, bcs, 'igx_solver_create_general')
-        self.method = 'bicgstab'
-        self.set_method(method)
+        self._create(rhs, bcs, 'igx_solver_create_general', 'bicgstab', method)
 
     @property
     def default_precond(self):
         return 'kron' if self.box is not None else 'jacobi'
 
-    def close(self):
-        if getattr(self, 'handle', None):
-            _lib.load().igx_solver_destroy(self.handle)
-            self.handle = None
-        if getattr(self, 'patch', None) is not None and self._own_patch:
-            self.patch.close()
-        self.patch = None
-
     def solve(self, tol=1e-8, maxiter=1000, precond='auto', x0=None, check_every=1, timed=False):
         """BiCGStab to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full solution vector.  `precond`: 'auto' (see the
         class), 'kron', 'jacobi' or None."""
-        return PatchSystem.solve(self, tol=tol, maxiter=maxiter, precond=self.default_precond if precond == 'auto' else precond,
-                                 x0=x0, check_every=check_every, timed=timed)
+        return self._solve(self.b, tol, maxiter, self.default_precond if precond == 'auto' else precond, x0, check_every, timed)
 
 
 ################################################################################
@@ -400,33 +436,19 @@ def schwarz_factors(kvs_list, boxes, kind='stiffness', mats1d=None):
     ``bsp_stiffness_1d`` / ``bsp_mass_1d``)."""
     if kind not in ('mass', 'stiffness'):
         raise ValueError('the Schwarz preconditioner has a Kronecker set-up for mass and stiffness only, not %r' % (kind,))
-    if mats1d is None:
-        from .assemble import bsp_mass_1d, bsp_stiffness_1d
-
-        def mats1d(kv):
-            return (bsp_stiffness_1d(kv) if kind == 'stiffness' else None), bsp_mass_1d(kv)
-    U, lam = [], []
+    U, lam, mode = [], [], None
     for kvs, (lo, hi) in zip(kvs_list, boxes):
-        Up, Lp = [], []
-        for kv, a, b in zip(kvs, lo, hi):
-            K, M = mats1d(kv)
-            M = _dense(M)[a:b, a:b]
-            if kind == 'stiffness':
-                w, V = scipy.linalg.eigh(_dense(K)[a:b, a:b], M)
-            else:
-                w, V = scipy.linalg.eigh(M)
-            Up.append(np.ascontiguousarray(V))
-            Lp.append(np.ascontiguousarray(w))
+        Up, Lp, mode = fastdiag_factors(kvs, lo, hi, kind == 'stiffness', mats1d)
         floating = all(a == 0 for a in lo) and all(b == kv.numdofs for b, kv in zip(hi, kvs))
         if kind == 'stiffness' and floating and all(len(l) > 1 for l in Lp):
             sigma = min(l[1] for l in Lp)
             Lp = [l + sigma / len(Lp) for l in Lp]
         U.append(Up)
         lam.append(Lp)
-    return U, lam, (_lib.IGX_KRON_SUM if kind == 'stiffness' else _lib.IGX_KRON_PRODUCT)
+    return U, lam, mode
 
 
-class MultipatchSystem:
+class MultipatchSystem(_DeviceSystem):
     """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, of the global system of the multipatch `MP`, summed and
     solved on the device.
 
@@ -438,8 +460,10 @@ class MultipatchSystem:
     ``MP.assemble_system`` restarts them (a solve then raises), and ``MP.close()`` destroys the system's device solver.
     """
 
+    PRECONDS = _lib.MP_PRECONDS
+    FACTORED = 'schwarz'
+
     def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', **kwargs):
-        self.handle = None
         self.MP = MP
         _check_method(method)
         kinds = []
@@ -454,43 +478,14 @@ class MultipatchSystem:
         h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect)
         self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
         self.n = MP.numdofs
-        self.bc_indices, self.bc_values = _bcs_arrays(bcs)
-        idx = self.bc_indices
-        self._precond = None
-        self._schwarz = False
-        self.info = None
-        out = C.c_void_p()
-        _lib.check(_lib.load().igx_solver_create_multipatch(h, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size, C.byref(out)),
-                   'igx_solver_create_multipatch')
-        self.handle = out.value
         self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
+        self._attach('igx_solver_create_multipatch', (h,), bcs, method, 'cg')
         MP._solvers.add(self)
-        self.method = 'cg'
-        if method != 'cg':
-            _lib.check(_lib.load().igx_solver_set_method(self.handle, _lib.METHODS[method]), 'igx_solver_set_method')
-            self.method = method
 
-    def _release(self):
-        if getattr(self, 'handle', None):
-            _lib.load().igx_solver_destroy(self.handle)
-            self.handle = None
-
-    def close(self):
-        self._release()
+    def _drop_owner(self):
         MP = getattr(self, 'MP', None)
         if MP is not None:
             MP._solvers.discard(self)
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _live(self):
-        if not self.handle:
-            raise _lib.IgxError('MultipatchSystem: the solver was closed (or its Multipatch was closed or re-joined)')
-        return self.handle
 
     def schwarz_setup(self):
         """Boxes, factors and mode of the Schwarz preconditioner (host set-up)."""
@@ -504,26 +499,15 @@ class MultipatchSystem:
         U, lam, mode = schwarz_factors([tuple(kvs) for kvs, _ in MP.patches], boxes, kind)
         return boxes, U, lam, mode
 
-    def set_precond(self, precond):
-        key = precond if precond is not None else 'none'
-        if key not in _lib.MP_PRECONDS:
-            raise ValueError('unknown preconditioner %r' % (precond,))
-        h = self._live()
-        if key == self._precond:
-            return
-        lib = _lib.load()
-        if key == 'schwarz' and not self._schwarz:
-            boxes, U, lam, mode = self.schwarz_setup()
-            P = len(boxes)
-            lo = (C.c_int32 * (3 * P))(*[b[0][k] if k < len(b[0]) else 0 for b in boxes for k in range(3)])
-            hi = (C.c_int32 * (3 * P))(*[b[1][k] if k < len(b[1]) else 0 for b in boxes for k in range(3)])
-            Up = (_lib._dp * (3 * P))(*[_lib.dptr(u[k]) if k < len(u) else None for u in U for k in range(3)])
-            Lp = (_lib._dp * (3 * P))(*[_lib.dptr(l[k]) if k < len(l) else None for l in lam for k in range(3)])
-            _lib.check(lib.igx_solver_set_schwarz(h, lo, hi, Up, Lp, mode), 'igx_solver_set_schwarz')
-            self._schwarz = True
-        else:
-            _lib.check(lib.igx_solver_set_precond(h, _lib.MP_PRECONDS[key], None, None, None, None, 0), 'igx_solver_set_precond')
-        self._precond = key
+    def _set_factors(self, h):
+        boxes, U, lam, mode = self.schwarz_setup()
+        P = len(boxes)
+        lo = (C.c_int32 * (3 * P))(*[b[0][k] if k < len(b[0]) else 0 for b in boxes for k in range(3)])
+        hi = (C.c_int32 * (3 * P))(*[b[1][k] if k < len(b[1]) else 0 for b in boxes for k in range(3)])
+        Up = (_lib._dp * (3 * P))(*[_lib.dptr(u[k]) if k < len(u) else None for u in U for k in range(3)])
+        Lp = (_lib._dp * (3 * P))(*[_lib.dptr(l[k]) if k < len(l) else None for l in lam for k in range(3)])
+        _lib.check(_lib.load().igx_solver_set_schwarz(h, lo, hi, Up, Lp, mode), 'igx_solver_set_schwarz')
+        self._factors_set = True
 
     def solve(self, tol=1e-8, maxiter=1000, precond='jacobi', x0=None, check_every=1, timed=False, b=None):
         """CG (or BiCGStab) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the global solution vector (the Dirichlet values included).
@@ -533,38 +517,4 @@ class MultipatchSystem:
         fast-diagonalization solve per patch, a few small GEMMs that leave most of the device idle on 2D patches: on the 2D
         notebook domain (p = 3, n = 256) it takes 2.7x fewer iterations and 4x the time of Jacobi.  It pays in 3D and on
         ill-conditioned systems."""
-        self.set_precond(precond)
-        u = np.empty(self.n)
-        x0a = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64).ravel()
-        if x0a is not None and x0a.size != self.n:
-            raise ValueError('x0 has the wrong size')
-        ba = None if b is None else np.ascontiguousarray(b, dtype=np.float64).ravel()
-        if ba is not None and ba.size != self.n:
-            raise ValueError('b has the wrong size')
-        info = _lib.SolveInfo()
-        _lib.check(_lib.load().igx_solver_solve(self._live(), None if ba is None else _lib.dptr(ba), _lib.dptr(self.bc_values),
-                                                None if x0a is None else _lib.dptr(x0a), float(tol), int(maxiter),
-                                                int(check_every), 1 if timed else 0, _lib.dptr(u), C.byref(info)),
-                   'igx_solver_solve')
-        self.info = _info_dict(info, self._precond, self.method, self.handle)
-        return u
-
-    def _device_op(self, fn, what, x):
-        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
-        if x.size != self.n:
-            raise ValueError('vector of %d entries, the system has %d' % (x.size, self.n))
-        h = self._live()
-        d_x = DeviceArray.from_host(self._ctx, x)
-        d_y = DeviceArray(self._ctx, self.n)
-        _lib.check(fn(h, d_x.ptr, d_y.ptr), what)
-        return d_y.download()
-
-    def spmv(self, x):
-        """``R A R^T x`` on the device (global vectors in and out)."""
-        return self._device_op(_lib.load().igx_solver_spmv_d, 'igx_solver_spmv_d', x)
-
-    def apply_precond(self, r, precond=None):
-        """``z = P r`` on the device with the preconditioner of the last solve, or `precond` if given."""
-        if precond is not None:
-            self.set_precond(precond)
-        return self._device_op(_lib.load().igx_solver_precond_d, 'igx_solver_precond_d', r)
+        return self._solve(b, tol, maxiter, precond, x0, check_every, timed)

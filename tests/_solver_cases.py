@@ -81,20 +81,28 @@ def parse_gw_thresholds(src):
 
 
 def _cases(body, kernel):
-    """{(label, GW, U)} of the `case N:` / `default:` lines of a switch that launch or query `kernel<GW, U>`."""
+    """{(label, GW, U)} of the `case N:` / `default:` lines of a switch that name `kernel<GW, U>`."""
     out = set()
     for label, gw, u in re.findall(r'(case \d+|default):[^\n]*?\b%s<(\d+), (\d+)>' % kernel, body):
         out.add((None if label == 'default' else int(label.split()[1]), int(gw), int(u)))
     return out
 
 
+# the dispatch table of each SpMV kernel family: the function that maps a group width to its instantiation
+TABLES = {'k_spmv': 'decltype(auto) with_spmv_kernel(', 'k_csr_spmv': 'decltype(auto) with_csr_spmv_kernel('}
+
+
 def parse_dispatch(src):
-    """The case lines of spmv(), csr_spmv() and the two switches of spmv_occupancy()."""
-    occ = _function_body(src, 'int spmv_occupancy(')
-    return {'spmv': _cases(_function_body(src, 'int spmv(hipStream_t'), 'k_spmv'),
-            'csr_spmv': _cases(_function_body(src, 'int csr_spmv('), 'k_csr_spmv'),
-            'occupancy_spmv': _cases(occ, 'k_spmv'),
-            'occupancy_csr_spmv': _cases(occ, 'k_csr_spmv')}
+    """The case lines of the dispatch tables, per kernel family."""
+    return {kernel: _cases(_function_body(src, sig), kernel) for kernel, sig in TABLES.items()}
+
+
+def instances_outside_tables(src):
+    """The template argument lists of k_spmv / k_csr_spmv written anywhere but in the dispatch tables."""
+    for sig in TABLES.values():
+        body = _function_body(src, sig)
+        src = src.replace(body, '')
+    return re.findall(r'\bk_(?:csr_)?spmv\s*<[^>]*>', src)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 """The SpMV instantiations of the device solvers and the cases that run them cannot drift apart (no GPU needed).
 
-pyiga_amd/csrc/solve.hip picks the group width of k_spmv / k_csr_spmv with spmv_gw(maxlen) and launches one instantiation per
-width from the switches of spmv(), csr_spmv() and spmv_occupancy(); the SpMV and vector kernels loop over their rows with grids
-of at most NB_SPMV_MAX and NB_VEC blocks.  tests/_solver_cases.py restates all of it, and tests/test_solver_kernels_gpu.py runs
+pyiga_amd/csrc/solve.hip picks the group width of k_spmv / k_csr_spmv with spmv_gw(maxlen) and maps it to one instantiation
+per width in the dispatch table of each family (with_spmv_kernel, with_csr_spmv_kernel), through which both the launch and the
+occupancy query go; the SpMV and vector kernels loop over their rows with grids of at most NB_SPMV_MAX and NB_VEC blocks.  tests/_solver_cases.py restates all of it, and tests/test_solver_kernels_gpu.py runs
 its cases.  A new width, a changed threshold, a dropped case line or a larger grid constant fails here: the table must then
 be extended so that every instantiation, and the second pass of every grid-stride loop, still runs under a test."""
 import numpy as np
@@ -30,17 +30,22 @@ def test_spmv_gw_thresholds(src):
     assert sc.spmv_gw(1) == 4 and sc.spmv_gw(10 ** 6) == 64
 
 
-def test_dispatch_case_lines(src):
-    """Every width has a case line in spmv(), csr_spmv() and both switches of spmv_occupancy(); the label is the width it
-    launches (the default: GW 4), and the occupancy query asks about the kernel the launch uses."""
+def test_dispatch_table_case_lines(src):
+    """Every width has a case line in the dispatch table of each kernel family; the label is the width it names (the default:
+    GW 4)."""
     d = sc.parse_dispatch(src)
-    for name, inst in (('spmv', sc.SPMV_INSTANCES), ('csr_spmv', sc.CSR_SPMV_INSTANCES),
-                       ('occupancy_spmv', sc.SPMV_INSTANCES), ('occupancy_csr_spmv', sc.CSR_SPMV_INSTANCES)):
+    for name, inst in (('k_spmv', sc.SPMV_INSTANCES), ('k_csr_spmv', sc.CSR_SPMV_INSTANCES)):
         lines = d[name]
         assert len(lines) == len(sc.GWS), (name, sorted(lines, key=str))
         assert {(gw, u) for _, gw, u in lines} == inst, (name, sorted(lines, key=str))
         for label, gw, _ in lines:
             assert label == gw or (label is None and gw == 4), (name, label, gw)
+
+
+def test_no_instance_outside_the_dispatch_tables(src):
+    """No instantiation is named outside the tables: the launch and the occupancy query take their kernel from the same table,
+    so the query asks about the kernel that is launched."""
+    assert sc.instances_outside_tables(src) == []
 
 
 def test_spmv_pass_bounds():
