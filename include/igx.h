@@ -483,6 +483,27 @@ int  igx_solver_set_method(igx_solver *solver, int method);
 /* IGX_BREAKDOWN_* of the last solve, 0 if it did not break down (and for CG). */
 int  igx_solver_last_breakdown(const igx_solver *solver);
 
+/* --- Vector-valued forms (bfuns = [('u', nc), ('v', nc)]: elasticity, grad-div, ...): a block solver over the nc x nc scalar
+   IGX_FORM blocks A_pq (test component p, trial component q), each in the patch's structured layout.  Vectors have nc * N entries,
+   component-major (the reference's 'blocked' layout; N = nrows_total).  The block SpMV reads every block present once per product;
+   an absent block is zero.  The solver owns its blocks and frees them in igx_solver_destroy; it does NOT own the patch, which
+   must outlive the takes (re-assembling the patch afterwards leaves the solver as it is).  The other igx_solver_* calls work on
+   it unchanged: IGX_PRECOND_JACOBI takes the diagonals of the diagonal blocks, IGX_PRECOND_KRON (box and factor arguments NULL)
+   the block-diagonal preconditioner diag(P_0, .., P_{nc-1}) of the factors igx_solver_set_block_kron set per component.  A
+   solve, an SpMV or the Jacobi set-up while a diagonal block is missing: IGX_ERR_ARG.
+   A block solver of patch `patch` (whole patches only, as igx_solver_create) with ncomp = 2 or 3 components (else IGX_ERR_ARG);
+   fixed[0..nfixed) index into the nc * N entries.  It starts in IGX_METHOD_CG if `symmetric`, else in IGX_METHOD_BICGSTAB;
+   IGX_METHOD_CG on a solver made with symmetric = 0 is IGX_ERR_UNSUPPORTED.  No values are needed yet. */
+int  igx_solver_create_block(igx_patch *patch, int ncomp, int symmetric, const int64_t *fixed, int64_t nfixed, igx_solver **out);
+/* Moves the IGX_FORM values the patch holds now (igx_assemble(patch, IGX_FORM, algo, NULL)) into block (p, q): a hand-over of
+   the device buffer, not a copy.  The patch then holds no values (its next assembly allocates anew).  p or q out of range, a
+   block taken twice, or a patch without IGX_FORM values: IGX_ERR_ARG. */
+int  igx_solver_take_block(igx_solver *solver, int p, int q);
+/* The fast-diagonalization inverse (x)U_k . D^-1 . (x)U_k^T of component `comp` on its free box box_lo[k] <= i_k < box_hi[k],
+   which must be exactly the free dofs of that component (arguments as igx_solver_set_precond's, lam_mode IGX_KRON_*). */
+int  igx_solver_set_block_kron(igx_solver *solver, int comp, const int32_t *box_lo, const int32_t *box_hi,
+                               const double *const *U, const double *const *lam, int mode);
+
 /* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers.  The factors are dense, row-major, m[k] x n[k]
    (rectangular allowed).  x and y are tensors of shape (n_0, .., n_{dim-1}, batch) and (m_0, .., batch), addressed through an
    element offset and four strides (axis 3 = the trailing batch axis), so a sub-box of a longer vector can be read or written.

@@ -159,6 +159,9 @@ SYMBOLS = [
     ('igx_solver_set_method', C.c_int, [C.c_void_p, C.c_int]),
     ('igx_solver_last_breakdown', C.c_int, [C.c_void_p]),
     ('igx_solver_create_multipatch', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_create_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_take_block', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ('igx_solver_set_block_kron', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
     ('igx_solver_destroy', None, [C.c_void_p]),
     ('igx_solver_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
     ('igx_solver_set_schwarz', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),

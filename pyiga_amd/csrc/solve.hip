@@ -13,6 +13,8 @@
 //              nonzero), k_csr_diag its diagonal; the additive Schwarz preconditioner gathers the box of every patch
 //              (k_box_gather), applies the patch's fast-diagonalization inverse with the k_kron steps and adds it back
 //              (k_box_scatter), patch after patch.
+//   k_block_spmv  the product of a vector-valued form's NC x NC blocks (NC = 2, 3), which share the patch's layout: one group per
+//              scalar row computes the NC outputs (igx_solver_create_block).
 //   vector     fused CG updates and fixed-order two-pass dot products (fixed grid, fixed trees): two solves of the same
 //              system give bit-identical results.  alpha and beta stay in device memory.
 //   BiCGStab   for non-symmetric matrices (igx_solver_create_general / igx_solver_set_method): the same SpMVs and
@@ -130,6 +132,101 @@ __global__ void __launch_bounds__(BLOCK) k_spmv(const Geom g, const double *__re
             const double v = (b ? b[I] : 0.0) + s * acc;
             y[I] = v;
             if (pd) dot += pd[I] * v;
+        }
+    }
+    if (part) {
+        const double v = block_sum(dot, sh);
+        if (threadIdx.x == 0) part[blockIdx.x] = v;
+    }
+}
+
+// the NC x NC blocks of a vector-valued form: v[p * NC + q] holds block (p, q) (test component p, trial component q) in the
+// patch's structured layout, or is null (a block that was never assembled: zero)
+struct BlockVals {
+    const double *v[9];
+};
+
+// The contract of k_spmv over the block matrix [A_pq].  Vectors have NC * N entries, component-major
+// (x_q[J] = x[q N + J]): y[p N + I] = free[p N + I] ? (b ? b[p N + I] : 0) + s * sum_q (A_pq x_q)[I] : 0, part[block] = sum of
+// pd . y over the NC outputs of the rows of the block (optional).  All blocks share the patch's pattern: one group of GW lanes per
+// scalar row I decodes the row header and the lane's position once per entry, gathers x_q[J] once for all NC outputs and streams
+// the NC^2 values of the entry.  Absent blocks (uniform over the grid) and the rows of fixed components (uniform over the group)
+// are not read.
+template <int GW, int U, int NC>
+__global__ void __launch_bounds__(BLOCK) k_block_spmv(const Geom g, const BlockVals A, const uint8_t *__restrict__ freem,
+                                                      const double *__restrict__ x, const double *b, double s, double *y,
+                                                      const double *__restrict__ pd, double *part)
+{
+    __shared__ double sh[BLOCK];
+    const int lane = threadIdx.x % GW;
+    const long long ngroups = (long long)gridDim.x * (BLOCK / GW);
+    const long long N = g.nrows;
+    const int N1 = g.N[1], N2 = g.N[2];
+    const int N12 = N1 * N2;
+    double dot = 0.0;
+    long long I = (long long)blockIdx.x * (BLOCK / GW) + threadIdx.x / GW;
+    RowHdr h{};
+    if (I < N) h = row_hdr(g, freem, I);
+    for (; I < N; I += ngroups) {
+        const RowHdr cur = h;
+        if (I + ngroups < N) h = row_hdr(g, freem, I + ngroups);
+        bool fr[NC], any = false;
+#pragma unroll
+        for (int p = 0; p < NC; ++p) {
+            fr[p] = freem[p * N + I] != 0;
+            any = any || fr[p];
+        }
+        if (!any) {                                  // (uniform over the group)
+            if (lane < NC) y[lane * N + I] = 0.0;
+            continue;
+        }
+        const int c0 = cur.c0 - cur.l0, c1 = cur.c1 - cur.l1, c2 = cur.c2 - cur.l2;
+        const int len = c0 * c1 * c2;
+        const long long row = igx_rowptr3(&cur.r0, &cur.r1, &cur.r2, g.S1, g.S2, c0, c1, 0, 0, 0);
+        const int xbase = (cur.l0 * N1 + cur.l1) * N2 + cur.l2;
+        int c = lane % c2, bb = (lane / c2) % c1, a = lane / (c1 * c2);
+        const int dc = GW % c2, db = (GW / c2) % c1, da = GW / (c1 * c2);
+        double acc[NC];
+#pragma unroll
+        for (int p = 0; p < NC; ++p) acc[p] = 0.0;
+        for (int k0 = lane; k0 < len; k0 += U * GW) {
+            double v[U][NC][NC], xv[U][NC];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k0 + u * GW < len;
+                const long long J = xbase + a * N12 + bb * N2 + c;
+#pragma unroll
+                for (int q = 0; q < NC; ++q) xv[u][q] = in ? x[q * N + J] : 0.0;
+#pragma unroll
+                for (int p = 0; p < NC; ++p)
+#pragma unroll
+                    for (int q = 0; q < NC; ++q) {
+                        const double *vp = A.v[p * NC + q];
+                        v[u][p][q] = (in && fr[p] && vp) ? __builtin_nontemporal_load(vp + row + k0 + u * GW) : 0.0;
+                    }
+                c += dc; bb += db; a += da;
+                if (c >= c2) { c -= c2; ++bb; }
+                if (bb >= c1) { bb -= c1; ++a; }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int p = 0; p < NC; ++p)
+#pragma unroll
+                    for (int q = 0; q < NC; ++q) acc[p] += v[u][p][q] * xv[u][q];
+        }
+#pragma unroll
+        for (int p = 0; p < NC; ++p)
+#pragma unroll
+            for (int off = GW / 2; off > 0; off >>= 1) acc[p] += __shfl_xor(acc[p], off, GW);
+        if (lane == 0) {
+#pragma unroll
+            for (int p = 0; p < NC; ++p) {
+                const long long o = p * N + I;
+                const double v = fr[p] ? (b ? b[o] : 0.0) + s * acc[p] : 0.0;
+                y[o] = v;
+                if (pd) dot += pd[o] * v;
+            }
         }
     }
     if (part) {
@@ -705,6 +802,28 @@ decltype(auto) with_csr_spmv_kernel(int gw, F &&f)
     }
 }
 
+// the same for the block SpMV of nc = 2 or 3 components (U: NC^2 U values of each lane in flight)
+template <class F>
+decltype(auto) with_block_spmv_kernel(int gw, int nc, F &&f)
+{
+    if (nc == 3) {
+        switch (gw) {
+        case 64: return f(k_block_spmv<64, 2, 3>);
+        case 32: return f(k_block_spmv<32, 2, 3>);
+        case 16: return f(k_block_spmv<16, 2, 3>);
+        case 8: return f(k_block_spmv<8, 2, 3>);
+        default: return f(k_block_spmv<4, 2, 3>);
+        }
+    }
+    switch (gw) {
+    case 64: return f(k_block_spmv<64, 4, 2>);
+    case 32: return f(k_block_spmv<32, 4, 2>);
+    case 16: return f(k_block_spmv<16, 4, 2>);
+    case 8: return f(k_block_spmv<8, 4, 2>);
+    default: return f(k_block_spmv<4, 4, 2>);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // the fast-diagonalization inverse  (x) U_k . D^-1 . (x) U_k^T  of one box (m[k] dofs on axis k): x is read and y written at
 // io_off with the strides io_stride, in between compact box vectors.  Its factors, per axis U_k^T | U_k | lam_k, lie in one
@@ -820,12 +939,26 @@ struct igx_solver {
     int breakdown = 0;                        // reason of the last BiCGStab solve (IGX_BREAKDOWN_*), 0 if none
     hipEvent_t bev[8] = {};
     bool have_bev = false;
+    // block solver of a vector-valued form (igx_solver_create_block): ncomp components of g.nrows dofs each, n = ncomp g.nrows
+    int ncomp = 1;
+    bool symmetric = false;                   // made as symmetric: CG allowed
+    double *blk[9] = {};                      // block (p, q) at p * ncomp + q, taken from the patch (owned), or null
+    FastDiag bkron[3] = {};                   // per component: the fast-diagonalization inverse on its free box (in d_bkron[c])
+    double *d_bkron[3] = {};
 };
 
 namespace {
 
 int check_values(const igx_solver *s, const char *what)
 {
+    if (s->ncomp > 1) {                       // (the blocks are the solver's own: only a missing diagonal one is refused)
+        for (int c = 0; c < s->ncomp; ++c)
+            if (!s->blk[c * s->ncomp + c]) {
+                set_error("%s: diagonal block (%d, %d) missing: take it first (igx_solver_take_block)", what, c, c);
+                return IGX_ERR_ARG;
+            }
+        return IGX_OK;
+    }
     if (s->mp) {
         if (s->mp->generation != s->gen) {
             set_error("%s: the multipatch's sums were restarted (igx_multipatch_zero) since the solver was made: make a new solver "
@@ -844,11 +977,12 @@ int check_values(const igx_solver *s, const char *what)
 
 unsigned spmv_blocks(const igx_solver *s)
 {
-    const long long groups = BLOCK / s->gw;
-    return (unsigned)std::max<long long>(1, std::min<long long>(s->nb_spmv, (s->n + groups - 1) / groups));
+    const long long groups = BLOCK / s->gw, rows = s->n / s->ncomp;      // (a block solver: one group per scalar row)
+    return (unsigned)std::max<long long>(1, std::min<long long>(s->nb_spmv, (rows + groups - 1) / groups));
 }
 
-// y = free ? (b ? b : 0) + sign A x : 0 (and the partials of pd.y): k_spmv on a patch's values, k_csr_spmv on a multipatch's sums
+// y = free ? (b ? b : 0) + sign A x : 0 (and the partials of pd.y): k_spmv on a patch's values, k_csr_spmv on a multipatch's sums,
+// k_block_spmv on the blocks of a block solver
 int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
 {
     const unsigned nb = spmv_blocks(s);
@@ -857,6 +991,10 @@ int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, 
         with_csr_spmv_kernel(s->gw, [&](auto k) {
             k<<<nb, BLOCK, 0, st>>>(s->n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part);
         });
+    } else if (s->ncomp > 1) {
+        BlockVals A{};
+        for (int k = 0; k < s->ncomp * s->ncomp; ++k) A.v[k] = s->blk[k];
+        with_block_spmv_kernel(s->gw, s->ncomp, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, A, s->d_mask, x, b, sign, y, pd, part); });
     } else {
         with_spmv_kernel(s->gw, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, s->pt->d_data, s->d_mask, x, b, sign, y, pd, part); });
     }
@@ -866,10 +1004,16 @@ int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, 
 
 unsigned vec_blocks(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(NB_VEC, (n + BLOCK - 1) / BLOCK)); }
 
-// z = P r on the free box (kron), or nothing (none / Jacobi: z is formed by k_update or is r itself)
+// z = P r on the free box (kron; a block solver: on the free box of every component, diag(P_0, .., P_{nc-1})), or nothing
+// (none / Jacobi: z is formed by k_update or is r itself)
 int apply_kron(hipStream_t st, igx_solver *s, const double *r, double *z)
 {
     double *W[2] = {s->d_W, s->d_W + s->wlen};
+    if (s->ncomp > 1) {
+        for (int c = 0; c < s->ncomp; ++c)
+            if (int rc = apply_fastdiag(st, s->bkron[c], r, z, W)) return rc;
+        return IGX_OK;
+    }
     return apply_fastdiag(st, s->kron, r, z, W);
 }
 
@@ -899,7 +1043,8 @@ int spmv_occupancy(const igx_solver *s)
 {
     int per_cu = 0;
     auto occupancy = [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0); };
-    const hipError_t eo = s->mp ? with_csr_spmv_kernel(s->gw, occupancy) : with_spmv_kernel(s->gw, occupancy);
+    const hipError_t eo = s->mp ? with_csr_spmv_kernel(s->gw, occupancy)
+                                : s->ncomp > 1 ? with_block_spmv_kernel(s->gw, s->ncomp, occupancy) : with_spmv_kernel(s->gw, occupancy);
     if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
     return (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, s->ctx->ncu));
 }
@@ -909,6 +1054,8 @@ void free_solver(igx_solver *s)
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
     (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
     (void)hipFree(s->d_bvec); (void)hipFree(s->d_bsc);
+    for (double *v : s->blk) (void)hipFree(v);
+    for (double *v : s->d_bkron) (void)hipFree(v);
     if (s->have_ev)
         for (auto &e : s->ev) (void)hipEventDestroy(e);
     if (s->have_bev)
@@ -1158,20 +1305,21 @@ int init_solver(igx_solver *s, const int64_t *fixed, int64_t nfixed, long long m
     return IGX_OK;
 }
 
-// a solver over the values of `kind` the patch holds (the kind itself checked by the caller)
-int create_patch_solver(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what)
+// a solver over the values of `kind` the patch holds (the kind itself checked by the caller); ncomp > 1: a block solver of ncomp
+// components, whose blocks are taken from the patch later (igx_solver_take_block)
+int create_patch_solver(igx_patch *pt, int kind, int ncomp, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what)
 {
     if (pt->boxed || pt->row_lo != 0 || pt->row_hi != pt->nrows_total) {
         set_error("%s: whole patches only (no row slab, no span box)", what);
         return IGX_ERR_UNSUPPORTED;
     }
-    if (pt->values_kind != kind || !pt->d_data) {
+    if (ncomp == 1 && (pt->values_kind != kind || !pt->d_data)) {
         set_error("%s: assemble the patch with this kind first (igx_assemble, data_out may be NULL)", what);
         return IGX_ERR_ARG;
     }
     if (hipSetDevice(pt->ctx->device) != hipSuccess) { set_error("%s: hipSetDevice failed", what); return IGX_ERR_HIP; }
     igx_solver *s = new igx_solver;
-    s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->n = pt->nrows_total;
+    s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->ncomp = ncomp; s->n = ncomp * pt->nrows_total;
     for (int k = 0; k < pt->dim; ++k) s->N[k] = pt->ax[k].N;
     // per-axis tables as a 3D layout (2D: a one-dof outer axis in front)
     const int off = 3 - pt->dim;
@@ -1196,8 +1344,36 @@ int create_patch_solver(igx_patch *pt, int kind, const int64_t *fixed, int64_t n
     for (int a = 0; a < 3; ++a) { s->g.jlo[a] = s->d_tab + pos[a][0]; s->g.jhi[a] = s->d_tab + pos[a][1]; s->g.rp[a] = s->d_tab + pos[a][2]; }
     s->g.S1 = tab[pos[1][2] + s->g.N[1]];
     s->g.S2 = tab[pos[2][2] + s->g.N[2]];
-    s->g.nrows = s->n;
+    s->g.nrows = pt->nrows_total;
     *out = s;
+    return IGX_OK;
+}
+
+// the box lo[k] <= i_k < hi[k] (nb[k] = hi[k] - lo[k] out) must be exactly the free dofs of the component at `base` (a patch
+// solver: 0): the fast-diagonalization inverse leaves everything outside it at 0
+int check_free_box(const igx_solver *s, long long base, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                   const double *const *lam, int nb[3], const char *what)
+{
+    const int d = s->dim;
+    for (int k = 0; k < d; ++k) {
+        if (box_lo[k] < 0 || box_hi[k] > s->N[k] || box_lo[k] >= box_hi[k] || !U[k] || !lam[k]) {
+            set_error("%s: bad free box [%d, %d) on axis %d", what, box_lo[k], box_hi[k], k);
+            return IGX_ERR_ARG;
+        }
+        nb[k] = box_hi[k] - box_lo[k];
+    }
+    long long I = 0;
+    int i[3] = {0, 0, 0};
+    for (i[0] = 0; i[0] < s->N[0]; ++i[0])
+        for (i[1] = 0; i[1] < (d > 1 ? s->N[1] : 1); ++i[1])
+            for (i[2] = 0; i[2] < (d > 2 ? s->N[2] : 1); ++i[2], ++I) {
+                bool in = true;
+                for (int k = 0; k < d; ++k) in = in && i[k] >= box_lo[k] && i[k] < box_hi[k];
+                if (in != (s->h_free[base + I] != 0)) {
+                    set_error("%s: the free dofs are not the box given (dof %lld)", what, base + I);
+                    return IGX_ERR_ARG;
+                }
+            }
     return IGX_OK;
 }
 
@@ -1212,7 +1388,7 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
         set_error("igx_solver_create: CG needs a symmetric positive definite matrix (IGX_MASS or IGX_STIFFNESS), kind %d", kind);
         return IGX_ERR_UNSUPPORTED;
     }
-    return create_patch_solver(pt, kind, fixed, nfixed, out, "igx_solver_create");
+    return create_patch_solver(pt, kind, 1, fixed, nfixed, out, "igx_solver_create");
 }
 
 int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
@@ -1223,7 +1399,7 @@ int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int
         return IGX_ERR_ARG;
     }
     igx_solver *s = nullptr;
-    if (int rc = create_patch_solver(pt, kind, fixed, nfixed, &s, "igx_solver_create_general")) return rc;
+    if (int rc = create_patch_solver(pt, kind, 1, fixed, nfixed, &s, "igx_solver_create_general")) return rc;
     if (int rc = init_bicgstab(s, "igx_solver_create_general")) { free_solver(s); return rc; }
     s->method = IGX_METHOD_BICGSTAB;
     *out = s;
@@ -1234,7 +1410,11 @@ int igx_solver_set_method(igx_solver *s, int method)
 {
     if (!s) { set_error("igx_solver_set_method: null solver"); return IGX_ERR_ARG; }
     if (method == IGX_METHOD_CG) {
-        if (!s->mp && !spd_kind(s->kind)) {
+        if (s->ncomp > 1 && !s->symmetric) {
+            set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; the block solver was made as non-symmetric");
+            return IGX_ERR_UNSUPPORTED;
+        }
+        if (s->ncomp == 1 && !s->mp && !spd_kind(s->kind)) {
             set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; kind %d is not known to be one", s->kind);
             return IGX_ERR_UNSUPPORTED;
         }
@@ -1261,6 +1441,80 @@ int igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64
     return IGX_OK;
 }
 
+int igx_solver_create_block(igx_patch *pt, int ncomp, int symmetric, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    const char *what = "igx_solver_create_block";
+    if (!create_args_ok(pt, fixed, nfixed, out, what)) return IGX_ERR_ARG;
+    if (ncomp != 2 && ncomp != 3) { set_error("%s: ncomp must be 2 or 3, not %d", what, ncomp); return IGX_ERR_ARG; }
+    igx_solver *s = nullptr;
+    if (int rc = create_patch_solver(pt, IGX_FORM, ncomp, fixed, nfixed, &s, what)) return rc;
+    s->symmetric = symmetric != 0;
+    if (!s->symmetric) {
+        if (int rc = init_bicgstab(s, what)) { free_solver(s); return rc; }
+        s->method = IGX_METHOD_BICGSTAB;
+    }
+    *out = s;
+    return IGX_OK;
+}
+
+int igx_solver_take_block(igx_solver *s, int p, int q)
+{
+    const char *what = "igx_solver_take_block";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
+    if (p < 0 || p >= s->ncomp || q < 0 || q >= s->ncomp) { set_error("%s: block (%d, %d) of %d components", what, p, q, s->ncomp); return IGX_ERR_ARG; }
+    double *&dst = s->blk[p * s->ncomp + q];
+    if (dst) { set_error("%s: block (%d, %d) was taken already", what, p, q); return IGX_ERR_ARG; }
+    igx_patch *pt = s->pt;
+    if (pt->values_kind != IGX_FORM || !pt->d_data) {
+        set_error("%s: the patch holds no IGX_FORM values: assemble them first (igx_assemble, data_out may be NULL)", what);
+        return IGX_ERR_ARG;
+    }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    IGX_HIP(hipStreamSynchronize(pt->ctx->stream));
+    dst = pt->d_data;                               // the buffer changes hands: the patch's next assembly allocates anew
+    pt->d_data = nullptr;
+    pt->values_kind = -1;
+    return IGX_OK;
+}
+
+int igx_solver_set_block_kron(igx_solver *s, int comp, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                              const double *const *lam, int mode)
+{
+    const char *what = "igx_solver_set_block_kron";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
+    if (comp < 0 || comp >= s->ncomp) { set_error("%s: component %d of %d", what, comp, s->ncomp); return IGX_ERR_ARG; }
+    if (!box_lo || !box_hi || !U || !lam) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (mode != IGX_KRON_SUM && mode != IGX_KRON_PRODUCT) { set_error("%s: unknown lam_mode %d", what, mode); return IGX_ERR_ARG; }
+    const int d = s->dim;
+    const long long base = (long long)comp * s->g.nrows;
+    int nb[3] = {1, 1, 1};
+    if (int rc = check_free_box(s, base, box_lo, box_hi, U, lam, nb, what)) return rc;
+    std::vector<double> h;
+    pack_fastdiag(h, d, nb, U, lam);
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    IGX_HIP(hipStreamSynchronize(st));
+    if (s->precond == IGX_PRECOND_KRON) s->precond = IGX_PRECOND_NONE;      // (selected again by igx_solver_set_precond)
+    (void)hipFree(s->d_bkron[comp]); s->d_bkron[comp] = nullptr;
+    IGX_HIP(hipMalloc((void **)&s->d_bkron[comp], h.size() * sizeof(double)));
+    IGX_HIP(hipMemcpyAsync(s->d_bkron[comp], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const long long nbox = (long long)nb[0] * nb[1] * nb[2];
+    if (nbox > s->wlen) {                          // the two work buffers fit the largest box of any component
+        (void)hipFree(s->d_W); s->d_W = nullptr; s->wlen = 0;
+        IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)nbox * sizeof(double)));
+        s->wlen = nbox;
+    }
+    // (x) U_k^T reads the component's box of the full-length r, (x) U_k writes it into z
+    long long full_stride[4], off = base;
+    box_strides(d, s->N, full_stride);
+    for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
+    s->bkron[comp] = make_fastdiag(d, nb, s->d_bkron[comp], full_stride, off, mode);
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
 void igx_solver_destroy(igx_solver *s)
 {
     if (!s) return;
@@ -1279,7 +1533,11 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     if (precond == IGX_PRECOND_JACOBI) {
         if (int rc = check_values(s, "igx_solver_set_precond")) return rc;
         if (s->mp) k_csr_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->n, s->mp->d_indptr, s->mp->d_indices, s->mp->d_vals, s->d_mask, s->dinv);
-        else k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pt->d_data, s->d_mask, s->dinv);
+        else if (s->ncomp > 1) {
+            const long long N = s->g.nrows;                   // component c: the diagonal of block (c, c) at offset c N
+            for (int c = 0; c < s->ncomp; ++c)
+                k_diag<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(s->g, s->blk[c * s->ncomp + c], s->d_mask + c * N, s->dinv + c * N);
+        } else k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pt->d_data, s->d_mask, s->dinv);
         IGX_HIP(hipGetLastError());
         IGX_HIP(hipStreamSynchronize(st));
         s->precond = precond;
@@ -1293,32 +1551,20 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     }
     if (precond != IGX_PRECOND_KRON) { set_error("igx_solver_set_precond: unknown preconditioner %d", precond); return IGX_ERR_ARG; }
     if (s->mp) { set_error("igx_solver_set_precond: IGX_PRECOND_KRON needs a patch solver (multipatch: IGX_PRECOND_SCHWARZ)"); return IGX_ERR_UNSUPPORTED; }
+    if (s->ncomp > 1) {                                   // the factors of every component, set by igx_solver_set_block_kron
+        for (int c = 0; c < s->ncomp; ++c)
+            if (!s->d_bkron[c]) {
+                set_error("igx_solver_set_precond: set the Kronecker factors of component %d first (igx_solver_set_block_kron)", c);
+                return IGX_ERR_ARG;
+            }
+        s->precond = precond;
+        return IGX_OK;
+    }
     if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_precond: null argument"); return IGX_ERR_ARG; }
     if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_precond: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
     const int d = s->dim;
     int nb[3] = {1, 1, 1};
-    for (int k = 0; k < d; ++k) {
-        if (box_lo[k] < 0 || box_hi[k] > s->N[k] || box_lo[k] >= box_hi[k] || !U[k] || !lam[k]) {
-            set_error("igx_solver_set_precond: bad free box [%d, %d) on axis %d", box_lo[k], box_hi[k], k);
-            return IGX_ERR_ARG;
-        }
-        nb[k] = box_hi[k] - box_lo[k];
-    }
-    // the box must be exactly the free dofs: the preconditioner leaves everything outside it at 0
-    {
-        long long I = 0;
-        int i[3] = {0, 0, 0};
-        for (i[0] = 0; i[0] < s->N[0]; ++i[0])
-            for (i[1] = 0; i[1] < (d > 1 ? s->N[1] : 1); ++i[1])
-                for (i[2] = 0; i[2] < (d > 2 ? s->N[2] : 1); ++i[2], ++I) {
-                    bool in = true;
-                    for (int k = 0; k < d; ++k) in = in && i[k] >= box_lo[k] && i[k] < box_hi[k];
-                    if (in != (s->h_free[I] != 0)) {
-                        set_error("igx_solver_set_precond: the free dofs are not the box given (dof %lld)", I);
-                        return IGX_ERR_ARG;
-                    }
-                }
-    }
+    if (int rc = check_free_box(s, 0, box_lo, box_hi, U, lam, nb, "igx_solver_set_precond")) return rc;
     std::vector<double> h;
     pack_fastdiag(h, d, nb, U, lam);
     s->precond = IGX_PRECOND_NONE;

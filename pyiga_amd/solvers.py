@@ -18,6 +18,10 @@ and only the solution comes down.
 strings, the convection-diffusion form, ...), solved there by right-preconditioned BiCGStab -- what the reference does with
 ``assemble.assemble`` + ``RestrictedLinearSystem`` + ``make_solver`` (a direct LU) on the host.  ``method='bicgstab'`` also
 lets ``PatchSystem`` and ``MultipatchSystem`` solve by BiCGStab; ``MultipatchSystem`` then accepts non-symmetric forms.
+
+``VectorFormSystem(problem, kvs, rhs, bcs, bfuns=[('u', nc), ('v', nc)], geo=geo)``: the same for vector-valued forms (linear
+elasticity, grad-div, ...): the nc x nc scalar blocks are assembled on the device and stay there; a block SpMV and a
+block-diagonal fast-diagonalization preconditioner serve CG or BiCGStab.
 """
 import ctypes as C
 import re
@@ -397,6 +401,177 @@ class FormSystem(PatchSystem):
         """BiCGStab to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full solution vector.  `precond`: 'auto' (see the
         class), 'kron', 'jacobi' or None."""
         return self._solve(self.b, tol, maxiter, self.default_precond if precond == 'auto' else precond, x0, check_every, timed)
+
+
+################################################################################
+# Vector-valued Dirichlet problems of one patch on the device
+################################################################################
+
+def _vector_components(problem, kvs, args, bfuns):
+    """The number of components of a vector-valued volume form that VectorFormSystem solves; ValueError, before any device work,
+    for anything else (no ``geo``, a surface or boundary form, not bilinear, trial and test components that differ, a scalar form,
+    more than three components)."""
+    from . import tforms
+    if not isinstance(problem, str):
+        raise ValueError('VectorFormSystem needs a form string, not %r' % (problem,))
+    geo = args.get('geo')
+    if geo is None:
+        raise ValueError("required input parameter 'geo' missing")
+    if getattr(geo, 'dim', len(kvs)) != len(kvs) or re.search(r'\bds\b', problem):
+        raise ValueError('VectorFormSystem solves volume forms (dx), not surface or boundary forms: %r' % (problem,))
+    try:
+        bf = tforms.normalise_bfuns(problem, bfuns)
+    except NotImplementedError as e:
+        raise ValueError('VectorFormSystem: %s' % e)
+    if len(bf) != 2:
+        raise ValueError('VectorFormSystem needs a bilinear form (trial and test function), not arity %d: %r' % (len(bf), problem))
+    (_, ncu), (_, ncv) = bf
+    if ncu != ncv:
+        raise ValueError('VectorFormSystem: trial and test functions have %d and %d components (mixed systems are not '
+                         'supported)' % (ncu, ncv))
+    if ncu == 1:
+        raise ValueError('VectorFormSystem: %r is a scalar form: solve it with FormSystem' % (problem,))
+    if ncu not in (2, 3):
+        raise ValueError('VectorFormSystem solves forms of 2 or 3 components, not %d' % ncu)
+    return ncu
+
+
+def symmetric_block_tables(table, rtol=1e-13):
+    """True if the coefficient tables of a vector-valued form (``table[p][q][r][s]``: test component p with jet r, trial component
+    q with jet s; arrays on the Gauss grid or None) give a symmetric block matrix: ``C^{pq}_{rs} == C^{qp}_{sr}`` within `rtol`
+    of the largest entry of all tables, a None only opposite a None."""
+    nc = len(table)
+    big = 0.0
+    for row in table:
+        for tab in row:
+            for trow in tab:
+                for e in trow:
+                    if e is not None:
+                        big = max(big, float(np.max(np.abs(e))))
+    for p in range(nc):
+        for q in range(nc):
+            A, B = table[p][q], table[q][p]
+            for r in range(len(A)):
+                for s in range(len(A[r])):
+                    a, b = A[r][s], B[s][r]
+                    if (a is None) != (b is None):
+                        return False
+                    if a is not None and np.max(np.abs(np.asarray(a) - np.asarray(b))) > rtol * big:
+                        return False
+    return True
+
+
+class VectorFormSystem(_DeviceSystem):
+    """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, for a vector-valued form (``bfuns=[('u', nc),
+    ('v', nc)]``, nc = 2 or 3: linear elasticity, grad-div, ...) on one patch, assembled and solved on the device.
+
+    The nc x nc scalar blocks ``A_pq`` are assembled one after the other (IGX_FORM) and handed to the block solver of
+    ``igx_solver_create_block``; only the right-hand side goes up and the solution comes down.  Vectors have ``nc * N`` entries in
+    the reference's 'blocked' layout (component-major, as ``assemble(..., layout='blocked')``).  `method`: 'auto' is CG when the
+    coefficient tables are symmetric (``symmetric``), else BiCGStab; 'cg' on a non-symmetric form raises ValueError.  `rhs`: a
+    vector of ``nc * N`` entries or of shape ``(nc,) + ndofs``, a scalar, or a linear form string in the test function.  `bcs`:
+    ``(indices, values)`` in the blocked numbering, as ``compute_dirichlet_bcs`` gives them for a vector-valued ``dir_func``.
+    ``solve()`` uses the block-diagonal Kronecker preconditioner (the fast diagonalization of the parametric Laplacian on each
+    component's free box) when the Dirichlet dofs of every component are whole sides, else Jacobi.
+    """
+
+    def __init__(self, problem, kvs, rhs, bcs=None, args=None, bfuns=None, method='auto', **kwargs):
+        from . import assemble
+        from .form_assemblers import FormAssembler, _full_table
+        if method != 'auto':
+            _check_method(method)
+        args = dict(args or {})
+        args.update(kwargs)
+        self.kvs = tuple(kvs)
+        nc = _vector_components(problem, self.kvs, args, bfuns)
+        self.ncomp = nc
+        self.assembler = FormAssembler(self.kvs, args['geo'], problem, bfuns=bfuns, inputs=args)
+        self.patch = self.assembler.patch
+        table = self.assembler._table
+        self.symmetric = symmetric_block_tables(table)
+        if method == 'auto':
+            method = 'cg' if self.symmetric else 'bicgstab'
+        elif method == 'cg' and not self.symmetric:
+            raise ValueError('VectorFormSystem: CG needs a symmetric form; the coefficient tables of %r are not symmetric: '
+                             "method='bicgstab'" % (problem,))
+        self.ndofs = self.patch.ndofs
+        self.N = int(np.prod(self.ndofs))
+        self.n = nc * self.N
+        if isinstance(rhs, str):
+            test = _test_function_name(problem, bfuns)
+            rhs = assemble.assemble(rhs, self.kvs, args=args, bfuns=[(test, nc)], layout='blocked')
+        elif np.ndim(rhs) == 0:
+            rhs = np.full(self.n, float(rhs))
+        self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
+        if self.b.size != self.n:
+            raise ValueError('right-hand side has %d entries, the space %d x %d' % (self.b.size, nc, self.N))
+        self._ctx = self.patch.ctx
+        initial = 'cg' if self.symmetric else 'bicgstab'
+        self._attach('igx_solver_create_block', (self.patch.handle, nc, 1 if self.symmetric else 0), bcs, method, initial)
+        lib = _lib.load()
+        d = len(self.kvs)
+        self.present = [[False] * nc for _ in range(nc)]
+        for p in range(nc):
+            for q in range(nc):
+                tab = table[p][q]
+                if all(e is None for row in tab for e in row):
+                    continue                      # (an absent block: zero, never read)
+                self.patch.set_form(_full_table(tab, d))
+                self.patch.assemble('form', to_host=False)
+                _lib.check(lib.igx_solver_take_block(self.handle, p, q), 'igx_solver_take_block')
+                self.present[p][q] = True
+        idx = self.bc_indices
+        self.boxes = [dirichlet_box(self.ndofs, idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N)
+                      for c in range(nc)]
+
+    def _drop_owner(self):
+        if getattr(self, 'patch', None) is not None:
+            self.patch.close()
+        self.patch = None
+
+    @property
+    def default_precond(self):
+        return 'kron' if all(b is not None for b in self.boxes) else 'jacobi'
+
+    def kron_factors(self):
+        """Per component ``(lo, hi, U, lam, mode)``: the fast diagonalization of the parametric Laplacian on its free box.  A
+        component without a wholly fixed side gets ``sigma / d`` added to every ``lam_k`` (``sigma = min_k lam_k[1]``, as a
+        floating Schwarz patch): the inverse stays symmetric positive definite."""
+        out = []
+        for c, box in enumerate(self.boxes):
+            if box is None:
+                raise ValueError("precond='kron' needs the Dirichlet dofs of every component to be a union of whole sides of the "
+                                 "patch (component %d is not)" % c)
+            lo, hi = box
+            U, lam, mode = fastdiag_factors(self.kvs, lo, hi, True)
+            floating = all(a == 0 for a in lo) and all(b == kv.numdofs for b, kv in zip(hi, self.kvs))
+            if floating and all(len(l) > 1 for l in lam):
+                sigma = min(l[1] for l in lam)
+                lam = [l + sigma / len(lam) for l in lam]
+            out.append((lo, hi, U, lam, mode))
+        return out
+
+    def _set_factors(self, h):
+        lib = _lib.load()
+        for c, (lo, hi, U, lam, mode) in enumerate(self.kron_factors()):
+            lo_ = (C.c_int32 * 3)(*lo)
+            hi_ = (C.c_int32 * 3)(*hi)
+            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
+            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+            _lib.check(lib.igx_solver_set_block_kron(h, c, lo_, hi_, Up, Lp, mode), 'igx_solver_set_block_kron')
+        _lib.check(lib.igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, None, None, None, None, 0), 'igx_solver_set_precond')
+        self._factors_set = True
+
+    def solve(self, tol=1e-8, maxiter=1000, precond='auto', x0=None, check_every=1, timed=False):
+        """CG or BiCGStab (``method``) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the full blocked solution vector of
+        ``nc * N`` entries (the Dirichlet values included).  `precond`: 'auto' (see the class), 'kron', 'jacobi' or None."""
+        return self._solve(self.b, tol, maxiter, self.default_precond if precond == 'auto' else precond, x0, check_every, timed)
+
+
+def _test_function_name(problem, bfuns):
+    """The name of the test function of the bilinear form `problem` (the last of its basis functions)."""
+    from . import tforms
+    return tforms.normalise_bfuns(problem, bfuns)[-1][0]
 
 
 ################################################################################
