@@ -38,6 +38,8 @@
  *   igx_solver_* / igx_kron_apply_d    <- RestrictedLinearSystem + make_solver / cg, fastdiag_solver, KroneckerOperator
  *                                         pyiga/assemble.py:571-652, pyiga/solvers.py:17-42, pyiga/operators.py:60-86,
  *                                         pyiga/approx.py:62-96 (one patch, matrix values never leave the device)
+ *   igx_solver_*_parabolic / _dirk_*   <- crank_nicolson, sdirk3, esdirk34, ... (dirk_step, constant steps)
+ *                                         pyiga/solvers.py:366-473 (linear M u' = f - K u, one patch, on the device)
  */
 #ifndef IGX_H
 #define IGX_H
@@ -503,6 +505,59 @@ int  igx_solver_take_block(igx_solver *solver, int p, int q);
    which must be exactly the free dofs of that component (arguments as igx_solver_set_precond's, lam_mode IGX_KRON_*). */
 int  igx_solver_set_block_kron(igx_solver *solver, int comp, const int32_t *box_lo, const int32_t *box_hi,
                                const double *const *U, const double *const *lam, int mode);
+
+/* --- Parabolic problems: DIRK time stepping on the device (pyiga/solvers.py:366-473: dirk_step with constant steps) ----------
+   M u' = f - K u on the free dofs, u = g on the fixed ones, u(t0) = x0; f and g constant in time.  M is the patch's mass matrix,
+   K the matrix of kind_K (any kind igx_solver_create_general accepts).  One step of the tableau A ((stages + 1) x stages, row-major,
+   b the last row) from x (g on the fixed dofs):
+       stage i with a_ii = 0 (i = 0 only): y_0 = x, F_0 = F of the previous step's last stage (first step: f - K x0);
+       else  b_i = M x + tau sum_{j<i} a_ij F_j + tau gamma f,  R C R^T y_i = R (b_i - C ext(g)),  F_i = f - K y_i;
+       x_new = y_{s-1}  (stiffly accurate).
+   C = M + tau gamma K is formed once per (tau, tableau).  Every stage is one solve of the lifted system (the initial guess
+   y_{i-1}) by the solver's method and preconditioner, to ||r|| <= tol ||R (b_i - C ext(g))||.  M, K and C are the solver's
+   own value buffers; x, M x, y and the F_j stay on the device; a state comes down only when it is saved.  The other igx_solver_*
+   calls act on C (igx_solver_spmv_d: R C R^T x; Jacobi: the diagonal of C; IGX_PRECOND_KRON: any factors, e.g. those of
+   eigh(K_k, M_k) with lam'_k = tau gamma lam_k + 1/dim, the fast-diagonalization inverse of the parametric M + tau gamma K). */
+enum { IGX_DIRK_MAX_STAGES = 6 };
+enum { IGX_ROLE_MASS = 0, IGX_ROLE_OPERATOR = 1 };
+typedef struct {
+    int64_t steps;                 /* steps done */
+    int32_t converged;             /* 1 if every stage solve converged (then steps = nsteps) */
+    int32_t nsaved;                /* states written to `saved` */
+    int64_t iterations;            /* iterations of all stage solves */
+    int32_t max_stage_iterations;  /* the most iterations of one stage solve */
+    int32_t reserved;
+    float axpby_ms;                /* device time of forming C (the last igx_solver_set_dirk) */
+    float spmv_ms;                 /* timed != 0: the M x and F = f - K y products, summed over the run */
+    float combine_ms;              /* timed != 0: the stage combinations (b_i, the initial guess, y_i = x + ext(g)) */
+    float solve_ms;                /* timed != 0: the stage solves */
+    float total_ms;                /* device time of the whole run, transfers included */
+    float reserved2;
+} igx_dirk_info;
+/* A parabolic solver of one whole patch (as igx_solver_create: a row slab or a span box is IGX_ERR_UNSUPPORTED; an unknown kind
+   IGX_ERR_ARG).  No values are needed yet.  It starts in IGX_METHOD_CG if `symmetric` (M + tau gamma K symmetric positive
+   definite), else in IGX_METHOD_BICGSTAB; IGX_METHOD_CG on a solver made with symmetric = 0 is IGX_ERR_UNSUPPORTED. */
+int  igx_solver_create_parabolic(igx_patch *patch, int kind_K, int symmetric, const int64_t *fixed, int64_t nfixed, igx_solver **out);
+/* Moves the values the patch holds now into the solver: IGX_ROLE_MASS takes IGX_MASS values, IGX_ROLE_OPERATOR those of kind_K
+   (igx_assemble(patch, kind, algo, NULL) before each).  A hand-over of the device buffer, not a copy: the patch then holds no
+   values.  A role taken twice, a patch without the values of that kind, or a buffer whose length differs from the other role's:
+   IGX_ERR_ARG. */
+int  igx_solver_take_values(igx_solver *solver, int role);
+/* Validates the tableau A ((stages + 1) x stages, row-major, stages <= IGX_DIRK_MAX_STAGES) and the step tau, then forms
+   C = M + tau gamma K on the device (k_vals_axpby).  Refused (IGX_ERR_ARG): A not lower triangular, nonzero diagonal entries that
+   differ or are not positive, a zero diagonal past row 0, not stiffly accurate (b != the last stage row), tau <= 0, M or K not
+   taken.  Resets the preconditioner to IGX_PRECOND_NONE (Jacobi and Kronecker depend on C): select it again. */
+int  igx_solver_set_dirk(igx_solver *solver, int stages, const double *A, double tau);
+/* Integrates nsteps steps of the tableau set last from x0 (host, nrows_total; its fixed entries are replaced by g).  f: host load
+   vector (nrows_total); g: host values of the fixed dofs (in the order of `fixed`).  After every step k with k % save_every == 0,
+   and after the last, the state (g included) goes to the next row of saved (host, rows of nrows_total).  A stage solve that does
+   not converge within maxiter iterations (or breaks down) ends the run: info->converged = 0, info->steps the steps completed, and
+   the state after the last completed step is saved if it was not.  stage_iters (host, nsteps x stages, or NULL) receives the
+   iterations of each implicit stage.  timed != 0: events between the phases (info->spmv_ms etc.).  Deterministic: the same
+   inputs give bit-identical states. */
+int  igx_solver_dirk_run(igx_solver *solver, const double *f, const double *g, const double *x0, int64_t nsteps, int64_t save_every,
+                         double tol, int maxiter, int check_every, int timed, double *saved, int32_t *stage_iters,
+                         igx_dirk_info *info);
 
 /* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers.  The factors are dense, row-major, m[k] x n[k]
    (rectangular allowed).  x and y are tensors of shape (n_0, .., n_{dim-1}, batch) and (m_0, .., batch), addressed through an

@@ -82,6 +82,22 @@ class SolveInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+IGX_DIRK_MAX_STAGES = 6
+IGX_ROLE_MASS, IGX_ROLE_OPERATOR = 0, 1
+
+
+class DirkInfo(C.Structure):
+    _fields_ = [
+        ('steps', C.c_int64), ('converged', C.c_int32), ('nsaved', C.c_int32), ('iterations', C.c_int64),
+        ('max_stage_iterations', C.c_int32), ('reserved', C.c_int32),
+        ('axpby_ms', C.c_float), ('spmv_ms', C.c_float), ('combine_ms', C.c_float), ('solve_ms', C.c_float),
+        ('total_ms', C.c_float), ('reserved2', C.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
 class KronDesc(C.Structure):
     _fields_ = [
         ('dim', C.c_int32), ('m', C.c_int32 * 3), ('n', C.c_int32 * 3), ('d_B', C.c_void_p * 3),
@@ -168,6 +184,11 @@ SYMBOLS = [
     ('igx_solver_precond_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_spmv_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_solve', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(SolveInfo)]),
+    ('igx_solver_create_parabolic', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_take_values', C.c_int, [C.c_void_p, C.c_int]),
+    ('igx_solver_set_dirk', C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double]),
+    ('igx_solver_dirk_run', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
+                                      C.POINTER(C.c_int32), C.POINTER(DirkInfo)]),
     ('igx_kron_apply_d', C.c_int, [C.c_void_p, C.POINTER(KronDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
 ]
 

@@ -442,6 +442,56 @@ __global__ void k_pupdate(long long n, const double *z, double *p, const double 
 }
 
 // ---------------------------------------------------------------------------------------------
+// DIRK time stepping (igx_solver_create_parabolic)
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+constexpr int AXPBY_U = 4;                       // pairs of M and K values of each lane in flight
+constexpr int COMB_MAX = 8;                      // vectors of one k_dirk_rhs pass
+
+// C = alpha M + beta K over the 64-bit value range (24 bytes per value): 16-byte loads, non-temporal (M and K are not read again
+// by this pass), 16-byte stores; the odd last value by one lane
+__global__ void __launch_bounds__(BLOCK) k_vals_axpby(long long n, double alpha, const double *__restrict__ M, double beta,
+                                                      const double *__restrict__ K, double *__restrict__ C)
+{
+    const long long n2 = n / 2, stride = (long long)gridDim.x * BLOCK;
+    const dbl2 *M2 = reinterpret_cast<const dbl2 *>(M), *K2 = reinterpret_cast<const dbl2 *>(K);
+    dbl2 *C2 = reinterpret_cast<dbl2 *>(C);
+    const dbl2 zero = {0.0, 0.0};
+    for (long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x; i0 < n2; i0 += AXPBY_U * stride) {
+        dbl2 m[AXPBY_U], k[AXPBY_U];
+#pragma unroll
+        for (int u = 0; u < AXPBY_U; ++u) {
+            const bool in = i0 + u * stride < n2;
+            m[u] = in ? __builtin_nontemporal_load(M2 + i0 + u * stride) : zero;
+            k[u] = in ? __builtin_nontemporal_load(K2 + i0 + u * stride) : zero;
+        }
+#pragma unroll
+        for (int u = 0; u < AXPBY_U; ++u)
+            if (i0 + u * stride < n2) C2[i0 + u * stride] = alpha * m[u] + beta * k[u];
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) C[n - 1] = alpha * M[n - 1] + beta * K[n - 1];
+}
+
+// a linear combination of at most COMB_MAX vectors, coefficients by value
+struct Comb {
+    int nv;
+    double c[COMB_MAX];
+    const double *v[COMB_MAX];
+};
+
+// out = sum_k c[k] v[k], k = 0 .. nv-1 in this order (the stage right-hand side  M x + tau sum_j a_ij F_j + tau gamma f, and
+// y = x + ext(g)): one pass, (nv + 1) 8 bytes per entry
+__global__ void k_dirk_rhs(long long n, const Comb L, double *out)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < COMB_MAX; ++k)
+            if (k < L.nv) a += L.c[k] * L.v[k][i];
+        out[i] = a;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // BiCGStab (right-preconditioned, the "Templates" variant).  Its scalars live in a block of their own (BS_*)
 // that only k_fin_bicg writes.  BS_DONE freezes the solve: every update kernel returns at once when it is set, so iterations run
 // past the stop (check_every > 1) change neither x nor r.  BS_LAST marks the x / r update of this iteration as the final one
@@ -945,6 +995,19 @@ struct igx_solver {
     double *blk[9] = {};                      // block (p, q) at p * ncomp + q, taken from the patch (owned), or null
     FastDiag bkron[3] = {};                   // per component: the fast-diagonalization inverse on its free box (in d_bkron[c])
     double *d_bkron[3] = {};
+    // parabolic solver (igx_solver_create_parabolic): M and K taken from the patch (IGX_ROLE_*), C = M + tau gamma K formed by
+    // igx_solver_set_dirk; the SpMV, Jacobi and the solves act on C
+    bool parabolic = false;
+    double *pv[3] = {};                       // M | K | C, owned
+    long long nvals[2] = {};                  // values of M and K
+    bool c_formed = false;
+    int stages = 0;
+    double dirk_A[(IGX_DIRK_MAX_STAGES + 1) * IGX_DIRK_MAX_STAGES] = {};
+    double tau = 0.0, gamma = 0.0;
+    float axpby_ms = 0.0f;                    // device time of the last k_vals_axpby
+    double *d_dirk = nullptr;                 // xs | Mx | f | y | F_0 .. F_{stages-1}, n each (allocated by the first run)
+    hipEvent_t dev[6] = {};
+    bool have_dev = false;
 };
 
 namespace {
@@ -967,6 +1030,13 @@ int check_values(const igx_solver *s, const char *what)
         }
         return IGX_OK;
     }
+    if (s->parabolic) {                       // (its values are its own: they must be taken and C formed)
+        if (!s->c_formed) {
+            set_error("%s: no C = M + tau gamma K yet: take M and K (igx_solver_take_values), then igx_solver_set_dirk", what);
+            return IGX_ERR_ARG;
+        }
+        return IGX_OK;
+    }
     if (s->pt->values_kind != s->kind || !s->pt->d_data) {
         set_error("%s: the patch no longer holds the values of the solver's matrix (another kind was assembled since, or an "
                   "assembly failed): assemble it again", what);
@@ -974,6 +1044,9 @@ int check_values(const igx_solver *s, const char *what)
     }
     return IGX_OK;
 }
+
+// the values a scalar patch solver's SpMV and Jacobi read: the patch's, or a parabolic solver's own C
+const double *patch_values(const igx_solver *s) { return s->parabolic ? s->pv[2] : s->pt->d_data; }
 
 unsigned spmv_blocks(const igx_solver *s)
 {
@@ -996,8 +1069,18 @@ int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, 
         for (int k = 0; k < s->ncomp * s->ncomp; ++k) A.v[k] = s->blk[k];
         with_block_spmv_kernel(s->gw, s->ncomp, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, A, s->d_mask, x, b, sign, y, pd, part); });
     } else {
-        with_spmv_kernel(s->gw, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, s->pt->d_data, s->d_mask, x, b, sign, y, pd, part); });
+        const double *vals = patch_values(s);
+        with_spmv_kernel(s->gw, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, vals, s->d_mask, x, b, sign, y, pd, part); });
     }
+    IGX_HIP(hipGetLastError());
+    return IGX_OK;
+}
+
+// k_spmv over other values of the same layout (a parabolic solver's M or K): y = free ? (b ? b : 0) + sign V x : 0
+int spmv_values(hipStream_t st, const igx_solver *s, const double *vals, const double *x, const double *b, double sign, double *y)
+{
+    const unsigned nb = spmv_blocks(s);
+    with_spmv_kernel(s->gw, [&](auto k) { k<<<nb, BLOCK, 0, st>>>(s->g, vals, s->d_mask, x, b, sign, y, nullptr, nullptr); });
     IGX_HIP(hipGetLastError());
     return IGX_OK;
 }
@@ -1056,6 +1139,10 @@ void free_solver(igx_solver *s)
     (void)hipFree(s->d_bvec); (void)hipFree(s->d_bsc);
     for (double *v : s->blk) (void)hipFree(v);
     for (double *v : s->d_bkron) (void)hipFree(v);
+    for (double *v : s->pv) (void)hipFree(v);
+    (void)hipFree(s->d_dirk);
+    if (s->have_dev)
+        for (auto &e : s->dev) (void)hipEventDestroy(e);
     if (s->have_ev)
         for (auto &e : s->ev) (void)hipEventDestroy(e);
     if (s->have_bev)
@@ -1305,15 +1392,16 @@ int init_solver(igx_solver *s, const int64_t *fixed, int64_t nfixed, long long m
     return IGX_OK;
 }
 
-// a solver over the values of `kind` the patch holds (the kind itself checked by the caller); ncomp > 1: a block solver of ncomp
-// components, whose blocks are taken from the patch later (igx_solver_take_block)
-int create_patch_solver(igx_patch *pt, int kind, int ncomp, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what)
+// a solver over the values of `kind` the patch holds (the kind itself checked by the caller; values_now: they must be there now);
+// ncomp > 1: a block solver of ncomp components, whose blocks are taken from the patch later (igx_solver_take_block)
+int create_patch_solver(igx_patch *pt, int kind, int ncomp, bool values_now, const int64_t *fixed, int64_t nfixed, igx_solver **out,
+                        const char *what)
 {
     if (pt->boxed || pt->row_lo != 0 || pt->row_hi != pt->nrows_total) {
         set_error("%s: whole patches only (no row slab, no span box)", what);
         return IGX_ERR_UNSUPPORTED;
     }
-    if (ncomp == 1 && (pt->values_kind != kind || !pt->d_data)) {
+    if (values_now && (pt->values_kind != kind || !pt->d_data)) {
         set_error("%s: assemble the patch with this kind first (igx_assemble, data_out may be NULL)", what);
         return IGX_ERR_ARG;
     }
@@ -1388,7 +1476,7 @@ int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfi
         set_error("igx_solver_create: CG needs a symmetric positive definite matrix (IGX_MASS or IGX_STIFFNESS), kind %d", kind);
         return IGX_ERR_UNSUPPORTED;
     }
-    return create_patch_solver(pt, kind, 1, fixed, nfixed, out, "igx_solver_create");
+    return create_patch_solver(pt, kind, 1, true, fixed, nfixed, out, "igx_solver_create");
 }
 
 int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
@@ -1399,7 +1487,7 @@ int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int
         return IGX_ERR_ARG;
     }
     igx_solver *s = nullptr;
-    if (int rc = create_patch_solver(pt, kind, 1, fixed, nfixed, &s, "igx_solver_create_general")) return rc;
+    if (int rc = create_patch_solver(pt, kind, 1, true, fixed, nfixed, &s, "igx_solver_create_general")) return rc;
     if (int rc = init_bicgstab(s, "igx_solver_create_general")) { free_solver(s); return rc; }
     s->method = IGX_METHOD_BICGSTAB;
     *out = s;
@@ -1414,7 +1502,11 @@ int igx_solver_set_method(igx_solver *s, int method)
             set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; the block solver was made as non-symmetric");
             return IGX_ERR_UNSUPPORTED;
         }
-        if (s->ncomp == 1 && !s->mp && !spd_kind(s->kind)) {
+        if (s->parabolic && !s->symmetric) {
+            set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; the parabolic solver was made as non-symmetric");
+            return IGX_ERR_UNSUPPORTED;
+        }
+        if (s->ncomp == 1 && !s->mp && !s->parabolic && !spd_kind(s->kind)) {
             set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; kind %d is not known to be one", s->kind);
             return IGX_ERR_UNSUPPORTED;
         }
@@ -1447,7 +1539,7 @@ int igx_solver_create_block(igx_patch *pt, int ncomp, int symmetric, const int64
     if (!create_args_ok(pt, fixed, nfixed, out, what)) return IGX_ERR_ARG;
     if (ncomp != 2 && ncomp != 3) { set_error("%s: ncomp must be 2 or 3, not %d", what, ncomp); return IGX_ERR_ARG; }
     igx_solver *s = nullptr;
-    if (int rc = create_patch_solver(pt, IGX_FORM, ncomp, fixed, nfixed, &s, what)) return rc;
+    if (int rc = create_patch_solver(pt, IGX_FORM, ncomp, false, fixed, nfixed, &s, what)) return rc;
     s->symmetric = symmetric != 0;
     if (!s->symmetric) {
         if (int rc = init_bicgstab(s, what)) { free_solver(s); return rc; }
@@ -1537,7 +1629,7 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
             const long long N = s->g.nrows;                   // component c: the diagonal of block (c, c) at offset c N
             for (int c = 0; c < s->ncomp; ++c)
                 k_diag<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(s->g, s->blk[c * s->ncomp + c], s->d_mask + c * N, s->dinv + c * N);
-        } else k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pt->d_data, s->d_mask, s->dinv);
+        } else k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, patch_values(s), s->d_mask, s->dinv);
         IGX_HIP(hipGetLastError());
         IGX_HIP(hipStreamSynchronize(st));
         s->precond = precond;
@@ -1705,6 +1797,36 @@ int finish_solve(hipStream_t st, igx_solver *s, const double *gvals, double *u, 
     return IGX_OK;
 }
 
+// The device entry of the solves: R A R^T x = R (b - A w) with b in s->b and w = ext(g) in s->w (both on the device, full
+// length).  With x0_in_x the initial guess is in s->x already, zero on the fixed dofs; else x starts at 0.  r = R (b - A w), its
+// norm the reference of the relative residual; r -= A x0; then CG or BiCGStab (s->method).  The free part of the solution stays
+// in s->x (zero on the fixed dofs).
+int solve_lifted(hipStream_t st, igx_solver *s, bool x0_in_x, double tol, int maxiter, int check_every, int timed, igx_solve_info &inf)
+{
+    const long long n = s->n;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    if (!x0_in_x) IGX_HIP(hipMemsetAsync(s->x, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->p, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->q, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->z, 0, nbytes, st));
+    IGX_HIP(hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st));
+    const unsigned nbv = vec_blocks(n);
+    double *pA = s->d_part;
+    // r = R (b - A ext(g)); its norm is the reference of the relative residual
+    if (int rc = spmv(st, s, s->w, s->b, -1.0, s->r, nullptr, nullptr)) return rc;
+    k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
+    k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbv, s->d_sc, FIN_INIT);
+    double h_rr = 0.0;
+    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    const double bnorm = std::sqrt(h_rr);
+    if (x0_in_x) {
+        if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
+    }
+    return s->method == IGX_METHOD_BICGSTAB ? solve_bicgstab(st, s, bnorm, tol, maxiter, check_every, timed, inf)
+                                            : solve_cg(st, s, bnorm, tol, maxiter, check_every, timed, inf);
+}
+
 } // namespace
 
 extern "C" {
@@ -1729,29 +1851,13 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
     if (b) IGX_HIP(hipMemcpyAsync(s->b, b, nbytes, hipMemcpyHostToDevice, st));
     else IGX_HIP(hipMemcpyAsync(s->b, s->mp->d_vec, nbytes, hipMemcpyDeviceToDevice, st));      // the multipatch's summed vector
     IGX_HIP(hipMemcpyAsync(s->w, w.data(), nbytes, hipMemcpyHostToDevice, st));
-    IGX_HIP(hipMemsetAsync(s->x, 0, nbytes, st));
-    IGX_HIP(hipMemsetAsync(s->p, 0, nbytes, st));
-    IGX_HIP(hipMemsetAsync(s->q, 0, nbytes, st));
-    IGX_HIP(hipMemsetAsync(s->z, 0, nbytes, st));
-    IGX_HIP(hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st));
-    const unsigned nbv = vec_blocks(n);
-    double *pA = s->d_part;
-    // r = R (b - A ext(g)); its norm is the reference of the relative residual
-    if (int rc = spmv(st, s, s->w, s->b, -1.0, s->r, nullptr, nullptr)) return rc;
-    k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
-    k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbv, s->d_sc, FIN_INIT);
-    double h_rr = 0.0;
-    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
-    IGX_HIP(hipStreamSynchronize(st));
-    const double bnorm = std::sqrt(h_rr);
     if (x0) {
-        for (long long i = 0; i < n; ++i) w[i] = s->h_free[i] ? x0[i] : 0.0;
-        IGX_HIP(hipMemcpyAsync(s->x, w.data(), nbytes, hipMemcpyHostToDevice, st));
-        if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
+        std::vector<double> xf((size_t)n);
+        for (long long i = 0; i < n; ++i) xf[i] = s->h_free[i] ? x0[i] : 0.0;
+        IGX_HIP(hipMemcpyAsync(s->x, xf.data(), nbytes, hipMemcpyHostToDevice, st));
+        IGX_HIP(hipStreamSynchronize(st));                   // (xf leaves scope)
     }
-    const int rc = s->method == IGX_METHOD_BICGSTAB ? solve_bicgstab(st, s, bnorm, tol, maxiter, check_every, timed, inf)
-                                                    : solve_cg(st, s, bnorm, tol, maxiter, check_every, timed, inf);
-    if (rc) return rc;
+    if (int rc = solve_lifted(st, s, x0 != nullptr, tol, maxiter, check_every, timed, inf)) return rc;
     return finish_solve(st, s, gvals, u, info, inf);
 }
 
@@ -1790,6 +1896,263 @@ int igx_kron_apply_d(igx_ctx *ctx, const igx_kron_desc *d, const double *d_x, do
     (void)hipFree(own);
     if (rc) return rc;
     if (e != hipSuccess) { set_error("igx_kron_apply_d: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
+    return IGX_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Parabolic problems: DIRK time stepping of  M u' = f - K u  on the free dofs, u = g on the fixed ones (DESIGN.md section 16;
+// pyiga/solvers.py:366-473).  Every implicit stage solves  R C R^T y = R (b_i - C ext(g)),  C = M + tau gamma K,  with
+// b_i = M x + tau sum_{j<i} a_ij F_j + tau gamma f  and  F_j = f - K y_j.
+
+namespace {
+
+// a DIRK tableau in the reference's layout ((stages + 1) x stages, b the last row) that every implicit stage of every step solves
+// with one matrix: lower triangular, every nonzero diagonal entry one gamma > 0, only row 0 may have a zero diagonal, stiffly
+// accurate (b is the last stage row, exactly).  gamma out; false with igx_last_error
+bool dirk_ok(int st, const double *A, double tau, double &gamma, const char *what)
+{
+    if (st < 1 || st > IGX_DIRK_MAX_STAGES) { set_error("%s: %d stages (1 to %d)", what, st, IGX_DIRK_MAX_STAGES); return false; }
+    if (!(tau > 0.0) || !std::isfinite(tau)) { set_error("%s: tau must be positive and finite", what); return false; }
+    gamma = 0.0;
+    for (int i = 0; i <= st; ++i)
+        for (int j = 0; j < st; ++j) {
+            const double a = A[i * st + j];
+            if (!std::isfinite(a)) { set_error("%s: A[%d][%d] is not finite", what, i, j); return false; }
+            if (i < st && j > i && a != 0.0) { set_error("%s: A is not lower triangular (A[%d][%d] = %g)", what, i, j, a); return false; }
+        }
+    for (int i = 0; i < st; ++i) {
+        const double a = A[i * st + i];
+        if (a == 0.0) {
+            if (i > 0) { set_error("%s: zero diagonal in stage %d (only the first stage may be explicit)", what, i); return false; }
+            continue;
+        }
+        if (!(a > 0.0)) { set_error("%s: diagonal A[%d][%d] = %g is not positive", what, i, i, a); return false; }
+        if (gamma != 0.0 && a != gamma) { set_error("%s: two diagonal values (%.17g and %.17g): C would change per stage", what, gamma, a); return false; }
+        gamma = a;
+    }
+    if (gamma == 0.0) { set_error("%s: no implicit stage", what); return false; }
+    for (int j = 0; j < st; ++j)
+        if (A[st * st + j] != A[(st - 1) * st + j]) {
+            set_error("%s: the scheme is not stiffly accurate (b differs from the last stage row at %d)", what, j);
+            return false;
+        }
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int igx_solver_create_parabolic(igx_patch *pt, int kind_K, int symmetric, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    const char *what = "igx_solver_create_parabolic";
+    if (!create_args_ok(pt, fixed, nfixed, out, what)) return IGX_ERR_ARG;
+    if (kind_K != IGX_MASS && kind_K != IGX_STIFFNESS && kind_K != IGX_CONVDIFF && kind_K != IGX_FORM) {
+        set_error("%s: unknown kind %d", what, kind_K);
+        return IGX_ERR_ARG;
+    }
+    igx_solver *s = nullptr;
+    if (int rc = create_patch_solver(pt, kind_K, 1, false, fixed, nfixed, &s, what)) return rc;
+    s->parabolic = true;
+    s->symmetric = symmetric != 0;
+    if (!s->symmetric) {
+        if (int rc = init_bicgstab(s, what)) { free_solver(s); return rc; }
+        s->method = IGX_METHOD_BICGSTAB;
+    }
+    *out = s;
+    return IGX_OK;
+}
+
+int igx_solver_take_values(igx_solver *s, int role)
+{
+    const char *what = "igx_solver_take_values";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
+    if (role != IGX_ROLE_MASS && role != IGX_ROLE_OPERATOR) { set_error("%s: unknown role %d", what, role); return IGX_ERR_ARG; }
+    if (s->pv[role]) { set_error("%s: role %d was taken already", what, role); return IGX_ERR_ARG; }
+    igx_patch *pt = s->pt;
+    const int kind = role == IGX_ROLE_MASS ? IGX_MASS : s->kind;
+    if (pt->values_kind != kind || !pt->d_data) {
+        set_error("%s: the patch holds no values of kind %d: assemble them first (igx_assemble, data_out may be NULL)", what, kind);
+        return IGX_ERR_ARG;
+    }
+    const int other = 1 - role;
+    if (s->pv[other] && s->nvals[other] != pt->nnz) {
+        set_error("%s: value buffers of unequal length (%lld and %lld)", what, (long long)pt->nnz, s->nvals[other]);
+        return IGX_ERR_ARG;
+    }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    IGX_HIP(hipStreamSynchronize(pt->ctx->stream));
+    s->pv[role] = pt->d_data;                       // the buffer changes hands: the patch's next assembly allocates anew
+    s->nvals[role] = pt->nnz;
+    pt->d_data = nullptr;
+    pt->values_kind = -1;
+    return IGX_OK;
+}
+
+int igx_solver_set_dirk(igx_solver *s, int stages, const double *A, double tau)
+{
+    const char *what = "igx_solver_set_dirk";
+    if (!s || !A) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
+    if (!s->pv[IGX_ROLE_MASS] || !s->pv[IGX_ROLE_OPERATOR]) { set_error("%s: take M and K first (igx_solver_take_values)", what); return IGX_ERR_ARG; }
+    double gamma = 0.0;
+    if (!dirk_ok(stages, A, tau, gamma, what)) return IGX_ERR_ARG;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const long long nv = s->nvals[0];
+    if (!s->pv[2]) {
+        if (hipMalloc((void **)&s->pv[2], (size_t)nv * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: out of device memory (%.3f GB for C)", what, 8.0 * nv / 1e9);
+            return IGX_ERR_NOMEM;
+        }
+    }
+    if (!s->have_dev) {
+        for (auto &e : s->dev)
+            if (hipEventCreate(&e) != hipSuccess) { set_error("%s: hipEventCreate failed", what); return IGX_ERR_HIP; }
+        s->have_dev = true;
+    }
+    s->c_formed = false;
+    s->precond = IGX_PRECOND_NONE;                   // (Jacobi's diagonal and the Kronecker factors depend on C: set them again)
+    const long long blocks = std::min<long long>((nv / 2 + BLOCK - 1) / BLOCK, 16LL * std::max(1, s->ctx->ncu));
+    IGX_HIP(hipEventRecord(s->dev[0], st));
+    k_vals_axpby<<<(unsigned)std::max<long long>(1, blocks), BLOCK, 0, st>>>(nv, 1.0, s->pv[0], tau * gamma, s->pv[1], s->pv[2]);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipEventRecord(s->dev[1], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&s->axpby_ms, s->dev[0], s->dev[1]);
+    s->stages = stages;
+    std::copy(A, A + (stages + 1) * stages, s->dirk_A);
+    s->tau = tau;
+    s->gamma = gamma;
+    s->c_formed = true;
+    return IGX_OK;
+}
+
+int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, const double *x0, int64_t nsteps, int64_t save_every,
+                        double tol, int maxiter, int check_every, int timed, double *saved, int32_t *stage_iters, igx_dirk_info *info)
+{
+    const char *what = "igx_solver_dirk_run";
+    if (!s || !f || (!gvals && !s->fixed.empty()) || !x0 || !saved) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
+    if (nsteps < 1 || save_every < 1) { set_error("%s: nsteps and save_every must be >= 1", what); return IGX_ERR_ARG; }
+    if (!(tol >= 0.0) || maxiter < 0) { set_error("%s: tol must be >= 0 and maxiter >= 0", what); return IGX_ERR_ARG; }
+    if (int rc = check_values(s, what)) return rc;
+    if (check_every < 1) check_every = 1;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const long long n = s->n;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    if (!s->d_dirk) {
+        if (hipMalloc((void **)&s->d_dirk, (4 + IGX_DIRK_MAX_STAGES) * nbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: out of device memory (%.3f GB)", what, (4.0 + IGX_DIRK_MAX_STAGES) * nbytes / 1e9);
+            return IGX_ERR_NOMEM;
+        }
+    }
+    double *xs = s->d_dirk, *mx = xs + n, *fv = xs + 2 * n, *y = xs + 3 * n, *F[IGX_DIRK_MAX_STAGES];
+    for (int j = 0; j < IGX_DIRK_MAX_STAGES; ++j) F[j] = xs + (4 + j) * n;
+    const int ns = s->stages;
+    const double *A = s->dirk_A, tau = s->tau, gamma = s->gamma;
+    const bool explicit_first = A[0] == 0.0;
+    igx_dirk_info inf{};
+    inf.axpby_ms = s->axpby_ms;
+    s->breakdown = 0;
+    // f, ext(g) (s->w) and x0 with g on the fixed dofs: the only uploads
+    std::vector<double> h((size_t)n);
+    for (long long i = 0; i < n; ++i) h[i] = s->h_free[i] ? x0[i] : 0.0;
+    for (size_t k = 0; k < s->fixed.size(); ++k) h[s->fixed[k]] = gvals[k];
+    std::vector<double> w((size_t)n, 0.0);
+    for (size_t k = 0; k < s->fixed.size(); ++k) w[s->fixed[k]] = gvals[k];
+    hipEvent_t *E = s->dev;
+    IGX_HIP(hipEventRecord(E[4], st));
+    IGX_HIP(hipMemcpyAsync(xs, h.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(s->w, w.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(fv, f, nbytes, hipMemcpyHostToDevice, st));
+    const unsigned nbv = vec_blocks(n), nbm = (unsigned)((n + 255) / 256);
+    // timed: the device time since the last mark goes to `bucket` (E[0] / E[1] alternate)
+    int mark = 0;
+    if (timed) IGX_HIP(hipEventRecord(E[0], st));
+    auto lap = [&](float &bucket) -> int {
+        if (!timed) return IGX_OK;
+        IGX_HIP(hipEventRecord(E[1 - mark], st));
+        IGX_HIP(hipEventSynchronize(E[1 - mark]));
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, E[mark], E[1 - mark]);
+        bucket += ms;
+        mark = 1 - mark;
+        return IGX_OK;
+    };
+    auto save = [&]() -> int {                                      // the state xs to the next slot of `saved`
+        IGX_HIP(hipMemcpyAsync(saved + (size_t)inf.nsaved * n, xs, nbytes, hipMemcpyDeviceToHost, st));
+        IGX_HIP(hipStreamSynchronize(st));
+        ++inf.nsaved;
+        return IGX_OK;
+    };
+    if (explicit_first) {                                            // F_1 of the first step: f - K x0
+        if (int rc = spmv_values(st, s, s->pv[1], xs, fv, -1.0, F[0])) return rc;
+        if (int rc = lap(inf.spmv_ms)) return rc;
+    }
+    bool ok = true;
+    long long last_saved = 0;
+    for (long long k = 1; k <= nsteps && ok; ++k) {
+        if (int rc = spmv_values(st, s, s->pv[0], xs, nullptr, 1.0, mx)) return rc;          // M x
+        if (int rc = lap(inf.spmv_ms)) return rc;
+        const double *yprev = xs;
+        for (int i = 0; i < ns && ok; ++i) {
+            const double aii = A[i * ns + i];
+            if (aii == 0.0) continue;                                // (i = 0: y_1 = x, F_1 in F[0])
+            Comb L{};
+            L.c[L.nv] = 1.0; L.v[L.nv++] = mx;
+            for (int j = 0; j < i; ++j)
+                if (A[i * ns + j] != 0.0) { L.c[L.nv] = tau * A[i * ns + j]; L.v[L.nv++] = F[j]; }
+            L.c[L.nv] = tau * gamma; L.v[L.nv++] = fv;
+            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
+            k_mask_copy<<<nbm, 256, 0, st>>>(n, s->d_mask, yprev, s->x);    // the initial guess y_{i-1}
+            IGX_HIP(hipGetLastError());
+            if (int rc = lap(inf.combine_ms)) return rc;
+            igx_solve_info si{};
+            if (int rc = solve_lifted(st, s, true, tol, maxiter, check_every, 0, si)) return rc;
+            if (int rc = lap(inf.solve_ms)) return rc;
+            if (stage_iters) stage_iters[(k - 1) * ns + i] = si.iterations;
+            inf.iterations += si.iterations;
+            inf.max_stage_iterations = std::max(inf.max_stage_iterations, si.iterations);
+            if (!si.converged) { ok = false; break; }
+            Comb Y{};
+            Y.nv = 2; Y.c[0] = 1.0; Y.v[0] = s->x; Y.c[1] = 1.0; Y.v[1] = s->w;        // y_i = x + ext(g)
+            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, Y, y);
+            IGX_HIP(hipGetLastError());
+            if (int rc = lap(inf.combine_ms)) return rc;
+            yprev = y;
+            if (i < ns - 1 || explicit_first) {                      // F_i = f - K y_i (the last one only as F_1 of the next step)
+                if (int rc = spmv_values(st, s, s->pv[1], y, fv, -1.0, F[i])) return rc;
+                if (int rc = lap(inf.spmv_ms)) return rc;
+            }
+        }
+        if (!ok) break;
+        std::swap(xs, y);                                            // x_new = y_s
+        if (explicit_first) std::swap(F[0], F[ns - 1]);
+        inf.steps = k;
+        if (k % save_every == 0 || k == nsteps) {
+            if (int rc = save()) return rc;
+            last_saved = k;
+        }
+    }
+    if (!ok && inf.steps > 0 && last_saved != inf.steps) {          // the state after the last completed step
+        if (int rc = save()) return rc;
+    }
+    IGX_HIP(hipEventRecord(E[5], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("%s: kernel failure: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
+    }
+    (void)hipEventElapsedTime(&inf.total_ms, E[4], E[5]);
+    inf.converged = ok ? 1 : 0;
+    if (info) *info = inf;
     return IGX_OK;
 }
 

@@ -22,9 +22,16 @@ lets ``PatchSystem`` and ``MultipatchSystem`` solve by BiCGStab; ``MultipatchSys
 ``VectorFormSystem(problem, kvs, rhs, bcs, bfuns=[('u', nc), ('v', nc)], geo=geo)``: the same for vector-valued forms (linear
 elasticity, grad-div, ...): the nc x nc scalar blocks are assembled on the device and stay there; a block SpMV and a
 block-diagonal fast-diagonalization preconditioner serve CG or BiCGStab.
+
+``ParabolicSystem(kvs, geo, rhs, bcs, problem=None)``: the heat equation ``M u' = f - K u`` (or any device-valued form as K) of
+one patch, integrated on the device by a DIRK scheme with constant steps (``integrate``; the reference's ``crank_nicolson``,
+``sdirk3``, ..., pyiga/solvers.py:366-473).  Every stage solves with ``C = M + tau gamma K``; M, K and C stay on the device, and
+only the saved states come down.  ``dirk_tableau(name)`` gives the tableaux of the named schemes.
 """
 import ctypes as C
+import math
 import re
+import warnings
 
 import numpy as np
 import scipy.linalg
@@ -693,3 +700,298 @@ class MultipatchSystem(_DeviceSystem):
         notebook domain (p = 3, n = 256) it takes 2.7x fewer iterations and 4x the time of Jacobi.  It pays in 3D and on
         ill-conditioned systems."""
         return self._solve(b, tol, maxiter, precond, x0, check_every, timed)
+
+
+################################################################################
+# Parabolic problems of one patch on the device: DIRK time stepping
+################################################################################
+
+# Alexander (1977), three-stage SDIRK of order 3: gamma is the root in (1/6, 1/2) of 6 g^3 - 18 g^2 + 9 g - 1 = 0 (L-stability)
+_SDIRK3_GAMMA = 0.43586652150845899942
+
+
+def _tableau(name):
+    if name == 'implicit_euler':
+        return [[1.0],
+                [1.0]]
+    if name == 'crank_nicolson':
+        return [[0.0, 0.0],
+                [0.5, 0.5],
+                [0.5, 0.5]]
+    if name == 'sdirk3':
+        g = _SDIRK3_GAMMA
+        b2 = (6 * g * g - 20 * g + 5) / 4
+        b1 = 1 - b2 - g
+        return [[g, 0.0, 0.0],
+                [(1 - g) / 2, g, 0.0],
+                [b1, b2, g],
+                [b1, b2, g]]
+    if name == 'sdirk21':
+        # Ellsiepen: two stages, order 2, alpha = 1 - 1/sqrt(2)
+        a = 1 - math.sqrt(0.5)
+        return [[a, 0.0],
+                [1 - a, a],
+                [1 - a, a]]
+    if name == 'dirk34':
+        # four stages, explicit first stage, gamma = 0.1558983899988677 (the coefficients the reference runs; see DESIGN.md
+        # section 16: their weights sum to 1.0211)
+        g = 0.1558983899988677
+        a32, a42, a43 = 1.072486270734370, 0.7685298292769537, 0.09666483609791597
+        return [[0.0, 0.0, 0.0, 0.0],
+                [g, g, 0.0, 0.0],
+                [1 - a32 - g, a32, g, 0.0],
+                [0.0, a42, a43, g],
+                [0.0, a42, a43, g]]
+    if name == 'esdirk23':
+        # Jorgensen, Kristensen, Thomsen (2018): three stages, order 2, gamma = 1 - 1/sqrt(2)
+        g = 1 - math.sqrt(0.5)
+        return [[0.0, 0.0, 0.0],
+                [g, g, 0.0],
+                [(1 - g) / 2, (1 - g) / 2, g],
+                [(1 - g) / 2, (1 - g) / 2, g]]
+    if name == 'esdirk34':
+        # Jorgensen, Kristensen, Thomsen (2018): four stages, order 3, gamma the root of sdirk3
+        g = _SDIRK3_GAMMA
+        b = [0.10239940061991099768, -0.3768784522555561061, 0.83861253012718610911, g]
+        return [[0.0, 0.0, 0.0, 0.0],
+                [g, g, 0.0, 0.0],
+                [0.14073777472470619619, -0.1083655513813208000, g, 0.0],
+                b,
+                b]
+    return None
+
+
+DIRK_SCHEMES = ('implicit_euler', 'crank_nicolson', 'sdirk3', 'sdirk21', 'dirk34', 'esdirk23', 'esdirk34')
+
+
+def dirk_tableau(name):
+    """The tableau ``A`` of the named DIRK scheme in the reference's layout: shape ``(s + 1, s)``, the last row ``b`` (main rules:
+    no embedded ``b_hat`` row).  Schemes: ``DIRK_SCHEMES``."""
+    t = _tableau(name) if isinstance(name, str) else None
+    if t is None:
+        raise ValueError('unknown DIRK scheme %r: one of %s' % (name, ', '.join(DIRK_SCHEMES)))
+    return np.array(t, dtype=np.float64)
+
+
+def check_tableau(A):
+    """``(A, gamma)`` for a tableau every implicit stage of which solves with one matrix ``M + tau gamma K``: shape ``(s + 1, s)``,
+    ``1 <= s <= 6``, lower triangular, every nonzero diagonal entry one ``gamma > 0``, a zero diagonal only in row 0 (an explicit
+    first stage), stiffly accurate (``b`` equals the last stage row).  ValueError otherwise (what ``igx_solver_set_dirk``
+    refuses)."""
+    A = np.array(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] + 1 or not 1 <= A.shape[1] <= _lib.IGX_DIRK_MAX_STAGES:
+        raise ValueError('a DIRK tableau has shape (s + 1, s) with 1 <= s <= %d, not %s' % (_lib.IGX_DIRK_MAX_STAGES, A.shape))
+    s = A.shape[1]
+    if not np.all(np.isfinite(A)):
+        raise ValueError('the DIRK tableau has non-finite entries')
+    if np.any(np.triu(A[:s], 1) != 0):
+        raise ValueError('the DIRK tableau is not lower triangular')
+    diag = np.diag(A[:s])
+    if np.any(diag[1:] == 0):
+        raise ValueError('the DIRK tableau has a zero diagonal past the first stage (only the first stage may be explicit)')
+    nz = diag[diag != 0]
+    if nz.size == 0 or np.any(nz <= 0):
+        raise ValueError('the diagonal of the DIRK tableau must be positive (gamma > 0)')
+    if np.any(nz != nz[0]):
+        raise ValueError('the DIRK tableau has two diagonal values (%r): every stage must solve with one matrix' % (sorted(set(nz)),))
+    if np.any(A[s] != A[s - 1]):
+        raise ValueError('the DIRK tableau is not stiffly accurate (b differs from the last stage row); such schemes need a mass '
+                         'solve per step and are not supported')
+    return A, float(nz[0])
+
+
+def _scheme(scheme):
+    """(name or None, A, gamma) of a scheme name or tableau (ValueError as check_tableau)."""
+    if isinstance(scheme, str):
+        A, gamma = check_tableau(dirk_tableau(scheme))
+        return scheme, A, gamma
+    A, gamma = check_tableau(scheme)
+    return None, A, gamma
+
+
+def _form_kind(problem):
+    """The device kind of `problem` as far as it is known before any device work (None: the built-in stiffness form)."""
+    from . import assemble
+    if problem is None:
+        return 'stiffness'
+    if isinstance(problem, str):
+        return assemble._KNOWN_FORMS.get(assemble._normalise_form(problem)) or 'form'
+    cls = problem if isinstance(problem, type) else type(problem)
+    return getattr(cls, '_kind', None)
+
+
+class ParabolicSystem(_DeviceSystem):
+    """The parabolic problem ``M u' = f - K u`` on the free dofs, ``u = g`` on the dofs of `bcs`, ``u(t0) = u0``, of one patch,
+    integrated on the device by a DIRK scheme with constant steps (the reference's ``crank_nicolson``, ``sdirk3``, ``esdirk34``,
+    ... on ``RestrictedLinearSystem`` matrices, pyiga/solvers.py:366-473).
+
+    M is the mass matrix of the patch; K the stiffness matrix (`problem` None: the heat equation) or the matrix of any form that
+    ``FormSystem`` accepts (`problem`, with `args` / `kwargs` its inputs); f and g do not depend on time.  Both matrices are
+    assembled on the device and handed to the solver (``igx_solver_take_values``); ``C = M + tau gamma K`` is formed there.
+    `rhs`: the load vector, a scalar, a function of the physical coordinates (``inner_products``) or a linear form string.
+    `bcs`: ``(indices, values)`` as ``compute_dirichlet_bcs`` gives them, or None (pure Neumann).  `method`: 'auto' is CG for the
+    built-in stiffness (and mass) form, else BiCGStab; 'cg' on any other form raises ValueError before any assembly.
+
+    ``integrate(...)`` returns ``(times, solutions)``; ``spmv(x)`` is ``R C R^T x`` and ``apply_precond(r)`` the preconditioner
+    of C, for the scheme and step of ``set_scheme`` (or the last ``integrate``).
+    """
+
+    def __init__(self, kvs, geo, rhs, bcs=None, problem=None, args=None, method='auto', device=None, **kwargs):
+        from . import assemble
+        if method != 'auto':
+            _check_method(method)
+        args = dict(args or {})
+        args.update(kwargs)
+        if geo is not None:
+            args.setdefault('geo', geo)
+        self.kvs = tuple(kvs)
+        self.geo = geo
+        if problem is not None:
+            _check_device_form(problem, self.kvs, args)
+        kind = _form_kind(problem)
+        self.symmetric = kind in ('mass', 'stiffness')
+        if method == 'auto':
+            method = 'cg' if self.symmetric else 'bicgstab'
+        elif method == 'cg' and not self.symmetric:
+            raise ValueError("ParabolicSystem: CG needs M + tau gamma K symmetric positive definite; %r is not known to be "
+                             "symmetric: method='bicgstab'" % (problem,))
+        self.ndofs = tuple(kv.numdofs for kv in self.kvs)
+        self.n = int(np.prod(self.ndofs))
+        if problem is None:
+            self.patch = assemblers.DevicePatch(self.kvs, geo, device=device)
+            self._own_patch = True
+        else:
+            self.assembler = assemble.instantiate_assembler(problem, self.kvs, args)
+            self._own_patch = self.assembler is not problem
+            self.patch = self.assembler.patch
+            kind = self.assembler._kind
+        self.kind = kind
+        if isinstance(rhs, str):
+            rhs = assemble.assemble(rhs, self.kvs, args=args)
+        elif callable(rhs):
+            rhs = assemble.inner_products(self.kvs, rhs, f_physical=True, geo=geo)
+        elif np.ndim(rhs) == 0:
+            rhs = np.full(self.n, float(rhs))
+        self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
+        if self.b.size != self.n:
+            raise ValueError('right-hand side has %d entries, the space %d' % (self.b.size, self.n))
+        self._ctx = self.patch.ctx
+        self._attach('igx_solver_create_parabolic', (self.patch.handle, _lib.KINDS[self.kind], 1 if self.symmetric else 0), bcs,
+                     method, 'cg' if self.symmetric else 'bicgstab')
+        self.box = dirichlet_box(self.ndofs, self.bc_indices)
+        lib = _lib.load()
+        self.patch.assemble(self.kind, to_host=False)            # the values stay on the device and change hands
+        _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_OPERATOR), 'igx_solver_take_values')
+        self.patch.assemble('mass', to_host=False)
+        _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_MASS), 'igx_solver_take_values')
+        self._step = None                                        # (tau, tableau) of the C on the device
+        self._eig = None
+
+    def _drop_owner(self):
+        if getattr(self, 'patch', None) is not None and self._own_patch:
+            self.patch.close()
+        self.patch = None
+
+    @property
+    def default_precond(self):
+        return 'kron' if self.box is not None else 'jacobi'
+
+    def set_scheme(self, scheme, tau):
+        """Validates `scheme` (a name of ``DIRK_SCHEMES`` or a tableau) and `tau`, and forms ``C = M + tau gamma K`` on the device
+        (once per step and tableau).  Returns the tableau."""
+        _, A, gamma = _scheme(scheme)
+        tau = float(tau)
+        if not (tau > 0 and math.isfinite(tau)):
+            raise ValueError('tau must be positive and finite, not %r' % (tau,))
+        key = (tau, A.tobytes())
+        if key != self._step:
+            _lib.check(_lib.load().igx_solver_set_dirk(self._live(), A.shape[1], _lib.dptr(A), tau), 'igx_solver_set_dirk')
+            self._step = key
+            self._precond = None                                 # (the device reset it: Jacobi and Kronecker depend on C)
+            self.tau, self.gamma = tau, gamma
+        return A
+
+    def kron_factors(self):
+        """Per axis ``U_k`` and ``lam'_k = tau gamma lam_k + 1/d`` from ``eigh(K_k, M_k)`` on the free box: with
+        ``IGX_KRON_SUM`` the fast-diagonalization inverse of the parametric ``M + tau gamma K`` (exact on the identity map of the
+        unit square or cube; symmetric positive definite without any Dirichlet dof)."""
+        if self.box is None:
+            raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch (or none)")
+        if self._step is None:
+            raise ValueError('no step yet: set_scheme(scheme, tau) or integrate(...) first')
+        if self._eig is None:
+            self._eig = fastdiag_factors(self.kvs, self.box[0], self.box[1], True)[:2]
+        U, lam = self._eig
+        d = len(self.kvs)
+        return U, [self.tau * self.gamma * l + 1.0 / d for l in lam]
+
+    def _set_factors(self, h):
+        U, lam = self.kron_factors()
+        lo = (C.c_int32 * 3)(*self.box[0])
+        hi = (C.c_int32 * 3)(*self.box[1])
+        Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
+        Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+        _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, _lib.IGX_KRON_SUM),
+                   'igx_solver_set_precond')
+
+    def integrate(self, u0, tau, t_end, scheme='sdirk3', t0=0.0, tol=1e-10, maxiter=1000, precond='auto', save_every=1,
+                  check_every=1, timed=False):
+        """``ceil((t_end - t0) / tau)`` steps of `scheme` (a name of ``DIRK_SCHEMES`` or a tableau) from `u0` (a vector, or a
+        function of the physical coordinates: its L2 projection; its fixed entries are replaced by g).  Every stage solve runs
+        to ``||r|| <= tol ||R (b_i - C ext(g))||`` with `precond` ('auto': 'kron' when the Dirichlet dofs are whole sides or
+        absent, else 'jacobi'; 'kron', 'jacobi' or None).
+
+        Returns ``(times, solutions)`` as the reference's constant-step methods: ``times[k] = t0 + k tau`` of the states kept
+        (every `save_every`-th step and always the last; the last time may pass `t_end`), ``solutions`` the full vectors
+        (Dirichlet values included), ``solutions[0] = u0``.  A stage solve that does not converge within `maxiter` iterations
+        ends the integration: the states up to the last completed step are returned (a RuntimeWarning says so, and
+        ``info['converged']`` is False).  ``info``: the fields of ``igx_dirk_info`` and the iterations of every stage."""
+        name, A, gamma = _scheme(scheme)
+        tau, t0, t_end = float(tau), float(t0), float(t_end)
+        if not (tau > 0 and math.isfinite(tau)):
+            raise ValueError('tau must be positive and finite, not %r' % (tau,))
+        if not t_end > t0:
+            raise ValueError('t_end (%r) must be greater than t0 (%r)' % (t_end, t0))
+        save_every = int(save_every)
+        if save_every < 1:
+            raise ValueError('save_every must be >= 1')
+        key = self.default_precond if precond == 'auto' else precond
+        if (key if key is not None else 'none') not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        if key == 'kron' and self.box is None:
+            raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch (or none)")
+        nsteps = int(math.ceil((t_end - t0) / tau))
+        h = self._live()
+        if callable(u0):
+            from . import approx
+            u0 = approx.project_L2(self.kvs, u0, f_physical=True, geo=self.geo)
+        x0 = np.array(u0, dtype=np.float64).ravel()
+        if x0.size != self.n:
+            raise ValueError('u0 has %d entries, the space %d' % (x0.size, self.n))
+        x0[self.bc_indices] = self.bc_values
+        self.set_scheme(A, tau)
+        self.set_precond(key)
+        s = A.shape[1]
+        plan = [k for k in range(1, nsteps + 1) if k % save_every == 0 or k == nsteps]
+        saved = np.empty((len(plan), self.n))
+        iters = np.zeros((nsteps, s), dtype=np.int32)
+        info = _lib.DirkInfo()
+        _lib.check(_lib.load().igx_solver_dirk_run(h, _lib.dptr(self.b), _lib.dptr(self.bc_values), _lib.dptr(x0), nsteps,
+                                                   save_every, float(tol), int(maxiter), int(check_every), 1 if timed else 0,
+                                                   _lib.dptr(saved), iters.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(info)),
+                   'igx_solver_dirk_run')
+        steps, converged = int(info.steps), bool(info.converged)
+        kept = [k for k in plan if k <= steps]
+        if not converged and steps > 0 and (not kept or kept[-1] != steps):
+            kept.append(steps)
+        assert len(kept) == info.nsaved, (kept, info.nsaved)
+        implicit = [i for i in range(s) if A[i, i] != 0]
+        rows = iters[:steps + (0 if converged else 1), implicit]
+        reason = _lib.load().igx_solver_last_breakdown(h)
+        self.info = dict(info.as_dict(), converged=converged, nsteps=nsteps, scheme=name, tau=tau, gamma=gamma,
+                         stage_iterations=rows, step_iterations=rows.sum(axis=1), precond=self._precond, method=self.method,
+                         breakdown=_lib.BREAKDOWNS.get(reason, reason))
+        if not converged:
+            warnings.warn('ParabolicSystem.integrate: a stage solve of step %d did not converge within %d iterations; returning '
+                          'the %d steps completed' % (steps + 1, maxiter, steps), RuntimeWarning, stacklevel=2)
+        return [t0] + [t0 + k * tau for k in kept], [x0] + [saved[j] for j in range(len(kept))]
