@@ -406,7 +406,8 @@ int  igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec
    fixed dofs, and the restricted matrix R A R^T never exists.  The handle does NOT own the patch: the patch must outlive it. */
 typedef struct igx_solver igx_solver;
 enum { IGX_PRECOND_NONE = 0, IGX_PRECOND_JACOBI = 1, IGX_PRECOND_KRON = 2,
-       IGX_PRECOND_SCHWARZ = 3 };   /* multipatch solvers only: set up by igx_solver_set_schwarz */
+       IGX_PRECOND_SCHWARZ = 3,     /* multipatch solvers only: set up by igx_solver_set_schwarz */
+       IGX_PRECOND_MG = 4 };        /* multipatch solvers, CG only: one V-cycle of the hierarchy set up by igx_solver_set_mg_* */
 /* how the per-axis eigenvalues lam_k form the diagonal D of a Kronecker preconditioner  (x)U_k . D^-1 . (x)U_k^T */
 enum { IGX_KRON_SUM = 1,       /* D = sum_k 1 (x) .. (x) lam_k (x) .. (x) 1: fast diagonalization of sum_k K_k (x) M_rest (Sangalli-Tani) */
        IGX_KRON_PRODUCT = 2 }; /* D = (x)_k lam_k: with U_k, lam_k the eigenpairs of M_k this is (x) M_k^-1 */
@@ -447,6 +448,64 @@ int igx_solver_set_precond(igx_solver *solver, int precond, const int32_t *box_l
    IGX_ERR_UNSUPPORTED. */
 int igx_solver_set_schwarz(igx_solver *solver, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
                            const double *const *lam, int lam_mode);
+/* --- Geometric multigrid over a hierarchy of multipatch solvers (IGX_PRECOND_MG) -----------------------
+   A hierarchy is a chain of multipatch solvers, the finest first, each over the sums of the same problem on a coarser, nested
+   space with the same sides fixed.  Every solver of the chain gets a smoother (all but the coarsest) and either the next coarser
+   solver or the dense inverse of its matrix.  No handle owns another: all of them, and their multipatches, must outlive the
+   calls that walk the chain; destroying a solver unlinks it from its neighbours (the finer one loses IGX_PRECOND_MG), and a level
+   whose multipatch restarted its sums makes every call that applies the hierarchy return IGX_ERR_ARG.  `level` below counts
+   from the solver given (0) down the chain.
+
+   First-fit colouring of the graph of a CSR pattern (n rows; a symmetric pattern is assumed) restricted to the rows with
+   free_mask[i] != 0 (NULL: all rows): the rows are visited in ascending order and take the smallest colour none of their coloured
+   neighbours has.  colour[i] (n entries) is -1 on the other rows; *ncolours (may be NULL) the number of colours.  Host code:
+   needs no context and no device. */
+int igx_csr_colouring(int64_t n, const int32_t *indptr, const int32_t *indices, const uint8_t *free_mask, int32_t *colour,
+                      int32_t *ncolours);
+/* The Gauss-Seidel smoother of a multipatch solver: colour[i] (host, all dofs; read on the free dofs) such that no two coupled
+   free dofs share a colour (checked against the pattern: IGX_ERR_ARG names the first pair).  A forward sweep relaxes the colours
+   in ascending order, a backward sweep in descending order, one launch per colour; a level of at most block_rows free dofs runs
+   each sweep in a single launch of one block.  smooth_steps (1 .. 16): sweeps before and after the coarse correction. */
+int igx_solver_set_mg_smoother(igx_solver *solver, const int32_t *colour, int smooth_steps, int64_t block_rows);
+/* `coarse` becomes the next level of `solver`.  Both are multipatch solvers over the same number of patches with injective maps
+   (else IGX_ERR_UNSUPPORTED).  P[p*3+k] (host, row-major, fine x coarse dofs of axis k of patch p; axes beyond the patch's dimension
+   are not read): the 1D prolongation matrices, of which only the band of every row and column is kept.  mult (host, the fine
+   solver's dofs): the number of patches every dof belongs to.  Prolongation: x_f = P x_c on the free dofs, P = W^-1 sum_p X_pf
+   (P_0 (x) P_1 (x) P_2) X_pc^T, stored patch after patch; restriction: its transpose. */
+int igx_solver_set_mg_coarse(igx_solver *solver, igx_solver *coarse, const double *const *P, const double *mult);
+/* The coarsest level: inv (host, m x m row-major, m = free dofs of `solver` in ascending order) is applied as a dense product. */
+int igx_solver_set_mg_inverse(igx_solver *solver, const double *inv, int64_t m);
+typedef struct {
+    int64_t nrows, nfree, nnz; /* dofs, free dofs and stored entries of the level's matrix */
+    int32_t ncolours;          /* of the smoother (0: none) */
+    int32_t one_block;         /* 1 if a sweep is a single launch of one block */
+    int32_t smooth_steps;
+    int32_t dense_inverse;     /* 1 if the level is solved with a dense inverse */
+    int32_t has_coarse;        /* 1 if a coarser level is attached */
+    int32_t reserved;
+} igx_mg_info;
+int igx_solver_mg_info(igx_solver *solver, int level, igx_mg_info *out);
+/* The smoother's order of a level: rows (host, nfree) are the free dofs sorted by (colour, index), colour c at
+   colour_offsets[c] .. colour_offsets[c + 1] (host, ncolours + 1). */
+int igx_solver_mg_colours(igx_solver *solver, int level, int32_t *rows, int32_t *colour_offsets);
+/* The pieces alone, on device vectors of all dofs of their level (fixed entries are ignored on input and 0 on output):
+   one sweep in place on d_x with the right-hand side d_b, forward or backward (backward != 0); d_xf = P d_xc from level + 1 to
+   level; d_rc = P^T d_rf from level to level + 1.  The two buffers of a call must differ. */
+int igx_solver_mg_relax_d(igx_solver *solver, int level, int backward, const double *d_b, double *d_x);
+int igx_solver_mg_prolong_d(igx_solver *solver, int level, const double *d_xc, double *d_xf);
+int igx_solver_mg_restrict_d(igx_solver *solver, int level, const double *d_rf, double *d_rc);
+
+/* Device time of the phases of one V-cycle d_z = B d_r (the mean of `reps` cycles; events between the phases): per level the
+   sweeps, the residual (the CSR SpMV) and the transfers to and from the next level, the dense product of the coarsest level, the
+   additions of the corrections, and the kernels one cycle launches (memsets not counted). */
+#define IGX_MG_MAX_LEVELS 16
+typedef struct {
+    int32_t levels, launches;
+    float total_ms, coarse_ms, vector_ms, reserved;
+    float smooth_ms[IGX_MG_MAX_LEVELS], residual_ms[IGX_MG_MAX_LEVELS], transfer_ms[IGX_MG_MAX_LEVELS];
+} igx_mg_profile;
+int igx_solver_mg_profile_d(igx_solver *solver, const double *d_r, double *d_z, int reps, igx_mg_profile *out);
+
 /* d_z = P d_r on the device with the current preconditioner P (full-length vectors; NONE: the free entries of d_r).  d_r and
    d_z must not overlap (d_z is cleared before d_r is read); the same buffer for both is refused with IGX_ERR_ARG. */
 int igx_solver_precond_d(igx_solver *solver, const double *d_r, double *d_z);

@@ -61,10 +61,11 @@ class Timing(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-IGX_PRECOND_NONE, IGX_PRECOND_JACOBI, IGX_PRECOND_KRON, IGX_PRECOND_SCHWARZ = 0, 1, 2, 3
+IGX_PRECOND_NONE, IGX_PRECOND_JACOBI, IGX_PRECOND_KRON, IGX_PRECOND_SCHWARZ, IGX_PRECOND_MG = 0, 1, 2, 3, 4
 IGX_KRON_SUM, IGX_KRON_PRODUCT = 1, 2
 PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'kron': IGX_PRECOND_KRON}
-MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ}
+MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ,
+               'mg': IGX_PRECOND_MG}
 IGX_METHOD_CG, IGX_METHOD_BICGSTAB = 0, 1
 METHODS = {'cg': IGX_METHOD_CG, 'bicgstab': IGX_METHOD_BICGSTAB}
 IGX_BREAKDOWN_RHO, IGX_BREAKDOWN_ALPHA, IGX_BREAKDOWN_OMEGA, IGX_BREAKDOWN_NONFINITE = 1, 2, 3, 4
@@ -80,6 +81,24 @@ class SolveInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MgInfo(C.Structure):
+    _fields_ = [
+        ('nrows', C.c_int64), ('nfree', C.c_int64), ('nnz', C.c_int64), ('ncolours', C.c_int32), ('one_block', C.c_int32),
+        ('smooth_steps', C.c_int32), ('dense_inverse', C.c_int32), ('has_coarse', C.c_int32), ('reserved', C.c_int32),
+    ]
+
+
+IGX_MG_MAX_LEVELS = 16
+
+
+class MgProfile(C.Structure):
+    _fields_ = [
+        ('levels', C.c_int32), ('launches', C.c_int32), ('total_ms', C.c_float), ('coarse_ms', C.c_float), ('vector_ms', C.c_float),
+        ('reserved', C.c_float), ('smooth_ms', C.c_float * IGX_MG_MAX_LEVELS), ('residual_ms', C.c_float * IGX_MG_MAX_LEVELS),
+        ('transfer_ms', C.c_float * IGX_MG_MAX_LEVELS),
+    ]
 
 
 IGX_DIRK_MAX_STAGES = 6
@@ -181,6 +200,17 @@ SYMBOLS = [
     ('igx_solver_destroy', None, [C.c_void_p]),
     ('igx_solver_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
     ('igx_solver_set_schwarz', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
+    ('igx_csr_colouring', C.c_int, [C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32)]),
+    ('igx_solver_set_mg_smoother', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int64]),
+    ('igx_solver_set_mg_coarse', C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_dp), _dp]),
+    ('igx_solver_set_mg_inverse', C.c_int, [C.c_void_p, _dp, C.c_int64]),
+    ('igx_solver_mg_info', C.c_int, [C.c_void_p, C.c_int, C.POINTER(MgInfo)]),
+    ('igx_solver_mg_colours', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ('igx_solver_mg_profile_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MgProfile)]),
+    ('igx_solver_mg_relax_d', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ('igx_solver_mg_prolong_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    ('igx_solver_mg_restrict_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ('igx_solver_precond_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_spmv_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_solve', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(SolveInfo)]),

@@ -100,6 +100,13 @@ class KnotVector:
         g = np.convolve(kv, np.ones(p) / p)[p:-p]
         return np.clip(g, kv[0], kv[-1])
 
+    def refine(self, new_knots=None):
+        """The knot vector with `new_knots` inserted; without them, with the midpoint of every nonempty span inserted (uniform
+        refinement)."""
+        if new_knots is None:
+            new_knots = (self.mesh[1:] + self.mesh[:-1]) / 2
+        return KnotVector(np.sort(np.concatenate((self.kv, np.asarray(new_knots, dtype=self.kv.dtype).ravel()))), self.p)
+
     def copy(self):
         return KnotVector(self.kv.copy(), self.p)
 
@@ -126,6 +133,59 @@ def make_knots(p, a, b, n, mult=1):
          np.repeat(np.arange(a, b, (b - a) / n)[1:], mult),
          np.repeat(b, p + 1)))
     return KnotVector(kv, p)
+
+
+def _host_span(kv, u):
+    """``i`` with ``kv[i] <= u < kv[i+1]``, the last span closed on the right (host code: the multigrid set-up runs it once per
+    inserted knot)."""
+    knots, p = kv.kv, kv.p
+    if not knots[p] <= u <= knots[-p - 1]:
+        raise ValueError('knot %r lies outside the knot vector' % (u,))
+    return int(min(np.searchsorted(knots, u, side='right') - 1, knots.size - p - 2))
+
+
+def knot_insertion(kv, u):
+    """The ``(n+1) x n`` CSR matrix, ``n = kv.numdofs``, that maps the coefficients of a spline over `kv` to its coefficients
+    over `kv` with the knot `u` inserted (Boehm's algorithm)."""
+    import scipy.sparse
+    n, p, knots = kv.numdofs, kv.p, kv.kv
+    k = _host_span(kv, u)
+    # rows up to k-p copy their coefficient, rows past k copy the previous one, rows k-p+1 .. k blend two neighbours
+    blend = np.arange(k - p + 1, k + 1)
+    a = (u - knots[blend]) / (knots[blend + p] - knots[blend])
+    keep_lo = np.arange(0, k - p + 1)
+    keep_hi = np.arange(k + 1, n + 1)
+    rows = np.concatenate((keep_lo, keep_hi, blend, blend))
+    cols = np.concatenate((keep_lo, keep_hi - 1, blend - 1, blend))
+    vals = np.concatenate((np.ones(keep_lo.size + keep_hi.size), 1 - a, a))
+    return scipy.sparse.coo_matrix((vals, (rows, cols)), shape=(n + 1, n)).tocsr()
+
+
+def prolongation(kv1, kv2):
+    """The CSR matrix that maps the coefficients of a spline over `kv1` to its coefficients over `kv2`, whose space must contain
+    that of `kv1` (same degree, every knot of `kv1` with at least its multiplicity).  The product of one knot insertion per
+    missing knot, which is exact; entries below 1e-15 are pruned."""
+    import scipy.sparse
+    if kv1.p != kv2.p:
+        raise ValueError('prolongation between degrees %d and %d' % (kv1.p, kv2.p))
+    u1, c1 = np.unique(kv1.kv, return_counts=True)
+    u2, c2 = np.unique(kv2.kv, return_counts=True)
+    have = dict(zip(u1.tolist(), c1.tolist()))
+    new = []
+    for u, c in zip(u2.tolist(), c2.tolist()):
+        new += [u] * (c - have.pop(u, 0))
+    if have or len(new) != kv2.kv.size - kv1.kv.size:
+        raise ValueError('the knots of kv1 are not a subset of those of kv2')
+    P = scipy.sparse.identity(kv1.numdofs, format='csr')
+    kv = kv1
+    for u in new:
+        P = knot_insertion(kv, u) @ P
+        kv = kv.refine([u])
+    P = scipy.sparse.csr_matrix(P)
+    P.data[np.abs(P.data) < 1e-15] = 0.0
+    P.eliminate_zeros()
+    P.sort_indices()
+    return P
 
 
 def numdofs(kvs):

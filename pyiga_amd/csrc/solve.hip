@@ -25,6 +25,7 @@
 // local solve of every Schwarz patch; igx_solver_solve forms the lifted right-hand side and hands over to solve_cg or
 // solve_bicgstab.
 #include "igx_internal.h"
+#include "mg_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1008,6 +1009,8 @@ struct igx_solver {
     double *d_dirk = nullptr;                 // xs | Mx | f | y | F_0 .. F_{stages-1}, n each (allocated by the first run)
     hipEvent_t dev[6] = {};
     bool have_dev = false;
+    // multigrid (igx_solver_set_mg_*, multigrid.hip): this solver's level of the hierarchy, or null
+    igx::MgLevel *mg = nullptr;
 };
 
 namespace {
@@ -1028,7 +1031,7 @@ int check_values(const igx_solver *s, const char *what)
                       "over the new sums", what);
             return IGX_ERR_ARG;
         }
-        return IGX_OK;
+        return s->precond == IGX_PRECOND_MG ? mg_check(s, what) : IGX_OK;     // (every coarser level's sums as well)
     }
     if (s->parabolic) {                       // (its values are its own: they must be taken and C formed)
         if (!s->c_formed) {
@@ -1119,6 +1122,7 @@ int apply_schwarz(hipStream_t st, igx_solver *s, const double *r, double *z)
 // the preconditioners applied by kernels of their own (Kronecker, Schwarz); Jacobi is fused into k_update
 int apply_dense(hipStream_t st, igx_solver *s, const double *r, double *z)
 {
+    if (s->precond == IGX_PRECOND_MG) return mg_apply(st, s, r, z);
     return s->precond == IGX_PRECOND_SCHWARZ ? apply_schwarz(st, s, r, z) : apply_kron(st, s, r, z);
 }
 
@@ -1134,6 +1138,7 @@ int spmv_occupancy(const igx_solver *s)
 
 void free_solver(igx_solver *s)
 {
+    mg_free(s);
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
     (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
     (void)hipFree(s->d_bvec); (void)hipFree(s->d_bsc);
@@ -1229,7 +1234,8 @@ int solve_cg(hipStream_t st, igx_solver *s, double bnorm, double tol, int maxite
     const long long n = s->n;
     const unsigned nbv = vec_blocks(n), nbs = spmv_blocks(s);
     double *pA = s->d_part, *pB = s->d_part + NB_SPMV_MAX;
-    const bool kron = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ, jac = s->precond == IGX_PRECOND_JACOBI;
+    const bool kron = s->precond == IGX_PRECOND_KRON || s->precond == IGX_PRECOND_SCHWARZ || s->precond == IGX_PRECOND_MG;
+    const bool jac = s->precond == IGX_PRECOND_JACOBI;
     // z = P r, rz, rr; p = z
     const double *zz = (kron || jac) ? s->z : s->r;
     if (jac) {
@@ -1467,6 +1473,39 @@ int check_free_box(const igx_solver *s, long long base, const int32_t *box_lo, c
 
 } // namespace
 
+// what multigrid.hip sees of a solver (mg_internal.h)
+namespace igx {
+
+SolverRef solver_ref(const igx_solver *s)
+{
+    return SolverRef{s->ctx, s->mp, s->n, s->gw, s->d_mask, s->h_free.data(), s->precond, s->method};
+}
+
+MgLevel *&solver_mg(igx_solver *s) { return s->mg; }
+
+void solver_drop_mg_precond(igx_solver *s)
+{
+    if (s->precond == IGX_PRECOND_MG) s->precond = IGX_PRECOND_NONE;
+}
+
+int solver_check_sums(const igx_solver *s, const char *what)
+{
+    if (!s->mp) { set_error("%s: a multigrid level needs a multipatch solver", what); return IGX_ERR_UNSUPPORTED; }
+    if (s->mp->generation != s->gen) {
+        set_error("%s: the sums of a multipatch of the multigrid hierarchy were restarted (igx_multipatch_zero) since its solver was "
+                  "made: make the solvers again", what);
+        return IGX_ERR_ARG;
+    }
+    return IGX_OK;
+}
+
+int solver_residual(hipStream_t st, const igx_solver *s, const double *x, const double *b, double *y)
+{
+    return spmv(st, s, x, b, -1.0, y, nullptr, nullptr);
+}
+
+} // namespace igx
+
 extern "C" {
 
 int igx_solver_create(igx_patch *pt, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out)
@@ -1514,6 +1553,10 @@ int igx_solver_set_method(igx_solver *s, int method)
         return IGX_OK;
     }
     if (method != IGX_METHOD_BICGSTAB) { set_error("igx_solver_set_method: unknown method %d", method); return IGX_ERR_ARG; }
+    if (s->precond == IGX_PRECOND_MG) {
+        set_error("igx_solver_set_method: the multigrid preconditioner serves CG only: select another preconditioner first");
+        return IGX_ERR_UNSUPPORTED;
+    }
     IGX_HIP(hipSetDevice(s->ctx->device));
     if (int rc = init_bicgstab(s, "igx_solver_set_method")) return rc;
     s->method = method;
@@ -1641,6 +1684,13 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
         s->precond = precond;
         return IGX_OK;
     }
+    if (precond == IGX_PRECOND_MG) {
+        if (!s->mp) { set_error("igx_solver_set_precond: the multigrid preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
+        if (s->method != IGX_METHOD_CG) { set_error("igx_solver_set_precond: the multigrid preconditioner serves CG only"); return IGX_ERR_UNSUPPORTED; }
+        if (int rc = mg_check(s, "igx_solver_set_precond")) return rc;
+        s->precond = precond;
+        return IGX_OK;
+    }
     if (precond != IGX_PRECOND_KRON) { set_error("igx_solver_set_precond: unknown preconditioner %d", precond); return IGX_ERR_ARG; }
     if (s->mp) { set_error("igx_solver_set_precond: IGX_PRECOND_KRON needs a patch solver (multipatch: IGX_PRECOND_SCHWARZ)"); return IGX_ERR_UNSUPPORTED; }
     if (s->ncomp > 1) {                                   // the factors of every component, set by igx_solver_set_block_kron
@@ -1755,6 +1805,10 @@ int igx_solver_precond_d(igx_solver *s, const double *d_r, double *d_z)
         break;
     case IGX_PRECOND_SCHWARZ:
         if (int rc = apply_schwarz(st, s, d_r, d_z)) return rc;
+        break;
+    case IGX_PRECOND_MG:                                   // (the V-cycle reads r with zeros on the fixed dofs)
+        k_mask_copy<<<nb, 256, 0, st>>>(s->n, s->d_mask, d_r, s->w);
+        if (int rc = mg_apply(st, s, s->w, d_z)) return rc;
         break;
     default: k_mask_copy<<<nb, 256, 0, st>>>(s->n, s->d_mask, d_r, d_z); break;
     }

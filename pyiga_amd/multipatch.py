@@ -170,6 +170,8 @@ class Multipatch:
         self.N_ofs = np.concatenate(([0], np.cumsum(self.N)))
         self.shared_per_patch = [dict() for _ in self.patches]
         self.shared_dofs = []
+        self.boundary_joins = []                  # the arguments of every join_boundaries call, in order, and whether
+        self.bare_joins = False                   # join_dofs was called directly: such joins cannot be replayed on other knots
         self._handle = None
         self._ctx = None                          # the context the handle lives on
         self._pattern = None
@@ -194,6 +196,10 @@ class Multipatch:
 
     def join_dofs(self, p1, I1, p2, I2):
         """Join the dofs `I1` of patch `p1` with the dofs `I2` of patch `p2`."""
+        self.bare_joins = True
+        self._join_dofs(p1, I1, p2, I2)
+
+    def _join_dofs(self, p1, I1, p2, I2):
         assert len(I1) == len(I2), 'dof arrays must have the same length'
         assert p1 != p2, 'patches must be different'
         self._drop_device()
@@ -220,7 +226,22 @@ class Multipatch:
         boundary) reverses the traversal of `p2`'s boundary along that axis."""
         dofs1 = boundary_dofs(self.patches[p1][0], bdspec1, ravel=True)
         dofs2 = boundary_dofs(self.patches[p2][0], bdspec2, ravel=True, flip=flip)
-        self.join_dofs(p1, dofs1, p2, dofs2)
+        self._join_dofs(p1, dofs1, p2, dofs2)
+        self.boundary_joins.append((p1, bdspec1, p2, bdspec2, None if flip is None else tuple(flip)))
+
+    def replay_joins(self, patches):
+        """A finalized multipatch of `patches` (one per patch of this one, e.g. the same geometries over coarser knot vectors)
+        joined as this one was.  ValueError if this one was joined through bare :meth:`join_dofs` calls."""
+        if self.bare_joins:
+            raise ValueError('the multipatch was joined through join_dofs: its joins cannot be replayed on other knot vectors')
+        patches = list(patches)
+        if len(patches) != self.numpatches:
+            raise ValueError('%d patches given, the multipatch has %d' % (len(patches), self.numpatches))
+        MP = Multipatch(patches)
+        for join in self.boundary_joins:
+            MP.join_boundaries(*join)
+        MP.finalize()
+        return MP
 
     def finalize(self):
         """Set up the numbering after all joins."""
