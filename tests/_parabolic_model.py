@@ -17,8 +17,19 @@ def _split(n, bc_idx):
     return np.flatnonzero(~fixed), np.flatnonzero(fixed)
 
 
-def restricted_dirk(A, M, K, f, bc_idx, bc_val, u0, tau, nsteps):
-    """Full state vectors (g on the fixed dofs) after 0 .. nsteps steps."""
+def stage_solver(M, K, bc_idx, tau, gamma):
+    """The exact stage solve of restricted_dirk, y = (M_ff + tau gamma K_ff)^-1 r, factorized once: for several integrations with
+    one tau and gamma at a size where the factorization is most of the model's time (minimum-degree ordering on the symmetric
+    pattern: a third of the default's time at 264 k dofs)."""
+    M, K = scipy.sparse.csr_matrix(M), scipy.sparse.csr_matrix(K)
+    fr, _ = _split(M.shape[0], bc_idx)
+    C = scipy.sparse.csc_matrix(M[fr][:, fr] + tau * gamma * K[fr][:, fr])
+    return scipy.sparse.linalg.splu(C, permc_spec='MMD_AT_PLUS_A').solve
+
+
+def restricted_dirk(A, M, K, f, bc_idx, bc_val, u0, tau, nsteps, solve=None):
+    """Full state vectors (g on the fixed dofs) after 0 .. nsteps steps.  `solve`: the stage solve of stage_solver, if it was
+    factorized already."""
     M, K = scipy.sparse.csr_matrix(M), scipy.sparse.csr_matrix(K)
     fr, fx = _split(M.shape[0], bc_idx)
     g = np.zeros(M.shape[0])
@@ -27,7 +38,8 @@ def restricted_dirk(A, M, K, f, bc_idx, bc_val, u0, tau, nsteps):
     bf = f[fr] - K[fr][:, fx] @ g[fx]
     s = A.shape[1]
     gamma = max(A[i, i] for i in range(s))
-    solve = scipy.sparse.linalg.factorized(scipy.sparse.csc_matrix(Mf + tau * gamma * Kf))
+    if solve is None:
+        solve = scipy.sparse.linalg.factorized(scipy.sparse.csc_matrix(Mf + tau * gamma * Kf))
     x = np.asarray(u0, dtype=float)[fr].copy()
     Fx = None
     out = [x]

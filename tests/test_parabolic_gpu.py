@@ -209,3 +209,111 @@ def test_refusals_on_the_device_path():
         solvers.ParabolicSystem(kvs, geo, 0.0, problem=form_assemblers.FormAssembler)
     with pytest.raises(ValueError, match='surface'):
         solvers.ParabolicSystem(kvs[:1], geo, 0.0, problem='u * v * dx')
+
+
+# ---------------------------------------------------------------------------------------------
+# k_vals_axpby and k_dirk_rhs past one grid and at full length (the constants and tableaux: tests/_mg_cases.py)
+def _check_stage_matrix(kvs, geo, sides, tag):
+    """S.spmv against free * ((M + tau gamma K) (free * x)) row by row in long double, M and K as the device assembled them.
+    Returns the number of values of C."""
+    bcs = assemble.compute_dirichlet_bcs(kvs, geo, [(s, 1.0) for s in sides])
+    from pyiga_amd import assemblers
+    patch = assemblers.DevicePatch(kvs, geo)                   # (the values in the patch's own layout: no entry is dropped)
+    try:
+        M = patch.csr('mass').copy()
+        K = patch.csr('stiffness').copy()
+    finally:
+        patch.close()
+    assert np.array_equal(M.indptr, K.indptr) and np.array_equal(M.indices, K.indices)
+    S = solvers.ParabolicSystem(kvs, geo, 1.0, bcs)
+    try:
+        tau = 1e-3
+        S.set_scheme('sdirk3', tau)
+        gamma = solvers.check_tableau(solvers.dirk_tableau('sdirk3'))[1]
+        n = M.shape[0]
+        x = np.random.default_rng(1).standard_normal(n)
+        free = np.ones(n)
+        free[bcs[0]] = 0
+        y = S.spmv(x)
+        nv = int(S.patch.pattern()[1].size)        # the values k_vals_axpby combines: those of the patch's layout
+        assert nv == M.nnz
+    finally:
+        S.close()
+    ld = np.longdouble
+    tg = ld(tau) * ld(gamma)
+    Cl = scipy.sparse.csr_matrix((M.data.astype(ld) + tg * K.data.astype(ld), M.indices, M.indptr), shape=M.shape)
+    Ca = scipy.sparse.csr_matrix((np.abs(M.data).astype(ld) + tg * np.abs(K.data).astype(ld), M.indices, M.indptr), shape=M.shape)
+    xf = (free * x).astype(ld)
+    want = free * (Cl @ xf)
+    mag = Ca @ np.abs(xf)
+    err = np.abs(y.astype(ld) - want)
+    rel = float(err.max() / np.abs(want).max())
+    rows = float((err[free > 0] / mag[free > 0]).max())
+    print('C = M + tau gamma K', tag, 'values', nv, 'rel. difference %.2e' % rel, 'largest row error / row magnitude %.2e' % rows)
+    assert rel < 1e-13, (tag, rel)
+    assert rows < 1e-13, (tag, rows)                # a single wrong value of C changes its row by the order of its magnitude
+    assert not y[bcs[0]].any()
+    return nv
+
+
+def test_stage_matrix_past_one_grid_of_k_vals_axpby():
+    """3D p = 3, n = 30: 219^3 = 10 503 459 values, an odd number (the last value is the tail lane's) and more than the 16 ncu
+    blocks of 256 lanes cover with AXPBY_U = 4 pairs each, so every u and a second trip of the outer loop run."""
+    import subprocess
+    import sys
+    import _mg_cases as mc
+    # (torch in a child process: this one has initialised the library's HIP runtime, beside which torch's finds no device)
+    out = subprocess.run([sys.executable, '-c', 'import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)'],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    ncu = int(out.stdout.split()[-1])
+    kvs = (bspline.make_knots(3, 0.0, 1.0, 30),) * 3
+    geo = geometry.tensor_product(geometry.line_segment(0.0, 1.0), geometry.quarter_annulus())
+    nv = _check_stage_matrix(kvs, geo, [(0, 1)], '3d_p3_n30')
+    one_trip = 16 * ncu * 256 * mc.AXPBY_U * 2
+    print('k_vals_axpby: values', nv, 'one trip of the grid', one_trip, '(ncu %d)' % ncu)
+    assert one_trip == 32768 * ncu and nv > one_trip and nv % 2 == 1
+
+
+def test_stage_matrix_of_an_odd_tiny_patch():
+    """2D p = 1, n = 2: 49 values; 24 pairs in a partial block and the tail lane do all the work."""
+    kvs = (bspline.make_knots(1, 0.0, 1.0, 2),) * 2
+    assert _check_stage_matrix(kvs, geometry.quarter_annulus(), [(0, 1)], '2d_p1_n2') == 49
+
+
+def test_full_tableaux_past_one_grid_of_k_dirk_rhs():
+    """2D p = 2, n = 512: 264 196 dofs, more than the NB_VEC blocks of k_dirk_rhs hold, and tableaux of IGX_DIRK_MAX_STAGES stages
+    with a full lower triangle, with and without an explicit first stage: the last stage combines 7 vectors (M x, five F_j, f).
+    Two steps of each against the host model (one factorization: the tableaux share their gamma)."""
+    import _mg_cases as mc
+    import _solver_cases as sc
+    tabs = mc.dirk6_tableaux()
+    kvs = (bspline.make_knots(2, 0.0, 1.0, 512),) * 2
+    geo = geometry.quarter_annulus()
+    f, gf = (lambda x, y: 10 * (1 + x * y)), (lambda x, y: 1 + 0.1 * x)
+    bcs = assemble.compute_dirichlet_bcs(kvs, geo, [('left', gf), ('right', gf)])
+    rhs = assemble.inner_products(kvs, f, f_physical=True, geo=geo).ravel()
+    M, K = assemble.mass(kvs, geo), assemble.stiffness(kvs, geo)
+    n = M.shape[0]
+    assert n == 264196 > sc.vec_pass_rows()
+    u0 = 1.0 + 0.1 * np.random.default_rng(9).standard_normal(n)     # rough: K u0 is large, every F_j weighs in the stage sums
+    tau = 1e-5
+    gamma = {solvers.check_tableau(A)[1] for A in tabs.values()}
+    assert len(gamma) == 1
+    solve = P.stage_solver(M, K, bcs[0], tau, gamma.pop())
+    S = solvers.ParabolicSystem(kvs, geo, rhs, bcs)
+    try:
+        for name in ('sdirk6', 'esdirk6'):
+            A = tabs[name]
+            times, sols = S.integrate(u0, tau, 1.5 * tau, scheme=A, tol=1e-12)
+            assert len(sols) == 3 and S.info['converged']
+            implicit = int(np.count_nonzero(np.diag(A[:6])))
+            assert S.info['stage_iterations'].shape == (2, implicit) and implicit == (5 if name == 'esdirk6' else 6)
+            ref = P.restricted_dirk(A, M, K, rhs, bcs[0], bcs[1], sols[0], tau, 2, solve=solve)
+            d = _relmax(sols, ref)
+            step = _relmax([sols[2] - sols[0]], [ref[2] - ref[0]])
+            print('DIRK', name, 'dofs', n, 'stage iterations', S.info['stage_iterations'].tolist(), 'rel. difference %.2e' % d,
+                  'of the change over two steps %.2e' % step)
+            assert d < 1e-8, (name, d)
+    finally:
+        S.close()
