@@ -40,6 +40,8 @@
  *                                         pyiga/approx.py:62-96 (one patch, matrix values never leave the device)
  *   igx_solver_*_parabolic / _dirk_*   <- crank_nicolson, sdirk3, esdirk34, ... (dirk_step, constant steps)
  *                                         pyiga/solvers.py:366-473 (linear M u' = f - K u, one patch, on the device)
+ *   igx_solver_set_stepper / _step_*   <- sdirk21 .. esdirk34 with adaptive steps, ros3p .. rosi2p1 (rosenbrock_step)
+ *                                         pyiga/solvers.py:430-435, 475-534, 684-939 (a session of attempts)
  */
 #ifndef IGX_H
 #define IGX_H
@@ -617,6 +619,71 @@ int  igx_solver_set_dirk(igx_solver *solver, int stages, const double *A, double
 int  igx_solver_dirk_run(igx_solver *solver, const double *f, const double *g, const double *x0, int64_t nsteps, int64_t save_every,
                          double tol, int maxiter, int check_every, int timed, double *saved, int32_t *stage_iters,
                          igx_dirk_info *info);
+
+/* --- Adaptive steps and Rosenbrock methods: a session of attempts (pyiga/solvers.py:430-435, 475-534, 684-939) ---------------
+   The number of steps is not known in advance, so the host drives the controller and the device runs one attempt per call:
+       igx_solver_set_stepper, igx_solver_set_step_precond, igx_solver_step_begin, then per attempt igx_solver_step_attempt and,
+       if the host accepts it, igx_solver_step_accept (and igx_solver_step_state to bring a state down).
+   One attempt with the step tau from the state x (g on the fixed dofs), which it leaves untouched:
+     IGX_STEPPER_DIRK        the stages of igx_solver_dirk_run; candidate x_new = y_{s-1}.  With an estimate: x_est is
+                             M_ff^-1 (M_ff x + tau sum_i b^_i F_i), and M_ff x_new = M_ff x + tau sum_i b_i F_i (the last stage), so
+                             R M R^T (x_est - x_new) = tau sum_i (b^_i - b_i) F_i: one CG solve on M whatever K is.
+     IGX_STEPPER_ROSENBROCK  R C R^T k_i = R (f - K (x + tau sum_{j<i} (a_ij + gamma_ij) k_j)), k_i = 0 on the fixed dofs (F is affine,
+                             J = -K); candidate x_new = x + tau sum b_i k_i, x_est = x + tau sum b^_i k_i.
+   C = M + tau gamma K is formed again only when tau gamma differs from that of the C on the device.  The estimate is
+       r = || (x_est - x_new) / (err_tol + err_tol |x|) ||_2 / sqrt(n_free)   over the free dofs (k_err_norm).
+   The session owns C and the preconditioner data while it runs: after it, igx_solver_set_dirk and igx_solver_set_precond again
+   before igx_solver_dirk_run or igx_solver_solve. */
+enum { IGX_STEPPER_DIRK = 0, IGX_STEPPER_ROSENBROCK = 1 };
+enum { IGX_STEP_STATE = 0, IGX_STEP_CANDIDATE = 1 };
+typedef struct {
+    double  r;                     /* the error ratio (0 without an estimate or when a solve did not converge) */
+    int32_t converged;             /* 1 if every solve of the attempt converged: there is a candidate */
+    int32_t reformed;              /* 1 if C was formed again for this tau */
+    int32_t has_estimate;          /* 1 if err_tol > 0 */
+    int32_t mass_iterations;       /* iterations of the mass solve of an embedded DIRK rule */
+    int32_t stage_iterations[IGX_DIRK_MAX_STAGES];   /* per stage (0: explicit, or not reached) */
+    int64_t n_free;
+    float axpby_ms;                /* forming C, if it was formed */
+    float spmv_ms;                 /* timed != 0: the products with M and K */
+    float combine_ms;              /* timed != 0: right-hand sides, initial guesses, the candidate */
+    float solve_ms;                /* timed != 0: the stage solves */
+    float mass_ms;                 /* timed != 0: the mass solve */
+    float err_ms;                  /* timed != 0: k_err_norm, its finish and the read-back */
+    float total_ms;                /* device time of the whole attempt */
+    float reserved;
+} igx_step_info;
+/* The scheme of the session.  IGX_STEPPER_DIRK: A as igx_solver_set_dirk takes it ((stages + 1) x stages, the same conditions),
+   Gamma NULL, b NULL or equal to the last row of A.  IGX_STEPPER_ROSENBROCK: A and Gamma stages x stages, A strictly lower
+   triangular, Gamma lower triangular with one positive diagonal value gamma, b of stages weights.  b_hat: the weights of the
+   embedded rule, or NULL (no estimate).  Anything else: IGX_ERR_ARG.  Ends a running session. */
+int  igx_solver_set_stepper(igx_solver *solver, int family, int stages, const double *A, const double *Gamma, const double *b,
+                            const double *b_hat);
+/* The preconditioner of the session's solves: IGX_PRECOND_NONE, IGX_PRECOND_JACOBI (the diagonal of the values in use, by k_diag)
+   or IGX_PRECOND_KRON with the factors U_k and the RAW eigenvalues lam_k of eigh(K_k, M_k) on the free box (arguments as
+   igx_solver_set_precond's).  The device rewrites the eigenvalue slots per attempt: tau gamma lam_k + 1/dim for C, 1/dim for M
+   (U_k^T M_k U_k = I: the inverse of the parametric mass matrix).  A change of step uploads nothing.  igx_solver_set_precond
+   replaces the factors: call this again after it. */
+int  igx_solver_set_step_precond(igx_solver *solver, int precond, const int32_t *box_lo, const int32_t *box_hi,
+                                 const double *const *U, const double *const *lam_raw);
+/* Starts a session: f, g and x0 as igx_solver_dirk_run takes them, the only uploads of vectors. */
+int  igx_solver_step_begin(igx_solver *solver, const double *f, const double *g, const double *x0);
+/* One attempt.  err_tol <= 0: no estimate (constant steps; required if the scheme has no b_hat).  Every solve runs to
+   ||r|| <= solve_tol ||r0|| within maxiter iterations, r0 the residual of its start value: zero (r0 the right-hand side) but for
+   the DIRK stages, which start from y_{i-1} and so are solved for their increment (the reference's Newton measures rtol the same
+   way); a start value that meets solve_tol ||rhs|| already is taken as it is.  A solve that does not converge ends the attempt
+   with info->converged = 0 (no candidate; the host rejects and halves tau).  The state and, for an explicit first stage, F_1 are
+   untouched by the attempt. */
+int  igx_solver_step_attempt(igx_solver *solver, double tau, double err_tol, double solve_tol, int maxiter, int check_every,
+                             int timed, igx_step_info *info);
+/* The candidate of the last attempt becomes the state (a swap of pointers). */
+int  igx_solver_step_accept(igx_solver *solver);
+/* The state (IGX_STEP_STATE) or the candidate of the last attempt (IGX_STEP_CANDIDATE), g included, to the host. */
+int  igx_solver_step_state(igx_solver *solver, int which, double *out);
+/* k_err_norm alone on device vectors of the solver's length (any solver):
+   *r = || (sum_k coef[k] d_v[k]) / (tol + tol |d_x|) ||_2 / sqrt(n_free) over the free dofs; nv from 1 to 8. */
+int  igx_solver_error_ratio_d(igx_solver *solver, int nv, const double *coef, const double *const *d_v, const double *d_x,
+                              double tol, double *r);
 
 /* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers.  The factors are dense, row-major, m[k] x n[k]
    (rectangular allowed).  x and y are tensors of shape (n_0, .., n_{dim-1}, batch) and (m_0, .., batch), addressed through an

@@ -117,6 +117,20 @@ class DirkInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
 
+IGX_STEPPER_DIRK, IGX_STEPPER_ROSENBROCK = 0, 1
+IGX_STEP_STATE, IGX_STEP_CANDIDATE = 0, 1
+COMB_MAX = 8                    # vectors of one k_dirk_rhs / k_err_norm pass (csrc/solve.hip)
+
+
+class StepInfo(C.Structure):
+    _fields_ = [
+        ('r', C.c_double), ('converged', C.c_int32), ('reformed', C.c_int32), ('has_estimate', C.c_int32),
+        ('mass_iterations', C.c_int32), ('stage_iterations', C.c_int32 * IGX_DIRK_MAX_STAGES), ('n_free', C.c_int64),
+        ('axpby_ms', C.c_float), ('spmv_ms', C.c_float), ('combine_ms', C.c_float), ('solve_ms', C.c_float),
+        ('mass_ms', C.c_float), ('err_ms', C.c_float), ('total_ms', C.c_float), ('reserved', C.c_float),
+    ]
+
+
 class KronDesc(C.Structure):
     _fields_ = [
         ('dim', C.c_int32), ('m', C.c_int32 * 3), ('n', C.c_int32 * 3), ('d_B', C.c_void_p * 3),
@@ -219,6 +233,13 @@ SYMBOLS = [
     ('igx_solver_set_dirk', C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double]),
     ('igx_solver_dirk_run', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, _dp,
                                       C.POINTER(C.c_int32), C.POINTER(DirkInfo)]),
+    ('igx_solver_set_stepper', C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    ('igx_solver_set_step_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp)]),
+    ('igx_solver_step_begin', C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    ('igx_solver_step_attempt', C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(StepInfo)]),
+    ('igx_solver_step_accept', C.c_int, [C.c_void_p]),
+    ('igx_solver_step_state', C.c_int, [C.c_void_p, C.c_int, _dp]),
+    ('igx_solver_error_ratio_d', C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, _dp]),
     ('igx_kron_apply_d', C.c_int, [C.c_void_p, C.POINTER(KronDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
 ]
 

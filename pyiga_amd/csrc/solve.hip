@@ -492,6 +492,71 @@ __global__ void k_dirk_rhs(long long n, const Comb L, double *out)
     }
 }
 
+// The error estimate of an adaptive step fused with its weighted norm:  e_j = sum_k c[k] v[k][j],
+// part[block] = sum over the free dofs of (e_j / (tol + tol |x_j|))^2.  Fixed dofs are left out by a select, so whatever finite or
+// non-finite value e has there does not reach the sum.  One grid-stride pass of (nv + 1) 8 bytes + the mask byte per dof; the
+// partials are finished by k_fin in its fixed order.  V2: every vector, x and the mask are 16-byte aligned, so that two dofs are
+// one 16-byte load of each vector and one 2-byte load of the mask; the odd last dof is lane 0's of block 0
+template <bool V2>
+__global__ void __launch_bounds__(BLOCK) k_err_norm(long long n, const Comb L, const double *__restrict__ x,
+                                                    const uint8_t *__restrict__ freem, double tol, double *part)
+{
+    __shared__ double sh[BLOCK];
+    const long long stride = (long long)gridDim.x * BLOCK, t0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    double s = 0.0;
+    auto term = [&](double e, double xj, bool free) {
+        const double q = e / (tol + tol * fabs(xj));
+        return free ? q * q : 0.0;
+    };
+    if (V2) {
+        const long long n2 = n / 2;
+        const dbl2 *x2 = reinterpret_cast<const dbl2 *>(x);
+        const unsigned short *m2 = reinterpret_cast<const unsigned short *>(freem);
+        for (long long i = t0; i < n2; i += stride) {
+            dbl2 e = {0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < COMB_MAX; ++k)
+                if (k < L.nv) e += L.c[k] * reinterpret_cast<const dbl2 *>(L.v[k])[i];
+            const dbl2 xv = x2[i];
+            const unsigned m = m2[i];
+            s += term(e.x, xv.x, (m & 0xffu) != 0);
+            s += term(e.y, xv.y, (m >> 8) != 0);
+        }
+        if ((n & 1) && t0 == 0) {
+            double e = 0.0;
+#pragma unroll
+            for (int k = 0; k < COMB_MAX; ++k)
+                if (k < L.nv) e += L.c[k] * L.v[k][n - 1];
+            s += term(e, x[n - 1], freem[n - 1] != 0);
+        }
+    } else {
+        for (long long i = t0; i < n; i += stride) {
+            double e = 0.0;
+#pragma unroll
+            for (int k = 0; k < COMB_MAX; ++k)
+                if (k < L.nv) e += L.c[k] * L.v[k][i];
+            s += term(e, x[i], freem[i] != 0);
+        }
+    }
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// the eigenvalue slots of the packed fast-diagonalization factors from the raw eigenvalues kept beside them:
+// lam'_k = scale lam_k + shift  (C = M + tau gamma K: scale = tau gamma, shift = 1/dim; M: scale = 0)
+struct LamSlots {
+    int nax;
+    int m[3];
+    long long slot[3], raw[3];               // offsets of lam'_k in the factor buffer and of lam_k in the raw one
+};
+
+__global__ void k_kron_lam(const LamSlots L, const double *__restrict__ raw, double *fac, double scale, double shift)
+{
+    for (int k = 0; k < L.nax; ++k)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < L.m[k]; i += gridDim.x * blockDim.x)
+            fac[L.slot[k] + i] = scale * raw[L.raw[k] + i] + shift;
+}
+
 // ---------------------------------------------------------------------------------------------
 // BiCGStab (right-preconditioned, the "Templates" variant).  Its scalars live in a block of their own (BS_*)
 // that only k_fin_bicg writes.  BS_DONE freezes the solve: every update kernel returns at once when it is set, so iterations run
@@ -1009,6 +1074,24 @@ struct igx_solver {
     double *d_dirk = nullptr;                 // xs | Mx | f | y | F_0 .. F_{stages-1}, n each (allocated by the first run)
     hipEvent_t dev[6] = {};
     bool have_dev = false;
+    // adaptive stepping session (igx_solver_set_stepper .. igx_solver_step_accept)
+    double c_tg = 0.0;                        // the tau gamma of the C on the device (c_formed)
+    const double *vals_sel = nullptr;         // the values the SpMV and Jacobi read instead of C (the mass solve: M)
+    int family = -1;                          // IGX_STEPPER_*, -1: no stepper set
+    int st_stages = 0;
+    bool st_bhat = false;
+    double st_A[(IGX_DIRK_MAX_STAGES + 1) * IGX_DIRK_MAX_STAGES] = {};    // DIRK: b the last row; Rosenbrock: stages rows
+    double st_G[IGX_DIRK_MAX_STAGES * IGX_DIRK_MAX_STAGES] = {};
+    double st_b[IGX_DIRK_MAX_STAGES] = {}, st_bh[IGX_DIRK_MAX_STAGES] = {};
+    double st_gamma = 0.0;
+    int step_precond = -1;                    // the session's preconditioner (IGX_PRECOND_*), -1: not set (or replaced since)
+    LamSlots lam_slots{};
+    double *d_lamraw = nullptr;               // the raw eigenvalues lam_k, axis after axis
+    int pc_vals = -1;                         // what the preconditioner data was last made for: 0 M, 2 C (-1: nothing), with
+    double pc_tg = 0.0;                       // this tau gamma
+    double *d_wg = nullptr;                   // ext(g) of the session (allocated by the first igx_solver_step_begin)
+    bool step_live = false, have_mx = false, have_F0 = false, have_cand = false;
+    double *sx = nullptr, *smx = nullptr, *sfv = nullptr, *sy = nullptr, *sF[IGX_DIRK_MAX_STAGES] = {};
     // multigrid (igx_solver_set_mg_*, multigrid.hip): this solver's level of the hierarchy, or null
     igx::MgLevel *mg = nullptr;
 };
@@ -1049,7 +1132,11 @@ int check_values(const igx_solver *s, const char *what)
 }
 
 // the values a scalar patch solver's SpMV and Jacobi read: the patch's, or a parabolic solver's own C
-const double *patch_values(const igx_solver *s) { return s->parabolic ? s->pv[2] : s->pt->d_data; }
+const double *patch_values(const igx_solver *s)
+{
+    if (!s->parabolic) return s->pt->d_data;
+    return s->vals_sel ? s->vals_sel : s->pv[2];       // (vals_sel: M, during the mass solve of an embedded DIRK attempt)
+}
 
 unsigned spmv_blocks(const igx_solver *s)
 {
@@ -1145,7 +1232,7 @@ void free_solver(igx_solver *s)
     for (double *v : s->blk) (void)hipFree(v);
     for (double *v : s->d_bkron) (void)hipFree(v);
     for (double *v : s->pv) (void)hipFree(v);
-    (void)hipFree(s->d_dirk);
+    (void)hipFree(s->d_dirk); (void)hipFree(s->d_lamraw); (void)hipFree(s->d_wg);
     if (s->have_dev)
         for (auto &e : s->dev) (void)hipEventDestroy(e);
     if (s->have_ev)
@@ -1664,6 +1751,8 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     if (!s) { set_error("igx_solver_set_precond: null solver"); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
+    s->step_precond = -1;                                // (a stepping session's preconditioner data is replaced: set it again)
+    s->pc_vals = -1;
     if (precond == IGX_PRECOND_NONE) { s->precond = precond; return IGX_OK; }
     if (precond == IGX_PRECOND_JACOBI) {
         if (int rc = check_values(s, "igx_solver_set_precond")) return rc;
@@ -1854,8 +1943,16 @@ int finish_solve(hipStream_t st, igx_solver *s, const double *gvals, double *u, 
 // The device entry of the solves: R A R^T x = R (b - A w) with b in s->b and w = ext(g) in s->w (both on the device, full
 // length).  With x0_in_x the initial guess is in s->x already, zero on the fixed dofs; else x starts at 0.  r = R (b - A w), its
 // norm the reference of the relative residual; r -= A x0; then CG or BiCGStab (s->method).  The free part of the solution stays
-// in s->x (zero on the fixed dofs).
-int solve_lifted(hipStream_t st, igx_solver *s, bool x0_in_x, double tol, int maxiter, int check_every, int timed, igx_solve_info &inf)
+// in s->x (zero on the fixed dofs).  `lift`: the vector w (s->w, or another full-length device vector), or null: nothing is
+// lifted, r = R b (the stages of a Rosenbrock method, whose unknowns vanish on the fixed dofs).  The matrix is the one spmv()
+// multiplies by (a parabolic solver: C, or the values of s->vals_sel) and the preconditioner the one s holds now.
+// `from_guess` (with x0_in_x): the stop is relative to the residual the initial guess leaves, ||r|| <= tol ||r0||, as the
+// reference's Newton measures it (pyiga/solvers.py:350-354: rtol times the residual at the start value): the solve is then one
+// for the increment x - x0, and its tolerance refers to the change of a stage and not to the 1/(tau |F|) times larger state.  A
+// guess that meets tol ||R (b - A w)|| already is the solution (no iteration), and the stop is never below
+// 100 eps ||R (b - A w)||, which the true residual cannot be seen to pass.
+int solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool x0_in_x, double tol, int maxiter, int check_every, int timed,
+                 igx_solve_info &inf, bool from_guess = false)
 {
     const long long n = s->n;
     const size_t nbytes = (size_t)n * sizeof(double);
@@ -1867,15 +1964,27 @@ int solve_lifted(hipStream_t st, igx_solver *s, bool x0_in_x, double tol, int ma
     const unsigned nbv = vec_blocks(n);
     double *pA = s->d_part;
     // r = R (b - A ext(g)); its norm is the reference of the relative residual
-    if (int rc = spmv(st, s, s->w, s->b, -1.0, s->r, nullptr, nullptr)) return rc;
+    if (lift) {
+        if (int rc = spmv(st, s, lift, s->b, -1.0, s->r, nullptr, nullptr)) return rc;
+    } else k_mask_copy<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, s->d_mask, s->b, s->r);
     k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
     k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbv, s->d_sc, FIN_INIT);
     double h_rr = 0.0;
     IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
     IGX_HIP(hipStreamSynchronize(st));
-    const double bnorm = std::sqrt(h_rr);
+    double bnorm = std::sqrt(h_rr);
     if (x0_in_x) {
         if (int rc = spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
+        if (from_guess) {
+            k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, pA, nullptr);
+            k_fin<<<1, BLOCK, 0, st>>>(pA, nullptr, nbv, s->d_sc, FIN_INIT);
+            IGX_HIP(hipGetLastError());
+            IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+            IGX_HIP(hipStreamSynchronize(st));
+            IGX_HIP(hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st));
+            // (not below what double precision resolves of the true residual: 100 eps ||R (b - A w)||)
+            if (std::sqrt(h_rr) > tol * bnorm) bnorm = std::max(std::sqrt(h_rr), 100.0 * 2.220446049250313e-16 * bnorm / tol);
+        }
     }
     return s->method == IGX_METHOD_BICGSTAB ? solve_bicgstab(st, s, bnorm, tol, maxiter, check_every, timed, inf)
                                             : solve_cg(st, s, bnorm, tol, maxiter, check_every, timed, inf);
@@ -1911,7 +2020,7 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
         IGX_HIP(hipMemcpyAsync(s->x, xf.data(), nbytes, hipMemcpyHostToDevice, st));
         IGX_HIP(hipStreamSynchronize(st));                   // (xf leaves scope)
     }
-    if (int rc = solve_lifted(st, s, x0 != nullptr, tol, maxiter, check_every, timed, inf)) return rc;
+    if (int rc = solve_lifted(st, s, s->w, x0 != nullptr, tol, maxiter, check_every, timed, inf)) return rc;
     return finish_solve(st, s, gvals, u, info, inf);
 }
 
@@ -1995,6 +2104,50 @@ bool dirk_ok(int st, const double *A, double tau, double &gamma, const char *wha
     return true;
 }
 
+// xs | Mx | f | y | F_0 .. F_5 of a parabolic solver, n each (once)
+int alloc_dirk_vectors(igx_solver *s, const char *what)
+{
+    if (s->d_dirk) return IGX_OK;
+    const size_t nbytes = (size_t)s->n * sizeof(double);
+    if (hipMalloc((void **)&s->d_dirk, (4 + IGX_DIRK_MAX_STAGES) * nbytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: out of device memory (%.3f GB)", what, (4.0 + IGX_DIRK_MAX_STAGES) * nbytes / 1e9);
+        return IGX_ERR_NOMEM;
+    }
+    return IGX_OK;
+}
+
+// the buffer of C and the events of the time stepping (once)
+int alloc_stage_matrix(igx_solver *s, const char *what)
+{
+    const long long nv = s->nvals[0];
+    if (!s->pv[2]) {
+        if (hipMalloc((void **)&s->pv[2], (size_t)nv * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: out of device memory (%.3f GB for C)", what, 8.0 * nv / 1e9);
+            return IGX_ERR_NOMEM;
+        }
+    }
+    if (!s->have_dev) {
+        for (auto &e : s->dev)
+            if (hipEventCreate(&e) != hipSuccess) { set_error("%s: hipEventCreate failed", what); return IGX_ERR_HIP; }
+        s->have_dev = true;
+    }
+    return IGX_OK;
+}
+
+// C = M + tg K into the solver's buffer (k_vals_axpby between the events dev[0] and dev[1]; not synchronised)
+int form_stage_matrix(hipStream_t st, igx_solver *s, double tg)
+{
+    const long long nv = s->nvals[0];
+    const long long blocks = std::min<long long>((nv / 2 + BLOCK - 1) / BLOCK, 16LL * std::max(1, s->ctx->ncu));
+    IGX_HIP(hipEventRecord(s->dev[0], st));
+    k_vals_axpby<<<(unsigned)std::max<long long>(1, blocks), BLOCK, 0, st>>>(nv, 1.0, s->pv[0], tg, s->pv[1], s->pv[2]);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipEventRecord(s->dev[1], st));
+    return IGX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2056,32 +2209,18 @@ int igx_solver_set_dirk(igx_solver *s, int stages, const double *A, double tau)
     if (!dirk_ok(stages, A, tau, gamma, what)) return IGX_ERR_ARG;
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    const long long nv = s->nvals[0];
-    if (!s->pv[2]) {
-        if (hipMalloc((void **)&s->pv[2], (size_t)nv * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("%s: out of device memory (%.3f GB for C)", what, 8.0 * nv / 1e9);
-            return IGX_ERR_NOMEM;
-        }
-    }
-    if (!s->have_dev) {
-        for (auto &e : s->dev)
-            if (hipEventCreate(&e) != hipSuccess) { set_error("%s: hipEventCreate failed", what); return IGX_ERR_HIP; }
-        s->have_dev = true;
-    }
+    if (int rc = alloc_stage_matrix(s, what)) return rc;
     s->c_formed = false;
     s->precond = IGX_PRECOND_NONE;                   // (Jacobi's diagonal and the Kronecker factors depend on C: set them again)
-    const long long blocks = std::min<long long>((nv / 2 + BLOCK - 1) / BLOCK, 16LL * std::max(1, s->ctx->ncu));
-    IGX_HIP(hipEventRecord(s->dev[0], st));
-    k_vals_axpby<<<(unsigned)std::max<long long>(1, blocks), BLOCK, 0, st>>>(nv, 1.0, s->pv[0], tau * gamma, s->pv[1], s->pv[2]);
-    IGX_HIP(hipGetLastError());
-    IGX_HIP(hipEventRecord(s->dev[1], st));
+    s->pc_vals = -1;
+    if (int rc = form_stage_matrix(st, s, tau * gamma)) return rc;
     IGX_HIP(hipStreamSynchronize(st));
     (void)hipEventElapsedTime(&s->axpby_ms, s->dev[0], s->dev[1]);
     s->stages = stages;
     std::copy(A, A + (stages + 1) * stages, s->dirk_A);
     s->tau = tau;
     s->gamma = gamma;
+    s->c_tg = tau * gamma;
     s->c_formed = true;
     return IGX_OK;
 }
@@ -2095,18 +2234,18 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
     if (nsteps < 1 || save_every < 1) { set_error("%s: nsteps and save_every must be >= 1", what); return IGX_ERR_ARG; }
     if (!(tol >= 0.0) || maxiter < 0) { set_error("%s: tol must be >= 0 and maxiter >= 0", what); return IGX_ERR_ARG; }
     if (int rc = check_values(s, what)) return rc;
+    if (s->c_tg != s->tau * s->gamma || s->pc_vals != -1) {
+        set_error("%s: a stepping session (igx_solver_step_attempt) formed C or its preconditioner data since igx_solver_set_dirk: "
+                  "set the tableau and the preconditioner again", what);
+        return IGX_ERR_ARG;
+    }
     if (check_every < 1) check_every = 1;
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     const long long n = s->n;
     const size_t nbytes = (size_t)n * sizeof(double);
-    if (!s->d_dirk) {
-        if (hipMalloc((void **)&s->d_dirk, (4 + IGX_DIRK_MAX_STAGES) * nbytes) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("%s: out of device memory (%.3f GB)", what, (4.0 + IGX_DIRK_MAX_STAGES) * nbytes / 1e9);
-            return IGX_ERR_NOMEM;
-        }
-    }
+    if (int rc = alloc_dirk_vectors(s, what)) return rc;
+    s->step_live = false;                                            // (the vectors of a stepping session are overwritten)
     double *xs = s->d_dirk, *mx = xs + n, *fv = xs + 2 * n, *y = xs + 3 * n, *F[IGX_DIRK_MAX_STAGES];
     for (int j = 0; j < IGX_DIRK_MAX_STAGES; ++j) F[j] = xs + (4 + j) * n;
     const int ns = s->stages;
@@ -2169,7 +2308,7 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
             IGX_HIP(hipGetLastError());
             if (int rc = lap(inf.combine_ms)) return rc;
             igx_solve_info si{};
-            if (int rc = solve_lifted(st, s, true, tol, maxiter, check_every, 0, si)) return rc;
+            if (int rc = solve_lifted(st, s, s->w, true, tol, maxiter, check_every, 0, si)) return rc;
             if (int rc = lap(inf.solve_ms)) return rc;
             if (stage_iters) stage_iters[(k - 1) * ns + i] = si.iterations;
             inf.iterations += si.iterations;
@@ -2207,6 +2346,433 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
     (void)hipEventElapsedTime(&inf.total_ms, E[4], E[5]);
     inf.converged = ok ? 1 : 0;
     if (info) *info = inf;
+    return IGX_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Adaptive steps and Rosenbrock methods: a session of attempts (pyiga/solvers.py:430-435, 475-534, 684-707).
+// The host drives the controller; one attempt runs wholly on the device and leaves a candidate beside the untouched state.
+
+namespace {
+
+// a Rosenbrock scheme: A strictly lower triangular, Gamma lower triangular with one positive diagonal value (gamma out)
+bool rosenbrock_ok(int st, const double *A, const double *G, const double *b, const double *bh, double &gamma, const char *what)
+{
+    if (st < 1 || st > IGX_DIRK_MAX_STAGES) { set_error("%s: %d stages (1 to %d)", what, st, IGX_DIRK_MAX_STAGES); return false; }
+    for (int i = 0; i < st; ++i) {
+        if (!std::isfinite(b[i]) || (bh && !std::isfinite(bh[i]))) { set_error("%s: a weight of stage %d is not finite", what, i); return false; }
+        for (int j = 0; j < st; ++j) {
+            const double a = A[i * st + j], g = G[i * st + j];
+            if (!std::isfinite(a) || !std::isfinite(g)) { set_error("%s: entry [%d][%d] is not finite", what, i, j); return false; }
+            if (j >= i && a != 0.0) { set_error("%s: A is not strictly lower triangular (A[%d][%d] = %g)", what, i, j, a); return false; }
+            if (j > i && g != 0.0) { set_error("%s: Gamma is not lower triangular (Gamma[%d][%d] = %g)", what, i, j, g); return false; }
+        }
+    }
+    gamma = G[0];
+    if (!(gamma > 0.0)) { set_error("%s: the diagonal of Gamma must be positive (%g)", what, gamma); return false; }
+    for (int i = 1; i < st; ++i)
+        if (G[i * st + i] != gamma) {
+            set_error("%s: two diagonal values of Gamma (%.17g and %.17g): C would change per stage", what, gamma, G[i * st + i]);
+            return false;
+        }
+    return true;
+}
+
+// the preconditioner data of the session for the values `which` (0: M, 2: C with this tau gamma): the eigenvalue slots of the
+// Kronecker factors (k_kron_lam) or Jacobi's diagonal (k_diag on the values in use); nothing if they are in place
+int step_refresh_precond(hipStream_t st, igx_solver *s, int which, double tg)
+{
+    s->precond = s->step_precond;
+    if (s->pc_vals == which && (which == 0 || s->pc_tg == tg)) return IGX_OK;
+    if (s->step_precond == IGX_PRECOND_KRON) {
+        k_kron_lam<<<1, 256, 0, st>>>(s->lam_slots, s->d_lamraw, s->d_kron, which == 0 ? 0.0 : tg, 1.0 / s->dim);
+        IGX_HIP(hipGetLastError());
+    } else if (s->step_precond == IGX_PRECOND_JACOBI) {
+        k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, patch_values(s), s->d_mask, s->dinv);
+        IGX_HIP(hipGetLastError());
+    }
+    s->pc_vals = which;
+    s->pc_tg = tg;
+    return IGX_OK;
+}
+
+// sum over the free dofs of ((sum_k c_k v_k) / (tol + tol |x|))^2 into *sum (host), by k_err_norm and k_fin
+int err_norm(hipStream_t st, igx_solver *s, const Comb &L, const double *x, double tol, double *sum)
+{
+    const unsigned nbv = vec_blocks(s->n);
+    bool v2 = (reinterpret_cast<uintptr_t>(x) % 16 == 0) && (reinterpret_cast<uintptr_t>(s->d_mask) % 2 == 0);
+    for (int k = 0; k < L.nv; ++k) v2 = v2 && reinterpret_cast<uintptr_t>(L.v[k]) % 16 == 0;
+    if (v2) k_err_norm<true><<<nbv, BLOCK, 0, st>>>(s->n, L, x, s->d_mask, tol, s->d_part);
+    else k_err_norm<false><<<nbv, BLOCK, 0, st>>>(s->n, L, x, s->d_mask, tol, s->d_part);
+    k_fin<<<1, BLOCK, 0, st>>>(s->d_part, nullptr, nbv, s->d_sc, FIN_INIT);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipMemcpyAsync(sum, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
+bool step_solver_ok(const igx_solver *s, const char *what)
+{
+    if (!s) { set_error("%s: null solver", what); return false; }
+    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return false; }
+    if (!s->pv[IGX_ROLE_MASS] || !s->pv[IGX_ROLE_OPERATOR]) { set_error("%s: take M and K first (igx_solver_take_values)", what); return false; }
+    return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int igx_solver_set_stepper(igx_solver *s, int family, int stages, const double *A, const double *Gamma, const double *b,
+                           const double *b_hat)
+{
+    const char *what = "igx_solver_set_stepper";
+    if (!s || !A) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
+    double gamma = 0.0;
+    if (family == IGX_STEPPER_DIRK) {
+        if (Gamma) { set_error("%s: a DIRK scheme has no Gamma", what); return IGX_ERR_ARG; }
+        if (!dirk_ok(stages, A, 1.0, gamma, what)) return IGX_ERR_ARG;
+        for (int j = 0; j < stages; ++j) {
+            if (b && b[j] != A[stages * stages + j]) { set_error("%s: b differs from the last row of A at %d", what, j); return IGX_ERR_ARG; }
+            if (b_hat && !std::isfinite(b_hat[j])) { set_error("%s: b_hat[%d] is not finite", what, j); return IGX_ERR_ARG; }
+        }
+        std::copy(A, A + (stages + 1) * stages, s->st_A);
+        std::copy(A + stages * stages, A + (stages + 1) * stages, s->st_b);
+    } else if (family == IGX_STEPPER_ROSENBROCK) {
+        if (!Gamma || !b) { set_error("%s: a Rosenbrock scheme needs Gamma and b", what); return IGX_ERR_ARG; }
+        if (!rosenbrock_ok(stages, A, Gamma, b, b_hat, gamma, what)) return IGX_ERR_ARG;
+        std::copy(A, A + stages * stages, s->st_A);
+        std::copy(Gamma, Gamma + stages * stages, s->st_G);
+        std::copy(b, b + stages, s->st_b);
+    } else { set_error("%s: unknown family %d", what, family); return IGX_ERR_ARG; }
+    s->st_bhat = b_hat != nullptr;
+    if (b_hat) std::copy(b_hat, b_hat + stages, s->st_bh);
+    s->family = family;
+    s->st_stages = stages;
+    s->st_gamma = gamma;
+    s->step_live = false;                                 // (a session belongs to its scheme: begin again)
+    return IGX_OK;
+}
+
+int igx_solver_set_step_precond(igx_solver *s, int precond, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                                const double *const *lam_raw)
+{
+    const char *what = "igx_solver_set_step_precond";
+    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    s->step_precond = -1;
+    s->pc_vals = -1;
+    if (precond == IGX_PRECOND_NONE || precond == IGX_PRECOND_JACOBI) { s->step_precond = precond; return IGX_OK; }
+    if (precond != IGX_PRECOND_KRON) { set_error("%s: preconditioner %d (none, Jacobi or Kronecker)", what, precond); return IGX_ERR_ARG; }
+    if (!box_lo || !box_hi || !U || !lam_raw) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    const int d = s->dim;
+    int nb[3] = {1, 1, 1};
+    if (int rc = check_free_box(s, 0, box_lo, box_hi, U, lam_raw, nb, what)) return rc;
+    std::vector<double> h, raw;
+    pack_fastdiag(h, d, nb, U, lam_raw);
+    LamSlots L{};
+    L.nax = d;
+    size_t o = 0;
+    for (int k = 0; k < d; ++k) {                        // (the layout of pack_fastdiag: U_k^T | U_k | lam_k)
+        const size_t mk = (size_t)nb[k];
+        L.m[k] = nb[k];
+        L.slot[k] = (long long)(o + 2 * mk * mk);
+        L.raw[k] = (long long)raw.size();
+        raw.insert(raw.end(), lam_raw[k], lam_raw[k] + mk);
+        o += 2 * mk * mk + mk;
+    }
+    s->precond = IGX_PRECOND_NONE;
+    IGX_HIP(hipStreamSynchronize(st));
+    if (int rc = alloc_fastdiag(s, st, h, std::max<long long>(1, (long long)nb[0] * nb[1] * nb[2]))) return rc;
+    (void)hipFree(s->d_lamraw); s->d_lamraw = nullptr;
+    IGX_HIP(hipMalloc((void **)&s->d_lamraw, raw.size() * sizeof(double)));
+    IGX_HIP(hipMemcpyAsync(s->d_lamraw, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    long long full_stride[4], off = 0;
+    box_strides(d, s->N, full_stride);
+    for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
+    s->kron = make_fastdiag(d, nb, s->d_kron, full_stride, off, IGX_KRON_SUM);
+    s->lam_slots = L;
+    IGX_HIP(hipStreamSynchronize(st));
+    s->step_precond = IGX_PRECOND_KRON;
+    return IGX_OK;
+}
+
+int igx_solver_step_begin(igx_solver *s, const double *f, const double *gvals, const double *x0)
+{
+    const char *what = "igx_solver_step_begin";
+    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (!f || (!gvals && !s->fixed.empty()) || !x0) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (s->family < 0) { set_error("%s: no scheme yet (igx_solver_set_stepper)", what); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const long long n = s->n;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    s->step_live = false;
+    if (int rc = alloc_dirk_vectors(s, what)) return rc;
+    if (int rc = alloc_stage_matrix(s, what)) return rc;
+    if (!s->d_wg) {
+        if (hipMalloc((void **)&s->d_wg, nbytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: out of device memory (%.3f GB)", what, nbytes / 1e9);
+            return IGX_ERR_NOMEM;
+        }
+    }
+    double *v = s->d_dirk;
+    s->sx = v; s->smx = v + n; s->sfv = v + 2 * n; s->sy = v + 3 * n;
+    for (int j = 0; j < IGX_DIRK_MAX_STAGES; ++j) s->sF[j] = v + (4 + j) * n;
+    std::vector<double> h((size_t)n), w((size_t)n, 0.0);
+    for (long long i = 0; i < n; ++i) h[i] = s->h_free[i] ? x0[i] : 0.0;
+    for (size_t k = 0; k < s->fixed.size(); ++k) h[s->fixed[k]] = w[s->fixed[k]] = gvals[k];
+    IGX_HIP(hipMemcpyAsync(s->sx, h.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(s->d_wg, w.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(s->sfv, f, nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    s->have_mx = s->have_F0 = s->have_cand = false;
+    s->breakdown = 0;
+    s->step_live = true;
+    return IGX_OK;
+}
+
+int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double solve_tol, int maxiter, int check_every, int timed,
+                            igx_step_info *info)
+{
+    const char *what = "igx_solver_step_attempt";
+    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (!s->step_live) { set_error("%s: no session (igx_solver_step_begin; igx_solver_dirk_run and igx_solver_set_stepper end one)", what); return IGX_ERR_ARG; }
+    if (s->step_precond < 0) { set_error("%s: no preconditioner of the session (igx_solver_set_step_precond; igx_solver_set_precond replaces it)", what); return IGX_ERR_ARG; }
+    if (!(tau > 0.0) || !std::isfinite(tau)) { set_error("%s: tau must be positive and finite", what); return IGX_ERR_ARG; }
+    if (!(solve_tol >= 0.0) || maxiter < 0) { set_error("%s: solve_tol must be >= 0 and maxiter >= 0", what); return IGX_ERR_ARG; }
+    if (err_tol > 0.0 && !s->st_bhat) { set_error("%s: the scheme has no embedded rule (b_hat): err_tol must be <= 0", what); return IGX_ERR_ARG; }
+    if (check_every < 1) check_every = 1;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const long long n = s->n;
+    const int ns = s->st_stages;
+    const double *A = s->st_A, gamma = s->st_gamma, tg = tau * gamma;
+    const bool estimate = err_tol > 0.0;
+    const unsigned nbv = vec_blocks(n), nbm = (unsigned)((n + 255) / 256);
+    igx_step_info inf{};
+    inf.n_free = n - (long long)s->fixed.size();
+    inf.has_estimate = estimate ? 1 : 0;
+    s->have_cand = false;
+    s->breakdown = 0;
+    s->vals_sel = nullptr;
+    hipEvent_t *E = s->dev;
+    IGX_HIP(hipEventRecord(E[4], st));
+    if (!s->c_formed || s->c_tg != tg) {                            // C on the device belongs to another step
+        s->c_formed = false;
+        if (int rc = form_stage_matrix(st, s, tg)) return rc;
+        IGX_HIP(hipEventSynchronize(E[1]));
+        (void)hipEventElapsedTime(&s->axpby_ms, E[0], E[1]);
+        inf.axpby_ms = s->axpby_ms;
+        inf.reformed = 1;
+        s->c_tg = tg;
+        s->c_formed = true;
+        s->pc_vals = -1;
+    }
+    if (int rc = step_refresh_precond(st, s, 2, tg)) return rc;
+    int mark = 2;                                                    // timed: E[2] / E[3] alternate (E[0], E[1]: k_vals_axpby)
+    if (timed) IGX_HIP(hipEventRecord(E[mark], st));
+    auto lap = [&](float &bucket) -> int {
+        if (!timed) return IGX_OK;
+        const int next = 5 - mark;
+        IGX_HIP(hipEventRecord(E[next], st));
+        IGX_HIP(hipEventSynchronize(E[next]));
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, E[mark], E[next]);
+        bucket += ms;
+        mark = next;
+        return IGX_OK;
+    };
+    bool ok = true;
+    double sum = 0.0;
+    if (s->family == IGX_STEPPER_DIRK) {
+        double *xs = s->sx, *mx = s->smx, *fv = s->sfv, *y = s->sy, **F = s->sF;
+        const bool explicit_first = A[0] == 0.0;
+        if (explicit_first && !s->have_F0) {                         // F_1 of the first step: f - K x0
+            if (int rc = spmv_values(st, s, s->pv[1], xs, fv, -1.0, F[0])) return rc;
+            s->have_F0 = true;
+        }
+        if (!s->have_mx) {                                           // M x: kept over rejected attempts
+            if (int rc = spmv_values(st, s, s->pv[0], xs, nullptr, 1.0, mx)) return rc;
+            s->have_mx = true;
+        }
+        if (int rc = lap(inf.spmv_ms)) return rc;
+        const double *yprev = xs;
+        bool have_Fs = false;
+        for (int i = 0; i < ns && ok; ++i) {
+            const double aii = A[i * ns + i];
+            if (aii == 0.0) continue;                                // (i = 0: y_1 = x, F_1 in F[0])
+            Comb L{};
+            L.c[L.nv] = 1.0; L.v[L.nv++] = mx;
+            for (int j = 0; j < i; ++j)
+                if (A[i * ns + j] != 0.0) { L.c[L.nv] = tau * A[i * ns + j]; L.v[L.nv++] = F[j]; }
+            L.c[L.nv] = tg; L.v[L.nv++] = fv;
+            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
+            k_mask_copy<<<nbm, 256, 0, st>>>(n, s->d_mask, yprev, s->x);    // the initial guess y_{i-1}
+            IGX_HIP(hipGetLastError());
+            if (int rc = lap(inf.combine_ms)) return rc;
+            igx_solve_info si{};
+            if (int rc = solve_lifted(st, s, s->d_wg, true, solve_tol, maxiter, check_every, 0, si, true)) return rc;
+            if (int rc = lap(inf.solve_ms)) return rc;
+            inf.stage_iterations[i] = si.iterations;
+            if (!si.converged) { ok = false; break; }
+            Comb Y{};
+            Y.nv = 2; Y.c[0] = 1.0; Y.v[0] = s->x; Y.c[1] = 1.0; Y.v[1] = s->d_wg;     // y_i = x + ext(g)
+            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, Y, y);
+            IGX_HIP(hipGetLastError());
+            if (int rc = lap(inf.combine_ms)) return rc;
+            yprev = y;
+            // F_i = f - K y_i; the last one as F_1 of the next step, or where the embedded rule weighs it
+            if (i < ns - 1 || explicit_first || (estimate && s->st_bh[i] != s->st_b[i])) {
+                if (int rc = spmv_values(st, s, s->pv[1], y, fv, -1.0, F[i])) return rc;
+                if (int rc = lap(inf.spmv_ms)) return rc;
+                if (i == ns - 1) have_Fs = true;
+            }
+        }
+        if (ok && estimate) {
+            // e = x_est - x_new: the last stage equation is M x_new = M x + tau sum b_i F_i, so R M R^T e = tau sum (b^_i - b_i) F_i
+            // (the F_i vanish on the fixed dofs; nothing to lift).  One CG solve on M from zero: its relative residual is that
+            // of the estimate itself, not of the 1/err_tol times larger x_est
+            Comb L{};
+            for (int j = 0; j < ns; ++j) {
+                const double c = s->st_bh[j] - s->st_b[j];
+                if (c != 0.0 && (j < ns - 1 || have_Fs)) { L.c[L.nv] = tau * c; L.v[L.nv++] = F[j]; }
+            }
+            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
+            IGX_HIP(hipGetLastError());
+            if (int rc = lap(inf.combine_ms)) return rc;
+            s->vals_sel = s->pv[IGX_ROLE_MASS];
+            const int method = s->method;
+            s->method = IGX_METHOD_CG;                               // (M is symmetric positive definite whatever K is)
+            igx_solve_info si{};
+            int rc = step_refresh_precond(st, s, 0, 0.0);
+            if (!rc) rc = solve_lifted(st, s, nullptr, false, solve_tol, maxiter, check_every, 0, si);
+            s->method = method;
+            s->vals_sel = nullptr;
+            if (rc) return rc;
+            if (int rc2 = lap(inf.mass_ms)) return rc2;
+            inf.mass_iterations = si.iterations;
+            if (!si.converged) ok = false;
+            else {
+                Comb D{};
+                D.nv = 1; D.c[0] = 1.0; D.v[0] = s->x;
+                if (int rc2 = err_norm(st, s, D, xs, err_tol, &sum)) return rc2;
+                if (int rc2 = lap(inf.err_ms)) return rc2;
+            }
+        }
+    } else {
+        // Rosenbrock: C k_i = f~ - K (x + tau sum_j (a_ij + gamma_ij) k_j) on the free dofs, k_i = 0 on the fixed ones
+        double *xs = s->sx, *cand = s->smx, *fv = s->sfv, *yt = s->sy, **K = s->sF;
+        const double *G = s->st_G;
+        for (int i = 0; i < ns && ok; ++i) {
+            Comb L{};
+            L.c[L.nv] = 1.0; L.v[L.nv++] = xs;
+            for (int j = 0; j < i; ++j) {
+                const double c = A[i * ns + j] + G[i * ns + j];
+                if (c != 0.0) { L.c[L.nv] = tau * c; L.v[L.nv++] = K[j]; }
+            }
+            const double *yi = xs;
+            if (L.nv > 1) {
+                k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, yt);
+                IGX_HIP(hipGetLastError());
+                if (int rc = lap(inf.combine_ms)) return rc;
+                yi = yt;
+            }
+            if (int rc = spmv_values(st, s, s->pv[1], yi, fv, -1.0, s->b)) return rc;
+            if (int rc = lap(inf.spmv_ms)) return rc;
+            igx_solve_info si{};
+            if (int rc = solve_lifted(st, s, nullptr, false, solve_tol, maxiter, check_every, 0, si)) return rc;
+            IGX_HIP(hipMemcpyAsync(K[i], s->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            if (int rc = lap(inf.solve_ms)) return rc;
+            inf.stage_iterations[i] = si.iterations;
+            if (!si.converged) ok = false;
+        }
+        if (ok) {
+            Comb L{};
+            L.c[L.nv] = 1.0; L.v[L.nv++] = xs;
+            for (int j = 0; j < ns; ++j)
+                if (s->st_b[j] != 0.0) { L.c[L.nv] = tau * s->st_b[j]; L.v[L.nv++] = K[j]; }
+            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, cand);
+            IGX_HIP(hipGetLastError());
+            if (int rc = lap(inf.combine_ms)) return rc;
+            if (estimate) {
+                Comb D{};
+                for (int j = 0; j < ns; ++j) {
+                    const double c = s->st_bh[j] - s->st_b[j];
+                    if (c != 0.0) { D.c[D.nv] = tau * c; D.v[D.nv++] = K[j]; }
+                }
+                if (int rc = err_norm(st, s, D, xs, err_tol, &sum)) return rc;
+                if (int rc = lap(inf.err_ms)) return rc;
+            }
+        }
+    }
+    IGX_HIP(hipEventRecord(E[5], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("%s: kernel failure: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
+    }
+    (void)hipEventElapsedTime(&inf.total_ms, E[4], E[5]);
+    inf.converged = ok ? 1 : 0;
+    inf.r = (ok && estimate) ? std::sqrt(sum) / std::sqrt((double)std::max<long long>(1, inf.n_free)) : 0.0;
+    s->have_cand = ok;
+    if (info) *info = inf;
+    return IGX_OK;
+}
+
+int igx_solver_step_accept(igx_solver *s)
+{
+    const char *what = "igx_solver_step_accept";
+    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (!s->step_live || !s->have_cand) { set_error("%s: no candidate (a converged igx_solver_step_attempt first)", what); return IGX_ERR_ARG; }
+    if (s->family == IGX_STEPPER_DIRK) {
+        std::swap(s->sx, s->sy);                                     // x_new = y_s
+        if (s->st_A[0] == 0.0) std::swap(s->sF[0], s->sF[s->st_stages - 1]);
+    } else std::swap(s->sx, s->smx);
+    s->have_mx = false;
+    s->have_cand = false;
+    return IGX_OK;
+}
+
+int igx_solver_step_state(igx_solver *s, int which, double *out)
+{
+    const char *what = "igx_solver_step_state";
+    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (!out) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!s->step_live) { set_error("%s: no session (igx_solver_step_begin)", what); return IGX_ERR_ARG; }
+    if (which != IGX_STEP_STATE && which != IGX_STEP_CANDIDATE) { set_error("%s: unknown vector %d", what, which); return IGX_ERR_ARG; }
+    if (which == IGX_STEP_CANDIDATE && !s->have_cand) { set_error("%s: no candidate (a converged igx_solver_step_attempt first)", what); return IGX_ERR_ARG; }
+    const double *src = which == IGX_STEP_STATE ? s->sx : s->family == IGX_STEPPER_DIRK ? s->sy : s->smx;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    IGX_HIP(hipMemcpyAsync(out, src, (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
+int igx_solver_error_ratio_d(igx_solver *s, int nv, const double *coef, const double *const *d_v, const double *d_x, double tol,
+                             double *r)
+{
+    const char *what = "igx_solver_error_ratio_d";
+    if (!s || !coef || !d_v || !d_x || !r) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (nv < 1 || nv > COMB_MAX) { set_error("%s: %d vectors (1 to %d)", what, nv, COMB_MAX); return IGX_ERR_ARG; }
+    if (!(tol > 0.0)) { set_error("%s: tol must be positive", what); return IGX_ERR_ARG; }
+    Comb L{};
+    for (int k = 0; k < nv; ++k) {
+        if (!d_v[k]) { set_error("%s: vector %d is null", what, k); return IGX_ERR_ARG; }
+        L.c[k] = coef[k]; L.v[k] = d_v[k];
+    }
+    L.nv = nv;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    double sum = 0.0;
+    if (int rc = err_norm(s->ctx->stream, s, L, d_x, tol, &sum)) return rc;
+    const long long nfree = s->n - (long long)s->fixed.size();
+    *r = std::sqrt(sum) / std::sqrt((double)std::max<long long>(1, nfree));
     return IGX_OK;
 }
 

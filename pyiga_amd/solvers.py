@@ -28,6 +28,10 @@ block-diagonal fast-diagonalization preconditioner serve CG or BiCGStab.
 one patch, integrated on the device by a DIRK scheme with constant steps (``integrate``; the reference's ``crank_nicolson``,
 ``sdirk3``, ..., pyiga/solvers.py:366-473).  Every stage solves with ``C = M + tau gamma K``; M, K and C stay on the device, and
 only the saved states come down.  ``dirk_tableau(name)`` gives the tableaux of the named schemes.
+``integrate_adaptive`` chooses the step from the embedded rule of ``sdirk21``, ``dirk34``, ``esdirk23``, ``esdirk34``
+(``embedded_tableau``) or of the Rosenbrock methods ``ros3p``, ``ros3pw``, ``rowdaind2``, ``rodasp``, ``rosi2p1``
+(``rosenbrock_tableau``; pyiga/solvers.py:475-534, 684-939): the error estimate, its norm and the mass solve run on the device,
+the accept/reject controller on the host.
 """
 import ctypes as C
 import math
@@ -1066,6 +1070,122 @@ def _tableau(name):
 DIRK_SCHEMES = ('implicit_euler', 'crank_nicolson', 'sdirk3', 'sdirk21', 'dirk34', 'esdirk23', 'esdirk34')
 
 
+ADAPTIVE_DIRK_SCHEMES = ('sdirk21', 'dirk34', 'esdirk23', 'esdirk34')
+ROSENBROCK_SCHEMES = ('ros3p', 'ros3pw', 'rowdaind2', 'rodasp', 'rosi2p1')
+
+
+def embedded_tableau(name):
+    """``(A, err_order)`` of an embedded DIRK pair in the reference's layout: ``A`` of shape ``(s + 2, s)``, its first ``s + 1``
+    rows the main rule of ``dirk_tableau(name)``, the last row the weights ``b_hat`` of the embedded rule; ``err_order`` the
+    exponent of the step controller.  Schemes: ``ADAPTIVE_DIRK_SCHEMES``."""
+    if name not in ADAPTIVE_DIRK_SCHEMES:
+        raise ValueError('scheme %r has no embedded rule: one of %s' % (name, ', '.join(ADAPTIVE_DIRK_SCHEMES + ROSENBROCK_SCHEMES)))
+    A = dirk_tableau(name)
+    if name == 'sdirk21':
+        ah = 2 - 5 / 4 * math.sqrt(2)
+        b_hat, order = [1 - ah, ah], 1
+    elif name == 'dirk34':
+        b_hat, order = list(A[2]), 2                   # (the third stage row; its last weight is 0)
+    elif name == 'esdirk23':
+        g = A[1, 1]
+        b_hat, order = [(6 * g - 1) / (12 * g), 1 / (12 * g * (1 - 2 * g)), (1 - 3 * g) / (3 * (1 - 2 * g))], 3
+    else:
+        b_hat, order = [0.15702489786032493710, 0.11733044137043884870, 0.61667803039212146434, 0.10896663037711474985], 4
+    return np.vstack([A, b_hat]), order
+
+
+def _rosenbrock(name):
+    """(strict lower triangle of A, lower triangle of Gamma below the diagonal, gamma, b, b_hat, err_order), rows listed"""
+    if name == 'ros3p':
+        return ([[1.0], [1.0, 0.0]], [[-1.0], [-0.7886751347, -1.077350269]], 0.7886751347,
+                [2 / 3, 0, 1 / 3], [1 / 3, 1 / 3, 1 / 3], 2)
+    if name == 'ros3pw':
+        return ([[1.5773502691896257e+00], [5.0000000000000000e-01, 0.0]],
+                [[-1.5773502691896257e+00], [-6.7075317547305480e-01, -1.7075317547305482e-01]], 7.8867513459481287e-01,
+                [1.0566243270259355e-01, 4.9038105676657971e-02, 8.4529946162074843e-01],
+                [-1.7863279495408180e-01, 3.3333333333333333e-01, 8.4529946162074843e-01], 2)
+    if name == 'rowdaind2':
+        return ([[0.5], [0.28, 0.72], [0.28, 0.72, 0.0]],
+                [[-1.121794871794876e-1], [2.54, -3.84], [29.0 / 75.0, -0.72, 1.0 / 30.0]], 0.3,
+                [2.0 / 3.0, 0.0, 1.0 / 30.0, 0.3],
+                [4.799002800355166e-1, 5.176203811215082e-1, 2.479338842975209e-3, 0.0], 2)
+    if name == 'rosi2p1':
+        return ([[5.0000000000000000e-1], [5.5729261836499822e-1, 1.9270738163500176e-1],
+                 [-3.0084516445435860e-1, 1.8995581939026787e+0, -5.9871302944832006e-1]],
+                [[-5.0000000000000000e-1], [-6.4492162993321323e-1, 6.3491801247597734e-2],
+                 [9.3606009252719842e-3, -2.5462058718013519e-1, -3.2645441930944352e-1]], 4.3586652150845900e-1,
+                [5.2900072579103834e-2, 1.3492662311920438e+0, -9.1013275270050265e-1, 5.0796644892935516e-1],
+                [1.4974465479289098e-1, 7.0051069041421810e-1, 0.0, 1.4974465479289098e-1], 2)
+    return None
+
+
+def _lower(rows, s, diag=0.0):
+    T = np.zeros((s, s))
+    for i, row in enumerate(rows):
+        T[i + 1, :len(row)] = row
+    np.fill_diagonal(T, diag)
+    return T
+
+
+def rosenbrock_tableau(name):
+    """``(A, Gamma, b, b_hat, err_order)`` of a Rosenbrock method as the reference runs it: ``A`` strictly lower triangular,
+    ``Gamma`` lower triangular with the constant diagonal ``gamma``, the weights ``b`` and those of the embedded rule ``b_hat``.
+    Schemes: ``ROSENBROCK_SCHEMES`` (Lang and Teleaga; RODASP of Steinebach).  For an affine right-hand side stage 2 of
+    ``ros3p`` and ``ros3pw`` equals stage 1 and their estimate vanishes."""
+    if name == 'rodasp':
+        # given through B = A + Gamma, as in the literature
+        gamma = 0.25
+        A = _lower([[0.75], [8.6120400814152190E-2, 0.1238795991858478],
+                    [0.7749345355073236, 0.1492651549508680, -0.2941996904581916],
+                    [5.308746682646142, 1.330892140037269, -5.374137811655562, -0.2655010110278497],
+                    [-1.764437648774483, -0.4747565572063027, 2.369691846915802, 0.6195023590649829, 0.25]], 6)
+        b5 = [-1.764437648774483, -0.4747565572063027, 2.369691846915802, 0.6195023590649829]
+        b6 = [-8.0368370789113464E-2, -5.6490613592447572E-2, 0.4882856300427991, 0.5057162114816189, -0.1071428571428569]
+        B = _lower([[0.0], [-0.049392, -0.014112], [-0.4820494693877561, -0.1008795555555556, 0.9267290249433117], b5, b6], 6, gamma)
+        return A, B - A, np.array(b6 + [gamma]), np.array(b5 + [gamma, 0.0]), 3
+    t = _rosenbrock(name) if isinstance(name, str) else None
+    if t is None:
+        raise ValueError('unknown Rosenbrock scheme %r: one of %s' % (name, ', '.join(ROSENBROCK_SCHEMES)))
+    a, g, gamma, b, b_hat, order = t
+    s = len(b)
+    return _lower(a, s), _lower(g, s, gamma), np.array(b, dtype=np.float64), np.array(b_hat, dtype=np.float64), order
+
+
+def _stepper(scheme, need_estimate):
+    """The scheme of a stepping session: dict(family, name, stages, A, Gamma, b, b_hat, err_order, gamma).  `scheme`: a name of
+    DIRK_SCHEMES or ROSENBROCK_SCHEMES.  ValueError for an unknown name (as dirk_tableau) or, with `need_estimate`, for a scheme
+    without an embedded rule."""
+    if isinstance(scheme, str) and scheme in ROSENBROCK_SCHEMES:
+        A, G, b, b_hat, order = rosenbrock_tableau(scheme)
+        return dict(family=_lib.IGX_STEPPER_ROSENBROCK, name=scheme, stages=len(b), A=np.ascontiguousarray(A),
+                    Gamma=np.ascontiguousarray(G), b=b, b_hat=b_hat, err_order=order, gamma=float(G[0, 0]))
+    name, A, gamma = _scheme(scheme)
+    if name in ADAPTIVE_DIRK_SCHEMES:
+        E, order = embedded_tableau(name)
+        b_hat = np.ascontiguousarray(E[-1])
+    elif need_estimate:
+        raise ValueError('scheme %r has no embedded rule to choose the step by (tol given): one of %s'
+                         % (scheme if name is None else name, ', '.join(ADAPTIVE_DIRK_SCHEMES + ROSENBROCK_SCHEMES)))
+    else:
+        b_hat, order = None, None
+    return dict(family=_lib.IGX_STEPPER_DIRK, name=name, stages=A.shape[1], A=np.ascontiguousarray(A), Gamma=None,
+                b=np.ascontiguousarray(A[-1]), b_hat=b_hat, err_order=order, gamma=gamma)
+
+
+def next_step(tau, r, converged, step_factor, err_order):
+    """The reference's step controller (pyiga/solvers.py:505-531): ``(accepted, next tau)`` after an attempt with step `tau` whose
+    error ratio is `r`.  ``r == 0`` counts as 1e-15; accepted iff ``r <= 1``; the step changes by
+    ``min(5, max(0.2, step_factor r^(-1/err_order)))`` whether accepted or not.  An attempt whose solves did not converge is
+    rejected and halves the step."""
+    if not converged:
+        return False, tau * 0.5
+    if r == 0:
+        r = 1e-15
+    fac = step_factor * r ** (-1 / err_order)
+    fac = min(5.0, max(0.2, fac))
+    return bool(r <= 1), tau * fac
+
+
 def dirk_tableau(name):
     """The tableau ``A`` of the named DIRK scheme in the reference's layout: shape ``(s + 1, s)``, the last row ``b`` (main rules:
     no embedded ``b_hat`` row).  Schemes: ``DIRK_SCHEMES``."""
@@ -1188,6 +1308,7 @@ class ParabolicSystem(_DeviceSystem):
         _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_MASS), 'igx_solver_take_values')
         self._step = None                                        # (tau, tableau) of the C on the device
         self._eig = None
+        self._step_precond = None                                # the preconditioner of the stepping session on the device
 
     def _drop_owner(self):
         if getattr(self, 'patch', None) is not None and self._own_patch:
@@ -1236,6 +1357,12 @@ class ParabolicSystem(_DeviceSystem):
         _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, _lib.IGX_KRON_SUM),
                    'igx_solver_set_precond')
 
+    def set_precond(self, precond):
+        key = precond if precond is not None else 'none'
+        if key in self.PRECONDS and key != self._precond:
+            self._step_precond = None                            # (igx_solver_set_precond replaces the session's factors)
+        _DeviceSystem.set_precond(self, precond)
+
     def integrate(self, u0, tau, t_end, scheme='sdirk3', t0=0.0, tol=1e-10, maxiter=1000, precond='auto', save_every=1,
                   check_every=1, timed=False):
         """``ceil((t_end - t0) / tau)`` steps of `scheme` (a name of ``DIRK_SCHEMES`` or a tableau) from `u0` (a vector, or a
@@ -1247,7 +1374,12 @@ class ParabolicSystem(_DeviceSystem):
         (every `save_every`-th step and always the last; the last time may pass `t_end`), ``solutions`` the full vectors
         (Dirichlet values included), ``solutions[0] = u0``.  A stage solve that does not converge within `maxiter` iterations
         ends the integration: the states up to the last completed step are returned (a RuntimeWarning says so, and
-        ``info['converged']`` is False).  ``info``: the fields of ``igx_dirk_info`` and the iterations of every stage."""
+        ``info['converged']`` is False).  ``info``: the fields of ``igx_dirk_info`` and the iterations of every stage.
+
+        A name of ``ROSENBROCK_SCHEMES`` runs the constant-step Rosenbrock method (``integrate_adaptive`` with ``tol=None``)."""
+        if isinstance(scheme, str) and scheme in ROSENBROCK_SCHEMES:
+            return self.integrate_adaptive(u0, tau, t_end, None, scheme=scheme, t0=t0, solve_tol=tol, maxiter=maxiter,
+                                           precond=precond, save_every=save_every, check_every=check_every, timed=timed)
         name, A, gamma = _scheme(scheme)
         tau, t0, t_end = float(tau), float(t0), float(t_end)
         if not (tau > 0 and math.isfinite(tau)):
@@ -1297,3 +1429,179 @@ class ParabolicSystem(_DeviceSystem):
             warnings.warn('ParabolicSystem.integrate: a stage solve of step %d did not converge within %d iterations; returning '
                           'the %d steps completed' % (steps + 1, maxiter, steps), RuntimeWarning, stacklevel=2)
         return [t0] + [t0 + k * tau for k in kept], [x0] + [saved[j] for j in range(len(kept))]
+
+    def _check_precond(self, precond):
+        key = self.default_precond if precond == 'auto' else precond
+        if (key if key is not None else 'none') not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        if key == 'kron' and self.box is None:
+            raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch (or none)")
+        return key if key is not None else 'none'
+
+    def _set_step_precond(self, h, key):
+        """The session's preconditioner: for 'kron' the factors U_k and the RAW eigenvalues go up once; the device rescales
+        them per step and for the mass solve."""
+        if self._step_precond == key:
+            return
+        lib = _lib.load()
+        if key == 'kron':
+            if self._eig is None:
+                self._eig = fastdiag_factors(self.kvs, self.box[0], self.box[1], True)[:2]
+            U, lam = self._eig
+            lo = (C.c_int32 * 3)(*self.box[0])
+            hi = (C.c_int32 * 3)(*self.box[1])
+            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
+            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+            _lib.check(lib.igx_solver_set_step_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp), 'igx_solver_set_step_precond')
+        else:
+            _lib.check(lib.igx_solver_set_step_precond(h, self.PRECONDS[key], None, None, None, None), 'igx_solver_set_step_precond')
+        self._step_precond = key
+
+    def begin_steps(self, u0, scheme, precond='auto', need_estimate=True):
+        """Starts a stepping session (``igx_solver_set_stepper``, ``igx_solver_set_step_precond``, ``igx_solver_step_begin``) from
+        `u0` with the scheme `scheme`; returns ``(stepper, x0)``.  ``attempt_step`` / ``accept_step`` / ``step_state`` then run
+        it; ``integrate_adaptive`` is the driver built on them."""
+        st = _stepper(scheme, need_estimate)
+        key = self._check_precond(precond)
+        h = self._live()
+        if callable(u0):
+            from . import approx
+            u0 = approx.project_L2(self.kvs, u0, f_physical=True, geo=self.geo)
+        x0 = np.array(u0, dtype=np.float64).ravel()
+        if x0.size != self.n:
+            raise ValueError('u0 has %d entries, the space %d' % (x0.size, self.n))
+        x0[self.bc_indices] = self.bc_values
+        lib = _lib.load()
+        # the session forms its own C and preconditioner data: what set_scheme / set_precond left is void after it
+        self._step = None
+        self._precond = None
+        opt = lambda a: None if a is None else _lib.dptr(a)
+        _lib.check(lib.igx_solver_set_stepper(h, st['family'], st['stages'], _lib.dptr(st['A']), opt(st['Gamma']),
+                                              _lib.dptr(st['b']), opt(st['b_hat'])), 'igx_solver_set_stepper')
+        self._set_step_precond(h, key)
+        _lib.check(lib.igx_solver_step_begin(h, _lib.dptr(self.b), _lib.dptr(self.bc_values), _lib.dptr(x0)), 'igx_solver_step_begin')
+        return st, x0
+
+    def attempt_step(self, tau, err_tol=0.0, solve_tol=1e-10, maxiter=1000, check_every=1, timed=False):
+        """One attempt of the session with the step `tau` (``igx_solver_step_attempt``); returns the ``StepInfo``."""
+        info = _lib.StepInfo()
+        _lib.check(_lib.load().igx_solver_step_attempt(self._live(), float(tau), float(err_tol), float(solve_tol), int(maxiter),
+                                                       int(check_every), 1 if timed else 0, C.byref(info)), 'igx_solver_step_attempt')
+        return info
+
+    def accept_step(self):
+        _lib.check(_lib.load().igx_solver_step_accept(self._live()), 'igx_solver_step_accept')
+
+    def step_state(self, candidate=False):
+        """The state of the session, or the candidate of the last attempt, as a full vector."""
+        out = np.empty(self.n)
+        _lib.check(_lib.load().igx_solver_step_state(self._live(), _lib.IGX_STEP_CANDIDATE if candidate else _lib.IGX_STEP_STATE,
+                                                     _lib.dptr(out)), 'igx_solver_step_state')
+        return out
+
+    def error_ratio(self, vectors, coef, x, tol, offset=0):
+        """``|| (sum_k coef[k] vectors[k]) / (tol + tol |x|) ||_2 / sqrt(n_free)`` over the free dofs by ``k_err_norm`` alone
+        (``igx_solver_error_ratio_d``; at most ``_lib.COMB_MAX`` vectors).  `offset`: every vector starts that many doubles into
+        its device buffer (an odd number: no 16-byte alignment, the kernel's scalar path)."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64).ravel()
+        if not 1 <= len(vectors) <= _lib.COMB_MAX or coef.size != len(vectors):
+            raise ValueError('1 to %d vectors and as many coefficients' % _lib.COMB_MAX)
+        h = self._live()
+        offset = int(offset)
+        host = [np.asarray(v, dtype=np.float64).ravel() for v in list(vectors) + [x]]
+        if offset < 0 or any(v.size != self.n for v in host):
+            raise ValueError('vectors of the wrong size')
+        dev = [DeviceArray.from_host(self._ctx, np.concatenate([np.zeros(offset), v])) for v in host]
+        at = [d.ptr + 8 * offset for d in dev]
+        ptrs = (C.c_void_p * len(vectors))(*at[:-1])
+        r = C.c_double()
+        _lib.check(_lib.load().igx_solver_error_ratio_d(h, len(vectors), _lib.dptr(coef), ptrs, at[-1], float(tol),
+                                                        C.byref(r)), 'igx_solver_error_ratio_d')
+        return r.value
+
+    def integrate_adaptive(self, u0, tau0, t_end, tol, scheme='esdirk23', t0=0.0, step_factor=0.9, solve_tol=1e-10, maxiter=1000,
+                           precond='auto', save_every=1, max_attempts=10000, check_every=1, timed=False):
+        """Integrates from `t0` until ``t >= t_end`` with steps chosen by the embedded rule of `scheme` (a name of
+        ``ADAPTIVE_DIRK_SCHEMES`` or ``ROSENBROCK_SCHEMES``), as the reference's adaptive methods (pyiga/solvers.py:475-534): with
+        ``d = tol + tol |x|`` and ``r = ||(x_est - x_new) / d||_2 / sqrt(n_free)`` an attempt is accepted iff ``r <= 1`` and the
+        step changes by ``min(5, max(0.2, step_factor r^(-1/err_order)))`` after every attempt (``next_step``); an attempt one of
+        whose solves does not converge within `maxiter` iterations is rejected and halves the step.  The last step may pass
+        `t_end`.  ``tol=None``: constant steps of `tau0` (any name of ``DIRK_SCHEMES`` or ``ROSENBROCK_SCHEMES``).
+
+        Every solve runs to ``||r|| <= solve_tol ||r0||``, ``r0`` the residual of its start value.  That is the right-hand side
+        but for the DIRK stages, which start from the previous stage: they are solved for their increment (as the reference's
+        Newton measures its ``rtol``), also with ``tol=None``, where ``integrate`` with the same scheme stops relative to the
+        right-hand side.
+
+        Returns ``(times, solutions)`` of the accepted steps kept (every `save_every`-th and always the last; ``solutions[0] =
+        u0``).  At most `max_attempts` attempts are made: when they run out (or a constant step does not converge) the states so
+        far are returned, a RuntimeWarning says so and ``info['converged']`` is False.  ``info``: per attempt ``tau``, ``r``,
+        ``accepted``, ``stage_iterations``, ``mass_iterations``; the counts ``attempts``, ``rejections``, ``reformations``; the
+        phase times (ms, summed; all but ``total_ms`` and ``axpby_ms`` need `timed`)."""
+        tau0, t0, t_end = float(tau0), float(t0), float(t_end)
+        if not (tau0 > 0 and math.isfinite(tau0)):
+            raise ValueError('tau0 must be positive and finite, not %r' % (tau0,))
+        if not t_end > t0:
+            raise ValueError('t_end (%r) must be greater than t0 (%r)' % (t_end, t0))
+        if tol is not None and not tol > 0:
+            raise ValueError('tol must be positive (or None for constant steps), not %r' % (tol,))
+        if not 0 < step_factor <= 1:
+            raise ValueError('step_factor must lie in (0, 1], not %r' % (step_factor,))
+        save_every, max_attempts = int(save_every), int(max_attempts)
+        if save_every < 1:
+            raise ValueError('save_every must be >= 1')
+        if max_attempts < 1:
+            raise ValueError('max_attempts must be >= 1')
+        st, x0 = self.begin_steps(u0, scheme, precond, need_estimate=tol is not None)
+        times, sols = [t0], [x0]
+        log = dict(tau=[], r=[], accepted=[], stage_iterations=[], mass_iterations=[])
+        phases = dict.fromkeys(('axpby_ms', 'spmv_ms', 'combine_ms', 'solve_ms', 'mass_ms', 'err_ms', 'total_ms'), 0.0)
+        reformations = accepted = 0
+        last_kept = True
+        nsteps = int(math.ceil((t_end - t0) / tau0)) if tol is None else None
+        t, tau, converged, failed = t0, tau0, True, None
+        while (accepted < nsteps) if tol is None else (t < t_end):
+            if tol is not None and len(log['tau']) >= max_attempts:
+                converged, failed = False, 'the %d attempts allowed ran out at t = %g' % (max_attempts, t)
+                break
+            info = self.attempt_step(tau, 0.0 if tol is None else tol, solve_tol, maxiter, check_every, timed)
+            for k in phases:
+                phases[k] += getattr(info, k)
+            reformations += info.reformed
+            ok = bool(info.converged)
+            if tol is None:
+                accept, tau_next, r = ok, tau, 0.0
+            else:
+                r = info.r if ok else float('nan')
+                accept, tau_next = next_step(tau, info.r, ok, step_factor, st['err_order'])
+            log['tau'].append(tau)
+            log['r'].append(r)
+            log['accepted'].append(accept)
+            log['stage_iterations'].append(list(info.stage_iterations)[:st['stages']])
+            log['mass_iterations'].append(info.mass_iterations)
+            if tol is None and not ok:
+                converged, failed = False, 'a solve of step %d did not converge within %d iterations' % (accepted + 1, maxiter)
+                break
+            if accept:
+                self.accept_step()
+                accepted += 1
+                t = t0 + accepted * tau0 if tol is None else t + tau
+                last_kept = accepted % save_every == 0
+                if last_kept:
+                    times.append(t)
+                    sols.append(self.step_state())
+            tau = tau_next
+        if not last_kept:
+            times.append(t)
+            sols.append(self.step_state())
+        reason = _lib.load().igx_solver_last_breakdown(self.handle)
+        self.info = dict(phases, converged=converged, scheme=st['name'], gamma=st['gamma'], tol=tol, attempts=len(log['tau']),
+                         rejections=len(log['tau']) - accepted, accepted_steps=accepted, reformations=reformations,
+                         tau=np.array(log['tau']), r=np.array(log['r']), accepted=np.array(log['accepted'], dtype=bool),
+                         stage_iterations=np.array(log['stage_iterations'], dtype=np.int32).reshape(-1, st['stages']),
+                         mass_iterations=np.array(log['mass_iterations'], dtype=np.int32), precond=self._step_precond,
+                         method=self.method, breakdown=_lib.BREAKDOWNS.get(reason, reason))
+        if not converged:
+            warnings.warn('ParabolicSystem.integrate_adaptive: %s; returning the %d steps completed' % (failed, accepted),
+                          RuntimeWarning, stacklevel=2)
+        return times, sols
