@@ -132,7 +132,7 @@ typedef struct {
 typedef struct {
     float total_ms;
     float fields_ms, stage0_ms, stage1_ms, final_ms, entry_ms;
-    int32_t algo_used;                 /* IGX_ALGO_ENTRYWISE / IGX_ALGO_SUMFACT; 3 after igx_load_vector (total_ms = its contractions) */
+    int32_t algo_used;                 /* IGX_ALGO_ENTRYWISE / IGX_ALGO_SUMFACT; 3 after igx_load_vector (total_ms = its contractions), 4 / 5: igx_patch_eval_spline_d / _exprs_inputs_d */
     int32_t n_launches;
 } igx_timing;
 
@@ -332,6 +332,28 @@ int igx_load_vector_expr(igx_patch *patch, const char *expr, int parametric, dou
 /* Host only: compile that kernel (P = degree + 1 of the last two axes, npass = max(2, ceil(dofs of the last axis / 64)) <= 4). */
 int igx_rtc_compile_load_vector(int P, int npass, int parametric, const char *expr, const char *arch, char *path_out, int path_len, int *cache_hit);
 
+/* --- fields evaluated on the device as inputs of form coefficients (Newton's method) ------------------
+   A spline of the patch's OWN space (same knot vectors and degrees), given by its dofs in device memory (N0 x N1 [x N2]
+   doubles, C order), at the resident Gauss points.  d_out[0] receives the value; with want_grad != 0, d_out[1 .. dim] receive
+   the PHYSICAL gradient in the jet order of the form tables (D_1 = d/dx, x belonging to the last grid axis).  Every output is a
+   device array over the resident slab (igx_patch_gauss_slab planes x G1 [x G2], C order: the layout of igx_load_vector_d and
+   igx_patch_set_form_d).  One pass over the dofs (pyiga/bspline.py:880-921, BSplineFunc.grid_eval / grid_jacobian, with the
+   coefficients resident).  A row slab or a span box: IGX_ERR_UNSUPPORTED; a geometry given as Jacobian arrays serves
+   want_grad = 0 only (IGX_ERR_UNSUPPORTED otherwise).  igx_last_timing: total_ms = the kernels, algo_used = 4. */
+int igx_patch_eval_spline_d(igx_patch *patch, const double *d_coeffs, int want_grad, double *const d_out[4]);
+/* igx_patch_set_form_expr's coefficient kernel with m <= 16 further doubles f0 .. f{m-1} in scope, loaded from the device arrays
+   d_in[0 .. m) at the thread's resident Gauss point:  d_out[k * npts + i] = expr_k(x, y, z, pi, f0, ..) for the n expressions
+   (npts = resident points).  Same grammar, same refusals and the same on-disk cache (m is part of the generated source).  With a
+   geometry given as Jacobian arrays x, y, z are the parametric coordinates.  The arrays of igx_patch_eval_spline_d go in, the
+   result goes to igx_patch_set_form_d / igx_load_vector_jet_d (pyiga/codegen/cython.py:673-701 evaluates updatable inputs in
+   the field loop of the generated assembler).  igx_last_timing: total_ms = the kernel, algo_used = 5. */
+int igx_patch_eval_exprs_inputs_d(igx_patch *patch, int n, const char *const *expr, int m, const double *const *d_in, double *d_out, int *cache_hit);
+/* Host only: compile that kernel for `arch` (as igx_rtc_compile_form). */
+int igx_rtc_compile_exprs_inputs(int n, const char *const *expr, int m, const char *arch, char *path_out, int path_len, int *cache_hit);
+/* igx_load_vector_jet with the coefficients F_r on the RESIDENT Gauss slab in device memory (d_coef[r] or NULL) and the result
+   (row0_hi-row0_lo) x N1 [x N2] doubles left in device memory.  Replaces the IGX_FORM coefficients of the patch. */
+int igx_load_vector_jet_d(igx_patch *patch, const double *const d_coef[4], double *d_out);
+
 /* Precomputed fields (W or upper triangle of B) of the owned Gauss slab: out has shape
    (F, G0_local, G1[, G2]) (structure-of-arrays).  For tests of precompute_fields. */
 int igx_fields(igx_patch *patch, int kind, double *out, int64_t *shape4);
@@ -450,6 +472,22 @@ int igx_solver_set_precond(igx_solver *solver, int precond, const int32_t *box_l
    IGX_ERR_UNSUPPORTED. */
 int igx_solver_set_schwarz(igx_solver *solver, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
                            const double *const *lam, int lam_mode);
+/* --- Newton's method on a scalar patch solver (igx_solver_create_general): iterate, residual and Jacobian
+   stay in device memory; any other solver: IGX_ERR_UNSUPPORTED -----------------------------------------------------------------
+   The caller knows the matrix of the solver's kind to be symmetric positive definite (a traced coefficient table that is
+   symmetric): igx_solver_set_method(IGX_METHOD_CG) is accepted from now on. */
+int igx_solver_declare_symmetric(igx_solver *solver);
+/* The patch's values of the solver's OWN kind were assembled again (a new Jacobian): the staleness check of the solves is passed
+   as before, and the diagonal of the Jacobi preconditioner, if that is the one selected, is gathered again.  Values of another
+   kind, or none: IGX_ERR_ARG as in igx_solver_solve. */
+int igx_solver_values_changed(igx_solver *solver);
+/* *norm = || R v ||_2 of the full-length device vector v, R the restriction to the free dofs.  One double comes back. */
+int igx_solver_masked_norm_d(igx_solver *solver, const double *d_v, double *norm);
+/* One Newton update  x -= R^T (R J R^T)^-1 R F  with the full-length device vectors d_F and d_x and the matrix J the patch holds:
+   the linear solve starts from zero with zero fixed values, to ||r|| <= tol ||R F|| (the solver's method and preconditioner), and
+   the fixed entries of d_x are left as they are (pyiga/solvers.py:335-361, the step of newton()). */
+int igx_solver_newton_update_d(igx_solver *solver, const double *d_F, double *d_x, double tol, int maxiter, int check_every,
+                               igx_solve_info *info);
 /* --- Geometric multigrid over a hierarchy of multipatch solvers (IGX_PRECOND_MG) -----------------------
    A hierarchy is a chain of multipatch solvers, the finest first, each over the sums of the same problem on a coarser, nested
    space with the same sides fixed.  Every solver of the chain gets a smoother (all but the coarsest) and either the next coarser

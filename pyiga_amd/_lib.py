@@ -189,6 +189,10 @@ SYMBOLS = [
     ('igx_patch_set_coeff_affine', C.c_int, [C.c_void_p, C.c_double * 4]),
     ('igx_patch_set_form_d', C.c_int, [C.c_void_p, C.c_void_p * 16]),
     ('igx_patch_last_path', C.c_int, [C.c_void_p]),
+    ('igx_patch_eval_spline_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p * 4]),
+    ('igx_patch_eval_exprs_inputs_d', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int)]),
+    ('igx_rtc_compile_exprs_inputs', C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
+    ('igx_load_vector_jet_d', C.c_int, [C.c_void_p, C.c_void_p * 4, C.c_void_p]),
     ('igx_patch_gauss_slab', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ('igx_dev_alloc', C.c_void_p, [C.c_void_p, C.c_size_t]),
     ('igx_dev_free', None, [C.c_void_p, C.c_void_p]),
@@ -228,6 +232,10 @@ SYMBOLS = [
     ('igx_solver_precond_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_spmv_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('igx_solver_solve', C.c_int, [C.c_void_p, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(SolveInfo)]),
+    ('igx_solver_declare_symmetric', C.c_int, [C.c_void_p]),
+    ('igx_solver_values_changed', C.c_int, [C.c_void_p]),
+    ('igx_solver_masked_norm_d', C.c_int, [C.c_void_p, C.c_void_p, _dp]),
+    ('igx_solver_newton_update_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.POINTER(SolveInfo)]),
     ('igx_solver_create_parabolic', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
     ('igx_solver_take_values', C.c_int, [C.c_void_p, C.c_int]),
     ('igx_solver_set_dirk', C.c_int, [C.c_void_p, C.c_int, _dp, C.c_double]),

@@ -382,12 +382,34 @@ _KNOWN_FORMS = {
 }
 
 
+def _check_spline_inputs(problem, kvs, args, bfuns, boundary, surface):
+    """Spline functions among the inputs of a form string (pyiga/vform.py:1791-1802) are served for scalar volume forms in the
+    first-order jets of u and v; the cases that never reach the general assemblers are refused here, before anything is created
+    on the device, with a message that says which case it is (second or parametric derivatives: the assemblers trace the form
+    before they create their patch and refuse there)."""
+    from . import forms
+    spl = {k: v for k, v in args.items() if k != 'geo' and forms.is_spline_input(v)}
+    if not spl:
+        return
+    for name, val in spl.items():
+        forms.check_spline_input(name, val)
+    if bfuns is not None:
+        raise NotImplementedError('spline-function inputs together with bfuns= (vector-valued or custom basis functions) are not supported')
+    if boundary is not None or surface:
+        raise NotImplementedError('spline-function inputs in boundary and surface forms are not supported')
+    d = len(kvs)
+    if d not in (2, 3):
+        raise NotImplementedError('spline-function inputs are supported on 2D and 3D patches')
+
+
 def instantiate_assembler(problem, kvs, args, bfuns=None, boundary=None):
     """Assembler object for `problem`.  The reference compiles arbitrary form strings at run time
     (vform -> Cython -> gcc).  Here the three built-in forms map to their hand-written kernels, any other
     3D scalar form in u, v, grad, inner, dot goes through the general device form (``pyiga_amd.forms`` ->
     ``IGX_FORM``); assembler classes and objects are accepted as in the reference."""
     surface = isinstance(problem, str) and 'geo' in args and getattr(args['geo'], 'dim', None) == len(tuple(kvs)) + 1
+    if isinstance(problem, str):
+        _check_spline_inputs(problem, tuple(kvs), args, bfuns, boundary, surface)
     if isinstance(problem, str) and (bfuns is not None or boundary is not None or surface):
         # vector-valued basis functions and/or a boundary integral (pyiga/vform.py:1822-1845, pyiga/assemble.py:929-934)
         from .form_assemblers import FormAssembler
@@ -414,6 +436,8 @@ def instantiate_assembler(problem, kvs, args, bfuns=None, boundary=None):
             try:
                 return cls(kvs, args['geo'], problem, inputs=args)
             except NotImplementedError:
+                if any(forms.is_spline_input(v) for k, v in args.items() if k != 'geo'):
+                    raise
                 # second derivatives / parametric derivatives: parametric jet form assembled in passes (pyiga_amd.pforms)
                 cls = assemblers.ParametricFormAssembler2D if len(kvs) == 2 else assemblers.ParametricFormAssembler3D
                 return cls(kvs, args['geo'], problem, inputs=args)
@@ -448,7 +472,9 @@ class Assembler:
     ``Assembler(problem, kvs, geo=..., updatable=['geo'])``, then ``assemble(geo=new_geo)`` or ``update(geo=new_geo)`` +
     ``assemble()``.  `updatable` names must be inputs of the problem (``ValueError``), only they may be updated
     (``RuntimeError``).  The device assembler is instantiated again when an input changes: the per-patch set-up is a few
-    milliseconds, everything geometry-dependent has to be recomputed anyway."""
+    milliseconds, everything geometry-dependent has to be recomputed anyway.  The exception are scalar spline
+    functions among the inputs of a form string (``updatable=['w']``, the iterate of Newton's method): their dofs go up, their
+    fields are evaluated again on the device, and the assembler, its patch and the compiled kernel stay."""
 
     def __init__(self, problem, kvs, args=None, bfuns=None, boundary=None, symmetric=False, updatable=(), **kwargs):
         self._args = dict(args or {})
@@ -456,10 +482,12 @@ class Assembler:
         self._problem, self._kvs, self._bfuns, self._boundary = problem, kvs, bfuns, boundary
         self.symmetric = bool(symmetric)
         self.updatable = tuple(updatable)
-        self.asm = instantiate_assembler(problem, kvs, self._args, bfuns, boundary)
-        inputs = self._input_names()
-        if not all(name in inputs for name in self.updatable):
+        # (the inputs of a form string are known from its text: checked before anything is created on the device)
+        self.asm = None if isinstance(problem, str) else instantiate_assembler(problem, kvs, self._args, bfuns, boundary)
+        if not all(name in self._input_names() for name in self.updatable):
             raise ValueError('Assembler received an updatable argument which is not an assembler input')
+        if self.asm is None:
+            self.asm = instantiate_assembler(problem, kvs, self._args, bfuns, boundary)
 
     def _input_names(self):
         if isinstance(self._problem, str):
@@ -472,6 +500,12 @@ class Assembler:
         if not all(name in self.updatable for name in kwargs):
             raise RuntimeError('update() received an argument which was not specified as updatable')
         self._args.update(kwargs)
+        from . import forms
+        if kwargs and getattr(self.asm, 'fields', None) is not None and all(forms.is_spline_input(v) and k in self.asm.fields.ptrs for k, v in kwargs.items()):
+            # spline-function inputs of a traced form: only their dofs go up and the fields are evaluated again -- the device
+            # assembler, its patch and the compiled coefficient kernel stay
+            self.asm.update_fields(**kwargs)
+            return
         self.asm = instantiate_assembler(self._problem, self._kvs, self._args, self._bfuns, self._boundary)
 
     def assemble(self, format='csr', layout='blocked', **upd_fields):

@@ -113,7 +113,7 @@ class DevicePatch:
 
     def close(self):
         if getattr(self, 'handle', None):
-            for name in ('_d_f', '_d_vec', '_d_ij', '_d_val'):
+            for name in sorted(set(('_d_f', '_d_vec', '_d_ij', '_d_val')) | getattr(self, '_buf_names', set())):
                 self._dev_free(name)
             _lib.load().igx_patch_destroy(self.handle)
             self.handle = None
@@ -136,6 +136,9 @@ class DevicePatch:
         if not ptr:
             raise _lib.IgxError('igx_dev_alloc failed: ' + _lib.last_error())
         setattr(self, name, (ptr, nbytes))
+        if not hasattr(self, '_buf_names'):
+            self._buf_names = set()
+        self._buf_names.add(name)
         return ptr
 
     def resident_grid(self):
@@ -453,6 +456,99 @@ class DevicePatch:
         _lib.check(_lib.load().igx_load_vector_jet_expr(self.handle, arr, _lib.dptr(out), C.byref(hit)), 'igx_load_vector_jet_expr')
         return out
 
+    # -- fields evaluated on the device as inputs of form coefficients
+    def resident_points(self):
+        g0_lo, g0_n = self.gauss_slab()
+        return g0_n * int(np.prod(self.resident_grid()[1:]))
+
+    def upload_dofs(self, coeffs, buf='_d_dofs'):
+        """Dofs of a spline of the patch's own space (shape ndofs) to the device; returns the device pointer (kept by the patch
+        under the name `buf`)."""
+        c = _lib.f64(coeffs)
+        assert c.shape == self.ndofs, 'the coefficients do not belong to the space of the patch'
+        ptr = self._dev_buffer(buf, c.nbytes)
+        _lib.check(_lib.load().igx_dev_upload(self.ctx.handle, ptr, c.ctypes.data, c.nbytes), 'igx_dev_upload')
+        return ptr
+
+    def upload_fields(self, arrays, buf='_d_spl'):
+        """Arrays over the full Gauss grid to the device, their resident planes one after the other in the buffer `buf` (the
+        layout of eval_spline); returns the device pointers."""
+        npts = self.resident_points()
+        g0_lo, g0_n = self.gauss_slab()
+        G = tuple(self.info.ngauss[k] for k in range(self.dim))
+        base = self._dev_buffer(buf, 8 * npts * (1 + self.dim))
+        assert len(arrays) <= 1 + self.dim
+        for k, a in enumerate(arrays):
+            a = np.asarray(a, dtype=np.float64)
+            assert a.shape == G, 'field values have the wrong grid shape'
+            part = np.ascontiguousarray(a[g0_lo:g0_lo + g0_n])
+            _lib.check(_lib.load().igx_dev_upload(self.ctx.handle, base + 8 * npts * k, part.ctypes.data, part.nbytes), 'igx_dev_upload')
+        return [base + 8 * npts * k for k in range(len(arrays))]
+
+    def eval_spline(self, d_coeffs, want_grad=False, to_host=False, buf='_d_spl'):
+        """Value (and physical gradient, jet order: d/dx first, x belonging to the last grid axis) of the spline with the device
+        dof vector `d_coeffs` at the resident Gauss points (igx_patch_eval_spline_d).  Returns the device pointers of the 1 or
+        1 + dim arrays (kept by the patch, overwritten by the next call), or with to_host the arrays themselves."""
+        npts = self.resident_points()
+        n = 1 + self.dim if want_grad else 1
+        base = self._dev_buffer(buf, 8 * npts * (1 + self.dim))
+        ptrs = (C.c_void_p * 4)()
+        for k in range(n):
+            ptrs[k] = base + 8 * npts * k
+        _lib.check(_lib.load().igx_patch_eval_spline_d(self.handle, d_coeffs, 1 if want_grad else 0, ptrs), 'igx_patch_eval_spline_d')
+        if not to_host:
+            return [ptrs[k] for k in range(n)]
+        g0_lo, g0_n = self.gauss_slab()
+        out = np.empty((n, g0_n) + self.resident_grid()[1:])
+        _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, base, out.nbytes), 'igx_dev_download')
+        return out
+
+    def eval_exprs_inputs(self, exprs, d_inputs, to_host=False):
+        """out[k] = exprs[k](x, y, z, pi, f0, f1, ..) at the resident Gauss points, f_j read from the device array d_inputs[j]
+        (igx_patch_eval_exprs_inputs_d: compiled at run time, cached).  Returns (device pointers of the len(exprs) arrays, cache
+        hit); the arrays are kept by the patch and overwritten by the next call."""
+        npts = self.resident_points()
+        n, m = len(exprs), len(d_inputs)
+        base = self._dev_buffer('_d_tab', 8 * npts * n)
+        ex = (C.c_char_p * n)(*[e.encode() for e in exprs])
+        ins = (C.c_void_p * max(m, 1))(*d_inputs)
+        hit = C.c_int(0)
+        _lib.check(_lib.load().igx_patch_eval_exprs_inputs_d(self.handle, n, ex, m, ins, base, C.byref(hit)), 'igx_patch_eval_exprs_inputs_d')
+        if to_host:
+            g0_lo, g0_n = self.gauss_slab()
+            out = np.empty((n, g0_n) + self.resident_grid()[1:])
+            _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, base, out.nbytes), 'igx_dev_download')
+            return out, bool(hit.value)
+        return [base + 8 * npts * k for k in range(n)], bool(hit.value)
+
+    def set_form_resident(self, table):
+        """Physical coefficient table of IGX_FORM from device arrays over the resident slab: 4x4 nested list of device pointers or
+        None (igx_patch_set_form_d; the arrays are copied)."""
+        ptrs = (C.c_void_p * 16)()
+        for r in range(4):
+            for s in range(4):
+                if table[r][s] is not None:
+                    ptrs[4 * r + s] = table[r][s]
+        _lib.check(_lib.load().igx_patch_set_form_d(self.handle, ptrs), 'igx_patch_set_form_d')
+
+    def load_vector_jet_resident(self, jet, to_host=False):
+        """Load vector of  sum_r F_r D_r v  with F_r given as device arrays over the resident slab (pointers or None); the result
+        stays on the device (its pointer is returned) unless asked for (igx_load_vector_jet_d)."""
+        ptrs = (C.c_void_p * 4)()
+        for r, e in enumerate(jet):
+            if e is not None:
+                ptrs[r] = e
+        lo, hi = int(self.info.row_lo), int(self.info.row_hi)
+        nd = self.ndofs
+        n0 = (hi - lo) // int(np.prod(nd[1:]))
+        d_out = self._dev_buffer('_d_jet', 8 * n0 * int(np.prod(nd[1:])))
+        _lib.check(_lib.load().igx_load_vector_jet_d(self.handle, ptrs, d_out), 'igx_load_vector_jet_d')
+        if not to_host:
+            return d_out
+        out = np.empty((n0,) + nd[1:])
+        _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, d_out, out.nbytes), 'igx_dev_download')
+        return out
+
     def gauss(self, axis):
         """Gauss nodes and weights of an axis (of its part inside the bounding box, for an on-demand patch)."""
         n = self.info.ngauss[axis]
@@ -686,6 +782,69 @@ class ConvDiffAssembler3D(_DeviceAssembler):
         self.patch.set_coeff(vals)
 
 
+class FieldInputs:
+    """The spline-function inputs of traced forms on the device: per input the arrays of its value and,
+    if some form asks for it, its physical gradient at the resident Gauss points of `patch`.  A function of the patch's own space
+    goes up as its dofs and is evaluated there (igx_patch_eval_spline_d); a function of another space is evaluated with
+    grid_eval / grid_jacobian on the Gauss grid and uploaded (a correctness path).  Several assemblers of the same space and
+    geometry may read one FieldInputs: the arrays are plain device memory in the layout of the Gauss slab."""
+
+    def __init__(self, patch, geo):
+        self.patch, self.geo = patch, geo
+        self.ptrs, self.has_grad = {}, {}
+
+    def set(self, name, func, want_grad):
+        from . import forms
+        forms.check_spline_input(name, func)
+        patch, d = self.patch, self.patch.dim
+        want_grad = bool(want_grad or self.has_grad.get(name, False))
+        if tuple(func.kvs) == tuple(patch.kvs):
+            d_c = patch.upload_dofs(func.coeffs, buf='_d_dofs_' + name)
+            self.ptrs[name] = patch.eval_spline(d_c, want_grad, buf='_d_spl_' + name)
+        else:
+            grid = [patch.gauss(k)[0] for k in range(d)]
+            arrays = [func.grid_eval(grid)]
+            if want_grad:
+                gpar = np.asarray(func.grid_jacobian(grid))                         # d/d(xi_x, xi_y[, xi_z])
+                J = np.asarray(self.geo.grid_jacobian(grid))
+                gphys = np.linalg.solve(np.swapaxes(J, -1, -2), gpar[..., None])[..., 0]
+                arrays += [gphys[..., k] for k in range(d)]
+            self.ptrs[name] = patch.upload_fields(arrays, buf='_d_spl_' + name)
+        self.has_grad[name] = want_grad
+
+    def set_resident(self, name, d_coeffs, want_grad):
+        """The same from a dof vector that is in device memory already (the Newton iterate)."""
+        want_grad = bool(want_grad or self.has_grad.get(name, False))
+        self.ptrs[name] = self.patch.eval_spline(d_coeffs, want_grad, buf='_d_spl_' + name)
+        self.has_grad[name] = want_grad
+
+    def pointers(self, slots):
+        """Device pointers of the arrays f0, f1, .. of a traced form (symbolic.FieldSlots)."""
+        out = []
+        for name, comp in slots.slots:
+            assert comp == 0 or self.has_grad[name], 'the gradient of %r was not evaluated' % name
+            out.append(self.ptrs[name][comp])
+        return out
+
+
+def _spline_inputs(inputs):
+    from . import forms
+    return {k: v for k, v in (inputs or {}).items() if k != 'geo' and forms.is_spline_input(v)}
+
+
+def _trace_with_fields(what, trace, d):
+    """Run a tracing call with a fresh symbolic.FieldSlots; a form with spline inputs has no sampled path."""
+    from . import symbolic
+    slots = symbolic.FieldSlots(d)
+    try:
+        return trace(slots), slots
+    except NotImplementedError as e:
+        raise NotImplementedError('spline-function inputs are supported in forms of the first-order jets of u and v only '
+                                  '(no second or parametric derivatives, grad() of the input itself only): %s' % e)
+    except (symbolic.NotTraceable, TypeError) as e:
+        raise NotImplementedError('%s with spline-function inputs: every other coefficient must be traceable into a C expression (%s)' % (what, e))
+
+
 class _GeneralFormAssembler(_DeviceAssembler):
     """Scalar bilinear form in the first-order jets of u and v,
 
@@ -702,10 +861,32 @@ class _GeneralFormAssembler(_DeviceAssembler):
     _symmetric_form = False
     _kind = 'form'
 
-    def __init__(self, kvs0, geo, form, inputs=None, device=None, row0=None, bbox=None):
+    def __init__(self, kvs0, geo, form, inputs=None, device=None, row0=None, bbox=None, fields=None):
         from . import forms
-        super().__init__(kvs0, geo, device=device, row0=row0, bbox=bbox)
         d = self._dim
+        self.fields = None
+        spl = _spline_inputs(inputs) if isinstance(form, str) else {}
+        if spl:
+            # (0) spline functions among the inputs (an iterate: Newton's method): the table is traced with their values and
+            # gradients as the symbols f0, f1, .., evaluated on the device from arrays that are evaluated on the device.  No
+            # sampled path: checked and traced before anything is created on the device.
+            if bbox is not None or row0 is not None:
+                raise NotImplementedError('spline-function inputs: whole patches only (no row slab, no span box)')
+            if not isinstance(geo, (bspline.BSplineFunc, geometry.NurbsFunc)) or len(geo.kvs) != d:
+                raise NotImplementedError('spline-function inputs need a spline geometry')
+            self._exprs, self._slots = _trace_with_fields('a form', lambda sl: forms.symbolic_table(form, d, dict(inputs or {}), fields=sl), d)
+            if not any(e is not None for row in self._exprs for e in row):
+                raise ValueError('the form has no non-zero coefficient')
+        super().__init__(kvs0, geo, device=device, row0=row0, bbox=bbox)
+        if spl:
+            self.fields = fields if fields is not None else FieldInputs(self.patch, geo)
+            if fields is None:
+                for name, func in spl.items():
+                    self.fields.set(name, func, self._slots.wants_gradient(name))
+            self.table_mask = [[e is not None for e in row] for row in self._exprs]
+            self.compiled = True
+            self.apply_fields()
+            return
         # (1) the coefficients as generated device code: the string and its callable inputs are traced into C expressions in
         # the physical coordinates, one kernel per form is compiled at run time and cached (the reference: one compiled module
         # per form, pyiga/compile.py:58-73) -- nothing is sampled on the host.  IGX_FORM_RTC=0 switches it off.
@@ -752,6 +933,24 @@ class _GeneralFormAssembler(_DeviceAssembler):
                 full[r][s] = table[r][s]
         self.table_mask = [[e is not None for e in row] for row in table]
         self.patch.set_form(full)
+
+    def apply_fields(self):
+        """Evaluate the coefficient table from the current field arrays and make it the form of the patch (after the fields
+        changed, or after the patch's form was used for something else)."""
+        d = self._dim
+        where = [(r, s) for r in range(d + 1) for s in range(d + 1) if self._exprs[r][s] is not None]
+        ptrs, self.coeff_cache_hit = self.patch.eval_exprs_inputs([self._exprs[r][s] for r, s in where], self.fields.pointers(self._slots))
+        table = [[None] * 4 for _ in range(4)]
+        for (r, s), ptr in zip(where, ptrs):
+            table[r][s] = ptr
+        self.patch.set_form_resident(table)
+
+    def update_fields(self, **splines):
+        """New spline functions for inputs of the form: their dofs go up, the fields and the table are evaluated again; the patch,
+        its pattern and the compiled kernel stay."""
+        for name, func in splines.items():
+            self.fields.set(name, func, self._slots.wants_gradient(name))
+        self.apply_fields()
 
 
 class _ParametricFormAssembler(_DeviceAssembler):
@@ -903,10 +1102,31 @@ class _FormFunctionalAssembler(_FunctionalAssembler):
     run on the device."""
     _physical = True
 
-    def __init__(self, kvs0, geo, form, inputs=None, device=None, row0=None):
+    def __init__(self, kvs0, geo, form, inputs=None, device=None, row0=None, fields=None):
         from . import forms
+        self.fields = None
+        spl = _spline_inputs(inputs)
+        if spl:
+            # spline functions among the inputs: traced with the symbols f0, f1, .. (see _GeneralFormAssembler), before anything
+            # is created on the device; no sampled path
+            d = self._dim
+            if row0 is not None:
+                raise NotImplementedError('spline-function inputs: whole patches only (no row slab)')
+            if not isinstance(geo, (bspline.BSplineFunc, geometry.NurbsFunc)) or len(geo.kvs) != d:
+                raise NotImplementedError('spline-function inputs need a spline geometry')
+            from . import symbolic
+            traced, self._slots = _trace_with_fields('a functional', lambda sl: forms.functional_jet(form, (1,) * d, symbolic.coordinates(d), dict(inputs or {}), traced=True, fields=sl), d)
+            self._field_exprs = [None if e is None else symbolic.c_source(e) for e in traced]
         super().__init__(kvs0, geo, lambda *xyz: 0.0, device=device, row0=row0)
         self._form, self._inputs = form, inputs
+        if spl:
+            self.fields = fields if fields is not None else FieldInputs(self.patch, geo)
+            if fields is None:
+                for name, func in spl.items():
+                    self.fields.set(name, func, self._slots.wants_gradient(name))
+            self._jet_exprs, self._jet = None, [None if e is None else True for e in self._field_exprs]
+            self.coeff_cache_hit = None
+            return
         # the coefficients of v and grad(v) as generated device code when the string and its inputs can be traced (pyiga_amd.symbolic)
         self._jet_exprs = None
         if os.environ.get('IGX_FORM_RTC', '1') != '0' and isinstance(geo, (bspline.BSplineFunc, geometry.NurbsFunc)):
@@ -925,7 +1145,26 @@ class _FormFunctionalAssembler(_FunctionalAssembler):
         X = np.asarray(geo.grid_eval(list(self.gaussgrid)))
         self._jet = forms.functional_jet(form, G, X, dict(inputs or {}))
 
+    def assemble_vector_resident(self, to_host=False):
+        """The functional of a form with spline-function inputs from the current field arrays; the result stays on the device
+        (its pointer is returned) unless asked for.  Replaces the form of the patch."""
+        where = [r for r, e in enumerate(self._field_exprs) if e is not None]
+        if not where:
+            raise ValueError('the functional has no non-zero coefficient')
+        ptrs, self.coeff_cache_hit = self.patch.eval_exprs_inputs([self._field_exprs[r] for r in where], self.fields.pointers(self._slots))
+        jet = [None] * 4
+        for r, ptr in zip(where, ptrs):
+            jet[r] = ptr
+        return self.patch.load_vector_jet_resident(jet, to_host=to_host)
+
+    def update_fields(self, **splines):
+        for name, func in splines.items():
+            self.fields.set(name, func, self._slots.wants_gradient(name))
+        self._vector = None
+
     def assemble_vector(self):
+        if self._vector is None and self.fields is not None:
+            self._vector = self.assemble_vector_resident(to_host=True)
         if self._vector is None:
             if self._jet_exprs is not None and any(e is not None for e in self._jet_exprs):
                 try:

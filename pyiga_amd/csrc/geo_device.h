@@ -14,6 +14,76 @@ struct GeoView {
     int nc;               // components incl. weight
 };
 
+// geometry: homogeneous spline value + parametric derivatives at one grid point.
+// jac[c][k]: component c, derivative along GRID AXIS k (not yet reordered to x,y,z).
+
+template <int DIM>
+__device__ inline void eval_geo(const GeoView &gv, const int g[3], double val[MAX_COMP], double jac[MAX_COMP][3])
+{
+    const int nc = gv.nc;
+    for (int c = 0; c < MAX_COMP; ++c) {
+        val[c] = 0.0;
+        for (int k = 0; k < 3; ++k) jac[c][k] = 0.0;
+    }
+    const double *V0 = gv.V[0] + (size_t)g[0] * gv.P[0] * 2;
+    const double *V1 = gv.V[1] + (size_t)g[1] * gv.P[1] * 2;
+    const int f0 = gv.fa[0][g[0]], f1 = gv.fa[1][g[1]];
+    if (DIM == 2) {
+        for (int a0 = 0; a0 < gv.P[0]; ++a0) {
+            double sv[MAX_COMP], sd[MAX_COMP];
+            for (int c = 0; c < MAX_COMP; ++c) sv[c] = sd[c] = 0.0;
+            const double *row = gv.ctrl + ((size_t)(f0 + a0) * gv.N[1] + f1) * nc;
+            for (int a1 = 0; a1 < gv.P[1]; ++a1) {
+                const double n1 = V1[a1 * 2], d1 = V1[a1 * 2 + 1];
+                for (int c = 0; c < nc; ++c) {
+                    const double cf = row[(size_t)a1 * nc + c];
+                    sv[c] += n1 * cf;
+                    sd[c] += d1 * cf;
+                }
+            }
+            const double n0 = V0[a0 * 2], d0 = V0[a0 * 2 + 1];
+            for (int c = 0; c < nc; ++c) {
+                val[c] += n0 * sv[c];
+                jac[c][0] += d0 * sv[c];
+                jac[c][1] += n0 * sd[c];
+            }
+        }
+    } else {
+        const double *V2 = gv.V[2] + (size_t)g[2] * gv.P[2] * 2;
+        const int f2 = gv.fa[2][g[2]];
+        for (int a0 = 0; a0 < gv.P[0]; ++a0) {
+            double tv[MAX_COMP], t1[MAX_COMP], t2[MAX_COMP];
+            for (int c = 0; c < MAX_COMP; ++c) tv[c] = t1[c] = t2[c] = 0.0;
+            for (int a1 = 0; a1 < gv.P[1]; ++a1) {
+                double sv[MAX_COMP], sd[MAX_COMP];
+                for (int c = 0; c < MAX_COMP; ++c) sv[c] = sd[c] = 0.0;
+                const double *row = gv.ctrl + (((size_t)(f0 + a0) * gv.N[1] + (f1 + a1)) * gv.N[2] + f2) * nc;
+                for (int a2 = 0; a2 < gv.P[2]; ++a2) {
+                    const double n2 = V2[a2 * 2], d2 = V2[a2 * 2 + 1];
+                    for (int c = 0; c < nc; ++c) {
+                        const double cf = row[(size_t)a2 * nc + c];
+                        sv[c] += n2 * cf;
+                        sd[c] += d2 * cf;
+                    }
+                }
+                const double n1 = V1[a1 * 2], d1 = V1[a1 * 2 + 1];
+                for (int c = 0; c < nc; ++c) {
+                    tv[c] += n1 * sv[c];
+                    t1[c] += d1 * sv[c];
+                    t2[c] += n1 * sd[c];
+                }
+            }
+            const double n0 = V0[a0 * 2], d0 = V0[a0 * 2 + 1];
+            for (int c = 0; c < nc; ++c) {
+                val[c] += n0 * tv[c];
+                jac[c][0] += d0 * tv[c];
+                jac[c][1] += n0 * t1[c];
+                jac[c][2] += n0 * t2[c];
+            }
+        }
+    }
+}
+
 // homogeneous value/derivatives -> physical Jacobian Jm[r][c] = dG_r / d xi_c with c in (x,y,z)
 // order, i.e. c = 0 differentiates along the LAST grid axis (pyiga/bspline.py:917-921); NURBS by
 // the quotient rule (pyiga/geometry.py:17-25).
@@ -39,6 +109,17 @@ __device__ inline void finish_jacobian(const double val[MAX_COMP], const double 
             for (int c = 0; c < DIM; ++c) Jm[r][c] = jac[r][DIM - 1 - c];
         }
     }
+}
+
+// Physical Jacobian Jm[r][c] = dG_r / d xi_c with c in (x,y,z) order, i.e. c = 0 differentiates
+// along the LAST grid axis (pyiga/bspline.py:917-921); NURBS by the quotient rule.
+template <int DIM>
+__device__ inline void physical_jacobian(const GeoView &gv, bool nurbs, const int g[3], int ncomp,
+                                         double Jm[MAX_COMP][3], double ev[MAX_COMP])
+{
+    double val[MAX_COMP], jac[MAX_COMP][3];
+    eval_geo<DIM>(gv, g, val, jac);
+    finish_jacobian<DIM>(val, jac, nurbs, ncomp, gv.nc, Jm, ev);
 }
 
 // quadrature fields of one point from its Jacobian (row-major t[]): f[0] = W for the mass form, the upper

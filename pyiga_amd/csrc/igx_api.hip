@@ -161,7 +161,7 @@ static int setup_geo_axis(GeoAxis &g, const double *kv, int len, int p, const do
 
 static void free_geo_axis(GeoAxis &g) { (void)hipFree(g.d_kv); (void)hipFree(g.d_V); (void)hipFree(g.d_fa); }
 
-static int load_vector_jet_run(igx_patch *pt, double *out);
+static int load_vector_jet_run(igx_patch *pt, double *out, double *d_out = nullptr);
 
 // the sampled scalar coefficient of IGX_CONVDIFF: an affine coefficient is evaluated inside k_geoA and sampled into d_coeff only for the
 // kernels that read the array (field kernels of the stage / entry-wise paths) -- 1.5 GB and a 17 ms launch at C5 that the fast
@@ -374,6 +374,7 @@ void igx_patch_destroy(igx_patch *pt)
     (void)hipFree(pt->d_geoa_tab); (void)hipFree(pt->d_geoa_tabn); (void)hipFree(pt->d_zeros); (void)hipFree(pt->d_triv); (void)hipFree(pt->d_tpairs);
     (void)hipFree(pt->d_ws_ij); (void)hipFree(pt->d_ws_out);
     (void)hipFree(pt->d_lv_f); (void)hipFree(pt->d_lv_t1); (void)hipFree(pt->d_lv_t2); (void)hipFree(pt->d_lv_o);
+    (void)hipFree(pt->d_sp_ws);
     delete pt;
 }
 
@@ -1395,6 +1396,75 @@ int igx_load_vector_expr(igx_patch *pt, const char *expr, int parametric, double
     return IGX_OK;
 }
 
+// A spline of the patch's own space at the resident Gauss points, from a device dof vector (kern_spline.hip)
+int igx_patch_eval_spline_d(igx_patch *pt, const double *d_coeffs, int want_grad, double *const d_out[4])
+{
+    if (!pt || !d_coeffs || !d_out || !d_out[0]) { set_error("igx_patch_eval_spline_d: null argument"); return IGX_ERR_ARG; }
+    if (pt->boxed) { set_error("igx_patch_eval_spline_d: the patch holds a span box (batched entries only)"); return IGX_ERR_UNSUPPORTED; }
+    if (pt->r0_lo != 0 || pt->r0_hi != pt->ax[0].N) { set_error("igx_patch_eval_spline_d: whole patches only (the dof vector is the patch's, a row slab holds a part of the Gauss grid)"); return IGX_ERR_UNSUPPORTED; }
+    if (want_grad && pt->geo_kind == IGX_GEO_JACOBIAN) { set_error("igx_patch_eval_spline_d: the physical gradient needs a spline geometry"); return IGX_ERR_UNSUPPORTED; }
+    if (int rcb = basis_orders_ok(pt, IGX_MASS, "igx_patch_eval_spline_d")) return rcb;
+    if (want_grad)
+        for (int r = 1; r <= pt->dim; ++r)
+            if (!d_out[r]) { set_error("igx_patch_eval_spline_d: gradient array %d is null", r); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(pt->ctx->device));
+    hipStream_t st = pt->ctx->stream;
+    int rc;
+    if ((rc = ws_reserve(&pt->d_sp_ws, &pt->sp_ws_cap, spline_eval_workspace(pt, want_grad), "spline evaluation workspace"))) return rc;
+    (void)hipEventRecord(pt->ctx->ev[6], st);
+    rc = launch_spline_eval(st, pt, d_coeffs, want_grad, d_out, pt->d_sp_ws);
+    (void)hipEventRecord(pt->ctx->ev[7], st);
+    if (rc) return rc;
+    IGX_HIP(hipStreamSynchronize(st));
+    memset(&pt->timing, 0, sizeof(pt->timing));
+    (void)hipEventElapsedTime(&pt->timing.total_ms, pt->ctx->ev[6], pt->ctx->ev[7]);
+    pt->timing.algo_used = 4;                        // spline evaluation
+    pt->timing.n_launches = pt->dim == 3 ? 2 : 1;
+    return IGX_OK;
+}
+
+// out[k * npts + i] = expr_k(x, y, z, pi, f0 .. f{m-1}) at the resident points, f_j = d_in[j][i]
+int igx_patch_eval_exprs_inputs_d(igx_patch *pt, int n, const char *const *expr, int m, const double *const *d_in, double *d_out, int *cache_hit)
+{
+    if (!pt || !expr || !d_out || n < 1 || m < 0 || (m > 0 && !d_in)) { set_error("igx_patch_eval_exprs_inputs_d: bad argument"); return IGX_ERR_ARG; }
+    if (pt->boxed) { set_error("igx_patch_eval_exprs_inputs_d: the patch holds a span box (batched entries only)"); return IGX_ERR_UNSUPPORTED; }
+    IGX_HIP(hipSetDevice(pt->ctx->device));
+    hipStream_t st = pt->ctx->stream;
+    (void)hipEventRecord(pt->ctx->ev[6], st);
+    int rc = launch_form_exprs_inputs(st, pt, n, expr, m, d_in, d_out, cache_hit);
+    (void)hipEventRecord(pt->ctx->ev[7], st);
+    if (rc) return rc;
+    IGX_HIP(hipStreamSynchronize(st));
+    memset(&pt->timing, 0, sizeof(pt->timing));
+    (void)hipEventElapsedTime(&pt->timing.total_ms, pt->ctx->ev[6], pt->ctx->ev[7]);
+    pt->timing.algo_used = 5;                        // coefficient expressions
+    pt->timing.n_launches = 1;
+    return IGX_OK;
+}
+
+int igx_rtc_compile_exprs_inputs(int n, const char *const *expr, int m, const char *arch, char *path_out, int path_len, int *cache_hit)
+{
+    return rtc_compile_form_inputs(n, expr, m, arch, path_out, path_len, cache_hit);
+}
+
+// igx_load_vector_jet with the coefficients on the resident slab and the result in device memory
+int igx_load_vector_jet_d(igx_patch *pt, const double *const d_coef[4], double *d_out)
+{
+    if (!pt || !d_coef || !d_out) { set_error("igx_load_vector_jet_d: null argument"); return IGX_ERR_ARG; }
+    if (pt->boxed) { set_error("igx_load_vector_jet_d: the patch holds a span box (batched entries only)"); return IGX_ERR_UNSUPPORTED; }
+    if (int rcb = basis_orders_ok(pt, IGX_MASS, "igx_load_vector_jet_d")) return rcb;
+    for (int r = pt->dim + 1; r < 4; ++r)
+        if (d_coef[r]) { set_error("igx_load_vector_jet_d: coefficient %d does not exist in %dD", r, pt->dim); return IGX_ERR_ARG; }
+    const double *table[16];
+    for (int k = 0; k < 16; ++k) table[k] = nullptr;
+    bool any = false;
+    for (int r = 0; r < 4; ++r) { table[4 * r] = d_coef[r]; any = any || d_coef[r]; }
+    if (!any) { set_error("igx_load_vector_jet_d: all coefficients are absent"); return IGX_ERR_ARG; }
+    int rc = igx_patch_set_form_d(pt, table);
+    if (rc) return rc;
+    return load_vector_jet_run(pt, nullptr, d_out);
+}
+
 int igx_rtc_compile_load_vector(int P, int npass, int parametric, const char *expr, const char *arch, char *path_out, int path_len, int *cache_hit)
 {
     return rtc_compile_lv12(P, npass, parametric, expr, arch, path_out, path_len, cache_hit);
@@ -1403,7 +1473,7 @@ int igx_rtc_compile_load_vector(int P, int npass, int parametric, const char *ex
 } // extern "C"
 
 // the contractions of a jet functional whose coefficients are the column 0 of the patch's form
-static int igx::load_vector_jet_run(igx_patch *pt, double *out)
+static int igx::load_vector_jet_run(igx_patch *pt, double *out, double *d_out)
 {
     const int dim = pt->dim;
     int rc = ensure_fields(pt, IGX_FORM);
@@ -1413,17 +1483,14 @@ static int igx::load_vector_jet_run(igx_patch *pt, double *out)
     const size_t npts = (size_t)pd.npts_loc;
     size_t n_out;
     if ((rc = lv_workspace(pt, &n_out))) return rc;
-    double *d_t1 = pt->d_lv_t1, *d_t2 = pt->d_lv_t2, *d_o = pt->d_lv_o;
-    auto cleanup = [&]() {};
+    double *d_t1 = pt->d_lv_t1, *d_t2 = pt->d_lv_t2, *d_o = d_out ? d_out : pt->d_lv_o;      // (d_out: the result stays on the device)
     for (int k = 0; k < pd.form_n && rc == IGX_OK; ++k) {
         const int a = pd.form_ab[k] >> 2;                  // jet index of v; derivative a >= 1 acts on grid axis dim - a
         rc = launch_load_vector(st, pt, pt->d_fields + (size_t)k * npts, nullptr, d_o, d_t1, d_t2, a >= 1 ? dim - a : -1, k > 0);
     }
     hipError_t e = hipSuccess;
-    if (rc == IGX_OK) e = hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (rc == IGX_OK && out) e = hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    cleanup();
     if (e != hipSuccess) { set_error("igx_load_vector_jet: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
     return rc;
 }
-

@@ -221,6 +221,8 @@ struct igx_patch {
     long long aca_requests = 0, aca_entries = 0; int aca_rank = 0;      // igx_fast_assemble_stats
     double *d_lv_f = nullptr, *d_lv_t1 = nullptr, *d_lv_t2 = nullptr, *d_lv_o = nullptr;
     size_t lv_f_cap = 0, lv_t1_cap = 0, lv_t2_cap = 0, lv_o_cap = 0;
+    double *d_sp_ws = nullptr;                // axis-0 expansion of igx_patch_eval_spline_d (kern_spline.hip), grow-only
+    size_t sp_ws_cap = 0;
     // fused sweep + final stage (fused.hip)
     long long nnz_ext = 0;                    // values of the owned rows + the p0 halo planes above them (mirror sources)
     double *d_zeros = nullptr;                // a row of zeros: input of absent sweep slots
@@ -283,6 +285,12 @@ int entries_pair_boxes(igx_patch *pt, int kind, const PairBoxes &B, double *out_
 int launch_entries_csr(hipStream_t st, const igx_patch *pt, int kind, double *d_data);
 int launch_load_vector(hipStream_t st, const igx_patch *pt, const double *d_f, const double *d_W, double *d_out,
                        double *d_t1, double *d_t2, int deriv_axis = -1, int accumulate = 0, int *n_launches = nullptr /* 2: k_lv12 + axis 0, else one per axis */);
+// a spline of the patch's space from a device dof vector at the resident Gauss points (kern_spline.hip)
+size_t spline_eval_workspace(const igx_patch *pt, int want_grad);
+int launch_spline_eval(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, double *const d_out[4], double *d_ws);
+// coefficient expressions that also read device arrays f0 .. f{m-1} at the thread's point (rtc.hip)
+int launch_form_exprs_inputs(hipStream_t st, igx_patch *pt, int n_expr, const char *const *expr, int m, const double *const *d_in, double *d_out, int *cache_hit);
+int rtc_compile_form_inputs(int n_expr, const char *const *expr, int m, const char *arch, char *path_out, int path_len, int *cache_hit);
 inline int igx_num_fields(int dim, int kind, int form_n = 0)
 {
     return kind == IGX_MASS ? 1 : (kind == IGX_CONVDIFF ? 9 : (kind == IGX_FORM ? form_n : dim * (dim + 1) / 2));

@@ -880,4 +880,74 @@ int rtc_compile_form(int n_expr, const char *const *expr, const char *arch, char
     return IGX_OK;
 }
 
+// The same kernel with m further doubles f0 .. f{m-1} in scope, loaded from m device arrays at the thread's resident point: the
+// coefficients of a form that depend on fields evaluated on the device (a spline iterate and its gradient: kern_spline.hip).
+// m is part of the source -- and so of the cache key.  The struct is part of the generated source AND of this file.
+constexpr int RTC_MAX_INPUTS = 16;
+struct IgxIn { const double *p[RTC_MAX_INPUTS]; };
+static std::string form_inputs_source(int n_expr, const char *const *expr, int m)
+{
+    std::string s;
+    s += "// generated by libigx (igx_patch_eval_exprs_inputs_d): coefficient fields of a form from the physical coordinates and " + std::to_string(m) + " input arrays\n";
+    s += RTC_PRELUDE;
+    s += "struct IgxIn { const double *p[" + std::to_string(RTC_MAX_INPUTS) + "]; };\n";
+    s += "extern \"C\" __global__ void igx_form_inputs_expr(const IgxCo co, const IgxIn in, double *out, long long n)\n{\n";
+    s += "    int g[3];\n    const long long i = igx_point(co, g);\n    if (i < 0 || i >= n) return;\n";
+    s += "    double x, y, z;\n    igx_coords(co, g, x, y, z);\n    const double pi = 3.14159265358979323846;\n    (void)x; (void)y; (void)z; (void)pi;\n";
+    for (int j = 0; j < m; ++j) {
+        const std::string f = "f" + std::to_string(j);
+        s += "    const double " + f + " = in.p[" + std::to_string(j) + "][i];\n    (void)" + f + ";\n";
+    }
+    for (int k = 0; k < n_expr; ++k) {
+        s += "    out[" + std::to_string(k) + " * n + i] = (double)(";
+        s += expr[k];
+        s += ");\n";
+    }
+    s += "}\n";
+    return s;
+}
+
+static int exprs_inputs_ok(int n_expr, const char *const *expr, int m, const char *what)
+{
+    if (!expr || n_expr < 1 || m < 0 || m > RTC_MAX_INPUTS) { set_error("%s: bad argument (1 or more expressions, at most %d inputs)", what, RTC_MAX_INPUTS); return IGX_ERR_ARG; }
+    for (int k = 0; k < n_expr; ++k)
+        if (!expr[k]) { set_error("%s: expression %d is null", what, k); return IGX_ERR_ARG; }
+    return exprs_ok(n_expr, expr, what);
+}
+
+int launch_form_exprs_inputs(hipStream_t st, igx_patch *pt, int n_expr, const char *const *expr, int m, const double *const *d_in, double *d_out, int *hit)
+{
+    if (int rc = exprs_inputs_ok(n_expr, expr, m, "igx_patch_eval_exprs_inputs_d")) return rc;
+    for (int j = 0; j < m; ++j)
+        if (!d_in[j]) { set_error("igx_patch_eval_exprs_inputs_d: input array %d is null", j); return IGX_ERR_ARG; }
+    // the coordinates: physical with a spline geometry, else (Jacobian arrays) the parametric ones
+    const bool parametric = pt->geo_kind == IGX_GEO_JACOBIAN;
+    hipFunction_t fn;
+    if (int rc = rtc_function(pt, form_inputs_source(n_expr, expr, m), "igx_form_inputs_expr", &fn, hit)) return rc;
+    long long nn = pt->dev.npts_loc;
+    if (nn == 0) return IGX_OK;
+    IgxCo co{};
+    IgxIn in{};
+    const int dim = pt->dim;
+    fill_co(pt, parametric, co);
+    for (int j = 0; j < m; ++j) in.p[j] = d_in[j];
+    void *args[] = {(void *)&co, (void *)&in, (void *)&d_out, (void *)&nn};
+    const int Ll = dim == 3 ? pt->dev.L2 : pt->dev.L1;
+    const unsigned gx = (unsigned)((Ll + 255) / 256), gy = (unsigned)(dim == 3 ? pt->dev.L1 : pt->dev.G0_loc), gz = (unsigned)(dim == 3 ? pt->dev.G0_loc : 1);
+    if (gy > 65535u || gz > 65535u) { set_error("coefficient expression: Gauss grid beyond the launch grid"); return IGX_ERR_UNSUPPORTED; }
+    if (hipModuleLaunchKernel(fn, gx, gy, gz, 256, 1, 1, 0, st, args, nullptr) != hipSuccess) { (void)hipGetLastError(); set_error("launch of the compiled coefficient kernel failed"); return IGX_ERR_HIP; }
+    return IGX_OK;
+}
+
+int rtc_compile_form_inputs(int n_expr, const char *const *expr, int m, const char *arch, char *path_out, int path_len, int *hit)
+{
+    if (!arch) { set_error("igx_rtc_compile_exprs_inputs: null argument"); return IGX_ERR_ARG; }
+    if (int rc = exprs_inputs_ok(n_expr, expr, m, "igx_rtc_compile_exprs_inputs")) return rc;
+    std::vector<char> code;
+    std::string path;
+    if (int rc = rtc_code_object(form_inputs_source(n_expr, expr, m), arch, code, path, hit)) return rc;
+    if (path_out && path_len > 0) { strncpy(path_out, path.c_str(), (size_t)path_len - 1); path_out[path_len - 1] = 0; }
+    return IGX_OK;
+}
+
 } // namespace igx

@@ -1018,6 +1018,13 @@ struct SwPatch {
     FastDiag F;
 };
 
+// x -= d (the Newton update; d vanishes on the fixed dofs)
+__global__ void k_sub(long long n, double *x, const double *d)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] -= d[i];
+}
+
 struct igx_solver {
     igx_ctx *ctx = nullptr;
     igx_patch *pt = nullptr;                  // the patch of a patch solver, or
@@ -1632,7 +1639,7 @@ int igx_solver_set_method(igx_solver *s, int method)
             set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; the parabolic solver was made as non-symmetric");
             return IGX_ERR_UNSUPPORTED;
         }
-        if (s->ncomp == 1 && !s->mp && !s->parabolic && !spd_kind(s->kind)) {
+        if (s->ncomp == 1 && !s->mp && !s->parabolic && !spd_kind(s->kind) && !s->symmetric) {     // (symmetric: igx_solver_declare_symmetric)
             set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; kind %d is not known to be one", s->kind);
             return IGX_ERR_UNSUPPORTED;
         }
@@ -2022,6 +2029,80 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
     }
     if (int rc = solve_lifted(st, s, s->w, x0 != nullptr, tol, maxiter, check_every, timed, inf)) return rc;
     return finish_solve(st, s, gvals, u, info, inf);
+}
+
+// --- Newton's method on a patch solver: the iterate, the residual and the Jacobian stay on the device ----
+static int newton_solver_ok(const igx_solver *s, const char *what)
+{
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->mp || s->ncomp > 1 || s->parabolic) { set_error("%s: scalar patch solvers only", what); return IGX_ERR_UNSUPPORTED; }
+    return IGX_OK;
+}
+
+int igx_solver_declare_symmetric(igx_solver *s)
+{
+    if (int rc = newton_solver_ok(s, "igx_solver_declare_symmetric")) return rc;
+    s->symmetric = true;
+    return IGX_OK;
+}
+
+int igx_solver_values_changed(igx_solver *s)
+{
+    if (int rc = newton_solver_ok(s, "igx_solver_values_changed")) return rc;
+    if (int rc = check_values(s, "igx_solver_values_changed")) return rc;
+    if (s->precond != IGX_PRECOND_JACOBI) return IGX_OK;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, patch_values(s), s->d_mask, s->dinv);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
+int igx_solver_masked_norm_d(igx_solver *s, const double *d_v, double *norm)
+{
+    if (int rc = newton_solver_ok(s, "igx_solver_masked_norm_d")) return rc;
+    if (!d_v || !norm) { set_error("igx_solver_masked_norm_d: null argument"); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const long long n = s->n;
+    const unsigned nbv = vec_blocks(n);
+    IGX_HIP(hipMemsetAsync(s->d_sc, 0, SC_N * sizeof(double), st));
+    k_mask_copy<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, s->d_mask, d_v, s->r);
+    k_dot2<<<nbv, BLOCK, 0, st>>>(n, s->r, s->r, nullptr, nullptr, s->d_part, nullptr);
+    k_fin<<<1, BLOCK, 0, st>>>(s->d_part, nullptr, nbv, s->d_sc, FIN_INIT);
+    IGX_HIP(hipGetLastError());
+    double h_rr = 0.0;
+    IGX_HIP(hipMemcpyAsync(&h_rr, s->d_sc + SC_RR, sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    *norm = std::sqrt(h_rr);
+    return IGX_OK;
+}
+
+int igx_solver_newton_update_d(igx_solver *s, const double *d_F, double *d_x, double tol, int maxiter, int check_every, igx_solve_info *info)
+{
+    if (int rc = newton_solver_ok(s, "igx_solver_newton_update_d")) return rc;
+    if (!d_F || !d_x) { set_error("igx_solver_newton_update_d: null argument"); return IGX_ERR_ARG; }
+    if (!(tol >= 0.0) || maxiter < 0) { set_error("igx_solver_newton_update_d: tol must be >= 0 and maxiter >= 0"); return IGX_ERR_ARG; }
+    if (int rc = check_values(s, "igx_solver_newton_update_d")) return rc;
+    if (check_every < 1) check_every = 1;
+    s->breakdown = 0;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const long long n = s->n;
+    igx_solve_info inf{};
+    IGX_HIP(hipEventRecord(s->ev[5], st));
+    IGX_HIP(hipMemcpyAsync(s->b, d_F, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    // nothing is lifted: the increment vanishes on the fixed dofs, r = R F, the solve starts from zero
+    if (int rc = solve_lifted(st, s, nullptr, false, tol, maxiter, check_every, 0, inf)) return rc;
+    k_sub<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, d_x, s->x);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipEventRecord(s->ev[4], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&inf.total_ms, s->ev[5], s->ev[4]);
+    inf.n_free = n - (long long)s->fixed.size();
+    if (info) *info = inf;
+    return IGX_OK;
 }
 
 int igx_kron_apply_d(igx_ctx *ctx, const igx_kron_desc *d, const double *d_x, double *d_y, double *d_work, int64_t work_len)

@@ -14,6 +14,12 @@ which is what ``IGX_FORM`` of libigx assembles (include/igx.h).  Supported: scal
 physical coordinates returning scalars, tuples/vectors or ``(3,3)`` arrays; constants and arrays).
 Anything else (higher derivatives, vector-valued bases, surface integrals, ``div``/``curl`` ...) raises
 ``NotImplementedError`` -- the general compiler is row f1 "full" of SURVEY section 8.
+
+A scalar spline function (``BSplineFunc`` with ``output_shape() == ()``) among the inputs is a parametric field
+(pyiga/vform.py:1791-1802): its name stands for its value at the Gauss points and ``grad(name)`` for its physical gradient.
+Such a form is traced only (``symbolic_table`` / ``functional_jet(traced=True)`` with a ``symbolic.FieldSlots``): value and
+gradient components become the symbols ``f0, f1, ..`` which the generated coefficient kernel reads from arrays evaluated on
+the device.
 """
 import numpy as np
 
@@ -99,6 +105,15 @@ class _Coef:
     def __pow__(self, k): return _Coef(self.a ** k, self.rank)
 
 
+class _Field(_Coef):
+    """A scalar spline-function input: a scalar coefficient that also knows its physical gradient (``grad(w)``).  Whatever is
+    computed from it is a plain coefficient again: ``grad`` of that stays unsupported."""
+
+    def __init__(self, a, gradient):
+        super().__init__(a, 0)
+        self.gradient = gradient          # () -> array G + (d,)
+
+
 class _Lin:
     """Expression that is linear in the jet of ONE basis function: scalar-valued  s*phi + w.grad(phi)
     (vector=False) or vector-valued  M grad(phi) + t*phi  (vector=True)."""
@@ -136,6 +151,12 @@ class _Lin:
         return _Lin(self.who, self.vector, ad(self.s, o.s), ad(self.w, o.w), ad(self.M, o.M), ad(self.t, o.t))
 
     def __sub__(self, o): return self + (-o)
+
+    def __getitem__(self, c):
+        """Component c of a vector-valued expression  M grad(phi) + t phi, e.g. ``grad(u)[0]``."""
+        if not self.vector:
+            raise NotImplementedError('indexing a scalar expression in a basis function')
+        return _Lin(self.who, False, s=None if self.t is None else self.t[..., c], w=None if self.M is None else self.M[..., c, :])
 
 
 class _Bil:
@@ -200,7 +221,7 @@ class _Dx:
 def _jet(lin):
     """Scalar-valued linear expression -> list of 4 coefficient arrays (value, d/dx, d/dy, d/dz) or None."""
     assert not lin.vector
-    d = (lin.s if lin.w is None else lin.w[..., 0]).ndim
+    d = lin.w.shape[-1] if lin.w is not None else lin.s.ndim
     return [lin.s] + [None if lin.w is None else lin.w[..., k] for k in range(d)]
 
 
@@ -231,9 +252,24 @@ def _vec_jet(lin):
     return out
 
 
-def make_namespace(G, X, inputs):
+def is_spline_input(val):
+    """A spline function given as a form input (not a callable of the coordinates)."""
+    return hasattr(val, 'grid_eval') and not callable(val)
+
+
+def check_spline_input(name, val):
+    """Only scalar B-spline functions are served as inputs; says which case it is otherwise."""
+    from .bspline import BSplineFunc
+    if not isinstance(val, BSplineFunc):
+        raise NotImplementedError('form input %r: only B-spline functions (BSplineFunc) are supported as spline inputs' % name)
+    if val.output_shape() != ():
+        raise NotImplementedError('form input %r: vector-valued spline inputs are not supported (scalar spline functions only)' % name)
+
+
+def make_namespace(G, X, inputs, fields=None):
     """Names available to a form string.  G: grid shape; X: physical coordinates, G + (3,); inputs: dict of
-    callables (evaluated at the physical coordinates) or constants."""
+    callables (evaluated at the physical coordinates) or constants.  fields: the ``symbolic.FieldSlots`` of a traced
+    evaluation, which serves scalar spline functions among the inputs."""
     d = len(G)
     assert X.shape == G + (d,), 'physical coordinates do not fit the grid'
     one = np.ones(G)
@@ -250,6 +286,10 @@ def make_namespace(G, X, inputs):
     def grad(e, dims=None, parametric=False):
         if dims is not None or parametric:
             raise NotImplementedError('grad(dims=..., parametric=...): see pyiga_amd.pforms')
+        if isinstance(e, _Field):
+            return _Coef(e.gradient(), 1)
+        if isinstance(e, _Coef):
+            raise NotImplementedError('grad() of a coefficient expression: only grad(w) of a spline-function input w itself')
         if not (isinstance(e, _Lin) and not e.vector and e.w is None):
             raise NotImplementedError('grad() of anything but u or v (times a constant)')
         c = _uniform_value(e.s)
@@ -322,8 +362,14 @@ def make_namespace(G, X, inputs):
     for name, val in inputs.items():
         if name in ('geo',):
             continue
-        if hasattr(val, 'grid_eval') and not callable(val):
-            raise NotImplementedError('spline functions as form inputs')
+        if is_spline_input(val):
+            check_spline_input(name, val)
+            if val.sdim != d:
+                raise ValueError('form input %r: a spline function of %d variables on a %dD patch' % (name, val.sdim, d))
+            if fields is None:
+                raise NotImplementedError('spline functions as form inputs are evaluated on the device: this path samples on the host')
+            ns[name] = _Field(fields.value(name), (lambda n: lambda: fields.gradient(n))(name))
+            continue
         if callable(val):
             vals = val(*(X[..., k] for k in range(d)))
             if not isinstance(vals, (tuple, list)):
@@ -338,10 +384,10 @@ def make_namespace(G, X, inputs):
     return ns
 
 
-def coefficient_table(expr, G, X, inputs, traced=False):
+def coefficient_table(expr, G, X, inputs, traced=False, fields=None):
     """Evaluate the form string; returns the 4x4 table of coefficient arrays (shape G) or None.  traced: the arrays are
     object arrays of expression trees (symbolic_table)."""
-    ns = make_namespace(G, X, inputs)
+    ns = make_namespace(G, X, inputs, fields)
     try:
         res = eval(expr, {'__builtins__': {}}, ns)
     except NameError as e:
@@ -358,20 +404,21 @@ def coefficient_table(expr, G, X, inputs, traced=False):
     return table
 
 
-def symbolic_table(expr, d, inputs):
+def symbolic_table(expr, d, inputs, fields=None):
     """The coefficient table of the form string as C expressions in the physical coordinates (x, y[, z]): the string -- and
     every callable among the inputs -- is evaluated ONCE, on a grid of one point whose coordinates are symbols
     (pyiga_amd.symbolic).  Raises (symbolic.NotTraceable or whatever numpy makes of the attempt) when something cannot be
-    traced; the caller then samples the coefficients on the host."""
+    traced; the caller then samples the coefficients on the host.  fields: the ``symbolic.FieldSlots`` that collects the device
+    arrays f0, f1, .. the expressions read (spline-function inputs)."""
     from . import symbolic
-    table = coefficient_table(expr, (1,) * d, symbolic.coordinates(d), inputs, traced=True)
+    table = coefficient_table(expr, (1,) * d, symbolic.coordinates(d), inputs, traced=True, fields=fields)
     return [[None if e is None else symbolic.c_source(e) for e in row] for row in table]
 
 
-def functional_jet(expr, G, X, inputs, traced=False):
+def functional_jet(expr, G, X, inputs, traced=False, fields=None):
     """Evaluate an arity-1 form string ``(F0 * v + inner(F, grad(v))) * dx``; returns the list
     ``[F0, F_1, ..., F_d]`` of coefficient arrays on the grid (shape G) or None."""
-    ns = make_namespace(G, X, inputs)
+    ns = make_namespace(G, X, inputs, fields)
     ns.pop('u')
     try:
         res = eval(expr, {'__builtins__': {}}, ns)

@@ -1605,3 +1605,211 @@ class ParabolicSystem(_DeviceSystem):
             warnings.warn('ParabolicSystem.integrate_adaptive: %s; returning the %d steps completed' % (failed, accepted),
                           RuntimeWarning, stacklevel=2)
         return times, sols
+
+
+################################################################################
+# Nonlinear Dirichlet problems of one patch on the device: Newton's method
+################################################################################
+
+class NoConvergenceError(Exception):
+    """An iteration stopped after its maximum number of steps (pyiga/solvers.py:329-333)."""
+
+    def __init__(self, method, num_iter, last_iterate):
+        super().__init__('%s: no convergence after %d iterations' % (method, num_iter))
+        self.method = method
+        self.num_iter = num_iter
+        self.last_iterate = last_iterate
+
+
+def newton_loop(residual_norm, form_jacobian, update, atol, rtol, maxiter, freeze_jac):
+    """The bookkeeping of Newton's method as the reference does it (pyiga/solvers.py:335-361), on callbacks that act on the
+    current iterate wherever it lives: ``residual_norm()`` evaluates F there and returns ``||R F||``, ``form_jacobian()`` forms J
+    there, ``update()`` does ``x -= J^-1 F`` with the J formed last and returns the inner iterations.  The target is
+    ``max(atol, rtol ||R F(x0)||)``, tested (``<``) before each step; J is formed again every `freeze_jac` steps.  Returns
+    ``(converged, info)``, info = Newton steps, the residual norm before every step (and after the last), the inner iterations
+    per step and the number of Jacobians formed."""
+    if freeze_jac < 1:
+        raise ValueError('freeze_jac must be at least 1')
+    norms, inner, jacobians = [residual_norm()], [], 0
+    target = max(atol, rtol * norms[0])
+    converged = False
+    for it in range(maxiter):
+        if norms[-1] < target:
+            converged = True
+            break
+        if it % freeze_jac == 0:
+            form_jacobian()
+            jacobians += 1
+        inner.append(update())
+        norms.append(residual_norm())
+    return converged, dict(iterations=len(inner), residual_norms=norms, inner_iterations=inner, jacobians=jacobians, target=target)
+
+
+def _symmetric_traced_table(table):
+    """The test VectorFormSystem applies to sampled tables (symmetric_block_tables), on a traced one: entry (r, s) and entry
+    (s, r) are the same expression text, a None only opposite a None."""
+    n = len(table)
+    return all(table[r][s] == table[s][r] for r in range(n) for s in range(n))
+
+
+class NewtonSystem(PatchSystem):
+    """The nonlinear Dirichlet problem ``F(x) = 0``, ``x = g`` on the dofs of `bcs`, on one patch, by Newton's method with the
+    iterate, the residual and the Jacobian in device memory (the reference's idiom: ``F(x) = Assembler(residual,
+    updatable=[unknown]).assemble(w=BSplineFunc(kvs, x))``, J likewise, ``RestrictedLinearSystem``, ``solvers.newton``).
+
+    `residual`: an arity-1 form string in ``v`` and the unknown; `jacobian`: an arity-2 form string in ``u``, ``v`` and the
+    unknown (named `unknown`, a scalar spline function of the patch's space: its value, and ``grad(unknown)``); other inputs as
+    for ``assemble.assemble``.  The linear solves are CG when the traced coefficient table of the Jacobian is symmetric, else
+    BiCGStab (`method`: 'auto', 'cg', 'bicgstab').  Residual and Jacobian run on two patches of the same space: the solver reads
+    the Jacobian's patch, whose form is never anything but the Jacobian's.  Needs the run-time compiler (no host fallback)."""
+
+    def __init__(self, kvs, geo, residual, jacobian, bcs, unknown='w', args=None, method='auto', **inputs):
+        from . import bspline, forms
+        inputs = dict(args or {}, **inputs)
+        inputs.pop('geo', None)
+        self.kvs = tuple(kvs)
+        self.unknown = unknown
+        d = len(self.kvs)
+        if forms.arity(residual) != 1 or forms.arity(jacobian) != 2:
+            raise ValueError('NewtonSystem: the residual is a linear functional in v, the Jacobian a bilinear form in u and v')
+        if method not in ('auto', 'cg', 'bicgstab'):
+            raise ValueError("unknown method %r: 'auto', 'cg' or 'bicgstab'" % (method,))
+        self.ndofs = tuple(kv.numdofs for kv in self.kvs)
+        self.n = int(np.prod(self.ndofs))
+        w0 = bspline.BSplineFunc(self.kvs, np.zeros(self.ndofs))
+        full = dict(inputs, geo=geo)
+        full[unknown] = w0
+        cls2 = assemblers.GeneralFormAssembler2D if d == 2 else assemblers.GeneralFormAssembler3D
+        cls1 = assemblers.GeneralFunctionalAssembler2D if d == 2 else assemblers.GeneralFunctionalAssembler3D
+        from .assemble import _check_spline_inputs
+        _check_spline_inputs(residual, self.kvs, full, None, None, False)
+        _check_spline_inputs(jacobian, self.kvs, full, None, None, False)
+        self.patch = self.jac = self.res = self.d_x = None
+        try:
+            self.jac = cls2(self.kvs, geo, jacobian, inputs=full)
+            self.assembler, self.patch, self.kind = self.jac, self.jac.patch, 'form'
+            self.res = cls1(self.kvs, geo, residual, inputs=full, fields=self.jac.fields)
+            self._want_grad = self.jac._slots.wants_gradient(unknown) or self.res._slots.wants_gradient(unknown)
+            self.symmetric = _symmetric_traced_table(self.jac._exprs)
+            if method == 'auto':
+                method = 'cg' if self.symmetric else 'bicgstab'
+            self._ctx = self.patch.ctx
+            self.d_x = DeviceArray(self._ctx, self.n)
+            self.patch.assemble('form', to_host=False)                # J(0): the solver is made over values of its kind
+            self.b = np.zeros(self.n)
+            self._attach('igx_solver_create_general', (self.patch.handle, _lib.KINDS['form']), bcs, 'bicgstab', 'bicgstab')
+            if self.symmetric:
+                _lib.check(_lib.load().igx_solver_declare_symmetric(self.handle), 'igx_solver_declare_symmetric')
+            self.set_method(method)
+        except BaseException:
+            self._release()
+            self._drop_owner()                                    # (nothing of a failed construction stays on the device)
+            raise
+        self.box = dirichlet_box(self.ndofs, self.bc_indices)
+
+    def _drop_owner(self):
+        for name in ('jac', 'res'):
+            a = getattr(self, name, None)
+            if a is not None and getattr(a, 'patch', None) is not None:
+                a.patch.close()
+            setattr(self, name, None)
+        if getattr(self, 'd_x', None) is not None:
+            self.d_x.free()
+            self.d_x = None
+        self.patch = None
+
+    def _kron_factors(self):
+        return fastdiag_factors(self.kvs, self.box[0], self.box[1], True)     # the parametric Laplacian of the free box
+
+    @property
+    def default_precond(self):
+        return 'kron' if self.box is not None else 'jacobi'
+
+    # -- the steps of one iteration, all on the device
+    def _start(self, x0):
+        x = np.zeros(self.n) if x0 is None else np.array(x0, dtype=np.float64).ravel()
+        if x.size != self.n:
+            raise ValueError('x0 has the wrong size')
+        x[self.bc_indices] = self.bc_values
+        self.d_x.upload(x)
+
+    _phases = None                    # solve(timed=True): device ms of the phases, one dict per evaluation / formation / solve
+
+    def _note(self, **ms):
+        if self._phases is not None:
+            self._phases.append(ms)
+
+    def _residual_norm(self):
+        self._live()
+        self.jac.fields.set_resident(self.unknown, self.d_x.ptr, self._want_grad)       # step 1: the fields of the iterate
+        fields_ms = self.patch.timing()['total_ms'] if self._phases is not None else 0.0
+        self._d_F = self.res.assemble_vector_resident()                                 # step 2: F
+        # (igx_load_vector_jet_d leaves the timing of the coefficient kernel before it in place)
+        self._note(fields_ms=fields_ms, residual_coefficients_ms=self.res.patch.timing()['total_ms'] if self._phases is not None else 0.0)
+        nrm = C.c_double(0.0)
+        _lib.check(_lib.load().igx_solver_masked_norm_d(self.handle, self._d_F, C.byref(nrm)), 'igx_solver_masked_norm_d')
+        return float(nrm.value)
+
+    def _form_jacobian(self):
+        self.jac.apply_fields()                                                         # step 3: J
+        coef_ms = self.patch.timing()['total_ms'] if self._phases is not None else 0.0
+        self.patch.assemble('form', to_host=False)
+        self._note(jacobian_coefficients_ms=coef_ms, jacobian_assembly_ms=self.patch.timing()['total_ms'] if self._phases is not None else 0.0)
+        _lib.check(_lib.load().igx_solver_values_changed(self.handle), 'igx_solver_values_changed')
+
+    def _update(self, lin_tol, lin_maxiter):
+        info = _lib.SolveInfo()
+        _lib.check(_lib.load().igx_solver_newton_update_d(self.handle, self._d_F, self.d_x.ptr, float(lin_tol), int(lin_maxiter), 1,
+                                                         C.byref(info)), 'igx_solver_newton_update_d')
+        if not info.converged:
+            warnings.warn('NewtonSystem: the linear solve stopped after %d iterations at relative residual %.2e' % (info.iterations, info.relres),
+                          RuntimeWarning, stacklevel=3)
+        self._note(solve_ms=float(info.total_ms), inner_iterations=int(info.iterations))
+        return int(info.iterations)
+
+    def solve(self, x0=None, atol=1e-6, rtol=1e-6, maxiter=100, freeze_jac=1, lin_tol=1e-10, lin_maxiter=1000, precond='auto',
+              callback=None, timed=False):
+        """Newton's method from `x0` (a full vector whose fixed entries are replaced by g; default zero on the free dofs) to
+        ``||R F(x)|| < max(atol, rtol ||R F(x0)||)``; returns the full solution vector.  ``NoConvergenceError`` after `maxiter`
+        steps.  `callback(k, x)`: the iterate (host copy) after step k.  Statistics in ``info``; with `timed` also
+        ``info['phases']``: the device ms of every field evaluation + coefficient kernel, Jacobian formation and linear solve, in
+        the order they ran."""
+        self._phases = [] if timed else None
+        self.set_precond(self.default_precond if precond == 'auto' else precond)
+        self._start(x0)
+
+        def update():
+            inner = self._update(lin_tol, lin_maxiter)
+            its.append(inner)
+            if callback is not None:
+                callback(len(its), self.d_x.download())
+            return inner
+        its = []
+        converged, info = newton_loop(self._residual_norm, self._form_jacobian, update, atol, rtol, maxiter, freeze_jac)
+        self.info = dict(info, converged=converged, method=self.method, precond=self._precond)
+        if timed:
+            self.info['phases'], self._phases = self._phases, None
+        x = self.d_x.download()
+        if not converged:
+            raise NoConvergenceError('newton', maxiter, x)
+        return x
+
+    def residual(self, x):
+        """F(x) as a host vector (all dofs)."""
+        self._start(x)
+        self._residual_norm()
+        return self._download(self._d_F)
+
+    def _download(self, ptr):
+        out = np.empty(self.n)
+        _lib.check(_lib.load().igx_dev_download(self._ctx.handle, out.ctypes.data, ptr, out.nbytes), 'igx_dev_download')
+        return out
+
+    def jacobian(self, x):
+        """J(x) as scipy CSR (all dofs)."""
+        self._start(x)
+        self.jac.fields.set_resident(self.unknown, self.d_x.ptr, self._want_grad)
+        self.jac.apply_fields()
+        A = self.patch.csr('form')
+        _lib.check(_lib.load().igx_solver_values_changed(self._live()), 'igx_solver_values_changed')     # (the solver's values are new)
+        return A

@@ -196,6 +196,39 @@ def coordinates(d):
     return X
 
 
+class FieldSlots:
+    """The device arrays a traced form reads besides the coordinates: slot k is the symbol ``f<k>`` of the generated kernel
+    (``igx_patch_eval_exprs_inputs_d``).  ``slots[k] = (name, comp)``: input `name`, comp 0 its value, comp 1..d its physical
+    derivative D_comp (D_1 = d/dx).  Slots are handed out in the order of first use."""
+
+    def __init__(self, d):
+        self.d = d
+        self.slots = []
+
+    def _sym(self, name, comp):
+        key = (name, comp)
+        if key not in self.slots:
+            self.slots.append(key)
+        return Sym('f%d' % self.slots.index(key))
+
+    def value(self, name):
+        a = np.empty((1,) * self.d, dtype=object)
+        a[(0,) * self.d] = self._sym(name, 0)
+        return a
+
+    def gradient(self, name):
+        a = np.empty((1,) * self.d + (self.d,), dtype=object)
+        for k in range(self.d):
+            a[(0,) * self.d + (k,)] = self._sym(name, 1 + k)
+        return a
+
+    def names(self):
+        return sorted({name for name, _ in self.slots})
+
+    def wants_gradient(self, name):
+        return any(n == name and c > 0 for n, c in self.slots)
+
+
 def c_source(e):
     """C text of a traced scalar (the single entry of an object array, a Sym or a number)."""
     if isinstance(e, np.ndarray):
