@@ -225,7 +225,10 @@ bool lv12_shape(const igx_patch *pt, int *clen_out, int *nch_out, size_t *lds_ou
     const PatchDev &pd = pt->dev;
     if (pd.dim != 3) return false;
     const AxisDev &a1 = pd.ax[1], &a2 = pd.ax[2];
-    const long long G0 = pd.G0_loc;
+    // the Gauss planes of the WHOLE axis 0, not of the resident slab: a row slab must cut the mid axis into the chunks of the whole
+    // patch, or a dof that is stored there is the sum of two addends here and the slab differs from its rows of the whole vector
+    // in the last bit (tests/test_lv_kernels_gpu.py, case ch_g0cap: 120 planes, the slab's 62 gave 75 chunks against 67)
+    const long long G0 = pd.ax[0].G;
     const int PQ = a2.P * a2.q;
     const size_t lds12 = ((size_t)((PQ * a2.N + 1) & ~1) + LV_WAVES * (size_t)((a2.G + 1) & ~1)) * sizeof(double);
     if (!(a2.P >= 2 && a2.P <= 6 && a1.P == a2.P && PQ <= VEC_MAXSUP && a2.N <= 64 * LV_MAXPASS && a2.G % 2 == 0 && a2.G <= 640 && lds12 <= 64 * 1024

@@ -2376,14 +2376,25 @@ def test_load_vector_function_compiled(iga, tmp_path, monkeypatch):
         assert np.abs(got - ref).max() <= 1e-13 * np.abs(ref).max()
     # the one-kernel path (geometry + weight + function: igx_load_vector_expr) against the two-array path (function values by a
     # generated kernel, weight field by the library, both read back: igx_patch_eval_expr_d + igx_load_vector_d), slabs included
-    for kvs, geo, f in cases:
+    # (the first two cases are refused by the one-kernel path -- unequal degrees of the last two axes, 2D -- and
+    # load_vector_expr falls back to the two arrays: only the third, with equal mid and last degrees, runs igx_lv12_expr)
+    import ctypes
+    fused = ((mk(2, 0.0, 1.0, 5), mk(3, 0.0, 1.0, 6), mk(3, 0.0, 1.0, 4)), _geo(iga, 'cylinder'), f3)
+    for kvs, geo, f in cases + [fused]:
         from pyiga_amd import symbolic
         src = symbolic.trace_function(f, len(kvs))
         N0 = kvs[0].numdofs
         for row0 in (None, (1, N0 - 2)):
             patch = iga.assemblers.DevicePatch(kvs, geo, row0=row0)
             for par in (False, True):
+                if kvs is fused[0]:
+                    direct = np.empty(patch.row_range[1] - patch.row_range[0])
+                    rc = iga._lib.load().igx_load_vector_expr(patch.handle, src.encode(), 1 if par else 0, iga._lib.dptr(direct), ctypes.byref(ctypes.c_int(0)))
+                    assert rc == iga._lib.IGX_OK, (row0, par, rc)
+                    assert patch.timing()['n_launches'] == 2
                 one = patch.load_vector_expr(src, parametric=par)
+                if kvs is fused[0]:
+                    assert np.array_equal(one.ravel(), direct)
                 patch.eval_function_expr(src, parametric=par)
                 two = patch.load_vector_resident(to_host=True)
                 assert one.shape == two.shape and np.abs(one - two).max() <= 1e-13 * np.abs(two).max(), (len(kvs), row0, par)

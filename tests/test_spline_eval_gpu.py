@@ -9,6 +9,8 @@ import pytest
 
 from pyiga_amd import _lib, assemblers, bspline, geometry
 
+import _lv_cases as lc
+
 pytestmark = pytest.mark.gpu
 
 EPS = np.finfo(np.float64).eps
@@ -87,16 +89,32 @@ def _reference(patch, kvs, geo, c):
     return val, tol_val, gpar, tol_d, gphys, tol_phys
 
 
-@pytest.mark.parametrize('geo_name', ['identity', 'annulus'])
-@pytest.mark.parametrize('shape', sorted(SHAPES))
-def test_spline_eval_against_numpy(shape, geo_name):
-    degrees, spans, double = SHAPES[shape]
-    kvs = _kvs(degrees, spans, double)
+# A dense 3x3 matrix, all nine entries non-zero and of distinct magnitude, det A = 0.94: the Jacobian of the mapped cube has no
+# zero entry, so every cofactor of the kernel's inverse matters (line x annulus has four zero entries: a swapped index in five of
+# the nine cofactors cannot show there)
+DENSE_A = np.array([[1.0, 0.3, -0.22], [0.15, 0.9, 0.25], [-0.1, 0.2, 1.2]])
+SHEAR_A = np.array([[1.1, 0.35], [-0.2, 0.8]])
+
+
+def _dense_geo(name, dim):
+    """'affine': the unit cube's (square's) multilinear control net mapped by DENSE_A (SHEAR_A); 'bent': the same with a
+    multiquadratic net and the interior control point moved."""
+    A = DENSE_A if dim == 3 else SHEAR_A
+    if name == 'affine':
+        return (geometry.unit_cube() if dim == 3 else geometry.unit_square()).apply_matrix(A)
+    kv = bspline.make_knots(2, 0.0, 1.0, 1)
+    g = np.array([0.0, 0.5, 1.0])
+    pts = np.stack(np.meshgrid(*(dim * (g,)), indexing='ij')[::-1], axis=-1)          # (x, y, z) order: x belongs to the last axis
+    ctrl = pts @ A.T
+    ctrl[(1,) * dim] += np.array([0.1, -0.07, 0.05])[:dim]
+    return bspline.BSplineFunc(dim * (kv,), ctrl)
+
+
+def _check_against_numpy(kvs, geo, tag, seed, affine=None):
     dim = len(kvs)
-    geo = _geo(geo_name, dim)
     patch = assemblers.DevicePatch(kvs, geo)
     try:
-        rng = np.random.default_rng(1234 + len(shape))
+        rng = np.random.default_rng(seed)
         c = rng.uniform(-1.0, 1.0, size=tuple(kv.numdofs for kv in kvs))
         val, tol_val, gpar, tol_d, gphys, tol_phys = _reference(patch, kvs, geo, c)
         d_c = patch.upload_dofs(c)
@@ -107,13 +125,69 @@ def test_spline_eval_against_numpy(shape, geo_name):
         assert full.shape == (1 + dim,) + val.shape
         err1 = abs(full[0] - val).max()
         errg = abs(np.moveaxis(full[1:], 0, -1) - gphys).max()
-        print('%s %s: value %.2e / %.2e (tol %.2e)  gradient %.2e (tol %.2e)' % (shape, geo_name, err0, err1, tol_val, errg, tol_phys))
+        print('%s: value %.2e / %.2e (tol %.2e)  gradient %.2e (tol %.2e)' % (tag, err0, err1, tol_val, errg, tol_phys))
         assert err0 <= tol_val and err1 <= tol_val
         assert np.array_equal(only[0], full[0]), 'the value does not depend on whether the gradient is asked for'
         assert errg <= tol_phys
-        if geo_name == 'identity':        # J = I: the outputs ARE the parametric derivatives, each within its own bound
-            for r in range(dim):
-                assert abs(full[1 + r] - gpar[..., r]).max() <= dim * tol_d[r]
+        if affine is not None:            # J = A everywhere: the gradient is A^-T times the parametric one, in numpy alone
+            Ainv = np.linalg.inv(affine)
+            gA = np.einsum('cr,...c->...r', Ainv, gpar)
+            assert abs(np.moveaxis(full[1:], 0, -1) - gA).max() <= max(tol_d) * dim * abs(Ainv).max()
+        return full, gpar, tol_d
+    finally:
+        patch.close()
+
+
+@pytest.mark.parametrize('geo_name', ['identity', 'annulus'])
+@pytest.mark.parametrize('shape', sorted(SHAPES))
+def test_spline_eval_against_numpy(shape, geo_name):
+    degrees, spans, double = SHAPES[shape]
+    kvs = _kvs(degrees, spans, double)
+    dim = len(kvs)
+    full, gpar, tol_d = _check_against_numpy(kvs, _geo(geo_name, dim), '%s %s' % (shape, geo_name), 1234 + len(shape))
+    if geo_name == 'identity':        # J = I: the outputs ARE the parametric derivatives, each within its own bound
+        for r in range(dim):
+            assert abs(full[1 + r] - gpar[..., r]).max() <= dim * tol_d[r]
+
+
+@pytest.mark.parametrize('geo_name', ['affine', 'bent'])
+@pytest.mark.parametrize('shape', ['3d_p2', '3d_mixed_double', '3d_last129', '2d_double'])
+def test_spline_eval_with_a_dense_jacobian(shape, geo_name):
+    """A geometry whose Jacobian has no zero entry: every cofactor of the inverse in k_spline12 enters the gradient."""
+    degrees, spans, double = SHAPES[shape]
+    kvs = _kvs(degrees, spans, double)
+    dim = len(kvs)
+    geo = _dense_geo(geo_name, dim)
+    grid = tuple(np.array([0.3, 0.8]) for _ in range(dim))
+    assert (abs(geo.grid_jacobian(grid)) > 0.05).all()
+    A = (DENSE_A if dim == 3 else SHEAR_A) if geo_name == 'affine' else None
+    _check_against_numpy(kvs, geo, '%s %s' % (shape, geo_name), 4321 + len(shape), affine=A)
+
+
+@pytest.mark.parametrize('sid', [c.id for c in lc.SPLINE_CASES])
+def test_spline_launch_shapes(sid):
+    """The launch shapes of k_spline12 the other cases do not reach (tests/_lv_cases.py restates spline12_waves and lpw, and
+    tests/test_lv_coverage_cpu.py ties the restatement to the source): a wave walking 8 lines, blocks of 2 and of 1 wave, and the
+    refusal on the host when not even one wave's lines fit the LDS (nothing is launched; the patch serves the value afterwards)."""
+    case = lc.SPLINE_BY_ID[sid]
+    kvs = _kvs(case.degrees, case.spans)
+    dim = case.dim
+    assert kvs[-1].numdofs == case.nlast()
+    geo = _geo('identity', dim)
+    if case.waves > 0:
+        full, gpar, tol_d = _check_against_numpy(kvs, geo, sid, 99 + len(sid))
+        for r in range(dim):
+            assert abs(full[1 + r] - gpar[..., r]).max() <= dim * tol_d[r]
+        return
+    patch = assemblers.DevicePatch(kvs, geo)
+    try:
+        c = np.random.default_rng(11).uniform(-1.0, 1.0, size=tuple(kv.numdofs for kv in kvs))
+        d_c = patch.upload_dofs(c)
+        with pytest.raises(_lib.IgxError) as e:
+            patch.eval_spline(d_c, want_grad=True)
+        assert e.value.code == _lib.IGX_ERR_UNSUPPORTED
+        val, tol_val = _reference(patch, kvs, geo, c)[:2]
+        assert abs(patch.eval_spline(d_c, want_grad=False, to_host=True)[0] - val).max() <= tol_val
     finally:
         patch.close()
 
