@@ -352,14 +352,19 @@ def test_row_slabs_equal_full(iga, d, p, n, G, algo, monkeypatch):
 
 def test_final_stage_variants_agree(iga, monkeypatch):
     """The three final-stage kernels (quadrature-lane: default where it applies; LDS-table VALU; matrix-core)
-    give the same matrix, each exactly symmetric."""
+    give the same matrix, each exactly symmetric -- and each the oracle's (a mistake the three share does not pass); degrees 2
+    to 5.  (Every instantiation of the three, one case each: tests/_stage_cases.py, tests/test_stage_kernels_gpu.py.)"""
+    from oracle import iga_oracle as orc
     monkeypatch.setenv('IGX_DEBUG_POISON', '1')
     mk = iga.bspline.make_knots
     cases = [((mk(2, 0., 1., 10),) * 3, 'twisted_box'), ((mk(4, 0., 1., 5),) * 3, 'cylinder'),
              ((mk(3, 0., 1., 40), mk(3, 0., 1., 33)), 'quarter_annulus'),
-             ((mk(2, 0., 1., 3, mult=2), mk(2, 0., 1., 3), mk(3, 0., 1., 4)), 'cylinder')]
+             ((mk(2, 0., 1., 3, mult=2), mk(2, 0., 1., 3), mk(3, 0., 1., 4)), 'cylinder'),
+             ((mk(5, 0., 1., 2), mk(5, 0., 1., 2), mk(5, 0., 1., 3)), 'cylinder')]
     for kvs, gname in cases:
+        okvs = tuple(orc.KnotVector(np.asarray(kv.kv), kv.p) for kv in kvs)
         for kind in ('mass', 'stiffness'):
+            R = orc.assemble(kind, okvs, getattr(orc, 'geo_' + gname)(), nthreads=8)
             out = {}
             for sel in ('q', 'valu', 'mfma'):
                 monkeypatch.setenv('IGX_FINAL', sel)
@@ -368,6 +373,7 @@ def test_final_stage_variants_agree(iga, monkeypatch):
                 patch.close()
                 assert not np.isnan(out[sel].data).any()
                 assert abs(out[sel] - out[sel].T).max() == 0.0
+                assert out[sel].nnz == R.nnz and rel_maxdiff(out[sel], R) <= RTOL, (sel, kind, gname, rel_maxdiff(out[sel], R))
             assert rel_maxdiff(out['mfma'], out['valu']) <= 1e-14
             assert rel_maxdiff(out['q'], out['valu']) <= 1e-14
     monkeypatch.delenv('IGX_FINAL')
