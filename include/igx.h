@@ -42,6 +42,8 @@
  *                                         pyiga/solvers.py:366-473 (linear M u' = f - K u, one patch, on the device)
  *   igx_solver_set_stepper / _step_*   <- sdirk21 .. esdirk34 with adaptive steps, ros3p .. rosi2p1 (rosenbrock_step)
  *                                         pyiga/solvers.py:430-435, 475-534, 684-939 (a session of attempts)
+ *   igx_solver_eig_*                   <- scipy.sparse.linalg.eigsh / lobpcg on the two host matrices of a patch
+ *                                         (the lowest eigenpairs of K x = lam M x; block LOBPCG, the pieces on the device)
  */
 #ifndef IGX_H
 #define IGX_H
@@ -723,7 +725,76 @@ int  igx_solver_step_state(igx_solver *solver, int which, double *out);
 int  igx_solver_error_ratio_d(igx_solver *solver, int nv, const double *coef, const double *const *d_v, const double *d_x,
                               double tol, double *r);
 
-/* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers.  The factors are dense, row-major, m[k] x n[k]
+/* --- Generalized eigenproblems: the pieces of a block LOBPCG for K x = lam M x ------------------------
+   On a solver made by igx_solver_create_parabolic (symmetric) that has taken M and K (igx_solver_take_values); no C is needed.
+   A block holds m <= 16 vectors of all dofs, row-major with the columns interleaved: entry (I, j) at I * mb + j, mb the row
+   stride: 4, 8 or 16, the smallest of them >= m.  Padding columns are zero and never enter a Gram matrix; the rows of fixed dofs
+   are zero.  The host drives the iteration (Gram matrices and norms come down, coefficient matrices go up); the device keeps the
+   blocks of a session under the ids below.  Every reduction has a fixed order and no atomics: the same calls give the same bits.
+       igx_solver_eig_set_precond, igx_solver_eig_begin, then products / gram / combine / residuals / precond in any order,
+       igx_solver_eig_download, igx_solver_eig_info, igx_solver_eig_end.
+   Calls on a solver that is not such a parabolic one, or (but for set_precond and the _d calls) outside a session: IGX_ERR_ARG. */
+enum { IGX_EIG_X = 0, IGX_EIG_KX, IGX_EIG_MX, IGX_EIG_W, IGX_EIG_KW, IGX_EIG_MW, IGX_EIG_P, IGX_EIG_KP, IGX_EIG_MP, IGX_EIG_R,
+       IGX_EIG_NBLOCKS };
+typedef struct {
+    int32_t m, mb;                 /* columns and row stride of the session's blocks */
+    int32_t products;              /* block products (k_spmm2 launches) */
+    int32_t grams, combines, residuals, preconds;    /* launches of the other phases */
+    int32_t reserved;
+    int64_t n_free;
+    float products_ms;             /* timed != 0: device time per phase, summed over the session */
+    float gram_ms;
+    float combine_ms;
+    float residual_ms;
+    float precond_ms;
+    float reserved2;
+} igx_eig_info;
+/* The preconditioner of igx_solver_eig_precond and igx_solver_eig_precond_d: IGX_PRECOND_NONE (the masked copy),
+   IGX_PRECOND_JACOBI (the diagonal of K) or IGX_PRECOND_KRON with factors as igx_solver_set_precond takes them (the free dofs must
+   be exactly the box).  Independent of igx_solver_set_precond. */
+int  igx_solver_eig_set_precond(igx_solver *solver, int precond, const int32_t *box_lo, const int32_t *box_hi,
+                                const double *const *U, const double *const *lam, int lam_mode);
+/* Starts a session with blocks of m columns (1 <= m <= 16): X0 (host, nrows_total x m, row-major) goes into IGX_EIG_X with its
+   fixed rows cleared, every other block is cleared.  timed != 0: events around every phase (igx_eig_info). */
+int  igx_solver_eig_begin(igx_solver *solver, int m, const double *X0, int timed);
+/* dst_K = R K R^T src and dst_M = R M R^T src in one pass over both value arrays (k_spmm2); dst_K or dst_M < 0: the other
+   matrix alone.  src must differ from both. */
+int  igx_solver_eig_products(igx_solver *solver, int src, int dst_K, int dst_M);
+/* G = [A_0 .. A_{na-1}]^T [B_0 .. B_{nb-1}] over the free dofs (na, nb from 1 to 3; k_gram and its finish) to the host:
+   (na m) x (nb m), row-major. */
+int  igx_solver_eig_gram(igx_solver *solver, int na, const int32_t *a, int nb, const int32_t *b, double *G);
+/* nupd (1 or 2) combinations: block dst[u] = sum_{j < nsrc[u]} block src[3 u + j] . coef[(3 u + j) m m ..] (m x m, row-major:
+   entry (a, b) takes column a of the source into column b), nsrc[u] from 1 to 3.  triple != 0: dst and src name blocks among
+   X, W, P and the same combination is applied to their K and M companions.  Every source is read before any destination is
+   written (the results go to scratch blocks whose pointers are swapped in): a destination may be among the sources. */
+int  igx_solver_eig_combine(igx_solver *solver, int nupd, const int32_t *dst, const int32_t *nsrc, const int32_t *src,
+                            const double *coef, int triple);
+/* IGX_EIG_R = KX - MX diag(lam) (lam: host, m) and, in the same kernel, the column 2-norms of R and of KX over the free dofs
+   (host, m each). */
+int  igx_solver_eig_residuals(igx_solver *solver, const double *lam, double *rnorm, double *knorm);
+/* block dst = T block src, column by column, T the preconditioner of igx_solver_eig_set_precond; src != dst. */
+int  igx_solver_eig_precond(igx_solver *solver, int src, int dst);
+/* The first k <= m columns of a block to the host (nrows_total x k, row-major). */
+int  igx_solver_eig_download(igx_solver *solver, int block, int k, double *out);
+int  igx_solver_eig_info(igx_solver *solver, igx_eig_info *info);
+/* Ends the session and frees its blocks (the preconditioner set last stays). */
+int  igx_solver_eig_end(igx_solver *solver);
+/* The pieces on device buffers of nrows_total * mb doubles (mb 4, 8 or 16; 16-byte aligned), outside any session.
+   products_d: d_X is masked first (a copy), then d_YK = R K R^T X and d_YM = R M R^T X; one of them may be NULL.
+   gram_d: as igx_solver_eig_gram with the first m columns of the blocks d_A[0..na) and d_B[0..nb).
+   combine_d: d_Y = sum_{j < nsrc} d_S[j] . coef[j] (coef: host, nsrc x m x m); d_Y must not be a source.
+   residuals_d: d_R = d_KX - d_MX diag(lam) and the two column norms (m each).
+   precond_d: d_Z = T d_R; different buffers. */
+int  igx_solver_eig_products_d(igx_solver *solver, int mb, const double *d_X, double *d_YK, double *d_YM);
+int  igx_solver_eig_gram_d(igx_solver *solver, int mb, int m, int na, const double *const *d_A, int nb, const double *const *d_B,
+                           double *G);
+int  igx_solver_eig_combine_d(igx_solver *solver, int mb, int m, int nsrc, const double *const *d_S, const double *coef,
+                              double *d_Y);
+int  igx_solver_eig_residuals_d(igx_solver *solver, int mb, int m, const double *d_KX, const double *d_MX, const double *lam,
+                                double *d_R, double *rnorm, double *knorm);
+int  igx_solver_eig_precond_d(igx_solver *solver, int mb, const double *d_R, double *d_Z);
+
+/* Kronecker product  y = D^-1 (B_0 (x) B_1 [(x) B_2]) x  on device buffers. The factors are dense, row-major, m[k] x n[k]
    (rectangular allowed).  x and y are tensors of shape (n_0, .., n_{dim-1}, batch) and (m_0, .., batch), addressed through an
    element offset and four strides (axis 3 = the trailing batch axis), so a sub-box of a longer vector can be read or written.
    D: lam_mode 0 none, IGX_KRON_SUM / IGX_KRON_PRODUCT of d_lam[k] (m[k] each) at the output index.  d_work: 2 * W doubles with

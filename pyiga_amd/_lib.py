@@ -131,6 +131,21 @@ class StepInfo(C.Structure):
     ]
 
 
+IGX_EIG_BLOCKS = {'X': 0, 'KX': 1, 'MX': 2, 'W': 3, 'KW': 4, 'MW': 5, 'P': 6, 'KP': 7, 'MP': 8, 'R': 9}
+
+
+class EigInfo(C.Structure):
+    _fields_ = [
+        ('m', C.c_int32), ('mb', C.c_int32), ('products', C.c_int32), ('grams', C.c_int32), ('combines', C.c_int32),
+        ('residuals', C.c_int32), ('preconds', C.c_int32), ('reserved', C.c_int32), ('n_free', C.c_int64),
+        ('products_ms', C.c_float), ('gram_ms', C.c_float), ('combine_ms', C.c_float), ('residual_ms', C.c_float),
+        ('precond_ms', C.c_float), ('reserved2', C.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
 class KronDesc(C.Structure):
     _fields_ = [
         ('dim', C.c_int32), ('m', C.c_int32 * 3), ('n', C.c_int32 * 3), ('d_B', C.c_void_p * 3),
@@ -248,6 +263,21 @@ SYMBOLS = [
     ('igx_solver_step_accept', C.c_int, [C.c_void_p]),
     ('igx_solver_step_state', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_solver_error_ratio_d', C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, _dp]),
+    ('igx_solver_eig_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
+    ('igx_solver_eig_begin', C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
+    ('igx_solver_eig_products', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ('igx_solver_eig_gram', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), _dp]),
+    ('igx_solver_eig_combine', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_int]),
+    ('igx_solver_eig_residuals', C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    ('igx_solver_eig_precond', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ('igx_solver_eig_download', C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
+    ('igx_solver_eig_info', C.c_int, [C.c_void_p, C.POINTER(EigInfo)]),
+    ('igx_solver_eig_end', C.c_int, [C.c_void_p]),
+    ('igx_solver_eig_products_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('igx_solver_eig_gram_d', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), _dp]),
+    ('igx_solver_eig_combine_d', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _dp, C.c_void_p]),
+    ('igx_solver_eig_residuals_d', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p, _dp, _dp]),
+    ('igx_solver_eig_precond_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ('igx_kron_apply_d', C.c_int, [C.c_void_p, C.POINTER(KronDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
 ]
 

@@ -1813,3 +1813,497 @@ class NewtonSystem(PatchSystem):
         A = self.patch.csr('form')
         _lib.check(_lib.load().igx_solver_values_changed(self._live()), 'igx_solver_values_changed')     # (the solver's values are new)
         return A
+
+
+################################################################################
+# Generalized eigenproblems of one patch on the device: block LOBPCG
+################################################################################
+
+EIG_WIDTHS = (4, 8, 16)                  # the compiled row strides MB of the block kernels (csrc/solve.hip)
+EIG_MAX_BLOCK = EIG_WIDTHS[-1]
+# A projected mass Gram matrix, scaled to a unit diagonal, counts as positive definite when its smallest eigenvalue is above
+# this: below it the columns of [X W P] are dependent to within sqrt(eps) and the projected pencil loses half of its digits.
+RR_MIN_EIG = 1e-9
+
+
+def eig_width(m):
+    """The row stride of a block of `m` columns: the smallest compiled width >= m."""
+    for w in EIG_WIDTHS:
+        if m <= w:
+            return w
+    raise ValueError('block of %d columns: at most %d' % (m, EIG_MAX_BLOCK))
+
+
+def _sym(G):
+    G = np.asarray(G, dtype=np.float64)
+    return 0.5 * (G + G.T)
+
+
+def _unit_diagonal(G):
+    """``(s, s G s)`` with ``s = diag(G)^-1/2``, or None when G has a non-finite entry or a non-positive diagonal one."""
+    if not np.all(np.isfinite(G)):
+        return None
+    d = np.diag(G)
+    if not np.all(d > 0.0):
+        return None
+    s = 1.0 / np.sqrt(d)
+    return s, G * s[:, None] * s[None, :]
+
+
+def rayleigh_ritz(GK, GM, m):
+    """The `m` lowest eigenpairs of the projected pencil ``GK c = lam GM c`` (``scipy.linalg.eigh``): ``(lam, C, ok)`` with
+    ``C^T GM C = I``.  Both matrices are symmetrised; GM is scaled to a unit diagonal first, so that blocks of very different
+    norms do not decide its conditioning.  ``ok`` is False, and lam and C are None, when a matrix is not finite, GM is not
+    positive definite to ``RR_MIN_EIG`` on that scale, or LAPACK fails: nothing is raised and nothing half-computed comes back."""
+    GK, GM = _sym(GK), _sym(GM)
+    sc = _unit_diagonal(GM)
+    if sc is None or not np.all(np.isfinite(GK)):
+        return None, None, False
+    s, GMs = sc
+    GKs = GK * s[:, None] * s[None, :]
+    try:
+        if scipy.linalg.eigvalsh(GMs)[0] <= RR_MIN_EIG:
+            return None, None, False
+        lam, C = scipy.linalg.eigh(GKs, GMs)
+    except (scipy.linalg.LinAlgError, ValueError):
+        return None, None, False
+    if not (np.all(np.isfinite(lam)) and np.all(np.isfinite(C))):
+        return None, None, False
+    return lam[:m].copy(), np.ascontiguousarray(s[:, None] * C[:, :m]), True
+
+
+def _inv_chol_t(G):
+    """``L^-T`` of the Cholesky factor ``G = L L^T`` (so that ``B L^-T`` is orthonormal when G is the Gram matrix of B), or None
+    when G is not numerically positive definite (judged on the unit-diagonal scale, as rayleigh_ritz does)."""
+    sc = _unit_diagonal(_sym(G))
+    if sc is None:
+        return None
+    s, Gs = sc
+    try:
+        if scipy.linalg.eigvalsh(Gs)[0] <= RR_MIN_EIG:
+            return None
+        L = scipy.linalg.cholesky(Gs, lower=True)
+    except (scipy.linalg.LinAlgError, ValueError):
+        return None
+    return np.ascontiguousarray(s[:, None] * scipy.linalg.solve_triangular(L, np.eye(L.shape[0]), lower=True).T)
+
+
+def lobpcg_loop(ops, m, k, tol, maxiter):
+    """Knyazev's block LOBPCG for the `k` lowest eigenpairs of ``K x = lam M x`` with a block of `m` columns, on an operations
+    object that keeps the blocks wherever they live (EigenSystem: on the device; the tests: numpy arrays).  Only Gram matrices
+    and residual norms come back from `ops`, only coefficient matrices go to it:
+
+    - ``ops.start()``: the masked start block becomes ``X``;
+    - ``ops.products(name)``: ``K<name>``, ``M<name>`` from block ``name`` ('X', 'W'), one pass over both matrices;
+    - ``ops.gram(A, B)``: the Gram matrix of the concatenated blocks named in the lists A and B;
+    - ``ops.combine(updates, triple)``: for every ``(dst, srcs, coeffs)`` the block ``sum_j srcs[j] @ coeffs[j]`` -- all read
+      before any is written; `triple`: the same for the K and M companions of the named blocks;
+    - ``ops.residuals(lam)``: ``R = KX - MX diag(lam)``; returns the column norms of R and of KX;
+    - ``ops.precond(src, dst)``.
+
+    Pair i has converged when ``||R_i|| <= tol ||K X_i||``; the loop stops when the first k have.  A failed Cholesky or projected
+    eigh drops P for that iteration (a restart); two restarts in consecutive iterations end the solve unconverged.
+    Returns ``(lam, info)`` with all m Ritz values; the Ritz vectors are the block ``X`` of `ops`."""
+    eye = np.eye(m)
+    info = dict(iterations=0, restarts=0, products=0, block=m, converged=np.zeros(k, dtype=bool), residuals=np.full(k, np.inf),
+                failed=None)
+
+    def fail(why):
+        info['failed'] = why
+        return np.full(m, np.nan), info
+
+    ops.start()
+    ops.products('X')
+    info['products'] += 1
+    Ci = _inv_chol_t(ops.gram(['X'], ['MX']))
+    if Ci is None:
+        return fail('the start block is not of full rank in the mass inner product')
+    ops.combine([('X', ['X'], [Ci])], True)
+    lam, C, ok = rayleigh_ritz(ops.gram(['X'], ['KX']), ops.gram(['X'], ['MX']), m)
+    if not ok:
+        return fail('the Rayleigh-Ritz step on the start block failed')
+    ops.combine([('X', ['X'], [C])], True)
+    have_p, last_restart = False, -2
+
+    def restart(it):
+        nonlocal have_p, last_restart
+        info['restarts'] += 1
+        again = last_restart == it - 1
+        last_restart = it
+        have_p = False
+        return again
+
+    it = 0
+    while True:
+        rn, kn = ops.residuals(lam)
+        rn, kn = np.asarray(rn)[:m], np.asarray(kn)[:m]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            rel = np.where(kn > 0.0, rn / kn, np.where(rn == 0.0, 0.0, np.inf))
+        info['residuals'] = rel[:k].copy()
+        info['converged'] = rn[:k] <= tol * kn[:k]
+        if info['converged'].all() or it >= maxiter:
+            break
+        it += 1
+        info['iterations'] = it
+        ops.precond('R', 'W')
+        ops.combine([('W', ['W', 'X'], [eye, -ops.gram(['MX'], ['W'])])], False)          # W -= X (X^T M W)
+        ops.products('W')
+        info['products'] += 1
+        Ci = _inv_chol_t(ops.gram(['W'], ['MW']))
+        if Ci is None:                                          # (W is dependent: nothing to iterate with)
+            if restart(it):
+                info['failed'] = 'two restarts in a row'
+                break
+            continue
+        ops.combine([('W', ['W'], [Ci])], True)
+        names = ['X', 'W'] + (['P'] if have_p else [])
+        GK = ops.gram(names, ['K' + b for b in names])
+        GM = ops.gram(names, ['M' + b for b in names])
+        lam_new, C, ok = rayleigh_ritz(GK, GM, m)
+        if not ok and have_p:                                   # this iteration runs without P
+            if restart(it):
+                info['failed'] = 'two restarts in a row'
+                break
+            names = ['X', 'W']
+            lam_new, C, ok = rayleigh_ritz(GK[:2 * m, :2 * m], GM[:2 * m, :2 * m], m)
+        if not ok:
+            if restart(it):
+                info['failed'] = 'two restarts in a row'
+                break
+            continue
+        lam = lam_new
+        coeffs = [C[j * m:(j + 1) * m] for j in range(len(names))]
+        ops.combine([('X', names, coeffs), ('P', names[1:], coeffs[1:])], True)
+        Ci = _inv_chol_t(ops.gram(['P'], ['MP']))
+        if Ci is None:                                          # the next iteration runs without P
+            if restart(it):
+                info['failed'] = 'two restarts in a row'
+                break
+            continue
+        ops.combine([('P', ['P'], [Ci])], True)
+        have_p = True
+    return lam, info
+
+
+def _symmetric_problem(problem, kvs, args):
+    """Is the matrix of `problem` known to be symmetric before any device work?  The built-in stiffness and mass forms are; a
+    general form string is when its traced coefficient table is (the test NewtonSystem applies to its Jacobian); an assembler
+    class or object when its kind is one of the two."""
+    from . import forms
+    kind = _form_kind(problem)
+    if kind in ('mass', 'stiffness'):
+        return True
+    if kind != 'form' or not isinstance(problem, str):
+        return False
+    try:
+        return _symmetric_traced_table(forms.symbolic_table(problem, len(kvs), dict(args)))
+    except Exception:
+        return False
+
+
+class _DeviceEigOps:
+    """The operations of ``lobpcg_loop`` on the blocks of a device session (``igx_solver_eig_*``)."""
+
+    def __init__(self, handle, n, m, X0, timed):
+        self.h, self.n, self.m = handle, n, m
+        self.X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        self.timed = 1 if timed else 0
+        self.lib = _lib.load()
+
+    @staticmethod
+    def _ids(names):
+        return (C.c_int32 * len(names))(*[_lib.IGX_EIG_BLOCKS[b] for b in names])
+
+    def start(self):
+        _lib.check(self.lib.igx_solver_eig_begin(self.h, self.m, _lib.dptr(self.X0), self.timed), 'igx_solver_eig_begin')
+
+    def products(self, name):
+        B = _lib.IGX_EIG_BLOCKS
+        _lib.check(self.lib.igx_solver_eig_products(self.h, B[name], B['K' + name], B['M' + name]), 'igx_solver_eig_products')
+
+    def gram(self, A, B):
+        G = np.empty((len(A) * self.m, len(B) * self.m))
+        _lib.check(self.lib.igx_solver_eig_gram(self.h, len(A), self._ids(A), len(B), self._ids(B), _lib.dptr(G)), 'igx_solver_eig_gram')
+        return G
+
+    def combine(self, updates, triple):
+        dst = self._ids([u[0] for u in updates])
+        nsrc = (C.c_int32 * len(updates))(*[len(u[1]) for u in updates])
+        src = (C.c_int32 * (3 * len(updates)))()
+        for i, (_, names, _) in enumerate(updates):
+            for j, b in enumerate(names):
+                src[3 * i + j] = _lib.IGX_EIG_BLOCKS[b]
+        coef = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.float64).reshape(-1) for u in updates for c in u[2]]))
+        _lib.check(self.lib.igx_solver_eig_combine(self.h, len(updates), dst, nsrc, src, _lib.dptr(coef), 1 if triple else 0),
+                   'igx_solver_eig_combine')
+
+    def residuals(self, lam):
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        rn, kn = np.empty(self.m), np.empty(self.m)
+        _lib.check(self.lib.igx_solver_eig_residuals(self.h, _lib.dptr(lam), _lib.dptr(rn), _lib.dptr(kn)), 'igx_solver_eig_residuals')
+        return rn, kn
+
+    def precond(self, src, dst):
+        B = _lib.IGX_EIG_BLOCKS
+        _lib.check(self.lib.igx_solver_eig_precond(self.h, B[src], B[dst]), 'igx_solver_eig_precond')
+
+    def download(self, name, k):
+        out = np.empty((self.n, k))
+        _lib.check(self.lib.igx_solver_eig_download(self.h, _lib.IGX_EIG_BLOCKS[name], k, _lib.dptr(out)), 'igx_solver_eig_download')
+        return out
+
+    def info(self):
+        info = _lib.EigInfo()
+        _lib.check(self.lib.igx_solver_eig_info(self.h, C.byref(info)), 'igx_solver_eig_info')
+        return info.as_dict()
+
+    def end(self):
+        _lib.check(self.lib.igx_solver_eig_end(self.h), 'igx_solver_eig_end')
+
+
+def default_eig_block(k):
+    """``k + max(2, k // 2)`` columns (the guard columns keep the k-th pair away from the edge of the block), at most 16."""
+    return min(EIG_MAX_BLOCK, k + max(2, k // 2))
+
+
+def _check_eig_args(k, block, n_free):
+    if k < 1:
+        raise ValueError('k must be at least 1, not %r' % (k,))
+    if block > EIG_MAX_BLOCK:
+        raise ValueError('block of %d columns: at most %d' % (block, EIG_MAX_BLOCK))
+    if k > block:
+        raise ValueError('k = %d pairs need a block of at least k columns, not %d' % (k, block))
+    if 3 * block > n_free:
+        raise ValueError('a block of %d columns needs at least %d free dofs, the problem has %d' % (block, 3 * block, n_free))
+
+
+class EigenSystem(_DeviceSystem):
+    """The lowest eigenpairs of ``K x = lam M x`` on the free dofs of one patch (x = 0 on the dofs of `bcs`), by block LOBPCG
+    with both matrices, the blocks and the preconditioner in device memory.
+
+    M is the mass matrix of the patch; K the stiffness matrix (`problem` None) or the matrix of any form that ``FormSystem``
+    accepts and whose traced coefficient table is symmetric (`problem`, with `args` / `inputs` its inputs).  Both are assembled on
+    the device and handed to the solver as ``ParabolicSystem`` does; no ``C = M + tau gamma K`` is formed.  `bcs`:
+    ``(indices, values)`` or just the indices; only the indices are used.
+
+    ``solve(k)`` returns ``(lam, U)``: the k smallest eigenvalues in ascending order and ``U`` of shape ``(prod(ndofs), k)`` with
+    ``U^T M U = I`` and zeros on the fixed dofs; ``info`` holds the statistics.  ``block_products``, ``gram``, ``combine``,
+    ``residuals`` and ``apply_precond`` run the block kernels alone on host arrays of shape ``(n, m)``."""
+
+    def __init__(self, kvs, geo, bcs=None, problem=None, args=None, device=None, **inputs):
+        from . import assemble
+        args = dict(args or {})
+        args.update(inputs)
+        if geo is not None:
+            args.setdefault('geo', geo)
+        self.kvs = tuple(kvs)
+        self.geo = geo
+        if problem is not None:
+            _check_device_form(problem, self.kvs, args)
+            if not _symmetric_problem(problem, self.kvs, args):
+                raise ValueError('EigenSystem: %r is not known to be symmetric (the built-in stiffness and mass forms are, and a '
+                                 'form string whose traced coefficient table is)' % (problem,))
+        self.ndofs = tuple(kv.numdofs for kv in self.kvs)
+        self.n = int(np.prod(self.ndofs))
+        if bcs is None:
+            idx = np.zeros(0, dtype=np.int64)
+        elif isinstance(bcs, tuple) and len(bcs) == 2 and np.ndim(bcs[0]) >= 1:
+            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
+        else:
+            idx = np.asarray(bcs, dtype=np.int64).ravel()
+        idx = np.unique(idx)
+        if idx.size and (idx[0] < 0 or idx[-1] >= self.n):
+            raise ValueError('fixed dof out of range')
+        if _form_kind(problem) == 'stiffness' and idx.size == 0:
+            raise ValueError('EigenSystem: the stiffness matrix without any fixed dof is singular (the constants), and the relative '
+                             "stopping rule ||r|| <= tol ||K x|| has no scale there.  Shift instead: problem='(inner(grad(u), "
+                             "grad(v)) + u*v) * dx', then subtract 1 from the eigenvalues")
+        self.n_free = self.n - idx.size
+        if problem is None:
+            self.patch = assemblers.DevicePatch(self.kvs, geo, device=device)
+            self._own_patch = True
+            self.kind = 'stiffness'
+        else:
+            self.assembler = assemble.instantiate_assembler(problem, self.kvs, args)
+            self._own_patch = self.assembler is not problem
+            self.patch = self.assembler.patch
+            self.kind = self.assembler._kind
+        self._ctx = self.patch.ctx
+        try:
+            self._attach('igx_solver_create_parabolic', (self.patch.handle, _lib.KINDS[self.kind], 1), (idx, np.zeros(idx.size)),
+                         'cg', 'cg')
+            self.box = dirichlet_box(self.ndofs, self.bc_indices)
+            lib = _lib.load()
+            self.patch.assemble(self.kind, to_host=False)            # the values stay on the device and change hands
+            _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_OPERATOR), 'igx_solver_take_values')
+            self.patch.assemble('mass', to_host=False)
+            _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_MASS), 'igx_solver_take_values')
+        except BaseException:
+            self._release()
+            self._drop_owner()
+            raise
+        self._eig_precond = False                                    # (no preconditioner of the eigen pieces set yet)
+
+    def _drop_owner(self):
+        if getattr(self, 'patch', None) is not None and self._own_patch:
+            self.patch.close()
+        self.patch = None
+
+    @property
+    def default_precond(self):
+        return 'kron' if self.box is not None else 'jacobi'
+
+    def _kron_factors(self):
+        return fastdiag_factors(self.kvs, self.box[0], self.box[1], True)     # the parametric Laplacian of the free box
+
+    def set_precond(self, precond):
+        """The preconditioner of ``solve`` and ``apply_precond``: 'auto', 'kron', 'jacobi' or None."""
+        if precond == 'auto':
+            precond = self.default_precond
+        key = precond if precond is not None else 'none'
+        if key not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        if key == self._eig_precond:
+            return key
+        lib = _lib.load()
+        if key == 'kron':
+            if self.box is None:
+                raise ValueError("precond='kron' needs the fixed dofs to be a union of whole sides of the patch")
+            U, lam, mode = self._kron_factors()
+            lo = (C.c_int32 * 3)(*self.box[0])
+            hi = (C.c_int32 * 3)(*self.box[1])
+            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
+            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+            _lib.check(lib.igx_solver_eig_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_eig_set_precond')
+        else:
+            _lib.check(lib.igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
+        self._eig_precond = key
+        return key
+
+    def solve(self, k=6, tol=1e-8, maxiter=200, precond='auto', block=None, X0=None, seed=0, timed=False):
+        """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i M x_i|| <= tol ||K x_i||`` for the k lowest pairs.  `block`: the
+        columns iterated (default ``k + max(2, k // 2)``, at most 16); `X0`: a start block of shape ``(n, block)``, else normal
+        deviates of ``numpy.random.default_rng(seed)``.  Deterministic: the same inputs give the same bits."""
+        k = int(k)
+        m = default_eig_block(max(k, 1)) if block is None else int(block)
+        _check_eig_args(k, m, self.n_free)
+        if X0 is None:
+            X0 = np.random.default_rng(seed).standard_normal((self.n, m))
+        else:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (self.n, m):
+                raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (self.n, m)))
+        h = self._live()
+        key = self.set_precond(precond)
+        ops = _DeviceEigOps(h, self.n, m, X0, timed)
+        try:
+            lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
+            U = ops.download('X', k)
+            dev = ops.info()
+        finally:
+            ops.end()
+        info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
+        if timed:
+            info.update({name: dev[name] for name in dev if name.endswith('_ms')})
+        self.info = info
+        return lam[:k].copy(), U
+
+    # -- the pieces alone, on host arrays of shape (n, m)
+    def _upload_block(self, A):
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != self.n or not 1 <= A.shape[1] <= EIG_MAX_BLOCK:
+            raise ValueError('block of shape %r: (%d, m) with 1 <= m <= %d' % (A.shape, self.n, EIG_MAX_BLOCK))
+        return A.shape[1]
+
+    def _padded(self, A, mb):
+        P = np.zeros((self.n, mb))
+        P[:, :A.shape[1]] = A
+        return DeviceArray.from_host(self._ctx, P)
+
+    def _down(self, d, mb, m):
+        return np.ascontiguousarray(d.download().reshape(self.n, mb)[:, :m])
+
+    def block_products(self, X):
+        """``(R K R^T X, R M R^T X)`` by one pass of the block product over both matrices."""
+        h = self._live()
+        m = self._upload_block(X)
+        mb = eig_width(m)
+        d_x = self._padded(np.asarray(X, dtype=np.float64), mb)
+        d_k, d_m = DeviceArray(self._ctx, self.n * mb), DeviceArray(self._ctx, self.n * mb)
+        _lib.check(_lib.load().igx_solver_eig_products_d(h, mb, d_x.ptr, d_k.ptr, d_m.ptr), 'igx_solver_eig_products_d')
+        return self._down(d_k, mb, m), self._down(d_m, mb, m)
+
+    def block_product(self, X, which='K'):
+        """``R K R^T X`` (or ``R M R^T X``, ``which='M'``) by the one-matrix form of the block product."""
+        h = self._live()
+        m = self._upload_block(X)
+        mb = eig_width(m)
+        d_x = self._padded(np.asarray(X, dtype=np.float64), mb)
+        d_y = DeviceArray(self._ctx, self.n * mb)
+        args = (d_y.ptr, None) if which == 'K' else (None, d_y.ptr)
+        _lib.check(_lib.load().igx_solver_eig_products_d(h, mb, d_x.ptr, *args), 'igx_solver_eig_products_d')
+        return self._down(d_y, mb, m)
+
+    def gram(self, A, B):
+        """``A^T B`` over the free dofs; A and B: blocks of the same number of columns, or lists of up to three such blocks
+        (the Gram matrix of their concatenations)."""
+        h = self._live()
+        A = [A] if isinstance(A, np.ndarray) else list(A)
+        B = [B] if isinstance(B, np.ndarray) else list(B)
+        m = self._upload_block(A[0])
+        if any(self._upload_block(Z) != m for Z in A + B) or not (1 <= len(A) <= 3 and 1 <= len(B) <= 3):
+            raise ValueError('gram: one to three blocks a side, all of the same number of columns')
+        mb = eig_width(m)
+        dA = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in A]
+        dB = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in B]
+        G = np.empty((len(A) * m, len(B) * m))
+        pa = (C.c_void_p * len(dA))(*[d.ptr for d in dA])
+        pb = (C.c_void_p * len(dB))(*[d.ptr for d in dB])
+        _lib.check(_lib.load().igx_solver_eig_gram_d(h, mb, m, len(dA), pa, len(dB), pb, _lib.dptr(G)), 'igx_solver_eig_gram_d')
+        return G
+
+    def combine(self, blocks, coeffs):
+        """``sum_j blocks[j] @ coeffs[j]`` for up to three blocks of m columns and m x m coefficient matrices."""
+        h = self._live()
+        blocks, coeffs = list(blocks), [np.asarray(c, dtype=np.float64) for c in coeffs]
+        m = self._upload_block(blocks[0])
+        if not 1 <= len(blocks) <= 3 or len(coeffs) != len(blocks) or any(self._upload_block(Z) != m for Z in blocks) \
+                or any(c.shape != (m, m) for c in coeffs):
+            raise ValueError('combine: one to three blocks of m columns with an m x m coefficient matrix each')
+        mb = eig_width(m)
+        dS = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in blocks]
+        d_y = DeviceArray(self._ctx, self.n * mb)
+        ps = (C.c_void_p * len(dS))(*[d.ptr for d in dS])
+        cf = np.ascontiguousarray(np.stack(coeffs))
+        _lib.check(_lib.load().igx_solver_eig_combine_d(h, mb, m, len(dS), ps, _lib.dptr(cf), d_y.ptr), 'igx_solver_eig_combine_d')
+        return self._down(d_y, mb, m)
+
+    def residuals(self, KX, MX, lam):
+        """``(R, ||R_j||, ||KX_j||)`` with ``R = KX - MX diag(lam)`` on the free dofs (zero elsewhere), by the fused kernel."""
+        h = self._live()
+        m = self._upload_block(KX)
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if self._upload_block(MX) != m or lam.shape != (m,):
+            raise ValueError('residuals: KX and MX of m columns and m values of lam')
+        mb = eig_width(m)
+        d_k, d_m = self._padded(np.asarray(KX, dtype=np.float64), mb), self._padded(np.asarray(MX, dtype=np.float64), mb)
+        d_r = DeviceArray(self._ctx, self.n * mb)
+        rn, kn = np.empty(m), np.empty(m)
+        _lib.check(_lib.load().igx_solver_eig_residuals_d(h, mb, m, d_k.ptr, d_m.ptr, _lib.dptr(lam), d_r.ptr, _lib.dptr(rn),
+                                                          _lib.dptr(kn)), 'igx_solver_eig_residuals_d')
+        return self._down(d_r, mb, m), rn, kn
+
+    def apply_precond(self, R, precond='auto'):
+        """The preconditioner applied to every column of the block R."""
+        h = self._live()
+        m = self._upload_block(R)
+        self.set_precond(precond)
+        mb = eig_width(m)
+        d_r = self._padded(np.asarray(R, dtype=np.float64), mb)
+        d_z = DeviceArray(self._ctx, self.n * mb)
+        _lib.check(_lib.load().igx_solver_eig_precond_d(h, mb, d_r.ptr, d_z.ptr), 'igx_solver_eig_precond_d')
+        return self._down(d_z, mb, m)
+
+    def spmv(self, x):
+        raise NotImplementedError('EigenSystem holds two matrices: block_products(X) or block_product(X, which)')

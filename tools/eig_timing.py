@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Times of the block product of the device eigen-solver (pyiga_amd.solvers.EigenSystem) against the
+single-vector SpMV it replaces, and the per-phase split of one full solve:
+  c3d  3D quarter-annulus cylinder, p=3 n=48: 132 651 dofs, 45.5 M values per matrix (364 MB each: K and M together do not fit
+       the 256 MB last-level cache, so the products stream HBM)
+  c0   a small smoke case
+For m = 4, 8, 16 the new path is ONE igx_solver_eig_products_d call (the masked copy of X + k_spmm2 over both matrices), the
+baseline 2 m calls of igx_solver_spmv_d (the masked copy of x + k_spmv), m on a stiffness and m on a mass PatchSystem of the same
+patch.  Every call is timed on the device by a pair of events on the library's stream (warm-up, then REPS repetitions, the median);
+the baseline is m times the sum of the two medians.  The achieved rate of the value stream is 2 nnz 8 bytes over the time of the
+block product.  Then EigenSystem.solve(k=6, timed=True) at the same size: iterations and the device ms per phase.  Prints one
+JSON line per measurement."""
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pyiga_amd import _lib, bspline, geometry, solvers  # noqa: E402
+from pyiga_amd.operators import DeviceArray  # noqa: E402
+
+REPS, WARMUP = 30, 5
+
+
+def _case(name):
+    if name == 'c3d':
+        p, n = 3, 48
+    elif name == 'c0':
+        p, n = 2, 8
+    else:
+        raise SystemExit('unknown case %r' % name)
+    kvs = 3 * (bspline.make_knots(p, 0.0, 1.0, n),)
+    return kvs, geometry.tensor_product(geometry.line_segment(0.0, 1.0), geometry.quarter_annulus())
+
+
+def _boundary(ndofs):
+    idx = np.arange(int(np.prod(ndofs))).reshape(ndofs)
+    on = np.zeros(ndofs, dtype=bool)
+    for k, n in enumerate(ndofs):
+        for e in (0, n - 1):
+            s = [slice(None)] * len(ndofs)
+            s[k] = e
+            on[tuple(s)] = True
+    return np.sort(idx[on])
+
+
+class DeviceTimer:
+    """Device time of a call by two events on the library's stream (the HIP runtime the library itself uses)."""
+
+    def __init__(self, ctx):
+        self.hip = C.CDLL('libamdhip64.so')
+        self.stream = C.c_void_p(_lib.load().igx_stream(ctx.handle))
+        self.ev = [C.c_void_p(), C.c_void_p()]
+        for e in self.ev:
+            assert self.hip.hipEventCreate(C.byref(e)) == 0
+
+    def ms(self, call):
+        assert self.hip.hipEventRecord(self.ev[0], self.stream) == 0
+        call()
+        assert self.hip.hipEventRecord(self.ev[1], self.stream) == 0
+        assert self.hip.hipEventSynchronize(self.ev[1]) == 0
+        t = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(t), self.ev[0], self.ev[1]) == 0
+        return t.value
+
+    def median(self, call):
+        for _ in range(WARMUP):
+            call()
+        return float(np.median([self.ms(call) for _ in range(REPS)]))
+
+
+def run(name):
+    kvs, geo = _case(name)
+    ndofs = tuple(kv.numdofs for kv in kvs)
+    n = int(np.prod(ndofs))
+    fixed = _boundary(ndofs)
+    bcs = (fixed, np.zeros(fixed.size))
+    lib = _lib.load()
+    rng = np.random.default_rng(0)
+    S = solvers.EigenSystem(kvs, geo, bcs)
+    PK = solvers.PatchSystem(kvs, geo, np.zeros(n), bcs, kind='stiffness')
+    PM = solvers.PatchSystem(kvs, geo, np.zeros(n), bcs, kind='mass')
+    try:
+        nnz = int(PK.patch.nnz)
+        T = DeviceTimer(S._ctx)
+        d_x, d_y = DeviceArray.from_host(S._ctx, rng.standard_normal(n)), DeviceArray(S._ctx, n)
+        t_k = T.median(lambda: _lib.check(lib.igx_solver_spmv_d(PK.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d'))
+        t_m = T.median(lambda: _lib.check(lib.igx_solver_spmv_d(PM.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d'))
+        print(json.dumps({'case': name, 'ndofs': list(ndofs), 'nnz': nnz, 'baseline': 'igx_solver_spmv_d', 'reps': REPS,
+                          'stiffness_ms': round(t_k, 4), 'mass_ms': round(t_m, 4),
+                          'GBs': round(8e-6 * nnz / t_k, 1)}), flush=True)
+        for m in (4, 8, 16):
+            mb = solvers.eig_width(m)
+            d_X = DeviceArray.from_host(S._ctx, rng.standard_normal((n, mb)))
+            d_K, d_M = DeviceArray(S._ctx, n * mb), DeviceArray(S._ctx, n * mb)
+            t2 = T.median(lambda: _lib.check(lib.igx_solver_eig_products_d(S.handle, mb, d_X.ptr, d_K.ptr, d_M.ptr), 'igx_solver_eig_products_d'))
+            t1 = T.median(lambda: _lib.check(lib.igx_solver_eig_products_d(S.handle, mb, d_X.ptr, d_K.ptr, None), 'igx_solver_eig_products_d'))
+            base = m * (t_k + t_m)
+            print(json.dumps({'case': name, 'm': m, 'block_product_ms': round(t2, 4), 'single_products_ms': round(base, 4),
+                              'ratio_single_over_block': round(base / t2, 2), 'one_matrix_ms': round(t1, 4),
+                              'value_stream_GBs': round(16e-6 * nnz / t2, 1)}), flush=True)
+        lam, _ = S.solve(k=6, tol=1e-8, timed=True)
+        info = S.info
+        print(json.dumps({'case': name, 'solve': 'k=6 tol=1e-8', 'block': int(info['block']), 'precond': info['precond'],
+                          'iterations': int(info['iterations']), 'converged': bool(info['converged'].all()),
+                          'restarts': int(info['restarts']), 'lam': [round(float(v), 9) for v in lam],
+                          'phase_ms': {k: round(float(v), 3) for k, v in info.items() if k.endswith('_ms')}}), flush=True)
+    finally:
+        S.close()
+        PK.close()
+        PM.close()
+
+
+if __name__ == '__main__':
+    for c in (sys.argv[1:] or ['c3d']):
+        run(c)
