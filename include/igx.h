@@ -425,6 +425,9 @@ int  igx_multipatch_scatter_host(igx_multipatch *mp, int p, const double *vals);
 int  igx_multipatch_scatter_vector(igx_multipatch *mp, int p, const double *b);
 /* Global values (nnz, in the order of igx_multipatch_pattern) and vector (nrows) to host.  Either may be NULL. */
 int  igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec);
+/* The nnz values of the current sums, in the order of igx_multipatch_pattern, copied device to device into the caller's buffer
+   (nnz doubles of the same context): what a second matrix over the same pattern is made of (igx_solver_set_mass_d). */
+int  igx_multipatch_values_d(const igx_multipatch *mp, double *d_out);
 
 /* --- Dirichlet problems of one patch on the device: preconditioned CG (pyiga/assemble.py:571-652, pyiga/solvers.py:17-42) ----
    The solver reads the CSR values that the patch holds on the device after an assembly with data_out = NULL, in the patch's own
@@ -733,7 +736,11 @@ int  igx_solver_error_ratio_d(igx_solver *solver, int nv, const double *coef, co
    blocks of a session under the ids below.  Every reduction has a fixed order and no atomics: the same calls give the same bits.
        igx_solver_eig_set_precond, igx_solver_eig_begin, then products / gram / combine / residuals / precond in any order,
        igx_solver_eig_download, igx_solver_eig_info, igx_solver_eig_end.
-   Calls on a solver that is not such a parabolic one, or (but for set_precond and the _d calls) outside a session: IGX_ERR_ARG. */
+   Calls on a solver that is not such a parabolic one, or (but for set_precond and the _d calls) outside a session: IGX_ERR_ARG.
+   A multipatch solver (igx_solver_create_multipatch) that has been given a mass matrix (igx_solver_set_mass_d) is accepted as
+   well: K is the multipatch's summed values (restarted sums: IGX_ERR_ARG, as for every call on such a
+   solver), M the solver's own array, the block product k_csr_spmm2 over the global CSR pattern, nrows_total the global dofs.
+   Without a mass matrix: IGX_ERR_ARG. */
 enum { IGX_EIG_X = 0, IGX_EIG_KX, IGX_EIG_MX, IGX_EIG_W, IGX_EIG_KW, IGX_EIG_MW, IGX_EIG_P, IGX_EIG_KP, IGX_EIG_MP, IGX_EIG_R,
        IGX_EIG_NBLOCKS };
 typedef struct {
@@ -749,9 +756,15 @@ typedef struct {
     float precond_ms;
     float reserved2;
 } igx_eig_info;
+/* The second matrix of a multipatch solver: d_M holds nnz values in the order of igx_multipatch_pattern, allocated with
+   igx_dev_alloc on the solver's context.  The solver takes ownership: it frees d_M when it is destroyed, and a second call frees
+   the array of the first.  A patch solver: IGX_ERR_UNSUPPORTED. */
+int  igx_solver_set_mass_d(igx_solver *solver, double *d_M);
 /* The preconditioner of igx_solver_eig_precond and igx_solver_eig_precond_d: IGX_PRECOND_NONE (the masked copy),
    IGX_PRECOND_JACOBI (the diagonal of K) or IGX_PRECOND_KRON with factors as igx_solver_set_precond takes them (the free dofs must
-   be exactly the box).  Independent of igx_solver_set_precond. */
+   be exactly the box).  Independent of igx_solver_set_precond.  A multipatch solver takes NONE, JACOBI or IGX_PRECOND_MG: one
+   V-cycle of the hierarchy of igx_solver_set_mg_* per column (not set up: IGX_ERR_ARG; the _d form cycles all mb columns, a
+   session the first m); IGX_PRECOND_KRON and IGX_PRECOND_SCHWARZ: IGX_ERR_UNSUPPORTED. */
 int  igx_solver_eig_set_precond(igx_solver *solver, int precond, const int32_t *box_lo, const int32_t *box_hi,
                                 const double *const *U, const double *const *lam, int lam_mode);
 /* Starts a session with blocks of m columns (1 <= m <= 16): X0 (host, nrows_total x m, row-major) goes into IGX_EIG_X with its

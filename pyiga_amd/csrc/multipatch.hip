@@ -630,4 +630,18 @@ int igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec)
     return IGX_OK;
 }
 
+int igx_multipatch_values_d(const igx_multipatch *mp, double *d_out)
+{
+    if (!mp || !d_out) { set_error("igx_multipatch_values_d: null argument"); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(mp->ctx->device));
+    hipStream_t st = mp->ctx->stream;
+    IGX_HIP(hipMemcpyAsync(d_out, mp->d_vals, mp->nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("igx_multipatch_values_d: kernel failure: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
+    }
+    return IGX_OK;
+}
+
 } // extern "C"

@@ -13,6 +13,8 @@
 //              nonzero), k_csr_diag its diagonal; the additive Schwarz preconditioner gathers the box of every patch
 //              (k_box_gather), applies the patch's fast-diagonalization inverse with the k_kron steps and adds it back
 //              (k_box_scatter), patch after patch.
+//   k_csr_spmm2  the block product of the multipatch eigen-solver over the same CSR pattern: K and M times a block of interleaved
+//              columns in one pass (k_spmm2 is its structured twin of section 22).
 //   k_block_spmv  the product of a vector-valued form's NC x NC blocks (NC = 2, 3), which share the patch's layout: one group per
 //              scalar row computes the NC outputs (igx_solver_create_block).
 //   vector     fused CG updates and fixed-order two-pass dot products (fixed grid, fixed trees): two solves of the same
@@ -1034,7 +1036,7 @@ struct EigState {
     double *d_fac = nullptr, *d_W = nullptr;  // Kronecker: packed factors, two work buffers of nbox * EIG_MB_MAX
     int precond = IGX_PRECOND_NONE;
     int box_lo[3] = {}, box_nb[3] = {1, 1, 1}, lam_mode = 0;
-    int nb_spmm[3][2] = {};                   // resident blocks of k_spmm2 per width and matrix count (0: not asked yet)
+    int nb_spmm[3][2] = {};                   // resident blocks of the block product per width and matrix count (0: not asked yet)
     hipEvent_t ev[2] = {};
     bool have_ev = false;
     igx_eig_info info{};
@@ -1125,6 +1127,7 @@ struct igx_solver {
     igx::MgLevel *mg = nullptr;
     // block eigen-solver (igx_solver_eig_*): made by its first call, or null
     EigState *eig = nullptr;
+    double *d_mass = nullptr;                 // a multipatch solver's second matrix (igx_solver_set_mass_d), owned
 };
 
 namespace {
@@ -1266,7 +1269,7 @@ void free_solver(igx_solver *s)
     }
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
     (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
-    (void)hipFree(s->d_bvec); (void)hipFree(s->d_bsc);
+    (void)hipFree(s->d_bvec); (void)hipFree(s->d_bsc); (void)hipFree(s->d_mass);
     for (double *v : s->blk) (void)hipFree(v);
     for (double *v : s->d_bkron) (void)hipFree(v);
     for (double *v : s->pv) (void)hipFree(v);
@@ -3032,6 +3035,125 @@ decltype(auto) with_spmm2_kernel(int gw, int mb, int nm, F &&f)
     }
 }
 
+// The block product over the general CSR pattern of a multipatch: k_spmm2's contract and inner structure,
+// with k_csr_spmv's row-to-group map, its header (free flag, indptr) one row ahead and its 64-bit offsets.  Per entry a lane loads
+// the K value, the M value and the column index once (non-temporal) and gathers the MB x-entries of that column as 16-byte loads.
+// x must vanish on the fixed dofs; the rows of fixed dofs are not read and come out as 0.  Fixed order, no atomics.
+template <int GW, int MB, int U, int NM>
+__global__ void __launch_bounds__(BLOCK) k_csr_spmm2(long long nrows, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                     const double *__restrict__ vK, const double *__restrict__ vM,
+                                                     const uint8_t *__restrict__ freem, const double *__restrict__ x,
+                                                     double *__restrict__ yK, double *__restrict__ yM)
+{
+    constexpr int T = NM * MB, H = MB / 2;
+    const int lane = threadIdx.x % GW;
+    const long long ngroups = (long long)gridDim.x * (BLOCK / GW);
+    const dbl2 zero2 = {0.0, 0.0};
+    long long I = (long long)blockIdx.x * (BLOCK / GW) + threadIdx.x / GW;
+    long long nk0 = 0, nk1 = 0;
+    int nfr = 0;
+    if (I < nrows) { nfr = freem[I]; nk0 = indptr[I]; nk1 = indptr[I + 1]; }
+    for (; I < nrows; I += ngroups) {
+        const long long k0 = nk0, k1 = nk1;
+        const int fr = nfr;
+        if (I + ngroups < nrows) { nfr = freem[I + ngroups]; nk0 = indptr[I + ngroups]; nk1 = indptr[I + ngroups + 1]; }
+        if (!fr) {                                   // (uniform over the group)
+            for (int j = lane; j < MB; j += GW) {
+                yK[I * MB + j] = 0.0;
+                if (NM == 2) yM[I * MB + j] = 0.0;
+            }
+            continue;
+        }
+        double acc[T];
+#pragma unroll
+        for (int i = 0; i < T; ++i) acc[i] = 0.0;
+        for (long long k = k0 + lane; k < k1; k += U * GW) {
+            double v[U][NM];
+            int c[U];
+            dbl2 xv[U][H];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k + u * GW < k1;
+                v[u][0] = in ? __builtin_nontemporal_load(vK + k + u * GW) : 0.0;
+                if (NM == 2) v[u][NM - 1] = in ? __builtin_nontemporal_load(vM + k + u * GW) : 0.0;
+                c[u] = in ? __builtin_nontemporal_load(indices + k + u * GW) : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const dbl2 *xr = reinterpret_cast<const dbl2 *>(x + (long long)(c[u] >= 0 ? c[u] : 0) * MB);
+#pragma unroll
+                for (int j = 0; j < H; ++j) xv[u][j] = c[u] >= 0 ? xr[j] : zero2;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int q = 0; q < NM; ++q)
+#pragma unroll
+                    for (int j = 0; j < H; ++j) {
+                        acc[q * MB + 2 * j] += v[u][q] * xv[u][j].x;
+                        acc[q * MB + 2 * j + 1] += v[u][q] * xv[u][j].y;
+                    }
+        }
+        int base = 0;
+        ReduceScatter<GW, GW / 2, T>::run(acc, lane, base);
+        constexpr int TF = T >= GW ? T / GW : 1;     // sums a writing lane holds: the original indices base .. base + TF - 1
+        if (T >= GW || (lane & (GW / T - 1)) == 0) {
+#pragma unroll
+            for (int i = 0; i < TF; ++i) {
+                const int o = base + i;              // (q, j) = (o / MB, o % MB); TF divides MB: one q per lane
+                double *y = (NM == 2 && o >= MB) ? yM : yK;
+                y[I * MB + (o % MB)] = acc[i];
+            }
+        }
+    }
+}
+
+// the instantiations of the CSR block product, as with_spmm2_gw / with_spmm2_kernel name those of the structured one (U: the table
+// of DESIGN.md section 23)
+template <int MB, int NM, class F>
+decltype(auto) with_csr_spmm2_gw(int gw, F &&f)
+{
+    switch (gw) {
+    case 64: return f(k_csr_spmm2<64, MB, 32 / MB, NM>);
+    case 32: return f(k_csr_spmm2<32, MB, 16 / MB, NM>);
+    case 16: return f(k_csr_spmm2<16, MB, 16 / MB, NM>);
+    case 8: return f(k_csr_spmm2<8, MB, 16 / MB, NM>);
+    default: return f(k_csr_spmm2<4, MB, 16 / MB, NM>);
+    }
+}
+
+template <class F>
+decltype(auto) with_csr_spmm2_kernel(int gw, int mb, int nm, F &&f)
+{
+    if (nm == 2) {
+        switch (mb) {
+        case 4: return with_csr_spmm2_gw<4, 2>(gw, f);
+        case 8: return with_csr_spmm2_gw<8, 2>(gw, f);
+        default: return with_csr_spmm2_gw<16, 2>(gw, f);
+        }
+    }
+    switch (mb) {
+    case 4: return with_csr_spmm2_gw<4, 1>(gw, f);
+    case 8: return with_csr_spmm2_gw<8, 1>(gw, f);
+    default: return with_csr_spmm2_gw<16, 1>(gw, f);
+    }
+}
+
+// column j of a block of mb interleaved columns as a contiguous vector (zero on the fixed dofs), and back: the V-cycle of a
+// multipatch solver works on one vector, so a block goes through it column by column
+__global__ void k_block_col_get(long long n, int mb, int j, const uint8_t *__restrict__ freem, const double *__restrict__ blk,
+                                double *__restrict__ v)
+{
+    for (long long I = (long long)blockIdx.x * blockDim.x + threadIdx.x; I < n; I += (long long)gridDim.x * blockDim.x)
+        v[I] = freem[I] ? blk[I * mb + j] : 0.0;
+}
+
+__global__ void k_block_col_put(long long n, int mb, int j, const double *__restrict__ v, double *__restrict__ blk)
+{
+    for (long long I = (long long)blockIdx.x * blockDim.x + threadIdx.x; I < n; I += (long long)gridDim.x * blockDim.x)
+        blk[I * mb + j] = v[I];
+}
+
 // Gram matrix of up to three A blocks against up to three B blocks over the free rows, first stage: block `blockIdx.x` sums its
 // chunks of GR_RC rows (chunk ch = blockIdx.x, + gridDim.x, ..: a fixed order) through LDS tiles; thread (ty, tx) keeps the
 // entries (ty + 16 r, tx + 16 c) of the concatenated (3 MB) x (3 MB) matrix.  part[block][GR_W][GR_W], GR_W = 16 ceil(3 MB / 16).
@@ -3211,11 +3333,16 @@ __global__ void k_block_scale(long long n, int mb, const double *__restrict__ d,
 bool eig_mb_ok(int mb) { return mb == 4 || mb == 8 || mb == 16; }
 int eig_mb_slot(int mb) { return mb == 4 ? 0 : mb == 8 ? 1 : 2; }
 
-int eig_check(const igx_solver *s, const char *what)
+int eig_check(const igx_solver *s, const char *what, bool values)
 {
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->mp) {                              // K: the multipatch's current sums, M: the solver's own array
+        if (!s->d_mass) { set_error("%s: a multipatch solver needs its mass matrix first (igx_solver_set_mass_d)", what); return IGX_ERR_ARG; }
+        return values ? check_values(s, what) : IGX_OK;
+    }
     if (!s->parabolic || !s->symmetric || s->ncomp != 1) {
-        set_error("%s: needs a symmetric parabolic solver (igx_solver_create_parabolic)", what);
+        set_error("%s: needs a symmetric parabolic solver (igx_solver_create_parabolic) or a multipatch solver with a mass matrix "
+                  "(igx_solver_set_mass_d)", what);
         return IGX_ERR_ARG;
     }
     if (!s->pv[IGX_ROLE_MASS] || !s->pv[IGX_ROLE_OPERATOR]) { set_error("%s: take M and K first (igx_solver_take_values)", what); return IGX_ERR_ARG; }
@@ -3226,9 +3353,9 @@ constexpr size_t EIG_SMALL = 4096;       // doubles of d_small: Gram result (<= 
 constexpr size_t EIG_COEF = 2304, EIG_LAM = EIG_COEF + 6 * 256, EIG_NORM = EIG_LAM + 16;
 
 // the state of the eigen pieces (made once per solver): partial sums, the small buffer, the masked-input block, events
-int eig_state(igx_solver *s, const char *what, EigState **out)
+int eig_state(igx_solver *s, const char *what, EigState **out, bool values = true)
 {
-    if (int rc = eig_check(s, what)) return rc;
+    if (int rc = eig_check(s, what, values)) return rc;
     IGX_HIP(hipSetDevice(s->ctx->device));
     if (!s->eig) {
         EigState *e = new EigState;
@@ -3292,12 +3419,20 @@ int eig_products(hipStream_t st, igx_solver *s, EigState *e, int mb, const doubl
     int &nb = e->nb_spmm[eig_mb_slot(mb)][nm - 1];
     if (!nb) {
         int per_cu = 0;
-        const hipError_t eo = with_spmm2_kernel(s->gw, mb, nm, [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0); });
+        auto occupancy = [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0); };
+        const hipError_t eo = s->mp ? with_csr_spmm2_kernel(s->gw, mb, nm, occupancy) : with_spmm2_kernel(s->gw, mb, nm, occupancy);
         if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
         nb = (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, s->ctx->ncu));
     }
     const long long groups = BLOCK / s->gw;
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(nb, (s->n + groups - 1) / groups));
+    if (const igx_multipatch *m = s->mp) {
+        const double *vK = m->d_vals, *vM = s->d_mass;
+        if (nm == 2) with_csr_spmm2_kernel(s->gw, mb, 2, [&](auto k) { k<<<grid, BLOCK, 0, st>>>(s->n, m->d_indptr, m->d_indices, vK, vM, s->d_mask, x, yK, yM); });
+        else with_csr_spmm2_kernel(s->gw, mb, 1, [&](auto k) { k<<<grid, BLOCK, 0, st>>>(s->n, m->d_indptr, m->d_indices, yK ? vK : vM, nullptr, s->d_mask, x, yK ? yK : yM, nullptr); });
+        IGX_HIP(hipGetLastError());
+        return IGX_OK;
+    }
     const double *vK = s->pv[IGX_ROLE_OPERATOR], *vM = s->pv[IGX_ROLE_MASS];
     if (nm == 2) with_spmm2_kernel(s->gw, mb, 2, [&](auto k) { k<<<grid, BLOCK, 0, st>>>(s->g, vK, vM, s->d_mask, x, yK, yM); });
     else with_spmm2_kernel(s->gw, mb, 1, [&](auto k) { k<<<grid, BLOCK, 0, st>>>(s->g, yK ? vK : vM, nullptr, s->d_mask, x, yK ? yK : yM, nullptr); });
@@ -3365,10 +3500,23 @@ int eig_residuals(hipStream_t st, igx_solver *s, EigState *e, int mb, int m, con
 }
 
 // z = T r on blocks of mb columns: the fast-diagonalization inverse with batch = mb on the free box (z cleared outside it),
-// Jacobi scaling, or the masked copy
-int eig_precond(hipStream_t st, igx_solver *s, EigState *e, int mb, const double *r, double *z)
+// Jacobi scaling, or the masked copy; a multipatch solver's V-cycle on the first m columns one after the other (the others: 0)
+int eig_precond(hipStream_t st, igx_solver *s, EigState *e, int mb, int m, const double *r, double *z)
 {
     const unsigned nb = vec_blocks(s->n * mb);
+    if (e->precond == IGX_PRECOND_MG) {
+        if (int rc = mg_check(s, "igx_solver_eig_precond")) return rc;
+        if (m < mb) IGX_HIP(hipMemsetAsync(z, 0, (size_t)s->n * mb * sizeof(double), st));
+        const unsigned nbv = vec_blocks(s->n);
+        for (int j = 0; j < m; ++j) {
+            k_block_col_get<<<nbv, BLOCK, 0, st>>>(s->n, mb, j, s->d_mask, r, s->w);
+            IGX_HIP(hipGetLastError());
+            if (int rc = mg_apply(st, s, s->w, s->z)) return rc;
+            k_block_col_put<<<nbv, BLOCK, 0, st>>>(s->n, mb, j, s->z, z);
+            IGX_HIP(hipGetLastError());
+        }
+        return IGX_OK;
+    }
     if (e->precond == IGX_PRECOND_KRON) {
         long long full_stride[4], off = 0;
         box_strides(s->dim, s->N, full_stride);
@@ -3390,6 +3538,19 @@ bool eig_block_ok(int b) { return b >= 0 && b < EIG_NBLK; }
 
 extern "C" {
 
+int igx_solver_set_mass_d(igx_solver *s, double *d_M)
+{
+    const char *what = "igx_solver_set_mass_d";
+    if (!s || !d_M) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!s->mp) { set_error("%s: needs a multipatch solver (a patch solver takes M with igx_solver_take_values)", what); return IGX_ERR_UNSUPPORTED; }
+    if (d_M == s->mp->d_vals) { set_error("%s: the multipatch's own sums cannot be handed over (igx_multipatch_values_d copies them)", what); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    IGX_HIP(hipStreamSynchronize(s->ctx->stream));
+    if (s->d_mass != d_M) (void)hipFree(s->d_mass);
+    s->d_mass = d_M;
+    return IGX_OK;
+}
+
 int igx_solver_eig_set_precond(igx_solver *s, int precond, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
                                const double *const *lam, int lam_mode)
 {
@@ -3400,9 +3561,21 @@ int igx_solver_eig_set_precond(igx_solver *s, int precond, const int32_t *box_lo
     if (precond == IGX_PRECOND_NONE) { e->precond = precond; return IGX_OK; }
     if (precond == IGX_PRECOND_JACOBI) {
         if (!e->d_dinv) IGX_HIP(hipMalloc((void **)&e->d_dinv, (size_t)s->n * sizeof(double)));
-        k_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->g, s->pv[IGX_ROLE_OPERATOR], s->d_mask, e->d_dinv);
+        const unsigned nbd = (unsigned)((s->n + 255) / 256);
+        if (s->mp) k_csr_diag<<<nbd, 256, 0, st>>>(s->n, s->mp->d_indptr, s->mp->d_indices, s->mp->d_vals, s->d_mask, e->d_dinv);
+        else k_diag<<<nbd, 256, 0, st>>>(s->g, s->pv[IGX_ROLE_OPERATOR], s->d_mask, e->d_dinv);
         IGX_HIP(hipGetLastError());
         IGX_HIP(hipStreamSynchronize(st));
+        e->precond = precond;
+        return IGX_OK;
+    }
+    if (s->mp) {                              // a multipatch solver: the V-cycle of its hierarchy; no Kronecker, no Schwarz
+        if (precond == IGX_PRECOND_KRON || precond == IGX_PRECOND_SCHWARZ) {
+            set_error("%s: a multipatch solver's blocks take IGX_PRECOND_NONE, IGX_PRECOND_JACOBI or IGX_PRECOND_MG", what);
+            return IGX_ERR_UNSUPPORTED;
+        }
+        if (precond != IGX_PRECOND_MG) { set_error("%s: unknown preconditioner %d", what, precond); return IGX_ERR_ARG; }
+        if (int rc = mg_check(s, what)) return rc;
         e->precond = precond;
         return IGX_OK;
     }
@@ -3550,7 +3723,7 @@ int igx_solver_eig_precond(igx_solver *s, int src, int dst)
     if (!eig_block_ok(src) || !eig_block_ok(dst) || src == dst) { set_error("%s: bad blocks %d -> %d", what, src, dst); return IGX_ERR_ARG; }
     hipStream_t st = s->ctx->stream;
     EigPhase ph(st, e, PH_PRECOND, true);
-    if (int rc = eig_precond(st, s, e, e->mb, e->blk[src], e->blk[dst])) return rc;
+    if (int rc = eig_precond(st, s, e, e->mb, e->m, e->blk[src], e->blk[dst])) return rc;
     return ph.done();
 }
 
@@ -3581,7 +3754,7 @@ int igx_solver_eig_end(igx_solver *s)
 {
     const char *what = "igx_solver_eig_end";
     EigState *e = nullptr;
-    if (int rc = eig_state(s, what, &e)) return rc;
+    if (int rc = eig_state(s, what, &e, false)) return rc;         // (a session ends over restarted sums as well)
     IGX_HIP(hipStreamSynchronize(s->ctx->stream));
     (void)hipFree(e->d_blocks); e->d_blocks = nullptr;
     e->m = e->mb = 0;
@@ -3660,7 +3833,7 @@ int igx_solver_eig_precond_d(igx_solver *s, int mb, const double *d_R, double *d
     if (!eig_mb_ok(mb) || !d_R || !d_Z || d_R == d_Z) { set_error("%s: bad argument (different buffers; row stride 4, 8 or 16)", what); return IGX_ERR_ARG; }
     hipStream_t st = s->ctx->stream;
     EigPhase ph(st, e, PH_PRECOND, false);
-    if (int rc = eig_precond(st, s, e, mb, d_R, d_Z)) return rc;
+    if (int rc = eig_precond(st, s, e, mb, mb, d_R, d_Z)) return rc;              // (every column: a zero column comes out as zero)
     IGX_HIP(hipStreamSynchronize(st));
     return ph.done();
 }

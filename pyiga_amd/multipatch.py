@@ -375,7 +375,8 @@ class Multipatch:
         """System matrix and right-hand side ``(A, b)`` of the bilinear form `problem` and the linear functional `rhs` over
         all patches (arguments as for :func:`pyiga_amd.assemble.assemble`).  Each patch is assembled in turn and scattered
         into the global sums on the device -- from the patch's device values when the assembler leaves them there -- and
-        its device memory is freed before the next one.  The pattern keeps entries whose values sum to 0."""
+        its device memory is freed before the next one.  The pattern keeps entries whose values sum to 0.  `rhs` None: the
+        matrix alone, ``b`` is 0."""
         if bfuns is not None:
             raise NotImplementedError('vector-valued multipatch problems are not supported')
         h = self._sum_system(problem, rhs, args, symmetric, format, layout, kwargs)
@@ -389,7 +390,7 @@ class Multipatch:
     def _sum_system(self, problem, rhs, args, symmetric, format, layout, kwargs, on_assembler=None):
         """Restart the device sums and add every patch's matrix and right-hand side to them (the loop of
         :meth:`assemble_system`); returns the handle, the sums left on the device.  `on_assembler(p, asm)` is called with each
-        patch's assembler before it assembles."""
+        patch's assembler before it assembles.  `rhs` None: the matrices alone (an eigenproblem has no load vector)."""
         from . import assemble as asm_mod
         from .assemblers import _DeviceAssembler, _ParametricFormAssembler
         lib = _lib.load()
@@ -428,6 +429,8 @@ class Multipatch:
             self.last_sources.append('device' if device else 'host')
             t_asm.append((t1 - t0) * 1e3)
             t_sc.append((t2 - t1) * 1e3)
+            if rhs is None:                           # (no load vector wanted: the summed vector stays 0)
+                continue
             b_p = _lib.f64(np.asarray(asm_mod.assemble(rhs, kvs, args=args, symmetric=symmetric, format=format, layout=layout)).ravel())
             if b_p.shape[0] != self.N[p]:
                 raise ValueError('patch %d: right-hand side has %d entries, expected %d' % (p, b_p.shape[0], self.N[p]))

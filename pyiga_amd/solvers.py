@@ -707,6 +707,8 @@ class MultipatchSystem(_DeviceSystem):
 
     PRECONDS = _lib.MP_PRECONDS
     FACTORED = 'schwarz'
+    _inspect_symmetry = True                  # (False: the caller has shown the form to be symmetric before, as
+                                              # MultipatchEigenSystem does for its own levels)
 
     def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', **kwargs):
         self.MP = MP
@@ -716,7 +718,7 @@ class MultipatchSystem(_DeviceSystem):
         kinds = []
 
         def inspect(p, asm):
-            if method == 'cg' and not getattr(asm, '_symmetric_form', True):
+            if self._inspect_symmetry and method == 'cg' and not getattr(asm, '_symmetric_form', True):
                 raise ValueError('MultipatchSystem solves by CG and needs a form known to be symmetric; the assembler of patch %d '
                                  '(%s) cannot show that its form is (general form strings never can).  Accepted: the built-in '
                                  "mass and stiffness forms ('u*v*dx', 'inner(grad(u),grad(v))*dx') and assemblers that do not "
@@ -815,7 +817,7 @@ class MultipatchSystem(_DeviceSystem):
                                                                   ravel=True)] for p, ax, side in sides]
                 fixed = np.unique(np.concatenate(fixed)) if fixed else np.zeros(0, dtype=np.int64)
                 try:
-                    Sc = MultipatchSystem(MPc, problem, rhs, (fixed, np.zeros(fixed.size)), args=args, **kwargs)
+                    Sc = self._level_system(MPc, problem, rhs, (fixed, np.zeros(fixed.size)), args, kwargs)
                 except Exception:
                     MPc.close()
                     raise
@@ -860,6 +862,10 @@ class MultipatchSystem(_DeviceSystem):
         if self._precond == 'mg':
             self._precond = None                  # (the device dropped it when the hierarchy changed)
         return self
+
+    def _level_system(self, MPc, problem, rhs, bcs, args, kwargs):
+        """The system of a coarse level of the hierarchy."""
+        return MultipatchSystem(MPc, problem, rhs, bcs, args=args, **kwargs)
 
     def _mg_level(self, level):
         self._live()
@@ -2077,7 +2083,108 @@ def _check_eig_args(k, block, n_free):
         raise ValueError('a block of %d columns needs at least %d free dofs, the problem has %d' % (block, 3 * block, n_free))
 
 
-class EigenSystem(_DeviceSystem):
+class _EigBlockPieces:
+    """The block kernels of the eigen-solvers alone, on host arrays of shape ``(n, m)`` (``igx_solver_eig_*_d``): shared by
+    ``EigenSystem`` and ``MultipatchEigenSystem``, which supply ``_live()``, ``_ctx``, ``n`` and ``_set_eig_precond``."""
+
+    # -- the pieces alone, on host arrays of shape (n, m)
+    def _upload_block(self, A):
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != self.n or not 1 <= A.shape[1] <= EIG_MAX_BLOCK:
+            raise ValueError('block of shape %r: (%d, m) with 1 <= m <= %d' % (A.shape, self.n, EIG_MAX_BLOCK))
+        return A.shape[1]
+
+    def _padded(self, A, mb):
+        P = np.zeros((self.n, mb))
+        P[:, :A.shape[1]] = A
+        return DeviceArray.from_host(self._ctx, P)
+
+    def _down(self, d, mb, m):
+        return np.ascontiguousarray(d.download().reshape(self.n, mb)[:, :m])
+
+    def block_products(self, X):
+        """``(R K R^T X, R M R^T X)`` by one pass of the block product over both matrices."""
+        h = self._live()
+        m = self._upload_block(X)
+        mb = eig_width(m)
+        d_x = self._padded(np.asarray(X, dtype=np.float64), mb)
+        d_k, d_m = DeviceArray(self._ctx, self.n * mb), DeviceArray(self._ctx, self.n * mb)
+        _lib.check(_lib.load().igx_solver_eig_products_d(h, mb, d_x.ptr, d_k.ptr, d_m.ptr), 'igx_solver_eig_products_d')
+        return self._down(d_k, mb, m), self._down(d_m, mb, m)
+
+    def block_product(self, X, which='K'):
+        """``R K R^T X`` (or ``R M R^T X``, ``which='M'``) by the one-matrix form of the block product."""
+        h = self._live()
+        m = self._upload_block(X)
+        mb = eig_width(m)
+        d_x = self._padded(np.asarray(X, dtype=np.float64), mb)
+        d_y = DeviceArray(self._ctx, self.n * mb)
+        args = (d_y.ptr, None) if which == 'K' else (None, d_y.ptr)
+        _lib.check(_lib.load().igx_solver_eig_products_d(h, mb, d_x.ptr, *args), 'igx_solver_eig_products_d')
+        return self._down(d_y, mb, m)
+
+    def gram(self, A, B):
+        """``A^T B`` over the free dofs; A and B: blocks of the same number of columns, or lists of up to three such blocks
+        (the Gram matrix of their concatenations)."""
+        h = self._live()
+        A = [A] if isinstance(A, np.ndarray) else list(A)
+        B = [B] if isinstance(B, np.ndarray) else list(B)
+        m = self._upload_block(A[0])
+        if any(self._upload_block(Z) != m for Z in A + B) or not (1 <= len(A) <= 3 and 1 <= len(B) <= 3):
+            raise ValueError('gram: one to three blocks a side, all of the same number of columns')
+        mb = eig_width(m)
+        dA = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in A]
+        dB = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in B]
+        G = np.empty((len(A) * m, len(B) * m))
+        pa = (C.c_void_p * len(dA))(*[d.ptr for d in dA])
+        pb = (C.c_void_p * len(dB))(*[d.ptr for d in dB])
+        _lib.check(_lib.load().igx_solver_eig_gram_d(h, mb, m, len(dA), pa, len(dB), pb, _lib.dptr(G)), 'igx_solver_eig_gram_d')
+        return G
+
+    def combine(self, blocks, coeffs):
+        """``sum_j blocks[j] @ coeffs[j]`` for up to three blocks of m columns and m x m coefficient matrices."""
+        h = self._live()
+        blocks, coeffs = list(blocks), [np.asarray(c, dtype=np.float64) for c in coeffs]
+        m = self._upload_block(blocks[0])
+        if not 1 <= len(blocks) <= 3 or len(coeffs) != len(blocks) or any(self._upload_block(Z) != m for Z in blocks) \
+                or any(c.shape != (m, m) for c in coeffs):
+            raise ValueError('combine: one to three blocks of m columns with an m x m coefficient matrix each')
+        mb = eig_width(m)
+        dS = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in blocks]
+        d_y = DeviceArray(self._ctx, self.n * mb)
+        ps = (C.c_void_p * len(dS))(*[d.ptr for d in dS])
+        cf = np.ascontiguousarray(np.stack(coeffs))
+        _lib.check(_lib.load().igx_solver_eig_combine_d(h, mb, m, len(dS), ps, _lib.dptr(cf), d_y.ptr), 'igx_solver_eig_combine_d')
+        return self._down(d_y, mb, m)
+
+    def residuals(self, KX, MX, lam):
+        """``(R, ||R_j||, ||KX_j||)`` with ``R = KX - MX diag(lam)`` on the free dofs (zero elsewhere), by the fused kernel."""
+        h = self._live()
+        m = self._upload_block(KX)
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if self._upload_block(MX) != m or lam.shape != (m,):
+            raise ValueError('residuals: KX and MX of m columns and m values of lam')
+        mb = eig_width(m)
+        d_k, d_m = self._padded(np.asarray(KX, dtype=np.float64), mb), self._padded(np.asarray(MX, dtype=np.float64), mb)
+        d_r = DeviceArray(self._ctx, self.n * mb)
+        rn, kn = np.empty(m), np.empty(m)
+        _lib.check(_lib.load().igx_solver_eig_residuals_d(h, mb, m, d_k.ptr, d_m.ptr, _lib.dptr(lam), d_r.ptr, _lib.dptr(rn),
+                                                          _lib.dptr(kn)), 'igx_solver_eig_residuals_d')
+        return self._down(d_r, mb, m), rn, kn
+
+    def apply_precond(self, R, precond='auto'):
+        """The preconditioner applied to every column of the block R."""
+        h = self._live()
+        m = self._upload_block(R)
+        self._set_eig_precond(precond)
+        mb = eig_width(m)
+        d_r = self._padded(np.asarray(R, dtype=np.float64), mb)
+        d_z = DeviceArray(self._ctx, self.n * mb)
+        _lib.check(_lib.load().igx_solver_eig_precond_d(h, mb, d_r.ptr, d_z.ptr), 'igx_solver_eig_precond_d')
+        return self._down(d_z, mb, m)
+
+
+class EigenSystem(_EigBlockPieces, _DeviceSystem):
     """The lowest eigenpairs of ``K x = lam M x`` on the free dofs of one patch (x = 0 on the dofs of `bcs`), by block LOBPCG
     with both matrices, the blocks and the preconditioner in device memory.
 
@@ -2181,6 +2288,8 @@ class EigenSystem(_DeviceSystem):
         self._eig_precond = key
         return key
 
+    _set_eig_precond = set_precond
+
     def solve(self, k=6, tol=1e-8, maxiter=200, precond='auto', block=None, X0=None, seed=0, timed=False):
         """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i M x_i|| <= tol ||K x_i||`` for the k lowest pairs.  `block`: the
         columns iterated (default ``k + max(2, k // 2)``, at most 16); `X0`: a start block of shape ``(n, block)``, else normal
@@ -2209,101 +2318,191 @@ class EigenSystem(_DeviceSystem):
         self.info = info
         return lam[:k].copy(), U
 
-    # -- the pieces alone, on host arrays of shape (n, m)
-    def _upload_block(self, A):
-        A = np.asarray(A, dtype=np.float64)
-        if A.ndim != 2 or A.shape[0] != self.n or not 1 <= A.shape[1] <= EIG_MAX_BLOCK:
-            raise ValueError('block of shape %r: (%d, m) with 1 <= m <= %d' % (A.shape, self.n, EIG_MAX_BLOCK))
-        return A.shape[1]
-
-    def _padded(self, A, mb):
-        P = np.zeros((self.n, mb))
-        P[:, :A.shape[1]] = A
-        return DeviceArray.from_host(self._ctx, P)
-
-    def _down(self, d, mb, m):
-        return np.ascontiguousarray(d.download().reshape(self.n, mb)[:, :m])
-
-    def block_products(self, X):
-        """``(R K R^T X, R M R^T X)`` by one pass of the block product over both matrices."""
-        h = self._live()
-        m = self._upload_block(X)
-        mb = eig_width(m)
-        d_x = self._padded(np.asarray(X, dtype=np.float64), mb)
-        d_k, d_m = DeviceArray(self._ctx, self.n * mb), DeviceArray(self._ctx, self.n * mb)
-        _lib.check(_lib.load().igx_solver_eig_products_d(h, mb, d_x.ptr, d_k.ptr, d_m.ptr), 'igx_solver_eig_products_d')
-        return self._down(d_k, mb, m), self._down(d_m, mb, m)
-
-    def block_product(self, X, which='K'):
-        """``R K R^T X`` (or ``R M R^T X``, ``which='M'``) by the one-matrix form of the block product."""
-        h = self._live()
-        m = self._upload_block(X)
-        mb = eig_width(m)
-        d_x = self._padded(np.asarray(X, dtype=np.float64), mb)
-        d_y = DeviceArray(self._ctx, self.n * mb)
-        args = (d_y.ptr, None) if which == 'K' else (None, d_y.ptr)
-        _lib.check(_lib.load().igx_solver_eig_products_d(h, mb, d_x.ptr, *args), 'igx_solver_eig_products_d')
-        return self._down(d_y, mb, m)
-
-    def gram(self, A, B):
-        """``A^T B`` over the free dofs; A and B: blocks of the same number of columns, or lists of up to three such blocks
-        (the Gram matrix of their concatenations)."""
-        h = self._live()
-        A = [A] if isinstance(A, np.ndarray) else list(A)
-        B = [B] if isinstance(B, np.ndarray) else list(B)
-        m = self._upload_block(A[0])
-        if any(self._upload_block(Z) != m for Z in A + B) or not (1 <= len(A) <= 3 and 1 <= len(B) <= 3):
-            raise ValueError('gram: one to three blocks a side, all of the same number of columns')
-        mb = eig_width(m)
-        dA = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in A]
-        dB = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in B]
-        G = np.empty((len(A) * m, len(B) * m))
-        pa = (C.c_void_p * len(dA))(*[d.ptr for d in dA])
-        pb = (C.c_void_p * len(dB))(*[d.ptr for d in dB])
-        _lib.check(_lib.load().igx_solver_eig_gram_d(h, mb, m, len(dA), pa, len(dB), pb, _lib.dptr(G)), 'igx_solver_eig_gram_d')
-        return G
-
-    def combine(self, blocks, coeffs):
-        """``sum_j blocks[j] @ coeffs[j]`` for up to three blocks of m columns and m x m coefficient matrices."""
-        h = self._live()
-        blocks, coeffs = list(blocks), [np.asarray(c, dtype=np.float64) for c in coeffs]
-        m = self._upload_block(blocks[0])
-        if not 1 <= len(blocks) <= 3 or len(coeffs) != len(blocks) or any(self._upload_block(Z) != m for Z in blocks) \
-                or any(c.shape != (m, m) for c in coeffs):
-            raise ValueError('combine: one to three blocks of m columns with an m x m coefficient matrix each')
-        mb = eig_width(m)
-        dS = [self._padded(np.asarray(Z, dtype=np.float64), mb) for Z in blocks]
-        d_y = DeviceArray(self._ctx, self.n * mb)
-        ps = (C.c_void_p * len(dS))(*[d.ptr for d in dS])
-        cf = np.ascontiguousarray(np.stack(coeffs))
-        _lib.check(_lib.load().igx_solver_eig_combine_d(h, mb, m, len(dS), ps, _lib.dptr(cf), d_y.ptr), 'igx_solver_eig_combine_d')
-        return self._down(d_y, mb, m)
-
-    def residuals(self, KX, MX, lam):
-        """``(R, ||R_j||, ||KX_j||)`` with ``R = KX - MX diag(lam)`` on the free dofs (zero elsewhere), by the fused kernel."""
-        h = self._live()
-        m = self._upload_block(KX)
-        lam = np.ascontiguousarray(lam, dtype=np.float64)
-        if self._upload_block(MX) != m or lam.shape != (m,):
-            raise ValueError('residuals: KX and MX of m columns and m values of lam')
-        mb = eig_width(m)
-        d_k, d_m = self._padded(np.asarray(KX, dtype=np.float64), mb), self._padded(np.asarray(MX, dtype=np.float64), mb)
-        d_r = DeviceArray(self._ctx, self.n * mb)
-        rn, kn = np.empty(m), np.empty(m)
-        _lib.check(_lib.load().igx_solver_eig_residuals_d(h, mb, m, d_k.ptr, d_m.ptr, _lib.dptr(lam), d_r.ptr, _lib.dptr(rn),
-                                                          _lib.dptr(kn)), 'igx_solver_eig_residuals_d')
-        return self._down(d_r, mb, m), rn, kn
-
-    def apply_precond(self, R, precond='auto'):
-        """The preconditioner applied to every column of the block R."""
-        h = self._live()
-        m = self._upload_block(R)
-        self.set_precond(precond)
-        mb = eig_width(m)
-        d_r = self._padded(np.asarray(R, dtype=np.float64), mb)
-        d_z = DeviceArray(self._ctx, self.n * mb)
-        _lib.check(_lib.load().igx_solver_eig_precond_d(h, mb, d_r.ptr, d_z.ptr), 'igx_solver_eig_precond_d')
-        return self._down(d_z, mb, m)
-
     def spmv(self, x):
         raise NotImplementedError('EigenSystem holds two matrices: block_products(X) or block_product(X, which)')
+
+
+STIFFNESS_FORM = 'inner(grad(u), grad(v)) * dx'
+MASS_FORM = 'u * v * dx'
+
+
+class _SymmetricLevelSystem(MultipatchSystem):
+    """A coarse level of ``MultipatchEigenSystem``: its form was shown to be symmetric (``_symmetric_problem``) before any level
+    was made, which the assembler of a general form string cannot declare."""
+    _inspect_symmetry = False
+
+
+class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
+    """The lowest eigenpairs of ``K x = lam M x`` on the free dofs of the multipatch `MP` (x = 0 on the dofs of `bcs`), by block
+    LOBPCG with both global CSR matrices, the blocks and the preconditioner in device memory.
+
+    M is the mass matrix summed over `MP`; K the summed stiffness matrix (`problem` None) or that of any form ``FormSystem``
+    accepts whose matrix is known to be symmetric on every patch (`problem`, with `args` / `inputs` its inputs).  The mass sums
+    are copied into an array of the solver's own, then `problem` is summed: K is what `MP` holds, so a later
+    ``MP.assemble_system`` restarts it (``solve`` then raises IgxError) and ``MP.close()`` destroys the solver.  `bcs`:
+    ``(indices, values)`` or just the indices; only the indices are used.
+
+    ``solve(k)`` returns ``(lam, U)`` as ``EigenSystem.solve`` does, ``U`` of shape ``(MP.numdofs, k)``.  Preconditioners: 'mg'
+    (one V-cycle of ``set_multigrid`` per column), 'jacobi', None.  ``block_products``, ``gram``, ``combine``, ``residuals`` and
+    ``apply_precond`` run the block kernels alone on host arrays of shape ``(n, m)``; ``spmv(x)`` is ``R K R^T x`` and
+    ``vcycle(r)`` the V-cycle on one vector."""
+
+    PRECONDS = {None: _lib.IGX_PRECOND_NONE, 'none': _lib.IGX_PRECOND_NONE, 'jacobi': _lib.IGX_PRECOND_JACOBI, 'mg': _lib.IGX_PRECOND_MG}
+
+    def __init__(self, MP, bcs=None, problem=None, args=None, **inputs):
+        self.MP = MP
+        args = dict(args or {})
+        args.update(inputs)
+        if args.get('bfuns') is not None:
+            raise ValueError('MultipatchEigenSystem: vector-valued problems (bfuns) are not supported')
+        if problem is not None:
+            for kvs, geo in MP.patches:
+                pargs = dict(args, geo=geo)
+                _check_device_form(problem, tuple(kvs), pargs)
+                if not _symmetric_problem(problem, tuple(kvs), pargs):
+                    raise ValueError('MultipatchEigenSystem: %r is not known to be symmetric (the built-in stiffness and mass '
+                                     'forms are, and a form string whose traced coefficient table is)' % (problem,))
+        self.n = MP.numdofs
+        if bcs is None:
+            idx = np.zeros(0, dtype=np.int64)
+        elif isinstance(bcs, tuple) and len(bcs) == 2 and np.ndim(bcs[0]) >= 1:
+            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
+        else:
+            idx = np.asarray(bcs, dtype=np.int64).ravel()
+        idx = np.unique(idx)
+        if idx.size and (idx[0] < 0 or idx[-1] >= self.n):
+            raise ValueError('fixed dof out of range')
+        if _form_kind(problem) == 'stiffness' and idx.size == 0:
+            raise ValueError('MultipatchEigenSystem: the stiffness matrix without any fixed dof is singular (the constants), and '
+                             "the relative stopping rule ||r|| <= tol ||K x|| has no scale there.  Shift instead: "
+                             "problem='(inner(grad(u), grad(v)) + u*v) * dx', then subtract 1 from the eigenvalues")
+        self.n_free = self.n - idx.size
+        form = STIFFNESS_FORM if problem is None else problem
+        self._problem = (form, None, args, {})
+        self._mg = None
+        self._eig_precond = False                                    # (no preconditioner of the eigen pieces set yet)
+        lib = _lib.load()
+        kinds = []
+        h = MP._sum_system(MASS_FORM, None, args, False, 'csr', 'blocked', {})
+        self._ctx = MP._ctx
+        d_M = lib.igx_dev_alloc(self._ctx.handle, max(1, MP.info()['nnz']) * 8)
+        if not d_M:
+            raise _lib.IgxError('igx_dev_alloc failed: ' + _lib.last_error())
+        try:
+            _lib.check(lib.igx_multipatch_values_d(h, d_M), 'igx_multipatch_values_d')
+            h = MP._sum_system(form, None, args, False, 'csr', 'blocked', {},
+                               on_assembler=lambda p, asm: kinds.append(getattr(asm, '_kind', None)))
+            self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
+            self._attach('igx_solver_create_multipatch', (h,), (idx, np.zeros(idx.size)), 'cg', 'cg')
+            _lib.check(lib.igx_solver_set_mass_d(self.handle, d_M), 'igx_solver_set_mass_d')      # (the array changes hands)
+        except BaseException:
+            lib.igx_dev_free(self._ctx.handle, d_M)
+            self._release()
+            raise
+        MP._solvers.add(self)
+
+    def _level_system(self, MPc, problem, rhs, bcs, args, kwargs):
+        return _SymmetricLevelSystem(MPc, problem, rhs, bcs, args=args, **kwargs)
+
+    def set_method(self, method):
+        if method != 'cg':
+            raise ValueError('MultipatchEigenSystem has no linear solve: its method stays cg')
+        _DeviceSystem.set_method(self, method)
+
+    def _precond_key(self, precond):
+        """The name of `precond` ('none' for None), or ValueError: before any device work."""
+        if precond == 'schwarz':
+            raise ValueError("the Schwarz preconditioner is not offered for eigenproblems (in the host model it takes as many "
+                             "iterations as Jacobi): use precond='mg'")
+        key = precond if precond is not None else 'none'
+        if key != 'auto' and key not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        return key
+
+    def _auto_precond(self):
+        """'mg' if a hierarchy of at least two levels is set up or ``set_multigrid()`` makes one, else 'jacobi'."""
+        if self._mg is None:
+            try:
+                self.set_multigrid()
+            except ValueError:
+                return 'jacobi'
+        if len(self._mg['systems']) < 2:
+            self._drop_multigrid()
+            return 'jacobi'
+        return 'mg'
+
+    def set_precond(self, precond):
+        """The preconditioner of ``solve`` and of ``apply_precond`` on blocks: 'auto', 'mg', 'jacobi' or None.  'auto' is 'mg' when
+        ``set_multigrid()`` succeeds with at least one coarser level (the fixed dofs a union of whole patch sides, injective
+        maps), else 'jacobi'; 'mg' alone calls ``set_multigrid()`` with its defaults if no hierarchy is set up."""
+        key = self._precond_key(precond)
+        h = self._live()
+        if key == 'auto':
+            key = self._auto_precond()
+        elif key == 'mg' and self._mg is None:
+            self.set_multigrid()
+        if key == self._eig_precond:
+            return key
+        _lib.check(_lib.load().igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
+        self._eig_precond = key
+        return key
+
+    _set_eig_precond = set_precond
+
+    def _drop_multigrid(self):
+        MultipatchSystem._drop_multigrid(self)
+        if getattr(self, '_eig_precond', None) == 'mg':
+            self._eig_precond = False
+
+    def set_multigrid(self, *args, **kwargs):
+        MultipatchSystem.set_multigrid(self, *args, **kwargs)
+        if self._eig_precond == 'mg':
+            self._eig_precond = False             # (checked again against the new hierarchy)
+        return self
+
+    set_multigrid.__doc__ = MultipatchSystem.set_multigrid.__doc__
+
+    def solve(self, k=6, tol=1e-8, maxiter=200, precond='auto', block=None, X0=None, seed=0, timed=False):
+        """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i M x_i|| <= tol ||K x_i||`` for the k lowest pairs; arguments and
+        ``info`` as ``EigenSystem.solve``.  `precond`: see ``set_precond``.  The V-cycle is applied column by column (`block`
+        cycles per iteration).  Deterministic on injective maps: the same inputs give the same bits."""
+        k = int(k)
+        m = default_eig_block(max(k, 1)) if block is None else int(block)
+        _check_eig_args(k, m, self.n_free)
+        self._precond_key(precond)
+        if X0 is None:
+            X0 = np.random.default_rng(seed).standard_normal((self.n, m))
+        else:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (self.n, m):
+                raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (self.n, m)))
+        h = self._live()
+        key = self.set_precond(precond)
+        ops = _DeviceEigOps(h, self.n, m, X0, timed)
+        try:
+            lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
+            U = ops.download('X', k)
+            dev = ops.info()
+        finally:
+            ops.end()
+        info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
+        if key == 'mg':
+            info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
+        if timed:
+            info.update({name: dev[name] for name in dev if name.endswith('_ms')})
+        self.info = info
+        return lam[:k].copy(), U
+
+    def vcycle(self, r):
+        """One V-cycle of the hierarchy on the vector `r` of all dofs (``MultipatchSystem.apply_precond(r, 'mg')``)."""
+        h = self._live()
+        if self._mg is None:
+            self.set_multigrid()
+        if self._precond != 'mg':
+            _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_MG, None, None, None, None, 0), 'igx_solver_set_precond')
+            self._precond = 'mg'
+        return self._device_op(_lib.load().igx_solver_precond_d, 'igx_solver_precond_d', r)
+
+    def schwarz_setup(self):
+        raise ValueError("the Schwarz preconditioner is not offered for eigenproblems: use precond='mg'")
+

@@ -1,0 +1,126 @@
+"""The cases that run every instantiation of the CSR block product of the multipatch eigen-solver (k_csr_spmm2,
+pyiga_amd/csrc/solve.hip), and what decides them.
+
+A plain helper module (no GPU needed to import it): tests/test_mp_eig_cpu.py checks on the host that the dispatch reaches all
+30 ``(GW, MB, NM)`` and that the table reaches every group width and wraps the grid-stride loop of each;
+tests/test_mp_eig_kernels_gpu.py runs the cases.
+
+- The group width of a multipatch is ``spmv_gw(max_row(multipatch_pattern(MP)))``: the block product takes k_csr_spmv's
+  row-to-group map, and the longest row includes the interface rows.
+- One grid-stride pass covers at most NB_SPMV_MAX blocks of BLOCK / GW rows (``_eig_cases.spmm_pass_rows``).
+"""
+import re
+from typing import NamedTuple
+
+import numpy as np
+
+import _mpsolve_model as M
+import _solver_cases as SC
+from _eig_cases import COLUMNS, WIDTHS, eig_width, spmm_pass_rows     # noqa: F401
+from _solver_cases import GWS, MultipatchCase     # noqa: F401
+
+SHIFTED_FORM = '(inner(grad(u), grad(v)) + u*v) * dx'
+MASKS = ('sides', 'fifth', 'none')
+
+LSHAPE_OUTER = [(0, 'left'), (0, 'bottom'), (0, 'top'), (1, 'bottom'), (1, 'right'), (2, 'left'), (2, 'right'), (2, 'top')]
+CUBES2_OUTER = [(q, (ax, sd)) for q in (0, 1) for ax in range(3) for sd in (0, 1) if (q, ax, sd) not in ((0, 2, 1), (1, 2, 0))]
+OUTER = {'lshape': LSHAPE_OUTER, 'notebook': M.NOTEBOOK_DIRICHLET, 'cubes2': CUBES2_OUTER}
+
+
+def outer_dofs(MP, domain):
+    """The fixed dofs of the eigenproblems on `domain`: the outer boundary (notebook: the notebook's Dirichlet sides)."""
+    return M.fixed_dofs(MP, OUTER[domain])
+
+
+def mask_dofs(MP, domain, mask):
+    if mask == 'sides':
+        return outer_dofs(MP, domain)
+    if mask == 'fifth':
+        return np.sort(np.random.default_rng(5).permutation(MP.numdofs)[:MP.numdofs // 5]).astype(np.int64)
+    return np.zeros(0, dtype=np.int64)
+
+
+# ---------------------------------------------------------------------------------------------
+# parsing solve.hip
+def parse_csr_spmm_dispatch(src):
+    """{(GW, MB, NM)}: the instantiations of k_csr_spmm2 the two dispatch functions reach, the {(label, GW)} of the group-width
+    switch and the {GW: U expression} the switch writes."""
+    gw_body = SC._function_body(src, 'decltype(auto) with_csr_spmm2_gw(')
+    gws, us = set(), {}
+    for label, gw, u in re.findall(r'(case \d+|default):[^\n]*?\bk_csr_spmm2<(\d+), MB, ([^,]+), NM>', gw_body):
+        gws.add((None if label == 'default' else int(label.split()[1]), int(gw)))
+        us[int(gw)] = u.strip()
+    body = SC._function_body(src, 'decltype(auto) with_csr_spmm2_kernel(')
+    pairs = {(int(mb), int(nm)) for mb, nm in re.findall(r'with_csr_spmm2_gw<(\d+), (\d+)>', body)}
+    return {(gw, mb, nm) for _, gw in gws for mb, nm in pairs}, gws, us
+
+
+def csr_spmm_outside_tables(src):
+    """Template argument lists of k_csr_spmm2 written anywhere but in with_csr_spmm2_gw."""
+    src = src.replace(SC._function_body(src, 'decltype(auto) with_csr_spmm2_gw('), '')
+    return re.findall(r'\bk_csr_spmm2\s*<[^>]*>', src)
+
+
+# ---------------------------------------------------------------------------------------------
+# the cases
+class BlockCase(NamedTuple):
+    mp: MultipatchCase
+    columns: tuple     # m of the blocks run on it
+
+    @property
+    def id(self):
+        return self.mp.id
+
+
+# one small domain per group width, run with every m of COLUMNS and every mask of MASKS: every (GW, MB, NM)
+SMALL_CASES = [
+    BlockCase(MultipatchCase('lshape_p1_n6', 'lshape', 1, 6, 4), COLUMNS),
+    BlockCase(MultipatchCase('lshape_p2_n5', 'lshape', 2, 5, 8), COLUMNS),
+    BlockCase(MultipatchCase('notebook_p3_n5', 'notebook', 3, 5, 16), COLUMNS),
+    BlockCase(MultipatchCase('lshape_p5_n6', 'lshape', 5, 6, 32), COLUMNS),
+    BlockCase(MultipatchCase('cubes2_p3_n4', 'cubes2', 3, 4, 64), COLUMNS),
+]
+
+# one multipatch past the pass bound per group width (those of the CSR SpMV tests), each at one width
+WRAP_CASES = [BlockCase(c, (m,)) for c, m in zip(SC.MULTIPATCH_CASES[:5], (3, 8, 13, 4, 5))]
+
+# gram, combine, residuals: a multipatch whose row count is no multiple of 256
+ROWS_CASE = MultipatchCase('notebook_p3_n9', 'notebook', 3, 9, 16)
+ROWS_COLUMNS = (3, 8, 13)
+
+# the goldens of tests/golden/golden_mp_eig.npz: name -> (domain, p, n)
+GOLDEN_CASES = {'lshape': ('lshape', 2, 8), 'notebook': ('notebook', 3, 8), 'cubes2': ('cubes2', 2, 4)}
+
+
+def golden_domain(name):
+    domain, p, n = GOLDEN_CASES[name]
+    return MultipatchCase('golden_' + name, domain, p, n, 0).build(), domain
+
+
+# ---------------------------------------------------------------------------------------------
+# the oracle's matrices summed through MP.patch_to_global
+def oracle_geos(orc, domain):
+    """The oracle's geometry of every patch of `domain` up to a rigid motion or a reflection, which change neither the stiffness
+    nor the mass matrix (as tests/test_multigrid_cpu.py takes them)."""
+    if domain == 'lshape':
+        return 3 * [orc.geo_unit_cube(2)]
+    if domain == 'notebook':
+        return [orc.geo_quarter_annulus(), orc.geo_unit_cube(2), orc.geo_quarter_annulus(), orc.geo_quarter_annulus()]
+    return 2 * [orc.geo_unit_cube(3)]
+
+
+def oracle_sums(orc, MP, domain, p, n, kinds=('stiffness', 'mass')):
+    """The global CSR matrices sum_q X_q A_q X_q^T of `kinds` from the oracle's patch matrices."""
+    import scipy.sparse as sp
+    geos = oracle_geos(orc, domain)
+    okv = orc.make_knots(p, 0.0, 1.0, n)
+    d = len(MP.patches[0][0])
+    out = []
+    for kind in kinds:
+        A = None
+        for q in range(MP.numpatches):
+            X = MP.patch_to_global(q)
+            T = X @ orc.assemble(kind, (okv,) * d, geos[q]) @ X.T
+            A = T if A is None else A + T
+        out.append(sp.csr_matrix(A))
+    return out

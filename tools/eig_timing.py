@@ -9,7 +9,14 @@ baseline 2 m calls of igx_solver_spmv_d (the masked copy of x + k_spmv), m on a 
 patch.  Every call is timed on the device by a pair of events on the library's stream (warm-up, then REPS repetitions, the median);
 the baseline is m times the sum of the two medians.  The achieved rate of the value stream is 2 nnz 8 bytes over the time of the
 block product.  Then EigenSystem.solve(k=6, timed=True) at the same size: iterations and the device ms per phase.  Prints one
-JSON line per measurement."""
+JSON line per measurement.
+  mp   the multipatch eigen-solver (solvers.MultipatchEigenSystem) on two unit cubes joined on a face,
+       p=3 n=40: 157 165 dofs, about 45 M values per matrix over the general CSR pattern (values and indices pass the last-level
+       cache).  One igx_solver_eig_products_d call (the masked copy of X + k_csr_spmm2 over both matrices) against 2 m calls of
+       igx_solver_spmv_d on the same solver (the masked copy of x + k_csr_spmv over the same pattern; the mass product runs the
+       same kernel over the same pattern, so it is counted at the time of the stiffness product), then one solve with 'mg' and
+       one with 'jacobi': iterations, restarts, device ms per phase and wall time.
+  mp0  the same on a small domain (a smoke case)"""
 import ctypes as C
 import json
 import os
@@ -113,6 +120,60 @@ def run(name):
         PM.close()
 
 
+def run_mp(name):
+    import time
+    from pyiga_amd import assemble
+    p, n = (3, 40) if name == 'mp' else (2, 6)
+    kvs = 3 * (bspline.make_knots(p, 0.0, 1.0, n),)
+    cube = geometry.unit_cube()
+    MP = assemble.Multipatch([(kvs, cube), (kvs, cube.translate((1, 0, 0)))])
+    MP.join_boundaries(0, (2, 1), 1, (2, 0))
+    MP.finalize()
+    fixed = []
+    for q in (0, 1):
+        for ax in range(3):
+            for sd in (0, 1):
+                if (q, ax, sd) not in ((0, 2, 1), (1, 2, 0)):                 # every face but the interface
+                    fixed.append(MP.patch_to_global_idx(q)[assemble.boundary_dofs(kvs, (ax, sd), ravel=True)])
+    fixed = np.unique(np.concatenate(fixed))
+    lib = _lib.load()
+    rng = np.random.default_rng(0)
+    S = solvers.MultipatchEigenSystem(MP, (fixed, np.zeros(fixed.size)))
+    try:
+        nrows, nnz = MP.numdofs, int(MP.info()['nnz'])
+        T = DeviceTimer(S._ctx)
+        d_x, d_y = DeviceArray.from_host(S._ctx, rng.standard_normal(nrows)), DeviceArray(S._ctx, nrows)
+        t_k = T.median(lambda: _lib.check(lib.igx_solver_spmv_d(S.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d'))
+        print(json.dumps({'case': name, 'dofs': nrows, 'nnz': nnz, 'baseline': 'igx_solver_spmv_d (k_csr_spmv)', 'reps': REPS,
+                          'spmv_ms': round(t_k, 4), 'GBs': round(12e-6 * nnz / t_k, 1)}), flush=True)
+        for m in (4, 8, 16):
+            mb = solvers.eig_width(m)
+            d_X = DeviceArray.from_host(S._ctx, rng.standard_normal((nrows, mb)))
+            d_K, d_M = DeviceArray(S._ctx, nrows * mb), DeviceArray(S._ctx, nrows * mb)
+            t2 = T.median(lambda: _lib.check(lib.igx_solver_eig_products_d(S.handle, mb, d_X.ptr, d_K.ptr, d_M.ptr), 'igx_solver_eig_products_d'))
+            t1 = T.median(lambda: _lib.check(lib.igx_solver_eig_products_d(S.handle, mb, d_X.ptr, d_K.ptr, None), 'igx_solver_eig_products_d'))
+            base = 2 * m * t_k
+            print(json.dumps({'case': name, 'm': m, 'block_product_ms': round(t2, 4), 'single_products_ms': round(base, 4),
+                              'ratio_single_over_block': round(base / t2, 2), 'one_matrix_ms': round(t1, 4),
+                              'stream_GBs': round(20e-6 * nnz / t2, 1)}), flush=True)
+        for precond in ('mg', 'jacobi'):
+            t0 = time.perf_counter()
+            if precond == 'mg':
+                S.set_multigrid()
+            t1 = time.perf_counter()
+            lam, _ = S.solve(k=6, tol=1e-8, precond=precond, maxiter=1000, timed=True)
+            t2 = time.perf_counter()
+            info = S.info
+            print(json.dumps({'case': name, 'solve': 'k=6 tol=1e-8', 'block': int(info['block']), 'precond': info['precond'],
+                              'levels': info.get('levels'), 'iterations': int(info['iterations']),
+                              'converged': bool(info['converged'].all()), 'restarts': int(info['restarts']),
+                              'lam': [round(float(v), 9) for v in lam], 'setup_s': round(t1 - t0, 3), 'wall_s': round(t2 - t1, 3),
+                              'phase_ms': {k: round(float(v), 3) for k, v in info.items() if k.endswith('_ms')}}), flush=True)
+    finally:
+        S.close()
+        MP.close()
+
+
 if __name__ == '__main__':
     for c in (sys.argv[1:] or ['c3d']):
-        run(c)
+        (run_mp if c in ('mp', 'mp0') else run)(c)

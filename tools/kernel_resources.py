@@ -15,7 +15,7 @@ for line in out.splitlines():
     m = re.search(r'Function Name: (\S+)', line)
     if m:
         cur = subprocess.run(['c++filt', m.group(1)], capture_output=True, text=True).stdout.strip()
-        cur = re.sub(r'\(.*', '', cur)
+        cur = re.sub(r'\(.*', '', cur.replace('(anonymous namespace)::', '').replace('void ', ''))
         rows[cur] = {}
         continue
     m = re.search(r'remark: \s*(SGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)', line)
