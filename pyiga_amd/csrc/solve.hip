@@ -1341,14 +1341,19 @@ int init_bicgstab(igx_solver *s, const char *what)
     return IGX_OK;
 }
 
-// the packed fast-diagonalization factors h on the device (s->d_kron) and two work buffers of wlen doubles (s->d_W), in place
-// of the previous ones
-int alloc_fastdiag(igx_solver *s, hipStream_t st, const std::vector<double> &h, long long wlen)
+// h (packed fast-diagonalization factors, raw eigenvalues) on the device at d_buf, in place of the buffer there; not synchronised
+int upload_replacing(hipStream_t st, const std::vector<double> &h, double *&d_buf)
 {
-    (void)hipFree(s->d_kron); s->d_kron = nullptr;
-    (void)hipFree(s->d_W); s->d_W = nullptr;
-    IGX_HIP(hipMalloc((void **)&s->d_kron, h.size() * sizeof(double)));
-    IGX_HIP(hipMemcpyAsync(s->d_kron, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    (void)hipFree(d_buf); d_buf = nullptr;
+    IGX_HIP(hipMalloc((void **)&d_buf, h.size() * sizeof(double)));
+    IGX_HIP(hipMemcpyAsync(d_buf, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    return IGX_OK;
+}
+
+// two work buffers of wlen doubles (s->d_W), in place of the previous ones
+int alloc_fastdiag_work(igx_solver *s, long long wlen)
+{
+    (void)hipFree(s->d_W); s->d_W = nullptr; s->wlen = 0;
     IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)wlen * sizeof(double)));
     s->wlen = wlen;
     return IGX_OK;
@@ -1599,6 +1604,36 @@ int check_free_box(const igx_solver *s, long long base, const int32_t *box_lo, c
     return IGX_OK;
 }
 
+// the inverse on the box of nb dofs from box_lo on of the component at `base`, in the full-length vectors: (x) U_k^T reads the box
+// of r, (x) U_k writes it into z
+FastDiag box_fastdiag(const igx_solver *s, long long base, const int32_t *box_lo, const int *nb, const double *d_fac, int lam_mode,
+                      long long batch = 1)
+{
+    long long full_stride[4], off = base;
+    box_strides(s->dim, s->N, full_stride);
+    for (int k = 0; k < s->dim; ++k) off += box_lo[k] * full_stride[k];
+    return make_fastdiag(s->dim, nb, d_fac, full_stride, off, lam_mode, batch);
+}
+
+// The Kronecker inverse on the free box of the component at `base` of a patch solver, for the entry point `what`: checks the
+// arguments, packs the factors and puts them on the device at d_fac in place of the previous ones (synchronised before and
+// after).  *reset (or null) becomes IGX_PRECOND_NONE before anything is freed, whatever fails later.  nb out
+int box_fastdiag_setup(igx_solver *s, long long base, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                       const double *const *lam, int lam_mode, const char *what, int *reset, double *&d_fac, int nb[3])
+{
+    if (!box_lo || !box_hi || !U || !lam) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("%s: unknown lam_mode %d", what, lam_mode); return IGX_ERR_ARG; }
+    nb[0] = nb[1] = nb[2] = 1;
+    if (int rc = check_free_box(s, base, box_lo, box_hi, U, lam, nb, what)) return rc;
+    std::vector<double> h;
+    pack_fastdiag(h, s->dim, nb, U, lam);
+    if (reset) *reset = IGX_PRECOND_NONE;
+    IGX_HIP(hipStreamSynchronize(s->ctx->stream));
+    if (int rc = upload_replacing(s->ctx->stream, h, d_fac)) return rc;
+    IGX_HIP(hipStreamSynchronize(s->ctx->stream));       // (h goes away)
+    return IGX_OK;
+}
+
 } // namespace
 
 // what multigrid.hip sees of a solver (mg_internal.h)
@@ -1748,33 +1783,16 @@ int igx_solver_set_block_kron(igx_solver *s, int comp, const int32_t *box_lo, co
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
     if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
     if (comp < 0 || comp >= s->ncomp) { set_error("%s: component %d of %d", what, comp, s->ncomp); return IGX_ERR_ARG; }
-    if (!box_lo || !box_hi || !U || !lam) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
-    if (mode != IGX_KRON_SUM && mode != IGX_KRON_PRODUCT) { set_error("%s: unknown lam_mode %d", what, mode); return IGX_ERR_ARG; }
-    const int d = s->dim;
-    const long long base = (long long)comp * s->g.nrows;
-    int nb[3] = {1, 1, 1};
-    if (int rc = check_free_box(s, base, box_lo, box_hi, U, lam, nb, what)) return rc;
-    std::vector<double> h;
-    pack_fastdiag(h, d, nb, U, lam);
     IGX_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    IGX_HIP(hipStreamSynchronize(st));
-    if (s->precond == IGX_PRECOND_KRON) s->precond = IGX_PRECOND_NONE;      // (selected again by igx_solver_set_precond)
-    (void)hipFree(s->d_bkron[comp]); s->d_bkron[comp] = nullptr;
-    IGX_HIP(hipMalloc((void **)&s->d_bkron[comp], h.size() * sizeof(double)));
-    IGX_HIP(hipMemcpyAsync(s->d_bkron[comp], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    const long long base = (long long)comp * s->g.nrows;
+    int nb[3];
+    // (a Kronecker preconditioner in use is dropped: selected again by igx_solver_set_precond)
+    if (int rc = box_fastdiag_setup(s, base, box_lo, box_hi, U, lam, mode, what, s->precond == IGX_PRECOND_KRON ? &s->precond : nullptr,
+                                    s->d_bkron[comp], nb)) return rc;
     const long long nbox = (long long)nb[0] * nb[1] * nb[2];
-    if (nbox > s->wlen) {                          // the two work buffers fit the largest box of any component
-        (void)hipFree(s->d_W); s->d_W = nullptr; s->wlen = 0;
-        IGX_HIP(hipMalloc((void **)&s->d_W, 2 * (size_t)nbox * sizeof(double)));
-        s->wlen = nbox;
-    }
-    // (x) U_k^T reads the component's box of the full-length r, (x) U_k writes it into z
-    long long full_stride[4], off = base;
-    box_strides(d, s->N, full_stride);
-    for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
-    s->bkron[comp] = make_fastdiag(d, nb, s->d_bkron[comp], full_stride, off, mode);
-    IGX_HIP(hipStreamSynchronize(st));
+    if (nbox > s->wlen)                            // the two work buffers fit the largest box of any component
+        if (int rc = alloc_fastdiag_work(s, nbox)) return rc;
+    s->bkron[comp] = box_fastdiag(s, base, box_lo, nb, s->d_bkron[comp], mode);
     return IGX_OK;
 }
 
@@ -1832,21 +1850,10 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
         s->precond = precond;
         return IGX_OK;
     }
-    if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_precond: null argument"); return IGX_ERR_ARG; }
-    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_precond: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
-    const int d = s->dim;
-    int nb[3] = {1, 1, 1};
-    if (int rc = check_free_box(s, 0, box_lo, box_hi, U, lam, nb, "igx_solver_set_precond")) return rc;
-    std::vector<double> h;
-    pack_fastdiag(h, d, nb, U, lam);
-    s->precond = IGX_PRECOND_NONE;
-    if (int rc = alloc_fastdiag(s, st, h, std::max<long long>(1, (long long)nb[0] * nb[1] * nb[2]))) return rc;
-    // (x) U_k^T reads the box of the full-length r, (x) U_k writes it into z
-    long long full_stride[4], off = 0;
-    box_strides(d, s->N, full_stride);
-    for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
-    s->kron = make_fastdiag(d, nb, s->d_kron, full_stride, off, lam_mode);
-    IGX_HIP(hipStreamSynchronize(st));
+    int nb[3];
+    if (int rc = box_fastdiag_setup(s, 0, box_lo, box_hi, U, lam, lam_mode, "igx_solver_set_precond", &s->precond, s->d_kron, nb)) return rc;
+    if (int rc = alloc_fastdiag_work(s, (long long)nb[0] * nb[1] * nb[2])) return rc;
+    s->kron = box_fastdiag(s, 0, box_lo, nb, s->d_kron, lam_mode);
     s->precond = IGX_PRECOND_KRON;
     return IGX_OK;
 }
@@ -1904,7 +1911,8 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
     (void)hipFree(s->d_box); s->d_box = nullptr;
     s->sw.clear();
     if (s->precond == IGX_PRECOND_SCHWARZ) s->precond = IGX_PRECOND_NONE;
-    if (int rc = alloc_fastdiag(s, st, h, wlen)) return rc;
+    if (int rc = upload_replacing(st, h, s->d_kron)) return rc;
+    if (int rc = alloc_fastdiag_work(s, wlen)) return rc;
     IGX_HIP(hipMalloc((void **)&s->d_box, (size_t)wlen * sizeof(double)));
     for (size_t j = 0; j < sw.size(); ++j) {
         const int d = sw[j].F.dim;
@@ -1964,17 +1972,22 @@ int igx_solver_spmv_d(igx_solver *s, const double *d_x, double *d_y)
 
 namespace {
 
+// the end of a call between the events `begin` and `end`: the stream drained, a kernel failure reported under `what`, the time out
+int close_call(hipStream_t st, hipEvent_t begin, hipEvent_t end, const char *what, float &total_ms)
+{
+    IGX_HIP(hipEventRecord(end, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s: kernel failure: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
+    (void)hipEventElapsedTime(&total_ms, begin, end);
+    return IGX_OK;
+}
+
 // the solution x + ext(g) to the host, the device time of the whole solve (from ev[5]) and the info block
 int finish_solve(hipStream_t st, igx_solver *s, const double *gvals, double *u, igx_solve_info *info, igx_solve_info &inf)
 {
     IGX_HIP(hipMemcpyAsync(u, s->x, (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, st));
-    IGX_HIP(hipEventRecord(s->ev[4], st));
-    IGX_HIP(hipStreamSynchronize(st));
-    {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("igx_solver_solve: kernel failure: %s", hipGetErrorString(e)); return IGX_ERR_HIP; }
-    }
-    (void)hipEventElapsedTime(&inf.total_ms, s->ev[5], s->ev[4]);
+    if (int rc = close_call(st, s->ev[5], s->ev[4], "igx_solver_solve", inf.total_ms)) return rc;
     for (size_t k = 0; k < s->fixed.size(); ++k) u[s->fixed[k]] = gvals[k];
     inf.n_free = s->n - (long long)s->fixed.size();
     if (info) *info = inf;
@@ -2263,6 +2276,93 @@ int form_stage_matrix(hipStream_t st, igx_solver *s, double tg)
     return IGX_OK;
 }
 
+// timed: the device time since the last lap goes to a bucket; the events ev[mark] and ev[other] alternate
+struct PhaseTimer {
+    hipEvent_t *ev;
+    int mark, other, timed;                  // (the caller records ev[mark] where the first phase starts)
+    int lap(hipStream_t st, float &bucket)
+    {
+        if (!timed) return IGX_OK;
+        IGX_HIP(hipEventRecord(ev[other], st));
+        IGX_HIP(hipEventSynchronize(ev[other]));
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ev[mark], ev[other]);
+        bucket += ms;
+        std::swap(mark, other);
+        return IGX_OK;
+    }
+};
+
+// x0 with g on the fixed dofs to d_x, ext(g) to d_w and f to d_f: the only uploads of a run or a session.  `begin` (or null) is
+// recorded ahead of them; synchronised
+int upload_start_state(hipStream_t st, const igx_solver *s, const double *f, const double *gvals, const double *x0, double *d_x,
+                       double *d_w, double *d_f, hipEvent_t begin)
+{
+    const long long n = s->n;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    std::vector<double> h((size_t)n), w((size_t)n, 0.0);
+    for (long long i = 0; i < n; ++i) h[i] = s->h_free[i] ? x0[i] : 0.0;
+    for (size_t k = 0; k < s->fixed.size(); ++k) h[s->fixed[k]] = w[s->fixed[k]] = gvals[k];
+    if (begin) IGX_HIP(hipEventRecord(begin, st));
+    IGX_HIP(hipMemcpyAsync(d_x, h.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(d_w, w.data(), nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipMemcpyAsync(d_f, f, nbytes, hipMemcpyHostToDevice, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
+// the implicit stages of one DIRK step, for igx_solver_dirk_run and the session's igx_solver_step_attempt alike; ok out: every
+// stage solve converged (else the chain ends with the stage that did not)
+struct StageChain {
+    const double *A; int ns;                 // the tableau, ns columns
+    double tau, tg;                          // the step and tau gamma
+    double *xs, *mx, *fv, *y, **F;           // the state x, M x, f, the stage value (y_s: the new state) and F_j = f - K y_j
+    const double *wg;                        // ext(g)
+    bool from_guess;                         // the stage solves stop relative to the increment, not to the right-hand side
+    double tol; int maxiter, check_every;
+    bool keep_last_F;                        // F_s is formed too: F_1 of the next step, or weighed by the embedded rule
+    int32_t *stage_iters;                    // ns of them: the iterations of every stage that was solved (the others: untouched)
+    float *spmv_ms, *combine_ms, *solve_ms;  // the phase buckets of T
+};
+
+int dirk_stage_chain(hipStream_t st, igx_solver *s, const StageChain &c, PhaseTimer &T, bool &ok)
+{
+    const long long n = s->n;
+    const unsigned nbv = vec_blocks(n), nbm = (unsigned)((n + 255) / 256);
+    const int ns = c.ns;
+    const double *A = c.A, *yprev = c.xs;
+    ok = true;
+    for (int i = 0; i < ns && ok; ++i) {
+        const double aii = A[i * ns + i];
+        if (aii == 0.0) continue;                                // (i = 0: y_1 = x, F_1 in F[0])
+        Comb L{};
+        L.c[L.nv] = 1.0; L.v[L.nv++] = c.mx;
+        for (int j = 0; j < i; ++j)
+            if (A[i * ns + j] != 0.0) { L.c[L.nv] = c.tau * A[i * ns + j]; L.v[L.nv++] = c.F[j]; }
+        L.c[L.nv] = c.tg; L.v[L.nv++] = c.fv;
+        k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
+        k_mask_copy<<<nbm, 256, 0, st>>>(n, s->d_mask, yprev, s->x);    // the initial guess y_{i-1}
+        IGX_HIP(hipGetLastError());
+        if (int rc = T.lap(st, *c.combine_ms)) return rc;
+        igx_solve_info si{};
+        if (int rc = solve_lifted(st, s, c.wg, true, c.tol, c.maxiter, c.check_every, 0, si, c.from_guess)) return rc;
+        if (int rc = T.lap(st, *c.solve_ms)) return rc;
+        c.stage_iters[i] = si.iterations;
+        if (!si.converged) { ok = false; break; }
+        Comb Y{};
+        Y.nv = 2; Y.c[0] = 1.0; Y.v[0] = s->x; Y.c[1] = 1.0; Y.v[1] = c.wg;        // y_i = x + ext(g)
+        k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, Y, c.y);
+        IGX_HIP(hipGetLastError());
+        if (int rc = T.lap(st, *c.combine_ms)) return rc;
+        yprev = c.y;
+        if (i < ns - 1 || c.keep_last_F) {                       // F_i = f - K y_i
+            if (int rc = spmv_values(st, s, s->pv[1], c.y, c.fv, -1.0, c.F[i])) return rc;
+            if (int rc = T.lap(st, *c.spmv_ms)) return rc;
+        }
+    }
+    return IGX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2340,6 +2440,8 @@ int igx_solver_set_dirk(igx_solver *s, int stages, const double *A, double tau)
     return IGX_OK;
 }
 
+// Not built on the session calls (igx_solver_step_*), and dirk_A / tau / gamma not merged with st_*: the session scales the Kronecker
+// eigenvalues on the device and stops its stage solves relative to the increment, so the iteration counts would change.
 int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, const double *x0, int64_t nsteps, int64_t save_every,
                         double tol, int maxiter, int check_every, int timed, double *saved, int32_t *stage_iters, igx_dirk_info *info)
 {
@@ -2369,31 +2471,10 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
     igx_dirk_info inf{};
     inf.axpby_ms = s->axpby_ms;
     s->breakdown = 0;
-    // f, ext(g) (s->w) and x0 with g on the fixed dofs: the only uploads
-    std::vector<double> h((size_t)n);
-    for (long long i = 0; i < n; ++i) h[i] = s->h_free[i] ? x0[i] : 0.0;
-    for (size_t k = 0; k < s->fixed.size(); ++k) h[s->fixed[k]] = gvals[k];
-    std::vector<double> w((size_t)n, 0.0);
-    for (size_t k = 0; k < s->fixed.size(); ++k) w[s->fixed[k]] = gvals[k];
     hipEvent_t *E = s->dev;
-    IGX_HIP(hipEventRecord(E[4], st));
-    IGX_HIP(hipMemcpyAsync(xs, h.data(), nbytes, hipMemcpyHostToDevice, st));
-    IGX_HIP(hipMemcpyAsync(s->w, w.data(), nbytes, hipMemcpyHostToDevice, st));
-    IGX_HIP(hipMemcpyAsync(fv, f, nbytes, hipMemcpyHostToDevice, st));
-    const unsigned nbv = vec_blocks(n), nbm = (unsigned)((n + 255) / 256);
-    // timed: the device time since the last mark goes to `bucket` (E[0] / E[1] alternate)
-    int mark = 0;
+    if (int rc = upload_start_state(st, s, f, gvals, x0, xs, s->w, fv, E[4])) return rc;      // ext(g) in s->w
+    PhaseTimer T{E, 0, 1, timed};
     if (timed) IGX_HIP(hipEventRecord(E[0], st));
-    auto lap = [&](float &bucket) -> int {
-        if (!timed) return IGX_OK;
-        IGX_HIP(hipEventRecord(E[1 - mark], st));
-        IGX_HIP(hipEventSynchronize(E[1 - mark]));
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, E[mark], E[1 - mark]);
-        bucket += ms;
-        mark = 1 - mark;
-        return IGX_OK;
-    };
     auto save = [&]() -> int {                                      // the state xs to the next slot of `saved`
         IGX_HIP(hipMemcpyAsync(saved + (size_t)inf.nsaved * n, xs, nbytes, hipMemcpyDeviceToHost, st));
         IGX_HIP(hipStreamSynchronize(st));
@@ -2402,43 +2483,24 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
     };
     if (explicit_first) {                                            // F_1 of the first step: f - K x0
         if (int rc = spmv_values(st, s, s->pv[1], xs, fv, -1.0, F[0])) return rc;
-        if (int rc = lap(inf.spmv_ms)) return rc;
+        if (int rc = T.lap(st, inf.spmv_ms)) return rc;
     }
     bool ok = true;
     long long last_saved = 0;
     for (long long k = 1; k <= nsteps && ok; ++k) {
         if (int rc = spmv_values(st, s, s->pv[0], xs, nullptr, 1.0, mx)) return rc;          // M x
-        if (int rc = lap(inf.spmv_ms)) return rc;
-        const double *yprev = xs;
-        for (int i = 0; i < ns && ok; ++i) {
-            const double aii = A[i * ns + i];
-            if (aii == 0.0) continue;                                // (i = 0: y_1 = x, F_1 in F[0])
-            Comb L{};
-            L.c[L.nv] = 1.0; L.v[L.nv++] = mx;
-            for (int j = 0; j < i; ++j)
-                if (A[i * ns + j] != 0.0) { L.c[L.nv] = tau * A[i * ns + j]; L.v[L.nv++] = F[j]; }
-            L.c[L.nv] = tau * gamma; L.v[L.nv++] = fv;
-            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
-            k_mask_copy<<<nbm, 256, 0, st>>>(n, s->d_mask, yprev, s->x);    // the initial guess y_{i-1}
-            IGX_HIP(hipGetLastError());
-            if (int rc = lap(inf.combine_ms)) return rc;
-            igx_solve_info si{};
-            if (int rc = solve_lifted(st, s, s->w, true, tol, maxiter, check_every, 0, si)) return rc;
-            if (int rc = lap(inf.solve_ms)) return rc;
-            if (stage_iters) stage_iters[(k - 1) * ns + i] = si.iterations;
-            inf.iterations += si.iterations;
-            inf.max_stage_iterations = std::max(inf.max_stage_iterations, si.iterations);
-            if (!si.converged) { ok = false; break; }
-            Comb Y{};
-            Y.nv = 2; Y.c[0] = 1.0; Y.v[0] = s->x; Y.c[1] = 1.0; Y.v[1] = s->w;        // y_i = x + ext(g)
-            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, Y, y);
-            IGX_HIP(hipGetLastError());
-            if (int rc = lap(inf.combine_ms)) return rc;
-            yprev = y;
-            if (i < ns - 1 || explicit_first) {                      // F_i = f - K y_i (the last one only as F_1 of the next step)
-                if (int rc = spmv_values(st, s, s->pv[1], y, fv, -1.0, F[i])) return rc;
-                if (int rc = lap(inf.spmv_ms)) return rc;
-            }
+        if (int rc = T.lap(st, inf.spmv_ms)) return rc;
+        int32_t it[IGX_DIRK_MAX_STAGES];
+        std::fill(it, it + ns, -1);                                  // (-1: not solved)
+        // the stage solves stop relative to their right-hand side; the last F only as F_1 of the next step
+        const StageChain chain{A, ns, tau, tau * gamma, xs, mx, fv, y, F, s->w, false, tol, maxiter, check_every, explicit_first,
+                               it, &inf.spmv_ms, &inf.combine_ms, &inf.solve_ms};
+        if (int rc = dirk_stage_chain(st, s, chain, T, ok)) return rc;
+        for (int i = 0; i < ns; ++i) {
+            if (it[i] < 0) continue;
+            if (stage_iters) stage_iters[(k - 1) * ns + i] = it[i];
+            inf.iterations += it[i];
+            inf.max_stage_iterations = std::max(inf.max_stage_iterations, it[i]);
         }
         if (!ok) break;
         std::swap(xs, y);                                            // x_new = y_s
@@ -2452,13 +2514,7 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
     if (!ok && inf.steps > 0 && last_saved != inf.steps) {          // the state after the last completed step
         if (int rc = save()) return rc;
     }
-    IGX_HIP(hipEventRecord(E[5], st));
-    IGX_HIP(hipStreamSynchronize(st));
-    {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("%s: kernel failure: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
-    }
-    (void)hipEventElapsedTime(&inf.total_ms, E[4], E[5]);
+    if (int rc = close_call(st, E[4], E[5], what, inf.total_ms)) return rc;
     inf.converged = ok ? 1 : 0;
     if (info) *info = inf;
     return IGX_OK;
@@ -2583,16 +2639,14 @@ int igx_solver_set_step_precond(igx_solver *s, int precond, const int32_t *box_l
     s->pc_vals = -1;
     if (precond == IGX_PRECOND_NONE || precond == IGX_PRECOND_JACOBI) { s->step_precond = precond; return IGX_OK; }
     if (precond != IGX_PRECOND_KRON) { set_error("%s: preconditioner %d (none, Jacobi or Kronecker)", what, precond); return IGX_ERR_ARG; }
-    if (!box_lo || !box_hi || !U || !lam_raw) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
-    const int d = s->dim;
-    int nb[3] = {1, 1, 1};
-    if (int rc = check_free_box(s, 0, box_lo, box_hi, U, lam_raw, nb, what)) return rc;
-    std::vector<double> h, raw;
-    pack_fastdiag(h, d, nb, U, lam_raw);
+    int nb[3];
+    if (int rc = box_fastdiag_setup(s, 0, box_lo, box_hi, U, lam_raw, IGX_KRON_SUM, what, &s->precond, s->d_kron, nb)) return rc;
+    if (int rc = alloc_fastdiag_work(s, (long long)nb[0] * nb[1] * nb[2])) return rc;
+    std::vector<double> raw;
     LamSlots L{};
-    L.nax = d;
+    L.nax = s->dim;
     size_t o = 0;
-    for (int k = 0; k < d; ++k) {                        // (the layout of pack_fastdiag: U_k^T | U_k | lam_k)
+    for (int k = 0; k < s->dim; ++k) {                   // (the layout of pack_fastdiag: U_k^T | U_k | lam_k)
         const size_t mk = (size_t)nb[k];
         L.m[k] = nb[k];
         L.slot[k] = (long long)(o + 2 * mk * mk);
@@ -2600,16 +2654,8 @@ int igx_solver_set_step_precond(igx_solver *s, int precond, const int32_t *box_l
         raw.insert(raw.end(), lam_raw[k], lam_raw[k] + mk);
         o += 2 * mk * mk + mk;
     }
-    s->precond = IGX_PRECOND_NONE;
-    IGX_HIP(hipStreamSynchronize(st));
-    if (int rc = alloc_fastdiag(s, st, h, std::max<long long>(1, (long long)nb[0] * nb[1] * nb[2]))) return rc;
-    (void)hipFree(s->d_lamraw); s->d_lamraw = nullptr;
-    IGX_HIP(hipMalloc((void **)&s->d_lamraw, raw.size() * sizeof(double)));
-    IGX_HIP(hipMemcpyAsync(s->d_lamraw, raw.data(), raw.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    long long full_stride[4], off = 0;
-    box_strides(d, s->N, full_stride);
-    for (int k = 0; k < d; ++k) off += box_lo[k] * full_stride[k];
-    s->kron = make_fastdiag(d, nb, s->d_kron, full_stride, off, IGX_KRON_SUM);
+    if (int rc = upload_replacing(st, raw, s->d_lamraw)) return rc;
+    s->kron = box_fastdiag(s, 0, box_lo, nb, s->d_kron, IGX_KRON_SUM);
     s->lam_slots = L;
     IGX_HIP(hipStreamSynchronize(st));
     s->step_precond = IGX_PRECOND_KRON;
@@ -2639,13 +2685,7 @@ int igx_solver_step_begin(igx_solver *s, const double *f, const double *gvals, c
     double *v = s->d_dirk;
     s->sx = v; s->smx = v + n; s->sfv = v + 2 * n; s->sy = v + 3 * n;
     for (int j = 0; j < IGX_DIRK_MAX_STAGES; ++j) s->sF[j] = v + (4 + j) * n;
-    std::vector<double> h((size_t)n), w((size_t)n, 0.0);
-    for (long long i = 0; i < n; ++i) h[i] = s->h_free[i] ? x0[i] : 0.0;
-    for (size_t k = 0; k < s->fixed.size(); ++k) h[s->fixed[k]] = w[s->fixed[k]] = gvals[k];
-    IGX_HIP(hipMemcpyAsync(s->sx, h.data(), nbytes, hipMemcpyHostToDevice, st));
-    IGX_HIP(hipMemcpyAsync(s->d_wg, w.data(), nbytes, hipMemcpyHostToDevice, st));
-    IGX_HIP(hipMemcpyAsync(s->sfv, f, nbytes, hipMemcpyHostToDevice, st));
-    IGX_HIP(hipStreamSynchronize(st));
+    if (int rc = upload_start_state(st, s, f, gvals, x0, s->sx, s->d_wg, s->sfv, nullptr)) return rc;
     s->have_mx = s->have_F0 = s->have_cand = false;
     s->breakdown = 0;
     s->step_live = true;
@@ -2669,7 +2709,7 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
     const int ns = s->st_stages;
     const double *A = s->st_A, gamma = s->st_gamma, tg = tau * gamma;
     const bool estimate = err_tol > 0.0;
-    const unsigned nbv = vec_blocks(n), nbm = (unsigned)((n + 255) / 256);
+    const unsigned nbv = vec_blocks(n);
     igx_step_info inf{};
     inf.n_free = n - (long long)s->fixed.size();
     inf.has_estimate = estimate ? 1 : 0;
@@ -2690,19 +2730,8 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
         s->pc_vals = -1;
     }
     if (int rc = step_refresh_precond(st, s, 2, tg)) return rc;
-    int mark = 2;                                                    // timed: E[2] / E[3] alternate (E[0], E[1]: k_vals_axpby)
-    if (timed) IGX_HIP(hipEventRecord(E[mark], st));
-    auto lap = [&](float &bucket) -> int {
-        if (!timed) return IGX_OK;
-        const int next = 5 - mark;
-        IGX_HIP(hipEventRecord(E[next], st));
-        IGX_HIP(hipEventSynchronize(E[next]));
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, E[mark], E[next]);
-        bucket += ms;
-        mark = next;
-        return IGX_OK;
-    };
+    PhaseTimer T{E, 2, 3, timed};                                    // (E[0], E[1]: k_vals_axpby)
+    if (timed) IGX_HIP(hipEventRecord(E[2], st));
     bool ok = true;
     double sum = 0.0;
     if (s->family == IGX_STEPPER_DIRK) {
@@ -2716,39 +2745,12 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
             if (int rc = spmv_values(st, s, s->pv[0], xs, nullptr, 1.0, mx)) return rc;
             s->have_mx = true;
         }
-        if (int rc = lap(inf.spmv_ms)) return rc;
-        const double *yprev = xs;
-        bool have_Fs = false;
-        for (int i = 0; i < ns && ok; ++i) {
-            const double aii = A[i * ns + i];
-            if (aii == 0.0) continue;                                // (i = 0: y_1 = x, F_1 in F[0])
-            Comb L{};
-            L.c[L.nv] = 1.0; L.v[L.nv++] = mx;
-            for (int j = 0; j < i; ++j)
-                if (A[i * ns + j] != 0.0) { L.c[L.nv] = tau * A[i * ns + j]; L.v[L.nv++] = F[j]; }
-            L.c[L.nv] = tg; L.v[L.nv++] = fv;
-            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
-            k_mask_copy<<<nbm, 256, 0, st>>>(n, s->d_mask, yprev, s->x);    // the initial guess y_{i-1}
-            IGX_HIP(hipGetLastError());
-            if (int rc = lap(inf.combine_ms)) return rc;
-            igx_solve_info si{};
-            if (int rc = solve_lifted(st, s, s->d_wg, true, solve_tol, maxiter, check_every, 0, si, true)) return rc;
-            if (int rc = lap(inf.solve_ms)) return rc;
-            inf.stage_iterations[i] = si.iterations;
-            if (!si.converged) { ok = false; break; }
-            Comb Y{};
-            Y.nv = 2; Y.c[0] = 1.0; Y.v[0] = s->x; Y.c[1] = 1.0; Y.v[1] = s->d_wg;     // y_i = x + ext(g)
-            k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, Y, y);
-            IGX_HIP(hipGetLastError());
-            if (int rc = lap(inf.combine_ms)) return rc;
-            yprev = y;
-            // F_i = f - K y_i; the last one as F_1 of the next step, or where the embedded rule weighs it
-            if (i < ns - 1 || explicit_first || (estimate && s->st_bh[i] != s->st_b[i])) {
-                if (int rc = spmv_values(st, s, s->pv[1], y, fv, -1.0, F[i])) return rc;
-                if (int rc = lap(inf.spmv_ms)) return rc;
-                if (i == ns - 1) have_Fs = true;
-            }
-        }
+        if (int rc = T.lap(st, inf.spmv_ms)) return rc;
+        // the stage solves stop relative to the increment; the last F as F_1 of the next step, or where the embedded rule weighs it
+        const bool have_Fs = explicit_first || (estimate && s->st_bh[ns - 1] != s->st_b[ns - 1]);
+        const StageChain chain{A, ns, tau, tg, xs, mx, fv, y, F, s->d_wg, true, solve_tol, maxiter, check_every, have_Fs,
+                               inf.stage_iterations, &inf.spmv_ms, &inf.combine_ms, &inf.solve_ms};
+        if (int rc = dirk_stage_chain(st, s, chain, T, ok)) return rc;
         if (ok && estimate) {
             // e = x_est - x_new: the last stage equation is M x_new = M x + tau sum b_i F_i, so R M R^T e = tau sum (b^_i - b_i) F_i
             // (the F_i vanish on the fixed dofs; nothing to lift).  One CG solve on M from zero: its relative residual is that
@@ -2760,7 +2762,7 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
             }
             k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, s->b);
             IGX_HIP(hipGetLastError());
-            if (int rc = lap(inf.combine_ms)) return rc;
+            if (int rc = T.lap(st, inf.combine_ms)) return rc;
             s->vals_sel = s->pv[IGX_ROLE_MASS];
             const int method = s->method;
             s->method = IGX_METHOD_CG;                               // (M is symmetric positive definite whatever K is)
@@ -2770,14 +2772,14 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
             s->method = method;
             s->vals_sel = nullptr;
             if (rc) return rc;
-            if (int rc2 = lap(inf.mass_ms)) return rc2;
+            if (int rc2 = T.lap(st, inf.mass_ms)) return rc2;
             inf.mass_iterations = si.iterations;
             if (!si.converged) ok = false;
             else {
                 Comb D{};
                 D.nv = 1; D.c[0] = 1.0; D.v[0] = s->x;
                 if (int rc2 = err_norm(st, s, D, xs, err_tol, &sum)) return rc2;
-                if (int rc2 = lap(inf.err_ms)) return rc2;
+                if (int rc2 = T.lap(st, inf.err_ms)) return rc2;
             }
         }
     } else {
@@ -2795,15 +2797,15 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
             if (L.nv > 1) {
                 k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, yt);
                 IGX_HIP(hipGetLastError());
-                if (int rc = lap(inf.combine_ms)) return rc;
+                if (int rc = T.lap(st, inf.combine_ms)) return rc;
                 yi = yt;
             }
             if (int rc = spmv_values(st, s, s->pv[1], yi, fv, -1.0, s->b)) return rc;
-            if (int rc = lap(inf.spmv_ms)) return rc;
+            if (int rc = T.lap(st, inf.spmv_ms)) return rc;
             igx_solve_info si{};
             if (int rc = solve_lifted(st, s, nullptr, false, solve_tol, maxiter, check_every, 0, si)) return rc;
             IGX_HIP(hipMemcpyAsync(K[i], s->x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            if (int rc = lap(inf.solve_ms)) return rc;
+            if (int rc = T.lap(st, inf.solve_ms)) return rc;
             inf.stage_iterations[i] = si.iterations;
             if (!si.converged) ok = false;
         }
@@ -2814,7 +2816,7 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
                 if (s->st_b[j] != 0.0) { L.c[L.nv] = tau * s->st_b[j]; L.v[L.nv++] = K[j]; }
             k_dirk_rhs<<<nbv, BLOCK, 0, st>>>(n, L, cand);
             IGX_HIP(hipGetLastError());
-            if (int rc = lap(inf.combine_ms)) return rc;
+            if (int rc = T.lap(st, inf.combine_ms)) return rc;
             if (estimate) {
                 Comb D{};
                 for (int j = 0; j < ns; ++j) {
@@ -2822,17 +2824,11 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
                     if (c != 0.0) { D.c[D.nv] = tau * c; D.v[D.nv++] = K[j]; }
                 }
                 if (int rc = err_norm(st, s, D, xs, err_tol, &sum)) return rc;
-                if (int rc = lap(inf.err_ms)) return rc;
+                if (int rc = T.lap(st, inf.err_ms)) return rc;
             }
         }
     }
-    IGX_HIP(hipEventRecord(E[5], st));
-    IGX_HIP(hipStreamSynchronize(st));
-    {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("%s: kernel failure: %s", what, hipGetErrorString(e)); return IGX_ERR_HIP; }
-    }
-    (void)hipEventElapsedTime(&inf.total_ms, E[4], E[5]);
+    if (int rc = close_call(st, E[4], E[5], what, inf.total_ms)) return rc;
     inf.converged = ok ? 1 : 0;
     inf.r = (ok && estimate) ? std::sqrt(sum) / std::sqrt((double)std::max<long long>(1, inf.n_free)) : 0.0;
     s->have_cand = ok;
@@ -3518,10 +3514,7 @@ int eig_precond(hipStream_t st, igx_solver *s, EigState *e, int mb, int m, const
         return IGX_OK;
     }
     if (e->precond == IGX_PRECOND_KRON) {
-        long long full_stride[4], off = 0;
-        box_strides(s->dim, s->N, full_stride);
-        for (int k = 0; k < s->dim; ++k) off += e->box_lo[k] * full_stride[k];
-        const FastDiag F = make_fastdiag(s->dim, e->box_nb, e->d_fac, full_stride, off, e->lam_mode, mb);
+        const FastDiag F = box_fastdiag(s, 0, e->box_lo, e->box_nb, e->d_fac, e->lam_mode, mb);
         const long long wl = (long long)e->box_nb[0] * e->box_nb[1] * e->box_nb[2] * EIG_MB_MAX;
         double *W[2] = {e->d_W, e->d_W + wl};
         IGX_HIP(hipMemsetAsync(z, 0, (size_t)s->n * mb * sizeof(double), st));
@@ -3580,21 +3573,11 @@ int igx_solver_eig_set_precond(igx_solver *s, int precond, const int32_t *box_lo
         return IGX_OK;
     }
     if (precond != IGX_PRECOND_KRON) { set_error("%s: unknown preconditioner %d", what, precond); return IGX_ERR_ARG; }
-    if (!box_lo || !box_hi || !U || !lam) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
-    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("%s: unknown lam_mode %d", what, lam_mode); return IGX_ERR_ARG; }
-    int nb[3] = {1, 1, 1};
-    if (int rc = check_free_box(s, 0, box_lo, box_hi, U, lam, nb, what)) return rc;
-    std::vector<double> h;
-    pack_fastdiag(h, s->dim, nb, U, lam);
-    IGX_HIP(hipStreamSynchronize(st));
-    e->precond = IGX_PRECOND_NONE;
-    (void)hipFree(e->d_fac); e->d_fac = nullptr;
+    int nb[3];
+    if (int rc = box_fastdiag_setup(s, 0, box_lo, box_hi, U, lam, lam_mode, what, &e->precond, e->d_fac, nb)) return rc;
     (void)hipFree(e->d_W); e->d_W = nullptr;
     const size_t wl = (size_t)nb[0] * nb[1] * nb[2] * EIG_MB_MAX;
-    IGX_HIP(hipMalloc((void **)&e->d_fac, h.size() * sizeof(double)));
     IGX_HIP(hipMalloc((void **)&e->d_W, 2 * wl * sizeof(double)));
-    IGX_HIP(hipMemcpyAsync(e->d_fac, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    IGX_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < 3; ++k) { e->box_lo[k] = k < s->dim ? box_lo[k] : 0; e->box_nb[k] = nb[k]; }
     e->lam_mode = lam_mode;
     e->precond = IGX_PRECOND_KRON;

@@ -158,18 +158,29 @@ def fastdiag_factors(kvs, lo, hi, stiff, mats1d=None):
     return U, lam, (_lib.IGX_KRON_SUM if stiff else _lib.IGX_KRON_PRODUCT)
 
 
+def _box_args(lo, hi, U, lam):
+    """The ctypes arrays ``(box_lo, box_hi, U, lam)`` of ``igx_solver_set_precond`` and its kin: three slots per box (one box, or
+    the boxes of all patches one after the other), an absent factor (None) a null pointer.  The caller keeps the NumPy arrays
+    alive over the call."""
+    n = max(3, len(lo))
+    ptrs = lambda arrays: (_lib._dp * n)(*[None if a is None else _lib.dptr(a) for a in arrays])
+    return (C.c_int32 * n)(*lo), (C.c_int32 * n)(*hi), ptrs(U), ptrs(lam)
+
+
 class _DeviceSystem:
     """What the device-resident Dirichlet problems share: the solver handle (``igx_solver_*``) and its lifecycle, the method, the
     preconditioner, the solve and the solver's SpMV and preconditioner alone.
 
     A subclass sets ``PRECONDS`` (preconditioner names -> ``IGX_PRECOND_*``), ``_ctx`` (the context of the device vectors) and
     ``n``, creates the handle with ``_attach``, and implements ``_set_factors(handle)`` (the preconditioner ``FACTORED`` that
-    needs a host set-up) and ``_drop_owner()`` (what ``close()`` releases besides the handle).  ``_factors_set``: the set-up is
-    done once and kept (else it runs whenever ``FACTORED`` is chosen)."""
+    needs a host set-up).  ``_drop_owner()`` is what ``close()`` releases besides the handle: the ``patch``, unless it is the
+    caller's (``_own_patch`` False); a system that owns something else overrides it.  ``_factors_set``: the set-up is done once
+    and kept (else it runs whenever ``FACTORED`` is chosen)."""
     PRECONDS = _lib.PRECONDS
     FACTORED = 'kron'
     handle = None
     _factors_set = False
+    _own_patch = True
 
     def _attach(self, create, args, bcs, method, initial):
         """The device solver made by `create` (``igx_solver_create*``, leading arguments `args`) with the fixed dofs of `bcs`;
@@ -210,6 +221,11 @@ class _DeviceSystem:
         else:
             _lib.check(_lib.load().igx_solver_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_set_precond')
         self._precond = key
+
+    def _drop_owner(self):
+        if getattr(self, 'patch', None) is not None and self._own_patch:
+            self.patch.close()
+        self.patch = None
 
     def _release(self):
         if self.handle:
@@ -278,7 +294,6 @@ class PatchSystem(_DeviceSystem):
     None.  ``solve(...)`` returns the completed full vector and leaves the solver's statistics in ``info``.  ``spmv(x)``
     (``R A R^T x``) and ``apply_precond(r)`` (``z = P r``) run the solver's SpMV and preconditioner alone on the device.
     """
-    _own_patch = True
 
     def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None, method='cg'):
         self.kvs = tuple(kvs)
@@ -305,11 +320,6 @@ class PatchSystem(_DeviceSystem):
         self._attach(create, (self.patch.handle, _lib.KINDS[self.kind]), bcs, method, initial)
         self.box = dirichlet_box(self.ndofs, self.bc_indices)
 
-    def _drop_owner(self):
-        if getattr(self, 'patch', None) is not None and self._own_patch:
-            self.patch.close()
-        self.patch = None
-
     def _kron_factors(self):
         """Per-axis eigenvectors and eigenvalues of the 1D Dirichlet matrices of the free range."""
         stiff = self.kind != 'mass'                           # (any other form: the parametric Laplacian of the free box)
@@ -319,10 +329,7 @@ class PatchSystem(_DeviceSystem):
         if self.box is None:
             raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch")
         U, lam, mode = self._kron_factors()
-        lo = (C.c_int32 * 3)(*self.box[0])
-        hi = (C.c_int32 * 3)(*self.box[1])
-        Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
-        Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+        lo, hi, Up, Lp = _box_args(self.box[0], self.box[1], U, lam)
         _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_set_precond')
 
     def solve(self, tol=1e-8, maxiter=1000, precond='kron', x0=None, check_every=1, timed=False):
@@ -536,11 +543,6 @@ class VectorFormSystem(_DeviceSystem):
         self.boxes = [dirichlet_box(self.ndofs, idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N)
                       for c in range(nc)]
 
-    def _drop_owner(self):
-        if getattr(self, 'patch', None) is not None:
-            self.patch.close()
-        self.patch = None
-
     @property
     def default_precond(self):
         return 'kron' if all(b is not None for b in self.boxes) else 'jacobi'
@@ -566,10 +568,7 @@ class VectorFormSystem(_DeviceSystem):
     def _set_factors(self, h):
         lib = _lib.load()
         for c, (lo, hi, U, lam, mode) in enumerate(self.kron_factors()):
-            lo_ = (C.c_int32 * 3)(*lo)
-            hi_ = (C.c_int32 * 3)(*hi)
-            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
-            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+            lo_, hi_, Up, Lp = _box_args(lo, hi, U, lam)
             _lib.check(lib.igx_solver_set_block_kron(h, c, lo_, hi_, Up, Lp, mode), 'igx_solver_set_block_kron')
         _lib.check(lib.igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, None, None, None, None, 0), 'igx_solver_set_precond')
         self._factors_set = True
@@ -985,11 +984,9 @@ class MultipatchSystem(_DeviceSystem):
 
     def _set_factors(self, h):
         boxes, U, lam, mode = self.schwarz_setup()
-        P = len(boxes)
-        lo = (C.c_int32 * (3 * P))(*[b[0][k] if k < len(b[0]) else 0 for b in boxes for k in range(3)])
-        hi = (C.c_int32 * (3 * P))(*[b[1][k] if k < len(b[1]) else 0 for b in boxes for k in range(3)])
-        Up = (_lib._dp * (3 * P))(*[_lib.dptr(u[k]) if k < len(u) else None for u in U for k in range(3)])
-        Lp = (_lib._dp * (3 * P))(*[_lib.dptr(l[k]) if k < len(l) else None for l in lam for k in range(3)])
+        slots = lambda per_patch, fill: [v[k] if k < len(v) else fill for v in per_patch for k in range(3)]
+        lo, hi, Up, Lp = _box_args(slots([b[0] for b in boxes], 0), slots([b[1] for b in boxes], 0), slots(U, None),
+                                   slots(lam, None))
         _lib.check(_lib.load().igx_solver_set_schwarz(h, lo, hi, Up, Lp, mode), 'igx_solver_set_schwarz')
         self._factors_set = True
 
@@ -1248,6 +1245,20 @@ def _form_kind(problem):
     return getattr(cls, '_kind', None)
 
 
+def _check_times(name, tau, t0, t_end, save_every):
+    """``(tau, t0, t_end, save_every)`` of an integration as three floats and an int, or ValueError (`name`: what the caller
+    calls its step)."""
+    tau, t0, t_end = float(tau), float(t0), float(t_end)
+    if not (tau > 0 and math.isfinite(tau)):
+        raise ValueError('%s must be positive and finite, not %r' % (name, tau))
+    if not t_end > t0:
+        raise ValueError('t_end (%r) must be greater than t0 (%r)' % (t_end, t0))
+    save_every = int(save_every)
+    if save_every < 1:
+        raise ValueError('save_every must be >= 1')
+    return tau, t0, t_end, save_every
+
+
 class ParabolicSystem(_DeviceSystem):
     """The parabolic problem ``M u' = f - K u`` on the free dofs, ``u = g`` on the dofs of `bcs`, ``u(t0) = u0``, of one patch,
     integrated on the device by a DIRK scheme with constant steps (the reference's ``crank_nicolson``, ``sdirk3``, ``esdirk34``,
@@ -1316,11 +1327,6 @@ class ParabolicSystem(_DeviceSystem):
         self._eig = None
         self._step_precond = None                                # the preconditioner of the stepping session on the device
 
-    def _drop_owner(self):
-        if getattr(self, 'patch', None) is not None and self._own_patch:
-            self.patch.close()
-        self.patch = None
-
     @property
     def default_precond(self):
         return 'kron' if self.box is not None else 'jacobi'
@@ -1356,10 +1362,7 @@ class ParabolicSystem(_DeviceSystem):
 
     def _set_factors(self, h):
         U, lam = self.kron_factors()
-        lo = (C.c_int32 * 3)(*self.box[0])
-        hi = (C.c_int32 * 3)(*self.box[1])
-        Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
-        Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+        lo, hi, Up, Lp = _box_args(self.box[0], self.box[1], U, lam)
         _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, _lib.IGX_KRON_SUM),
                    'igx_solver_set_precond')
 
@@ -1387,28 +1390,11 @@ class ParabolicSystem(_DeviceSystem):
             return self.integrate_adaptive(u0, tau, t_end, None, scheme=scheme, t0=t0, solve_tol=tol, maxiter=maxiter,
                                            precond=precond, save_every=save_every, check_every=check_every, timed=timed)
         name, A, gamma = _scheme(scheme)
-        tau, t0, t_end = float(tau), float(t0), float(t_end)
-        if not (tau > 0 and math.isfinite(tau)):
-            raise ValueError('tau must be positive and finite, not %r' % (tau,))
-        if not t_end > t0:
-            raise ValueError('t_end (%r) must be greater than t0 (%r)' % (t_end, t0))
-        save_every = int(save_every)
-        if save_every < 1:
-            raise ValueError('save_every must be >= 1')
-        key = self.default_precond if precond == 'auto' else precond
-        if (key if key is not None else 'none') not in self.PRECONDS:
-            raise ValueError('unknown preconditioner %r' % (precond,))
-        if key == 'kron' and self.box is None:
-            raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch (or none)")
+        tau, t0, t_end, save_every = _check_times('tau', tau, t0, t_end, save_every)
+        key = self._check_precond(precond)
         nsteps = int(math.ceil((t_end - t0) / tau))
         h = self._live()
-        if callable(u0):
-            from . import approx
-            u0 = approx.project_L2(self.kvs, u0, f_physical=True, geo=self.geo)
-        x0 = np.array(u0, dtype=np.float64).ravel()
-        if x0.size != self.n:
-            raise ValueError('u0 has %d entries, the space %d' % (x0.size, self.n))
-        x0[self.bc_indices] = self.bc_values
+        x0 = self._start_vector(u0)
         self.set_scheme(A, tau)
         self.set_precond(key)
         s = A.shape[1]
@@ -1444,6 +1430,18 @@ class ParabolicSystem(_DeviceSystem):
             raise ValueError("precond='kron' needs the Dirichlet dofs to be a union of whole sides of the patch (or none)")
         return key if key is not None else 'none'
 
+    def _start_vector(self, u0):
+        """`u0` (a vector, or a function of the physical coordinates: its L2 projection) as a full vector of its own with g on
+        the fixed dofs."""
+        if callable(u0):
+            from . import approx
+            u0 = approx.project_L2(self.kvs, u0, f_physical=True, geo=self.geo)
+        x0 = np.array(u0, dtype=np.float64).ravel()
+        if x0.size != self.n:
+            raise ValueError('u0 has %d entries, the space %d' % (x0.size, self.n))
+        x0[self.bc_indices] = self.bc_values
+        return x0
+
     def _set_step_precond(self, h, key):
         """The session's preconditioner: for 'kron' the factors U_k and the RAW eigenvalues go up once; the device rescales
         them per step and for the mass solve."""
@@ -1454,10 +1452,7 @@ class ParabolicSystem(_DeviceSystem):
             if self._eig is None:
                 self._eig = fastdiag_factors(self.kvs, self.box[0], self.box[1], True)[:2]
             U, lam = self._eig
-            lo = (C.c_int32 * 3)(*self.box[0])
-            hi = (C.c_int32 * 3)(*self.box[1])
-            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
-            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+            lo, hi, Up, Lp = _box_args(self.box[0], self.box[1], U, lam)
             _lib.check(lib.igx_solver_set_step_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp), 'igx_solver_set_step_precond')
         else:
             _lib.check(lib.igx_solver_set_step_precond(h, self.PRECONDS[key], None, None, None, None), 'igx_solver_set_step_precond')
@@ -1470,13 +1465,7 @@ class ParabolicSystem(_DeviceSystem):
         st = _stepper(scheme, need_estimate)
         key = self._check_precond(precond)
         h = self._live()
-        if callable(u0):
-            from . import approx
-            u0 = approx.project_L2(self.kvs, u0, f_physical=True, geo=self.geo)
-        x0 = np.array(u0, dtype=np.float64).ravel()
-        if x0.size != self.n:
-            raise ValueError('u0 has %d entries, the space %d' % (x0.size, self.n))
-        x0[self.bc_indices] = self.bc_values
+        x0 = self._start_vector(u0)
         lib = _lib.load()
         # the session forms its own C and preconditioner data: what set_scheme / set_precond left is void after it
         self._step = None
@@ -1544,18 +1533,12 @@ class ParabolicSystem(_DeviceSystem):
         far are returned, a RuntimeWarning says so and ``info['converged']`` is False.  ``info``: per attempt ``tau``, ``r``,
         ``accepted``, ``stage_iterations``, ``mass_iterations``; the counts ``attempts``, ``rejections``, ``reformations``; the
         phase times (ms, summed; all but ``total_ms`` and ``axpby_ms`` need `timed`)."""
-        tau0, t0, t_end = float(tau0), float(t0), float(t_end)
-        if not (tau0 > 0 and math.isfinite(tau0)):
-            raise ValueError('tau0 must be positive and finite, not %r' % (tau0,))
-        if not t_end > t0:
-            raise ValueError('t_end (%r) must be greater than t0 (%r)' % (t_end, t0))
+        tau0, t0, t_end, save_every = _check_times('tau0', tau0, t0, t_end, save_every)
         if tol is not None and not tol > 0:
             raise ValueError('tol must be positive (or None for constant steps), not %r' % (tol,))
         if not 0 < step_factor <= 1:
             raise ValueError('step_factor must lie in (0, 1], not %r' % (step_factor,))
-        save_every, max_attempts = int(save_every), int(max_attempts)
-        if save_every < 1:
-            raise ValueError('save_every must be >= 1')
+        max_attempts = int(max_attempts)
         if max_attempts < 1:
             raise ValueError('max_attempts must be >= 1')
         st, x0 = self.begin_steps(u0, scheme, precond, need_estimate=tol is not None)
@@ -2251,11 +2234,6 @@ class EigenSystem(_EigBlockPieces, _DeviceSystem):
             raise
         self._eig_precond = False                                    # (no preconditioner of the eigen pieces set yet)
 
-    def _drop_owner(self):
-        if getattr(self, 'patch', None) is not None and self._own_patch:
-            self.patch.close()
-        self.patch = None
-
     @property
     def default_precond(self):
         return 'kron' if self.box is not None else 'jacobi'
@@ -2278,10 +2256,7 @@ class EigenSystem(_EigBlockPieces, _DeviceSystem):
             if self.box is None:
                 raise ValueError("precond='kron' needs the fixed dofs to be a union of whole sides of the patch")
             U, lam, mode = self._kron_factors()
-            lo = (C.c_int32 * 3)(*self.box[0])
-            hi = (C.c_int32 * 3)(*self.box[1])
-            Up = (_lib._dp * 3)(*[_lib.dptr(u) for u in U])
-            Lp = (_lib._dp * 3)(*[_lib.dptr(l) for l in lam])
+            lo, hi, Up, Lp = _box_args(self.box[0], self.box[1], U, lam)
             _lib.check(lib.igx_solver_eig_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_eig_set_precond')
         else:
             _lib.check(lib.igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
