@@ -134,7 +134,7 @@ typedef struct {
 typedef struct {
     float total_ms;
     float fields_ms, stage0_ms, stage1_ms, final_ms, entry_ms;
-    int32_t algo_used;                 /* IGX_ALGO_ENTRYWISE / IGX_ALGO_SUMFACT; 3 after igx_load_vector (total_ms = its contractions), 4 / 5: igx_patch_eval_spline_d / _exprs_inputs_d */
+    int32_t algo_used;                 /* IGX_ALGO_ENTRYWISE / IGX_ALGO_SUMFACT; 3 after igx_load_vector (total_ms = its contractions), 4 / 5: igx_patch_eval_spline_d / _exprs_inputs_d, 6: igx_patch_quad_sums_d / _error_sums_d */
     int32_t n_launches;
 } igx_timing;
 
@@ -355,6 +355,22 @@ int igx_rtc_compile_exprs_inputs(int n, const char *const *expr, int m, const ch
 /* igx_load_vector_jet with the coefficients F_r on the RESIDENT Gauss slab in device memory (d_coef[r] or NULL) and the result
    (row0_hi-row0_lo) x N1 [x N2] doubles left in device memory.  Replaces the IGX_FORM coefficients of the patch. */
 int igx_load_vector_jet_d(igx_patch *patch, const double *const d_coef[4], double *d_out);
+
+/* --- integrals and error norms over a whole patch -----------------------------------------------------
+   Every array is a device array over the resident Gauss points in the layout of igx_patch_eval_spline_d.  Total and per-element
+   sums are formed in a fixed order without atomics: two calls with the same inputs return the same bits.  A row slab or a span
+   box: IGX_ERR_UNSUPPORTED.  igx_last_timing: total_ms = the kernels, algo_used = 6.
+
+   out[k] = sum over the patch of W f_k, W = gw |det J|, for 1 <= nf <= 4 arrays; d_elem: NULL or [nf][nelem] per-element sums,
+   elements in span order (s0, s1[, s2]) row-major.  Replaces pyiga/assemble.py:658-697 (integrate) for one patch. */
+int igx_patch_quad_sums_d(igx_patch *patch, int nf, const double *const *d_f, double *d_elem, double *out);
+/* u_h: the spline of the patch's own space with the DEVICE dof vector d_coeffs.  d_exact (or NULL: all absent): d_exact[0] the
+   exact values at the resident Gauss points or NULL; d_exact[1..dim]: the exact physical gradient in jet order (d/dx first, x the
+   last grid axis) or NULL; all or none of the gradient arrays.  An absent array is zero.  out[0] = sum W (u_h - g)^2; with
+   want_grad out[1] = sum W |grad u_h - grad g|^2 (a spline geometry: a geometry given as Jacobian arrays serves want_grad = 0
+   only).  d_elem: NULL or [1 + want_grad][nelem]. */
+int igx_patch_error_sums_d(igx_patch *patch, const double *d_coeffs, int want_grad, const double *const d_exact[4],
+                           double *d_elem, double out[2]);
 
 /* Precomputed fields (W or upper triangle of B) of the owned Gauss slab: out has shape
    (F, G0_local, G1[, G2]) (structure-of-arrays).  For tests of precompute_fields. */

@@ -1,5 +1,5 @@
-"""Interpolation in tensor-product spline spaces (the part of ``pyiga.approx`` the Dirichlet helpers use,
-pyiga/approx.py:14-47)."""
+"""Interpolation and L2 projection in tensor-product spline spaces (the part of ``pyiga.approx`` the Dirichlet helpers use,
+pyiga/approx.py:14-47, 62-96), and the error norms of a spline given by its dofs."""
 import numpy as np
 import scipy.sparse.linalg
 
@@ -73,3 +73,100 @@ def project_L2(kvs, f, f_physical=False, geo=None):
     finally:
         S.close()
     return x.reshape(rhs.shape)
+
+
+def _trace_exact(exact, grad_exact, dim):
+    """C texts of the exact value and (if given) of its `dim` partials, or None when one of them cannot be traced."""
+    from . import symbolic
+    src = symbolic.trace_function(exact, dim)
+    if src is None:
+        return None
+    srcs = [src]
+    if grad_exact is not None:
+        try:
+            X = symbolic.coordinates(dim)
+            val = grad_exact(*(X[..., k] for k in range(dim)))
+            if not isinstance(val, (tuple, list)) or len(val) != dim:
+                return None
+            srcs += [symbolic.c_source(np.broadcast_to(np.asarray(v, dtype=object), (1,) * dim)) for v in val]
+        except Exception:
+            return None
+    return srcs
+
+
+def _exact_arrays(patch, geo, exact, grad_exact, f_physical):
+    """Device pointers of the exact value and of its physical partials over the resident Gauss points of `patch` (None where
+    absent): by ONE generated kernel when the functions are traceable and the coordinates the kernel sees are the ones they are
+    given in, else sampled on the host and uploaded."""
+    from . import _lib, geometry
+    if exact is None:
+        return None
+    dim = patch.dim
+    n = 1 + (dim if grad_exact is not None else 0)
+    ptrs = None
+    # the generated kernels evaluate at the PHYSICAL points of a spline geometry (no geometry: the two coincide)
+    if geo is None or (f_physical and isinstance(geo, (bspline.BSplineFunc, geometry.NurbsFunc))):
+        srcs = _trace_exact(exact, grad_exact, dim)
+        if srcs is not None:
+            try:
+                ptrs, _ = patch.eval_exprs_inputs(srcs, [], buf='_d_qex')
+            except _lib.IgxError as e:                           # (no run-time compiler on this box / not traceable into a kernel: sampled on the host)
+                if not _lib.sampled_fallback(e, 'the exact solution of an error norm'):
+                    raise
+    if ptrs is None:
+        grid = tuple(patch.gauss(k)[0] for k in range(dim))
+        G = tuple(len(ax) for ax in grid)
+        sample = (lambda f: utils.grid_eval_transformed(f, grid, geo)) if (f_physical and geo is not None) else (lambda f: utils.grid_eval(f, grid))
+        arrs = [np.broadcast_to(np.asarray(sample(exact), dtype=float), G)]
+        if grad_exact is not None:
+            g = np.asarray(sample(grad_exact), dtype=float)
+            if g.shape != G + (dim,):
+                raise ValueError('grad_exact returns the %d physical partials (d/dx first)' % dim)
+            arrs += [g[..., k] for k in range(dim)]
+        ptrs = patch.upload_fields(arrs, buf='_d_qex')
+    return list(ptrs) + [None] * (4 - n)
+
+
+def error_norms(kvs, geo, u, exact=None, grad_exact=None, f_physical=True, elementwise=False, patch=None):
+    """``(l2, h1)``: the L2 norm and the H1 seminorm of ``u_h - exact`` over the geometry `geo` (None: the parameter domain), for
+    the spline `u_h` of the tensor-product space `kvs` given by `u` -- a dof array of ``prod(ndofs)`` entries, a scalar
+    ``BSplineFunc`` on `kvs`, or an ``operators.DeviceArray`` of the dofs (read where it is).
+
+    ``exact(x, y[, z])`` returns the value, ``grad_exact(x, y[, z])`` the physical partials, d/dx first; with
+    ``f_physical=False`` both are given in parametric coordinates.  `h1` is None when `exact` comes without `grad_exact`; without
+    `exact` the norms are those of `u_h` itself.  ``elementwise=True``: the two entries are the arrays of the SQUARED element
+    contributions, of shape ``numspans``.  `patch`: a ``DevicePatch`` of (kvs, geo) to use instead of setting one up.
+
+    One fused device pass (``igx_patch_error_sums_d``): spline, gradient, difference, square and weight at the Gauss points of
+    the ``max(p) + 1`` rule, summed element by element in a fixed order.  2D and 3D.
+    """
+    from . import assemblers, geometry
+    from .operators import DeviceArray
+    if isinstance(kvs, bspline.KnotVector):
+        kvs = (kvs,)
+    kvs = tuple(kvs)
+    dim = len(kvs)
+    assert dim in (2, 3), 'error_norms: 2D and 3D patches'
+    if grad_exact is not None and exact is None:
+        raise ValueError('error_norms: grad_exact without exact')
+    ndofs = tuple(kv.numdofs for kv in kvs)
+    n = int(np.prod(ndofs))
+    if isinstance(u, DeviceArray):
+        size, c = u.n, None
+    else:
+        c = np.asarray(u.coeffs if hasattr(u, 'coeffs') else u, dtype=np.float64)
+        size = c.size
+    if size != n:
+        raise ValueError('error_norms: %d dofs, the space has %d' % (size, n))
+    want_grad = exact is None or grad_exact is not None
+    P = patch if patch is not None else assemblers.DevicePatch(kvs, geo if geo is not None else geometry.unit_cube(dim))
+    try:
+        d_u = u.ptr if c is None else P.upload_dofs(c.reshape(ndofs), buf='_d_qdofs')
+        d_exact = _exact_arrays(P, geo, exact, grad_exact, f_physical)
+        res = P.error_sums(d_u, want_grad, d_exact, elementwise=elementwise)
+    finally:
+        if patch is None:
+            P.close()
+    if elementwise:
+        return res[1][0], (res[1][1] if want_grad else None)
+    return float(np.sqrt(res[0])), (float(np.sqrt(res[1])) if want_grad else None)

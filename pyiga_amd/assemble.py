@@ -367,6 +367,64 @@ def inner_products(kvs, f, f_physical=False, geo=None):
 
 
 ################################################################################
+# Integration (pyiga/assemble.py:658-697)
+################################################################################
+
+def integrate(kvs, f, f_physical=False, geo=None):
+    """Integral of the function `f` over the geometry `geo`, or over the parameter domain without one: a float, or an array
+    over the component axes of a non-scalar `f`.
+
+    `f` is a function of (x, y, z) or a spline function object; `f_physical` says whether it is given in physical coordinates
+    (then `geo` is required).  The rule is the tensor Gauss rule with ``max(p) + 1`` points per span.  2D and 3D run on the
+    device: a traceable scalar callable is evaluated at the Gauss points there, anything else is sampled on the host and uploaded;
+    the products with the weight field are summed element by element in a fixed order (``DevicePatch.quad_sums``).  1D is a few
+    numpy lines on the host.
+    """
+    from . import geometry, utils, symbolic
+    from .quadrature import make_tensor_quadrature
+    if isinstance(kvs, bspline.KnotVector):
+        kvs = (kvs,)
+    kvs = tuple(kvs)
+    dim = len(kvs)
+    if f_physical:
+        assert geo is not None, 'integrate in physical domain requires geometry'
+    if dim == 1:
+        grid, gw = make_tensor_quadrature([kvs[0].mesh], kvs[0].p + 1)
+        fvals = np.array(utils.grid_eval_transformed(f, grid, geo) if f_physical else utils.grid_eval(f, grid), dtype=float)
+        w = gw[0].copy()
+        if geo is not None:
+            jac = np.asarray(geo.grid_jacobian(grid), dtype=float).reshape(len(grid[0]), -1)
+            assert jac.shape[1] == 1, '1D integrals need a scalar-valued geometry map'
+            w = w * np.abs(jac[:, 0])
+        return (fvals * w.reshape((-1,) + (1,) * (fvals.ndim - 1))).sum(axis=0)
+    assert dim in (2, 3), 'Dimensions higher than 3 are currently not implemented.'
+    g = geo if geo is not None else geometry.unit_cube(dim)     # parameter domain: |det J| = 1
+    patch = assemblers.DevicePatch(kvs, g)
+    try:
+        src = symbolic.trace_function(f, dim) if (not f_physical or isinstance(geo, (bspline.BSplineFunc, geometry.NurbsFunc))) else None
+        if src is not None:
+            try:
+                patch.eval_function_expr(src, parametric=not f_physical)
+                return patch.quad_sums([patch._d_f[0]])[0]
+            except _lib.IgxError as e:                           # (no run-time compiler on this box / not traceable into a kernel: sampled on the host)
+                if not _lib.sampled_fallback(e, 'the function of an integral'):
+                    raise
+        grid = tuple(patch.gauss(k)[0] for k in range(dim))
+        fvals = np.asarray(utils.grid_eval_transformed(f, grid, geo) if f_physical else utils.grid_eval(f, grid), dtype=float)
+        G = tuple(len(ax) for ax in grid)
+        comp_shape = fvals.shape[dim:]
+        flat = fvals.reshape(G + (-1,))
+        out = np.empty(flat.shape[-1])
+        for c0 in range(0, out.size, 4):                         # igx_patch_quad_sums_d takes up to 4 arrays
+            c1 = min(c0 + 4, out.size)
+            ptrs = patch.upload_fields([flat[..., c] for c in range(c0, c1)], buf='_d_qf')
+            out[c0:c1] = patch.quad_sums(ptrs)
+        return out.reshape(comp_shape) if comp_shape else out[0]
+    finally:
+        patch.close()
+
+
+################################################################################
 # Custom forms (pyiga/assemble.py:837-897)
 ################################################################################
 

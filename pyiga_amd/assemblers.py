@@ -42,6 +42,7 @@ class DevicePatch:
         lib = _lib.load()
         self.ctx = _lib.context(device)
         self.kvs = tuple(kvs)
+        self.geo = geo
         self.dim = len(self.kvs)
         assert self.dim in (2, 3), 'libigx assembles 2D and 3D patches'
         # Gauss points per span: max p + 1 (pyiga/assemblers.pyx:1338) unless the caller fixes it (a boundary patch uses the
@@ -472,12 +473,11 @@ class DevicePatch:
 
     def upload_fields(self, arrays, buf='_d_spl'):
         """Arrays over the full Gauss grid to the device, their resident planes one after the other in the buffer `buf` (the
-        layout of eval_spline); returns the device pointers."""
+        layout of eval_spline; the buffer holds 1 + dim arrays, or as many as are given); returns the device pointers."""
         npts = self.resident_points()
         g0_lo, g0_n = self.gauss_slab()
         G = tuple(self.info.ngauss[k] for k in range(self.dim))
-        base = self._dev_buffer(buf, 8 * npts * (1 + self.dim))
-        assert len(arrays) <= 1 + self.dim
+        base = self._dev_buffer(buf, 8 * npts * max(1 + self.dim, len(arrays)))
         for k, a in enumerate(arrays):
             a = np.asarray(a, dtype=np.float64)
             assert a.shape == G, 'field values have the wrong grid shape'
@@ -503,13 +503,52 @@ class DevicePatch:
         _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, base, out.nbytes), 'igx_dev_download')
         return out
 
-    def eval_exprs_inputs(self, exprs, d_inputs, to_host=False):
+    # -- integrals and error sums over the patch
+    @property
+    def numspans(self):
+        return tuple(self.info.nspans[k] for k in range(self.dim))
+
+    def _elem_result(self, d_elem, n):
+        out = np.empty((n,) + self.numspans)
+        _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, d_elem, out.nbytes), 'igx_dev_download')
+        return out
+
+    def quad_sums(self, d_arrays, elementwise=False):
+        """``sum W f_k`` over the patch for up to 4 device arrays over the resident Gauss points, W = Gauss weight times
+        ``|det J|`` (igx_patch_quad_sums_d).  Returns the array of the totals, or with `elementwise` (totals, per-element sums
+        of shape ``(len(d_arrays),) + numspans``)."""
+        nf = len(d_arrays)
+        ptrs = (C.c_void_p * max(nf, 1))(*d_arrays)
+        out = np.empty(max(nf, 1))
+        d_elem = self._dev_buffer('_d_qelem', 8 * nf * int(np.prod(self.numspans))) if elementwise else None
+        _lib.check(_lib.load().igx_patch_quad_sums_d(self.handle, nf, ptrs, d_elem, _lib.dptr(out)), 'igx_patch_quad_sums_d')
+        out = out[:nf]
+        return (out, self._elem_result(d_elem, nf)) if elementwise else out
+
+    def error_sums(self, d_coeffs, want_grad, d_exact, elementwise=False):
+        """``sum W (u_h - g)^2`` and, with `want_grad`, ``sum W |grad u_h - grad g|^2`` for the spline u_h with the device dof
+        vector `d_coeffs` (igx_patch_error_sums_d).  `d_exact`: device pointers of the exact value and of its physical partials
+        (d/dx first) over the resident Gauss points, None where absent (= 0), or None for all.  Returns the array of the 1 or 2
+        sums, or with `elementwise` (sums, per-element sums of shape ``(1 or 2,) + numspans``)."""
+        n = 2 if want_grad else 1
+        ptrs = (C.c_void_p * 4)()
+        for r, e in enumerate(d_exact or ()):
+            if e is not None:
+                ptrs[r] = e
+        out = np.empty(2)
+        d_elem = self._dev_buffer('_d_qelem', 8 * n * int(np.prod(self.numspans))) if elementwise else None
+        _lib.check(_lib.load().igx_patch_error_sums_d(self.handle, d_coeffs, 1 if want_grad else 0, ptrs, d_elem, _lib.dptr(out)),
+                   'igx_patch_error_sums_d')
+        out = out[:n].copy()
+        return (out, self._elem_result(d_elem, n)) if elementwise else out
+
+    def eval_exprs_inputs(self, exprs, d_inputs, to_host=False, buf='_d_tab'):
         """out[k] = exprs[k](x, y, z, pi, f0, f1, ..) at the resident Gauss points, f_j read from the device array d_inputs[j]
         (igx_patch_eval_exprs_inputs_d: compiled at run time, cached).  Returns (device pointers of the len(exprs) arrays, cache
-        hit); the arrays are kept by the patch and overwritten by the next call."""
+        hit); the arrays are kept by the patch (in its buffer `buf`) and overwritten by the next call."""
         npts = self.resident_points()
         n, m = len(exprs), len(d_inputs)
-        base = self._dev_buffer('_d_tab', 8 * npts * n)
+        base = self._dev_buffer(buf, 8 * npts * n)
         ex = (C.c_char_p * n)(*[e.encode() for e in exprs])
         ins = (C.c_void_p * max(m, 1))(*d_inputs)
         hit = C.c_int(0)

@@ -122,6 +122,40 @@ __device__ inline void physical_jacobian(const GeoView &gv, bool nurbs, const in
     finish_jacobian<DIM>(val, jac, nurbs, ncomp, gv.nc, Jm, ev);
 }
 
+// Physical gradient of a function from its PARAMETRIC gradient gp in jet order (last grid axis first) at Gauss point gi:
+// D_r w = sum_c (d xi_c / d x_r) Dhat_c w, the inverse of Jm[r][c] = d G_r / d xi_c.  One text for the spline evaluation
+// (kern_spline.hip) and the error sums (kern_quad.hip): the two compute the same gradient.
+template <int DIM>
+__device__ __forceinline__ void physical_gradient(const GeoView &gv, bool nurbs, const int gi[3], const double gp[3], double pg[3])
+{
+    double Jm[MAX_COMP][3], ev[MAX_COMP];
+    physical_jacobian<DIM>(gv, nurbs, gi, DIM, Jm, ev);
+    if (DIM == 2) {
+        const double inv = 1.0 / (Jm[0][0] * Jm[1][1] - Jm[0][1] * Jm[1][0]);
+        // JI = inv * [[J11, -J01], [-J10, J00]]; D_r = sum_c JI[c][r] gp[c]
+        pg[0] = inv * (Jm[1][1] * gp[0] - Jm[1][0] * gp[1]);
+        pg[1] = inv * (Jm[0][0] * gp[1] - Jm[0][1] * gp[0]);
+    } else {
+        const double t[9] = {Jm[0][0], Jm[0][1], Jm[0][2], Jm[1][0], Jm[1][1], Jm[1][2], Jm[2][0], Jm[2][1], Jm[2][2]};
+        const double t3 = t[4] * t[8] - t[5] * t[7];
+        const double t4 = t[3] * t[8] - t[5] * t[6];
+        const double t5 = t[3] * t[7] - t[4] * t[6];
+        const double inv = 1.0 / ((t[0] * t3 - t[1] * t4) + t[2] * t5);
+        double JI[9];                               // JI[3 c + r] = d xi_c / d x_r (fields_form: T[1 + c][1 + r])
+        JI[0] = inv * t3;
+        JI[1] = inv * -(t[1] * t[8] - t[2] * t[7]);
+        JI[2] = inv * (t[1] * t[5] - t[2] * t[4]);
+        JI[3] = inv * -t4;
+        JI[4] = inv * (t[0] * t[8] - t[2] * t[6]);
+        JI[5] = inv * -(t[0] * t[5] - t[2] * t[3]);
+        JI[6] = inv * t5;
+        JI[7] = inv * -(t[0] * t[7] - t[1] * t[6]);
+        JI[8] = inv * (t[0] * t[4] - t[1] * t[3]);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) pg[r] = (JI[r] * gp[0] + JI[3 + r] * gp[1]) + JI[6 + r] * gp[2];
+    }
+}
+
 // quadrature fields of one point from its Jacobian (row-major t[]): f[0] = W for the mass form, the upper
 // triangle of  W * JacInv JacInv^T  (row-major) for the stiffness form.  Returns the number of fields.
 template <int DIM>

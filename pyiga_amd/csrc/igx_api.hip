@@ -375,6 +375,7 @@ void igx_patch_destroy(igx_patch *pt)
     (void)hipFree(pt->d_ws_ij); (void)hipFree(pt->d_ws_out);
     (void)hipFree(pt->d_lv_f); (void)hipFree(pt->d_lv_t1); (void)hipFree(pt->d_lv_t2); (void)hipFree(pt->d_lv_o);
     (void)hipFree(pt->d_sp_ws);
+    (void)hipFree(pt->d_q_ws);
     delete pt;
 }
 
@@ -1421,6 +1422,73 @@ int igx_patch_eval_spline_d(igx_patch *pt, const double *d_coeffs, int want_grad
     pt->timing.algo_used = 4;                        // spline evaluation
     pt->timing.n_launches = pt->dim == 3 ? 2 : 1;
     return IGX_OK;
+}
+
+// Whole patches only, as igx_patch_eval_spline_d: the sums walk the Gauss grid of the patch
+static int quad_patch_ok(const igx_patch *pt, const char *who)
+{
+    if (pt->boxed) { set_error("%s: the patch holds a span box (batched entries only)", who); return IGX_ERR_UNSUPPORTED; }
+    if (pt->r0_lo != 0 || pt->r0_hi != pt->ax[0].N) { set_error("%s: whole patches only (a row slab holds a part of the Gauss grid)", who); return IGX_ERR_UNSUPPORTED; }
+    return IGX_OK;
+}
+
+// the totals down, the timing record of the two quadrature entry points
+static int quad_done(igx_patch *pt, hipStream_t st, const double *d_tot, int nk, double *out, int n_launches)
+{
+    IGX_HIP(hipMemcpyAsync(out, d_tot, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    memset(&pt->timing, 0, sizeof(pt->timing));
+    (void)hipEventElapsedTime(&pt->timing.total_ms, pt->ctx->ev[6], pt->ctx->ev[7]);
+    pt->timing.algo_used = 6;                        // quadrature sums
+    pt->timing.n_launches = n_launches;
+    return IGX_OK;
+}
+
+int igx_patch_quad_sums_d(igx_patch *pt, int nf, const double *const *d_f, double *d_elem, double *out)
+{
+    if (!pt || !d_f || !out || nf < 1 || nf > 4) { set_error("igx_patch_quad_sums_d: bad argument (1 <= nf <= 4 arrays)"); return IGX_ERR_ARG; }
+    for (int k = 0; k < nf; ++k)
+        if (!d_f[k]) { set_error("igx_patch_quad_sums_d: array %d is null", k); return IGX_ERR_ARG; }
+    if (int rcp = quad_patch_ok(pt, "igx_patch_quad_sums_d")) return rcp;
+    IGX_HIP(hipSetDevice(pt->ctx->device));
+    hipStream_t st = pt->ctx->stream;
+    int rc = ensure_fields(pt, IGX_MASS);           // W = gw0*gw1*gw2*|det J| on the resident Gauss slab
+    if (rc) return rc;
+    if ((rc = ws_reserve(&pt->d_q_ws, &pt->q_ws_cap, quad_workspace(pt, nf), "quadrature workspace"))) return rc;
+    double *d_tot = nullptr;
+    int nl = 0;
+    (void)hipEventRecord(pt->ctx->ev[6], st);
+    rc = launch_quad_sums(st, pt, nf, d_f, pt->d_fields, d_elem, pt->d_q_ws, &d_tot, &nl);
+    (void)hipEventRecord(pt->ctx->ev[7], st);
+    if (rc) return rc;
+    return quad_done(pt, st, d_tot, nf, out, nl);
+}
+
+int igx_patch_error_sums_d(igx_patch *pt, const double *d_coeffs, int want_grad, const double *const d_exact[4], double *d_elem, double out[2])
+{
+    if (!pt || !d_coeffs || !out) { set_error("igx_patch_error_sums_d: null argument"); return IGX_ERR_ARG; }
+    if (int rcp = quad_patch_ok(pt, "igx_patch_error_sums_d")) return rcp;
+    if (want_grad && pt->geo_kind == IGX_GEO_JACOBIAN) { set_error("igx_patch_error_sums_d: the physical gradient needs a spline geometry"); return IGX_ERR_UNSUPPORTED; }
+    if (int rcb = basis_orders_ok(pt, IGX_MASS, "igx_patch_error_sums_d")) return rcb;
+    if (want_grad && d_exact) {
+        int have = 0;
+        for (int r = 1; r <= pt->dim; ++r) have += d_exact[r] ? 1 : 0;
+        if (have != 0 && have != pt->dim) { set_error("igx_patch_error_sums_d: all or none of the exact gradient arrays"); return IGX_ERR_ARG; }
+    }
+    IGX_HIP(hipSetDevice(pt->ctx->device));
+    hipStream_t st = pt->ctx->stream;
+    int rc = ensure_fields(pt, IGX_MASS);
+    if (rc) return rc;
+    const int nk = want_grad ? 2 : 1;
+    if ((rc = ws_reserve(&pt->d_sp_ws, &pt->sp_ws_cap, spline_eval_workspace(pt, want_grad), "spline evaluation workspace"))) return rc;
+    if ((rc = ws_reserve(&pt->d_q_ws, &pt->q_ws_cap, quad_workspace(pt, nk), "quadrature workspace"))) return rc;
+    double *d_tot = nullptr;
+    int nl = 0;
+    (void)hipEventRecord(pt->ctx->ev[6], st);
+    rc = launch_error_sums(st, pt, d_coeffs, want_grad, d_exact, pt->d_fields, d_elem, pt->d_sp_ws, pt->d_q_ws, &d_tot, &nl);
+    (void)hipEventRecord(pt->ctx->ev[7], st);
+    if (rc) return rc;
+    return quad_done(pt, st, d_tot, nk, out, nl);
 }
 
 // out[k * npts + i] = expr_k(x, y, z, pi, f0 .. f{m-1}) at the resident points, f_j = d_in[j][i]

@@ -223,6 +223,8 @@ struct igx_patch {
     size_t lv_f_cap = 0, lv_t1_cap = 0, lv_t2_cap = 0, lv_o_cap = 0;
     double *d_sp_ws = nullptr;                // axis-0 expansion of igx_patch_eval_spline_d (kern_spline.hip), grow-only
     size_t sp_ws_cap = 0;
+    double *d_q_ws = nullptr;                 // partial lines, element sums and totals of igx_patch_quad_sums_d / _error_sums_d (kern_quad.hip), grow-only
+    size_t q_ws_cap = 0;
     // fused sweep + final stage (fused.hip)
     long long nnz_ext = 0;                    // values of the owned rows + the p0 halo planes above them (mirror sources)
     double *d_zeros = nullptr;                // a row of zeros: input of absent sweep slots
@@ -288,6 +290,13 @@ int launch_load_vector(hipStream_t st, const igx_patch *pt, const double *d_f, c
 // a spline of the patch's space from a device dof vector at the resident Gauss points (kern_spline.hip)
 size_t spline_eval_workspace(const igx_patch *pt, int want_grad);
 int launch_spline_eval(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, double *const d_out[4], double *d_ws);
+int launch_spline_axis0(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, double *d_ws, const double **t0, const double **t1);
+// sums of W f_k and error sums of a spline over a whole patch, total and per element, in a fixed order (kern_quad.hip)
+size_t quad_workspace(const igx_patch *pt, int nk);
+int launch_quad_sums(hipStream_t st, const igx_patch *pt, int nf, const double *const *d_f, const double *d_W, double *d_elem, double *d_ws,
+                     double **d_tot, int *n_launches);
+int launch_error_sums(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, const double *const d_exact[4], const double *d_W,
+                      double *d_elem, double *d_sp_ws, double *d_ws, double **d_tot, int *n_launches);
 // coefficient expressions that also read device arrays f0 .. f{m-1} at the thread's point (rtc.hip)
 int launch_form_exprs_inputs(hipStream_t st, igx_patch *pt, int n_expr, const char *const *expr, int m, const double *const *d_in, double *d_out, int *cache_hit);
 int rtc_compile_form_inputs(int n_expr, const char *const *expr, int m, const char *arch, char *path_out, int path_len, int *cache_hit);

@@ -97,36 +97,13 @@ __global__ void __launch_bounds__(SP_MAXWAVES * 64) k_spline12(const double *__r
             const long long idx = L * Gl + g;
             out.o[0][idx] = v;
             if (GRAD) {
-                // physical gradient: D_r w = sum_c (d xi_c / d x_r) Dhat_c w, the inverse of Jm[r][c] = d G_r / d xi_c
                 int gi[3];
                 if (DIM == 3) { gi[0] = g0_lo + (int)plane; gi[1] = gm; gi[2] = g; }
                 else { gi[0] = gm; gi[1] = g; gi[2] = 0; }
-                double Jm[MAX_COMP][3], ev[MAX_COMP];
-                physical_jacobian<DIM>(gv, nurbs != 0, gi, DIM, Jm, ev);
-                if (DIM == 2) {
-                    const double inv = 1.0 / (Jm[0][0] * Jm[1][1] - Jm[0][1] * Jm[1][0]);
-                    // JI = inv * [[J11, -J01], [-J10, J00]]; D_r = sum_c JI[c][r] gp[c]
-                    out.o[1][idx] = inv * (Jm[1][1] * gp[0] - Jm[1][0] * gp[1]);
-                    out.o[2][idx] = inv * (Jm[0][0] * gp[1] - Jm[0][1] * gp[0]);
-                } else {
-                    const double t[9] = {Jm[0][0], Jm[0][1], Jm[0][2], Jm[1][0], Jm[1][1], Jm[1][2], Jm[2][0], Jm[2][1], Jm[2][2]};
-                    const double t3 = t[4] * t[8] - t[5] * t[7];
-                    const double t4 = t[3] * t[8] - t[5] * t[6];
-                    const double t5 = t[3] * t[7] - t[4] * t[6];
-                    const double inv = 1.0 / ((t[0] * t3 - t[1] * t4) + t[2] * t5);
-                    double JI[9];                               // JI[3 c + r] = d xi_c / d x_r (fields_form: T[1 + c][1 + r])
-                    JI[0] = inv * t3;
-                    JI[1] = inv * -(t[1] * t[8] - t[2] * t[7]);
-                    JI[2] = inv * (t[1] * t[5] - t[2] * t[4]);
-                    JI[3] = inv * -t4;
-                    JI[4] = inv * (t[0] * t[8] - t[2] * t[6]);
-                    JI[5] = inv * -(t[0] * t[5] - t[2] * t[3]);
-                    JI[6] = inv * t5;
-                    JI[7] = inv * -(t[0] * t[7] - t[1] * t[6]);
-                    JI[8] = inv * (t[0] * t[4] - t[1] * t[3]);
+                double pg[3];
+                physical_gradient<DIM>(gv, nurbs != 0, gi, gp, pg);
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) out.o[1 + r][idx] = (JI[r] * gp[0] + JI[3 + r] * gp[1]) + JI[6 + r] * gp[2];
-                }
+                for (int r = 0; r < DIM; ++r) out.o[1 + r][idx] = pg[r];
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -149,6 +126,25 @@ size_t spline_eval_workspace(const igx_patch *pt, int want_grad)
     return pd.dim == 3 ? (size_t)(want_grad ? 2 : 1) * pd.G0_loc * pd.ax[1].N * pd.ax[2].N : 0;
 }
 
+// 3D: the axis-0 expansion of the dofs into d_ws (spline_eval_workspace() doubles); *t0 / *t1: what k_spline12 and k_err12 read as
+// value / axis-0 derivative planes (2D: the dofs themselves, nothing launched)
+int launch_spline_axis0(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, double *d_ws, const double **t0, const double **t1)
+{
+    const PatchDev &pd = pt->dev;
+    *t0 = d_coeffs;
+    *t1 = nullptr;
+    if (pd.dim != 3) return IGX_OK;
+    const bool grad = want_grad != 0;
+    const long long B = (long long)pd.ax[1].N * pd.ax[2].N, total = (long long)pd.G0_loc * B;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (grad) k_spline_axis0<2><<<grid, 256, 0, st>>>(d_coeffs, d_ws, pd.ax[0], pd.g0_lo, pd.G0_loc, B);
+    else k_spline_axis0<1><<<grid, 256, 0, st>>>(d_coeffs, d_ws, pd.ax[0], pd.g0_lo, pd.G0_loc, B);
+    IGX_HIP(hipGetLastError());
+    *t0 = d_ws;
+    *t1 = grad ? d_ws + total : nullptr;
+    return IGX_OK;
+}
+
 // d_coeffs: N0 x N1 [x N2] dofs; d_out[0 .. dim]: resident slab arrays (value, physical gradient in jet order; the gradient only
 // with want_grad); d_ws: spline_eval_workspace() doubles.  The caller has checked the patch (whole, not boxed, a spline geometry
 // for the gradient).
@@ -162,15 +158,7 @@ int launch_spline_eval(hipStream_t st, const igx_patch *pt, const double *d_coef
     const int nw = spline12_waves(dim, grad, al.N);
     if (nw == 0) { set_error("igx_patch_eval_spline_d: %d dofs on the last axis do not fit the line buffers", al.N); return IGX_ERR_UNSUPPORTED; }
     const double *t0 = d_coeffs, *t1 = nullptr;
-    if (dim == 3) {
-        const long long B = (long long)pd.ax[1].N * pd.ax[2].N, total = (long long)pd.G0_loc * B;
-        const dim3 grid((unsigned)((total + 255) / 256));
-        if (grad) k_spline_axis0<2><<<grid, 256, 0, st>>>(d_coeffs, d_ws, pd.ax[0], pd.g0_lo, pd.G0_loc, B);
-        else k_spline_axis0<1><<<grid, 256, 0, st>>>(d_coeffs, d_ws, pd.ax[0], pd.g0_lo, pd.G0_loc, B);
-        IGX_HIP(hipGetLastError());
-        t0 = d_ws;
-        t1 = grad ? d_ws + total : nullptr;
-    }
+    if (int rc = launch_spline_axis0(st, pt, d_coeffs, want_grad, d_ws, &t0, &t1)) return rc;
     SplineOut out{};
     for (int k = 0; k < 4; ++k) out.o[k] = k == 0 || (grad && k <= dim) ? d_out[k] : nullptr;
     GeoView gv{};

@@ -285,6 +285,21 @@ class Multipatch:
             bcs.append((p2g[p][idx], vals))
         return combine_bcs(bcs)
 
+    def error_norms(self, u, exact, grad_exact=None):
+        """``(l2, h1)`` of ``u_h - exact`` over the whole domain for the global dof vector `u`; `exact` and `grad_exact` as for
+        ``approx.error_norms`` (physical coordinates; `h1` is None without `grad_exact`).  The patches are taken in turn, one
+        ``DevicePatch`` at a time; the squares are summed and the root is taken once."""
+        from . import approx
+        u = np.asarray(u, dtype=np.float64).ravel()
+        if u.size != self.numdofs:
+            raise ValueError('error_norms: %d dofs, the multipatch has %d' % (u.size, self.numdofs))
+        sq = np.zeros(2)
+        for p, (kvs, geo) in enumerate(self.patches):
+            l2, h1 = approx.error_norms(kvs, geo, self.global_to_patch(p) @ u, exact, grad_exact)
+            sq += (l2 ** 2, 0.0 if h1 is None else h1 ** 2)
+        want_grad = exact is None or grad_exact is not None
+        return float(np.sqrt(sq[0])), (float(np.sqrt(sq[1])) if want_grad else None)
+
     # -- device side
     def _drop_device(self):
         for solver in list(getattr(self, '_solvers', ())):

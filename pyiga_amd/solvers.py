@@ -285,7 +285,20 @@ class _DeviceSystem:
         return self._device_op(_lib.load().igx_solver_precond_d, 'igx_solver_precond_d', r)
 
 
-class PatchSystem(_DeviceSystem):
+class _PatchErrorNorms:
+    """``error_norms`` of the one-patch systems: they have ``self.patch`` and ``self.kvs``."""
+
+    def error_norms(self, u, exact=None, grad_exact=None, elementwise=False):
+        """``(l2, h1)`` of ``u_h - exact`` for a solution `u` of this system (host dofs, a scalar ``BSplineFunc`` or a
+        ``DeviceArray``), `exact` and `grad_exact` functions of the physical coordinates: ``approx.error_norms`` on the system's
+        own patch, so the geometry is not set up a second time."""
+        from . import approx
+        if self.patch is None:
+            raise _lib.IgxError('%s: the system was closed' % type(self).__name__)
+        return approx.error_norms(self.kvs, self.patch.geo, u, exact, grad_exact, elementwise=elementwise, patch=self.patch)
+
+
+class PatchSystem(_PatchErrorNorms, _DeviceSystem):
     """The Dirichlet problem ``A u = b`` with ``u = g`` on the dofs of `bcs`, for the mass or stiffness matrix of one patch,
     assembled and solved on the device.
 
@@ -729,6 +742,10 @@ class MultipatchSystem(_DeviceSystem):
         self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
         self._attach('igx_solver_create_multipatch', (h,), bcs, method, 'cg')
         MP._solvers.add(self)
+
+    def error_norms(self, u, exact, grad_exact=None):
+        """``Multipatch.error_norms`` of the system's multipatch for a global solution vector `u`."""
+        return self.MP.error_norms(u, exact, grad_exact)
 
     def _drop_owner(self):
         self._drop_multigrid()
@@ -1259,7 +1276,7 @@ def _check_times(name, tau, t0, t_end, save_every):
     return tau, t0, t_end, save_every
 
 
-class ParabolicSystem(_DeviceSystem):
+class ParabolicSystem(_PatchErrorNorms, _DeviceSystem):
     """The parabolic problem ``M u' = f - K u`` on the free dofs, ``u = g`` on the dofs of `bcs`, ``u(t0) = u0``, of one patch,
     integrated on the device by a DIRK scheme with constant steps (the reference's ``crank_nicolson``, ``sdirk3``, ``esdirk34``,
     ... on ``RestrictedLinearSystem`` matrices, pyiga/solvers.py:366-473).
@@ -2167,7 +2184,7 @@ class _EigBlockPieces:
         return self._down(d_z, mb, m)
 
 
-class EigenSystem(_EigBlockPieces, _DeviceSystem):
+class EigenSystem(_PatchErrorNorms, _EigBlockPieces, _DeviceSystem):
     """The lowest eigenpairs of ``K x = lam M x`` on the free dofs of one patch (x = 0 on the dofs of `bcs`), by block LOBPCG
     with both matrices, the blocks and the preconditioner in device memory.
 
