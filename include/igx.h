@@ -403,6 +403,18 @@ int igx_patch_placement(const igx_patch *patch, int *tried, float *best_ms, floa
    (No counterpart in the reference: its index type is size_t throughout, pyiga/assemble_tools_cy.pyx:44-49.) */
 int igx_fused_stage_fits(int64_t c0max, int64_t S_mid, int64_t S_last, int64_t G_mid, int64_t G_last);
 
+/* Planning queries of the same stage, host arithmetic only (no device, no patch; no counterpart in the reference).
+   igx_fused_rows_per_tile: rows of the last axis a block of the stage takes for P = degree + 1 (2 .. 6) of the swept and the
+   last axis, the slot set `mask` of the form (bit 4 y + t1: an input array enters the sweep with last-axis type y and
+   mid-axis type t1; 0x0001 mass, 0x135F the full first-order set, 0x1248 2D stiffness) and na = 1 or 2 arrays per slot; -1
+   where no kernel is compiled for the arguments.  The last axis of N dofs is cut into ceil(N / rows) tiles of equal height.
+   igx_fused_chunk_plan: how a launch of npairs * ntiles blocks cuts the mid_rows rows of the swept axis on a chip that holds
+   `slots` blocks at a time: out = { rows per chunk, chunks, main_blocks, tail_k, tail_rows }.  With tail_k = 0 every block
+   walks one of the chunks; with tail_k > 0 (then chunks = 1) the first main_blocks blocks walk the whole axis and each of
+   the others one of tail_k chunks of tail_rows rows, the last one clipped.  IGX_ERR_ARG for arguments out of range. */
+int igx_fused_rows_per_tile(int P, int mask, int na);
+int igx_fused_chunk_plan(int npairs, int ntiles, int mid_rows, int64_t slots, int P, int out[5]);
+
 /* --- multipatch: sum_p X_p A_p X_p^T on the device (pyiga/assemble.py:1103-1389) -------------------------------------------
    X_p is the 0/1 matrix of the local-to-global map l2g[p] (Multipatch.patch_to_global_idx, pyiga/assemble.py:1276-1293).  The
    handle does NOT own the patches: they are read by the calls that take them and may be destroyed afterwards. */

@@ -925,6 +925,15 @@ int fused2_rows_per_tile(int P, int mask, int na)
     }
     return 1;
 }
+// the chunk plan launch_bf2_k gives a launch of npairs x ntiles blocks per chunk of the mid axis on a chip that holds `slots`
+// blocks at a time (host arithmetic: igx_fused_chunk_plan)
+void fused2_chunk_plan(int npairs, int ntiles, int mid_rows, long long slots, int P, int out[5])
+{
+    BFArgs A{};
+    A.npairs = npairs; A.ntiles = ntiles; A.mid_lo = 0; A.mid_hi = mid_rows;
+    bf2_choose_chunks(A, slots, P);
+    out[0] = A.mrows; out[1] = A.nmchunks; out[2] = (int)A.main_blocks; out[3] = A.tail_k; out[4] = A.tail_mrows;
+}
 static void bf_signature(const BFInputs &in, int &ny, int &mask, int &na)
 {
     int ymax = 0;

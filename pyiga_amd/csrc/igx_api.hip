@@ -237,6 +237,20 @@ int igx_fused_stage_fits(int64_t c0max, int64_t S_mid, int64_t S_last, int64_t G
 {
     return igx::fused_offsets_fit(c0max, S_mid, S_last, G_mid, G_last) ? 1 : 0;
 }
+int igx_fused_rows_per_tile(int P, int mask, int na)
+{
+    BFInputs in{};
+    for (int b = 0; b < 16; ++b) in.slot_n[b >> 2][b & 3] = ((mask >> b) & 1) ? na : 0;
+    if (P < 2 || P > 6 || na < 1 || na > 2 || (mask & ~0xffff) || !igx::fused_supported(in)) return -1;
+    return igx::fused2_rows_per_tile(P, mask, na);
+}
+int igx_fused_chunk_plan(int npairs, int ntiles, int mid_rows, int64_t slots, int P, int out[5])
+{
+    if (!out || npairs < 1 || ntiles < 1 || mid_rows < 1 || slots < 1 || P < 2 || P > 6) { set_error("igx_fused_chunk_plan: argument out of range"); return IGX_ERR_ARG; }
+    if ((long long)npairs * ntiles > 0x7fffffffLL / 16) { set_error("igx_fused_chunk_plan: too many blocks"); return IGX_ERR_ARG; }
+    igx::fused2_chunk_plan(npairs, ntiles, mid_rows, slots, P, out);
+    return IGX_OK;
+}
 const char *igx_last_error(void) { return g_err; }
 
 igx_ctx *igx_create(int device_id)

@@ -332,6 +332,10 @@ struct MirrorInputs {
 int fused_supported(const BFInputs &in);
 // 32-bit buffer offsets of k_bf2 / k_mirror2 (fused.hip): row block of an outer row and a K1 slice below 2^31 bytes
 bool fused_offsets_fit(long long c0max, long long S_mid, long long S_last, long long G_mid, long long G_last);
+// host arithmetic of launch_bf (igx_fused_rows_per_tile, igx_fused_chunk_plan): rows of the last axis per tile of k_bf2<P, ., mask, na>;
+// {mrows, nmchunks, main_blocks, tail_k, tail_mrows} of bf2_choose_chunks
+int fused2_rows_per_tile(int P, int mask, int na);
+void fused2_chunk_plan(int npairs, int ntiles, int mid_rows, long long slots, int P, int out[5]);
 int launch_bf(hipStream_t st, const igx_patch *pt, const BFInputs &in, double *d_data);
 int launch_mirror(hipStream_t st, const igx_patch *pt, const MirrorInputs &in, double *d_data);
 // k_bf3 (fused3.hip): the fused stage of the symmetric forms that writes both triangles itself (no mirror pass)

@@ -984,7 +984,7 @@ def test_full_size_c4(iga, oracle, monkeypatch):
         cols = S.indices[S.indptr[r]:S.indptr[r + 1]]
         return np.stack([np.full(3, r), cols[[0, cols.size // 2, -1]]], 1)
     # every row of one line of the last axis (all positions inside all tiles of the fused stage: one whole tile column of
-    # k_bf2), three entries each, and every entry of one interior row
+    # k_bf3, the default; k_bf2 has tests/test_bf2_kernels_gpu.py), three entries each, and every entry of one interior row
     full_row = int(line[57])
     fr_cols = S.indices[S.indptr[full_row]:S.indptr[full_row + 1]]
     pr = np.concatenate([picks(r) for r in sample[::6]] + [picks(r) for r in line] + [np.stack([np.full(fr_cols.size, full_row), fr_cols], 1)])
@@ -1492,15 +1492,19 @@ def test_fullsize_vs_reference_3d(iga, golden, path, monkeypatch):
 @pytest.mark.parametrize('d,p,n', [(2, 1, 9), (2, 2, 33), (2, 3, 70), (2, 4, 37), (2, 5, 21), (3, 1, 7), (3, 2, 13),
                                    (3, 3, 11), (3, 4, 9), (3, 5, 8)])
 def test_fused_equals_unfused(iga, d, p, n, monkeypatch):
-    """The fused sweep + final stage + mirror pass against the round-1 kernels (K2 through HBM) for every degree of
-    the fast path, mass and stiffness: same matrix to rounding, exactly symmetric, every value written."""
+    """The fused sweep + final stage against the round-1 kernels (K2 through HBM) for every degree of the fast path, mass and
+    stiffness: same matrix to rounding, exactly symmetric, every value written.  Since k_bf3 took over the symmetric forms,
+    IGX_PATH=fused runs k_bf3 here in 2D and 3D (it writes both triangles: no mirror pass); the first fused stage k_bf2 and the
+    mirror passes are tested in tests/test_bf2_kernels_gpu.py."""
     monkeypatch.setenv('IGX_DEBUG_POISON', '1')
     kv = iga.bspline.make_knots(p, 0., 1., n)
     kvs = (kv,) * d
     geo = iga.geometry.quarter_annulus() if d == 2 else _geo(iga, 'cylinder')
     for kind in ('mass', 'stiffness'):
         monkeypatch.setenv('IGX_PATH', 'fused')
-        A = iga.assemblers.DevicePatch(kvs, geo).csr(kind, algo='sumfact')
+        patch = iga.assemblers.DevicePatch(kvs, geo)
+        A = patch.csr(kind, algo='sumfact')
+        assert {'fused', 'bf3', 'both'} <= patch.last_path() and 'mirror' not in patch.last_path(), (kind, patch.last_path())
         monkeypatch.setenv('IGX_PATH', 'unfused')
         B = iga.assemblers.DevicePatch(kvs, geo).csr(kind, algo='sumfact')
         assert not np.isnan(A.data).any()
