@@ -119,7 +119,7 @@ class DirkInfo(C.Structure):
 
 IGX_STEPPER_DIRK, IGX_STEPPER_ROSENBROCK = 0, 1
 IGX_STEP_STATE, IGX_STEP_CANDIDATE = 0, 1
-COMB_MAX = 8                    # vectors of one k_dirk_rhs / k_err_norm pass (csrc/solve.hip)
+COMB_MAX = 8                    # vectors of one k_dirk_rhs / k_err_norm pass (csrc/solve_step.hip)
 
 
 class StepInfo(C.Structure):

@@ -1825,7 +1825,7 @@ class NewtonSystem(PatchSystem):
 # Generalized eigenproblems of one patch on the device: block LOBPCG
 ################################################################################
 
-EIG_WIDTHS = (4, 8, 16)                  # the compiled row strides MB of the block kernels (csrc/solve.hip)
+EIG_WIDTHS = (4, 8, 16)                  # the compiled row strides MB of the block kernels (csrc/solve_eig.hip)
 EIG_MAX_BLOCK = EIG_WIDTHS[-1]
 # A projected mass Gram matrix, scaled to a unit diagonal, counts as positive definite when its smallest eigenvalue is above
 # this: below it the columns of [X W P] are dependent to within sqrt(eps) and the projected pencil loses half of its digits.

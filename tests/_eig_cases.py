@@ -1,4 +1,4 @@
-"""The cases that run every instantiation of the block kernels of the eigen-solver (pyiga_amd/csrc/solve.hip), and what decides
+"""The cases that run every instantiation of the block kernels of the eigen-solver (pyiga_amd/csrc/solve_eig.hip), and what decides
 them.
 
 A plain helper module (no GPU needed to import it): tests/test_eig_cpu.py checks on the host that the table reaches every
@@ -43,7 +43,7 @@ def vec_pass_rows():
 
 
 # ---------------------------------------------------------------------------------------------
-# parsing solve.hip
+# parsing the solver source (_solver_cases.read_source)
 def parse_constants(src):
     out = {}
     for name in ('NB_GRAM', 'GR_RC'):

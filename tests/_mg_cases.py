@@ -1,5 +1,5 @@
 """The cases that run every instantiation and every loop of the multigrid kernels (pyiga_amd/csrc/multigrid.hip) and of the DIRK
-kernels of pyiga_amd/csrc/solve.hip (k_vals_axpby, k_dirk_rhs), and what decides them.
+kernels of pyiga_amd/csrc/solve_step.hip (k_vals_axpby, k_dirk_rhs), and what decides them.
 
 A plain helper module (no GPU needed to import it): tests/test_mg_coverage_cpu.py checks on the host that the tables below reach
 what they claim, tests/test_mg_kernels_gpu.py and tests/test_parabolic_gpu.py run them.
@@ -45,7 +45,7 @@ NB_GS_MAX = 8192
 BLOCK_ONE = 1024
 # the (GW, U) instantiations of k_csr_gs and k_csr_gs_block: the widths and batches of k_csr_spmv
 GS_INSTANCES = {(64, 8), (32, 4), (16, 4), (8, 4), (4, 4)}
-# constants of the DIRK kernels of solve.hip and of include/igx.h
+# constants of the DIRK kernels of solve_step.hip and of include/igx.h
 COMB_MAX = 8
 AXPBY_U = 4
 DIRK_MAX_STAGES = 6

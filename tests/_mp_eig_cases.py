@@ -1,5 +1,5 @@
 """The cases that run every instantiation of the CSR block product of the multipatch eigen-solver (k_csr_spmm2,
-pyiga_amd/csrc/solve.hip), and what decides them.
+pyiga_amd/csrc/solve_eig.hip), and what decides them.
 
 A plain helper module (no GPU needed to import it): tests/test_mp_eig_cpu.py checks on the host that the dispatch reaches all
 30 ``(GW, MB, NM)`` and that the table reaches every group width and wraps the grid-stride loop of each;
@@ -41,7 +41,7 @@ def mask_dofs(MP, domain, mask):
 
 
 # ---------------------------------------------------------------------------------------------
-# parsing solve.hip
+# parsing the solver source (_solver_cases.read_source)
 def parse_csr_spmm_dispatch(src):
     """{(GW, MB, NM)}: the instantiations of k_csr_spmm2 the two dispatch functions reach, the {(label, GW)} of the group-width
     switch and the {GW: U expression} the switch writes."""

@@ -21,9 +21,11 @@ import numpy as np
 import scipy.sparse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOLVE_HIP = os.path.join(ROOT, 'pyiga_amd', 'csrc', 'solve.hip')
+# the solver source: the internal header, then the units of the linear solvers, the time stepping and the eigen-solver
+SOLVE_SOURCES = tuple(os.path.join(ROOT, 'pyiga_amd', 'csrc', fn)
+                      for fn in ('solve_internal.h', 'solve.hip', 'solve_step.hip', 'solve_eig.hip'))
 
-# constants of solve.hip (test_solver_coverage_cpu.py reads them from the source and compares)
+# constants of solve_internal.h (test_solver_coverage_cpu.py reads them from the source and compares)
 BLOCK = 256
 NB_VEC = 1024
 NB_SPMV_MAX = 8192
@@ -51,10 +53,14 @@ def vec_pass_rows():
 
 
 # ---------------------------------------------------------------------------------------------
-# parsing solve.hip
+# parsing the solver source
 def read_source():
-    with open(SOLVE_HIP) as f:
-        return f.read()
+    """The text of solve_internal.h and of the three units, joined in this order."""
+    parts = []
+    for path in SOLVE_SOURCES:
+        with open(path) as f:
+            parts.append(f.read())
+    return '\n'.join(parts)
 
 
 def _function_body(src, signature):

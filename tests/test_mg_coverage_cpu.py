@@ -2,7 +2,7 @@
 
 pyiga_amd/csrc/multigrid.hip maps the group width of the sweep kernels to one instantiation of k_csr_gs / k_csr_gs_block per width
 in with_gs_kernel, loops over the rows of a colour with a grid of at most NB_GS_MAX blocks, and k_mg_transfer carries a dof count
-and a band width per axis; solve.hip's k_dirk_rhs holds at most COMB_MAX vectors.  tests/_mg_cases.py restates all of it, and
+and a band width per axis; solve_step.hip's k_dirk_rhs holds at most COMB_MAX vectors.  tests/_mg_cases.py restates all of it, and
 tests/test_mg_kernels_gpu.py and tests/test_parabolic_gpu.py run its cases.  A new width, a changed batch, a dropped case line, a
 larger grid constant, more DIRK stages or a transfer case that became isotropic fails here: the tables must then be extended so that
 every instantiation and every loop still runs under a test that would notice a mistake in it."""
@@ -161,8 +161,7 @@ def test_dense_cases_sizes():
 
 
 def test_dirk_bound_and_full_tableaux():
-    with open(sc.SOLVE_HIP) as f:
-        solve_src = f.read()
+    solve_src = sc.read_source()
     with open(mc.IGX_H) as f:
         header = f.read()
     from pyiga_amd import _lib
