@@ -44,6 +44,8 @@
  *                                         pyiga/solvers.py:430-435, 475-534, 684-939 (a session of attempts)
  *   igx_solver_eig_*                   <- scipy.sparse.linalg.eigsh / lobpcg on the two host matrices of a patch
  *                                         (the lowest eigenpairs of K x = lam M x; block LOBPCG, the pieces on the device)
+ *   igx_solver_take_mass + _eig_*      <- the same on assemble(vector form, layout='blocked') and block_diag([mass] * nc):
+ *                                         elastic vibration, K x = lam (I (x) M) x on a block solver (igx_solver_create_block)
  */
 #ifndef IGX_H
 #define IGX_H
@@ -768,7 +770,13 @@ int  igx_solver_error_ratio_d(igx_solver *solver, int nv, const double *coef, co
    A multipatch solver (igx_solver_create_multipatch) that has been given a mass matrix (igx_solver_set_mass_d) is accepted as
    well: K is the multipatch's summed values (restarted sums: IGX_ERR_ARG, as for every call on such a
    solver), M the solver's own array, the block product k_csr_spmm2 over the global CSR pattern, nrows_total the global dofs.
-   Without a mass matrix: IGX_ERR_ARG. */
+   Without a mass matrix: IGX_ERR_ARG.
+   A block solver (igx_solver_create_block with symmetric != 0) whose diagonal blocks are all present and that has taken a mass
+   matrix (igx_solver_take_mass) is accepted too: the vector-valued eigenproblem K x = lam (I (x) M) x, K
+   the ncomp x ncomp blocks, M one scalar matrix for every component.  Blocks then have ncomp * nrows_total rows, component-major
+   (entry (q N + J, j) at (q N + J) mb + j); the block product is k_block_spmm2, every other entry works on the longer blocks
+   unchanged.  A block solver that is not symmetric: the message of every other solver; a missing diagonal block or mass:
+   IGX_ERR_ARG. */
 enum { IGX_EIG_X = 0, IGX_EIG_KX, IGX_EIG_MX, IGX_EIG_W, IGX_EIG_KW, IGX_EIG_MW, IGX_EIG_P, IGX_EIG_KP, IGX_EIG_MP, IGX_EIG_R,
        IGX_EIG_NBLOCKS };
 typedef struct {
@@ -788,11 +796,18 @@ typedef struct {
    igx_dev_alloc on the solver's context.  The solver takes ownership: it frees d_M when it is destroyed, and a second call frees
    the array of the first.  A patch solver: IGX_ERR_UNSUPPORTED. */
 int  igx_solver_set_mass_d(igx_solver *solver, double *d_M);
+/* The mass matrix of a block solver's eigenproblem: the patch's current values (IGX_MASS, or IGX_FORM for a density-weighted
+   mass) change hands as a block does (igx_solver_take_block); the solver frees them in igx_solver_destroy.  A second call, a
+   solver that is not a block solver, or a patch without such values: IGX_ERR_ARG. */
+int  igx_solver_take_mass(igx_solver *solver);
 /* The preconditioner of igx_solver_eig_precond and igx_solver_eig_precond_d: IGX_PRECOND_NONE (the masked copy),
    IGX_PRECOND_JACOBI (the diagonal of K) or IGX_PRECOND_KRON with factors as igx_solver_set_precond takes them (the free dofs must
    be exactly the box).  Independent of igx_solver_set_precond.  A multipatch solver takes NONE, JACOBI or IGX_PRECOND_MG: one
    V-cycle of the hierarchy of igx_solver_set_mg_* per column (not set up: IGX_ERR_ARG; the _d form cycles all mb columns, a
-   session the first m); IGX_PRECOND_KRON and IGX_PRECOND_SCHWARZ: IGX_ERR_UNSUPPORTED. */
+   session the first m); IGX_PRECOND_KRON and IGX_PRECOND_SCHWARZ: IGX_ERR_UNSUPPORTED.  A block solver: JACOBI is the diagonal
+   of every diagonal block; KRON takes NULL box arguments and applies the factors of igx_solver_set_block_kron per component, on
+   that component's box with all mb columns at once (a component without factors, or box arguments: IGX_ERR_ARG; factors set
+   again later: select KRON again). */
 int  igx_solver_eig_set_precond(igx_solver *solver, int precond, const int32_t *box_lo, const int32_t *box_hi,
                                 const double *const *U, const double *const *lam, int lam_mode);
 /* Starts a session with blocks of m columns (1 <= m <= 16): X0 (host, nrows_total x m, row-major) goes into IGX_EIG_X with its

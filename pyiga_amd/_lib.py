@@ -269,6 +269,7 @@ SYMBOLS = [
     ('igx_solver_step_state', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_solver_error_ratio_d', C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, _dp]),
     ('igx_solver_set_mass_d', C.c_int, [C.c_void_p, C.c_void_p]),
+    ('igx_solver_take_mass', C.c_int, [C.c_void_p]),
     ('igx_solver_eig_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
     ('igx_solver_eig_begin', C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
     ('igx_solver_eig_products', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

@@ -99,12 +99,6 @@ __global__ void __launch_bounds__(BLOCK) k_spmv(const Geom g, const double *__re
     }
 }
 
-// the NC x NC blocks of a vector-valued form: v[p * NC + q] holds block (p, q) (test component p, trial component q) in the
-// patch's structured layout, or is null (a block that was never assembled: zero)
-struct BlockVals {
-    const double *v[9];
-};
-
 // The contract of k_spmv over the block matrix [A_pq].  Vectors have NC * N entries, component-major
 // (x_q[J] = x[q N + J]): y[p N + I] = free[p N + I] ? (b ? b[p N + I] : 0) + s * sum_q (A_pq x_q)[I] : 0, part[block] = sum of
 // pd . y over the NC outputs of the rows of the block (optional).  All blocks share the patch's pattern: one group of GW lanes per
@@ -1504,6 +1498,28 @@ int igx_solver_set_block_kron(igx_solver *s, int comp, const int32_t *box_lo, co
     if (nbox > s->wlen)                            // the two work buffers fit the largest box of any component
         if (int rc = alloc_fastdiag_work(s, nbox)) return rc;
     s->block.bkron[comp] = box_fastdiag(s, base, box_lo, nb, s->block.d_bkron[comp], mode);
+    for (int k = 0; k < 3; ++k) { s->block.klo[comp][k] = k < s->dim ? box_lo[k] : 0; s->block.knb[comp][k] = nb[k]; }
+    s->block.kmode[comp] = mode;
+    if (s->eig) eig_drop_block_kron(s);            // (the eigen pieces sized their work buffers for the previous boxes)
+    return IGX_OK;
+}
+
+int igx_solver_take_mass(igx_solver *s)
+{
+    const char *what = "igx_solver_take_mass";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
+    if (s->block.mass) { set_error("%s: the mass matrix was taken already", what); return IGX_ERR_ARG; }
+    igx_patch *pt = s->pt;
+    if ((pt->values_kind != IGX_MASS && pt->values_kind != IGX_FORM) || !pt->d_data) {
+        set_error("%s: the patch holds no IGX_MASS or IGX_FORM values: assemble them first (igx_assemble, data_out may be NULL)", what);
+        return IGX_ERR_ARG;
+    }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    IGX_HIP(hipStreamSynchronize(pt->ctx->stream));
+    s->block.mass = pt->d_data;                     // the buffer changes hands, as a block does
+    pt->d_data = nullptr;
+    pt->values_kind = -1;
     return IGX_OK;
 }
 

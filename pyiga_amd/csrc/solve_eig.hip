@@ -4,10 +4,12 @@
 //                (DESIGN.md section 22).
 //   k_csr_spmm2  the block product of the multipatch eigen-solver over the general CSR pattern: K and M times a block of
 //                interleaved columns in one pass (k_spmm2 is its structured twin of section 22).
+//   k_block_spmm2  the block product of a block solver's vector-valued form: the NC x NC blocks and one scalar M times a block of
+//                interleaved columns of NC N rows in one launch.
 //   k_gram, k_block_comb, k_resid, k_block_scale: Gram matrices, block combinations, residuals with their column norms and the
 //                batched Jacobi scaling, all in a fixed summation order.
-// Host side: one dispatch per block product (with_spmm2_kernel, with_csr_spmm2_kernel) names the instantiations, for the launch
-// and the occupancy query alike.  The solver structure, the row layout (Geom, row_hdr) and the fast-diagonalization and
+// Host side: one dispatch per block product (with_spmm2_kernel, with_csr_spmm2_kernel, with_block_spmm2_kernel) names the
+// instantiations, for the launch and the occupancy query alike.  The solver structure, the row layout (Geom, row_hdr) and the fast-diagonalization and
 // multigrid preconditioners come from solve.hip and multigrid.hip through solve_internal.h.
 #include "solve_internal.h"
 
@@ -32,6 +34,7 @@ struct EigState {
     double *d_fac = nullptr, *d_W = nullptr;  // Kronecker: packed factors, two work buffers of nbox * EIG_MB_MAX
     int precond = IGX_PRECOND_NONE;
     int box_lo[3] = {}, box_nb[3] = {1, 1, 1}, lam_mode = 0;
+    long long block_wl = 0;                   // a block solver: the length of one work buffer (its largest component box * EIG_MB_MAX)
     int nb_spmm[3][2] = {};                   // resident blocks of the block product per width and matrix count (0: not asked yet)
     hipEvent_t ev[2] = {};
     bool have_ev = false;
@@ -48,6 +51,11 @@ void eig_free(igx_solver *s)
         delete e;
     }
     (void)hipFree(s->d_mass);
+}
+
+void eig_drop_block_kron(igx_solver *s)
+{
+    if (s->eig && s->eig->precond == IGX_PRECOND_KRON) s->eig->precond = IGX_PRECOND_NONE;
 }
 
 } // namespace igx
@@ -192,6 +200,156 @@ decltype(auto) with_spmm2_kernel(int gw, int mb, int nm, F &&f)
     case 8: return with_spmm2_gw<8, 1>(gw, f);
     default: return with_spmm2_gw<16, 1>(gw, f);
     }
+}
+
+// block (p, q) of the NC x NC blocks by a chain of uniform selects: p and q are loop variables, and an index into the by-value
+// argument would put the pointers into scratch
+template <int NC>
+__device__ __forceinline__ const double *block_ptr(const BlockVals &A, int p, int q)
+{
+    const double *r = A.v[0];
+#pragma unroll
+    for (int k = 1; k < NC * NC; ++k) r = (p * NC + q == k) ? A.v[k] : r;
+    return r;
+}
+
+// One walk of a lane through its entries of the row (k_spmm2's): acc[0 .. MB) += v0 . x, and (NW == 2) acc[MB .. 2 MB) += v1 . x,
+// for the values v0 (and v1) of the row at `row` and the x-entries of the trial component that starts at xq.  A null v0 or v1
+// (uniform over the grid) is not read and counts as zero: with NW == 2 the walks q != p add zeros to the sums of M.  That costs
+// multiply-adds, of which the kernel has plenty to spare, and keeps one loop for every walk: with a loop of its own per case the
+// sums did not stay in the same registers across them, and the kernel took 256 VGPRs at MB = 16.
+template <int GW, int MB, int U, int NW>
+__device__ __forceinline__ void block_row_walk(const double *__restrict__ v0, const double *__restrict__ v1, long long row, int len,
+                                               const double *__restrict__ xq, int lane, int c, int bb, int a, int c1, int c2,
+                                               int N12, int N2, double *acc)
+{
+    constexpr int H = MB / 2;
+    const dbl2 zero2 = {0.0, 0.0};
+    const int dc = GW % c2, db = (GW / c2) % c1, da = GW / (c1 * c2);
+    for (int k0 = lane; k0 < len; k0 += U * GW) {
+        double v[U][NW];
+        dbl2 xv[U][H];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const bool in = k0 + u * GW < len;
+            v[u][0] = (in && v0) ? __builtin_nontemporal_load(v0 + row + k0 + u * GW) : 0.0;
+            if (NW == 2) v[u][NW - 1] = (in && v1) ? __builtin_nontemporal_load(v1 + row + k0 + u * GW) : 0.0;
+            const dbl2 *xr = reinterpret_cast<const dbl2 *>(xq +(long long)(a * N12 + bb * N2 + c) * MB);
+#pragma unroll
+            for (int j = 0; j < H; ++j) xv[u][j] = in ? xr[j] : zero2;
+            c += dc; bb += db; a += da;
+            if (c >= c2) { c -= c2; ++bb; }
+            if (bb >= c1) { bb -= c1; ++a; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int w = 0; w < NW; ++w)
+#pragma unroll
+                for (int j = 0; j < H; ++j) {
+                    acc[w * MB + 2 * j] += v[u][w] * xv[u][j].x;
+                    acc[w * MB + 2 * j + 1] += v[u][w] * xv[u][j].y;
+                }
+    }
+}
+
+// The block product of a vector-valued form: blocks of NC N rows, component-major (entry (q N + J, j) at
+// (q N + J) MB + j), and MB interleaved columns.
+//   yK[(p N + I) MB + j] = free[p N + I] ? sum_q sum_J A_pq[I, J] x[(q N + J) MB + j] : 0
+//   yM[(p N + I) MB + j] = free[p N + I] ?       sum_J M[I, J]   x[(p N + J) MB + j] : 0     (one scalar M for every component)
+// NM == 2: both; NM == 1: K alone (vM null) or M alone (vM given; A is not read), written to yK.  One group of GW lanes serves a
+// scalar row I (k_spmm2's row-to-group map, header one row ahead and lane walk) and keeps the NM MB sums of one test component p
+// at a time: it walks the row once per trial component q whose block is present, and the M value joins the walk q == p, so every
+// value of A_pq is read once (non-temporal), M at most NC times, and x_q comes from L2 again for every p.  Absent blocks (uniform
+// over the grid) and the rows of fixed components (uniform over the group) are not read.  x must vanish on the fixed dofs.  The
+// order of the sums is fixed (q ascending, then the walk, then ReduceScatter); no atomics.
+template <int GW, int MB, int U, int NC, int NM>
+__global__ void __launch_bounds__(BLOCK) k_block_spmm2(const Geom g, const BlockVals A, const double *__restrict__ vM,
+                                                       const uint8_t *__restrict__ freem, const double *__restrict__ x,
+                                                       double *__restrict__ yK, double *__restrict__ yM)
+{
+    constexpr int T = NM * MB;
+    const int lane = threadIdx.x % GW;
+    const long long ngroups = (long long)gridDim.x * (BLOCK / GW);
+    const long long N = g.nrows;
+    const int N1 = g.N[1], N2 = g.N[2];
+    const int N12 = N1 * N2;
+    const bool m_only = NM == 1 && vM != nullptr;
+    long long I = (long long)blockIdx.x * (BLOCK / GW) + threadIdx.x / GW;
+    RowHdr h{};
+    if (I < N) h = row_hdr(g, freem, I);
+    for (; I < N; I += ngroups) {
+        const RowHdr cur = h;
+        if (I + ngroups < N) h = row_hdr(g, freem, I + ngroups);
+        const int c0 = cur.c0 - cur.l0, c1 = cur.c1 - cur.l1, c2 = cur.c2 - cur.l2;
+        const int len = c0 * c1 * c2;
+        const long long row = igx_rowptr3(&cur.r0, &cur.r1, &cur.r2, g.S1, g.S2, c0, c1, 0, 0, 0);
+        const long long xbase = (long long)(cur.l0 * N1 + cur.l1) * N2 + cur.l2;
+        const int c = lane % c2, bb = (lane / c2) % c1, a = lane / (c1 * c2);
+#pragma unroll 1
+        for (int p = 0; p < NC; ++p) {
+            const long long o = (p * N + I) * MB;
+            if (!freem[p * N + I]) {                     // (uniform over the group)
+                for (int j = lane; j < MB; j += GW) {
+                    yK[o + j] = 0.0;
+                    if (NM == 2) yM[o + j] = 0.0;
+                }
+                continue;
+            }
+            double acc[T];
+#pragma unroll
+            for (int i = 0; i < T; ++i) acc[i] = 0.0;
+#pragma unroll 1
+            for (int q = 0; q < NC; ++q) {
+                const double *v0 = m_only ? (q == p ? vM : nullptr) : block_ptr<NC>(A, p, q);
+                const double *v1 = (NM == 2 && q == p) ? vM : nullptr;
+                if (!v0 && !v1) continue;                // (an absent block: uniform over the grid)
+                block_row_walk<GW, MB, U, NM>(v0, v1, row, len, x + (q * N + xbase) * MB, lane, c, bb, a, c1, c2, N12, N2, acc);
+            }
+            int base = 0;
+            ReduceScatter<GW, GW / 2, T>::run(acc, lane, base);
+            constexpr int TF = T >= GW ? T / GW : 1;     // sums a writing lane holds: the original indices base .. base + TF - 1
+            if (T >= GW || (lane & (GW / T - 1)) == 0) {
+#pragma unroll
+                for (int i = 0; i < TF; ++i) {
+                    const int ob = base + i;             // (matrix, j) = (ob / MB, ob % MB); TF divides MB: one matrix per lane
+                    double *y = (NM == 2 && ob >= MB) ? yM : yK;
+                    y[o + (ob % MB)] = acc[i];
+                }
+            }
+        }
+    }
+}
+
+// f(the instantiation of the vector block product at group width gw) for a row stride MB, NM matrices and NC components: with
+// with_block_spmm2_kernel the only place that names one (U as k_spmm2's)
+template <int MB, int NM, int NC, class F>
+decltype(auto) with_block_spmm2_gw(int gw, F &&f)
+{
+    switch (gw) {
+    case 64: return f(k_block_spmm2<64, MB, 32 / MB, NC, NM>);
+    case 32: return f(k_block_spmm2<32, MB, 16 / MB, NC, NM>);
+    case 16: return f(k_block_spmm2<16, MB, 16 / MB, NC, NM>);
+    case 8: return f(k_block_spmm2<8, MB, 16 / MB, NC, NM>);
+    default: return f(k_block_spmm2<4, MB, 16 / MB, NC, NM>);
+    }
+}
+
+template <int NM, int NC, class F>
+decltype(auto) with_block_spmm2_mb(int gw, int mb, F &&f)
+{
+    switch (mb) {
+    case 4: return with_block_spmm2_gw<4, NM, NC>(gw, f);
+    case 8: return with_block_spmm2_gw<8, NM, NC>(gw, f);
+    default: return with_block_spmm2_gw<16, NM, NC>(gw, f);
+    }
+}
+
+template <class F>
+decltype(auto) with_block_spmm2_kernel(int gw, int mb, int nm, int nc, F &&f)
+{
+    if (nc == 3) return nm == 2 ? with_block_spmm2_mb<2, 3>(gw, mb, f) : with_block_spmm2_mb<1, 3>(gw, mb, f);
+    return nm == 2 ? with_block_spmm2_mb<2, 2>(gw, mb, f) : with_block_spmm2_mb<1, 2>(gw, mb, f);
 }
 
 // The block product over the general CSR pattern of a multipatch: k_spmm2's contract and inner structure,
@@ -499,6 +657,11 @@ int eig_check(const igx_solver *s, const char *what, bool values)
         if (!s->d_mass) { set_error("%s: a multipatch solver needs its mass matrix first (igx_solver_set_mass_d)", what); return IGX_ERR_ARG; }
         return values ? check_values(s, what) : IGX_OK;
     }
+    if (s->ncomp > 1 && s->symmetric) {      // a block solver: K its blocks (every diagonal one present), M the mass it took
+        if (int rc = check_values(s, what)) return rc;
+        if (!s->block.mass) { set_error("%s: a block solver needs its mass matrix first (igx_solver_take_mass)", what); return IGX_ERR_ARG; }
+        return IGX_OK;
+    }
     if (!s->parabolic || !s->symmetric || s->ncomp != 1) {
         set_error("%s: needs a symmetric parabolic solver (igx_solver_create_parabolic) or a multipatch solver with a mass matrix "
                   "(igx_solver_set_mass_d)", what);
@@ -579,12 +742,23 @@ int eig_products(hipStream_t st, igx_solver *s, EigState *e, int mb, const doubl
     if (!nb) {
         int per_cu = 0;
         auto occupancy = [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0); };
-        const hipError_t eo = s->mp ? with_csr_spmm2_kernel(s->gw, mb, nm, occupancy) : with_spmm2_kernel(s->gw, mb, nm, occupancy);
+        const hipError_t eo = s->mp          ? with_csr_spmm2_kernel(s->gw, mb, nm, occupancy)
+                              : s->ncomp > 1 ? with_block_spmm2_kernel(s->gw, mb, nm, s->ncomp, occupancy)
+                                             : with_spmm2_kernel(s->gw, mb, nm, occupancy);
         if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
         nb = (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, s->ctx->ncu));
     }
-    const long long groups = BLOCK / s->gw;
-    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(nb, (s->n + groups - 1) / groups));
+    const long long groups = BLOCK / s->gw, rows = s->n / s->ncomp;      // (a block solver: one group per scalar row)
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(nb, (rows + groups - 1) / groups));
+    if (s->ncomp > 1) {
+        BlockVals A{};
+        if (yK)
+            for (int k = 0; k < s->ncomp * s->ncomp; ++k) A.v[k] = s->block.blk[k];
+        const double *vM = yM ? s->block.mass : nullptr;
+        with_block_spmm2_kernel(s->gw, mb, nm, s->ncomp, [&](auto k) { k<<<grid, BLOCK, 0, st>>>(s->g, A, vM, s->d_mask, x, yK ? yK : yM, nm == 2 ? yM : nullptr); });
+        IGX_HIP(hipGetLastError());
+        return IGX_OK;
+    }
     if (const igx_multipatch *m = s->mp) {
         const double *vK = m->d_vals, *vM = s->d_mass;
         if (nm == 2) with_csr_spmm2_kernel(s->gw, mb, 2, [&](auto k) { k<<<grid, BLOCK, 0, st>>>(s->n, m->d_indptr, m->d_indices, vK, vM, s->d_mask, x, yK, yM); });
@@ -676,6 +850,16 @@ int eig_precond(hipStream_t st, igx_solver *s, EigState *e, int mb, int m, const
         }
         return IGX_OK;
     }
+    if (e->precond == IGX_PRECOND_KRON && s->ncomp > 1) {        // diag(P_0, .., P_{nc-1}): each component's box, batch = mb
+        double *W[2] = {e->d_W, e->d_W + e->block_wl};
+        IGX_HIP(hipMemsetAsync(z, 0, (size_t)s->n * mb * sizeof(double), st));
+        for (int c = 0; c < s->ncomp; ++c) {
+            const BlockState &B = s->block;
+            const FastDiag F = box_fastdiag(s, c * s->g.nrows, B.klo[c], B.knb[c], B.d_bkron[c], B.kmode[c], mb);
+            if (int rc = apply_fastdiag(st, F, r, z, W)) return rc;
+        }
+        return IGX_OK;
+    }
     if (e->precond == IGX_PRECOND_KRON) {
         const FastDiag F = box_fastdiag(s, 0, e->box_lo, e->box_nb, e->d_fac, e->lam_mode, mb);
         const long long wl = (long long)e->box_nb[0] * e->box_nb[1] * e->box_nb[2] * EIG_MB_MAX;
@@ -717,7 +901,9 @@ int igx_solver_eig_set_precond(igx_solver *s, int precond, const int32_t *box_lo
     if (precond == IGX_PRECOND_NONE) { e->precond = precond; return IGX_OK; }
     if (precond == IGX_PRECOND_JACOBI) {
         if (!e->d_dinv) IGX_HIP(hipMalloc((void **)&e->d_dinv, (size_t)s->n * sizeof(double)));
-        jacobi_diagonal(st, s, s->mp ? s->mp->d_vals : s->par.pv[IGX_ROLE_OPERATOR], e->d_dinv);
+        if (s->ncomp > 1) {                   // component c: the diagonal of block (c, c) at offset c g.nrows
+            for (int c = 0; c < s->ncomp; ++c) jacobi_diagonal(st, s, s->block.blk[c * s->ncomp + c], e->d_dinv + c * s->g.nrows, c);
+        } else jacobi_diagonal(st, s, s->mp ? s->mp->d_vals : s->par.pv[IGX_ROLE_OPERATOR], e->d_dinv);
         IGX_HIP(hipGetLastError());
         IGX_HIP(hipStreamSynchronize(st));
         e->precond = precond;
@@ -734,6 +920,21 @@ int igx_solver_eig_set_precond(igx_solver *s, int precond, const int32_t *box_lo
         return IGX_OK;
     }
     if (precond != IGX_PRECOND_KRON) { set_error("%s: unknown preconditioner %d", what, precond); return IGX_ERR_ARG; }
+    if (s->ncomp > 1) {                       // a block solver: the factors of every component, set by igx_solver_set_block_kron
+        if (box_lo || box_hi || U || lam) { set_error("%s: a block solver takes its Kronecker factors per component (igx_solver_set_block_kron): pass NULL here", what); return IGX_ERR_ARG; }
+        long long nbox = 1;
+        for (int c = 0; c < s->ncomp; ++c) {
+            if (!s->block.d_bkron[c]) { set_error("%s: set the Kronecker factors of component %d first (igx_solver_set_block_kron)", what, c); return IGX_ERR_ARG; }
+            nbox = std::max(nbox, (long long)s->block.knb[c][0] * s->block.knb[c][1] * s->block.knb[c][2]);
+        }
+        e->precond = IGX_PRECOND_NONE;
+        IGX_HIP(hipStreamSynchronize(st));
+        (void)hipFree(e->d_W); e->d_W = nullptr;
+        e->block_wl = nbox * EIG_MB_MAX;
+        IGX_HIP(hipMalloc((void **)&e->d_W, 2 * (size_t)e->block_wl * sizeof(double)));
+        e->precond = IGX_PRECOND_KRON;
+        return IGX_OK;
+    }
     int nb[3];
     if (int rc = box_fastdiag_setup(s, 0, box_lo, box_hi, U, lam, lam_mode, what, &e->precond, e->d_fac, nb)) return rc;
     (void)hipFree(e->d_W); e->d_W = nullptr;

@@ -57,6 +57,12 @@ __device__ __forceinline__ RowHdr row_hdr(const Geom &g, const uint8_t *freem, l
     return h;
 }
 
+// the NC x NC blocks of a vector-valued form: v[p * NC + q] holds block (p, q) (test component p, trial component q) in the
+// patch's structured layout, or is null (a block that was never assembled: zero)
+struct BlockVals {
+    const double *v[9];
+};
+
 // the contractions of a whole Kronecker product: x (strided) -> work -> ... -> y (strided)
 struct KronPlan {
     int dim;
@@ -121,10 +127,13 @@ struct BlockState {
     double *blk[9] = {};                      // block (p, q) at p * ncomp + q, taken from the patch (owned), or null
     FastDiag bkron[3] = {};                   // per component: the fast-diagonalization inverse on its free box (in d_bkron[c])
     double *d_bkron[3] = {};
+    int klo[3][3] = {}, knb[3][3] = {}, kmode[3] = {};   // per component: its box and lam_mode (the eigen-solver's batched plans)
+    double *mass = nullptr;                   // the scalar mass matrix of the eigen-solver (igx_solver_take_mass), owned, or null
     void release()
     {
         for (double *v : blk) (void)hipFree(v);
         for (double *v : d_bkron) (void)hipFree(v);
+        (void)hipFree(mass);
     }
 };
 
@@ -254,5 +263,6 @@ int sum_partials(hipStream_t st, igx_solver *s, unsigned nb, double *sum);
 
 // ---- solve_eig.hip
 void eig_free(igx_solver *s);                 // the eigen-solver's state and the mass matrix of a multipatch solver
+void eig_drop_block_kron(igx_solver *s);      // a block solver's Kronecker factors were replaced: the eigen pieces select them again
 
 } // namespace igx

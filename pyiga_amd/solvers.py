@@ -32,6 +32,11 @@ only the saved states come down.  ``dirk_tableau(name)`` gives the tableaux of t
 (``embedded_tableau``) or of the Rosenbrock methods ``ros3p``, ``ros3pw``, ``rowdaind2``, ``rodasp``, ``rosi2p1``
 (``rosenbrock_tableau``; pyiga/solvers.py:475-534, 684-939): the error estimate, its norm and the mass solve run on the device,
 the accept/reject controller on the host.
+
+``EigenSystem(kvs, geo, bcs)``, ``MultipatchEigenSystem(MP, bcs)`` and ``VectorEigenSystem(problem, kvs, bcs, bfuns=[('u', nc),
+('v', nc)], geo=geo)``: the lowest eigenpairs of ``K x = lam M x`` on one patch, on a multipatch, and for a vector-valued form
+(elastic vibration, ``M`` the same mass matrix for every component), by block LOBPCG (``lobpcg_loop``) with the matrices, the
+blocks and the preconditioner on the device.
 """
 import ctypes as C
 import math
@@ -493,7 +498,63 @@ def symmetric_block_tables(table, rtol=1e-13):
     return True
 
 
-class VectorFormSystem(_DeviceSystem):
+class _VectorBlocks:
+    """What the device systems of a vector-valued form share (``VectorFormSystem``, ``VectorEigenSystem``): the hand-over of the
+    nc x nc scalar blocks to a block solver, the free box of every component and the block-diagonal Kronecker factors.  They
+    supply ``kvs``, ``ndofs``, ``N``, ``ncomp``, ``patch``, ``handle`` and ``bc_indices``."""
+
+    def _take_blocks(self, table):
+        """Every block of `table` that is not absent, assembled (IGX_FORM) and handed to the solver; ``present[p][q]``."""
+        from .form_assemblers import _full_table
+        lib = _lib.load()
+        nc, d = self.ncomp, len(self.kvs)
+        self.present = [[False] * nc for _ in range(nc)]
+        for p in range(nc):
+            for q in range(nc):
+                tab = table[p][q]
+                if all(e is None for row in tab for e in row):
+                    continue                      # (an absent block: zero, never read)
+                self.patch.set_form(_full_table(tab, d))
+                self.patch.assemble('form', to_host=False)
+                _lib.check(lib.igx_solver_take_block(self.handle, p, q), 'igx_solver_take_block')
+                self.present[p][q] = True
+
+    def _component_boxes(self):
+        idx = self.bc_indices
+        self.boxes = [dirichlet_box(self.ndofs, idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N)
+                      for c in range(self.ncomp)]
+
+    @property
+    def default_precond(self):
+        return 'kron' if all(b is not None for b in self.boxes) else 'jacobi'
+
+    def kron_factors(self):
+        """Per component ``(lo, hi, U, lam, mode)``: the fast diagonalization of the parametric Laplacian on its free box.  A
+        component without a wholly fixed side gets ``sigma / d`` added to every ``lam_k`` (``sigma = min_k lam_k[1]``, as a
+        floating Schwarz patch): the inverse stays symmetric positive definite."""
+        out = []
+        for c, box in enumerate(self.boxes):
+            if box is None:
+                raise ValueError("precond='kron' needs the Dirichlet dofs of every component to be a union of whole sides of the "
+                                 "patch (component %d is not)" % c)
+            lo, hi = box
+            U, lam, mode = fastdiag_factors(self.kvs, lo, hi, True)
+            floating = all(a == 0 for a in lo) and all(b == kv.numdofs for b, kv in zip(hi, self.kvs))
+            if floating and all(len(l) > 1 for l in lam):
+                sigma = min(l[1] for l in lam)
+                lam = [l + sigma / len(lam) for l in lam]
+            out.append((lo, hi, U, lam, mode))
+        return out
+
+    def _set_block_kron(self, h):
+        """The factors of every component on the device (``igx_solver_set_block_kron``)."""
+        lib = _lib.load()
+        for c, (lo, hi, U, lam, mode) in enumerate(self.kron_factors()):
+            lo_, hi_, Up, Lp = _box_args(lo, hi, U, lam)
+            _lib.check(lib.igx_solver_set_block_kron(h, c, lo_, hi_, Up, Lp, mode), 'igx_solver_set_block_kron')
+
+
+class VectorFormSystem(_VectorBlocks, _DeviceSystem):
     """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, for a vector-valued form (``bfuns=[('u', nc),
     ('v', nc)]``, nc = 2 or 3: linear elasticity, grad-div, ...) on one patch, assembled and solved on the device.
 
@@ -509,7 +570,7 @@ class VectorFormSystem(_DeviceSystem):
 
     def __init__(self, problem, kvs, rhs, bcs=None, args=None, bfuns=None, method='auto', **kwargs):
         from . import assemble
-        from .form_assemblers import FormAssembler, _full_table
+        from .form_assemblers import FormAssembler
         if method != 'auto':
             _check_method(method)
         args = dict(args or {})
@@ -540,50 +601,12 @@ class VectorFormSystem(_DeviceSystem):
         self._ctx = self.patch.ctx
         initial = 'cg' if self.symmetric else 'bicgstab'
         self._attach('igx_solver_create_block', (self.patch.handle, nc, 1 if self.symmetric else 0), bcs, method, initial)
-        lib = _lib.load()
-        d = len(self.kvs)
-        self.present = [[False] * nc for _ in range(nc)]
-        for p in range(nc):
-            for q in range(nc):
-                tab = table[p][q]
-                if all(e is None for row in tab for e in row):
-                    continue                      # (an absent block: zero, never read)
-                self.patch.set_form(_full_table(tab, d))
-                self.patch.assemble('form', to_host=False)
-                _lib.check(lib.igx_solver_take_block(self.handle, p, q), 'igx_solver_take_block')
-                self.present[p][q] = True
-        idx = self.bc_indices
-        self.boxes = [dirichlet_box(self.ndofs, idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N)
-                      for c in range(nc)]
-
-    @property
-    def default_precond(self):
-        return 'kron' if all(b is not None for b in self.boxes) else 'jacobi'
-
-    def kron_factors(self):
-        """Per component ``(lo, hi, U, lam, mode)``: the fast diagonalization of the parametric Laplacian on its free box.  A
-        component without a wholly fixed side gets ``sigma / d`` added to every ``lam_k`` (``sigma = min_k lam_k[1]``, as a
-        floating Schwarz patch): the inverse stays symmetric positive definite."""
-        out = []
-        for c, box in enumerate(self.boxes):
-            if box is None:
-                raise ValueError("precond='kron' needs the Dirichlet dofs of every component to be a union of whole sides of the "
-                                 "patch (component %d is not)" % c)
-            lo, hi = box
-            U, lam, mode = fastdiag_factors(self.kvs, lo, hi, True)
-            floating = all(a == 0 for a in lo) and all(b == kv.numdofs for b, kv in zip(hi, self.kvs))
-            if floating and all(len(l) > 1 for l in lam):
-                sigma = min(l[1] for l in lam)
-                lam = [l + sigma / len(lam) for l in lam]
-            out.append((lo, hi, U, lam, mode))
-        return out
+        self._take_blocks(table)
+        self._component_boxes()
 
     def _set_factors(self, h):
-        lib = _lib.load()
-        for c, (lo, hi, U, lam, mode) in enumerate(self.kron_factors()):
-            lo_, hi_, Up, Lp = _box_args(lo, hi, U, lam)
-            _lib.check(lib.igx_solver_set_block_kron(h, c, lo_, hi_, Up, Lp, mode), 'igx_solver_set_block_kron')
-        _lib.check(lib.igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, None, None, None, None, 0), 'igx_solver_set_precond')
+        self._set_block_kron(h)
+        _lib.check(_lib.load().igx_solver_set_precond(h, _lib.IGX_PRECOND_KRON, None, None, None, None, 0), 'igx_solver_set_precond')
         self._factors_set = True
 
     def solve(self, tol=1e-8, maxiter=1000, precond='auto', x0=None, check_every=1, timed=False):
@@ -2083,9 +2106,52 @@ def _check_eig_args(k, block, n_free):
         raise ValueError('a block of %d columns needs at least %d free dofs, the problem has %d' % (block, 3 * block, n_free))
 
 
+def _eig_fixed_dofs(bcs, n):
+    """The sorted unique fixed dofs of `bcs` (``(indices, values)`` or just the indices) among `n` dofs."""
+    if bcs is None:
+        idx = np.zeros(0, dtype=np.int64)
+    elif isinstance(bcs, tuple) and len(bcs) == 2 and np.ndim(bcs[0]) >= 1:
+        idx = np.asarray(bcs[0], dtype=np.int64).ravel()
+    else:
+        idx = np.asarray(bcs, dtype=np.int64).ravel()
+    idx = np.unique(idx)
+    if idx.size and (idx[0] < 0 or idx[-1] >= n):
+        raise ValueError('fixed dof out of range')
+    return idx
+
+
+def _patch_eig_solve(S, k, tol, maxiter, precond, block, X0, seed, timed):
+    """``solve`` of the one-patch eigen-systems (``EigenSystem``, ``VectorEigenSystem``): ``lobpcg_loop`` on the device session
+    of `S`, which supplies ``n``, ``n_free``, ``_live()`` and ``set_precond``."""
+    k = int(k)
+    m = default_eig_block(max(k, 1)) if block is None else int(block)
+    _check_eig_args(k, m, S.n_free)
+    if X0 is None:
+        X0 = np.random.default_rng(seed).standard_normal((S.n, m))
+    else:
+        X0 = np.asarray(X0, dtype=np.float64)
+        if X0.shape != (S.n, m):
+            raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (S.n, m)))
+    h = S._live()
+    key = S.set_precond(precond)
+    ops = _DeviceEigOps(h, S.n, m, X0, timed)
+    try:
+        lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
+        U = ops.download('X', k)
+        dev = ops.info()
+    finally:
+        ops.end()
+    info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
+    if timed:
+        info.update({name: dev[name] for name in dev if name.endswith('_ms')})
+    S.info = info
+    return lam[:k].copy(), U
+
+
 class _EigBlockPieces:
     """The block kernels of the eigen-solvers alone, on host arrays of shape ``(n, m)`` (``igx_solver_eig_*_d``): shared by
-    ``EigenSystem`` and ``MultipatchEigenSystem``, which supply ``_live()``, ``_ctx``, ``n`` and ``_set_eig_precond``."""
+    ``EigenSystem``, ``VectorEigenSystem`` and ``MultipatchEigenSystem``, which supply ``_live()``, ``_ctx``, ``n`` and
+    ``_set_eig_precond``."""
 
     # -- the pieces alone, on host arrays of shape (n, m)
     def _upload_block(self, A):
@@ -2212,15 +2278,7 @@ class EigenSystem(_PatchErrorNorms, _EigBlockPieces, _DeviceSystem):
                                  'form string whose traced coefficient table is)' % (problem,))
         self.ndofs = tuple(kv.numdofs for kv in self.kvs)
         self.n = int(np.prod(self.ndofs))
-        if bcs is None:
-            idx = np.zeros(0, dtype=np.int64)
-        elif isinstance(bcs, tuple) and len(bcs) == 2 and np.ndim(bcs[0]) >= 1:
-            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
-        else:
-            idx = np.asarray(bcs, dtype=np.int64).ravel()
-        idx = np.unique(idx)
-        if idx.size and (idx[0] < 0 or idx[-1] >= self.n):
-            raise ValueError('fixed dof out of range')
+        idx = _eig_fixed_dofs(bcs, self.n)
         if _form_kind(problem) == 'stiffness' and idx.size == 0:
             raise ValueError('EigenSystem: the stiffness matrix without any fixed dof is singular (the constants), and the relative '
                              "stopping rule ||r|| <= tol ||K x|| has no scale there.  Shift instead: problem='(inner(grad(u), "
@@ -2286,32 +2344,110 @@ class EigenSystem(_PatchErrorNorms, _EigBlockPieces, _DeviceSystem):
         """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i M x_i|| <= tol ||K x_i||`` for the k lowest pairs.  `block`: the
         columns iterated (default ``k + max(2, k // 2)``, at most 16); `X0`: a start block of shape ``(n, block)``, else normal
         deviates of ``numpy.random.default_rng(seed)``.  Deterministic: the same inputs give the same bits."""
-        k = int(k)
-        m = default_eig_block(max(k, 1)) if block is None else int(block)
-        _check_eig_args(k, m, self.n_free)
-        if X0 is None:
-            X0 = np.random.default_rng(seed).standard_normal((self.n, m))
-        else:
-            X0 = np.asarray(X0, dtype=np.float64)
-            if X0.shape != (self.n, m):
-                raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (self.n, m)))
-        h = self._live()
-        key = self.set_precond(precond)
-        ops = _DeviceEigOps(h, self.n, m, X0, timed)
-        try:
-            lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
-            U = ops.download('X', k)
-            dev = ops.info()
-        finally:
-            ops.end()
-        info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
-        if timed:
-            info.update({name: dev[name] for name in dev if name.endswith('_ms')})
-        self.info = info
-        return lam[:k].copy(), U
+        return _patch_eig_solve(self, k, tol, maxiter, precond, block, X0, seed, timed)
 
     def spmv(self, x):
         raise NotImplementedError('EigenSystem holds two matrices: block_products(X) or block_product(X, which)')
+
+
+class VectorEigenSystem(_VectorBlocks, _EigBlockPieces, _DeviceSystem):
+    """The lowest eigenpairs of ``K x = lam (I (x) M) x`` for a vector-valued form K (``bfuns=[('u', nc), ('v', nc)]``, nc = 2 or
+    3) on the free dofs of one patch: the natural frequencies and mode shapes of an elastic body, by block LOBPCG with the
+    nc x nc blocks, the mass matrix, the iterated blocks and the preconditioner in device memory.
+
+    `problem`, `bfuns`, `args` / `inputs` (``geo`` among them): as ``VectorFormSystem`` takes them (a form string); the block
+    coefficient tables must be symmetric.  `bcs`: ``(indices, values)`` or just the indices, in the blocked numbering
+    (component-major, as ``assemble(..., layout='blocked')``); only the indices are used.  `mass`: None for the mass matrix of
+    the patch, or a scalar bilinear form string that ``FormSystem`` accepts and whose traced table is symmetric, such as
+    ``'rho*u*v*dx'`` for a density; the same M weighs every component.
+
+    ``solve(k)`` returns ``(lam, U)``: the k smallest eigenvalues in ascending order and ``U`` of shape ``(nc * N, k)`` with
+    ``U^T (I (x) M) U = I`` and zeros on the fixed dofs; ``U.reshape((nc,) + ndofs + (k,))`` gives the components on the tensor
+    grid of dofs.  ``block_products``, ``gram``, ``combine``, ``residuals`` and ``apply_precond`` run the block kernels alone on
+    host arrays of shape ``(nc * N, m)``.  The preconditioner is the block-diagonal Kronecker one of ``VectorFormSystem``
+    (``kron_factors``) when the fixed dofs of every component are whole sides, else Jacobi."""
+
+    def __init__(self, problem, kvs, bcs=None, args=None, bfuns=None, mass=None, **inputs):
+        from . import tforms
+        from .form_assemblers import FormAssembler, _full_table
+        args = dict(args or {})
+        args.update(inputs)
+        self.kvs = tuple(kvs)
+        nc = _vector_components(problem, self.kvs, args, bfuns)
+        if mass is not None:
+            ok = isinstance(mass, str)
+            if ok:
+                try:
+                    _check_device_form(mass, self.kvs, args)
+                    ok = _symmetric_problem(mass, self.kvs, args)
+                except Exception as e:
+                    raise ValueError('VectorEigenSystem: mass=%r: %s' % (mass, e))
+            if not ok:
+                raise ValueError('VectorEigenSystem: mass=%r is not a scalar bilinear form string whose traced coefficient table '
+                                 "is symmetric (such as 'rho*u*v*dx'), or None for the mass matrix of the patch" % (mass,))
+        self.ncomp = nc
+        self.ndofs = tuple(kv.numdofs for kv in self.kvs)
+        self.N = int(np.prod(self.ndofs))
+        self.n = nc * self.N
+        idx = _eig_fixed_dofs(bcs, self.n)
+        self.n_free = self.n - idx.size
+        self.assembler = FormAssembler(self.kvs, args['geo'], problem, bfuns=bfuns, inputs=args)
+        self.patch = self.assembler.patch
+        table = self.assembler._table
+        if not symmetric_block_tables(table):
+            raise ValueError('VectorEigenSystem: the block coefficient tables of %r are not symmetric' % (problem,))
+        if idx.size == 0 and all(table[p][q][0][0] is None for p in range(nc) for q in range(nc)):
+            raise ValueError('VectorEigenSystem: without any fixed dof and without a zeroth-order term K annihilates the constants, '
+                             'and the relative stopping rule ||r|| <= tol ||K x|| has no scale there.  Shift instead: add '
+                             "'+ inner(u, v)' to the form, then subtract 1 from the eigenvalues")
+        self._ctx = self.patch.ctx
+        try:
+            self._attach('igx_solver_create_block', (self.patch.handle, nc, 1), (idx, np.zeros(idx.size)), 'cg', 'cg')
+            self._take_blocks(table)
+            self._component_boxes()
+            if mass is None:
+                self.patch.assemble('mass', to_host=False)           # the values stay on the device and change hands
+            else:
+                d = len(self.kvs)
+                grid = [self.patch.gauss(k)[0] for k in range(d)]
+                X = np.asarray(args['geo'].grid_eval(grid))
+                scalar = {k: v for k, v in args.items() if k != 'geo'}
+                _, _, mtable, _ = tforms.evaluate(mass, tuple(len(g) for g in grid), X, scalar, None)
+                self.patch.set_form(_full_table(mtable[0][0], d))
+                self.patch.assemble('form', to_host=False)
+            _lib.check(_lib.load().igx_solver_take_mass(self.handle), 'igx_solver_take_mass')
+        except BaseException:
+            self._release()
+            self._drop_owner()
+            raise
+        self._eig_precond = False                                    # (no preconditioner of the eigen pieces set yet)
+
+    def set_precond(self, precond):
+        """The preconditioner of ``solve`` and ``apply_precond``: 'auto', 'kron', 'jacobi' or None."""
+        if precond == 'auto':
+            precond = self.default_precond
+        key = precond if precond is not None else 'none'
+        if key not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        if key == self._eig_precond:
+            return key
+        if key == 'kron' and not self._factors_set:
+            self._set_block_kron(h)                                  # (ValueError when a component has no free box)
+            self._factors_set = True
+        _lib.check(_lib.load().igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
+        self._eig_precond = key
+        return key
+
+    _set_eig_precond = set_precond
+
+    def solve(self, k=6, tol=1e-8, maxiter=200, precond='auto', block=None, X0=None, seed=0, timed=False):
+        """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i (I (x) M) x_i|| <= tol ||K x_i||`` for the k lowest pairs;
+        arguments, ``info`` and determinism as ``EigenSystem.solve`` (`X0` of shape ``(nc * N, block)``)."""
+        return _patch_eig_solve(self, k, tol, maxiter, precond, block, X0, seed, timed)
+
+    def spmv(self, x):
+        raise NotImplementedError('VectorEigenSystem holds two matrices: block_products(X) or block_product(X, which)')
 
 
 STIFFNESS_FORM = 'inner(grad(u), grad(v)) * dx'

@@ -16,7 +16,15 @@ JSON line per measurement.
        igx_solver_spmv_d on the same solver (the masked copy of x + k_csr_spmv over the same pattern; the mass product runs the
        same kernel over the same pattern, so it is counted at the time of the stiffness product), then one solve with 'mg' and
        one with 'jacobi': iterations, restarts, device ms per phase and wall time.
-  mp0  the same on a small domain (a smoke case)"""
+  mp0  the same on a small domain (a smoke case)
+  vec3d  the vector-valued eigen-solver (solvers.VectorEigenSystem): linear elasticity (mu = 1, lam = 2),
+       three components, on the quarter-annulus cylinder, p=2 n=50: 52^3 scalar dofs, nine blocks and the mass matrix, clamped
+       on the lower side of axis 0.  One igx_solver_eig_products_d call (the masked copy of X + k_block_spmm2 over the nine
+       blocks and M; `one_matrix_ms`: over the blocks alone) against m calls of igx_solver_spmv_d on a VectorFormSystem of the
+       same patch (the masked copy of x + k_block_spmv: the only product of blocked vectors there was, K alone).  The rate of the
+       value stream counts (blocks + nc) nnz 8 bytes per block product.  Then one solve, k=6.  The lines also go to
+       profiles/veceig_timing.txt (`--out PATH`: elsewhere)
+  vec0   the same on a small patch (a smoke case; printed only)"""
 import ctypes as C
 import json
 import os
@@ -174,6 +182,73 @@ def run_mp(name):
         MP.close()
 
 
+ELASTICITY = '(2*mu*inner(0.5*(grad(u)+grad(u).T), 0.5*(grad(v)+grad(v).T)) + lam*div(u)*div(v)) * dx'
+
+
+def run_vec(name, out=None):
+    """The vector-valued eigen-solver: every line is printed and, for `vec3d`, written to `out` (default
+    profiles/veceig_timing.txt)."""
+    p, n = (2, 50) if name == 'vec3d' else (2, 6)        # (make_knots has the reference's extra sliver span at n = 49)
+    nc = 3
+    kvs = 3 * (bspline.make_knots(p, 0.0, 1.0, n),)
+    geo = geometry.tensor_product(geometry.line_segment(0.0, 1.0), geometry.quarter_annulus())
+    ndofs = tuple(kv.numdofs for kv in kvs)
+    N = int(np.prod(ndofs))
+    nrows = nc * N
+    side = np.arange(N).reshape(ndofs)[0].ravel()                       # the lower side of axis 0, every component: a cantilever
+    fixed = np.concatenate([side + c * N for c in range(nc)])
+    bcs = (fixed, np.zeros(fixed.size))
+    lib = _lib.load()
+    rng = np.random.default_rng(0)
+    lines = []
+
+    def emit(rec):
+        lines.append(json.dumps(rec))
+        print(lines[-1], flush=True)
+    bf = [('u', nc), ('v', nc)]
+    S = solvers.VectorEigenSystem(ELASTICITY, kvs, bcs, bfuns=bf, geo=geo, mu=1.0, lam=2.0)
+    P = solvers.VectorFormSystem(ELASTICITY, kvs, 0.0, bcs, bfuns=bf, geo=geo, mu=1.0, lam=2.0)
+    try:
+        nnz = int(S.patch.nnz)
+        nblk = sum(sum(r) for r in S.present)
+        T = DeviceTimer(S._ctx)
+        d_x, d_y = DeviceArray.from_host(S._ctx, rng.standard_normal(nrows)), DeviceArray(S._ctx, nrows)
+        t_k = T.median(lambda: _lib.check(lib.igx_solver_spmv_d(P.handle, d_x.ptr, d_y.ptr), 'igx_solver_spmv_d'))
+        emit({'case': name, 'ndofs': list(ndofs), 'ncomp': nc, 'nnz': nnz, 'blocks': nblk, 'baseline': 'igx_solver_spmv_d (k_block_spmv)',
+              'reps': REPS, 'stiffness_ms': round(t_k, 4), 'GBs': round(8e-6 * nblk * nnz / t_k, 1)})
+        for m in (4, 8, 16):
+            mb = solvers.eig_width(m)
+            d_X = DeviceArray.from_host(S._ctx, rng.standard_normal((nrows, mb)))
+            d_K, d_M = DeviceArray(S._ctx, nrows * mb), DeviceArray(S._ctx, nrows * mb)
+            t2 = T.median(lambda: _lib.check(lib.igx_solver_eig_products_d(S.handle, mb, d_X.ptr, d_K.ptr, d_M.ptr), 'igx_solver_eig_products_d'))
+            t1 = T.median(lambda: _lib.check(lib.igx_solver_eig_products_d(S.handle, mb, d_X.ptr, d_K.ptr, None), 'igx_solver_eig_products_d'))
+            base = m * t_k                                               # (the parent's path has no mass product of blocked vectors: K alone)
+            emit({'case': name, 'm': m, 'block_product_ms': round(t2, 4), 'one_matrix_ms': round(t1, 4), 'single_products_ms': round(base, 4),
+                  'ratio_single_over_block': round(base / t2, 2), 'ratio_single_over_one_matrix': round(base / t1, 2),
+                  'value_stream_GBs': round(8e-6 * (nblk + nc) * nnz / t2, 1), 'one_matrix_value_stream_GBs': round(8e-6 * nblk * nnz / t1, 1)})
+        lam, _ = S.solve(k=6, tol=1e-8, maxiter=1000, timed=True)
+        info = S.info
+        emit({'case': name, 'solve': 'k=6 tol=1e-8 maxiter=1000', 'block': int(info['block']), 'precond': info['precond'],
+              'iterations': int(info['iterations']), 'converged': bool(info['converged'].all()), 'restarts': int(info['restarts']),
+              'lam': [round(float(v), 9) for v in lam], 'phase_ms': {k: round(float(v), 3) for k, v in info.items() if k.endswith('_ms')}})
+    finally:
+        S.close()
+        P.close()
+    if name == 'vec3d':
+        path = out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'veceig_timing.txt')
+        with open(path, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 if __name__ == '__main__':
-    for c in (sys.argv[1:] or ['c3d']):
-        (run_mp if c in ('mp', 'mp0') else run)(c)
+    args = sys.argv[1:]
+    out = None
+    if '--out' in args:
+        i = args.index('--out')
+        out = args[i + 1]
+        del args[i:i + 2]
+    for c in (args or ['c3d']):
+        if c in ('vec3d', 'vec0'):
+            run_vec(c, out)
+        else:
+            (run_mp if c in ('mp', 'mp0') else run)(c)
