@@ -640,6 +640,34 @@ int  igx_solver_take_block(igx_solver *solver, int p, int q);
 int  igx_solver_set_block_kron(igx_solver *solver, int comp, const int32_t *box_lo, const int32_t *box_hi,
                                const double *const *U, const double *const *lam, int mode);
 
+/* --- Vector-valued forms on a multipatch (elasticity on a multi-patch solid): a block solver over the nc x nc scalar blocks
+   A_pq = sum_patch X A^{patch}_pq X^T, which all share the global CSR pattern of `mp`.  A global vector has
+   nc * nrows entries, component-major; every component uses the scalar numbering and joins of the multipatch, and the mask of
+   fixed dofs covers all nc * nrows entries.  One block SpMV per product reads every present block once.
+   A block solver over the pattern of `mp` with ncomp = 2 or 3 components (else IGX_ERR_ARG); fixed[0..nfixed) are blocked
+   global indices in [0, ncomp * nrows).  It starts in IGX_METHOD_CG if `symmetric`, else in IGX_METHOD_BICGSTAB; IGX_METHOD_CG
+   on a solver made with symmetric = 0 is IGX_ERR_UNSUPPORTED.  The solver reads the pattern of `mp`, which must outlive it, but
+   owns its value buffers: restarting the multipatch's sums afterwards leaves it as it is.  igx_solver_solve needs b (host,
+   nc * nrows; NULL: IGX_ERR_ARG).  Preconditioners: NONE, JACOBI (the diagonals of the diagonal blocks), SCHWARZ once
+   igx_solver_set_block_schwarz has set every component; IGX_PRECOND_KRON, IGX_PRECOND_MG and the eigen, parabolic, stepping and
+   Newton calls: IGX_ERR_UNSUPPORTED. */
+int  igx_solver_create_multipatch_block(igx_multipatch *mp, int ncomp, int symmetric, const int64_t *fixed, int64_t nfixed,
+                                        igx_solver **out);
+/* Copies the current sums of the multipatch (after igx_multipatch_zero and the scatters of EVERY patch: the interior rows are
+   only ever overwritten, so a patch without values for this block scatters zeros) device to device into nnz doubles of the
+   solver's own: block (p, q).  A block taken twice, p or q out of range, or sums restarted with nothing scattered since:
+   IGX_ERR_ARG.  A block never taken is absent: zero, never read.  Peak memory: the present blocks plus the multipatch's own
+   value array. */
+int  igx_solver_take_multipatch_block(igx_solver *solver, int p, int q);
+/* The nnz values of block (p, q) to the host, in the order of igx_multipatch_pattern (an absent block: IGX_ERR_ARG). */
+int  igx_solver_download_multipatch_block(const igx_solver *solver, int p, int q, double *vals);
+/* Per component, the additive Schwarz preconditioner of igx_solver_set_schwarz (same arguments) acting on the slice
+   [comp * nrows, (comp + 1) * nrows) of the vectors with that component's mask.  Once every component is set,
+   igx_solver_set_precond(IGX_PRECOND_SCHWARZ) selects diag(P_0, .., P_{nc-1}).  A multipatch whose maps are not all injective:
+   IGX_ERR_UNSUPPORTED. */
+int  igx_solver_set_block_schwarz(igx_solver *solver, int comp, const int32_t *box_lo, const int32_t *box_hi,
+                                  const double *const *U, const double *const *lam, int lam_mode);
+
 /* --- Parabolic problems: DIRK time stepping on the device (pyiga/solvers.py:366-473: dirk_step with constant steps) ----------
    M u' = f - K u on the free dofs, u = g on the fixed ones, u(t0) = x0; f and g constant in time.  M is the patch's mass matrix,
    K the matrix of kind_K (any kind igx_solver_create_general accepts).  One step of the tableau A ((stages + 1) x stages, row-major,

@@ -66,6 +66,7 @@ IGX_KRON_SUM, IGX_KRON_PRODUCT = 1, 2
 PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'kron': IGX_PRECOND_KRON}
 MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ,
                'mg': IGX_PRECOND_MG}
+MPVEC_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ}
 IGX_METHOD_CG, IGX_METHOD_BICGSTAB = 0, 1
 METHODS = {'cg': IGX_METHOD_CG, 'bicgstab': IGX_METHOD_BICGSTAB}
 IGX_BREAKDOWN_RHO, IGX_BREAKDOWN_ALPHA, IGX_BREAKDOWN_OMEGA, IGX_BREAKDOWN_NONFINITE = 1, 2, 3, 4
@@ -235,6 +236,10 @@ SYMBOLS = [
     ('igx_solver_create_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
     ('igx_solver_take_block', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ('igx_solver_set_block_kron', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
+    ('igx_solver_create_multipatch_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_take_multipatch_block', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ('igx_solver_download_multipatch_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
+    ('igx_solver_set_block_schwarz', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
     ('igx_solver_destroy', None, [C.c_void_p]),
     ('igx_solver_set_precond', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),
     ('igx_solver_set_schwarz', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int]),

@@ -428,6 +428,7 @@ struct igx_multipatch {
     long long zero_from = 0;                   // igx_multipatch_zero clears values [zero_from, nnz): the rows more than one local row reaches
     long long vzero_from = 0;                  // ... and vector entries [vzero_from, nglobal)
     unsigned long long generation = 0;         // bumped by igx_multipatch_zero: a solver made over older sums refuses to run
+    unsigned long long scattered = ~0ULL;      // the generation whose sums last received a patch's values (none yet: no generation)
     int32_t *d_indptr = nullptr, *d_indices = nullptr, *d_contrib = nullptr;
     double *d_vals = nullptr, *d_vec = nullptr, *d_stage = nullptr;
     size_t stage_len = 0;

@@ -16,6 +16,7 @@ struct SolverRef {
     const uint8_t *d_mask;                    // 1 on the free dofs (device), and
     const uint8_t *h_free;                    // the same on the host
     int precond, method;
+    int ncomp;                                // > 1: a multipatch block solver (no multigrid)
 };
 
 // solve.hip

@@ -228,6 +228,7 @@ int level_of(igx_solver *s, MgLevel **out, const char *what)
 {
     const SolverRef R = solver_ref(s);
     if (!R.mp) { set_error("%s: multigrid needs a multipatch solver", what); return IGX_ERR_UNSUPPORTED; }
+    if (R.ncomp > 1) { set_error("%s: no multigrid for multipatch block solvers (vector-valued systems)", what); return IGX_ERR_UNSUPPORTED; }
     MgLevel *&L = solver_mg(s);
     if (!L) {
         IGX_HIP(hipSetDevice(R.ctx->device));

@@ -491,6 +491,7 @@ int run_scatter(igx_multipatch *mp, int p, const double *d_src)
     if (P.n) k_scatter<<<waves_grid(P.n), 256, 0, st>>>(P.d_info, P.d_cpos, P.n, d_src, mp->d_vals);
     IGX_HIP(hipGetLastError());
     IGX_HIP(hipStreamSynchronize(st));     // (host staging buffer and the source patch may be reused / freed after the call)
+    mp->scattered = mp->generation;
     return IGX_OK;
 }
 

@@ -15,12 +15,14 @@
 //              (k_box_scatter), patch after patch.
 //   k_block_spmv  the product of a vector-valued form's NC x NC blocks (NC = 2, 3), which share the patch's layout: one group per
 //              scalar row computes the NC outputs (igx_solver_create_block).
+//   k_csr_block_spmv  the same product for the blocks of a vector-valued form on a multipatch, which share its global CSR
+//              pattern (igx_solver_create_multipatch_block); Schwarz then acts component by component.
 //   vector     fused CG updates and fixed-order two-pass dot products (fixed grid, fixed trees): two solves of the same
 //              system give bit-identical results.  alpha and beta stay in device memory.
 //   BiCGStab   for non-symmetric matrices (igx_solver_create_general / igx_solver_set_method): the same SpMVs and
 //              preconditioners, fused p / s / x-r updates that emit their dot partials, and k_fin_bicg for rho, alpha, omega,
 //              the stop and breakdown on the device.
-// Host side: one dispatch table per SpMV family (with_spmv_kernel, with_csr_spmv_kernel) names the instantiations, for the launch
+// Host side: one dispatch table per SpMV family (with_spmv_kernel, with_csr_spmv_kernel, ...) names the instantiations, for the launch
 // and the occupancy query alike; one fast-diagonalization block (FastDiag) is the Kronecker preconditioner of a patch and the
 // local solve of every Schwarz patch; igx_solver_solve forms the lifted right-hand side and hands over to solve_cg or
 // solve_bicgstab.  Newton's method on a patch solver is the same solve for the increment.
@@ -251,6 +253,91 @@ __global__ void __launch_bounds__(BLOCK) k_csr_spmv(long long nrows, const int32
             const double v = (b ? b[I] : 0.0) + s * acc;
             y[I] = v;
             if (pd) dot += pd[I] * v;
+        }
+    }
+    if (part) {
+        const double v = block_sum(dot, sh);
+        if (threadIdx.x == 0) part[blockIdx.x] = v;
+    }
+}
+
+// The contracts of k_csr_spmv and k_block_spmv together: the block matrix [A_pq] of a vector-valued form over the global CSR
+// pattern of a multipatch, which all NC x NC blocks share.  Vectors have NC * N entries, component-major
+// (x_q[J] = x[q N + J], N the scalar global dofs): y[p N + I] = free[p N + I] ? (b ? b[p N + I] : 0) + s * sum_q (A_pq x_q)[I] : 0,
+// part[block] = sum of pd . y over the NC outputs of the rows of the block (optional).  One group of GW lanes per scalar global
+// row I: per entry a lane loads the column index once, gathers x_q[J] for the NC trial components and streams the values of the
+// blocks that are present (uniform over the grid) and whose test component is free in this row (uniform over the group).  Values
+// and indices are read once, non-temporally, at 64-bit offsets; the row header (indptr and the NC free flags, bit p of fr) is
+// loaded one row ahead.
+template <int GW, int U, int NC>
+__global__ void __launch_bounds__(BLOCK) k_csr_block_spmv(long long N, const int32_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                          const BlockVals A, const uint8_t *__restrict__ freem,
+                                                          const double *__restrict__ x, const double *b, double s, double *y,
+                                                          const double *__restrict__ pd, double *part)
+{
+    __shared__ double sh[BLOCK];
+    const int lane = threadIdx.x % GW;
+    const long long ngroups = (long long)gridDim.x * (BLOCK / GW);
+    double dot = 0.0;
+    long long I = (long long)blockIdx.x * (BLOCK / GW) + threadIdx.x / GW;
+    auto row_flags = [&](long long R) {
+        int f = 0;
+#pragma unroll
+        for (int p = 0; p < NC; ++p) f |= (freem[p * N + R] != 0) << p;
+        return f;
+    };
+    long long nk0 = 0, nk1 = 0;
+    int nfr = 0;
+    if (I < N) { nfr = row_flags(I); nk0 = indptr[I]; nk1 = indptr[I + 1]; }
+    for (; I < N; I += ngroups) {
+        const long long k0 = nk0, k1 = nk1;
+        const int fr = nfr;
+        if (I + ngroups < N) { nfr = row_flags(I + ngroups); nk0 = indptr[I + ngroups]; nk1 = indptr[I + ngroups + 1]; }
+        if (!fr) {                                   // (uniform over the group)
+            if (lane < NC) y[lane * N + I] = 0.0;
+            continue;
+        }
+        double acc[NC];
+#pragma unroll
+        for (int p = 0; p < NC; ++p) acc[p] = 0.0;
+        for (long long k = k0 + lane; k < k1; k += U * GW) {
+            double v[U][NC][NC], xv[U][NC];
+            int c[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k + u * GW < k1;
+                c[u] = in ? __builtin_nontemporal_load(indices + k + u * GW) : -1;
+#pragma unroll
+                for (int p = 0; p < NC; ++p)
+#pragma unroll
+                    for (int q = 0; q < NC; ++q) {
+                        const double *vp = A.v[p * NC + q];
+                        v[u][p][q] = (in && ((fr >> p) & 1) && vp) ? __builtin_nontemporal_load(vp + k + u * GW) : 0.0;
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int q = 0; q < NC; ++q) xv[u][q] = c[u] >= 0 ? x[q * N + c[u]] : 0.0;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int p = 0; p < NC; ++p)
+#pragma unroll
+                    for (int q = 0; q < NC; ++q) acc[p] += v[u][p][q] * xv[u][q];
+        }
+#pragma unroll
+        for (int p = 0; p < NC; ++p)
+#pragma unroll
+            for (int off = GW / 2; off > 0; off >>= 1) acc[p] += __shfl_xor(acc[p], off, GW);
+        if (lane == 0) {
+#pragma unroll
+            for (int p = 0; p < NC; ++p) {
+                const long long o = p * N + I;
+                const double v = ((fr >> p) & 1) ? (b ? b[o] : 0.0) + s * acc[p] : 0.0;
+                y[o] = v;
+                if (pd) dot += pd[o] * v;
+            }
         }
     }
     if (part) {
@@ -759,6 +846,28 @@ decltype(auto) with_block_spmv_kernel(int gw, int nc, F &&f)
     }
 }
 
+// the same for the block SpMV over a multipatch's CSR pattern (the U of k_block_spmv: the same NC^2 U values in flight per lane)
+template <class F>
+decltype(auto) with_csr_block_spmv_kernel(int gw, int nc, F &&f)
+{
+    if (nc == 3) {
+        switch (gw) {
+        case 64: return f(k_csr_block_spmv<64, 2, 3>);
+        case 32: return f(k_csr_block_spmv<32, 2, 3>);
+        case 16: return f(k_csr_block_spmv<16, 2, 3>);
+        case 8: return f(k_csr_block_spmv<8, 2, 3>);
+        default: return f(k_csr_block_spmv<4, 2, 3>);
+        }
+    }
+    switch (gw) {
+    case 64: return f(k_csr_block_spmv<64, 4, 2>);
+    case 32: return f(k_csr_block_spmv<32, 4, 2>);
+    case 16: return f(k_csr_block_spmv<16, 4, 2>);
+    case 8: return f(k_csr_block_spmv<8, 4, 2>);
+    default: return f(k_csr_block_spmv<4, 4, 2>);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // the fast-diagonalization inverse of one box (FastDiag, solve_internal.h)
 
@@ -838,7 +947,8 @@ void mask_copy(hipStream_t st, const igx_solver *s, const double *x, double *y)
 void jacobi_diagonal(hipStream_t st, const igx_solver *s, const double *vals, double *dinv, int comp)
 {
     if (const igx_multipatch *m = s->mp) {
-        k_csr_diag<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->n, m->d_indptr, m->d_indices, vals, s->d_mask, dinv);
+        const long long N = m->nglobal;
+        k_csr_diag<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(N, m->d_indptr, m->d_indices, vals, s->d_mask + comp * N, dinv);
         return;
     }
     const long long N = s->g.nrows;
@@ -859,7 +969,8 @@ int check_values(const igx_solver *s, const char *what)
     if (s->ncomp > 1) {                       // (the blocks are the solver's own: only a missing diagonal one is refused)
         for (int c = 0; c < s->ncomp; ++c)
             if (!s->block.blk[c * s->ncomp + c]) {
-                set_error("%s: diagonal block (%d, %d) missing: take it first (igx_solver_take_block)", what, c, c);
+                set_error("%s: diagonal block (%d, %d) missing: take it first (%s)", what, c, c,
+                          s->mp ? "igx_solver_take_multipatch_block" : "igx_solver_take_block");
                 return IGX_ERR_ARG;
             }
         return IGX_OK;
@@ -901,11 +1012,18 @@ static unsigned spmv_blocks(const igx_solver *s)
 }
 
 // y = free ? (b ? b : 0) + sign A x : 0 (and the partials of pd.y): k_spmv on a patch's values, k_csr_spmv on a multipatch's sums,
-// k_block_spmv on the blocks of a block solver
+// k_block_spmv on the blocks of a block solver, k_csr_block_spmv on those of a multipatch block solver
 int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
 {
     const unsigned nb = spmv_blocks(s);
-    if (s->mp) {
+    if (s->mp && s->ncomp > 1) {
+        const igx_multipatch *m = s->mp;
+        BlockVals A{};
+        for (int k = 0; k < s->ncomp * s->ncomp; ++k) A.v[k] = s->block.blk[k];
+        with_csr_block_spmv_kernel(s->gw, s->ncomp, [&](auto k) {
+            k<<<nb, BLOCK, 0, st>>>(m->nglobal, m->d_indptr, m->d_indices, A, s->d_mask, x, b, sign, y, pd, part);
+        });
+    } else if (s->mp) {
         const igx_multipatch *m = s->mp;
         with_csr_spmv_kernel(s->gw, [&](auto k) {
             k<<<nb, BLOCK, 0, st>>>(s->n, m->d_indptr, m->d_indices, m->d_vals, s->d_mask, x, b, sign, y, pd, part);
@@ -947,17 +1065,22 @@ static int apply_kron(hipStream_t st, igx_solver *s, const double *r, double *z)
 }
 
 // z = sum_p X_p M_p B_p M_p X_p^T r: per patch, in patch order, gather the box, the two Kronecker products, add back on the free dofs
+// (a multipatch block solver: component after component on its slice of the vectors and of the mask, with its own patches)
 static int apply_schwarz(hipStream_t st, igx_solver *s, const double *r, double *z)
 {
     IGX_HIP(hipMemsetAsync(z, 0, (size_t)s->n * sizeof(double), st));
     double *W[2] = {s->d_W, s->d_W + s->wlen};
-    for (const SwPatch &P : s->sw) {
-        const unsigned nb = (unsigned)((P.map.nbox + 255) / 256);
-        k_box_gather<<<nb, 256, 0, st>>>(P.map, s->d_mask, r, s->d_box);
-        IGX_HIP(hipGetLastError());
-        if (int rc = apply_fastdiag(st, P.F, s->d_box, s->d_box, W)) return rc;
-        k_box_scatter<<<nb, 256, 0, st>>>(P.map, s->d_mask, s->d_box, z);
-        IGX_HIP(hipGetLastError());
+    const long long N = s->n / s->ncomp;
+    for (int c = 0; c < s->ncomp; ++c) {
+        const long long o = c * N;
+        for (const SwPatch &P : s->ncomp > 1 ? s->block.bsw[c] : s->sw) {
+            const unsigned nb = (unsigned)((P.map.nbox + 255) / 256);
+            k_box_gather<<<nb, 256, 0, st>>>(P.map, s->d_mask + o, r + o, s->d_box);
+            IGX_HIP(hipGetLastError());
+            if (int rc = apply_fastdiag(st, P.F, s->d_box, s->d_box, W)) return rc;
+            k_box_scatter<<<nb, 256, 0, st>>>(P.map, s->d_mask + o, s->d_box, z + o);
+            IGX_HIP(hipGetLastError());
+        }
     }
     return IGX_OK;
 }
@@ -973,7 +1096,7 @@ static int spmv_occupancy(const igx_solver *s)
 {
     int per_cu = 0;
     auto occupancy = [&](auto k) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0); };
-    const hipError_t eo = s->mp ? with_csr_spmv_kernel(s->gw, occupancy)
+    const hipError_t eo = s->mp ? (s->ncomp > 1 ? with_csr_block_spmv_kernel(s->gw, s->ncomp, occupancy) : with_csr_spmv_kernel(s->gw, occupancy))
                                 : s->ncomp > 1 ? with_block_spmv_kernel(s->gw, s->ncomp, occupancy) : with_spmv_kernel(s->gw, occupancy);
     if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
     return (int)std::min<long long>(NB_SPMV_MAX, (long long)std::max(1, per_cu) * std::max(1, s->ctx->ncu));
@@ -1346,7 +1469,15 @@ int box_fastdiag_setup(igx_solver *s, long long base, const int32_t *box_lo, con
 // what multigrid.hip sees of a solver (mg_internal.h)
 SolverRef solver_ref(const igx_solver *s)
 {
-    return SolverRef{s->ctx, s->mp, s->n, s->gw, s->d_mask, s->h_free.data(), s->precond, s->method};
+    return SolverRef{s->ctx, s->mp, s->n, s->gw, s->d_mask, s->h_free.data(), s->precond, s->method, s->ncomp};
+}
+
+int refuse_multipatch_block(const igx_solver *s, const char *what)
+{
+    if (!s || !s->mp || s->ncomp < 2) return IGX_OK;
+    set_error("%s: a multipatch block solver (igx_solver_create_multipatch_block) serves the linear solves, the SpMV and its "
+              "Jacobi and Schwarz preconditioners only", what);
+    return IGX_ERR_UNSUPPORTED;
 }
 
 MgLevel *&solver_mg(igx_solver *s) { return s->mg; }
@@ -1444,6 +1575,66 @@ int igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64
     return IGX_OK;
 }
 
+int igx_solver_create_multipatch_block(igx_multipatch *mp, int ncomp, int symmetric, const int64_t *fixed, int64_t nfixed, igx_solver **out)
+{
+    const char *what = "igx_solver_create_multipatch_block";
+    if (!create_args_ok(mp, fixed, nfixed, out, what)) return IGX_ERR_ARG;
+    if (ncomp != 2 && ncomp != 3) { set_error("%s: ncomp must be 2 or 3, not %d", what, ncomp); return IGX_ERR_ARG; }
+    if (hipSetDevice(mp->ctx->device) != hipSuccess) { set_error("%s: hipSetDevice failed", what); return IGX_ERR_HIP; }
+    igx_solver *s = new igx_solver;
+    // (the blocks are the solver's own copies: it is not bound to the generation of the multipatch's sums)
+    s->ctx = mp->ctx; s->mp = mp; s->gen = mp->generation; s->kind = -1; s->ncomp = ncomp; s->n = ncomp * mp->nglobal;
+    s->symmetric = symmetric != 0;
+    if (int rc = init_solver(s, fixed, nfixed, mp->max_row, {}, what)) return rc;
+    if (!s->symmetric) {
+        if (int rc = init_bicgstab(s, what)) { free_solver(s); return rc; }
+        s->method = IGX_METHOD_BICGSTAB;
+    }
+    *out = s;
+    return IGX_OK;
+}
+
+int igx_solver_take_multipatch_block(igx_solver *s, int p, int q)
+{
+    const char *what = "igx_solver_take_multipatch_block";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (!s->mp || s->ncomp < 2) { set_error("%s: not a multipatch block solver (igx_solver_create_multipatch_block)", what); return IGX_ERR_ARG; }
+    if (p < 0 || p >= s->ncomp || q < 0 || q >= s->ncomp) { set_error("%s: block (%d, %d) of %d components", what, p, q, s->ncomp); return IGX_ERR_ARG; }
+    double *&dst = s->block.blk[p * s->ncomp + q];
+    if (dst) { set_error("%s: block (%d, %d) was taken already", what, p, q); return IGX_ERR_ARG; }
+    const igx_multipatch *mp = s->mp;
+    if (mp->scattered != mp->generation) {
+        set_error("%s: nothing was scattered into the multipatch's sums since they were restarted (igx_multipatch_zero clears the "
+                  "interface rows only): scatter every patch first", what);
+        return IGX_ERR_ARG;
+    }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    double *copy = nullptr;
+    if (hipMalloc((void **)&copy, (size_t)mp->nnz * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: out of device memory (%.3f GB)", what, 8.0 * mp->nnz / 1e9);
+        return IGX_ERR_NOMEM;
+    }
+    if (int rc = igx_multipatch_values_d(mp, copy)) { (void)hipFree(copy); return rc; }
+    dst = copy;
+    return IGX_OK;
+}
+
+int igx_solver_download_multipatch_block(const igx_solver *s, int p, int q, double *vals)
+{
+    const char *what = "igx_solver_download_multipatch_block";
+    if (!s || !vals) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!s->mp || s->ncomp < 2) { set_error("%s: not a multipatch block solver (igx_solver_create_multipatch_block)", what); return IGX_ERR_ARG; }
+    if (p < 0 || p >= s->ncomp || q < 0 || q >= s->ncomp) { set_error("%s: block (%d, %d) of %d components", what, p, q, s->ncomp); return IGX_ERR_ARG; }
+    const double *src = s->block.blk[p * s->ncomp + q];
+    if (!src) { set_error("%s: block (%d, %d) is absent", what, p, q); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    IGX_HIP(hipMemcpyAsync(vals, src, (size_t)s->mp->nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+    IGX_HIP(hipStreamSynchronize(st));
+    return IGX_OK;
+}
+
 int igx_solver_create_block(igx_patch *pt, int ncomp, int symmetric, const int64_t *fixed, int64_t nfixed, igx_solver **out)
 {
     const char *what = "igx_solver_create_block";
@@ -1464,7 +1655,7 @@ int igx_solver_take_block(igx_solver *s, int p, int q)
 {
     const char *what = "igx_solver_take_block";
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
-    if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
+    if (s->ncomp < 2 || s->mp) { set_error("%s: not a block solver of a patch (igx_solver_create_block)", what); return IGX_ERR_ARG; }
     if (p < 0 || p >= s->ncomp || q < 0 || q >= s->ncomp) { set_error("%s: block (%d, %d) of %d components", what, p, q, s->ncomp); return IGX_ERR_ARG; }
     double *&dst = s->block.blk[p * s->ncomp + q];
     if (dst) { set_error("%s: block (%d, %d) was taken already", what, p, q); return IGX_ERR_ARG; }
@@ -1486,6 +1677,7 @@ int igx_solver_set_block_kron(igx_solver *s, int comp, const int32_t *box_lo, co
 {
     const char *what = "igx_solver_set_block_kron";
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
     if (comp < 0 || comp >= s->ncomp) { set_error("%s: component %d of %d", what, comp, s->ncomp); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(s->ctx->device));
@@ -1508,6 +1700,7 @@ int igx_solver_take_mass(igx_solver *s)
 {
     const char *what = "igx_solver_take_mass";
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
     if (s->block.mass) { set_error("%s: the mass matrix was taken already", what); return IGX_ERR_ARG; }
     igx_patch *pt = s->pt;
@@ -1542,10 +1735,11 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     if (precond == IGX_PRECOND_NONE) { s->precond = precond; return IGX_OK; }
     if (precond == IGX_PRECOND_JACOBI) {
         if (int rc = check_values(s, "igx_solver_set_precond")) return rc;
-        if (s->mp) jacobi_diagonal(st, s, s->mp->d_vals, s->dinv);
-        else if (s->ncomp > 1) {                              // component c: the diagonal of block (c, c) at offset c g.nrows
-            for (int c = 0; c < s->ncomp; ++c) jacobi_diagonal(st, s, s->block.blk[c * s->ncomp + c], s->dinv + c * s->g.nrows, c);
-        } else jacobi_diagonal(st, s, patch_values(s), s->dinv);
+        if (s->ncomp > 1) {                                   // component c: the diagonal of block (c, c) at offset c (scalar rows)
+            const long long N = s->n / s->ncomp;
+            for (int c = 0; c < s->ncomp; ++c) jacobi_diagonal(st, s, s->block.blk[c * s->ncomp + c], s->dinv + c * N, c);
+        } else if (s->mp) jacobi_diagonal(st, s, s->mp->d_vals, s->dinv);
+        else jacobi_diagonal(st, s, patch_values(s), s->dinv);
         IGX_HIP(hipGetLastError());
         IGX_HIP(hipStreamSynchronize(st));
         s->precond = precond;
@@ -1553,11 +1747,21 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     }
     if (precond == IGX_PRECOND_SCHWARZ) {
         if (!s->mp) { set_error("igx_solver_set_precond: the Schwarz preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
+        if (s->ncomp > 1) {                                   // the factors of every component, set by igx_solver_set_block_schwarz
+            for (int c = 0; c < s->ncomp; ++c)
+                if (s->block.bsw[c].empty()) {
+                    set_error("igx_solver_set_precond: set the Schwarz factors of component %d first (igx_solver_set_block_schwarz)", c);
+                    return IGX_ERR_ARG;
+                }
+            s->precond = precond;
+            return IGX_OK;
+        }
         if (s->sw.empty() || !s->d_W) { set_error("igx_solver_set_precond: set the Schwarz factors up first (igx_solver_set_schwarz)"); return IGX_ERR_ARG; }
         s->precond = precond;
         return IGX_OK;
     }
     if (precond == IGX_PRECOND_MG) {
+        if (int rc = refuse_multipatch_block(s, "igx_solver_set_precond(IGX_PRECOND_MG)")) return rc;
         if (!s->mp) { set_error("igx_solver_set_precond: the multigrid preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
         if (s->method != IGX_METHOD_CG) { set_error("igx_solver_set_precond: the multigrid preconditioner serves CG only"); return IGX_ERR_UNSUPPORTED; }
         if (int rc = mg_check(s, "igx_solver_set_precond")) return rc;
@@ -1583,31 +1787,30 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     return IGX_OK;
 }
 
-int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
-                           const double *const *lam, int lam_mode)
+// The host side of a Schwarz set-up over the multipatch of s (igx_solver_set_schwarz; igx_solver_set_block_schwarz per component):
+// the arguments checked, then per patch with a non-empty box its map in sw and, per axis, U_k^T | U_k | lam_k at fac[j] in h;
+// wlen: the largest box
+static int pack_schwarz(const igx_solver *s, const int32_t *box_lo, const int32_t *box_hi, const double *const *U, const double *const *lam,
+                        int lam_mode, const char *what, std::vector<SwPatch> &sw, std::vector<size_t> &fac, std::vector<double> &h,
+                        long long &wlen)
 {
-    if (!s) { set_error("igx_solver_set_schwarz: null solver"); return IGX_ERR_ARG; }
-    if (!s->mp) { set_error("igx_solver_set_schwarz: the Schwarz preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
+    if (!s->mp) { set_error("%s: the Schwarz preconditioner needs a multipatch solver", what); return IGX_ERR_UNSUPPORTED; }
     const igx_multipatch *mp = s->mp;
     if (!mp->injective) {
-        set_error("igx_solver_set_schwarz: a local-to-global map is not injective (two dofs of one patch share a global dof); "
-                  "use IGX_PRECOND_JACOBI");
+        set_error("%s: a local-to-global map is not injective (two dofs of one patch share a global dof); "
+                  "use IGX_PRECOND_JACOBI", what);
         return IGX_ERR_UNSUPPORTED;
     }
-    if (!box_lo || !box_hi || !U || !lam) { set_error("igx_solver_set_schwarz: null argument"); return IGX_ERR_ARG; }
-    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("igx_solver_set_schwarz: unknown lam_mode %d", lam_mode); return IGX_ERR_ARG; }
-    // per patch with a non-empty box its map and, per axis, U_k^T | U_k | lam_k at fac[j] in h
-    std::vector<SwPatch> sw;
-    std::vector<size_t> fac;
-    std::vector<double> h;
-    long long wlen = 1;
+    if (!box_lo || !box_hi || !U || !lam) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("%s: unknown lam_mode %d", what, lam_mode); return IGX_ERR_ARG; }
+    wlen = 1;
     for (int p = 0; p < mp->np; ++p) {
         const auto &P = mp->pp[p];
         bool empty = false;
         for (int k = 0; k < P.dim; ++k) {
             const int lo = box_lo[p * 3 + k], hi = box_hi[p * 3 + k];
             if (lo < 0 || hi > P.N[k] || lo > hi) {
-                set_error("igx_solver_set_schwarz: patch %d: bad box [%d, %d) on axis %d of %d dofs", p, lo, hi, k, P.N[k]);
+                set_error("%s: patch %d: bad box [%d, %d) on axis %d of %d dofs", what, p, lo, hi, k, P.N[k]);
                 return IGX_ERR_ARG;
             }
             empty = empty || lo == hi;
@@ -1619,7 +1822,7 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
         W.map.nbox = 1;
         for (int k = 0; k < P.dim; ++k) {
             const int m = box_hi[p * 3 + k] - box_lo[p * 3 + k];
-            if (!U[p * 3 + k] || !lam[p * 3 + k]) { set_error("igx_solver_set_schwarz: patch %d: factor of axis %d missing", p, k); return IGX_ERR_ARG; }
+            if (!U[p * 3 + k] || !lam[p * 3 + k]) { set_error("%s: patch %d: factor of axis %d missing", what, p, k); return IGX_ERR_ARG; }
             W.map.lo[off + k] = box_lo[p * 3 + k]; W.map.nb[off + k] = m; W.map.N[off + k] = P.N[k];
             W.map.nbox *= m;
         }
@@ -1629,7 +1832,36 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
         wlen = std::max(wlen, W.map.nbox);
         sw.push_back(W);
     }
-    if (sw.empty()) { set_error("igx_solver_set_schwarz: every patch box is empty"); return IGX_ERR_ARG; }
+    if (sw.empty()) { set_error("%s: every patch box is empty", what); return IGX_ERR_ARG; }
+    return IGX_OK;
+}
+
+// the fast-diagonalization plans of the packed patches over their factors on the device (compact box vectors in and out)
+static void plan_schwarz(std::vector<SwPatch> &sw, const std::vector<size_t> &fac, const double *d_fac, int lam_mode)
+{
+    for (size_t j = 0; j < sw.size(); ++j) {
+        const int d = sw[j].F.dim;
+        const int *m = sw[j].map.nb + (3 - d);
+        long long stride[4];
+        box_strides(d, m, stride);
+        sw[j].F = make_fastdiag(d, m, d_fac + fac[j], stride, 0, lam_mode);
+    }
+}
+
+int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                           const double *const *lam, int lam_mode)
+{
+    const char *what = "igx_solver_set_schwarz";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->mp && s->ncomp > 1) {
+        set_error("%s: a multipatch block solver takes its Schwarz factors per component (igx_solver_set_block_schwarz)", what);
+        return IGX_ERR_UNSUPPORTED;
+    }
+    std::vector<SwPatch> sw;
+    std::vector<size_t> fac;
+    std::vector<double> h;
+    long long wlen = 1;
+    if (int rc = pack_schwarz(s, box_lo, box_hi, U, lam, lam_mode, what, sw, fac, h, wlen)) return rc;
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     IGX_HIP(hipStreamSynchronize(st));
@@ -1639,16 +1871,41 @@ int igx_solver_set_schwarz(igx_solver *s, const int32_t *box_lo, const int32_t *
     if (int rc = upload_replacing(st, h, s->d_kron)) return rc;
     if (int rc = alloc_fastdiag_work(s, wlen)) return rc;
     IGX_HIP(hipMalloc((void **)&s->d_box, (size_t)wlen * sizeof(double)));
-    for (size_t j = 0; j < sw.size(); ++j) {
-        const int d = sw[j].F.dim;
-        const int *m = sw[j].map.nb + (3 - d);
-        long long stride[4];                            // compact box vectors in and out
-        box_strides(d, m, stride);
-        sw[j].F = make_fastdiag(d, m, s->d_kron + fac[j], stride, 0, lam_mode);
-    }
+    plan_schwarz(sw, fac, s->d_kron, lam_mode);
     IGX_HIP(hipStreamSynchronize(st));
     s->sw = std::move(sw);
     s->precond = IGX_PRECOND_SCHWARZ;
+    return IGX_OK;
+}
+
+int igx_solver_set_block_schwarz(igx_solver *s, int comp, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                                 const double *const *lam, int lam_mode)
+{
+    const char *what = "igx_solver_set_block_schwarz";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (!s->mp || s->ncomp < 2) { set_error("%s: not a multipatch block solver (igx_solver_create_multipatch_block)", what); return IGX_ERR_ARG; }
+    if (comp < 0 || comp >= s->ncomp) { set_error("%s: component %d of %d", what, comp, s->ncomp); return IGX_ERR_ARG; }
+    std::vector<SwPatch> sw;
+    std::vector<size_t> fac;
+    std::vector<double> h;
+    long long wlen = 1;
+    if (int rc = pack_schwarz(s, box_lo, box_hi, U, lam, lam_mode, what, sw, fac, h, wlen)) return rc;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    IGX_HIP(hipStreamSynchronize(st));
+    // (a Schwarz preconditioner in use is dropped: selected again by igx_solver_set_precond once every component is set)
+    if (s->precond == IGX_PRECOND_SCHWARZ) s->precond = IGX_PRECOND_NONE;
+    s->block.bsw[comp].clear();
+    if (int rc = upload_replacing(st, h, s->block.d_bkron[comp])) return rc;
+    if (wlen > s->wlen || !s->d_box) {                 // the work buffers and the box fit the largest box of any component
+        wlen = std::max(wlen, s->wlen);
+        (void)hipFree(s->d_box); s->d_box = nullptr;
+        if (int rc = alloc_fastdiag_work(s, wlen)) return rc;
+        IGX_HIP(hipMalloc((void **)&s->d_box, (size_t)wlen * sizeof(double)));
+    }
+    plan_schwarz(sw, fac, s->block.d_bkron[comp], lam_mode);
+    IGX_HIP(hipStreamSynchronize(st));                  // (h goes away)
+    s->block.bsw[comp] = std::move(sw);
     return IGX_OK;
 }
 
@@ -1773,7 +2030,8 @@ extern "C" {
 int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const double *x0, double tol, int maxiter, int check_every,
                      int timed, double *u, igx_solve_info *info)
 {
-    if (!s || (!b && !s->mp) || (!gvals && !s->fixed.empty()) || !u) { set_error("igx_solver_solve: null argument"); return IGX_ERR_ARG; }
+    // (b may be null on a scalar multipatch solver only: the multipatch's summed vector has scalar length)
+    if (!s || (!b && (!s->mp || s->ncomp > 1)) || (!gvals && !s->fixed.empty()) || !u) { set_error("igx_solver_solve: null argument"); return IGX_ERR_ARG; }
     if (!(tol >= 0.0) || maxiter < 0) { set_error("igx_solver_solve: tol must be >= 0 and maxiter >= 0"); return IGX_ERR_ARG; }
     if (int rc = check_values(s, "igx_solver_solve")) return rc;
     if (check_every < 1) check_every = 1;

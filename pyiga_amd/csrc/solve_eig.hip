@@ -653,6 +653,7 @@ int eig_mb_slot(int mb) { return mb == 4 ? 0 : mb == 8 ? 1 : 2; }
 int eig_check(const igx_solver *s, const char *what, bool values)
 {
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (s->mp) {                              // K: the multipatch's current sums, M: the solver's own array
         if (!s->d_mass) { set_error("%s: a multipatch solver needs its mass matrix first (igx_solver_set_mass_d)", what); return IGX_ERR_ARG; }
         return values ? check_values(s, what) : IGX_OK;
@@ -882,6 +883,7 @@ int igx_solver_set_mass_d(igx_solver *s, double *d_M)
 {
     const char *what = "igx_solver_set_mass_d";
     if (!s || !d_M) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (!s->mp) { set_error("%s: needs a multipatch solver (a patch solver takes M with igx_solver_take_values)", what); return IGX_ERR_UNSUPPORTED; }
     if (d_M == s->mp->d_vals) { set_error("%s: the multipatch's own sums cannot be handed over (igx_multipatch_values_d copies them)", what); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(s->ctx->device));

@@ -58,7 +58,8 @@ __device__ __forceinline__ RowHdr row_hdr(const Geom &g, const uint8_t *freem, l
 }
 
 // the NC x NC blocks of a vector-valued form: v[p * NC + q] holds block (p, q) (test component p, trial component q) in the
-// patch's structured layout, or is null (a block that was never assembled: zero)
+// patch's structured layout (a multipatch block solver: in the order of the multipatch's global CSR pattern), or is null (a
+// block that was never assembled: zero)
 struct BlockVals {
     const double *v[9];
 };
@@ -129,6 +130,9 @@ struct BlockState {
     double *d_bkron[3] = {};
     int klo[3][3] = {}, knb[3][3] = {}, kmode[3] = {};   // per component: its box and lam_mode (the eigen-solver's batched plans)
     double *mass = nullptr;                   // the scalar mass matrix of the eigen-solver (igx_solver_take_mass), owned, or null
+    // a multipatch block solver (igx_solver_create_multipatch_block): blk[] are copies of the multipatch's sums (nnz values each),
+    // and per component the Schwarz patches of igx_solver_set_block_schwarz, whose packed factors lie in d_bkron[c]
+    std::vector<SwPatch> bsw[3];
     void release()
     {
         for (double *v : blk) (void)hipFree(v);
@@ -215,7 +219,7 @@ struct igx_solver {
     hipEvent_t ev[6] = {};
     bool have_ev = false;
     int method = IGX_METHOD_CG;
-    int ncomp = 1;                            // components of a block solver (1: scalar)
+    int ncomp = 1;                            // components of a block solver (1: scalar); with mp set: a multipatch block solver
     bool symmetric = false;                   // made as symmetric: CG allowed
     bool parabolic = false;
     igx::BicgState bicg;
@@ -252,11 +256,14 @@ int create_patch_solver(igx_patch *pt, int kind, int ncomp, bool values_now, con
 int init_bicgstab(igx_solver *s, const char *what);
 void free_solver(igx_solver *s);
 int close_call(hipStream_t st, hipEvent_t begin, hipEvent_t end, const char *what, float &total_ms);
+// IGX_ERR_UNSUPPORTED (with igx_last_error) if s is a multipatch block solver, which serves the linear solves only; else IGX_OK
+int refuse_multipatch_block(const igx_solver *s, const char *what);
 // the kernels of solve.hip that the other units need, each behind the one launch its callers made (not synchronised; a launch
 // failure shows in the caller's hipGetLastError)
 void mask_copy(hipStream_t st, const igx_solver *s, const double *x, double *y);          // k_mask_copy: y = free ? x : 0
 // k_diag / k_csr_diag: dinv = free ? 1 / diag(A) : 0 for the matrix `vals` in the solver's layout (a multipatch's CSR pattern, else
-// the patch's structured one; a block solver: the diagonal block of component comp, whose rows of the mask start at comp g.nrows)
+// the patch's structured one; a block solver of either layout: the diagonal block of component comp, whose rows of the mask
+// start at comp times the scalar rows; dinv points at the component's slice)
 void jacobi_diagonal(hipStream_t st, const igx_solver *s, const double *vals, double *dinv, int comp = 0);
 // k_fin: the first nb partial sums of s->d_part added up in their fixed order, read back into *sum (synchronised)
 int sum_partials(hipStream_t st, igx_solver *s, unsigned nb, double *sum);

@@ -318,6 +318,7 @@ int igx_solver_take_values(igx_solver *s, int role)
 {
     const char *what = "igx_solver_take_values";
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
     if (role != IGX_ROLE_MASS && role != IGX_ROLE_OPERATOR) { set_error("%s: unknown role %d", what, role); return IGX_ERR_ARG; }
     if (s->par.pv[role]) { set_error("%s: role %d was taken already", what, role); return IGX_ERR_ARG; }
@@ -345,6 +346,7 @@ int igx_solver_set_dirk(igx_solver *s, int stages, const double *A, double tau)
 {
     const char *what = "igx_solver_set_dirk";
     if (!s || !A) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
     if (!s->par.pv[IGX_ROLE_MASS] || !s->par.pv[IGX_ROLE_OPERATOR]) { set_error("%s: take M and K first (igx_solver_take_values)", what); return IGX_ERR_ARG; }
     double gamma = 0.0;
@@ -374,6 +376,7 @@ int igx_solver_dirk_run(igx_solver *s, const double *f, const double *gvals, con
 {
     const char *what = "igx_solver_dirk_run";
     if (!s || !f || (!gvals && !s->fixed.empty()) || !x0 || !saved) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
     if (nsteps < 1 || save_every < 1) { set_error("%s: nsteps and save_every must be >= 1", what); return IGX_ERR_ARG; }
     if (!(tol >= 0.0) || maxiter < 0) { set_error("%s: tol must be >= 0 and maxiter >= 0", what); return IGX_ERR_ARG; }
@@ -505,12 +508,13 @@ int err_norm(hipStream_t st, igx_solver *s, const Comb &L, const double *x, doub
     return sum_partials(st, s, nbv, sum);                           // (k_fin in its fixed order; synchronised)
 }
 
-bool step_solver_ok(const igx_solver *s, const char *what)
+int step_solver_ok(const igx_solver *s, const char *what)
 {
-    if (!s) { set_error("%s: null solver", what); return false; }
-    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return false; }
-    if (!s->par.pv[IGX_ROLE_MASS] || !s->par.pv[IGX_ROLE_OPERATOR]) { set_error("%s: take M and K first (igx_solver_take_values)", what); return false; }
-    return true;
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
+    if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
+    if (!s->par.pv[IGX_ROLE_MASS] || !s->par.pv[IGX_ROLE_OPERATOR]) { set_error("%s: take M and K first (igx_solver_take_values)", what); return IGX_ERR_ARG; }
+    return IGX_OK;
 }
 
 } // namespace
@@ -522,6 +526,7 @@ int igx_solver_set_stepper(igx_solver *s, int family, int stages, const double *
 {
     const char *what = "igx_solver_set_stepper";
     if (!s || !A) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (!s->parabolic) { set_error("%s: not a parabolic solver (igx_solver_create_parabolic)", what); return IGX_ERR_ARG; }
     double gamma = 0.0;
     if (family == IGX_STEPPER_DIRK) {
@@ -553,7 +558,7 @@ int igx_solver_set_step_precond(igx_solver *s, int precond, const int32_t *box_l
                                 const double *const *lam_raw)
 {
     const char *what = "igx_solver_set_step_precond";
-    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (int rc = step_solver_ok(s, what)) return rc;
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     s->step.step_precond = -1;
@@ -586,7 +591,7 @@ int igx_solver_set_step_precond(igx_solver *s, int precond, const int32_t *box_l
 int igx_solver_step_begin(igx_solver *s, const double *f, const double *gvals, const double *x0)
 {
     const char *what = "igx_solver_step_begin";
-    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (int rc = step_solver_ok(s, what)) return rc;
     if (!f || (!gvals && !s->fixed.empty()) || !x0) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
     if (s->step.family < 0) { set_error("%s: no scheme yet (igx_solver_set_stepper)", what); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(s->ctx->device));
@@ -617,7 +622,7 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
                             igx_step_info *info)
 {
     const char *what = "igx_solver_step_attempt";
-    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (int rc = step_solver_ok(s, what)) return rc;
     if (!s->step.step_live) { set_error("%s: no session (igx_solver_step_begin; igx_solver_dirk_run and igx_solver_set_stepper end one)", what); return IGX_ERR_ARG; }
     if (s->step.step_precond < 0) { set_error("%s: no preconditioner of the session (igx_solver_set_step_precond; igx_solver_set_precond replaces it)", what); return IGX_ERR_ARG; }
     if (!(tau > 0.0) || !std::isfinite(tau)) { set_error("%s: tau must be positive and finite", what); return IGX_ERR_ARG; }
@@ -760,7 +765,7 @@ int igx_solver_step_attempt(igx_solver *s, double tau, double err_tol, double so
 int igx_solver_step_accept(igx_solver *s)
 {
     const char *what = "igx_solver_step_accept";
-    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (int rc = step_solver_ok(s, what)) return rc;
     if (!s->step.step_live || !s->step.have_cand) { set_error("%s: no candidate (a converged igx_solver_step_attempt first)", what); return IGX_ERR_ARG; }
     if (s->step.family == IGX_STEPPER_DIRK) {
         std::swap(s->step.sx, s->step.sy);                                     // x_new = y_s
@@ -774,7 +779,7 @@ int igx_solver_step_accept(igx_solver *s)
 int igx_solver_step_state(igx_solver *s, int which, double *out)
 {
     const char *what = "igx_solver_step_state";
-    if (!step_solver_ok(s, what)) return IGX_ERR_ARG;
+    if (int rc = step_solver_ok(s, what)) return rc;
     if (!out) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
     if (!s->step.step_live) { set_error("%s: no session (igx_solver_step_begin)", what); return IGX_ERR_ARG; }
     if (which != IGX_STEP_STATE && which != IGX_STEP_CANDIDATE) { set_error("%s: unknown vector %d", what, which); return IGX_ERR_ARG; }

@@ -4,8 +4,9 @@
 The dof numbering is the reference's: the non-shared dofs of patch p get ``M_ofs[p]`` plus their rank in tensor-product
 order, shared dof ``sd`` gets ``M_ofs[-1] + sd`` in the order ``join_dofs`` creates them.  The global matrix
 ``sum_p X_p A_p X_p^T`` is formed on the device (``igx_multipatch_*``, pyiga_amd/csrc/multipatch.hip): its pattern once per
-``Multipatch``, then one scatter pass per patch straight from the patch's device values.  Scalar problems only.  The sums can
-also stay on the device and be solved there: ``pyiga_amd.solvers.MultipatchSystem``.
+``Multipatch``, then one scatter pass per patch straight from the patch's device values.  The sums can also stay on the
+device and be solved there: ``pyiga_amd.solvers.MultipatchSystem``.  Vector-valued forms are summed block after block over the
+same pattern (``assemble_vector_system``; solved on the device by ``pyiga_amd.solvers.MultipatchVectorSystem``).
 """
 import ctypes as C
 import itertools
@@ -275,14 +276,17 @@ class Multipatch:
         return self.patch_to_global(p).T
 
     def compute_dirichlet_bcs(self, bdconds):
-        """Dirichlet conditions ``[(patch, bdspec, dir_func), ...]`` as global ``(indices, values)``."""
+        """Dirichlet conditions ``[(patch, bdspec, dir_func), ...]`` as global ``(indices, values)``.  A vector-valued `dir_func`
+        gives blocked global indices: the local dof ``c * N_p + i`` of component c becomes ``c * numdofs + l2g_p[i]``, the
+        numbering of :meth:`assemble_vector_system` and ``solvers.MultipatchVectorSystem``."""
         bcs, p2g = [], {}
         for p, bdspec, g in bdconds:
             kvs, geo = self.patches[p]
             idx, vals = compute_dirichlet_bc(kvs, geo, bdspec, g)
             if p not in p2g:
                 p2g[p] = self.patch_to_global_idx(p)
-            bcs.append((p2g[p][idx], vals))
+            comp, loc = np.divmod(idx, self.N[p])
+            bcs.append((comp * self.numdofs + p2g[p][loc], vals))
         return combine_bcs(bcs)
 
     def error_norms(self, u, exact, grad_exact=None):
@@ -400,6 +404,106 @@ class Multipatch:
         b = np.empty(self.numdofs)
         _lib.check(_lib.load().igx_multipatch_download(h, _lib.dptr(data), _lib.dptr(b)), 'igx_multipatch_download')
         A = scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(self.numdofs, self.numdofs))
+        return A.asformat(format), b
+
+    # -- vector-valued forms: nc x nc scalar blocks over the one global pattern
+    def _vector_assemblers(self, problem, bfuns, args, who):
+        """``(nc, assemblers, args)`` of the vector-valued bilinear form `problem`: the checks of
+        ``solvers._vector_components`` (ValueError before any device work), then one ``FormAssembler`` per patch with that
+        patch's ``geo``.  The caller closes their patches."""
+        from . import solvers
+        from .form_assemblers import FormAssembler
+        args = {k: v for k, v in dict(args or {}).items() if k != 'geo'}
+        kvs0, geo0 = self.patches[0]
+        nc = solvers._vector_components(problem, tuple(kvs0), dict(args, geo=geo0), bfuns, who=who)
+        asms = []
+        try:
+            for kvs, geo in self.patches:
+                asms.append(FormAssembler(tuple(kvs), geo, problem, bfuns=bfuns, inputs=args))
+        except Exception:
+            for a in asms:
+                a.patch.close()
+            raise
+        return nc, asms, args
+
+    def _sum_vector_blocks(self, assemblers, nc, on_block):
+        """The block loop of a vector-valued form, blocks outermost: for every block (p, q) present on any patch the sums are
+        restarted, every patch scatters its scalar block -- a patch whose table for this block is absent scatters zeros, since
+        ``igx_multipatch_zero`` clears the interface rows only and the interior rows would keep the previous block's values --
+        and ``on_block(p, q, handle)`` takes the sums.  Returns ``present[p][q]``; a block absent on every patch is never
+        summed.  Restarting the sums makes every ``MultipatchSystem`` over this multipatch stale."""
+        from .form_assemblers import _full_table
+        lib = _lib.load()
+        h = self._device()
+        self.pattern()
+        absent = lambda tab: all(e is None for row in tab for e in row)          # noqa: E731
+        present = [[False] * nc for _ in range(nc)]
+        for p in range(nc):
+            for q in range(nc):
+                tabs = [asm._table[p][q] for asm in assemblers]
+                if all(absent(t) for t in tabs):
+                    continue
+                _lib.check(lib.igx_multipatch_zero(h), 'igx_multipatch_zero')
+                for k, (asm, tab) in enumerate(zip(assemblers, tabs)):
+                    if absent(tab):
+                        zeros = np.zeros(int(asm.patch.nnz))
+                        _lib.check(lib.igx_multipatch_scatter_host(h, k, _lib.dptr(zeros)), 'igx_multipatch_scatter_host')
+                        continue
+                    asm.patch.set_form(_full_table(tab, len(asm.kvs[0])))
+                    asm.patch.assemble('form', to_host=False)
+                    _lib.check(lib.igx_multipatch_scatter_patch(h, k, asm.patch.handle), 'igx_multipatch_scatter_patch')
+                on_block(p, q, h)
+                present[p][q] = True
+        return present
+
+    def _vector_rhs(self, rhs, test, nc, args):
+        """The blocked global right-hand side of ``nc * numdofs`` entries: `rhs` a linear form string in the test function `test`
+        (assembled per patch with ``bfuns=[(test, nc)]``, ``layout='blocked'`` and summed on the host with
+        ``patch_to_global_idx`` per component), a vector of that length, or a scalar."""
+        from . import assemble as asm_mod
+        n = self.numdofs
+        if isinstance(rhs, str):
+            b = np.zeros(nc * n)
+            for p, (kvs, geo) in enumerate(self.patches):
+                bp = np.asarray(asm_mod.assemble(rhs, tuple(kvs), args=dict(args, geo=geo), bfuns=[(test, nc)], layout='blocked'))
+                bp = bp.reshape(nc, self.N[p])
+                l2g = self.patch_to_global_idx(p)
+                for c in range(nc):
+                    np.add.at(b, c * n + l2g, bp[c])
+            return b
+        if np.ndim(rhs) == 0:
+            return np.full(nc * n, float(rhs))
+        b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
+        if b.size != nc * n:
+            raise ValueError('right-hand side has %d entries, the space %d x %d' % (b.size, nc, n))
+        return b
+
+    def assemble_vector_system(self, problem, rhs, bfuns, args=None, format='csr', **kwargs):
+        """``(A, b)`` of the vector-valued bilinear form `problem` (``bfuns=[('u', nc), ('v', nc)]``, nc = 2 or 3) and the
+        right-hand side `rhs` (a linear form string in the test function, a vector or a scalar) over all patches, in the blocked
+        layout: ``nc * numdofs`` entries, component-major, every component with the scalar numbering of the multipatch.  Block
+        (p, q) is ``sum_patch X A^patch_pq X^T``, summed on the device over the one global pattern, block after block; the
+        pattern keeps entries whose values sum to 0.  Restarts the device sums (a ``MultipatchSystem`` over them goes stale)."""
+        from . import solvers
+        args = dict(args or {})
+        args.update(kwargs)
+        nc, asms, args = self._vector_assemblers(problem, bfuns, args, 'Multipatch.assemble_vector_system')
+        n = self.numdofs
+        try:
+            indptr, indices = self.pattern()
+            blocks = [[None] * nc for _ in range(nc)]
+
+            def download(p, q, h):
+                data = np.empty(indices.shape[0])
+                _lib.check(_lib.load().igx_multipatch_download(h, _lib.dptr(data), None), 'igx_multipatch_download')
+                blocks[p][q] = scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(n, n))
+            self._sum_vector_blocks(asms, nc, download)
+        finally:
+            for a in asms:
+                a.patch.close()
+        blocks = [[B if B is not None else scipy.sparse.csr_matrix((n, n)) for B in row] for row in blocks]
+        A = scipy.sparse.bmat(blocks, format='csr')
+        b = self._vector_rhs(rhs, solvers._test_function_name(problem, bfuns), nc, args)
         return A.asformat(format), b
 
     def _sum_system(self, problem, rhs, args, symmetric, format, layout, kwargs, on_assembler=None):

@@ -24,6 +24,10 @@ lets ``PatchSystem`` and ``MultipatchSystem`` solve by BiCGStab; ``MultipatchSys
 elasticity, grad-div, ...): the nc x nc scalar blocks are assembled on the device and stay there; a block SpMV and a
 block-diagonal fast-diagonalization preconditioner serve CG or BiCGStab.
 
+``MultipatchVectorSystem(MP, problem, rhs, bcs, bfuns=[('u', nc), ('v', nc)])``: vector-valued forms on a multipatch (elasticity
+on a multi-patch solid): the nc x nc blocks are summed over the one global pattern and solved with one block CSR SpMV per
+product, Jacobi or a block-diagonal additive Schwarz preconditioner.
+
 ``ParabolicSystem(kvs, geo, rhs, bcs, problem=None)``: the heat equation ``M u' = f - K u`` (or any device-valued form as K) of
 one patch, integrated on the device by a DIRK scheme with constant steps (``integrate``; the reference's ``crank_nicolson``,
 ``sdirk3``, ..., pyiga/solvers.py:366-473).  Every stage solves with ``C = M + tau gamma K``; M, K and C stay on the device, and
@@ -444,32 +448,32 @@ class FormSystem(PatchSystem):
 # Vector-valued Dirichlet problems of one patch on the device
 ################################################################################
 
-def _vector_components(problem, kvs, args, bfuns):
-    """The number of components of a vector-valued volume form that VectorFormSystem solves; ValueError, before any device work,
-    for anything else (no ``geo``, a surface or boundary form, not bilinear, trial and test components that differ, a scalar form,
-    more than three components)."""
+def _vector_components(problem, kvs, args, bfuns, who='VectorFormSystem'):
+    """The number of components of a vector-valued volume form that `who` (VectorFormSystem, MultipatchVectorSystem, ...) solves;
+    ValueError, before any device work, for anything else (no ``geo``, a surface or boundary form, not bilinear, trial and test
+    components that differ, a scalar form, more than three components)."""
     from . import tforms
     if not isinstance(problem, str):
-        raise ValueError('VectorFormSystem needs a form string, not %r' % (problem,))
+        raise ValueError('%s needs a form string, not %r' % (who, problem))
     geo = args.get('geo')
     if geo is None:
         raise ValueError("required input parameter 'geo' missing")
     if getattr(geo, 'dim', len(kvs)) != len(kvs) or re.search(r'\bds\b', problem):
-        raise ValueError('VectorFormSystem solves volume forms (dx), not surface or boundary forms: %r' % (problem,))
+        raise ValueError('%s solves volume forms (dx), not surface or boundary forms: %r' % (who, problem))
     try:
         bf = tforms.normalise_bfuns(problem, bfuns)
     except NotImplementedError as e:
-        raise ValueError('VectorFormSystem: %s' % e)
+        raise ValueError('%s: %s' % (who, e))
     if len(bf) != 2:
-        raise ValueError('VectorFormSystem needs a bilinear form (trial and test function), not arity %d: %r' % (len(bf), problem))
+        raise ValueError('%s needs a bilinear form (trial and test function), not arity %d: %r' % (who, len(bf), problem))
     (_, ncu), (_, ncv) = bf
     if ncu != ncv:
-        raise ValueError('VectorFormSystem: trial and test functions have %d and %d components (mixed systems are not '
-                         'supported)' % (ncu, ncv))
+        raise ValueError('%s: trial and test functions have %d and %d components (mixed systems are not '
+                         'supported)' % (who, ncu, ncv))
     if ncu == 1:
-        raise ValueError('VectorFormSystem: %r is a scalar form: solve it with FormSystem' % (problem,))
+        raise ValueError('%s: %r is a scalar form: solve it with FormSystem' % (who, problem))
     if ncu not in (2, 3):
-        raise ValueError('VectorFormSystem solves forms of 2 or 3 components, not %d' % ncu)
+        raise ValueError('%s solves forms of 2 or 3 components, not %d' % (who, ncu))
     return ncu
 
 
@@ -1049,6 +1053,124 @@ class MultipatchSystem(_DeviceSystem):
         if precond == 'mg':
             self.info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
         return u
+
+
+class MultipatchVectorSystem(_DeviceSystem):
+    """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, for a vector-valued form (``bfuns=[('u', nc),
+    ('v', nc)]``, nc = 2 or 3: linear elasticity, grad-div, ...) on the multipatch `MP`, summed and solved on the device
+    (DESIGN.md section 28).
+
+    Vectors have ``nc * MP.numdofs`` entries, component-major; every component uses the scalar numbering and joins of `MP`.
+    Block (p, q) is ``sum_patch X A^patch_pq X^T``: the blocks are summed one after the other in the multipatch's device sums
+    (every patch assembles its scalar block and scatters it) and copied into the block solver of
+    ``igx_solver_create_multipatch_block``, which multiplies by all of them in one block SpMV over the global pattern.
+    `method`: 'auto' is CG when the coefficient tables of every patch are symmetric (``symmetric``), else BiCGStab; 'cg' on a
+    non-symmetric form raises ValueError.  `rhs`: a linear form string in the test function, a vector of ``nc * numdofs``
+    entries, or a scalar.  `bcs`: ``(indices, values)`` in the blocked numbering, as ``MP.compute_dirichlet_bcs`` gives them for
+    a vector-valued ``dir_func``.
+
+    Constructing the system restarts the sums of `MP`: a ``MultipatchSystem`` made over them before goes stale (its solves
+    raise), as after ``MP.assemble_system``.  The system owns copies of its blocks, so a later ``MP.assemble_system`` does not
+    disturb it; it reads the pattern of `MP`, and ``MP.close()`` destroys its device solver.
+    """
+
+    PRECONDS = _lib.MPVEC_PRECONDS
+    FACTORED = 'schwarz'
+
+    def __init__(self, MP, problem, rhs, bcs=None, bfuns=None, args=None, method='auto', **kwargs):
+        if method != 'auto':
+            _check_method(method)
+        self.MP = MP
+        args = dict(args or {})
+        args.update(kwargs)
+        nc, asms, args = MP._vector_assemblers(problem, bfuns, args, 'MultipatchVectorSystem')
+        try:
+            self.ncomp = nc
+            self.symmetric = all(symmetric_block_tables(a._table) for a in asms)
+            if method == 'auto':
+                method = 'cg' if self.symmetric else 'bicgstab'
+            elif method == 'cg' and not self.symmetric:
+                raise ValueError('MultipatchVectorSystem: CG needs a symmetric form; the coefficient tables of %r are not '
+                                 "symmetric: method='bicgstab'" % (problem,))
+            self.N = MP.numdofs
+            self.n = nc * self.N
+            self.b = MP._vector_rhs(rhs, _test_function_name(problem, bfuns), nc, args)
+            h = MP._device()
+            self._ctx = MP._ctx
+            initial = 'cg' if self.symmetric else 'bicgstab'
+            self._attach('igx_solver_create_multipatch_block', (h, nc, 1 if self.symmetric else 0), bcs, method, initial)
+            MP._solvers.add(self)
+            lib = _lib.load()
+            self.present = MP._sum_vector_blocks(
+                asms, nc, lambda p, q, _h: _lib.check(lib.igx_solver_take_multipatch_block(self.handle, p, q),
+                                                      'igx_solver_take_multipatch_block'))
+        finally:
+            for a in asms:
+                a.patch.close()
+
+    def _drop_owner(self):
+        MP = getattr(self, 'MP', None)
+        if MP is not None:
+            MP._solvers.discard(self)
+
+    def set_precond(self, precond):
+        if precond in ('mg', 'kron'):
+            raise ValueError('MultipatchVectorSystem has no %r preconditioner: \'jacobi\', \'schwarz\' or None' % (precond,))
+        _DeviceSystem.set_precond(self, precond)
+
+    def schwarz_setup(self):
+        """Per component ``(boxes, U, lam, mode)`` of the block-diagonal Schwarz preconditioner (host set-up): the boxes of
+        ``schwarz_boxes`` on that component's fixed dofs and the stiffness factors of ``schwarz_factors`` (a floating patch of a
+        component gets the ``sigma / d`` shift)."""
+        MP = self.MP
+        shapes = [tuple(kv.numdofs for kv in kvs) for kvs, _ in MP.patches]
+        maps = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
+        kvs_list = [tuple(kvs) for kvs, _ in MP.patches]
+        idx = self.bc_indices
+        out = []
+        for c in range(self.ncomp):
+            fixed = idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N
+            boxes = schwarz_boxes(shapes, maps, fixed)
+            U, lam, mode = schwarz_factors(kvs_list, boxes, 'stiffness')
+            out.append((boxes, U, lam, mode))
+        return out
+
+    def _set_factors(self, h):
+        lib = _lib.load()
+        slots = lambda per_patch, fill: [v[k] if k < len(v) else fill for v in per_patch for k in range(3)]
+        for c, (boxes, U, lam, mode) in enumerate(self.schwarz_setup()):
+            lo, hi, Up, Lp = _box_args(slots([b[0] for b in boxes], 0), slots([b[1] for b in boxes], 0), slots(U, None),
+                                       slots(lam, None))
+            _lib.check(lib.igx_solver_set_block_schwarz(h, c, lo, hi, Up, Lp, mode), 'igx_solver_set_block_schwarz')
+        _lib.check(lib.igx_solver_set_precond(h, _lib.IGX_PRECOND_SCHWARZ, None, None, None, None, 0), 'igx_solver_set_precond')
+        self._factors_set = True
+
+    def matrix(self):
+        """The ``nc n x nc n`` matrix the system solves with (fixed rows and columns included), downloaded block by block from
+        the solver: scipy CSR in the blocked layout.  An absent block has no entries; a present one keeps the whole pattern."""
+        h = self._live()
+        indptr, indices = self.MP.pattern()
+        lib = _lib.load()
+        N = self.N
+        blocks = []
+        for p in range(self.ncomp):
+            row = []
+            for q in range(self.ncomp):
+                if not self.present[p][q]:
+                    row.append(scipy.sparse.csr_matrix((N, N)))
+                    continue
+                data = np.empty(indices.shape[0])
+                _lib.check(lib.igx_solver_download_multipatch_block(h, p, q, _lib.dptr(data)), 'igx_solver_download_multipatch_block')
+                row.append(scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(N, N)))
+            blocks.append(row)
+        return scipy.sparse.bmat(blocks, format='csr')
+
+    def solve(self, tol=1e-8, maxiter=1000, precond='jacobi', x0=None, check_every=1, timed=False):
+        """CG or BiCGStab (``method``) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the blocked global solution vector of
+        ``nc * numdofs`` entries (the Dirichlet values included).  `precond`: 'jacobi' (the diagonals of the diagonal blocks),
+        'schwarz' (per component the additive Schwarz preconditioner of ``MultipatchSystem``: one fast-diagonalization solve of
+        the Laplacian per patch and component) or None; 'mg' and 'kron' raise ValueError."""
+        return self._solve(self.b, tol, maxiter, precond, x0, check_every, timed)
 
 
 ################################################################################

@@ -18,9 +18,12 @@ for line in out.splitlines():
         cur = re.sub(r'\(.*', '', cur.replace('(anonymous namespace)::', '').replace('void ', ''))
         rows[cur] = {}
         continue
-    m = re.search(r'remark: \s*(SGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)', line)
+    m = re.search(r'remark: \s*((?:Total)?SGPRs|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|'
+                  r'LDS Size \[bytes/block\]): (\d+)', line)
     if m and cur:
-        rows[cur][m.group(1).split(' ')[0]] = int(m.group(2))
-print('%-60s %5s %5s %8s %5s' % ('kernel', 'VGPR', 'SGPR', 'scratch', 'occ'))
+        key = m.group(1)
+        rows[cur][key if key.endswith('Spill') else key.replace('Total', '').split(' ')[0]] = int(m.group(2))
+print('%-60s %5s %5s %7s %7s %8s %5s' % ('kernel', 'VGPR', 'SGPR', 'Sspill', 'Vspill', 'scratch', 'occ'))
 for k, v in rows.items():
-    print('%-60s %5d %5d %8d %5d' % (k[:60], v.get('VGPRs', -1), v.get('SGPRs', -1), v.get('ScratchSize', -1), v.get('Occupancy', -1)))
+    print('%-60s %5d %5d %7d %7d %8d %5d' % (k[:60], v.get('VGPRs', -1), v.get('SGPRs', -1), v.get('SGPRs Spill', -1),
+                                             v.get('VGPRs Spill', -1), v.get('ScratchSize', -1), v.get('Occupancy', -1)))
