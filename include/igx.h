@@ -136,7 +136,7 @@ typedef struct {
 typedef struct {
     float total_ms;
     float fields_ms, stage0_ms, stage1_ms, final_ms, entry_ms;
-    int32_t algo_used;                 /* IGX_ALGO_ENTRYWISE / IGX_ALGO_SUMFACT; 3 after igx_load_vector (total_ms = its contractions), 4 / 5: igx_patch_eval_spline_d / _exprs_inputs_d, 6: igx_patch_quad_sums_d / _error_sums_d */
+    int32_t algo_used;                 /* IGX_ALGO_ENTRYWISE / IGX_ALGO_SUMFACT; 3 after igx_load_vector (total_ms = its contractions), 4 / 5: igx_patch_eval_spline_d / _exprs_inputs_d, 6: igx_patch_quad_sums_d / _error_sums_d, 7: igx_patch_add_face / _host (total_ms = the add) */
     int32_t n_launches;
 } igx_timing;
 
@@ -390,6 +390,25 @@ int igx_fields(igx_patch *patch, int kind, double *out, int64_t *shape4);
    matrices (pyiga/assemble.py:125-190,236-282), extended to separable geometry maps. */
 int igx_assemble_kron3(igx_patch *patch3, igx_patch *patch2, int kind, const double *m0, const double *k0, double *data_out);
 
+/* --- boundary terms (Robin, impedance): A[bd, bd] += R on the device ----------------------------------
+   Adds the matrix of a boundary integral over the side (axis, side) of the patch -- side 0: the dofs with i_axis = 0, side 1:
+   those with i_axis = N_axis - 1 -- to the values the patch holds on the device.  The face space is the tensor product of the
+   patch's other axes in their order; face entry (It, Jt) lands on volume entry (I, J), I and J being It and Jt with the side's
+   index inserted at `axis`.  Every target position is arithmetic on the per-axis tables (no index arrays, no search); the add
+   is a plain read-add-write (no atomics: within one face no two entries share a position), and successive calls run in stream
+   order, so where two faces meet the value is ((a + r_1) + r_2) in the order of the calls.
+   `face`: the (d-1)-dimensional patch of the face space holding its values on the device (igx_assemble(face, kind, algo, NULL));
+   a 3D volume takes a 2D face patch.  The _host variant takes the nvals values of the face matrix in the canonical CSR order of
+   the face space (rows of the face dofs, per row the columns jlo .. jhi of every face axis) and serves the 1D faces of 2D
+   patches and any face matrix formed on the host.
+   IGX_ERR_ARG: the patch holds no values (values_kind < 0), axis or side out of range, a face whose degrees, dof counts or
+   per-axis column ranges differ from those of the patch's other axes, a wrong nvals.  IGX_ERR_UNSUPPORTED: a row slab or span
+   box (either patch).  The kind of the values (values_kind) is unchanged, so igx_solver_create* and igx_solver_take_values accept
+   them afterwards; a solver that ALREADY reads the patch's values must be told with igx_solver_values_changed.
+   <- A[bd_dofs[:, None], bd_dofs] += R  on the host matrix */
+int igx_patch_add_face(igx_patch *patch, int axis, int side, const igx_patch *face);
+int igx_patch_add_face_host(igx_patch *patch, int axis, int side, const double *vals, int64_t nvals);
+
 /* Opt-in buffer placement (environment IGX_PLACEMENT_TRIES=n at igx_patch_create, 3D symmetric forms): the first
    igx_assemble allocates up to n candidate buffers for the CSR values, times the mirror pass of the patch on each and keeps
    the fastest (the pass follows where the driver put the buffer physically: +-10 % between allocations, stable over the life
@@ -458,6 +477,14 @@ int  igx_multipatch_download(const igx_multipatch *mp, double *vals, double *vec
 /* The nnz values of the current sums, in the order of igx_multipatch_pattern, copied device to device into the caller's buffer
    (nnz doubles of the same context): what a second matrix over the same pattern is made of (igx_solver_set_mass_d). */
 int  igx_multipatch_values_d(const igx_multipatch *mp, double *d_out);
+/* igx_patch_add_face[_host] on the global sums: the face matrix of side (axis, side) of patch p is added at the positions its
+   volume entries were scattered to (the patch's row plan: position + delta for rows stored directly, the position array
+   otherwise).  Call it after the scatters of the current sum: read-add-write, in stream order (atomic adds only where a map
+   l2g[p] is not injective).  Before patch p was scattered into the current sum (since igx_multipatch_zero): IGX_ERR_ARG, because
+   the scatter's plain stores would overwrite the add.  Other errors as igx_patch_add_face.  Add before igx_solver_create_multipatch: a
+   solver made earlier has gathered its Jacobi diagonal from the older values. */
+int  igx_multipatch_add_face(igx_multipatch *mp, int p, int axis, int side, const igx_patch *face);
+int  igx_multipatch_add_face_host(igx_multipatch *mp, int p, int axis, int side, const double *vals, int64_t nvals);
 
 /* --- Dirichlet problems of one patch on the device: preconditioned CG (pyiga/assemble.py:571-652, pyiga/solvers.py:17-42) ----
    The solver reads the CSR values that the patch holds on the device after an assembly with data_out = NULL, in the patch's own

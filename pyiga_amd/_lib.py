@@ -228,6 +228,10 @@ SYMBOLS = [
     ('igx_multipatch_scatter_vector', C.c_int, [C.c_void_p, C.c_int, _dp]),
     ('igx_multipatch_download', C.c_int, [C.c_void_p, _dp, _dp]),
     ('igx_multipatch_values_d', C.c_int, [C.c_void_p, C.c_void_p]),
+    ('igx_patch_add_face', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ('igx_patch_add_face_host', C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int64]),
+    ('igx_multipatch_add_face', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ('igx_multipatch_add_face_host', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int64]),
     ('igx_solver_create', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
     ('igx_solver_create_general', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
     ('igx_solver_set_method', C.c_int, [C.c_void_p, C.c_int]),

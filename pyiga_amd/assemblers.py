@@ -270,6 +270,20 @@ class DevicePatch:
                                             _lib.dptr(out) if to_host else None), 'igx_assemble')
         return out
 
+    def add_face(self, axis, side, face):
+        """Add the matrix of a boundary integral over the side ``(axis, side)`` to the values this patch holds on the device
+        (after ``assemble(kind, to_host=False)``).  `face`: the ``DevicePatch`` of the face space holding
+        its values on the device (``igx_patch_add_face``: 3D patches), or the host values of the face matrix in the canonical CSR
+        order of the face space (``igx_patch_add_face_host``; ``boundary_terms.face_values``).  Add before a solver is created
+        over the values or takes them."""
+        lib = _lib.load()
+        if isinstance(face, DevicePatch):
+            _lib.check(lib.igx_patch_add_face(self.handle, int(axis), int(side), face.handle), 'igx_patch_add_face')
+        else:
+            vals = _lib.f64(face).ravel()
+            _lib.check(lib.igx_patch_add_face_host(self.handle, int(axis), int(side), _lib.dptr(vals), C.c_int64(vals.size)),
+                       'igx_patch_add_face_host')
+
     def assemble_kron(self, kind, patch2, m0, k0=None, to_host=True):
         """Mass / stiffness values of this 3D patch from the 2D patch of its cross-section and the weighted 1D matrices of
         axis 0 (igx_assemble_kron3: separable geometry, see ``geometry.split_axis0`` and ``assemble.separable_terms``)."""

@@ -418,6 +418,7 @@ namespace igx {
 struct RowInfo {                             // per local row of a patch: the scatter plan (16 bytes)
     int32_t kstart, len, base, mode;         // base: delta (DIRECT) or offset of the row in the compacted position array
 };
+enum { MODE_DIRECT = 0, MODE_STORE = 1, MODE_RMW = 2, MODE_ATOMIC = 3 };   // RowInfo::mode: how the row's values reach the sums
 } // namespace igx
 
 struct igx_multipatch {
@@ -441,6 +442,13 @@ struct igx_multipatch {
         int32_t *d_l2g = nullptr;
         igx::RowInfo *d_info = nullptr;
         int32_t *d_cpos = nullptr;
+        // per-axis tables of the patch's value layout (igx_multipatch_add_face): host copies and one device allocation
+        // jlo | jhi | rp per axis, axis k at d_tab + tab_pos[k][0 .. 2]
+        std::vector<int> jlo[3], jhi[3], rp[3];
+        int p[3] = {0, 0, 0};
+        int *d_tab = nullptr;
+        size_t tab_pos[3][3] = {};
+        unsigned long long scattered = ~0ULL;  // the generation of the sums that last received this patch's values
     };
     std::vector<Patch> pp;
 };

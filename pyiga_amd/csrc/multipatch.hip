@@ -27,7 +27,6 @@ namespace {
 
 constexpr int WAVE = 64;
 constexpr int SORT_TILE = 1024;          // longest raw global row sorted in the LDS of one wave; longer rows: k_sort_long
-enum { MODE_DIRECT = 0, MODE_STORE = 1, MODE_RMW = 2, MODE_ATOMIC = 3 };
 
 
 __device__ __forceinline__ unsigned long long lanemask_lt(int lane) { return (1ull << lane) - 1ull; }
@@ -311,7 +310,7 @@ void mp_free(igx_multipatch *mp)
 {
     (void)hipSetDevice(mp->ctx->device);
     (void)hipStreamSynchronize(mp->ctx->stream);
-    for (auto &p : mp->pp) { (void)hipFree(p.d_l2g); (void)hipFree(p.d_info); (void)hipFree(p.d_cpos); }
+    for (auto &p : mp->pp) { (void)hipFree(p.d_l2g); (void)hipFree(p.d_info); (void)hipFree(p.d_cpos); (void)hipFree(p.d_tab); }
     (void)hipFree(mp->d_indptr); (void)hipFree(mp->d_indices); (void)hipFree(mp->d_contrib);
     (void)hipFree(mp->d_vals); (void)hipFree(mp->d_vec); (void)hipFree(mp->d_stage);
     delete mp;
@@ -492,6 +491,7 @@ int run_scatter(igx_multipatch *mp, int p, const double *d_src)
     IGX_HIP(hipGetLastError());
     IGX_HIP(hipStreamSynchronize(st));     // (host staging buffer and the source patch may be reused / freed after the call)
     mp->scattered = mp->generation;
+    mp->pp[p].scattered = mp->generation;
     return IGX_OK;
 }
 
@@ -524,7 +524,11 @@ igx_multipatch *igx_multipatch_create(igx_ctx *ctx, int npatches, igx_patch *con
         P.n = (int)patches[p]->nrows_total;
         P.nnz = patches[p]->nnz;
         P.dim = patches[p]->dim;
-        for (int k = 0; k < P.dim; ++k) P.N[k] = patches[p]->ax[k].N;
+        for (int k = 0; k < P.dim; ++k) {
+            const igx::Axis &A = patches[p]->ax[k];
+            P.N[k] = A.N; P.p[k] = A.p;
+            P.jlo[k] = A.jlo; P.jhi[k] = A.jhi; P.rp[k] = A.rp;
+        }
         std::vector<int32_t> s(l2g[p], l2g[p] + P.n);
         for (int32_t g : s)
             if (g < 0 || g >= nglobal) { set_error("igx_multipatch_create: patch %d maps a dof to %d, outside [0, %lld)", p, g, (long long)nglobal); delete mp; return nullptr; }

@@ -77,9 +77,11 @@ class FormAssembler:
     plugin interface for such forms: ``arity``, ``kvs``, ``num_components()``, ``multi_blocks()``, ``assemble_vector()``
     plus ``assemble(format, layout)``, which ``assemble.assemble_entries`` calls."""
 
-    def __init__(self, kvs, geo, form, bfuns=None, inputs=None, boundary=None, device=None):
+    def __init__(self, kvs, geo, form, bfuns=None, inputs=None, boundary=None, device=None, lazy_patch=False):
         kvs = tuple(kvs)
         self.kvs = (kvs, kvs)
+        self._lazy_patch = lazy_patch          # boundary forms of 3D patches: the face patch is made by ensure_patch(), so that the
+                                               # tables can be inspected before any device work (solvers.BoundaryTerm)
         self._geo = geo
         self._form = form
         self._device = device
@@ -212,8 +214,15 @@ class FormAssembler:
         else:
             self._table = [to_param1(jet) for jet in table]
         self.patch = None
-        if d == 3:
-            self.patch = DevicePatch(tkvs, _identity_geo(tkvs), device=self._device, nqp=self.nqp)
+        if d == 3 and not self._lazy_patch:
+            self.ensure_patch()
+
+    def ensure_patch(self):
+        """The face patch of a boundary form of a 3D patch (made with the assembler unless `lazy_patch`); None for the 1D faces
+        of 2D patches, whose matrices are formed on the host."""
+        if self.patch is None and self.boundary is not None and len(self._tkvs) == 2:
+            self.patch = DevicePatch(self._tkvs, _identity_geo(self._tkvs), device=self._device, nqp=self.nqp)
+        return self.patch
 
     # ---- the reference's interface
     def num_components(self):

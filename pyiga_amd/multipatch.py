@@ -390,15 +390,31 @@ class Multipatch:
         vals[pos] = A.data
         return vals
 
-    def assemble_system(self, problem, rhs, args=None, bfuns=None, symmetric=False, format='csr', layout='blocked', **kwargs):
+    def _boundary_terms(self, boundary_terms, rhs, args, kwargs, method=None, who='Multipatch.assemble_system'):
+        """``{patch index: boundary_terms.PatchTerms}`` of the ``BoundaryTerm`` list, checked and set up on the host (ValueError
+        before any device work); a term with a right-hand side needs the sums to have one (`rhs` not None)."""
+        from . import boundary_terms as bt
+        terms = bt.check_terms(boundary_terms, [len(kvs) for kvs, _ in self.patches], multipatch=True, method=method, who=who)
+        if rhs is None and any(t.rhs is not None for t in terms):
+            raise ValueError('%s: a boundary term has a right-hand side, but the sums are formed without a load vector (rhs=None)' % who)
+        out = {}
+        for p in sorted({t.patch for t in terms}):
+            kvs, geo = self.patches[p]
+            out[p] = bt.PatchTerms(tuple(kvs), geo, [t for t in terms if t.patch == p], method=method, who=who)
+        return out
+
+    def assemble_system(self, problem, rhs, args=None, bfuns=None, symmetric=False, format='csr', layout='blocked',
+                        boundary_terms=None, **kwargs):
         """System matrix and right-hand side ``(A, b)`` of the bilinear form `problem` and the linear functional `rhs` over
         all patches (arguments as for :func:`pyiga_amd.assemble.assemble`).  Each patch is assembled in turn and scattered
         into the global sums on the device -- from the patch's device values when the assembler leaves them there -- and
         its device memory is freed before the next one.  The pattern keeps entries whose values sum to 0.  `rhs` None: the
-        matrix alone, ``b`` is 0."""
+        matrix alone, ``b`` is 0.  `boundary_terms`: ``solvers.BoundaryTerm`` objects with their patch index; their face
+        matrices are added to the sums on the device after the scatters, their face loads to the patches' load vectors."""
         if bfuns is not None:
             raise NotImplementedError('vector-valued multipatch problems are not supported')
-        h = self._sum_system(problem, rhs, args, symmetric, format, layout, kwargs)
+        terms = self._boundary_terms(boundary_terms, rhs, args, kwargs)
+        h = self._sum_system(problem, rhs, args, symmetric, format, layout, kwargs, boundary_terms=terms)
         indptr, indices = self.pattern()
         data = np.empty(indices.shape[0])
         b = np.empty(self.numdofs)
@@ -506,11 +522,22 @@ class Multipatch:
         b = self._vector_rhs(rhs, solvers._test_function_name(problem, bfuns), nc, args)
         return A.asformat(format), b
 
-    def _sum_system(self, problem, rhs, args, symmetric, format, layout, kwargs, on_assembler=None):
+    def _sum_system(self, problem, rhs, args, symmetric, format, layout, kwargs, on_assembler=None, boundary_terms=None):
         """Restart the device sums and add every patch's matrix and right-hand side to them (the loop of
         :meth:`assemble_system`); returns the handle, the sums left on the device.  `on_assembler(p, asm)` is called with each
-        patch's assembler before it assembles.  `rhs` None: the matrices alone (an eigenproblem has no load vector)."""
+        patch's assembler before it assembles.  `rhs` None: the matrices alone (an eigenproblem has no load vector).
+        `boundary_terms` (:meth:`_boundary_terms`): the face loads join ``b_p`` before it is scattered (the scatter overwrites
+        singly-owned entries), the face matrices are added to the sums after the patch loop; their face patches are closed."""
+        boundary_terms = boundary_terms or {}
+        try:
+            return self._sum_patches(problem, rhs, args, symmetric, format, layout, kwargs, on_assembler, boundary_terms)
+        finally:
+            for t in boundary_terms.values():
+                t.close()
+
+    def _sum_patches(self, problem, rhs, args, symmetric, format, layout, kwargs, on_assembler, boundary_terms):
         from . import assemble as asm_mod
+        from . import boundary_terms as bt
         from .assemblers import _DeviceAssembler, _ParametricFormAssembler
         lib = _lib.load()
         h = self._device()
@@ -553,6 +580,9 @@ class Multipatch:
             b_p = _lib.f64(np.asarray(asm_mod.assemble(rhs, kvs, args=args, symmetric=symmetric, format=format, layout=layout)).ravel())
             if b_p.shape[0] != self.N[p]:
                 raise ValueError('patch %d: right-hand side has %d entries, expected %d' % (p, b_p.shape[0], self.N[p]))
+            if p in boundary_terms and boundary_terms[p].has_rhs:
+                b_p = boundary_terms[p].add_loads(b_p.copy())
             _lib.check(lib.igx_multipatch_scatter_vector(h, p, _lib.dptr(b_p)), 'igx_multipatch_scatter_vector')
+        bt.add_to_multipatch(self, h, boundary_terms)
         self.timings.update(assemble_ms=t_asm, scatter_ms=t_sc)
         return h

@@ -54,6 +54,8 @@ import scipy.sparse.linalg
 
 from . import _lib
 from . import assemblers
+from . import boundary_terms as _bt
+from .boundary_terms import BoundaryTerm
 from .operators import DeviceArray, DeviceKron, _dense
 
 
@@ -313,39 +315,70 @@ class PatchSystem(_PatchErrorNorms, _DeviceSystem):
 
     `rhs`: the load vector (any shape with ``prod(ndofs)`` entries), or a function of the physical coordinates whose load vector
     is then formed with ``assemble.inner_products``.  `bcs`: ``(indices, values)`` as ``compute_dirichlet_bcs`` returns them, or
-    None.  ``solve(...)`` returns the completed full vector and leaves the solver's statistics in ``info``.  ``spmv(x)``
-    (``R A R^T x``) and ``apply_precond(r)`` (``z = P r``) run the solver's SpMV and preconditioner alone on the device.
+    None.  `boundary_terms`: ``BoundaryTerm`` objects (Robin / impedance matrices and Neumann / Robin loads on sides of the
+    patch): the face matrices are added on the device to the values the patch holds there, the face loads to the load vector
+    (DESIGN.md section 29); a fixed dof on such a side keeps its Dirichlet value.  ``solve(...)`` returns the completed full
+    vector and leaves the solver's statistics in ``info``.  ``spmv(x)`` (``R A R^T x``) and ``apply_precond(r)`` (``z = P r``)
+    run the solver's SpMV and preconditioner alone on the device.
     """
+    _terms = None                             # boundary_terms.PatchTerms of the system, or None
+    _sigma = 0.0                              # 1^T R 1 of its boundary matrices (the shift of the pure-Robin Kronecker preconditioner)
 
-    def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None, method='cg'):
+    def __init__(self, kvs, geo, rhs, bcs=None, kind='stiffness', device=None, method='cg', boundary_terms=None):
         self.kvs = tuple(kvs)
         self.kind = kind
         if kind not in _lib.KINDS:
             raise ValueError('unknown kind %r' % (kind,))
         _check_method(method)
+        self._set_terms(boundary_terms, geo, method)
         self.patch = assemblers.DevicePatch(self.kvs, geo, device=device)
         self.ndofs = self.patch.ndofs
         self.n = int(np.prod(self.ndofs))
         if kind in ('mass', 'stiffness'):
             self.patch.assemble(kind, to_host=False)            # the values stay on the device
+            self._add_term_matrices()
         if callable(rhs):
             from . import assemble
             rhs = assemble.inner_products(self.kvs, rhs, f_physical=True, geo=geo)
         self._create(rhs, bcs, 'igx_solver_create', 'cg', method)
+
+    def _set_terms(self, boundary_terms, geo, method):
+        """The boundary terms, checked and set up on the host (ValueError before any device work)."""
+        terms = _bt.check_terms(boundary_terms, len(self.kvs), method=method, who=type(self).__name__)
+        if terms:
+            self._terms = _bt.PatchTerms(self.kvs, geo, terms, method=method, who=type(self).__name__)
+            self._sigma = self._terms.sigma()
+
+    def _add_term_matrices(self):
+        """The face matrices added to the values the patch holds on the device: after the assembly, before the solver is made."""
+        if self._terms is not None:
+            self._terms.add_matrices(self.patch.add_face)
 
     def _create(self, rhs, bcs, create, initial, method):
         """Right-hand side, Dirichlet data and the device solver (igx_solver_create or igx_solver_create_general)."""
         self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
         if self.b.size != self.n:
             raise ValueError('right-hand side has %d entries, the space %d' % (self.b.size, self.n))
+        if self._terms is not None:
+            try:
+                if self._terms.has_rhs:
+                    self.b = self._terms.add_loads(self.b.copy())
+            finally:
+                self._terms.close()                               # (the face patches: their values have been added)
         self._ctx = self.patch.ctx
         self._attach(create, (self.patch.handle, _lib.KINDS[self.kind]), bcs, method, initial)
         self.box = dirichlet_box(self.ndofs, self.bc_indices)
 
     def _kron_factors(self):
-        """Per-axis eigenvectors and eigenvalues of the 1D Dirichlet matrices of the free range."""
+        """Per-axis eigenvectors and eigenvalues of the 1D Dirichlet matrices of the free range.  With boundary matrices and no
+        fixed dof at all (pure Robin) the stiffness-like kinds get ``lam_k + s / d``, ``s = 1^T R 1 / |parametric domain|`` the
+        Rayleigh quotient of the boundary matrices on the constant: the constant mode (``sum lam_k = 0``) stays invertible."""
         stiff = self.kind != 'mass'                           # (any other form: the parametric Laplacian of the free box)
-        return fastdiag_factors(self.kvs, self.box[0], self.box[1], stiff)
+        U, lam, mode = fastdiag_factors(self.kvs, self.box[0], self.box[1], stiff)
+        if stiff and self._terms is not None and self._terms.has_matrix and self.bc_indices.size == 0:
+            shift = _bt.kron_shift(self.kvs, self._sigma)
+            lam = [l + shift for l in lam]
+        return U, lam, mode
 
     def _set_factors(self, h):
         if self.box is None:
@@ -408,17 +441,18 @@ class FormSystem(PatchSystem):
     convection-diffusion form of the reference's notebook, an assembler class or object); `args` / `kwargs`: its inputs,
     ``geo`` among them.  Forms whose values stay on the host (vector-valued, boundary or surface forms, second or parametric
     derivatives) raise ValueError.  `rhs`: a vector, a scalar, a function of the physical coordinates (``inner_products``) or
-    a linear form string (``'f*v*dx'``).  ``solve()`` uses the Kronecker preconditioner of the parametric Laplacian on the free
+    a linear form string (``'f*v*dx'``).  `boundary_terms`: as for ``PatchSystem``.  ``solve()`` uses the Kronecker preconditioner of the parametric Laplacian on the free
     box when the Dirichlet dofs are whole sides, else Jacobi.
     """
 
-    def __init__(self, problem, kvs, rhs, bcs=None, args=None, method='bicgstab', **kwargs):
+    def __init__(self, problem, kvs, rhs, bcs=None, args=None, method='bicgstab', boundary_terms=None, **kwargs):
         from . import assemble
         _check_method(method)
         args = dict(args or {})
         args.update(kwargs)
         self.kvs = tuple(kvs)
         _check_device_form(problem, self.kvs, args)
+        self._set_terms(boundary_terms, args.get('geo'), method)
         self.assembler = assemble.instantiate_assembler(problem, self.kvs, args)
         self._own_patch = self.assembler is not problem
         self.patch = self.assembler.patch
@@ -426,6 +460,7 @@ class FormSystem(PatchSystem):
         self.ndofs = self.patch.ndofs
         self.n = int(np.prod(self.ndofs))
         self.patch.assemble(self.kind, to_host=False)            # the values stay on the device
+        self._add_term_matrices()
         if isinstance(rhs, str):
             rhs = assemble.assemble(rhs, self.kvs, args=args)
         elif callable(rhs):
@@ -739,7 +774,9 @@ class MultipatchSystem(_DeviceSystem):
     `problem`, `rhs`, `args` / `kwargs`: as for ``MP.assemble_system`` (the same per-patch assemblies and scatters; the sums stay
     on the device).  With ``method='cg'`` (the default) the form must be symmetric: a form whose assembler declares
     ``_symmetric_form = False`` is refused.  ``method='bicgstab'`` solves any form; Schwarz then uses the stiffness factors.
-    `bcs`: ``(indices, values)`` as ``MP.compute_dirichlet_bcs`` returns them, or None.  ``solve(...)`` returns the completed
+    `bcs`: ``(indices, values)`` as ``MP.compute_dirichlet_bcs`` returns them, or None.  `boundary_terms`: ``BoundaryTerm``
+    objects, each with its patch index (``patch=``); with a matrix form among them ``precond='mg'`` raises ValueError (the
+    coarse levels would miss the boundary matrices).  ``solve(...)`` returns the completed
     global vector and leaves the solver's statistics in ``info``.  The system reads the sums `MP` holds: a later
     ``MP.assemble_system`` restarts them (a solve then raises), and ``MP.close()`` destroys the system's device solver.
     """
@@ -749,12 +786,16 @@ class MultipatchSystem(_DeviceSystem):
     _inspect_symmetry = True                  # (False: the caller has shown the form to be symmetric before, as
                                               # MultipatchEigenSystem does for its own levels)
 
-    def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', **kwargs):
+    def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', boundary_terms=None, **kwargs):
         self.MP = MP
         _check_method(method)
         self._problem = (problem, rhs, dict(args or {}), dict(kwargs))
         self._mg = None
         kinds = []
+        # boundary terms, set up on the host before any device work; their matrices are added to the
+        # sums after the scatters, their loads to the patches' load vectors before theirs
+        terms = MP._boundary_terms(boundary_terms, rhs, args, kwargs, method=method, who=type(self).__name__)
+        self._matrix_terms = any(t.has_matrix for t in terms.values())
 
         def inspect(p, asm):
             if self._inspect_symmetry and method == 'cg' and not getattr(asm, '_symmetric_form', True):
@@ -763,7 +804,7 @@ class MultipatchSystem(_DeviceSystem):
                                  "mass and stiffness forms ('u*v*dx', 'inner(grad(u),grad(v))*dx') and assemblers that do not "
                                  "declare _symmetric_form = False; any other form: method='bicgstab'" % (p, type(asm).__name__))
             kinds.append(getattr(asm, '_kind', None))
-        h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect)
+        h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect, boundary_terms=terms)
         self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
         self.n = MP.numdofs
         self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
@@ -799,10 +840,19 @@ class MultipatchSystem(_DeviceSystem):
         if precond == 'mg':
             if self.method != 'cg':
                 raise ValueError("precond='mg' serves method='cg' only")
+            self._refuse_mg_with_terms()
             self._live()
             if self._mg is None:
                 self.set_multigrid()
         _DeviceSystem.set_precond(self, precond)
+
+    _matrix_terms = False                     # the sums hold boundary matrices (boundary_terms with a matrix form)
+
+    def _refuse_mg_with_terms(self):
+        if self._matrix_terms:
+            raise ValueError("precond='mg' is not available with boundary terms that have a matrix form: the coarse levels assemble "
+                             "`problem` again and would miss the boundary matrices (load-only terms are fine); use 'schwarz', "
+                             "'jacobi' or None")
 
     def set_multigrid(self, levels=None, coarse=None, smooth_steps=1, coarse_max=2048, block_rows=None):
         """Sets up the hierarchy of ``precond='mg'``: a V-cycle with `smooth_steps` coloured Gauss-Seidel sweeps before (forward)
@@ -820,6 +870,7 @@ class MultipatchSystem(_DeviceSystem):
         from .multipatch import slice_indices
         if self.method != 'cg':
             raise ValueError("precond='mg' serves method='cg' only")
+        self._refuse_mg_with_terms()
         self._live()
         MP = self.MP
         if not MP.injective:
@@ -1432,12 +1483,14 @@ class ParabolicSystem(_PatchErrorNorms, _DeviceSystem):
     `rhs`: the load vector, a scalar, a function of the physical coordinates (``inner_products``) or a linear form string.
     `bcs`: ``(indices, values)`` as ``compute_dirichlet_bcs`` gives them, or None (pure Neumann).  `method`: 'auto' is CG for the
     built-in stiffness (and mass) form, else BiCGStab; 'cg' on any other form raises ValueError before any assembly.
+    `boundary_terms`: ``BoundaryTerm`` objects (time-independent): their face matrices are added to K on the device before the
+    solver takes it (convective cooling: ``K + R``), their face loads to f; M is untouched.
 
     ``integrate(...)`` returns ``(times, solutions)``; ``spmv(x)`` is ``R C R^T x`` and ``apply_precond(r)`` the preconditioner
     of C, for the scheme and step of ``set_scheme`` (or the last ``integrate``).
     """
 
-    def __init__(self, kvs, geo, rhs, bcs=None, problem=None, args=None, method='auto', device=None, **kwargs):
+    def __init__(self, kvs, geo, rhs, bcs=None, problem=None, args=None, method='auto', device=None, boundary_terms=None, **kwargs):
         from . import assemble
         if method != 'auto':
             _check_method(method)
@@ -1451,6 +1504,12 @@ class ParabolicSystem(_PatchErrorNorms, _DeviceSystem):
             _check_device_form(problem, self.kvs, args)
         kind = _form_kind(problem)
         self.symmetric = kind in ('mass', 'stiffness')
+        # boundary terms: K + R is the operator, the face loads join f; the mass matrix is untouched
+        terms = _bt.check_terms(boundary_terms, len(self.kvs), method=None if method == 'auto' else method, who='ParabolicSystem')
+        self._terms = _bt.PatchTerms(self.kvs, args.get('geo'), terms, method=None if method == 'auto' else method,
+                                     who='ParabolicSystem') if terms else None
+        if self._terms is not None and not self._terms.symmetric():
+            self.symmetric = False                               # ('auto' then takes BiCGStab)
         if method == 'auto':
             method = 'cg' if self.symmetric else 'bicgstab'
         elif method == 'cg' and not self.symmetric:
@@ -1476,12 +1535,19 @@ class ParabolicSystem(_PatchErrorNorms, _DeviceSystem):
         self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
         if self.b.size != self.n:
             raise ValueError('right-hand side has %d entries, the space %d' % (self.b.size, self.n))
+        if self._terms is not None and self._terms.has_rhs:
+            self.b = self._terms.add_loads(self.b.copy())
         self._ctx = self.patch.ctx
         self._attach('igx_solver_create_parabolic', (self.patch.handle, _lib.KINDS[self.kind], 1 if self.symmetric else 0), bcs,
                      method, 'cg' if self.symmetric else 'bicgstab')
         self.box = dirichlet_box(self.ndofs, self.bc_indices)
         lib = _lib.load()
         self.patch.assemble(self.kind, to_host=False)            # the values stay on the device and change hands
+        if self._terms is not None:                              # K + R: added before the solver takes the values
+            try:
+                self._terms.add_matrices(self.patch.add_face)
+            finally:
+                self._terms.close()
         _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_OPERATOR), 'igx_solver_take_values')
         self.patch.assemble('mass', to_host=False)
         _lib.check(lib.igx_solver_take_values(self.handle, _lib.IGX_ROLE_MASS), 'igx_solver_take_values')
