@@ -924,6 +924,41 @@ typedef struct {
 } igx_kron_desc;
 int igx_kron_apply_d(igx_ctx *ctx, const igx_kron_desc *desc, const double *d_x, double *d_y, double *d_work, int64_t work_len);
 
+/* Bilinear forms over TWO spline spaces on one mesh (Taylor-Hood, Q1-P0, ..: pyiga's assemble(problem, (kvs0, kvs1), bfuns=
+   [('u', nc, 0), ('p', nc, 1)])).  A pair is a full patch -- the TRIAL space (columns; space 0 of the reference), which owns the
+   geometry, the Gauss grid and the form fields -- plus a TEST space (rows; space 1) given by per-axis degree and open knot
+   vector.  The patch's quadrature is used as it is: create the patch with nqp = max degree over BOTH spaces + 1, the
+   reference's rule.  The matrix is prod(ndofs_test) x prod(ndofs_trial), canonical CSR holding exactly the product pattern:
+   row (i0, i1[, i2]) has the columns [jlo_0, jhi_0) x [jlo_1, jhi_1) [x ..] in lexicographic order, [jlo_k, jhi_k) the trial
+   functions of axis k whose mesh support meets that of test function i_k.
+   igx_pair_create returns NULL (igx_last_error names the condition) unless: the test space has the patch's dim; its degrees
+   are <= IGX_MAX_DEGREE and its knot vectors open; per axis its breakpoints equal the patch's exactly; the patch is whole (no
+   span box, no row slab, not an internal twin) and its basis tables hold (value, first derivative).  The patch must outlive
+   the pair. */
+typedef struct igx_pair igx_pair;
+typedef struct {
+    int32_t dim, reserved;
+    int32_t ndofs_trial[IGX_MAX_DIM], ndofs_test[IGX_MAX_DIM];
+    int64_t nrows, ncols, nnz;         /* prod(ndofs_test), prod(ndofs_trial), entries of the pattern */
+} igx_pair_info;
+igx_pair *igx_pair_create(igx_patch *patch, int dim, const int32_t *p, const int32_t *kv_len, const double *const *kv);
+void igx_pair_destroy(igx_pair *pair);
+int  igx_pair_get_info(const igx_pair *pair, igx_pair_info *info);
+/* indptr: nrows + 1 entries, indices: nnz global column ids; either may be NULL; kept on the device.  IGX_ERR_UNSUPPORTED
+   for nnz or ncols >= 2^31 (int32 indices) -- never a truncated pattern. */
+int  igx_pair_pattern(igx_pair *pair, int32_t *indptr, int32_t *indices);
+/* All nnz values in the order of igx_pair_pattern, one thread per entry in the reference's summation order; kept on the
+   device (igx_pair_d_data) and copied to data_out if it is not NULL.  kind: IGX_MASS, or IGX_FORM with the physical table of
+   igx_patch_set_form[_d|_expr] (a parametric jet form: IGX_ERR_UNSUPPORTED).  The fields are the patch's own: they depend on
+   geometry and coefficients only.  A launch beyond the grid limit is IGX_ERR_UNSUPPORTED. */
+int  igx_pair_assemble(igx_pair *pair, int kind, double *data_out);
+/* ij: M x 2 (row = ravelled test dof, column = ravelled trial dof), host in and out; disjoint supports or an index at or
+   past the row / column count give exactly 0.0.  The values have the bits of the corresponding igx_pair_assemble values. */
+int  igx_pair_entries(igx_pair *pair, int kind, const size_t *ij, size_t M, double *out);
+const double *igx_pair_d_data(const igx_pair *pair);     /* values of the last igx_pair_assemble (NULL before the first) */
+/* Device times of the last igx_pair_assemble: total_ms, fields_ms (0 when the patch still held the fields), entry_ms. */
+int  igx_pair_last_timing(const igx_pair *pair, igx_timing *t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,13 @@ class PatchInfo(C.Structure):
     ]
 
 
+class PairInfo(C.Structure):
+    _fields_ = [
+        ('dim', C.c_int32), ('reserved', C.c_int32), ('ndofs_trial', C.c_int32 * 3), ('ndofs_test', C.c_int32 * 3),
+        ('nrows', C.c_int64), ('ncols', C.c_int64), ('nnz', C.c_int64),
+    ]
+
+
 class MultipatchInfo(C.Structure):
     _fields_ = [
         ('npatches', C.c_int32), ('injective', C.c_int32), ('nrows', C.c_int64), ('nnz', C.c_int64),
@@ -295,6 +302,14 @@ SYMBOLS = [
     ('igx_solver_eig_residuals_d', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p, _dp, _dp]),
     ('igx_solver_eig_precond_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ('igx_kron_apply_d', C.c_int, [C.c_void_p, C.POINTER(KronDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    ('igx_pair_create', C.c_void_p, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp)]),
+    ('igx_pair_destroy', None, [C.c_void_p]),
+    ('igx_pair_get_info', C.c_int, [C.c_void_p, C.POINTER(PairInfo)]),
+    ('igx_pair_pattern', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ('igx_pair_assemble', C.c_int, [C.c_void_p, C.c_int, _dp]),
+    ('igx_pair_entries', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_size_t, _dp]),
+    ('igx_pair_d_data', C.c_void_p, [C.c_void_p]),
+    ('igx_pair_last_timing', C.c_int, [C.c_void_p, C.POINTER(Timing)]),
 ]
 
 _lib = None

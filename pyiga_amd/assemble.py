@@ -63,6 +63,41 @@ def bsp_stiffness_1d(knotvec):
     return bsp_mixed_deriv_biform_1d(knotvec, 1, 1)
 
 
+def bsp_mixed_deriv_biform_1d_asym(knotvec1, knotvec2, du, dv, quadgrid=None, nqp=None):
+    """Matrix of ``a(u,v) = (u^(du), v^(dv))`` relating two B-spline bases (pyiga/assemble.py:192-222): `knotvec1` is the
+    space of the trial functions (columns), `knotvec2` that of the test functions (rows); shape ``knotvec2.numdofs x
+    knotvec1.numdofs``.  The rule is iterated over `quadgrid` (default: the mesh of `knotvec1`; every cell must lie inside
+    one span of both knot vectors) with ``ceil((p1 + p2 - du - dv + 1)/2)`` Gauss points per cell."""
+    if quadgrid is None:
+        quadgrid = knotvec1.mesh
+    p1, p2 = knotvec1.p, knotvec2.p
+    if nqp is None:
+        nqp = int(math.ceil((p1 + p2 - du - dv + 1) / 2.0))
+    nspans = len(quadgrid) - 1
+    nodes, weights = make_iterated_quadrature(quadgrid, nqp)
+    trial = (bspline.active_deriv(knotvec1, nodes, du)[du] * weights).reshape(p1 + 1, nspans, nqp)
+    test = bspline.active_deriv(knotvec2, nodes, dv)[dv].reshape(p2 + 1, nspans, nqp)
+    blocks = np.empty((nspans, p2 + 1, p1 + 1))
+    for k in range(nspans):
+        blocks[k] = np.dot(test[:, k, :], trial[:, k, :].transpose())
+    first1 = bspline.findspans(knotvec1, nodes[::nqp]) - p1             # first active dof in the cell of each first node
+    first2 = bspline.findspans(knotvec2, nodes[::nqp]) - p2
+    rows = (first2[:, None, None] + np.arange(p2 + 1)[None, :, None]) + 0 * np.arange(p1 + 1)[None, None, :]
+    cols = (first1[:, None, None] + np.arange(p1 + 1)[None, None, :]) + 0 * np.arange(p2 + 1)[None, :, None]
+    shape = (knotvec2.numdofs, knotvec1.numdofs)
+    return scipy.sparse.coo_matrix((blocks.ravel(), (rows.ravel(), cols.ravel())), shape=shape).tocsr()
+
+
+def bsp_mass_1d_asym(knotvec1, knotvec2, quadgrid=None):
+    """Mass matrix relating two B-spline bases (trial: `knotvec1`, test: `knotvec2`)."""
+    return bsp_mixed_deriv_biform_1d_asym(knotvec1, knotvec2, 0, 0, quadgrid=quadgrid)
+
+
+def bsp_stiffness_1d_asym(knotvec1, knotvec2, quadgrid=None):
+    """Stiffness matrix relating two B-spline bases (trial: `knotvec1`, test: `knotvec2`)."""
+    return bsp_mixed_deriv_biform_1d_asym(knotvec1, knotvec2, 1, 1, quadgrid=quadgrid)
+
+
 ################################################################################
 # d-dimensional matrices (pyiga/assemble.py:236-282)
 ################################################################################
@@ -234,6 +269,8 @@ def assemble_entries(asm, symmetric=False, format='csr', layout='blocked', algo=
     if isinstance(asm, FormAssembler):
         # vector-valued functions and boundary integrals: one scalar jet form per pair of components on the device
         # (symmetric=True is the reference's request to compute half of the entries; the result is the same matrix)
+        if symmetric and asm.pair is not None:
+            raise ValueError('symmetric=True for a form over two different spaces (the matrix is rectangular)')
         if layout not in ('blocked', 'packed'):
             raise ValueError("layout %r: 'blocked' or 'packed'" % (layout,))
         return asm.assemble(format=format, layout=layout)
@@ -465,10 +502,14 @@ def instantiate_assembler(problem, kvs, args, bfuns=None, boundary=None):
     (vform -> Cython -> gcc).  Here the three built-in forms map to their hand-written kernels, any other
     3D scalar form in u, v, grad, inner, dot goes through the general device form (``pyiga_amd.forms`` ->
     ``IGX_FORM``); assembler classes and objects are accepted as in the reference."""
-    surface = isinstance(problem, str) and 'geo' in args and getattr(args['geo'], 'dim', None) == len(tuple(kvs)) + 1
+    from .form_assemblers import is_space_pair
+    # kvs = (kvs0, kvs1): a form over two spaces, the space of every function in `bfuns` (form_assemblers.space_roles)
+    two = isinstance(problem, str) and is_space_pair(kvs)
+    d = len(tuple(kvs)[0]) if two else len(tuple(kvs))
+    surface = isinstance(problem, str) and 'geo' in args and getattr(args['geo'], 'dim', None) == d + 1
     if isinstance(problem, str):
-        _check_spline_inputs(problem, tuple(kvs), args, bfuns, boundary, surface)
-    if isinstance(problem, str) and (bfuns is not None or boundary is not None or surface):
+        _check_spline_inputs(problem, tuple(kvs)[0] if two else tuple(kvs), args, bfuns, boundary, surface)
+    if isinstance(problem, str) and (bfuns is not None or boundary is not None or surface or two):
         # vector-valued basis functions and/or a boundary integral (pyiga/vform.py:1822-1845, pyiga/assemble.py:929-934)
         from .form_assemblers import FormAssembler
         if 'geo' not in args:
@@ -518,9 +559,15 @@ def assemble(problem, kvs, args=None, bfuns=None, boundary=None, symmetric=False
     """Assemble the matrix of a variational form (string, assembler class or assembler object); signature of
     pyiga/assemble.py:837.  `bfuns` (vector-valued basis functions), `boundary` (a face of the patch, forms in ``ds``) and
     `layout` ('blocked' | 'packed', vector-valued spaces) as in the reference; they go through
-    ``pyiga_amd.form_assemblers.FormAssembler``."""
+    ``pyiga_amd.form_assemblers.FormAssembler``.  `kvs` may be ``(kvs0, kvs1)``, two spaces on one mesh, with the space of
+    every function as the third element of its `bfuns` entry (``[('u', 2, 0), ('p', 1, 1)]``): the trial function in space 0,
+    the test function in space 1, a matrix of shape ``(ncv * N1, ncu * N0)`` (``form_assemblers.space_roles``)."""
     args = dict(args or {})
     args.update(kwargs)
+    if symmetric and isinstance(problem, str):
+        from .form_assemblers import space_roles
+        if space_roles(kvs, problem, bfuns)[1] is not None:          # (host logic: refused before anything exists on the device)
+            raise ValueError('symmetric=True for a form over two different spaces (the matrix is rectangular)')
     asm = instantiate_assembler(problem, kvs, args, bfuns, boundary)
     return assemble_entries(asm, symmetric=symmetric, format=format, layout=layout)
 

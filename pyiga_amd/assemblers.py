@@ -620,6 +620,85 @@ class DevicePatch:
         return scipy.sparse.csr_matrix((data, indices, indptr), shape=(nrows, self.shape[1]))
 
 
+class DevicePair:
+    """RAII wrapper of ``igx_pair``: a whole ``DevicePatch`` (the trial space: columns; geometry, Gauss grid and form fields)
+    plus a test space (rows) on the same mesh.  Matrices are ``prod(ndofs_test) x prod(ndofs_trial)``; `kind` is 'mass' or
+    'form' with the table given to ``patch.set_form``.  The patch's quadrature is used as it is: create the patch with
+    ``nqp = max degree over both spaces + 1``.  The patch must stay open while the pair is used."""
+
+    def __init__(self, patch, kvs_test):
+        lib = _lib.load()
+        self.patch = patch
+        self.kvs_test = tuple(kvs_test)
+        d = len(self.kvs_test)
+        arrs = [_lib.f64(kv.kv) for kv in self.kvs_test]
+        p = (C.c_int32 * d)(*[int(kv.p) for kv in self.kvs_test])
+        n = (C.c_int32 * d)(*[a.size for a in arrs])
+        kv = (_lib._dp * d)(*[_lib.dptr(a) for a in arrs])
+        self.handle = lib.igx_pair_create(patch.handle, d, p, n, kv)
+        if not self.handle:
+            raise _lib.IgxError('igx_pair_create failed: ' + _lib.last_error())
+        self.info = _lib.PairInfo()
+        _lib.check(lib.igx_pair_get_info(self.handle, C.byref(self.info)), 'igx_pair_get_info')
+        self._pattern = None
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            if getattr(self.patch.ctx, 'handle', None):       # (the context may be gone at interpreter shutdown)
+                _lib.load().igx_pair_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def shape(self):
+        return int(self.info.nrows), int(self.info.ncols)
+
+    @property
+    def nnz(self):
+        return int(self.info.nnz)
+
+    def pattern(self):
+        """(indptr, indices), canonical CSR, int32."""
+        if self._pattern is None:
+            indptr = np.empty(self.shape[0] + 1, dtype=np.int32)
+            indices = np.empty(self.nnz, dtype=np.int32)
+            _lib.check(_lib.load().igx_pair_pattern(self.handle, indptr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    indices.ctypes.data_as(C.POINTER(C.c_int32))), 'igx_pair_pattern')
+            self._pattern = (indptr, indices)
+        return self._pattern
+
+    def assemble(self, kind, to_host=False):
+        """Form all values on the device; returns them (host array) if `to_host`."""
+        out = np.empty(self.nnz) if to_host else None
+        _lib.check(_lib.load().igx_pair_assemble(self.handle, _lib.KINDS[kind], _lib.dptr(out) if to_host else None),
+                   'igx_pair_assemble')
+        return out
+
+    def csr(self, kind):
+        data = self.assemble(kind, to_host=True)
+        indptr, indices = self.pattern()
+        return scipy.sparse.csr_matrix((data, indices, indptr), shape=self.shape)
+
+    def entries(self, kind, idx):
+        """Entries (row = ravelled test dof, column = ravelled trial dof) for an ``M x 2`` index array."""
+        idx = np.ascontiguousarray(idx, dtype=np.uintp)
+        assert idx.ndim == 2 and idx.shape[1] == 2
+        out = np.zeros(idx.shape[0])
+        _lib.check(_lib.load().igx_pair_entries(self.handle, _lib.KINDS[kind], idx.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                                idx.shape[0], _lib.dptr(out)), 'igx_pair_entries')
+        return out
+
+    def timing(self):
+        t = _lib.Timing()
+        _lib.check(_lib.load().igx_pair_last_timing(self.handle, C.byref(t)), 'igx_pair_last_timing')
+        return t.as_dict()
+
+
 class _DeviceAssembler:
     """Common part of the four assembler classes (genericasm.pxi BaseAssembler{2,3}D)."""
     _kind = None

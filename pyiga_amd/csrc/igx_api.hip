@@ -59,7 +59,7 @@ static int dev_alloc_copy(T **dst, const T *src, size_t n, hipStream_t st)
 // Knot-vector bookkeeping: restates KnotVector.mesh / mesh_support_idx_all / mesh_span_indices
 // (pyiga/bspline.py:110-144), compute_sparsity_ij (pyiga/mlmatrix.py:420-440) and the iterated
 // Gauss rule (pyiga/quadrature.py:3-16).
-static int setup_axis(Axis &A, const double *kv, int len, int p, int q, const double *gx, const double *gw)
+int setup_axis(Axis &A, const double *kv, int len, int p, int q, const double *gx, const double *gw)
 {
     if (p < 0 || p > IGX_MAX_DEGREE) { set_error("degree %d out of range [0,%d]", p, IGX_MAX_DEGREE); return IGX_ERR_ARG; }
     if (len < 2 * (p + 1)) { set_error("knot vector too short (%d knots for degree %d)", len, p); return IGX_ERR_ARG; }

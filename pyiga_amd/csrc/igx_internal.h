@@ -244,6 +244,8 @@ static inline void stage_event(const igx_patch *pt, int k, hipStream_t st)
 // ---------------------------------------------------------------------------------------------
 // kernel launchers (defined in the kern_*.hip files)
 namespace igx {
+// host tables of one axis from its knot vector (igx_api.hip); also the test space of an igx_pair (pair.hip)
+int setup_axis(Axis &A, const double *kv, int len, int p, int q, const double *gx, const double *gw);
 int launch_basis_tables(hipStream_t st, const double *d_kv, int nk, int p, const double *d_u, size_t nu,
                         int numderiv, double *d_out_nd_p_n /* (nd+1,P,nu) or null */,
                         double *d_V /* [nu][P][2] or null */, int *d_fa /* [nu] or null */,

@@ -18,7 +18,7 @@ import numpy as np
 import scipy.sparse
 
 from . import bspline, geometry, tforms
-from .assemblers import DevicePatch
+from .assemblers import DevicePair, DevicePatch
 from .quadrature import make_tensor_quadrature
 
 
@@ -72,14 +72,65 @@ def _assemble_1d_jets(kv, nqp, C=None, F=None):
     return scipy.sparse.csr_matrix(A)
 
 
+def is_space_pair(kvs):
+    """True if `kvs` is ``(kvs0, kvs1)``, two tuples of knot vectors, and not one tuple of knot vectors."""
+    kvs = tuple(kvs)
+    return len(kvs) == 2 and not isinstance(kvs[0], bspline.KnotVector) and not isinstance(kvs[1], bspline.KnotVector)
+
+
+def space_roles(kvs, form, bfuns, geo=None, boundary=None):
+    """``(kvs_trial, kvs_test)`` of a form over the spaces `kvs` -- one tuple of knot vectors or a pair of them -- from the space
+    indices in `bfuns` (``('u', 2, 0)``: in space 0).  kvs_test is None unless the form couples two different spaces.  Host
+    logic only: everything that cannot be assembled is refused here, before anything exists on the device.
+
+    The reference's assemblers always take rows from space 1 and columns from space 0 and integrate on the mesh of space 0
+    (pyiga/genericasm.pxi); with the trial function in space 1 and the test function in space 0, or with unequal meshes, it
+    returns a matrix of wrong content.  Supported: the trial function (first of `bfuns`) in space 0 and the test function
+    (last) in space 1, or all functions in one space."""
+    bf = tforms.normalise_bfuns(form, bfuns)
+    spaces = [s for _, _, s in bf]
+    if not is_space_pair(kvs):
+        if any(spaces):
+            raise ValueError('basis function in space 1, but only one space was given: pass kvs=(kvs0, kvs1)')
+        return tuple(kvs), None
+    kvs0, kvs1 = (tuple(k) for k in kvs)
+    if len(kvs0) != len(kvs1):
+        raise ValueError('the two spaces have different dimensions (%d, %d)' % (len(kvs0), len(kvs1)))
+    if len(set(spaces)) <= 1:                      # every function in one space: a form on that space alone
+        return (kvs1 if spaces and spaces[0] == 1 else kvs0), None
+    if len(bf) != 2:
+        raise ValueError('arity should be 1 or 2')
+    if spaces != [0, 1]:
+        raise ValueError('the trial function %s is in space 1 and the test function %s in space 0: rows come from space 1 and '
+                         'columns from space 0, so pass the spaces in the other order, kvs=(kvs of %s, kvs of %s), and swap '
+                         'the space indices in bfuns' % (bf[0][0], bf[1][0], bf[0][0], bf[1][0]))
+    for k, (a, b) in enumerate(zip(kvs0, kvs1)):
+        if not np.array_equal(a.mesh, b.mesh):
+            raise ValueError('axis %d: the two spaces have different meshes (breakpoints); forms over two spaces are '
+                             'integrated on one mesh' % k)
+    if boundary is not None:
+        raise NotImplementedError('boundary integrals over two different spaces')
+    if geo is not None and getattr(geo, 'dim', len(kvs0)) != len(kvs0):
+        raise NotImplementedError('surface integrals over two different spaces')
+    import re
+    if re.search(r'\bds\b', form):
+        raise NotImplementedError('surface integrals (ds) over two different spaces')
+    return kvs0, kvs1
+
+
 class FormAssembler:
-    """Assembler object for a form string with `bfuns` (vector-valued functions) and/or `boundary`; the reference's
-    plugin interface for such forms: ``arity``, ``kvs``, ``num_components()``, ``multi_blocks()``, ``assemble_vector()``
-    plus ``assemble(format, layout)``, which ``assemble.assemble_entries`` calls."""
+    """Assembler object for a form string with `bfuns` (vector-valued functions, functions in two different spaces) and/or
+    `boundary`; the reference's plugin interface for such forms: ``arity``, ``kvs``, ``num_components()``,
+    ``multi_blocks()``, ``assemble_vector()`` plus ``assemble(format, layout)``, which ``assemble.assemble_entries`` calls.
+
+    `kvs`: a tuple of knot vectors, or ``(kvs0, kvs1)`` with the space of every function as the third element of its `bfuns`
+    entry (``space_roles``); the matrix of a form over two spaces has the rows of the test space and the columns of the
+    trial space, ``self.kvs = (kvs_trial, kvs_test)``."""
 
     def __init__(self, kvs, geo, form, bfuns=None, inputs=None, boundary=None, device=None, lazy_patch=False):
-        kvs = tuple(kvs)
-        self.kvs = (kvs, kvs)
+        kvs, kvs_test = space_roles(kvs, form, bfuns, geo, boundary)
+        self.kvs = (kvs, kvs if kvs_test is None else kvs_test)
+        self.pair = None
         self._lazy_patch = lazy_patch          # boundary forms of 3D patches: the face patch is made by ensure_patch(), so that the
                                                # tables can be inspected before any device work (solvers.BoundaryTerm)
         self._geo = geo
@@ -87,7 +138,7 @@ class FormAssembler:
         self._device = device
         d = len(kvs)
         assert geo.sdim == d, 'Geometry has wrong source dimension'
-        self.nqp = max(kv.p for kv in kvs) + 1
+        self.nqp = max(kv.p for kv in self.kvs[0] + self.kvs[1]) + 1      # (two spaces: over both, pyiga/codegen/cython.py:525)
         inputs = {k: v for k, v in dict(inputs or {}).items() if k != 'geo'}
         self.boundary = None if boundary is None else parse_bdspec(boundary, d)
         self._surface = boundary is None and geo.dim == d + 1
@@ -97,7 +148,11 @@ class FormAssembler:
         elif self.boundary is None:
             assert d in (2, 3), 'vector-valued forms are assembled for 2D and 3D patches'
             self._tkvs = kvs
-            self.patch = DevicePatch(kvs, geo, device=device)
+            if kvs_test is None:
+                self.patch = DevicePatch(kvs, geo, device=device)
+            else:                              # trial space = the patch; the test space rides on its Gauss grid and fields
+                self.patch = DevicePatch(kvs, geo, device=device, nqp=self.nqp)
+                self.pair = DevicePair(self.patch, kvs_test)
             grid = [self.patch.gauss(k)[0] for k in range(d)]
             G = tuple(len(g) for g in grid)
             X = np.asarray(geo.grid_eval(grid))
@@ -235,12 +290,13 @@ class FormAssembler:
 
     def _block_matrix(self, tab):
         n = int(np.prod([kv.numdofs for kv in self._tkvs]))
+        m = n if self.pair is None else self.pair.shape[0]
         if all(e is None for row in tab for e in row):
-            return scipy.sparse.csr_matrix((n, n))
+            return scipy.sparse.csr_matrix((m, n))
         if self.patch is None:
             return _assemble_1d_jets(self._tkvs[0], self.nqp, C=tab)
         self.patch.set_form(_full_table(tab, self._jd))
-        return self.patch.csr('form')
+        return self.patch.csr('form') if self.pair is None else self.pair.csr('form')
 
     def blocks(self):
         """[[A_pq]]: scalar matrices of test component p against trial component q."""
@@ -264,7 +320,7 @@ class FormAssembler:
                     out[:, p, q] = np.asarray(A[idx[:, 0], idx[:, 1]]).ravel()
                 else:
                     self.patch.set_form(_full_table(tab, self._jd))
-                    out[:, p, q] = self.patch.entries('form', idx)
+                    out[:, p, q] = (self.patch if self.pair is None else self.pair).entries('form', idx)
         # the reference declares the result as N x numcomp[0] x numcomp[1] (trial, test) over the same row-major
         # (test, trial) memory: identical for square blocks, a reinterpretation for rectangular ones
         return out.reshape(idx.shape[0], ncu, ncv)

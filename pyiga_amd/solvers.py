@@ -495,13 +495,12 @@ def _vector_components(problem, kvs, args, bfuns, who='VectorFormSystem'):
         raise ValueError("required input parameter 'geo' missing")
     if getattr(geo, 'dim', len(kvs)) != len(kvs) or re.search(r'\bds\b', problem):
         raise ValueError('%s solves volume forms (dx), not surface or boundary forms: %r' % (who, problem))
-    try:
-        bf = tforms.normalise_bfuns(problem, bfuns)
-    except NotImplementedError as e:
-        raise ValueError('%s: %s' % (who, e))
+    bf = tforms.normalise_bfuns(problem, bfuns)
+    if any(space != 0 for _, _, space in bf):
+        raise ValueError('%s: basis functions in different spaces (mixed systems are assembled, not solved, on the device)' % who)
     if len(bf) != 2:
         raise ValueError('%s needs a bilinear form (trial and test function), not arity %d: %r' % (who, len(bf), problem))
-    (_, ncu), (_, ncv) = bf
+    (_, ncu, _), (_, ncv, _) = bf
     if ncu != ncv:
         raise ValueError('%s: trial and test functions have %d and %d components (mixed systems are not '
                          'supported)' % (who, ncu, ncv))

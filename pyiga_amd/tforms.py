@@ -328,12 +328,14 @@ class Measured:
 
 
 def normalise_bfuns(expr, bfuns):
-    """[(name, components)] in the order (trial, test) the reference uses: names sorted ('u' before 'v') when detected from
-    the string (pyiga/vform.py:1822-1825), else as given."""
+    """[(name, components, space)] in the order (trial, test) the reference uses: names sorted ('u' before 'v') when detected
+    from the string (pyiga/vform.py:1822-1825), else as given.  space: index into the tuple of spaces the form is assembled
+    over (0 unless the caller says otherwise); which combinations can be assembled is decided by the assembler
+    (``form_assemblers.space_roles``)."""
     import re
     if bfuns is None:
         words = set(re.findall(r"[^\d\W]\w*", expr))
-        return [(bf, 1) for bf in sorted(words & {'u', 'v'})]
+        return [(bf, 1, 0) for bf in sorted(words & {'u', 'v'})]
     out = []
     for bf in bfuns:
         if isinstance(bf, str):
@@ -341,9 +343,10 @@ def normalise_bfuns(expr, bfuns):
         bf = tuple(bf)
         if len(bf) == 1:
             bf = bf + (1,)
-        if len(bf) == 3 and bf[2] != 0:
-            raise NotImplementedError('basis functions in different spaces')
-        out.append((str(bf[0]), int(bf[1])))
+        space = int(bf[2]) if len(bf) >= 3 else 0
+        if space not in (0, 1):
+            raise ValueError('basis function %s: space %d (a form is assembled over one or two spaces: 0 or 1)' % (bf[0], space))
+        out.append((str(bf[0]), int(bf[1]), space))
     return out
 
 
@@ -360,7 +363,7 @@ def evaluate(expr, G, X, inputs, bfuns=None, normal=None):
         raise ValueError('arity should be 1 or 2')
     J = d + 1
     ns = {}
-    for name, nc in bf:
+    for name, nc, _ in bf:                                 # (the coefficient table does not depend on the spaces)
         who = (name, name == bf[-1][0])                   # the last function of `bfuns` is the test function
         a = np.zeros((1,) * len(G) + ((nc,) if nc > 1 else ()) + (nc, J))
         if nc > 1:
@@ -396,7 +399,7 @@ def evaluate(expr, G, X, inputs, bfuns=None, normal=None):
     if normal is not None:
         ns['n'] = TExpr(normal, (d,), 'c')
     for name, val in inputs.items():
-        if name == 'geo' or name in ns and name in dict(bf):
+        if name == 'geo' or name in ns and name in [b[0] for b in bf]:
             continue
         if callable(val):
             vals = val(*(X[..., k] for k in range(d)))
@@ -414,7 +417,7 @@ def evaluate(expr, G, X, inputs, bfuns=None, normal=None):
     if not isinstance(res, Measured):
         raise NotImplementedError('the form must be an integral (... * dx or ... * ds)')
     e = res.e
-    ncs = tuple(nc for _, nc in bf)
+    ncs = tuple(b[1] for b in bf)
     if len(bf) == 2:
         if e.kind != 'b':
             raise NotImplementedError('the form must be bilinear in %s and %s' % (bf[0][0], bf[1][0]))
