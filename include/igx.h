@@ -630,18 +630,21 @@ int igx_solver_solve(igx_solver *solver, const double *b, const double *g, const
    on a breakdown: rho vanishing again right after a restart, a step 1e-13 |alpha| ||v|| > ||r|| (r^.v vanished), t.t = 0 or
    omega = 0, or a non-finite scalar.  u is then the last finite iterate.  A solve that has stopped leaves x and r as they are, so
    check_every does not change u; info->iterations counts the iterations entered. */
-enum { IGX_METHOD_CG = 0, IGX_METHOD_BICGSTAB = 1 };
+enum { IGX_METHOD_CG = 0, IGX_METHOD_BICGSTAB = 1,
+       IGX_METHOD_MINRES = 2 };      /* saddle-point solvers (igx_solver_create_saddle), and only they */
 enum { IGX_BREAKDOWN_RHO = 1,        /* rho = r^.r vanished twice in a row (the restart with r^ = r did not help) */
        IGX_BREAKDOWN_ALPHA = 2,      /* r^.v vanished: the step alpha v would exceed 1e13 ||r|| */
        IGX_BREAKDOWN_OMEGA = 3,      /* t.t = 0 or omega = 0: the half step x + alpha p^ is kept */
-       IGX_BREAKDOWN_NONFINITE = 4 };/* a scalar was not finite */
+       IGX_BREAKDOWN_NONFINITE = 4,  /* a scalar was not finite */
+       IGX_BREAKDOWN_INDEFINITE_PRECOND = 5 };   /* MINRES: r.(P r) < 0, the preconditioner is not positive definite */
 /* As igx_solver_create, for any kind the patch holds on the device (IGX_MASS, IGX_STIFFNESS, IGX_CONVDIFF, IGX_FORM; another
    value: IGX_ERR_ARG), with the same refusals (row slabs and span boxes, values not assembled or stale).  Starts in
    IGX_METHOD_BICGSTAB.  The patch's values must be the whole matrix of the form (a parametric jet form assembled in passes
    leaves only the last pass on the device). */
 int  igx_solver_create_general(igx_patch *patch, int kind, const int64_t *fixed, int64_t nfixed, igx_solver **out);
 /* The method of the following solves, on any solver.  IGX_METHOD_CG on a patch solver of a kind other than IGX_MASS /
-   IGX_STIFFNESS: IGX_ERR_UNSUPPORTED.  IGX_METHOD_BICGSTAB allocates its four extra vectors once (a CG solver has none). */
+   IGX_STIFFNESS: IGX_ERR_UNSUPPORTED.  IGX_METHOD_BICGSTAB allocates its four extra vectors once (a CG solver has none).
+   IGX_METHOD_MINRES on a solver that is not a saddle-point solver, and any other method on one: IGX_ERR_UNSUPPORTED. */
 int  igx_solver_set_method(igx_solver *solver, int method);
 /* IGX_BREAKDOWN_* of the last solve, 0 if it did not break down (and for CG). */
 int  igx_solver_last_breakdown(const igx_solver *solver);
@@ -958,6 +961,56 @@ int  igx_pair_entries(igx_pair *pair, int kind, const size_t *ij, size_t M, doub
 const double *igx_pair_d_data(const igx_pair *pair);     /* values of the last igx_pair_assemble (NULL before the first) */
 /* Device times of the last igx_pair_assemble: total_ms, fields_ms (0 when the patch still held the fields), entry_ms. */
 int  igx_pair_last_timing(const igx_pair *pair, igx_timing *t);
+
+/* --- Saddle-point systems  [[A, B^T], [B, 0]]  (Stokes) solved on the device with preconditioned MINRES ---
+   A: the nc x nc blocks of a vector-valued form over `patch_u` (velocity, N_u dofs per component), B = [B_0 .. B_{nc-1}]: the
+   values of `pair` (rows: its test space, the pressure, N_p dofs; columns: patch_u).  Vectors have nc * N_u + N_p entries, the
+   velocity components first, component-major.  The solver is a block solver with a pressure part: A is taken block by block with
+   igx_solver_take_block, B with igx_solver_take_pair_block; igx_solver_solve, igx_solver_spmv_d (R K R^T x), igx_solver_precond_d,
+   igx_solver_set_block_kron, igx_solver_set_precond and igx_solver_last_breakdown serve it.  Its method is IGX_METHOD_MINRES
+   (Paige and Saunders; any other: IGX_ERR_UNSUPPORTED): it stops at phi_k <= tol * phi_0, phi MINRES's own estimate of
+   sqrt(r^T P r), read back every check_every iterations; info->relres is the true ||R (b - K u)|| / ||R (b - K ext(g))|| from one
+   more product.  A non-finite scalar (IGX_BREAKDOWN_NONFINITE) or r.(P r) < 0 (IGX_BREAKDOWN_INDEFINITE_PRECOND) stops the solve
+   without converging; u is then the last finite iterate.  Two solves of one system are bit-identical, whatever check_every.
+   The eigen, parabolic, stepping, Newton and multigrid calls: IGX_ERR_UNSUPPORTED.
+
+   ncomp = 2 or 3 and a pair made over patch_u (else IGX_ERR_ARG); fixed[0..nfixed) index all nc * N_u + N_p entries. */
+int  igx_solver_create_saddle(igx_patch *patch_u, igx_pair *pair, int ncomp, const int64_t *fixed, int64_t nfixed, igx_solver **out);
+/* The values the pair holds now (igx_pair_assemble, IGX_FORM or IGX_MASS) become B_q: the device buffer changes hands
+   (igx_pair_d_data is NULL afterwards, the next assembly allocates anew), and B_q^T is formed on the device in the pair layout
+   of the swapped spaces (k_pair_transpose: an exact copy of the bits).  A block taken twice, q out of range, a pair other than
+   the solver's or one without values: IGX_ERR_ARG.  A product or a solve needs every B_q and the diagonal blocks of A. */
+int  igx_solver_take_pair_block(igx_solver *solver, igx_pair *pair, int q);
+/* The pressure part of the block-diagonal preconditioner diag(P_0, .., P_{nc-1}, P_S), selected with the rest by
+   igx_solver_set_precond(IGX_PRECOND_KRON | _JACOBI | _NONE; box and factor arguments NULL).  mode IGX_PRECOND_KRON: scale times
+   the fast-diagonalization inverse (lam_mode IGX_KRON_PRODUCT: (x) M_k^-1) on the box box_lo[k] <= i_k < box_hi[k] of the
+   pressure space (factors as igx_solver_set_precond's), applied to the masked vector and masked again, so that it stays positive
+   definite with a pinned dof.  mode IGX_PRECOND_JACOBI: scale times dinv (host, N_p entries; the box and factor arguments are not
+   read; its entries are not checked: a negative one makes the preconditioner indefinite, which the solve reports as
+   IGX_BREAKDOWN_INDEFINITE_PRECOND).  The velocity part: igx_solver_set_block_kron per component (KRON) or the diagonals of the
+   A_cc (JACOBI).  scale (positive, else IGX_ERR_ARG): the viscosity nu of  -nu Laplace u.  The call resets the preconditioner to
+   IGX_PRECOND_NONE, also when it fails: select it again with igx_solver_set_precond. */
+int  igx_solver_set_saddle_schur(igx_solver *solver, int mode, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
+                                 const double *const *lam, int lam_mode, const double *dinv, double scale);
+/* enable >= 0: whether the following solves remove the mean of the pressure part of the lifted right-hand side (the orthogonal
+   projection onto the range of a system whose kernel is the constant pressure: every velocity dof of the boundary fixed, no
+   pressure dof fixed; with a fixed pressure dof IGX_ERR_ARG) -- the final residual is projected alike; enable < 0: unchanged.
+   mean / norm (either may be NULL): that mean and the norm of that pressure part at the last solve. */
+int  igx_solver_saddle_projection(igx_solver *solver, int enable, double *mean, double *norm);
+/* Inspection calls of a saddle-point solver: no workflow needs them; the tests of the kernels and tools/saddle_timing.py do.
+   igx_solver_download_pair_block: the nnz values of B_q (transposed = 0: in the order of igx_pair_pattern) or of B_q^T
+   (transposed != 0: in the pair layout of the swapped spaces, i.e. in the order of the canonical CSR of the transposed matrix) to
+   the host.  An absent block: IGX_ERR_ARG.
+   igx_solver_saddle_product_d: one product with the whole contract of the row kernels, as the lifting and the MINRES iterations
+   call them: d_y = free ? (d_b ? d_b : 0) + sign * K d_x : 0 over all nc N_u + N_p rows (d_x is NOT masked; d_b may be NULL;
+   d_x and d_y different buffers), and with d_pd not NULL the kernels' dot partials of d_pd . d_y, added up in their fixed order
+   into *dot (dot may be NULL).  The two launches are timed apart.
+   igx_solver_saddle_timing: device ms of the last k_pair_transpose (igx_solver_take_pair_block) and of the velocity-row and the
+   pressure-row launch of the last igx_solver_saddle_product_d; any pointer may be NULL. */
+int  igx_solver_download_pair_block(const igx_solver *solver, int q, int transposed, double *vals);
+int  igx_solver_saddle_product_d(igx_solver *solver, const double *d_x, const double *d_b, double sign, const double *d_pd, double *d_y,
+                                 double *dot);
+int  igx_solver_saddle_timing(const igx_solver *solver, float *transpose_ms, float *u_rows_ms, float *p_rows_ms);
 
 #ifdef __cplusplus
 }

@@ -74,11 +74,12 @@ PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PREC
 MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ,
                'mg': IGX_PRECOND_MG}
 MPVEC_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ}
-IGX_METHOD_CG, IGX_METHOD_BICGSTAB = 0, 1
+IGX_METHOD_CG, IGX_METHOD_BICGSTAB, IGX_METHOD_MINRES = 0, 1, 2
 METHODS = {'cg': IGX_METHOD_CG, 'bicgstab': IGX_METHOD_BICGSTAB}
-IGX_BREAKDOWN_RHO, IGX_BREAKDOWN_ALPHA, IGX_BREAKDOWN_OMEGA, IGX_BREAKDOWN_NONFINITE = 1, 2, 3, 4
+SADDLE_METHODS = dict(METHODS, minres=IGX_METHOD_MINRES)      # (MINRES: saddle-point solvers, and only they)
+IGX_BREAKDOWN_RHO, IGX_BREAKDOWN_ALPHA, IGX_BREAKDOWN_OMEGA, IGX_BREAKDOWN_NONFINITE, IGX_BREAKDOWN_INDEFINITE_PRECOND = 1, 2, 3, 4, 5
 BREAKDOWNS = {0: None, IGX_BREAKDOWN_RHO: 'rho', IGX_BREAKDOWN_ALPHA: 'alpha', IGX_BREAKDOWN_OMEGA: 'omega',
-              IGX_BREAKDOWN_NONFINITE: 'nonfinite'}
+              IGX_BREAKDOWN_NONFINITE: 'nonfinite', IGX_BREAKDOWN_INDEFINITE_PRECOND: 'indefinite_precond'}
 
 
 class SolveInfo(C.Structure):
@@ -310,6 +311,14 @@ SYMBOLS = [
     ('igx_pair_entries', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_size_t, _dp]),
     ('igx_pair_d_data', C.c_void_p, [C.c_void_p]),
     ('igx_pair_last_timing', C.c_int, [C.c_void_p, C.POINTER(Timing)]),
+    ('igx_solver_create_saddle', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_void_p)]),
+    ('igx_solver_take_pair_block', C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ('igx_solver_set_saddle_schur', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_dp), C.POINTER(_dp), C.c_int,
+                                              _dp, C.c_double]),
+    ('igx_solver_saddle_projection', C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    ('igx_solver_download_pair_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
+    ('igx_solver_saddle_product_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, _dp]),
+    ('igx_solver_saddle_timing', C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 ]
 
 _lib = None

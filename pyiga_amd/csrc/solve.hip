@@ -26,8 +26,9 @@
 // and the occupancy query alike; one fast-diagonalization block (FastDiag) is the Kronecker preconditioner of a patch and the
 // local solve of every Schwarz patch; igx_solver_solve forms the lifted right-hand side and hands over to solve_cg or
 // solve_bicgstab.  Newton's method on a patch solver is the same solve for the increment.
-// The time stepping of parabolic problems is in solve_step.hip and the block eigen-solver in solve_eig.hip; solve_internal.h holds
-// the solver structure and what the three units call of each other.
+// The time stepping of parabolic problems is in solve_step.hip, the block eigen-solver in solve_eig.hip and the saddle-point solver
+// (MINRES; its entry points here hand over where s->saddle is set) in solve_saddle.hip; solve_internal.h holds the solver structure
+// and what the units call of each other.
 #include "solve_internal.h"
 
 #include <algorithm>
@@ -939,6 +940,8 @@ int apply_fastdiag(hipStream_t st, const FastDiag &F, const double *x, double *y
     return launch_kron_plan(st, F.kr, t, y, W2);
 }
 
+int spmv_group_width(long long maxlen) { return spmv_gw(maxlen); }
+
 void mask_copy(hipStream_t st, const igx_solver *s, const double *x, double *y)
 {
     k_mask_copy<<<(unsigned)((s->n + 255) / 256), 256, 0, st>>>(s->n, s->d_mask, x, y);
@@ -966,6 +969,7 @@ int sum_partials(hipStream_t st, igx_solver *s, unsigned nb, double *sum)
 
 int check_values(const igx_solver *s, const char *what)
 {
+    if (s->saddle) return saddle_check_values(s, what);
     if (s->ncomp > 1) {                       // (the blocks are the solver's own: only a missing diagonal one is refused)
         for (int c = 0; c < s->ncomp; ++c)
             if (!s->block.blk[c * s->ncomp + c]) {
@@ -1015,6 +1019,7 @@ static unsigned spmv_blocks(const igx_solver *s)
 // k_block_spmv on the blocks of a block solver, k_csr_block_spmv on those of a multipatch block solver
 int spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part)
 {
+    if (s->saddle) return saddle_spmv(st, s, x, b, sign, y, pd, part);
     const unsigned nb = spmv_blocks(s);
     if (s->mp && s->ncomp > 1) {
         const igx_multipatch *m = s->mp;
@@ -1106,7 +1111,7 @@ void free_solver(igx_solver *s)
 {
     mg_free(s);
     eig_free(s);
-    s->bicg.release(); s->block.release(); s->par.release(); s->step.release();
+    s->bicg.release(); s->block.release(); s->par.release(); s->step.release(); s->sad.release();
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
     (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
     if (s->have_ev)
@@ -1366,7 +1371,7 @@ static int init_solver(igx_solver *s, const int64_t *fixed, int64_t nfixed, long
 // a solver over the values of `kind` the patch holds (the kind itself checked by the caller; values_now: they must be there now);
 // ncomp > 1: a block solver of ncomp components, whose blocks are taken from the patch later (igx_solver_take_block)
 int create_patch_solver(igx_patch *pt, int kind, int ncomp, bool values_now, const int64_t *fixed, int64_t nfixed, igx_solver **out,
-                        const char *what)
+                        const char *what, long long extra)
 {
     if (pt->boxed || pt->row_lo != 0 || pt->row_hi != pt->nrows_total) {
         set_error("%s: whole patches only (no row slab, no span box)", what);
@@ -1378,7 +1383,7 @@ int create_patch_solver(igx_patch *pt, int kind, int ncomp, bool values_now, con
     }
     if (hipSetDevice(pt->ctx->device) != hipSuccess) { set_error("%s: hipSetDevice failed", what); return IGX_ERR_HIP; }
     igx_solver *s = new igx_solver;
-    s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->ncomp = ncomp; s->n = ncomp * pt->nrows_total;
+    s->ctx = pt->ctx; s->pt = pt; s->kind = kind; s->dim = pt->dim; s->ncomp = ncomp; s->n = ncomp * pt->nrows_total + extra;
     for (int k = 0; k < pt->dim; ++k) s->N[k] = pt->ax[k].N;
     // per-axis tables as a 3D layout (2D: a one-dof outer axis in front)
     const int off = 3 - pt->dim;
@@ -1411,21 +1416,22 @@ int create_patch_solver(igx_patch *pt, int kind, int ncomp, bool values_now, con
 // the box lo[k] <= i_k < hi[k] (nb[k] = hi[k] - lo[k] out) must be exactly the free dofs of the component at `base` (a patch
 // solver: 0): the fast-diagonalization inverse leaves everything outside it at 0
 static int check_free_box(const igx_solver *s, long long base, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
-                   const double *const *lam, int nb[3], const char *what)
+                   const double *const *lam, int nb[3], const char *what, const int *N, bool free_is_box)
 {
     const int d = s->dim;
     for (int k = 0; k < d; ++k) {
-        if (box_lo[k] < 0 || box_hi[k] > s->N[k] || box_lo[k] >= box_hi[k] || !U[k] || !lam[k]) {
+        if (box_lo[k] < 0 || box_hi[k] > N[k] || box_lo[k] >= box_hi[k] || !U[k] || !lam[k]) {
             set_error("%s: bad free box [%d, %d) on axis %d", what, box_lo[k], box_hi[k], k);
             return IGX_ERR_ARG;
         }
         nb[k] = box_hi[k] - box_lo[k];
     }
+    if (!free_is_box) return IGX_OK;
     long long I = 0;
     int i[3] = {0, 0, 0};
-    for (i[0] = 0; i[0] < s->N[0]; ++i[0])
-        for (i[1] = 0; i[1] < (d > 1 ? s->N[1] : 1); ++i[1])
-            for (i[2] = 0; i[2] < (d > 2 ? s->N[2] : 1); ++i[2], ++I) {
+    for (i[0] = 0; i[0] < N[0]; ++i[0])
+        for (i[1] = 0; i[1] < (d > 1 ? N[1] : 1); ++i[1])
+            for (i[2] = 0; i[2] < (d > 2 ? N[2] : 1); ++i[2], ++I) {
                 bool in = true;
                 for (int k = 0; k < d; ++k) in = in && i[k] >= box_lo[k] && i[k] < box_hi[k];
                 if (in != (s->h_free[base + I] != 0)) {
@@ -1439,10 +1445,10 @@ static int check_free_box(const igx_solver *s, long long base, const int32_t *bo
 // the inverse on the box of nb dofs from box_lo on of the component at `base`, in the full-length vectors: (x) U_k^T reads the box
 // of r, (x) U_k writes it into z
 FastDiag box_fastdiag(const igx_solver *s, long long base, const int32_t *box_lo, const int *nb, const double *d_fac, int lam_mode,
-                      long long batch)
+                      long long batch, const int *dims)
 {
     long long full_stride[4], off = base;
-    box_strides(s->dim, s->N, full_stride);
+    box_strides(s->dim, dims ? dims : s->N, full_stride);
     for (int k = 0; k < s->dim; ++k) off += box_lo[k] * full_stride[k];
     return make_fastdiag(s->dim, nb, d_fac, full_stride, off, lam_mode, batch);
 }
@@ -1451,12 +1457,13 @@ FastDiag box_fastdiag(const igx_solver *s, long long base, const int32_t *box_lo
 // arguments, packs the factors and puts them on the device at d_fac in place of the previous ones (synchronised before and
 // after).  *reset (or null) becomes IGX_PRECOND_NONE before anything is freed, whatever fails later.  nb out
 int box_fastdiag_setup(igx_solver *s, long long base, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
-                       const double *const *lam, int lam_mode, const char *what, int *reset, double *&d_fac, int nb[3])
+                       const double *const *lam, int lam_mode, const char *what, int *reset, double *&d_fac, int nb[3], const int *dims,
+                       bool free_is_box)
 {
     if (!box_lo || !box_hi || !U || !lam) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
     if (lam_mode != IGX_KRON_SUM && lam_mode != IGX_KRON_PRODUCT) { set_error("%s: unknown lam_mode %d", what, lam_mode); return IGX_ERR_ARG; }
     nb[0] = nb[1] = nb[2] = 1;
-    if (int rc = check_free_box(s, base, box_lo, box_hi, U, lam, nb, what)) return rc;
+    if (int rc = check_free_box(s, base, box_lo, box_hi, U, lam, nb, what, dims ? dims : s->N, free_is_box)) return rc;
     std::vector<double> h;
     pack_fastdiag(h, s->dim, nb, U, lam);
     if (reset) *reset = IGX_PRECOND_NONE;
@@ -1474,6 +1481,7 @@ SolverRef solver_ref(const igx_solver *s)
 
 int refuse_multipatch_block(const igx_solver *s, const char *what)
 {
+    if (s && s->saddle) return refuse_saddle(s, what);           // (what a multipatch block solver does not serve, a saddle solver does not either)
     if (!s || !s->mp || s->ncomp < 2) return IGX_OK;
     set_error("%s: a multipatch block solver (igx_solver_create_multipatch_block) serves the linear solves, the SpMV and its "
               "Jacobi and Schwarz preconditioners only", what);
@@ -1535,6 +1543,13 @@ int igx_solver_create_general(igx_patch *pt, int kind, const int64_t *fixed, int
 int igx_solver_set_method(igx_solver *s, int method)
 {
     if (!s) { set_error("igx_solver_set_method: null solver"); return IGX_ERR_ARG; }
+    const bool known = method == IGX_METHOD_CG || method == IGX_METHOD_BICGSTAB || method == IGX_METHOD_MINRES;
+    if (known && s->saddle != (method == IGX_METHOD_MINRES)) {
+        set_error("igx_solver_set_method: MINRES is the method of saddle-point solvers (igx_solver_create_saddle), and their only one: "
+                  "the matrix [[A, B^T], [B, 0]] is symmetric indefinite");
+        return IGX_ERR_UNSUPPORTED;
+    }
+    if (method == IGX_METHOD_MINRES) return IGX_OK;
     if (method == IGX_METHOD_CG) {
         if (s->ncomp > 1 && !s->symmetric) {
             set_error("igx_solver_set_method: CG needs a symmetric positive definite matrix; the block solver was made as non-symmetric");
@@ -1562,7 +1577,7 @@ int igx_solver_set_method(igx_solver *s, int method)
     return IGX_OK;
 }
 
-int igx_solver_last_breakdown(const igx_solver *s) { return s ? s->bicg.breakdown : 0; }
+int igx_solver_last_breakdown(const igx_solver *s) { return !s ? 0 : s->saddle ? s->sad.breakdown : s->bicg.breakdown; }
 
 int igx_solver_create_multipatch(igx_multipatch *mp, const int64_t *fixed, int64_t nfixed, igx_solver **out)
 {
@@ -1677,7 +1692,8 @@ int igx_solver_set_block_kron(igx_solver *s, int comp, const int32_t *box_lo, co
 {
     const char *what = "igx_solver_set_block_kron";
     if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
-    if (int rc = refuse_multipatch_block(s, what)) return rc;
+    if (!s->saddle)                                 // (a saddle solver: the velocity part of its block-diagonal preconditioner)
+        if (int rc = refuse_multipatch_block(s, what)) return rc;
     if (s->ncomp < 2) { set_error("%s: not a block solver (igx_solver_create_block)", what); return IGX_ERR_ARG; }
     if (comp < 0 || comp >= s->ncomp) { set_error("%s: component %d of %d", what, comp, s->ncomp); return IGX_ERR_ARG; }
     IGX_HIP(hipSetDevice(s->ctx->device));
@@ -1732,6 +1748,7 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
     hipStream_t st = s->ctx->stream;
     s->step.step_precond = -1;                                // (a stepping session's preconditioner data is replaced: set it again)
     s->step.pc_vals = -1;
+    if (s->saddle) return saddle_set_precond(s, precond);
     if (precond == IGX_PRECOND_NONE) { s->precond = precond; return IGX_OK; }
     if (precond == IGX_PRECOND_JACOBI) {
         if (int rc = check_values(s, "igx_solver_set_precond")) return rc;
@@ -1917,6 +1934,13 @@ int igx_solver_precond_d(igx_solver *s, const double *d_r, double *d_z)
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     const unsigned nb = (unsigned)((s->n + 255) / 256);
+    if (s->saddle) {                                       // (the masked r in s->w: the pressure inverse reads fixed dofs as 0)
+        mask_copy(st, s, d_r, s->w);
+        if (int rc = saddle_apply_precond(st, s, s->w, d_z)) return rc;
+        IGX_HIP(hipGetLastError());
+        IGX_HIP(hipStreamSynchronize(st));
+        return IGX_OK;
+    }
     switch (s->precond) {
     case IGX_PRECOND_JACOBI: k_scale<<<nb, 256, 0, st>>>(s->n, s->dinv, d_r, d_z); break;
     case IGX_PRECOND_KRON:
@@ -1990,6 +2014,7 @@ static int finish_solve(hipStream_t st, igx_solver *s, const double *gvals, doub
 int solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool x0_in_x, double tol, int maxiter, int check_every, int timed,
                  igx_solve_info &inf, bool from_guess)
 {
+    if (s->saddle) return saddle_solve_lifted(st, s, lift, x0_in_x, tol, maxiter, check_every, timed, inf);
     const long long n = s->n;
     const size_t nbytes = (size_t)n * sizeof(double);
     if (!x0_in_x) IGX_HIP(hipMemsetAsync(s->x, 0, nbytes, st));
@@ -2036,6 +2061,7 @@ int igx_solver_solve(igx_solver *s, const double *b, const double *gvals, const 
     if (int rc = check_values(s, "igx_solver_solve")) return rc;
     if (check_every < 1) check_every = 1;
     s->bicg.breakdown = 0;
+    s->sad.breakdown = 0;
     IGX_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     const long long n = s->n;

@@ -187,6 +187,47 @@ struct StepState {
 
 struct EigState;                              // the session of the block eigen-solver (solve_eig.hip)
 
+// per-axis tables of a rectangular value layout (the matrix of a pair, or its transpose), as a 3D layout like Geom: row
+// (i0, i1, i2) of the space N holds the columns prod_k [lo_k[i_k], hi_k[i_k]) of the space M in lexicographic order
+struct RectGeom {
+    int N[3], M[3];
+    const int *lo[3], *hi[3], *rp[3];
+    long long S1, S2;
+    long long nrows;
+};
+
+// saddle-point solver (igx_solver_create_saddle, solve_saddle.hip): [[A, B^T], [B, 0]] with the blocks A_pq
+// of the block solver (block.blk) over nu velocity dofs per component and B_q over np pressure dofs; n = ncomp nu + np
+struct SaddleState {
+    const igx_pair *pair = nullptr;           // the pair the solver was made over (its tables were copied: identity only)
+    long long nu = 0, np = 0, nnzB = 0;
+    int Np[3] = {1, 1, 1};                    // pressure dofs per axis (dim of them)
+    double *B[3] = {}, *BT[3] = {};           // B_q (taken from the pair, owned) and B_q^T in the layout of the swapped spaces
+    int *d_rtab = nullptr;                    // the tables of gB and gT
+    RectGeom gB{}, gT{};
+    int gw_u = 4, gw_p = 4, nb_u = 1, nb_p = 1;       // group width and resident blocks of each row kernel (fixed per solver)
+    int schur = -1;                           // the pressure part of the preconditioner: IGX_PRECOND_JACOBI / _KRON, -1: not set
+    FastDiag skron{};
+    double *d_skron = nullptr, *d_sdinv = nullptr;
+    double sscale = 1.0;
+    long long swlen = 0;                      // the pressure box of skron (the work buffers d_W hold two of the largest box)
+    double *d_mvec = nullptr;                 // MINRES: r1 | r2 | y | v | w | w1 | w2, n each (allocated with the solver)
+    double *d_msc = nullptr;                  // its scalars (MS_*), written by k_fin_minres only
+    int breakdown = 0;                        // IGX_BREAKDOWN_* of the last solve
+    int project = 0;                          // the solves remove the mean of the pressure part of the lifted right-hand side
+    double rhs_mean = 0.0, rhs_norm = 0.0;    // of that pressure part at the last solve
+    long long maxT = 1;                       // longest row of B^T
+    // device times (igx_solver_saddle_timing): of the last k_pair_transpose, and of the velocity- and the pressure-row launch of
+    // the last igx_solver_saddle_product_d
+    float transpose_ms = 0.0f, u_ms = 0.0f, p_ms = 0.0f;
+    void release()
+    {
+        for (double *v : B) (void)hipFree(v);
+        for (double *v : BT) (void)hipFree(v);
+        (void)hipFree(d_rtab); (void)hipFree(d_skron); (void)hipFree(d_sdinv); (void)hipFree(d_mvec); (void)hipFree(d_msc);
+    }
+};
+
 } // namespace igx
 
 struct igx_solver {
@@ -231,6 +272,8 @@ struct igx_solver {
     // block eigen-solver (igx_solver_eig_*, solve_eig.hip): made by its first call, or null
     igx::EigState *eig = nullptr;
     double *d_mass = nullptr;                 // a multipatch solver's second matrix (igx_solver_set_mass_d), owned
+    bool saddle = false;                      // made by igx_solver_create_saddle: n = ncomp g.nrows + sad.np, MINRES only
+    igx::SaddleState sad;
 };
 
 namespace igx {
@@ -244,15 +287,19 @@ int spmv_values(hipStream_t st, const igx_solver *s, const double *vals, const d
 int solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool x0_in_x, double tol, int maxiter, int check_every, int timed,
                  igx_solve_info &inf, bool from_guess = false);
 int apply_fastdiag(hipStream_t st, const FastDiag &F, const double *x, double *y, double *const W[2]);
+// (dims: the dofs per axis of the space the box lies in, default the patch's s->N; a box that need not be the free dofs: free_is_box
+// false -- the caller masks what the inverse returns)
 int box_fastdiag_setup(igx_solver *s, long long base, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
-                       const double *const *lam, int lam_mode, const char *what, int *reset, double *&d_fac, int nb[3]);
+                       const double *const *lam, int lam_mode, const char *what, int *reset, double *&d_fac, int nb[3],
+                       const int *dims = nullptr, bool free_is_box = true);
 FastDiag box_fastdiag(const igx_solver *s, long long base, const int32_t *box_lo, const int *nb, const double *d_fac, int lam_mode,
-                      long long batch = 1);
+                      long long batch = 1, const int *dims = nullptr);
 int alloc_fastdiag_work(igx_solver *s, long long wlen);
 int upload_replacing(hipStream_t st, const std::vector<double> &h, double *&d_buf);
 bool create_args_ok(const void *owner, const int64_t *fixed, int64_t nfixed, igx_solver **out, const char *what);
+// (extra: entries of the vectors past the ncomp components of the patch -- the pressure dofs of a saddle solver)
 int create_patch_solver(igx_patch *pt, int kind, int ncomp, bool values_now, const int64_t *fixed, int64_t nfixed, igx_solver **out,
-                        const char *what);
+                        const char *what, long long extra = 0);
 int init_bicgstab(igx_solver *s, const char *what);
 void free_solver(igx_solver *s);
 int close_call(hipStream_t st, hipEvent_t begin, hipEvent_t end, const char *what, float &total_ms);
@@ -268,8 +315,22 @@ void jacobi_diagonal(hipStream_t st, const igx_solver *s, const double *vals, do
 // k_fin: the first nb partial sums of s->d_part added up in their fixed order, read back into *sum (synchronised)
 int sum_partials(hipStream_t st, igx_solver *s, unsigned nb, double *sum);
 
+int spmv_group_width(long long maxlen);       // spmv_gw: the group width of the row kernels for a longest row of maxlen entries
+
+// ---- solve_saddle.hip
+// IGX_ERR_UNSUPPORTED (with igx_last_error) if s is a saddle-point solver, which serves MINRES solves, the product and its
+// preconditioner only; else IGX_OK
+int refuse_saddle(const igx_solver *s, const char *what);
+int saddle_check_values(const igx_solver *s, const char *what);
+int saddle_spmv(hipStream_t st, const igx_solver *s, const double *x, const double *b, double sign, double *y, const double *pd, double *part,
+                hipEvent_t mid = nullptr);
+int saddle_set_precond(igx_solver *s, int precond);
+int saddle_apply_precond(hipStream_t st, igx_solver *s, const double *r, double *z);
+int saddle_solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool x0_in_x, double tol, int maxiter, int check_every, int timed,
+                        igx_solve_info &inf);
+
 // ---- solve_eig.hip
-void eig_free(igx_solver *s);                 // the eigen-solver's state and the mass matrix of a multipatch solver
+void eig_free(igx_solver *s);                // the eigen-solver's state and the mass matrix of a multipatch solver
 void eig_drop_block_kron(igx_solver *s);      // a block solver's Kronecker factors were replaced: the eigen pieces select them again
 
 } // namespace igx

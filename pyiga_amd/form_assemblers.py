@@ -125,9 +125,10 @@ class FormAssembler:
 
     `kvs`: a tuple of knot vectors, or ``(kvs0, kvs1)`` with the space of every function as the third element of its `bfuns`
     entry (``space_roles``); the matrix of a form over two spaces has the rows of the test space and the columns of the
-    trial space, ``self.kvs = (kvs_trial, kvs_test)``."""
+    trial space, ``self.kvs = (kvs_trial, kvs_test)``.  `patch`: a ``DevicePatch`` over `kvs` to assemble a volume form on
+    (``solvers.SaddlePointSystem``: both of its forms on one patch); it stays the caller's."""
 
-    def __init__(self, kvs, geo, form, bfuns=None, inputs=None, boundary=None, device=None, lazy_patch=False):
+    def __init__(self, kvs, geo, form, bfuns=None, inputs=None, boundary=None, device=None, lazy_patch=False, patch=None):
         kvs, kvs_test = space_roles(kvs, form, bfuns, geo, boundary)
         self.kvs = (kvs, kvs if kvs_test is None else kvs_test)
         self.pair = None
@@ -148,7 +149,10 @@ class FormAssembler:
         elif self.boundary is None:
             assert d in (2, 3), 'vector-valued forms are assembled for 2D and 3D patches'
             self._tkvs = kvs
-            if kvs_test is None:
+            if patch is not None:              # the caller's patch over `kvs` (a volume form on one space: its Gauss rule is used)
+                assert kvs_test is None and tuple(patch.ndofs) == tuple(kv.numdofs for kv in kvs)
+                self.patch = patch
+            elif kvs_test is None:
                 self.patch = DevicePatch(kvs, geo, device=device)
             else:                              # trial space = the patch; the test space rides on its Gauss grid and fields
                 self.patch = DevicePatch(kvs, geo, device=device, nqp=self.nqp)

@@ -653,6 +653,197 @@ class VectorFormSystem(_VectorBlocks, _DeviceSystem):
         return self._solve(self.b, tol, maxiter, self.default_precond if precond == 'auto' else precond, x0, check_every, timed)
 
 
+class SaddlePointSystem(_VectorBlocks, _DeviceSystem):
+    """The Stokes-type saddle-point problem ``[[A, B^T], [B, 0]] (u, p) = (f, 0)``, ``(u, p) = g`` on the dofs of `bcs`, on one
+    patch, assembled and solved on the device with preconditioned MINRES (the reference's solve-stokes notebook without its
+    ``bmat`` and ``spsolve``).
+
+    `kvs` = ``(kvs_u, kvs_p)``: the velocity space (every component) and the pressure space, e.g. a Taylor-Hood pair, on one
+    mesh.  `a`: the velocity form in ``u`` and ``v`` (``ncomp`` components each), times `viscosity`; its coefficient tables must
+    be symmetric.  `b`: the form over the two spaces in ``u`` (space 0) and ``p`` (space 1), assembled as
+    ``form_assemblers.FormAssembler`` assembles forms over two spaces (its role rule and mesh checks apply).  Both are assembled
+    on one ``DevicePatch`` over `kvs_u` whose Gauss rule has ``max(p over both spaces) + 1`` points per span -- the blocks of `a`
+    are integrated with that rule too, not with the ``p_u + 1`` points ``assemble.assemble`` takes for `a` alone.
+    Vectors have ``nc * N_u + N_p`` entries: the velocity components first, component-major, then the pressure (the notebook's
+    ordering).  `bcs`: ``(indices, values)`` in that numbering.  `rhs`: a full vector, a linear form string in the velocity test
+    function ``v``, or a scalar (every velocity entry); the pressure part of the latter two is 0.
+
+    ``solve()`` returns the full vector; ``split(u)`` gives the coefficient arrays of velocity and pressure."""
+    PRESSURES = ('auto', 'mean', None)
+
+    def __init__(self, kvs, geo, bcs, rhs=0.0, a='inner(grad(u), grad(v)) * dx', b='div(u) * p * dx', ncomp=None, viscosity=1.0,
+                 args=None, **inputs):
+        from . import assemble, tforms
+        from .form_assemblers import FormAssembler, _full_table, is_space_pair
+        if not is_space_pair(kvs):
+            raise ValueError('SaddlePointSystem needs kvs=(kvs_u, kvs_p): the velocity and the pressure space')
+        self.kvs = tuple(kvs[0])
+        self.kvs_p = tuple(kvs[1])
+        d = len(self.kvs)
+        nc = d if ncomp is None else int(ncomp)
+        if nc not in (2, 3):
+            raise ValueError('SaddlePointSystem solves systems of 2 or 3 velocity components, not %d' % nc)
+        if not (viscosity > 0.0 and np.isfinite(viscosity)):
+            raise ValueError('viscosity must be positive')
+        self.ncomp, self.viscosity = nc, float(viscosity)
+        self.ndofs = tuple(int(kv.numdofs) for kv in self.kvs)
+        self.ndofs_p = tuple(int(kv.numdofs) for kv in self.kvs_p)
+        self.N, self.Np = int(np.prod(self.ndofs)), int(np.prod(self.ndofs_p))
+        self.n = nc * self.N + self.Np
+        idx, _ = _bcs_arrays(bcs)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+            raise ValueError('bcs: dof %d outside of the %d x %d + %d unknowns' % (idx.max() if idx.max() >= self.n else idx.min(),
+                                                                                  nc, self.N, self.Np))
+        args = dict(args or {})
+        args.update(inputs)
+        fargs = {k: v for k, v in args.items() if k != 'geo'}
+        bf_a, bf_b = [('u', nc), ('v', nc)], [('u', nc, 0), ('p', 1, 1)]
+        # (the structure of the tables at one point, before anything exists on the device; the values are checked below)
+        _, _, t1, _ = tforms.evaluate(a, (1,) * d, np.zeros((1,) * d + (d,)), fargs, bf_a)
+        if not symmetric_block_tables(t1):
+            raise ValueError('SaddlePointSystem: the coefficient tables of a=%r are not symmetric; non-symmetric velocity forms '
+                             '(Oseen, Navier-Stokes: BiCGStab or GMRES on the saddle-point matrix) are not supported' % (a,))
+        self.asm_b = FormAssembler((self.kvs, self.kvs_p), geo, b, bfuns=bf_b, inputs=fargs)
+        self.patch, self.pair = self.asm_b.patch, self.asm_b.pair
+        try:                                   # (from here on a patch exists on the device: close() on any failure)
+            if self.pair is None:
+                raise ValueError('SaddlePointSystem: b=%r does not couple the two spaces' % (b,))
+            self.asm_a = FormAssembler(self.kvs, geo, a, bfuns=bf_a, inputs=fargs, patch=self.patch)
+            table = self.asm_a._table
+            if not symmetric_block_tables(table):
+                raise ValueError('SaddlePointSystem: the coefficient tables of a=%r are not symmetric; non-symmetric velocity '
+                                 'forms (Oseen, Navier-Stokes: BiCGStab or GMRES on the saddle-point matrix) are not '
+                                 'supported' % (a,))
+            if self.viscosity != 1.0:
+                table = [[[[None if e is None else self.viscosity * np.asarray(e, dtype=np.float64) for e in row] for row in tab]
+                          for tab in trow] for trow in table]
+            if isinstance(rhs, str):
+                f = assemble.assemble(rhs, self.kvs, args=dict(fargs, geo=geo), bfuns=[('v', nc)], layout='blocked')
+                rhs = np.concatenate((np.asarray(f, dtype=np.float64).ravel(), np.zeros(self.Np)))
+            elif np.ndim(rhs) == 0:
+                rhs = np.concatenate((np.full(nc * self.N, float(rhs)), np.zeros(self.Np)))
+            self.b = np.ascontiguousarray(rhs, dtype=np.float64).ravel()
+            if self.b.size != self.n:
+                raise ValueError('right-hand side has %d entries, the system %d x %d + %d' % (self.b.size, nc, self.N, self.Np))
+            self._ctx = self.patch.ctx
+            self.method = 'minres'
+            self._attach('igx_solver_create_saddle', (self.patch.handle, self.pair.handle, nc), bcs, 'minres', 'minres')
+            self._take_blocks(table)
+            lib = _lib.load()
+            for q in range(nc):
+                self.patch.set_form(_full_table(self.asm_b._table[0][q], d))
+                self.pair.assemble('form', to_host=False)
+                _lib.check(lib.igx_solver_take_pair_block(self.handle, self.pair.handle, q), 'igx_solver_take_pair_block')
+        except Exception:
+            self.close()
+            raise
+        self._component_boxes()
+        pidx = self.bc_indices[self.bc_indices >= nc * self.N] - nc * self.N
+        self.pressure_fixed = pidx
+        self.enclosed = pidx.size == 0 and all(box is not None and all(a_ == 1 for a_ in box[0]) and
+                                               all(b_ == n_ - 1 for b_, n_ in zip(box[1], self.ndofs)) for box in self.boxes)
+        self._velocity_factors_set = False
+
+    def set_method(self, method):
+        """'minres' is the only method of a saddle-point system; 'cg' and 'bicgstab' raise IgxError (IGX_ERR_UNSUPPORTED)."""
+        if method not in _lib.SADDLE_METHODS:
+            raise ValueError("unknown method %r: 'minres'" % (method,))
+        if method != self.method:
+            _lib.check(_lib.load().igx_solver_set_method(self._live(), _lib.SADDLE_METHODS[method]), 'igx_solver_set_method')
+            self.method = method
+
+    def _drop_owner(self):
+        if getattr(self, 'pair', None) is not None:
+            self.pair.close()
+        self.pair = None
+        _DeviceSystem._drop_owner(self)
+
+    def kron_factors(self):
+        """As ``_VectorBlocks.kron_factors``, of `viscosity` times the parametric Laplacian."""
+        return [(lo, hi, U, [self.viscosity * l for l in lam], mode) for lo, hi, U, lam, mode in _VectorBlocks.kron_factors(self)]
+
+    def schur_factors(self):
+        """``(lo, hi, U, lam, mode)`` of the pressure part ``(x) M_k^-1``: on the whole pressure space, or on the free box when the
+        fixed pressure dofs are whole sides."""
+        box = dirichlet_box(self.ndofs_p, self.pressure_fixed)
+        lo, hi = box if box is not None else ((0,) * len(self.ndofs_p), self.ndofs_p)
+        return (lo, hi) + fastdiag_factors(self.kvs_p, lo, hi, False)
+
+    def _set_schur(self, h, key):
+        lib = _lib.load()
+        if key == 'kron':
+            lo, hi, U, lam, mode = self.schur_factors()
+            lo_, hi_, Up, Lp = _box_args(lo, hi, U, lam)
+            _lib.check(lib.igx_solver_set_saddle_schur(h, _lib.IGX_PRECOND_KRON, lo_, hi_, Up, Lp, mode, None, self.viscosity),
+                       'igx_solver_set_saddle_schur')
+        else:                                  # the inverse diagonal of (x) M_k
+            from .assemble import bsp_mass_1d
+            diag = np.ones(1)
+            for kv in self.kvs_p:
+                diag = np.multiply.outer(diag, _dense(bsp_mass_1d(kv)).diagonal()).ravel()
+            dinv = np.ascontiguousarray(1.0 / diag)
+            _lib.check(lib.igx_solver_set_saddle_schur(h, _lib.IGX_PRECOND_JACOBI, None, None, None, None, 0, _lib.dptr(dinv),
+                                                       self.viscosity), 'igx_solver_set_saddle_schur')
+
+    def set_precond(self, precond):
+        """'kron': ``diag(F_0, .., F_{nc-1}, viscosity (x) M_k^-1)`` with ``F_c`` the fast diagonalization of `viscosity` times the
+        parametric Laplacian on the free box of component c; 'jacobi': the inverse diagonals of the ``A_cc`` and of the pressure
+        mass matrix; None."""
+        key = precond if precond is not None else 'none'
+        if key not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        if key == self._precond:
+            return
+        if key == 'kron' and not self._velocity_factors_set:
+            self._set_block_kron(h)
+            self._velocity_factors_set = True
+        if key != 'none':
+            self._set_schur(h, key)
+        _lib.check(_lib.load().igx_solver_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_set_precond')
+        self._precond = key
+
+    def solve(self, tol=1e-8, maxiter=1000, precond='auto', pressure='auto', x0=None, check_every=1, timed=False):
+        """Preconditioned MINRES to ``phi_k <= tol * phi_0`` (MINRES's estimate of ``sqrt(r^T P r)``); returns the full vector
+        (Dirichlet values included).  ``info['relres']`` is the true relative residual from one more product, ``info['breakdown']``
+        None, 'nonfinite' or 'indefinite_precond'.
+
+        `precond`: 'auto' ('kron' when the Dirichlet dofs of every velocity component are whole sides, else 'jacobi'), 'kron',
+        'jacobi' or None.  `pressure`: when every velocity component is fixed on the whole boundary and no pressure dof is, the
+        matrix is singular with the constant pressure (all coefficients 1) as its kernel; 'auto' and 'mean' then remove the
+        mean of the lifted pressure right-hand side (warning if it exceeds 1e-10 of its norm: the data is incompatible), solve
+        unpinned and shift the pressure so that its first coefficient ('auto', the notebook's normalisation) or its coefficient
+        mean ('mean') is 0.  None does nothing of this: an outflow boundary, or a pinned dof in `bcs`."""
+        if pressure not in self.PRESSURES:
+            raise ValueError("unknown pressure %r: 'auto', 'mean' or None" % (pressure,))
+        if precond != 'auto' and (precond if precond is not None else 'none') not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        lib = _lib.load()
+        project = pressure is not None and self.enclosed
+        _lib.check(lib.igx_solver_saddle_projection(h, 1 if project else 0, None, None), 'igx_solver_saddle_projection')
+        u = self._solve(self.b, tol, maxiter, self.default_precond if precond == 'auto' else precond, x0, check_every, timed)
+        if project:
+            mean, norm = C.c_double(), C.c_double()
+            _lib.check(lib.igx_solver_saddle_projection(h, -1, C.byref(mean), C.byref(norm)), 'igx_solver_saddle_projection')
+            self.info.update(rhs_mean=mean.value, rhs_norm=norm.value)
+            if abs(mean.value) > 1e-10 * norm.value:
+                import warnings
+                warnings.warn('SaddlePointSystem: the pressure right-hand side has mean %.3e against a norm of %.3e: the data is '
+                              'not compatible with an enclosed flow; its mean was removed' % (mean.value, norm.value))
+            nv = self.ncomp * self.N
+            u[nv:] -= u[nv] if pressure == 'auto' else u[nv:].mean()
+        return u
+
+    def split(self, u):
+        """``(U, P)``: the velocity coefficients of shape ``ndofs_u + (nc,)`` and the pressure coefficients of shape ``ndofs_p``,
+        ready for ``BSplineFunc(kvs_u, U)`` and ``BSplineFunc(kvs_p, P)``."""
+        u = np.asarray(u)
+        nv = self.ncomp * self.N
+        U = np.stack([u[c * self.N:(c + 1) * self.N].reshape(self.ndofs) for c in range(self.ncomp)], axis=-1)
+        return U, u[nv:].reshape(self.ndofs_p)
+
+
 def _test_function_name(problem, bfuns):
     """The name of the test function of the bilinear form `problem` (the last of its basis functions)."""
     from . import tforms
