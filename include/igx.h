@@ -1012,6 +1012,38 @@ int  igx_solver_saddle_product_d(igx_solver *solver, const double *d_x, const do
                                  double *dot);
 int  igx_solver_saddle_timing(const igx_solver *solver, float *transpose_ms, float *u_rows_ms, float *p_rows_ms);
 
+/* --- Restarted GMRES on a saddle-point solver: Oseen systems  [[nu A + N(w), B^T], [B, 0]]   ---
+   The velocity blocks taken with igx_solver_take_block may form a non-symmetric matrix (a frozen-wind convection term added to
+   the viscous one); MINRES is then the wrong method, and this call selects right-preconditioned GMRES(restart) for the
+   following igx_solver_solve calls.  The solver's method stays IGX_METHOD_MINRES: that constant names the solver family
+   (saddle-point), which igx_solver_set_method guards; the Krylov method within the family is chosen here.
+   restart in 1..128 (else IGX_ERR_ARG): the basis of (restart + 1) * n doubles and the small arrays (Hessenberg column,
+   rotations, g, y, the triangular factor) are allocated once, and again only for a larger restart.  restart = 0 returns to MINRES
+   and frees nothing.  triangular != 0: igx_solver_set_precond's KRON or JACOBI parts are applied as the block upper-triangular
+   preconditioner, the solve with [[F, B^T], [0, -S]] -- z_p = -P_S r_p, z_u = P_F (r_u - B^T z_p) -- instead of diag(P_F, P_S),
+   also by igx_solver_precond_d; it is not symmetric, so with restart = 0 it is IGX_ERR_ARG.  Any solver that is not a
+   saddle-point solver: IGX_ERR_UNSUPPORTED.
+   The solve stops at |g_{j+1}| <= tol * ||r0||, GMRES's own residual norm, read back every check_every steps and at the end of
+   every cycle; at a restart the residual is formed again with a product.  info->iterations counts Arnoldi steps, info->relres is
+   the true relative residual as for MINRES.  h_{j+1,j} = 0 (the lucky breakdown) counts as converged; a non-finite scalar stops
+   the solve with IGX_BREAKDOWN_NONFINITE before any update of u by that cycle.  Two solves are bit-identical, whatever
+   check_every. */
+int  igx_solver_set_gmres(igx_solver *solver, int restart, int triangular);
+/* Restarts of the last GMRES solve (cycles after the first). */
+int  igx_solver_gmres_restarts(const igx_solver *solver);
+/* Inspection calls of GMRES: no workflow needs them; the tests of the kernels and tools/oseen_timing.py do.  All need GMRES
+   selected, and 1 <= ncols <= restart + 1.
+   igx_solver_gmres_orth_d: one full orthogonalisation (classical Gram-Schmidt twice) of d_w (n entries, overwritten) against the
+   first ncols columns of d_V (leading dimension n), the kernels of an Arnoldi step in their order; h_out (host, ncols doubles):
+   the coefficients h_k, the sums of both passes; norm_out: ||w|| afterwards.  Either may be NULL.
+   igx_solver_gmres_combine_d: d_t = sum_{k < ncols} y[k] d_V[:, k] (y on the host), the kernel of the update of x.
+   igx_solver_gmres_timing: the mean device ms of an orthogonalisation (with the scalars and the scale of the step) and of an
+   update of x (back substitution, combination, preconditioner, add) over the last timed solve -- or of the last of the two calls
+   above; any pointer may be NULL. */
+int  igx_solver_gmres_orth_d(igx_solver *solver, const double *d_V, int ncols, double *d_w, double *h_out, double *norm_out);
+int  igx_solver_gmres_combine_d(igx_solver *solver, const double *d_V, int ncols, const double *y, double *d_t);
+int  igx_solver_gmres_timing(const igx_solver *solver, float *orth_ms, float *combine_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -319,6 +319,11 @@ SYMBOLS = [
     ('igx_solver_download_pair_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
     ('igx_solver_saddle_product_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, _dp]),
     ('igx_solver_saddle_timing', C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ('igx_solver_set_gmres', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ('igx_solver_gmres_restarts', C.c_int, [C.c_void_p]),
+    ('igx_solver_gmres_orth_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _dp, _dp]),
+    ('igx_solver_gmres_combine_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_void_p]),
+    ('igx_solver_gmres_timing', C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 ]
 
 _lib = None

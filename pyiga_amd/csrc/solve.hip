@@ -1111,7 +1111,7 @@ void free_solver(igx_solver *s)
 {
     mg_free(s);
     eig_free(s);
-    s->bicg.release(); s->block.release(); s->par.release(); s->step.release(); s->sad.release();
+    s->bicg.release(); s->block.release(); s->par.release(); s->step.release(); s->sad.release(); s->gm.release();
     (void)hipFree(s->d_tab); (void)hipFree(s->d_mask); (void)hipFree(s->d_vec); (void)hipFree(s->d_part); (void)hipFree(s->d_sc);
     (void)hipFree(s->d_kron); (void)hipFree(s->d_W); (void)hipFree(s->d_box);
     if (s->have_ev)

@@ -1,5 +1,6 @@
 // What the units of the device solvers know of each other: solve.hip (the linear solvers, the block solver, Newton's method),
-// solve_step.hip (DIRK time stepping and the adaptive stepping session) and solve_eig.hip (the block eigen-solver).  It holds
+// solve_step.hip (DIRK time stepping and the adaptive stepping session), solve_eig.hip (the block eigen-solver), solve_saddle.hip
+// (saddle-point systems, MINRES) and solve_gmres.hip (GMRES on them).  It holds
 // what more than one of them needs and nothing else: the solver structure with the state of every mode in a group of its own,
 // the layout types and device helpers the row kernels of two units share, and the host helpers that cross a unit boundary.  A
 // kernel is launched only from the unit that defines it; a kernel that another unit needs has a host function here.
@@ -228,6 +229,22 @@ struct SaddleState {
     }
 };
 
+// restarted GMRES on a saddle-point solver (igx_solver_set_gmres, solve_gmres.hip).  Its work vectors are
+// the MINRES ones (sad.d_mvec: rhs | z | t | the triangular preconditioner's velocity right-hand side), which a GMRES solve
+// leaves free
+struct GmresState {
+    int restart = 0;                          // 0: the solver solves with MINRES
+    int triangular = 0;                       // the block upper-triangular preconditioner (saddle_apply_precond)
+    int cap = 0;                              // the restart the arrays below were allocated for
+    double *d_V = nullptr;                    // the basis: (cap + 1) columns of n
+    double *d_small = nullptr;                // scalars | h | hp | cs | sn | g | y | R (gmres_small_len(cap) doubles)
+    int restarts = 0;                         // of the last solve
+    float orth_ms = 0.0f, combine_ms = 0.0f;  // device time of the orthogonalisations / the updates of x of the last timed solve
+                                              // (igx_solver_gmres_orth_d, _combine_d: of that call)
+    int orth_count = 0, combine_count = 0;    // how many of each those times cover
+    void release() { (void)hipFree(d_V); (void)hipFree(d_small); }
+};
+
 } // namespace igx
 
 struct igx_solver {
@@ -272,8 +289,9 @@ struct igx_solver {
     // block eigen-solver (igx_solver_eig_*, solve_eig.hip): made by its first call, or null
     igx::EigState *eig = nullptr;
     double *d_mass = nullptr;                 // a multipatch solver's second matrix (igx_solver_set_mass_d), owned
-    bool saddle = false;                      // made by igx_solver_create_saddle: n = ncomp g.nrows + sad.np, MINRES only
+    bool saddle = false;                      // made by igx_solver_create_saddle: n = ncomp g.nrows + sad.np, MINRES or GMRES (gm)
     igx::SaddleState sad;
+    igx::GmresState gm;
 };
 
 namespace igx {
@@ -328,6 +346,14 @@ int saddle_set_precond(igx_solver *s, int precond);
 int saddle_apply_precond(hipStream_t st, igx_solver *s, const double *r, double *z);
 int saddle_solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool x0_in_x, double tol, int maxiter, int check_every, int timed,
                         igx_solve_info &inf);
+
+// y = a + b over the n entries (k_mr_add)
+void saddle_add(hipStream_t st, long long n, const double *a, const double *b, double *y);
+
+// ---- solve_gmres.hip
+// Right-preconditioned GMRES(s->gm.restart) on R K R^T x = rhs: the residual rhs - K x0 in s->r, x0 in s->x, rhs itself in `rhs`
+// (s->r where x0 = 0).  What solve_minres is to a solver with gm.restart == 0: saddle_solve_lifted enters one or the other.
+int solve_gmres(hipStream_t st, igx_solver *s, const double *rhs, double tol, int maxiter, int check_every, int timed, igx_solve_info &inf);
 
 // ---- solve_eig.hip
 void eig_free(igx_solver *s);                // the eigen-solver's state and the mass matrix of a multipatch solver

@@ -582,7 +582,9 @@ int saddle_set_precond(igx_solver *s, int precond)
     return IGX_OK;
 }
 
-// z = diag(P_0, .., P_{nc-1}, P_S) r for r with zeros on the fixed dofs (z and r different vectors)
+// z = diag(P_0, .., P_{nc-1}, P_S) r for r with zeros on the fixed dofs (z and r different vectors).  With the triangular variant
+// selected (igx_solver_set_gmres; GMRES only): the solve with [[F, B^T], [0, -S]] -- z_p = -P_S r_p, then
+// z_u = diag(P_0, ..) (r_u - B^T z_p), the B^T product by k_saddle_u with every block of A absent.
 int saddle_apply_precond(hipStream_t st, igx_solver *s, const double *r, double *z)
 {
     const SaddleState &S = s->sad;
@@ -592,20 +594,51 @@ int saddle_apply_precond(hipStream_t st, igx_solver *s, const double *r, double 
         return IGX_OK;
     }
     double *W[2] = {s->d_W, s->d_W + s->wlen};
-    if (s->precond == IGX_PRECOND_JACOBI) k_mr_mul<<<blocks256(nv), 256, 0, st>>>(nv, s->dinv, r, z);
-    else {
+    const bool tri = s->gm.restart > 0 && s->gm.triangular;
+    const double *ru = r;                            // what the velocity part is applied to
+    if (tri) {
+        double *t = S.d_mvec + 3 * s->n;
+        if (S.schur == IGX_PRECOND_JACOBI) {
+            k_mr_mul<<<blocks256(S.np), 256, 0, st>>>(S.np, S.d_sdinv, r + nv, z + nv);
+            k_mr_mask_scale<<<blocks256(S.np), 256, 0, st>>>(S.np, s->d_mask + nv, -1.0, z + nv);
+        } else {
+            IGX_HIP(hipMemsetAsync(z + nv, 0, (size_t)S.np * sizeof(double), st));
+            if (int rc = apply_fastdiag(st, S.skron, r, z, W)) return rc;
+            k_mr_mask_scale<<<blocks256(S.np), 256, 0, st>>>(S.np, s->d_mask + nv, -S.sscale, z + nv);
+        }
+        // (the velocity part of z is read by the row kernel, against the zeros that stand for the absent blocks: it must be finite)
         IGX_HIP(hipMemsetAsync(z, 0, (size_t)nv * sizeof(double), st));
-        for (int c = 0; c < s->ncomp; ++c)
-            if (int rc = apply_fastdiag(st, s->block.bkron[c], r, z, W)) return rc;
+        RectVals BT{};
+        for (int q = 0; q < s->ncomp; ++q) BT.v[q] = S.BT[q];
+        const BlockVals none{};
+        const unsigned nbu = saddle_blocks(S.nb_u, S.gw_u, S.nu);
+        with_saddle_u_kernel(S.gw_u, s->ncomp, [&](auto k) {
+            k<<<nbu, BLOCK, 0, st>>>(s->g, none, S.gT, BT, s->d_mask, z, r, -1.0, t, nullptr, nullptr);
+        });
+        IGX_HIP(hipGetLastError());
+        ru = t;
     }
-    if (S.schur == IGX_PRECOND_JACOBI) k_mr_mul<<<blocks256(S.np), 256, 0, st>>>(S.np, S.d_sdinv, r + nv, z + nv);
+    if (s->precond == IGX_PRECOND_JACOBI) k_mr_mul<<<blocks256(nv), 256, 0, st>>>(nv, s->dinv, ru, z);
     else {
-        IGX_HIP(hipMemsetAsync(z + nv, 0, (size_t)S.np * sizeof(double), st));
-        if (int rc = apply_fastdiag(st, S.skron, r, z, W)) return rc;
-        k_mr_mask_scale<<<blocks256(S.np), 256, 0, st>>>(S.np, s->d_mask + nv, S.sscale, z + nv);
+        if (!tri) IGX_HIP(hipMemsetAsync(z, 0, (size_t)nv * sizeof(double), st));
+        for (int c = 0; c < s->ncomp; ++c)
+            if (int rc = apply_fastdiag(st, s->block.bkron[c], ru, z, W)) return rc;
+    }
+    if (!tri) {
+        if (S.schur == IGX_PRECOND_JACOBI) k_mr_mul<<<blocks256(S.np), 256, 0, st>>>(S.np, S.d_sdinv, r + nv, z + nv);
+        else {
+            IGX_HIP(hipMemsetAsync(z + nv, 0, (size_t)S.np * sizeof(double), st));
+            if (int rc = apply_fastdiag(st, S.skron, r, z, W)) return rc;
+            k_mr_mask_scale<<<blocks256(S.np), 256, 0, st>>>(S.np, s->d_mask + nv, S.sscale, z + nv);
+        }
     }
     IGX_HIP(hipGetLastError());
     return IGX_OK;
+}
+
+void saddle_add(hipStream_t st, long long n, const double *a, const double *b, double *y)
+{
+    k_mr_add<<<blocks256(n), 256, 0, st>>>(n, a, b, y);
 }
 
 static int read_scalars(hipStream_t st, const igx_solver *s, double *h)
@@ -719,9 +752,17 @@ int saddle_solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool 
     if (int rc = project_pressure(st, s, s->r, &S.rhs_mean, &S.rhs_norm)) return rc;
     double bnorm = 0.0;
     if (int rc = vector_norm(st, s, s->r, &bnorm)) return rc;
-    if (x0_in_x)
+    const double *rhs = s->r;                        // (GMRES forms the residual again at every restart: it keeps the right-hand side)
+    if (x0_in_x) {
+        if (s->gm.restart > 0) {
+            IGX_HIP(hipMemcpyAsync(S.d_mvec, s->r, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            rhs = S.d_mvec;
+        }
         if (int rc = saddle_spmv(st, s, s->x, s->r, -1.0, s->r, nullptr, nullptr)) return rc;
-    if (int rc = solve_minres(st, s, tol, maxiter, check_every, timed, inf)) return rc;
+    }
+    if (s->gm.restart > 0) {
+        if (int rc = solve_gmres(st, s, rhs, tol, maxiter, check_every, timed, inf)) return rc;
+    } else if (int rc = solve_minres(st, s, tol, maxiter, check_every, timed, inf)) return rc;
     // the true residual R (b - K (ext(g) + x)), projected as the right-hand side was
     const double *full = s->x;
     if (lift) {

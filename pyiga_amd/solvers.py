@@ -41,6 +41,10 @@ the accept/reject controller on the host.
 ('v', nc)], geo=geo)``: the lowest eigenpairs of ``K x = lam M x`` on one patch, on a multipatch, and for a vector-valued form
 (elastic vibration, ``M`` the same mass matrix for every component), by block LOBPCG (``lobpcg_loop``) with the matrices, the
 blocks and the preconditioner on the device.
+
+``SaddlePointSystem((kvs_u, kvs_p), geo, bcs)`` and ``OseenSystem((kvs_u, kvs_p), geo, bcs, viscosity=nu, w=wind)``: the Stokes
+system ``[[A, B^T], [B, 0]]`` by preconditioned MINRES, and the Oseen system -- the same with a frozen-wind convection term in the
+velocity block -- by right-preconditioned restarted GMRES with a block-diagonal or block-triangular preconditioner.
 """
 import ctypes as C
 import math
@@ -670,6 +674,7 @@ class SaddlePointSystem(_VectorBlocks, _DeviceSystem):
 
     ``solve()`` returns the full vector; ``split(u)`` gives the coefficient arrays of velocity and pressure."""
     PRESSURES = ('auto', 'mean', None)
+    METHOD = 'minres'
 
     def __init__(self, kvs, geo, bcs, rhs=0.0, a='inner(grad(u), grad(v)) * dx', b='div(u) * p * dx', ncomp=None, viscosity=1.0,
                  args=None, **inputs):
@@ -717,6 +722,7 @@ class SaddlePointSystem(_VectorBlocks, _DeviceSystem):
             if self.viscosity != 1.0:
                 table = [[[[None if e is None else self.viscosity * np.asarray(e, dtype=np.float64) for e in row] for row in tab]
                           for tab in trow] for trow in table]
+            table = self._velocity_tables(table, geo, fargs)
             if isinstance(rhs, str):
                 f = assemble.assemble(rhs, self.kvs, args=dict(fargs, geo=geo), bfuns=[('v', nc)], layout='blocked')
                 rhs = np.concatenate((np.asarray(f, dtype=np.float64).ravel(), np.zeros(self.Np)))
@@ -726,8 +732,8 @@ class SaddlePointSystem(_VectorBlocks, _DeviceSystem):
             if self.b.size != self.n:
                 raise ValueError('right-hand side has %d entries, the system %d x %d + %d' % (self.b.size, nc, self.N, self.Np))
             self._ctx = self.patch.ctx
-            self.method = 'minres'
-            self._attach('igx_solver_create_saddle', (self.patch.handle, self.pair.handle, nc), bcs, 'minres', 'minres')
+            self.method = self.METHOD
+            self._attach('igx_solver_create_saddle', (self.patch.handle, self.pair.handle, nc), bcs, self.METHOD, self.METHOD)
             self._take_blocks(table)
             lib = _lib.load()
             for q in range(nc):
@@ -743,6 +749,10 @@ class SaddlePointSystem(_VectorBlocks, _DeviceSystem):
         self.enclosed = pidx.size == 0 and all(box is not None and all(a_ == 1 for a_ in box[0]) and
                                                all(b_ == n_ - 1 for b_, n_ in zip(box[1], self.ndofs)) for box in self.boxes)
         self._velocity_factors_set = False
+
+    def _velocity_tables(self, table, geo, fargs):
+        """The coefficient tables of the velocity block from the (scaled) tables of `a`: those themselves."""
+        return table
 
     def set_method(self, method):
         """'minres' is the only method of a saddle-point system; 'cg' and 'bicgstab' raise IgxError (IGX_ERR_UNSUPPORTED)."""
@@ -842,6 +852,128 @@ class SaddlePointSystem(_VectorBlocks, _DeviceSystem):
         nv = self.ncomp * self.N
         U = np.stack([u[c * self.N:(c + 1) * self.N].reshape(self.ndofs) for c in range(self.ncomp)], axis=-1)
         return U, u[nv:].reshape(self.ndofs_p)
+
+
+def add_block_tables(ta, tb):
+    """The entry-wise sum of two coefficient tables of a vector-valued form (``table[p][q][r][s]``: arrays on one Gauss grid or
+    None); a None entry is zero, an entry absent in both stays None."""
+    def add(x, y):
+        if x is None:
+            return y
+        if y is None:
+            return x
+        return np.asarray(x, dtype=np.float64) + np.asarray(y, dtype=np.float64)
+    return [[[[add(x, y) for x, y in zip(ra, rb)] for ra, rb in zip(xa, xb)] for xa, xb in zip(pa, pb)] for pa, pb in zip(ta, tb)]
+
+
+def _check_convection(convection, kvs_u, kvs_p, nc, fargs):
+    """ValueError, before any device work, unless `convection` is None or a bilinear volume form in ``u`` and ``v`` of `nc`
+    components each.  The form is evaluated at one point: inputs given as arrays over the Gauss grid enter with their first
+    value, callables with their value at the origin."""
+    from . import tforms
+    if convection is None:
+        return
+    if not isinstance(convection, str):
+        raise ValueError('OseenSystem: convection must be a form string or None, not %r' % (convection,))
+    if re.search(r'\bds\b', convection):
+        raise ValueError('OseenSystem: the convection term is a volume form (dx), not a surface or boundary form: %r' % (convection,))
+    d = len(kvs_u)
+    nqp = max(kv.p for kv in tuple(kvs_u) + tuple(kvs_p)) + 1
+    G = tuple(int(kv.numspans) * nqp for kv in kvs_u)
+    point = {}
+    for name, val in fargs.items():
+        if not callable(val) and np.ndim(val) >= d and np.shape(val)[:d] == G:
+            val = np.asarray(val, dtype=np.float64)[(0,) * d][(None,) * d]
+        point[name] = val
+    try:
+        arity, measure, table, ncs = tforms.evaluate(convection, (1,) * d, np.zeros((1,) * d + (d,)), point, [('u', nc), ('v', nc)])
+    except Exception as e:
+        raise ValueError('OseenSystem: convection=%r is not a bilinear volume form in u and v of %d components each: %s'
+                         % (convection, nc, e))
+    if arity != 2 or measure != 'dx' or tuple(ncs) != (nc, nc) or len(table) != nc or any(len(row) != nc for row in table):
+        raise ValueError('OseenSystem: convection=%r is not a bilinear volume form (dx) in u and v of %d components each'
+                         % (convection, nc))
+
+
+class OseenSystem(SaddlePointSystem):
+    """The Oseen problem ``[[nu A + N, B^T], [B, 0]] (u, p) = (f, 0)`` on one patch -- the linear system of every step of the
+    reference's solve-navier-stokes notebook, ``Re^-1 A_grad + A_linconv(vel)`` with the wind frozen -- assembled and solved on
+    the device with right-preconditioned restarted GMRES.
+
+    Everything is ``SaddlePointSystem``'s except the velocity block, `viscosity` times the (symmetric) form `a` plus the form
+    `convection` in ``u`` and ``v``, which is not scaled and need not be symmetric, and the Krylov method.  `convection` is
+    evaluated on the same Gauss grid as `a` and `b`, and its coefficient tables are added to those of `a` before the blocks are
+    assembled; its inputs (the wind ``w``) are what vector-valued forms accept: a callable of the physical coordinates that
+    returns a tuple, or an array over the Gauss grid with a trailing component axis.  ``convection=None``: the Stokes system,
+    solved by GMRES.  `restart`: the length of a GMRES cycle (1 to 128), the default of ``solve``."""
+    METHOD = 'gmres'
+    MAX_RESTART = 128
+
+    def __init__(self, kvs, geo, bcs, rhs=0.0, convection='grad(u).dot(w).dot(v) * dx', a='inner(grad(u), grad(v)) * dx',
+                 b='div(u) * p * dx', ncomp=None, viscosity=1.0, restart=40, args=None, **inputs):
+        from .form_assemblers import is_space_pair
+        if not is_space_pair(kvs):
+            raise ValueError('OseenSystem needs kvs=(kvs_u, kvs_p): the velocity and the pressure space')
+        self.restart = self._check_restart(restart)
+        nc = len(kvs[0]) if ncomp is None else int(ncomp)
+        fargs = dict(args or {})
+        fargs.update(inputs)
+        fargs.pop('geo', None)
+        if nc in (2, 3):                           # (any other count: the parent's refusal)
+            _check_convection(convection, kvs[0], kvs[1], nc, fargs)
+        self.convection = convection
+        SaddlePointSystem.__init__(self, kvs, geo, bcs, rhs=rhs, a=a, b=b, ncomp=ncomp, viscosity=viscosity, args=args, **inputs)
+
+    @classmethod
+    def _check_restart(cls, restart):
+        if not (isinstance(restart, (int, np.integer)) and 1 <= restart <= cls.MAX_RESTART):
+            raise ValueError('restart must be an integer from 1 to %d, not %r' % (cls.MAX_RESTART, restart))
+        return int(restart)
+
+    def _velocity_tables(self, table, geo, fargs):
+        """`viscosity` times the tables of `a` (given) plus those of the convection form on the same patch."""
+        from .form_assemblers import FormAssembler
+        if self.convection is None:
+            return table
+        asm = FormAssembler(self.kvs, geo, self.convection, bfuns=[('u', self.ncomp), ('v', self.ncomp)], inputs=fargs, patch=self.patch)
+        return add_block_tables(table, asm._table)
+
+    def set_method(self, method):
+        """'gmres' is the only method of an Oseen system."""
+        if method != 'gmres':
+            raise ValueError("unknown method %r: 'gmres'" % (method,))
+        self.method = method
+
+    def _select(self, precond, triangular, restart):
+        """GMRES(restart) with the triangular or the block-diagonal form of the preconditioner `precond` selected on the device."""
+        key = self.default_precond if precond == 'auto' else precond
+        tri = bool(triangular) and key is not None
+        _lib.check(_lib.load().igx_solver_set_gmres(self._live(), int(restart), 1 if tri else 0), 'igx_solver_set_gmres')
+        return tri
+
+    def solve(self, tol=1e-8, maxiter=1000, precond='auto', triangular=True, pressure='auto', x0=None, check_every=1, timed=False,
+              restart=None):
+        """Right-preconditioned GMRES(`restart`, default the system's) to ``|g_k| <= tol * ||r_0||``, GMRES's own residual norm;
+        returns the full vector (Dirichlet values included).  `precond` and `pressure` as ``SaddlePointSystem.solve``;
+        `triangular`: the block upper-triangular form ``[[F, B^T], [0, -S]]^-1`` of the preconditioner instead of the
+        block-diagonal one (ignored for ``precond=None``).  ``info['iterations']`` counts Arnoldi steps, ``info['restarts']`` the
+        cycles after the first, ``info['relres']`` is the true relative residual, ``info['breakdown']`` None or 'nonfinite'."""
+        restart = self.restart if restart is None else self._check_restart(restart)
+        if precond != 'auto' and (precond if precond is not None else 'none') not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        tri = self._select(precond, triangular, restart)
+        u = SaddlePointSystem.solve(self, tol=tol, maxiter=maxiter, precond=precond, pressure=pressure, x0=x0, check_every=check_every,
+                                    timed=timed)
+        self.info.update(restarts=int(_lib.load().igx_solver_gmres_restarts(self.handle)), restart=restart, triangular=tri)
+        return u
+
+    def apply_precond(self, r, precond=None, triangular=True):
+        """``z = P r`` on the device, as ``solve`` applies it: the triangular form when `triangular` (and a preconditioner is
+        selected)."""
+        if precond is not None:
+            self.set_precond(precond)
+        self._select(self._precond if self._precond != 'none' else None, triangular, self.restart)
+        return self._device_op(_lib.load().igx_solver_precond_d, 'igx_solver_precond_d', r)
 
 
 def _test_function_name(problem, bfuns):
