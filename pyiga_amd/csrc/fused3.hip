@@ -53,6 +53,8 @@
 
 namespace igx {
 
+constexpr int BF_MASK_MASS = 0x0001, BF_MASK_STIFF3 = 0x135F, BF_MASK_STIFF2 = 0x1248;
+
 // SYM: 0 non-symmetric form (one set of rings, every pair direct); 1 symmetric, every outer pair diagonal (2D: one set);
 //      2 symmetric with off-diagonal outer pairs (3D: direct + transposed set);
 //      3 (round 6) symmetric PER AXIS -- the 3D mass form: A[(i0,i1,i2),(j0,j1,j2)] = sum_g W N_i0 N_j0 N_i1 N_j1 N_i2 N_j2 does not
@@ -471,6 +473,35 @@ __device__ __forceinline__ void bf3_sweeper(const BFArgs &A, const int r0, const
     if constexpr (ST) store.init(A, *sc.B, sc.sw, slane);
     BF_STAMP_DECL
     __builtin_amdgcn_s_setprio(BF2_PRIO_S);
+    // Diagonal outer blocks of the 3D stiffness form when k_geoA has skipped the slices they would read twice (BFArgs::diag_skip; one
+    // scalar test per block).  Every role reads its arrays through spd: role 0 gets the slot (2, 0) values from the slice of slot
+    // (1, 0) -- two descriptors on one slice, the second load hits in the cache.  With diag_tr the inputs of the role of last-axis
+    // type 2 are those of type 1 with the mid-axis types transposed, and the two roles apply the same multiply-adds with a and b
+    // exchanged (shape 0 against shape 1 below): acc_2[a][b] is acc_1[b][a] bit for bit.  A diagonal block contracts the lines of
+    // the pairs (d + a, d) only, so role 1 writes acc_1[0][a] into role 2's lines in its own flush -- the same place between the
+    // same barriers -- and role 2 keeps the barriers and its store duty and nothing else.
+    constexpr bool DGM = MASK == BF_MASK_STIFF3, TRS = DGM && R.y == 1, TRD = DGM && R.y == 2;
+    static_assert(!DGM || (bf_role(MASK, 1).y == 1 && bf_role(MASK, 1).shape == 0 && bf_role(MASK, 1).f == 0 && bf_role(MASK, 1).has[0] && bf_role(MASK, 1).has[2] &&
+                           bf_role(MASK, 2).y == 2 && bf_role(MASK, 2).shape == 1 && bf_role(MASK, 2).f == 0 && bf_role(MASK, 2).has[0] && bf_role(MASK, 2).has[1]),
+                  "k_bf3: the roles of last-axis types 1 and 2 of the stiffness form mirror each other");
+    const bool dg = DGM && A.diag_skip && sc.B->diag0, dgt = dg && A.diag_tr;
+    if constexpr (TRD) {
+        if (dgt) {
+            for (int d = d_begin; d < rhi; ++d) {
+                bar_lds();                                   // B1
+                if constexpr (ST) store.issue(A, *sc.B, d - 1, sc.sw);
+                bar_lds();                                   // B2
+                if constexpr (ST) store.fetch(A, *sc.B, sc.sets, sc.dump, d, sc.sw, slane);
+            }
+            bar_lds();
+            if constexpr (ST) store.issue(A, *sc.B, rhi - 1, sc.sw);
+            bar_lds();
+            if constexpr (ST) store.fetch(A, *sc.B, sc.sets, sc.dump, rhi, sc.sw, slane);
+            if constexpr (ST) store.issue(A, *sc.B, rhi, sc.sw);
+            BF_STAMP_END(threadIdx.x >> 6);
+            return;
+        }
+    }
     cdp V1 = (cdp)A.V1;
     cip fa1 = (cip)A.fa1;
     double acc[P1][P1];
@@ -488,7 +519,8 @@ __device__ __forceinline__ void bf3_sweeper(const BFArgs &A, const int r0, const
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             urs[t1][i] = A.rs[R.y][t1][i] * 8;
-            rsrc[t1][i] = bf2_rsrc(A.sp[R.y][t1][i] + (long long)r0 * A.ss[R.y][t1][i] - (long long)A.gmid_lo * A.rs[R.y][t1][i]);
+            const double *src = (DGM && i == 0 && dg) ? A.spd[R.y][t1] : A.sp[R.y][t1][i];
+            rsrc[t1][i] = bf2_rsrc(src + (long long)r0 * A.ss[R.y][t1][i] - (long long)A.gmid_lo * A.rs[R.y][t1][i]);
         }
     auto ld = [&](const int t1, const int i, const int row) {
 #ifdef BF3_NOLOAD
@@ -516,6 +548,12 @@ __device__ __forceinline__ void bf3_sweeper(const BFArgs &A, const int r0, const
         for (int a = 0; a < P1; ++a) ln[a * LS] = acc[a][0];
 #pragma unroll
         for (int a = 1; a < P1; ++a) ln[(p1 + a) * LS] = acc[0][a];
+        if constexpr (TRS) {
+            if (dgt) {                                      // the lines (d + a, d) of the role of type 2 (the next role): this window transposed
+#pragma unroll
+                for (int a = 0; a < P1; ++a) ln[sc.tlp + a * LS] = acc[0][a];
+            }
+        }
 #pragma unroll
         for (int a = 0; a < P1 - 1; ++a)
 #pragma unroll
@@ -1058,8 +1096,6 @@ static int launch_bf3_k(hipStream_t st, const BFArgs &A0, int ncu_ctx)
     return IGX_OK;
 }
 
-constexpr int BF_MASK_MASS = 0x0001, BF_MASK_STIFF3 = 0x135F, BF_MASK_STIFF2 = 0x1248;
-
 // shapes (lane groups per role, contractor waves, halved passes) by the larger of the two degrees: those of k_bf2 (fused.hip,
 // BF2Cfg: chosen per degree and form from measurements)
 #ifndef BF3_NH
@@ -1217,6 +1253,11 @@ int launch_bf3(hipStream_t st, const igx_patch *pt, const BFInputs &in, double *
     A.data = d_data; A.sym = in.sym;
     A.mid_lo = in.mid_lo; A.mid_hi = in.mid_hi; A.span_hi = in.span_hi;
     A.npairs = in.npairs;
+    // diagonal outer blocks when k_geoA has skipped their duplicate slices: only the symmetric 3D stiffness kernels know how
+    if (in.diag_skip && !(mask == BF_MASK_STIFF3 && in.sym && pt->dim == 3 && !in.pad_stiff3)) { set_error("internal: fused stage asked to skip slices it has no kernel for"); return IGX_ERR_UNSUPPORTED; }
+    A.diag_skip = in.diag_skip; A.diag_tr = in.diag_skip ? in.diag_tr : 0;
+    for (int y = 0; y < 4; ++y)
+        for (int t1 = 0; t1 < 4; ++t1) A.spd[y][t1] = (in.diag_skip && in.diag_ptr[y][t1]) ? in.diag_ptr[y][t1] : A.sp[y][t1][0];
     if (pt->dim == 3) { A.own_lo = pt->r0_lo; A.own_hi = pt->r0_hi; } else { A.own_lo = 0; A.own_hi = 1; }
     // (the 3D mass form is symmetric per axis: SYM = 3 -- unless the rows of the mid axis are cut by repeated knots with unequal
     // degrees, which k_bf3 does not serve at all)

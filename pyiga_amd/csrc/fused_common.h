@@ -66,6 +66,11 @@ struct BFArgs {
     int npairs;
     const int *fa1, *mslo1, *jlo1, *jhi1;   // mid axis (k_bf3): first active dof of a span, first span of a dof's support, column range of a row
     int own_lo, own_hi;           // owned rows of the outer axis (k_bf3: a block stores the direct rows of an owned i0, the transposed ones of an owned j0)
+    // k_bf3, 3D stiffness: k_geoA has left out the slices of diagonal outer pairs that repeat another array's (BFInputs::diag_skip);
+    // a diagonal block reads In(y, t1, 0) from spd[y][t1] (same strides), and with diag_tr its role of last-axis type 2 loads
+    // nothing -- the role of type 1 writes both roles' lines
+    const double *spd[4][4];
+    int diag_skip, diag_tr;
 };
 
 // Diagnostic build (-DIGX_BF_STAMP, never the shipped library): every wave adds up the shader cycles it spends waiting

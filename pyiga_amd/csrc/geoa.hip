@@ -76,6 +76,10 @@ struct GeoAArgs {
     int fslot[16];
     int nsrc[GA_MAXS], sfield[GA_MAXS][4], stype[GA_MAXS][4];
     int nslots;                 // arrays the form has (<= 8): the sweep waves beyond them sweep nothing and store nothing
+    // 3D stiffness into k_bf3 (sumfact.hip: plan_diag_skip): array x is the member of axis-0 type 1 of a couple (same field, types 1
+    // and 2).  On a DIAGONAL pair (i0 = j0) its slice is the other member's, bit for bit -- one product V_a V_a per plane, the
+    // same planes in the same order -- and k_bf3 reads it there: the slice is not written
+    int nodiag[GA_MAXS];
 };
 constexpr int GA_NFT = 13;      // fields of a point a table form may keep in LDS: ten for a symmetric table with every entry, thirteen for
                                 // reaction + convection both ways + a symmetric diffusion block (sumfact.hip: form_table_plan)
@@ -192,11 +196,16 @@ __global__ void k_geoa_table(const double *V0s, int P, const double *V0g, const 
 struct K1Store {
     __amdgpu_buffer_rsrc_t rs;
     int voff, ok;
-    __device__ __forceinline__ K1Store(double *base, const long long pt, const int tile, const int soff_ok)
+    int voffd, nodiag;          // lane offset of the store of a DIAGONAL pair: voff, or out of range where the wave's array skips them
+    __device__ __forceinline__ K1Store(double *base, const long long pt, const int tile, const int soff_ok, const int nodiag_ = 0)
     {
         const long long t0 = (long long)tile * 64;
         rs = __builtin_amdgcn_make_buffer_rsrc((void *)(base + t0), (short)0, 0x7ffffff0, 0x00020000);
         voff = (int)(pt - t0) * 8;
+        // (no branch around the store: the descriptor's range check drops a lane offset at or above its length, whatever slice
+        // offset is added to it -- 0x7ffffff8 + a slice offset below 2^31 does not wrap)
+        nodiag = nodiag_;
+        voffd = nodiag_ ? 0x7ffffff8 : voff;
 #ifdef GA_K1_FLAT
         ok = 0;                                              // (A/B build: 64-bit addresses everywhere)
 #else
@@ -210,6 +219,15 @@ struct K1Store {
             i2s v; v.x = __double2loint(x); v.y = __double2hiint(x);
             __builtin_amdgcn_raw_buffer_store_b64(v, rs, voff, (int)((unsigned)slot * (unsigned)(stride * 8)), 0);
         } else out[(long long)slot * stride] = x;
+    }
+    // the pair (d, d) of a flush step
+    __device__ __forceinline__ void store_diag(double *out, const int slot, const long long stride, const double x) const
+    {
+        if (ok) {
+            typedef int i2s __attribute__((ext_vector_type(2)));
+            i2s v; v.x = __double2loint(x); v.y = __double2hiint(x);
+            __builtin_amdgcn_raw_buffer_store_b64(v, rs, voffd, (int)((unsigned)slot * (unsigned)(stride * 8)), 0);
+        } else if (!nodiag) out[(long long)slot * stride] = x;
     }
 };
 
@@ -1082,7 +1100,7 @@ k_geoA(const GeoAArgs A)
         const bool live = w < A.nslots;
         const int t = A.type[w], fi = A.field[w];
         double *const out = A.out[w] + pt;
-        const K1Store k1s(A.out[w], pt, tile, A.soff_ok);
+        const K1Store k1s(A.out[w], pt, tile, A.soff_ok, D2 ? 0 : A.nodiag[w]);
         double acc[P][P];
 #pragma unroll
         for (int a = 0; a < P; ++a)
@@ -1144,8 +1162,10 @@ k_geoA(const GeoAArgs A)
 #pragma unroll
                         for (int a = 0; a < P; ++a) pr[a] = rec8[a];
                     }
+                    // (pair a of the step is (d + a, d): a = 0 is the diagonal pair, which the second member of a couple skips)
+                    if (pr[0] >= 0 && write) k1s.store_diag(out, pr[0], A.stride, acc[0][0]);
 #pragma unroll
-                    for (int a = 0; a < P; ++a)
+                    for (int a = 1; a < P; ++a)
                         if (pr[a] >= 0 && write) k1s.store(out, pr[a], A.stride, acc[a][0]);
 #pragma unroll
                     for (int a = 0; a < P - 1; ++a)
@@ -1388,6 +1408,15 @@ bool geoA_supported(const igx_patch *pt, int kind, int nslots)
     return 2 * gspans <= (long long)pt->ax[0].G;
 }
 
+// Which sweep launch_geoA takes for a symmetric fixed form is decided by the degree on axis 0 and the matrix-core knob alone (below):
+// the pair-product sweep (GA_DPP, at most 16 lower pairs) multiplies V_a[tv] V_b[tu] first, so on a = b the types 1 and 2 give the
+// same product; the vector form of degree 5 computes V_b[tu] (V_a[tv] f) -- not the same roundings when tu and tv are exchanged
+bool geoA_diag_types_commute(const igx_patch *pt)
+{
+    const int P = pt->ax[0].P;
+    return GA_DPP && pt->dim == 3 && !pt->knobs.geoa_mf && P >= 2 && P * (P + 1) / 2 <= 16;
+}
+
 // general first-order forms (coefficient table): 3D spline geometries, degrees 2 .. 5 on axis 0, the whole Gauss slab resident
 bool geoA_form_supported(const igx_patch *pt)
 {
@@ -1401,7 +1430,7 @@ bool geoA_form_supported(const igx_patch *pt)
 
 int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *slot_field, const int *slot_type,
                 double *const *slot_out, long long slice_stride, int chunk_len, int nchunks, const int *slot_xfield, const int *slot_xtype,
-                const GeoAForm *form)
+                const GeoAForm *form, unsigned nodiag_mask)
 {
     const bool nonsym = kind == IGX_CONVDIFF || (form && !form->sym);
     if (nonsym) {
@@ -1496,7 +1525,9 @@ int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *
     for (int x = 0; x < nslots; ++x) {
         A.field[x] = slot_field ? slot_field[x] : 0; A.type[x] = slot_type ? slot_type[x] : 0; A.out[x] = slot_out[x];
         A.xfield[x] = slot_xfield ? slot_xfield[x] : -1; A.xtype[x] = slot_xtype ? slot_xtype[x] : 0;
+        A.nodiag[x] = (nodiag_mask >> x) & 1;
     }
+    if (nodiag_mask && (nonsym || form || pt->dim != 3 || !geoA_diag_types_commute(pt))) { set_error("internal: diagonal slices skipped on a sweep that does not repeat them"); return IGX_ERR_UNSUPPORTED; }
     A.nslots = nslots;
     for (int x = nslots; x < GA_MAXS; ++x) A.out[x] = A.out[0];  // (waves without an array: never stored through)
     A.ntiles = (int)((A.NPL + 63) / 64);

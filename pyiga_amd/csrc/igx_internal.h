@@ -123,6 +123,7 @@ struct igx_knobs {
     int poison = 0;                           // IGX_DEBUG_POISON: NaN-fill the CSR values before an assembly (tests)
     int bf = 0;                               // IGX_BF=2: symmetric 3D forms through k_bf2 + the mirror pass (the chain of rounds 3-4) instead of k_bf3
     int no_twin = 0;                          // IGX_NO_TWIN: no twin patch (repeated knots on the last axis: the stage kernels, as before round 6)
+    int no_diag_skip = 0;                     // IGX_NO_DIAG_SKIP: k_geoA writes and k_bf3 reads the K1 slices that diagonal outer pairs duplicate (A/B runs)
     int placement_tries = 1;                  // IGX_PLACEMENT_TRIES=n (opt-in, 3D symmetric forms): the CSR value buffer is the fastest of n
                                               // allocations under the mirror pass, timed once at its first assembly
     int stage_events = -1;                    // IGX_STAGE_EVENTS: events between the kernels of a chain (per-kernel device times in
@@ -323,6 +324,11 @@ struct BFInputs {
     const int *rp0, *jlo0, *jhi0;             // outer axis tables (device)
     int sym, mid_lo, mid_hi;
     int span_hi;                              // resident spans of the mid axis end here
+    // k_bf3, 3D stiffness (Plan::diag_skip): on a DIAGONAL outer pair the array of slot (y, t1) is read from diag_ptr[y][t1] -- the
+    // other member of its couple where k_geoA leaves the slot's own slice unwritten -- and (diag_tr) the role of last-axis type 2
+    // loads nothing: its lines are the transposed window of the role of type 1
+    int diag_skip = 0, diag_tr = 0;
+    const double *diag_ptr[4][4];
 };
 struct MirrorInputs {
     const Axis *mid, *last;
@@ -348,6 +354,9 @@ bool fused3_tr_fits(int p0, int p1, int p2, long long S_mid, long long S_last);
 int launch_bf3(hipStream_t st, const igx_patch *pt, const BFInputs &in, double *d_data);
 // fused geometry + stage A (geoa.hip)
 bool geoA_supported(const igx_patch *pt, int kind, int nslots);
+// the axis-0 sweep this patch takes forms V_a[tv] V_b[tu] as ONE product per (plane, pair): on a pair a = b the arrays of the
+// axis-0 types 1 and 2 over the same field are then the same bits (the pair-product sweep of k_geoA: p <= 4, vector form)
+bool geoA_diag_types_commute(const igx_patch *pt);
 // table of a general first-order form for k_geoA (FORM = 2 | 3): see GeoAArgs (geoa.hip)
 struct GeoAForm {
     int sym;                                  // symmetric table: lower pairs of axis 0, symmetric flush
@@ -359,7 +368,7 @@ struct GeoAForm {
 };
 int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *slot_field, const int *slot_type,
                 double *const *slot_out, long long slice_stride, int chunk_len, int nchunks, const int *slot_xfield = nullptr, const int *slot_xtype = nullptr,
-                const GeoAForm *form = nullptr);
+                const GeoAForm *form = nullptr, unsigned nodiag_mask = 0);
 bool geoA_form_supported(const igx_patch *pt);
 
 // The kernel chain of one sum-factorised assembly: sumfact_plan decides all of it from the patch, its knobs and the kind (no HIP
@@ -397,6 +406,13 @@ struct Plan {
     bool geoA = false;                        // stage 0: k_geoA, else k_stageA
     Fused fused = NO_FUSED;
     int slot_n[4][4] = {}, slot_arr[4][4][2]; // fused-stage inputs per (last-axis type, mid-axis type): count, array index
+    // 3D stiffness through k_geoA -> k_bf3: the arrays of a couple -- same field, axis-0 types 1 and 2 -- are the same bits on a
+    // diagonal outer pair.  diag_skip: k_geoA does not write those slices of the arrays in nodiag_mask (the members of type 1) and
+    // k_bf3 reads slot (y, t1) of a diagonal block from array diag_arr[y][t1]; diag_tr: with that, the inputs of the role of
+    // last-axis type 2 are those of type 1 with the mid-axis types transposed
+    bool diag_skip = false, diag_tr = false;
+    unsigned nodiag_mask = 0;
+    int diag_arr[4][4] = {};
     Final fin = FINAL_VALU;
     int mfma_nch = 0;                         // k_final_mfma: 8-point chunks of the Gauss window
     FormPlan form;

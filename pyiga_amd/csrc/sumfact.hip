@@ -944,6 +944,45 @@ static void plan_form_slots(Plan &pl)
             if (pl.form.slot_arr[y][t1] >= 0) pl.slot_arr[y][t1][pl.slot_n[y][t1]++] = pl.form.slot_arr[y][t1];
 }
 
+// Duplicate K1 slices of diagonal outer pairs (3D stiffness, k_geoA -> k_bf3).  Two arrays over the SAME field whose axis-0 types are 1
+// (N_i0 N'_j0) and 2 (N'_i0 N_j0) are the same sum on a pair i0 = j0, and -- where k_geoA forms one product per (plane, pair),
+// geoA_diag_types_commute -- the same bits.  Derived from the arrays X = (axis-0 type, field) and the slot table, not from the name of
+// the form: the member of type 1 of every such couple is not written on diagonal pairs (nodiag_mask), a diagonal block of k_bf3 reads
+// its slots from the member of type 2 (diag_arr), and where that makes the inputs of last-axis type 2 those of type 1 with the
+// mid-axis types transposed (t1 = tu + 2 tv <-> tv + 2 tu), the role of type 2 loads nothing at all (diag_tr).  Everything else that
+// reads K1 -- k_bf2, the stage kernels, the 2D chain, merged and table forms, mass -- keeps the flag false and sees K1 as ever.
+static void plan_diag_skip(const igx_patch *pt, Plan &pl)
+{
+    if (pt->knobs.no_diag_skip || pl.kind != IGX_STIFFNESS || pt->dim != 3 || !pl.sym || pl.merged || !pl.geoA || pl.fused != Plan::BF3) return;
+    if (pl.nX != 8 || (int)pl.X.size() != pl.nX || !geoA_diag_types_commute(pt)) return;
+    int partner[8];
+    unsigned mask = 0;
+    for (int x = 0; x < pl.nX; ++x) {
+        partner[x] = x;
+        if (pl.X[x].t0 != 1) continue;
+        int n = 0;
+        for (int z = 0; z < pl.nX; ++z)
+            if (pl.X[z].t0 == 2 && pl.X[z].f == pl.X[x].f) { partner[x] = z; ++n; }
+        if (n == 1) mask |= 1u << x;
+        else partner[x] = x;
+    }
+    if (!mask) return;
+    for (int y = 0; y < 4; ++y)
+        for (int t1 = 0; t1 < 4; ++t1) {
+            if (pl.slot_n[y][t1] > 1) return;
+            pl.diag_arr[y][t1] = pl.slot_n[y][t1] ? partner[pl.slot_arr[y][t1][0]] : -1;
+        }
+    pl.diag_skip = true;
+    pl.nodiag_mask = mask;
+    bool tr = false;
+    for (int t1 = 0; t1 < 4; ++t1) {
+        const int tt = (t1 >> 1) | ((t1 & 1) << 1);
+        if (pl.diag_arr[2][t1] != pl.diag_arr[1][tt]) { tr = false; break; }
+        if (pl.diag_arr[2][t1] >= 0) tr = true;
+    }
+    pl.diag_tr = tr;
+}
+
 void sumfact_plan(const igx_patch *pt, int kind, Plan &pl)
 {
     const int dim = pt->dim;
@@ -1084,6 +1123,7 @@ void sumfact_plan(const igx_patch *pt, int kind, Plan &pl)
         else
             for (size_t i = 0; i < terms.size(); ++i) add_slot(kind == IGX_MASS ? 0 : terms[i].t[2], terms[i].t[1], X[term_x[i]].slot);
         pl.fused = fused_kernel();
+        if (pl.fused == Plan::BF3) plan_diag_skip(pt, pl);
         if (pl.fused != Plan::NO_FUSED) return;
     }
     // ---- final stage: the matrix-core kernel on request (IGX_FINAL=mfma), the quadrature-lane kernel for single interior knots
@@ -1177,7 +1217,9 @@ static BFInputs bf_inputs(const Plan &pl, const double *base, size_t stride)
         for (int t1 = 0; t1 < 4; ++t1) {
             in.slot_n[y][t1] = pl.slot_n[y][t1];
             for (int i = 0; i < pl.slot_n[y][t1]; ++i) in.slot_ptr[y][t1][i] = base + (size_t)pl.slot_arr[y][t1][i] * stride;
+            in.diag_ptr[y][t1] = (pl.diag_skip && pl.diag_arr[y][t1] >= 0) ? base + (size_t)pl.diag_arr[y][t1] * stride : nullptr;
         }
+    in.diag_skip = pl.diag_skip ? 1 : 0; in.diag_tr = pl.diag_tr ? 1 : 0;
     in.sym = pl.sym ? 1 : 0;
     return in;
 }
@@ -1272,7 +1314,7 @@ static int run_stage0(igx_patch *pt, const Plan &pl, int np0, long long NPL, lon
             so[x] = pt->d_K1 + (size_t)xa.slot * np0 * NPLs;
         }
         const SweepChunks ch = sweep_chunks((NPL + 63) / 64, pt->s0_hi - pt->s0_lo, A0.P, dim == 2 ? geoa2d_min_chunk(A0.P) : 0);
-        if (int rc = launch_geoA(st, pt, pl.kind, pl.nX, sf, stp, so, NPLs, ch.len, ch.nchunks, sxf, sxt)) return rc;
+        if (int rc = launch_geoA(st, pt, pl.kind, pl.nX, sf, stp, so, NPLs, ch.len, ch.nchunks, sxf, sxt, nullptr, pl.diag_skip ? pl.nodiag_mask : 0u)) return rc;
         pt->last_path |= IGX_PATH_GEOA;
         pt->timing.n_launches++;
         return IGX_OK;
