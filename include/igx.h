@@ -213,6 +213,12 @@ int igx_patch_set_form(igx_patch *patch, const double *const coef[16]);
    (igx_patch_gauss_slab planes x G1 [x G2], C order): no host staging of full-grid arrays.  A failed call of either
    variant leaves the previously set form untouched. */
 int igx_patch_set_form_d(igx_patch *patch, const double *const d_coef[16]);
+/* igx_patch_set_form_d with the table  scale * d_a + d_b  formed by one kernel straight into the copy the patch keeps (no staging
+   array): the tables of an iterate-dependent form -- d_a the fixed part (uploaded once, e.g. the viscous form, scale the
+   viscosity), d_b the part evaluated from the iterate.  A NULL on one side counts as zero, an entry NULL on
+   both sides stays absent; d_a or d_b itself may be NULL (not both).  Each entry is rounded as the host sum is: the product, then
+   the sum.  A failed call leaves the previously set form untouched. */
+int igx_patch_set_form_sum_d(igx_patch *patch, const double *const d_a[16], double scale, const double *const d_b[16]);
 
 /* The same table given as C expressions in the physical coordinates x, y, z (and pi; the grammar of
    igx_patch_set_coeff_expr): expr[4*r + s] or NULL.  The FIELD kernel of the form is generated with the expressions inside
@@ -345,6 +351,13 @@ int igx_rtc_compile_load_vector(int P, int npass, int parametric, const char *ex
    coefficients resident).  A row slab or a span box: IGX_ERR_UNSUPPORTED; a geometry given as Jacobian arrays serves
    want_grad = 0 only (IGX_ERR_UNSUPPORTED otherwise).  igx_last_timing: total_ms = the kernels, algo_used = 4. */
 int igx_patch_eval_spline_d(igx_patch *patch, const double *d_coeffs, int want_grad, double *const d_out[4]);
+/* nc = 2 or 3 (else IGX_ERR_ARG) splines of the patch's own space in one pass: their dofs component-major in one device vector
+   (nc x N0 x N1 [x N2] doubles: the velocity part of a saddle-point solver's vector).  d_out[c], c < nc, receives the value of
+   component c; with want_grad != 0, d_out[nc + c * dim + r], r < dim, receives its physical partial r in the jet order above:
+   nc * (1 + dim) arrays, each over the resident slab.  The geometry Jacobian is evaluated and inverted once per point for all
+   components.  Component c has the bits of igx_patch_eval_spline_d on the dofs of component c, value and gradient.  Refusals as
+   igx_patch_eval_spline_d's; the line buffers hold nc times as much, so the longest last axis that fits is shorter. */
+int igx_patch_eval_vspline_d(igx_patch *patch, int nc, const double *d_coeffs, int want_grad, double *const d_out[12]);
 /* igx_patch_set_form_expr's coefficient kernel with m <= 16 further doubles f0 .. f{m-1} in scope, loaded from the device arrays
    d_in[0 .. m) at the thread's resident Gauss point:  d_out[k * npts + i] = expr_k(x, y, z, pi, f0, ..) for the n expressions
    (npts = resident points).  Same grammar, same refusals and the same on-disk cache (m is part of the generated source).  With a
@@ -665,6 +678,19 @@ int  igx_solver_create_block(igx_patch *patch, int ncomp, int symmetric, const i
    the device buffer, not a copy.  The patch then holds no values (its next assembly allocates anew).  p or q out of range, a
    block taken twice, or a patch without IGX_FORM values: IGX_ERR_ARG. */
 int  igx_solver_take_block(igx_solver *solver, int p, int q);
+/* Makes the IGX_FORM values the patch holds now the new block (p, q) of a live solver, whether the block is held already or
+   absent so far (a nonlinear iteration: DESIGN.md section 33).  The old buffer goes back to the patch as its next values buffer,
+   so that a replacement neither allocates nor frees; the patch then holds no values, as after igx_solver_take_block.  A selected
+   IGX_PRECOND_JACOBI gathers the diagonal of a replaced diagonal block again; Kronecker factors, B, B^T, the masks and the
+   projection state of a saddle-point solver are untouched.  Whether the new blocks fit the solver's method (CG: symmetric) is the
+   caller's business.  Not a block solver of a patch, p or q out of range, or a patch without IGX_FORM values: IGX_ERR_ARG; a solver
+   with an eigen-solver session: IGX_ERR_UNSUPPORTED. */
+int  igx_solver_replace_block(igx_solver *solver, int p, int q);
+/* hidden != 0: the products of a saddle-point solver leave the off-diagonal block (p, q) out, as if it were absent, until it is
+   shown again (hidden = 0) or replaced; the solver keeps the buffer.  What a Picard step after a Newton step needs when the
+   viscous form has no off-diagonal part: the Newton blocks must not enter the Picard residual, and nothing is freed.  Not a
+   saddle-point solver: IGX_ERR_UNSUPPORTED; p == q or out of range: IGX_ERR_ARG. */
+int  igx_solver_hide_block(igx_solver *solver, int p, int q, int hidden);
 /* The fast-diagonalization inverse (x)U_k . D^-1 . (x)U_k^T of component `comp` on its free box box_lo[k] <= i_k < box_hi[k],
    which must be exactly the free dofs of that component (arguments as igx_solver_set_precond's, lam_mode IGX_KRON_*). */
 int  igx_solver_set_block_kron(igx_solver *solver, int comp, const int32_t *box_lo, const int32_t *box_hi,
@@ -1043,6 +1069,20 @@ int  igx_solver_gmres_restarts(const igx_solver *solver);
 int  igx_solver_gmres_orth_d(igx_solver *solver, const double *d_V, int ncols, double *d_w, double *h_out, double *norm_out);
 int  igx_solver_gmres_combine_d(igx_solver *solver, const double *d_V, int ncols, const double *y, double *d_t);
 int  igx_solver_gmres_timing(const igx_solver *solver, float *orth_ms, float *combine_ms);
+
+/* --- The correction form of a nonlinear iteration on a saddle-point solver running GMRES (stationary Navier-Stokes: Picard and
+   Newton steps).  igx_solver_newton_update_d's siblings: that call serves scalar patch solvers only.
+   The iterate d_x (nc N_u + N_p doubles, Dirichlet values included) is the caller's device vector from the first step to the last.
+   igx_solver_saddle_residual_d: r = R (d_b - K d_x) by the row kernels (igx_solver_saddle_product_d's contract; d_b may be NULL),
+   its pressure mean removed if the solver projects (igx_solver_saddle_projection); r stays in the solver, *norm receives ||r||,
+   the one scalar that comes down.
+   igx_solver_saddle_correct_d: d_x += K^-1 r with the blocks the solver holds NOW -- they may have been replaced since the
+   residual was formed (igx_solver_replace_block: Newton forms the residual with the Picard blocks and solves with the Newton
+   blocks) -- by GMRES from zero with zero Dirichlet values to |g_k| <= tol * ||r||; info as igx_solver_solve's.
+   A solver that is not a saddle-point solver: IGX_ERR_ARG; MINRES selected: IGX_ERR_UNSUPPORTED. */
+int  igx_solver_saddle_residual_d(igx_solver *solver, const double *d_b, const double *d_x, double *norm);
+int  igx_solver_saddle_correct_d(igx_solver *solver, double *d_x, double tol, int maxiter, int check_every, int timed,
+                                 igx_solve_info *info);
 
 #ifdef __cplusplus
 }

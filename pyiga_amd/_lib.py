@@ -324,6 +324,12 @@ SYMBOLS = [
     ('igx_solver_gmres_orth_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _dp, _dp]),
     ('igx_solver_gmres_combine_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _dp, C.c_void_p]),
     ('igx_solver_gmres_timing', C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ('igx_patch_eval_vspline_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p * 12]),
+    ('igx_patch_set_form_sum_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    ('igx_solver_replace_block', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ('igx_solver_hide_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ('igx_solver_saddle_residual_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
+    ('igx_solver_saddle_correct_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(SolveInfo)]),
 ]
 
 _lib = None

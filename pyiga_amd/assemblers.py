@@ -517,6 +517,42 @@ class DevicePatch:
         _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, base, out.nbytes), 'igx_dev_download')
         return out
 
+    def eval_vspline(self, d_coeffs, nc, want_grad=False, to_host=False, buf='_d_vspl'):
+        """`nc` = 2 or 3 splines of the patch's space with component-major device dofs `d_coeffs` in one pass
+        (igx_patch_eval_vspline_d).  Returns ``(values, grads)``: the device pointers of the `nc` value arrays and
+        ``grads[c][r]`` of the physical partials (jet order; an empty list without `want_grad`), kept by the patch and
+        overwritten by the next call; with to_host the arrays themselves, values first, then the partials component by
+        component."""
+        npts = self.resident_points()
+        n = nc * (1 + self.dim) if want_grad else nc
+        base = self._dev_buffer(buf, 8 * npts * nc * (1 + self.dim))
+        ptrs = (C.c_void_p * 12)()
+        for k in range(n):
+            ptrs[k] = base + 8 * npts * k
+        _lib.check(_lib.load().igx_patch_eval_vspline_d(self.handle, nc, d_coeffs, 1 if want_grad else 0, ptrs), 'igx_patch_eval_vspline_d')
+        if to_host:
+            g0_lo, g0_n = self.gauss_slab()
+            out = np.empty((n, g0_n) + self.resident_grid()[1:])
+            _lib.check(_lib.load().igx_dev_download(self.ctx.handle, out.ctypes.data, base, out.nbytes), 'igx_dev_download')
+            return out
+        vals = [ptrs[c] for c in range(nc)]
+        grads = [[ptrs[nc + c * self.dim + r] for r in range(self.dim)] for c in range(nc)] if want_grad else []
+        return vals, grads
+
+    def set_form_sum_resident(self, table_a, scale, table_b):
+        """The form table ``scale * table_a + table_b`` from device arrays over the resident slab, formed on the device
+        (igx_patch_set_form_sum_d): 4x4 nested lists of device pointers or None; either table may be None."""
+        def pack(table):
+            if table is None:
+                return None
+            ptrs = (C.c_void_p * 16)()
+            for r in range(4):
+                for s in range(4):
+                    if table[r][s] is not None:
+                        ptrs[4 * r + s] = table[r][s]
+            return ptrs
+        _lib.check(_lib.load().igx_patch_set_form_sum_d(self.handle, pack(table_a), float(scale), pack(table_b)), 'igx_patch_set_form_sum_d')
+
     # -- integrals and error sums over the patch (DESIGN.md section 24)
     @property
     def numspans(self):

@@ -667,9 +667,32 @@ int igx_rtc_compile(const char *expr, const char *arch, char *path_out, int path
 // coefficient table of IGX_FORM: validated into locals, committed to the patch only when everything (allocation, copies)
 // has succeeded -- a failed call leaves the previous form in place.  `on_device`: the arrays are device pointers over the
 // RESIDENT Gauss slab (igx_patch_gauss_slab), else host pointers over the full grid.
-static int set_form_impl(igx_patch *pt, const double *const coef[16], bool on_device, const char *who)
+// the tables scale * a + b of igx_patch_set_form_sum_d, slot after slot: two roundings per entry, as the host forms the sum
+struct FormSumArgs { const double *a[16], *b[16]; };
+__global__ void __launch_bounds__(256) k_form_sum(const FormSumArgs T, const int n, const long long npts, const double scale, double *__restrict__ out)
 {
-    if (!pt || !coef) { set_error("%s: null argument", who); return IGX_ERR_ARG; }
+#pragma clang fp contract(off)                 // (a fused multiply-add would round once: the host's table rounds twice)
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    for (int k = 0; k < n; ++k) {
+        const double *a = T.a[k], *b = T.b[k];
+        double v;
+        if (a && b) {
+            const double sa = scale * a[i];
+            v = sa + b[i];
+        } else if (a) v = scale * a[i];
+        else v = b[i];
+        out[(long long)k * npts + i] = v;
+    }
+}
+
+// `sum_a` (device arrays, with on_device): the table is scale * sum_a + coef, an entry present if it is on either side
+static int set_form_impl(igx_patch *pt, const double *const coef_in[16], bool on_device, const char *who, const double *const sum_a[16] = nullptr,
+                         double scale = 1.0)
+{
+    if (!pt || (!coef_in && !sum_a)) { set_error("%s: null argument", who); return IGX_ERR_ARG; }
+    const double *coef[16];                       // what decides the presence of an entry: with sum_a, either side
+    for (int k = 0; k < 16; ++k) coef[k] = coef_in && coef_in[k] ? coef_in[k] : (sum_a ? sum_a[k] : nullptr);
     const int nj = pt->dim + 1;                   // jet size: value + dim derivatives
     for (int r = 0; r < 4; ++r)
         for (int s = 0; s < 4; ++s)
@@ -691,7 +714,14 @@ static int set_form_impl(igx_patch *pt, const double *const coef[16], bool on_de
     double *d_new = nullptr;
     hipError_t e = hipMalloc((void **)&d_new, std::max<size_t>(1, (size_t)n * npts) * sizeof(double));
     if (e != hipSuccess) { set_error("hipMalloc of %.2f GB for the form coefficients failed", n * npts * 8.0 / 1e9); return IGX_ERR_NOMEM; }
-    for (int k = 0; k < 16 && e == hipSuccess; ++k)
+    if (sum_a) {
+        FormSumArgs T{};
+        for (int k = 0; k < 16; ++k)
+            if (slot[k] >= 0) { T.a[slot[k]] = sum_a[k]; T.b[slot[k]] = coef_in ? coef_in[k] : nullptr; }
+        if (npts > 0) k_form_sum<<<(unsigned)((npts + 255) / 256), 256, 0, pt->ctx->stream>>>(T, n, (long long)npts, scale, d_new);
+        e = hipGetLastError();
+    }
+    for (int k = 0; k < 16 && e == hipSuccess && !sum_a; ++k)
         if (coef[k])
             e = on_device ? hipMemcpyAsync(d_new + (size_t)slot[k] * npts, coef[k], npts * sizeof(double), hipMemcpyDeviceToDevice, pt->ctx->stream)
                           : hipMemcpyAsync(d_new + (size_t)slot[k] * npts, coef[k] + (pt->boxed ? 0 : (size_t)pt->dev.g0_lo * per_plane), npts * sizeof(double),
@@ -923,6 +953,19 @@ int igx_patch_set_form_d(igx_patch *pt, const double *const d_coef[16])
     if (pt) pt->ftab.valid = false;                      // (sampled coefficients: the stage kernels over the field arrays)
     if (pt && pt->twin) pt->twin->ftab.valid = false;
     return set_form_impl(pt, d_coef, true, "igx_patch_set_form_d");
+}
+
+int igx_patch_set_form_sum_d(igx_patch *pt, const double *const d_a[16], double scale, const double *const d_b[16])
+{
+    if (!pt || (!d_a && !d_b)) { set_error("igx_patch_set_form_sum_d: null argument"); return IGX_ERR_ARG; }
+    if (!std::isfinite(scale)) { set_error("igx_patch_set_form_sum_d: scale must be finite"); return IGX_ERR_ARG; }
+    if (pt->boxed) { set_error("igx_patch_set_form_sum_d: the patch holds a span box"); return IGX_ERR_UNSUPPORTED; }
+    static const double *const none[16] = {};
+    const int rc = set_form_impl(pt, d_b, true, "igx_patch_set_form_sum_d", d_a ? d_a : none, scale);
+    if (rc) return rc;
+    pt->ftab.valid = false;                              // (sampled coefficients, as igx_patch_set_form_d)
+    if (pt->twin) pt->twin->ftab.valid = false;
+    return IGX_OK;
 }
 
 int igx_patch_gauss(const igx_patch *pt, int axis, double *nodes, double *weights)
@@ -1436,6 +1479,35 @@ int igx_patch_eval_spline_d(igx_patch *pt, const double *d_coeffs, int want_grad
     (void)hipEventElapsedTime(&pt->timing.total_ms, pt->ctx->ev[6], pt->ctx->ev[7]);
     pt->timing.algo_used = 4;                        // spline evaluation
     pt->timing.n_launches = pt->dim == 3 ? 2 : 1;
+    return IGX_OK;
+}
+
+// nc = 2 or 3 splines of the patch's own space, component-major in one device vector, in one pass (k_vspline12)
+int igx_patch_eval_vspline_d(igx_patch *pt, int nc, const double *d_coeffs, int want_grad, double *const d_out[12])
+{
+    const char *what = "igx_patch_eval_vspline_d";
+    if (!pt || !d_coeffs || !d_out) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (nc != 2 && nc != 3) { set_error("%s: %d components (2 or 3)", what, nc); return IGX_ERR_ARG; }
+    if (pt->boxed) { set_error("%s: the patch holds a span box (batched entries only)", what); return IGX_ERR_UNSUPPORTED; }
+    if (pt->r0_lo != 0 || pt->r0_hi != pt->ax[0].N) { set_error("%s: whole patches only (the dof vector is the patch's, a row slab holds a part of the Gauss grid)", what); return IGX_ERR_UNSUPPORTED; }
+    if (want_grad && pt->geo_kind == IGX_GEO_JACOBIAN) { set_error("%s: the physical gradient needs a spline geometry", what); return IGX_ERR_UNSUPPORTED; }
+    if (int rcb = basis_orders_ok(pt, IGX_MASS, what)) return rcb;
+    const int nout = nc * (want_grad ? 1 + pt->dim : 1);
+    for (int k = 0; k < nout; ++k)
+        if (!d_out[k]) { set_error("%s: output array %d is null", what, k); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(pt->ctx->device));
+    hipStream_t st = pt->ctx->stream;
+    int rc;
+    if ((rc = ws_reserve(&pt->d_sp_ws, &pt->sp_ws_cap, vspline_eval_workspace(pt, nc, want_grad), "spline evaluation workspace"))) return rc;
+    (void)hipEventRecord(pt->ctx->ev[6], st);
+    rc = launch_vspline_eval(st, pt, nc, d_coeffs, want_grad, d_out, pt->d_sp_ws);
+    (void)hipEventRecord(pt->ctx->ev[7], st);
+    if (rc) return rc;
+    IGX_HIP(hipStreamSynchronize(st));
+    memset(&pt->timing, 0, sizeof(pt->timing));
+    (void)hipEventElapsedTime(&pt->timing.total_ms, pt->ctx->ev[6], pt->ctx->ev[7]);
+    pt->timing.algo_used = 4;                        // spline evaluation
+    pt->timing.n_launches = pt->dim == 3 ? 1 + nc : 1;
     return IGX_OK;
 }
 

@@ -293,6 +293,8 @@ int launch_load_vector(hipStream_t st, const igx_patch *pt, const double *d_f, c
 // a spline of the patch's space from a device dof vector at the resident Gauss points (kern_spline.hip)
 size_t spline_eval_workspace(const igx_patch *pt, int want_grad);
 int launch_spline_eval(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, double *const d_out[4], double *d_ws);
+size_t vspline_eval_workspace(const igx_patch *pt, int nc, int want_grad);
+int launch_vspline_eval(hipStream_t st, const igx_patch *pt, int nc, const double *d_coeffs, int want_grad, double *const d_out[12], double *d_ws);
 int launch_spline_axis0(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, double *d_ws, const double **t0, const double **t1);
 // sums of W f_k and error sums of a spline over a whole patch, total and per element, in a fixed order (kern_quad.hip)
 size_t quad_workspace(const igx_patch *pt, int nk);

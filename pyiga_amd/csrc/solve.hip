@@ -1687,6 +1687,47 @@ int igx_solver_take_block(igx_solver *s, int p, int q)
     return IGX_OK;
 }
 
+int igx_solver_replace_block(igx_solver *s, int p, int q)
+{
+    const char *what = "igx_solver_replace_block";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (s->ncomp < 2 || s->mp) { set_error("%s: not a block solver of a patch (igx_solver_create_block)", what); return IGX_ERR_ARG; }
+    if (p < 0 || p >= s->ncomp || q < 0 || q >= s->ncomp) { set_error("%s: block (%d, %d) of %d components", what, p, q, s->ncomp); return IGX_ERR_ARG; }
+    if (s->eig) { set_error("%s: the solver holds an eigen-solver session, whose pieces were made for the present blocks", what); return IGX_ERR_UNSUPPORTED; }
+    igx_patch *pt = s->pt;
+    if (pt->values_kind != IGX_FORM || !pt->d_data) {
+        set_error("%s: the patch holds no IGX_FORM values: assemble them first (igx_assemble, data_out may be NULL)", what);
+        return IGX_ERR_ARG;
+    }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    IGX_HIP(hipStreamSynchronize(pt->ctx->stream));
+    IGX_HIP(hipStreamSynchronize(st));              // (no product of the solver reads the old values any more)
+    double *&dst = s->block.blk[p * s->ncomp + q];
+    double *old = dst;
+    dst = pt->d_data;                               // the buffers change hands: the old block is the patch's next values buffer
+    pt->d_data = old;                               // (both were allocated by igx_assemble for this patch: one size), or none yet
+    pt->values_kind = -1;
+    s->block.hidden[p * s->ncomp + q] = false;
+    if (p == q && s->precond == IGX_PRECOND_JACOBI) {
+        const long long N = s->saddle ? s->sad.nu : s->n / s->ncomp;
+        jacobi_diagonal(st, s, dst, s->dinv + p * N, p);
+        IGX_HIP(hipGetLastError());
+        IGX_HIP(hipStreamSynchronize(st));
+    }
+    return IGX_OK;
+}
+
+int igx_solver_hide_block(igx_solver *s, int p, int q, int hidden)
+{
+    const char *what = "igx_solver_hide_block";
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (!s->saddle) { set_error("%s: saddle-point solvers only (igx_solver_create_saddle)", what); return IGX_ERR_UNSUPPORTED; }
+    if (p < 0 || p >= s->ncomp || q < 0 || q >= s->ncomp || p == q) { set_error("%s: (%d, %d) is not an off-diagonal block of %d components", what, p, q, s->ncomp); return IGX_ERR_ARG; }
+    s->block.hidden[p * s->ncomp + q] = hidden != 0;      // (read on the host at every launch: the next product sees it)
+    return IGX_OK;
+}
+
 int igx_solver_set_block_kron(igx_solver *s, int comp, const int32_t *box_lo, const int32_t *box_hi, const double *const *U,
                               const double *const *lam, int mode)
 {

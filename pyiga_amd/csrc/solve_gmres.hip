@@ -354,11 +354,15 @@ int solve_gmres(hipStream_t st, igx_solver *s, const double *rhs, double tol, in
     G.restarts = 0;
     double h[GS_N] = {};
     int total = 0;
+    // G.project_ops: every product and every preconditioned vector loses its pressure mean, so that the iteration runs on Q K Q and
+    // Q P in the space of mean-free pressures (the partials of the sums are consumed before the next kernel writes d_part)
+    auto project = [&](double *v) { return G.project_ops ? saddle_project_vector(st, s, v) : (int)IGX_OK; };
     for (int cycle = 0;; ++cycle) {
         // the cycle's start: v_0 = r / ||r||, r = rhs - K x (the first cycle: as the caller formed it, in s->r)
         const double *r = s->r;
         if (cycle > 0) {
             if (int rc = saddle_spmv(st, s, s->x, rhs, -1.0, V, nullptr, nullptr)) return rc;
+            if (int rc = project(V)) return rc;
             r = V;
         }
         k_gm_sumsq<<<nbv, BLOCK, 0, st>>>(n, r, pN, a.sc, cycle == 0);
@@ -371,8 +375,10 @@ int solve_gmres(hipStream_t st, igx_solver *s, const double *rhs, double tol, in
             double *vj = V + (long long)j * n, *w = vj + n;
             if (timed) IGX_HIP(hipEventRecord(E[0], st));
             if (int rc = saddle_apply_precond(st, s, vj, z)) return rc;
+            if (int rc = project(z)) return rc;
             if (timed) IGX_HIP(hipEventRecord(E[1], st));
             if (int rc = saddle_spmv(st, s, z, nullptr, 1.0, w, nullptr, nullptr)) return rc;
+            if (int rc = project(w)) return rc;
             if (timed) IGX_HIP(hipEventRecord(E[2], st));
             if (int rc = orthogonalise(st, s, a, V, j + 1, w)) return rc;
             k_gm_fin<<<1, BLOCK, 0, st>>>(nullptr, 0, j + 1, pN, (int)nbv, a, GF_ROT, tol, 0);
@@ -396,6 +402,7 @@ int solve_gmres(hipStream_t st, igx_solver *s, const double *rhs, double tol, in
         k_gm_combine<MB><<<nbv, BLOCK, 0, st>>>(n, V, a.y, t, a.sc);
         IGX_HIP(hipGetLastError());
         if (int rc = saddle_apply_precond(st, s, t, z)) return rc;
+        if (int rc = project(z)) return rc;
         k_gm_axpy<<<nbv, BLOCK, 0, st>>>(n, z, s->x, a.sc);
         k_gm_fin<<<1, BLOCK, 0, st>>>(nullptr, 0, 0, nullptr, 0, a, GF_CLOSE, tol, total < maxiter ? 1 : 0);
         IGX_HIP(hipGetLastError());

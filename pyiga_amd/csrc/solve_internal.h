@@ -127,6 +127,7 @@ struct BicgState {
 // block solver of a vector-valued form (igx_solver_create_block): ncomp components of g.nrows dofs each, n = ncomp g.nrows
 struct BlockState {
     double *blk[9] = {};                      // block (p, q) at p * ncomp + q, taken from the patch (owned), or null
+    bool hidden[9] = {};                      // a saddle solver's products leave the block out (igx_solver_hide_block); it stays owned
     FastDiag bkron[3] = {};                   // per component: the fast-diagonalization inverse on its free box (in d_bkron[c])
     double *d_bkron[3] = {};
     int klo[3][3] = {}, knb[3][3] = {}, kmode[3] = {};   // per component: its box and lam_mode (the eigen-solver's batched plans)
@@ -238,6 +239,8 @@ struct GmresState {
     int cap = 0;                              // the restart the arrays below were allocated for
     double *d_V = nullptr;                    // the basis: (cap + 1) columns of n
     double *d_small = nullptr;                // scalars | h | hp | cs | sn | g | y | R (gmres_small_len(cap) doubles)
+    int project_ops = 0;                      // the solve runs on Q K Q and Q P, Q taking the pressure mean off (igx_solver_saddle_correct_d
+                                              // on a projecting solver: DESIGN.md section 33); 0: the operators as they are
     int restarts = 0;                         // of the last solve
     float orth_ms = 0.0f, combine_ms = 0.0f;  // device time of the orthogonalisations / the updates of x of the last timed solve
                                               // (igx_solver_gmres_orth_d, _combine_d: of that call)
@@ -346,6 +349,9 @@ int saddle_set_precond(igx_solver *s, int precond);
 int saddle_apply_precond(hipStream_t st, igx_solver *s, const double *r, double *z);
 int saddle_solve_lifted(hipStream_t st, igx_solver *s, const double *lift, bool x0_in_x, double tol, int maxiter, int check_every, int timed,
                         igx_solve_info &inf);
+
+// the mean of the free pressure part of v taken off it (a projecting solver; else nothing changes)
+int saddle_project_vector(hipStream_t st, igx_solver *s, double *v);
 
 // y = a + b over the n entries (k_mr_add)
 void saddle_add(hipStream_t st, long long n, const double *a, const double *b, double *y);

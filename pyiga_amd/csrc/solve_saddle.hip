@@ -478,7 +478,7 @@ unsigned saddle_blocks(int nb_max, int gw, long long rows)
 BlockVals block_vals(const igx_solver *s)
 {
     BlockVals A{};
-    for (int k = 0; k < s->ncomp * s->ncomp; ++k) A.v[k] = s->block.blk[k];
+    for (int k = 0; k < s->ncomp * s->ncomp; ++k) A.v[k] = s->block.hidden[k] ? nullptr : s->block.blk[k];
     return A;
 }
 
@@ -667,6 +667,8 @@ static int project_pressure(hipStream_t st, igx_solver *s, double *v, double *me
     }
     return IGX_OK;
 }
+
+int saddle_project_vector(hipStream_t st, igx_solver *s, double *v) { return project_pressure(st, s, v, nullptr, nullptr); }
 
 // ||v|| by the fixed-order two-pass sum
 static int vector_norm(hipStream_t st, igx_solver *s, const double *v, double *norm)
@@ -941,6 +943,63 @@ int igx_solver_saddle_product_d(igx_solver *s, const double *d_x, const double *
         if (d_pd)
             if (int rc = sum_partials(st, s, saddle_partials(s), dot)) return rc;
     }
+    return IGX_OK;
+}
+
+// --- the correction form of a nonlinear saddle-point iteration: the iterate is the caller's device vector,
+// the residual stays in s->b between the two calls, so that the blocks may be replaced in between (Newton: the residual is that
+// of the Picard matrix, the correction is solved with the Newton matrix)
+static int saddle_gmres_ok(const igx_solver *s, const char *what)
+{
+    if (!s) { set_error("%s: null solver", what); return IGX_ERR_ARG; }
+    if (!s->saddle) { set_error("%s: not a saddle-point solver (igx_solver_create_saddle)", what); return IGX_ERR_ARG; }
+    if (s->gm.restart <= 0) { set_error("%s: the solver does not run GMRES (igx_solver_set_gmres)", what); return IGX_ERR_UNSUPPORTED; }
+    return saddle_check_values(s, what);
+}
+
+int igx_solver_saddle_residual_d(igx_solver *s, const double *d_b, const double *d_x, double *norm)
+{
+    const char *what = "igx_solver_saddle_residual_d";
+    if (int rc = saddle_gmres_ok(s, what)) return rc;
+    if (!d_x || !norm) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (d_x == s->b || d_b == s->b) { set_error("%s: d_x and d_b must not be the solver's own vectors", what); return IGX_ERR_ARG; }
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    // r = R (b - K x) by the row kernels, x unmasked (it carries the Dirichlet values); projected as a solve projects its right-hand side
+    if (int rc = saddle_spmv(st, s, d_x, d_b, -1.0, s->b, nullptr, nullptr)) return rc;
+    if (s->sad.project)
+        if (int rc = project_pressure(st, s, s->b, nullptr, nullptr)) return rc;
+    return vector_norm(st, s, s->b, norm);
+}
+
+int igx_solver_saddle_correct_d(igx_solver *s, double *d_x, double tol, int maxiter, int check_every, int timed, igx_solve_info *info)
+{
+    const char *what = "igx_solver_saddle_correct_d";
+    if (int rc = saddle_gmres_ok(s, what)) return rc;
+    if (!d_x) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
+    if (!(tol >= 0.0) || maxiter < 0) { set_error("%s: tol must be >= 0 and maxiter >= 0", what); return IGX_ERR_ARG; }
+    if (check_every < 1) check_every = 1;
+    s->sad.breakdown = 0;
+    IGX_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    igx_solve_info inf{};
+    IGX_HIP(hipEventRecord(s->ev[5], st));
+    // nothing is lifted: the correction vanishes on the fixed dofs, the right-hand side is the residual in s->b, GMRES starts from zero
+    // A projecting solver: the constant pressure is the kernel of the continuous operator, but on a NURBS geometry only nearly that
+    // of the discrete one (B^T 1 is the quadrature error of int div v, 1e-9 on the golden case).  Left alone, GMRES resolves that
+    // direction once the residual is small enough: corrections with pressures of 1e3 and a velocity 1e-4 off.  The correction
+    // therefore runs on Q K Q and Q P, Q taking the pressure mean off: exactly singular, consistent, its solution mean-free.
+    s->gm.project_ops = s->sad.project ? 1 : 0;
+    const int rc_solve = saddle_solve_lifted(st, s, nullptr, false, tol, maxiter, check_every, timed, inf);
+    s->gm.project_ops = 0;
+    if (rc_solve) return rc_solve;
+    k_mr_add<<<blocks256(s->n), 256, 0, st>>>(s->n, d_x, s->x, d_x);
+    IGX_HIP(hipGetLastError());
+    IGX_HIP(hipEventRecord(s->ev[4], st));
+    IGX_HIP(hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&inf.total_ms, s->ev[5], s->ev[4]);
+    inf.n_free = s->n - (long long)s->fixed.size();
+    if (info) *info = inf;
     return IGX_OK;
 }
 

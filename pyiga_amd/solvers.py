@@ -933,10 +933,152 @@ class OseenSystem(SaddlePointSystem):
     def _velocity_tables(self, table, geo, fargs):
         """`viscosity` times the tables of `a` (given) plus those of the convection form on the same patch."""
         from .form_assemblers import FormAssembler
+        self._geo, self._fargs, self._visc_table = geo, dict(fargs), table       # (kept for update())
         if self.convection is None:
             return table
         asm = FormAssembler(self.kvs, geo, self.convection, bfuns=[('u', self.ncomp), ('v', self.ncomp)], inputs=fargs, patch=self.patch)
         return add_block_tables(table, asm._table)
+
+    # -- the convection blocks of a live system replaced (DESIGN.md section 33)
+    WIND_FORM = 'grad(u).dot(w).dot(v) * dx'
+    _d_atab = _d_wind = _phases = None
+
+    def _replace_blocks(self, table):
+        """``_take_blocks`` on a live solver: every block of `table` that is not absent is assembled and replaces the solver's
+        (``igx_solver_replace_block``: the buffers change hands, nothing is allocated after the first replacement)."""
+        from .form_assemblers import _full_table
+        lib = _lib.load()
+        nc, d = self.ncomp, len(self.kvs)
+        for p in range(nc):
+            for q in range(nc):
+                tab = table[p][q]
+                if all(e is None for row in tab for e in row):
+                    if self.present[p][q]:             # (only an off-diagonal block can be: the diagonal ones carry `a`)
+                        _lib.check(lib.igx_solver_hide_block(self.handle, p, q, 1), 'igx_solver_hide_block')
+                    continue
+                self.patch.set_form(_full_table(tab, d))
+                self.patch.assemble('form', to_host=False)
+                _lib.check(lib.igx_solver_replace_block(self.handle, p, q), 'igx_solver_replace_block')
+                self.present[p][q] = True
+
+    def _gauss_shape(self):
+        return tuple(int(self.patch.info.ngauss[k]) for k in range(len(self.kvs)))
+
+    def _device_a_tables(self):
+        """The unscaled tables of `a` on the device, uploaded once: ``[p][q]`` a 4x4 table of device pointers, or None."""
+        if self._d_atab is None:
+            nc, d, G = self.ncomp, len(self.kvs), self._gauss_shape()
+            out = [[None] * nc for _ in range(nc)]
+            for p in range(nc):
+                for q in range(nc):
+                    tab = self.asm_a._table[p][q]
+                    where = [(r, s) for r in range(d + 1) for s in range(d + 1) if tab[r][s] is not None]
+                    if not where:
+                        continue
+                    ptrs = self.patch.upload_fields([np.broadcast_to(np.asarray(tab[r][s], dtype=np.float64), G) for r, s in where],
+                                                    buf='_d_atab_%d%d' % (p, q))
+                    out[p][q] = [[None] * 4 for _ in range(4)]
+                    for (r, s), ptr in zip(where, ptrs):
+                        out[p][q][r][s] = ptr
+            self._d_atab = out
+        return self._d_atab
+
+    def _velocity_dofs(self, w):
+        """The component-major velocity dofs (``nc * N`` entries) of `w`: a full solution vector, its velocity part, or a
+        coefficient array of shape ``ndofs + (nc,)``; None if `w` is none of these."""
+        if callable(w):
+            return None
+        w = np.asarray(w, dtype=np.float64)
+        nv = self.ncomp * self.N
+        if w.ndim == 1 and w.size in (self.n, nv):
+            return np.ascontiguousarray(w[:nv])
+        if w.shape == self.ndofs + (self.ncomp,) and w.shape != self._gauss_shape() + (self.ncomp,):
+            return np.ascontiguousarray(np.moveaxis(w, -1, 0)).ravel()
+        return None
+
+    def _wind_blocks(self, d_u, newton=False, want_grad=None, evaluate=True):
+        """The blocks of ``viscosity a + (w . grad) u v`` -- with `newton` also ``+ (u . grad) w v`` -- for the wind with the
+        device dofs `d_u`, assembled and replaced: one fused evaluation of the wind (igx_patch_eval_vspline_d; with the gradient
+        if `want_grad`, default `newton`; not `evaluate`: the arrays of the last evaluation serve again), the tables formed on
+        the device (igx_patch_set_form_sum_d).  Returns the number of blocks assembled; with ``self._phases`` a list, the device
+        ms of the evaluation and of the assemblies are noted there."""
+        lib = _lib.load()
+        nc, d = self.ncomp, len(self.kvs)
+        if nc != d:
+            raise ValueError('a wind given by its dofs needs as many velocity components as dimensions')
+        atab = self._device_a_tables()
+        timed = self._phases is not None
+        if evaluate:
+            self._wind = self.patch.eval_vspline(d_u, nc, want_grad=newton if want_grad is None else want_grad)
+            if timed:
+                self._phases.append(dict(wind_ms=self.patch.timing()['total_ms']))
+        vals, grads = self._wind
+        count, asm_ms = 0, 0.0
+        for p in range(nc):
+            for q in range(nc):
+                if p != q and not newton:
+                    continue
+                b = [[None] * 4 for _ in range(4)]
+                if p == q:
+                    for j in range(d):
+                        b[0][1 + j] = vals[j]                     # (w . grad u_p) v_p: trial jet 1 + j, coefficient w_j
+                if newton:
+                    b[0][0] = grads[p][q]                         # (u_q d w_p / d x_q) v_p
+                self.patch.set_form_sum_resident(atab[p][q], self.viscosity, b)
+                self.patch.assemble('form', to_host=False)
+                if timed:
+                    asm_ms += self.patch.timing()['total_ms']
+                _lib.check(lib.igx_solver_replace_block(self.handle, p, q), 'igx_solver_replace_block')
+                self.present[p][q] = True
+                count += 1
+        if not newton:                                            # Newton blocks of an earlier step must not enter a Picard matrix
+            for p in range(nc):
+                for q in range(nc):
+                    if p != q and self.present[p][q]:
+                        if atab[p][q] is not None:
+                            self.patch.set_form_sum_resident(atab[p][q], self.viscosity, None)
+                            self.patch.assemble('form', to_host=False)
+                            _lib.check(lib.igx_solver_replace_block(self.handle, p, q), 'igx_solver_replace_block')
+                            count += 1
+                        else:
+                            _lib.check(lib.igx_solver_hide_block(self.handle, p, q, 1), 'igx_solver_hide_block')
+        if timed:
+            self._phases.append(dict(assembly_ms=asm_ms, blocks=count))
+        return count
+
+    def update(self, **inputs):
+        """Replaces the convection blocks of the live system by those of new inputs of the convection form, usually
+        ``update(w=...)``; ``solve()`` afterwards behaves as on a system constructed with them.  ``B``, ``B^T``, the
+        preconditioner factors and every buffer stay (a selected Jacobi preconditioner takes the new diagonals).
+
+        A callable or an array over the Gauss grid goes through the host tables, exactly as the constructor does.  ``w`` given as
+        a full solution vector (or its velocity part) or as a coefficient array of shape ``ndofs + (nc,)`` -- a spline of the
+        velocity space, e.g. the solution of a previous solve -- is evaluated and turned into tables on the device; that needs
+        the default convection form."""
+        from .form_assemblers import FormAssembler
+        self._live()
+        if self.convection is None:
+            raise ValueError('OseenSystem.update: the system was made without a convection form')
+        dofs = self._velocity_dofs(inputs['w']) if set(inputs) == {'w'} else None
+        if dofs is not None:
+            if self.convection != self.WIND_FORM:
+                raise ValueError('OseenSystem.update: a wind given by its dofs needs convection=%r' % (self.WIND_FORM,))
+            if self._d_wind is None:
+                self._d_wind = DeviceArray(self._ctx, self.ncomp * self.N)
+            self._d_wind.upload(dofs)
+            self._wind_blocks(self._d_wind.ptr)
+            return
+        fargs = dict(self._fargs, **inputs)
+        _check_convection(self.convection, self.kvs, self.kvs_p, self.ncomp, fargs)
+        asm = FormAssembler(self.kvs, self._geo, self.convection, bfuns=[('u', self.ncomp), ('v', self.ncomp)], inputs=fargs, patch=self.patch)
+        self._replace_blocks(add_block_tables(self._visc_table, asm._table))
+        self._fargs = fargs
+
+    def _drop_owner(self):
+        if self._d_wind is not None:
+            self._d_wind.free()
+            self._d_wind = None
+        SaddlePointSystem._drop_owner(self)
 
     def set_method(self, method):
         """'gmres' is the only method of an Oseen system."""
@@ -2352,6 +2494,190 @@ class NewtonSystem(PatchSystem):
         A = self.patch.csr('form')
         _lib.check(_lib.load().igx_solver_values_changed(self._live()), 'igx_solver_values_changed')     # (the solver's values are new)
         return A
+
+
+class NavierStokesSystem(OseenSystem):
+    """The stationary Navier-Stokes problem ``nu A u + (u . grad) u + B^T p = f``, ``B u = 0``, ``(u, p) = g`` on the dofs of
+    `bcs`, on one patch, by Picard or Newton steps with the iterate in device memory (the loop of the reference's
+    solve-navier-stokes notebook).
+
+    Everything linear is ``OseenSystem``'s: the spaces `kvs` = ``(kvs_u, kvs_p)``, `a` (times `viscosity`), `b`, `rhs`, `bcs`,
+    GMRES(`restart`) and its preconditioners.  The convection form is fixed -- ``grad(u).dot(w).dot(v) * dx`` with the wind ``w``
+    the iterate, and for Newton its derivative ``grad(w).dot(u).dot(v) * dx`` besides -- and needs as many velocity components as
+    dimensions.  ``B``, ``B^T``, the preconditioner factors and all buffers are made once; per step the wind is evaluated from
+    the iterate by one fused kernel, the coefficient tables are formed on the device, the velocity blocks are assembled and
+    replaced in the live solver, and only the residual norm and the solve statistics come down."""
+    NL_METHODS = ('picard', 'newton')
+    d_x = d_b = None
+
+    def __init__(self, kvs, geo, bcs, rhs=0.0, viscosity=1.0, a='inner(grad(u), grad(v)) * dx', b='div(u) * p * dx', ncomp=None,
+                 restart=40):
+        from .form_assemblers import is_space_pair
+        if is_space_pair(kvs) and (len(kvs[0]) if ncomp is None else int(ncomp)) != len(kvs[0]):
+            raise ValueError('NavierStokesSystem needs as many velocity components as dimensions')
+        OseenSystem.__init__(self, kvs, geo, bcs, rhs=rhs, convection=None, a=a, b=b, ncomp=ncomp, viscosity=viscosity, restart=restart)
+        self.convection = self.WIND_FORM
+        self._stokes_blocks_held = True             # the solver holds the blocks of `viscosity a` alone, as constructed
+
+    def _drop_owner(self):
+        for name in ('d_x', 'd_b'):
+            if getattr(self, name) is not None:
+                getattr(self, name).free()
+                setattr(self, name, None)
+        OseenSystem._drop_owner(self)
+
+    def update(self, newton=False, **inputs):
+        """``OseenSystem.update``; with `newton` (a wind given by its dofs only) every block also gets the Newton term
+        ``grad(w).dot(u).dot(v)``: the matrix of a Newton step at ``w``."""
+        self._stokes_blocks_held = False
+        if not newton:
+            return OseenSystem.update(self, **inputs)
+        self._live()
+        dofs = self._velocity_dofs(inputs['w']) if set(inputs) == {'w'} else None
+        if dofs is None:
+            raise ValueError('NavierStokesSystem.update: the Newton blocks need w given by its dofs')
+        if self._d_wind is None:
+            self._d_wind = DeviceArray(self._ctx, self.ncomp * self.N)
+        self._d_wind.upload(dofs)
+        self._wind_blocks(self._d_wind.ptr, newton=True)
+
+    def _check_solve_args(self, x0, method, picard_steps):
+        if method not in self.NL_METHODS:
+            raise ValueError("unknown method %r: 'picard' or 'newton'" % (method,))
+        if not isinstance(picard_steps, (int, np.integer)) or picard_steps < 0:
+            raise ValueError('picard_steps must be a non-negative integer, not %r' % (picard_steps,))
+        if x0 is None:
+            return None
+        x = np.array(x0, dtype=np.float64).ravel()
+        if x.size != self.n:
+            raise ValueError('x0 has %d entries, the system %d' % (x.size, self.n))
+        return x
+
+    def _restore_stokes_blocks(self):
+        """The blocks of `viscosity a` alone back in the solver (a solve from the Stokes solution after an earlier solve)."""
+        if self._stokes_blocks_held:
+            return
+        lib = _lib.load()
+        atab = self._device_a_tables()
+        for p in range(self.ncomp):
+            for q in range(self.ncomp):
+                if not self.present[p][q]:
+                    continue
+                if atab[p][q] is None:
+                    _lib.check(lib.igx_solver_hide_block(self.handle, p, q, 1), 'igx_solver_hide_block')
+                    continue
+                self.patch.set_form_sum_resident(atab[p][q], self.viscosity, None)
+                self.patch.assemble('form', to_host=False)
+                _lib.check(lib.igx_solver_replace_block(self.handle, p, q), 'igx_solver_replace_block')
+        self._stokes_blocks_held = True
+
+    def _vectors(self, x):
+        if self.d_x is None:
+            self.d_x = DeviceArray(self._ctx, self.n)
+            self.d_b = DeviceArray.from_host(self._ctx, self.b)
+        self.d_x.upload(x)
+
+    def solve(self, x0=None, method='newton', picard_steps=0, atol=1e-8, rtol=1e-8, maxiter=50, lin_tol=1e-10, lin_maxiter=1000,
+              precond='auto', triangular=True, pressure='auto', restart=None, timed=False, callback=None):
+        """Picard (`method` 'picard') or Newton steps ('newton', after `picard_steps` leading Picard steps) from `x0` -- a full
+        vector whose fixed entries are replaced by g; default the Stokes solution, solved to `lin_tol` -- to ``||R F(x)|| <
+        max(atol, rtol ||R F(x0)||)``, tested before every step; returns the full solution vector, ``NoConvergenceError`` (with
+        the last iterate) after `maxiter` steps.  A step: the wind (for Newton with its gradient) from the iterate; the diagonal
+        blocks ``viscosity a + (w . grad)`` assembled and replaced; ``r = R (b - K x)`` and its norm; for Newton all blocks
+        assembled again with ``(u . grad) w`` added; ``x += K^-1 r`` by GMRES from zero to ``lin_tol ||r||``.  Newton therefore
+        assembles the diagonal blocks twice per step: the residual is the Picard matrix's.  `precond`, `triangular`, `pressure`
+        and `restart` as ``OseenSystem.solve``.  `callback(k, x)`: a host copy of the iterate after step k, normalised as the
+        result is (it costs a download per step; without it only scalars come down).
+
+        ``info``: ``iterations`` (steps), ``residual_norms`` (before every step and after the last), ``inner_iterations`` and
+        ``restarts`` per correction solve, ``blocks_assembled``, ``stokes`` (the info of the first solve, or None); with `timed`
+        also ``phases``: the device ms of every wind evaluation, group of assemblies and correction solve, in their order."""
+        x = self._check_solve_args(x0, method, picard_steps)
+        restart = self.restart if restart is None else self._check_restart(restart)
+        if pressure not in self.PRESSURES:
+            raise ValueError("unknown pressure %r: 'auto', 'mean' or None" % (pressure,))
+        if precond != 'auto' and (precond if precond is not None else 'none') not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        h = self._live()
+        lib = _lib.load()
+        nc, nv = self.ncomp, self.ncomp * self.N
+        project = pressure is not None and self.enclosed
+        stokes = None
+        if x is None:
+            self._restore_stokes_blocks()
+            x = OseenSystem.solve(self, tol=lin_tol, maxiter=lin_maxiter, precond=precond, triangular=triangular, pressure=pressure,
+                                  restart=restart)
+            stokes = self.info
+        else:
+            x[self.bc_indices] = self.bc_values
+            _lib.check(lib.igx_solver_saddle_projection(h, 1 if project else 0, None, None), 'igx_solver_saddle_projection')
+            self._select(precond, triangular, restart)
+            self.set_precond(self.default_precond if precond == 'auto' else precond)
+        tri = bool(triangular) and self._precond != 'none'
+        self._vectors(x)
+        self._phases = [] if timed else None
+        self._stokes_blocks_held = False
+        inner, restarts, count = [], [], [0]
+
+        def newton_step():
+            return method == 'newton' and len(inner) >= picard_steps
+
+        def residual_norm():
+            count[0] += self._wind_blocks(self.d_x.ptr, newton=False, want_grad=newton_step())
+            nrm = C.c_double(0.0)
+            _lib.check(lib.igx_solver_saddle_residual_d(h, self.d_b.ptr, self.d_x.ptr, C.byref(nrm)), 'igx_solver_saddle_residual_d')
+            return float(nrm.value)
+
+        def form_jacobian():
+            if newton_step():
+                count[0] += self._wind_blocks(self.d_x.ptr, newton=True, evaluate=False)
+
+        def update():
+            info = _lib.SolveInfo()
+            _lib.check(lib.igx_solver_saddle_correct_d(h, self.d_x.ptr, float(lin_tol), int(lin_maxiter), 1, 1 if timed else 0,
+                                                       C.byref(info)), 'igx_solver_saddle_correct_d')
+            if not info.converged:
+                warnings.warn('NavierStokesSystem: the linear solve stopped after %d iterations at relative residual %.2e'
+                              % (info.iterations, info.relres), RuntimeWarning, stacklevel=3)
+            inner.append(int(info.iterations))
+            restarts.append(int(lib.igx_solver_gmres_restarts(h)))
+            if self._phases is not None:
+                self._phases.append(dict(solve_ms=float(info.total_ms), inner_iterations=int(info.iterations)))
+            if callback is not None:
+                callback(len(inner), normalised(self.d_x.download()))
+            return int(info.iterations)
+
+        def normalised(x):
+            if project:
+                x[nv:] -= x[nv] if pressure == 'auto' else x[nv:].mean()
+            return x
+        try:
+            converged, info = newton_loop(residual_norm, form_jacobian, update, atol, rtol, maxiter, 1)
+        finally:
+            phases, self._phases = self._phases, None
+        del info['jacobians']
+        self.info = dict(info, converged=converged, method=method, picard_steps=int(picard_steps), restarts=restarts,
+                         blocks_assembled=count[0], stokes=stokes, precond=self._precond, triangular=tri, restart=restart)
+        if timed:
+            self.info['phases'] = phases
+        x = normalised(self.d_x.download())
+        if not converged:
+            raise NoConvergenceError(method, maxiter, x)
+        return x
+
+    def residual(self, u):
+        """``R F(u)`` as a host vector (all dofs; zero on the fixed ones), ``F(u) = (viscosity A + N(u)) u + B^T p - f`` and the
+        divergence rows; the fixed entries of `u` are replaced by g."""
+        x = self._check_solve_args(u, 'picard', 0)
+        h = self._live()
+        x[self.bc_indices] = self.bc_values
+        self._vectors(x)
+        self._stokes_blocks_held = False
+        self._wind_blocks(self.d_x.ptr, newton=False)
+        d_y = DeviceArray(self._ctx, self.n)
+        _lib.check(_lib.load().igx_solver_saddle_product_d(h, self.d_x.ptr, self.d_b.ptr, -1.0, None, d_y.ptr, None),
+                   'igx_solver_saddle_product_d')
+        return -d_y.download()
 
 
 ################################################################################
