@@ -449,6 +449,21 @@ int igx_fused_stage_fits(int64_t c0max, int64_t S_mid, int64_t S_last, int64_t G
 int igx_fused_rows_per_tile(int P, int mask, int na);
 int igx_fused_chunk_plan(int npairs, int ntiles, int mid_rows, int64_t slots, int P, int out[5]);
 
+/* Planning queries of a patch, host arithmetic only: nothing is launched (no counterpart in the reference).  Each returns what
+   the launcher itself decides with -- the query and the launch call one function.
+   igx_patch_fields_plan: the kernel that forms the quadrature fields of `kind` from the geometry map.
+     out = { line-wise (1) or point-wise (0), lines per block, bytes of LDS of a block, components of the control net incl. the
+     NURBS weight (0: Jacobian array) }; lines per block and bytes are 0 for the point-wise kernel (Jacobian arrays, span boxes,
+     line coefficients above 64 KiB).  (A form given as expressions has a generated field kernel of its own, not described here.)
+   igx_patch_single2d_plan: the tile of the single-launch 2D mass / stiffness kernel, for the resident rows or (whole_patch != 0)
+     as if the patch were whole.  out = { supported, wanted (the assembly would take this kernel: small patches, or IGX_PATH=single),
+     rows per tile along axis 0, along axis 1, Gauss planes of axis 0 in LDS, window points of axis 1, geometry control columns
+     of axis 1 in LDS, bytes of LDS, blocks of the launch }; everything after `wanted` is 0 where the kernel does not support the
+     patch or no tile fits LDS.
+   IGX_ERR_ARG: null argument, unknown kind. */
+int igx_patch_fields_plan(const igx_patch *patch, int kind, int64_t out[4]);
+int igx_patch_single2d_plan(const igx_patch *patch, int kind, int whole_patch, int64_t out[9]);
+
 /* --- multipatch: sum_p X_p A_p X_p^T on the device (pyiga/assemble.py:1103-1389) -------------------------------------------
    X_p is the 0/1 matrix of the local-to-global map l2g[p] (Multipatch.patch_to_global_idx, pyiga/assemble.py:1276-1293).  The
    handle does NOT own the patches: they are read by the calls that take them and may be destroyed afterwards. */

@@ -200,6 +200,8 @@ SYMBOLS = [
     ('igx_fused_stage_fits', C.c_int, [C.c_int64] * 5),
     ('igx_fused_rows_per_tile', C.c_int, [C.c_int] * 3),
     ('igx_fused_chunk_plan', C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
+    ('igx_patch_fields_plan', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    ('igx_patch_single2d_plan', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     ('igx_assemble_kron3', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _dp, _dp, _dp]),
     ('igx_patch_set_coeff_expr', C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     ('igx_rtc_compile', C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),

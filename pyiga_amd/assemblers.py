@@ -317,6 +317,22 @@ class DevicePatch:
         bits = _lib.load().igx_patch_last_path(self.handle)
         return {name for bit, name in ((1, 'geoA'), (2, 'fused'), (4, 'mirror'), (8, 'single'), (16, 'kron'), (32, 'both'), (64, 'bf3'), (128, 'twin')) if bits & bit}
 
+    def fields_plan(self, kind):
+        """The kernel that forms the quadrature fields of `kind` (igx_patch_fields_plan; nothing is launched):
+        {'lines': line-wise or point-wise, 'lpb': lines per block, 'lds': bytes of LDS, 'nc': control-net components}."""
+        out = (C.c_int64 * 4)()
+        _lib.check(_lib.load().igx_patch_fields_plan(self.handle, _lib.KINDS[kind], out), 'igx_patch_fields_plan')
+        return {'lines': bool(out[0]), 'lpb': int(out[1]), 'lds': int(out[2]), 'nc': int(out[3])}
+
+    def single2d_plan(self, kind, whole_patch=False):
+        """The tile of the single-launch 2D kernel for `kind` (igx_patch_single2d_plan; nothing is launched)."""
+        out = (C.c_int64 * 9)()
+        _lib.check(_lib.load().igx_patch_single2d_plan(self.handle, _lib.KINDS[kind], 1 if whole_patch else 0, out), 'igx_patch_single2d_plan')
+        names = ('supported', 'wanted', 'R0', 'R1', 'NG0', 'WIN', 'NCOL', 'lds', 'blocks')
+        d = {n: int(v) for n, v in zip(names, out)}
+        d['supported'], d['wanted'] = bool(d['supported']), bool(d['wanted'])
+        return d
+
     def placement(self):
         """Outcome of the opt-in buffer placement search (IGX_PLACEMENT_TRIES, include/igx.h igx_patch_placement):
         {'tried': n, 'best_ms': .., 'worst_ms': ..}; tried == 0: the search did not run."""

@@ -202,6 +202,8 @@ static int ensure_fields(igx_patch *pt, int kind)
         pt->fields_cap = need;
     }
     pt->fields_kind = -1;
+    if (pt->knobs.poison)                         // IGX_DEBUG_POISON: every field of every point must be written
+        IGX_HIP(hipMemsetAsync(pt->d_fields, 0xFF, need * sizeof(double), pt->ctx->stream));
     // (a form given as expressions has its own generated field kernel: no coefficient arrays)
     int rc = (kind == IGX_FORM && pt->form_fn) ? launch_form_fields(pt->ctx->stream, pt, pt->form_fn, pt->d_fields)
                                                 : launch_geo_fields(pt->ctx->stream, pt, kind, pt->d_fields);
@@ -250,6 +252,21 @@ int igx_fused_chunk_plan(int npairs, int ntiles, int mid_rows, int64_t slots, in
     if ((long long)npairs * ntiles > 0x7fffffffLL / 16) { set_error("igx_fused_chunk_plan: too many blocks"); return IGX_ERR_ARG; }
     igx::fused2_chunk_plan(npairs, ntiles, mid_rows, slots, P, out);
     return IGX_OK;
+}
+int igx_patch_fields_plan(const igx_patch *pt, int kind, int64_t out[4])
+{
+    if (!pt || !out) { set_error("igx_patch_fields_plan: null argument"); return IGX_ERR_ARG; }
+    if (kind < IGX_MASS || kind > IGX_FORM) { set_error("igx_patch_fields_plan: unknown kind %d", kind); return IGX_ERR_ARG; }
+    const GeoFieldsPlan plan = geo_fields_plan(pt);
+    out[0] = plan.lines ? 1 : 0; out[1] = plan.LPB; out[2] = (int64_t)plan.lds;
+    out[3] = pt->geo_kind == IGX_GEO_JACOBIAN ? 0 : pt->ncomp;
+    return IGX_OK;
+}
+int igx_patch_single2d_plan(const igx_patch *pt, int kind, int whole_patch, int64_t out[9])
+{
+    if (!pt || !out) { set_error("igx_patch_single2d_plan: null argument"); return IGX_ERR_ARG; }
+    if (kind < IGX_MASS || kind > IGX_FORM) { set_error("igx_patch_single2d_plan: unknown kind %d", kind); return IGX_ERR_ARG; }
+    return single2d_plan_query(pt, kind, whole_patch != 0, out);
 }
 const char *igx_last_error(void) { return g_err; }
 

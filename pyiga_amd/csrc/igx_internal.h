@@ -120,7 +120,7 @@ struct igx_knobs {
                                               // measured in round 4: 5.08 against 4.50 ms for the vector form at C4 -- DESIGN.md section 3; off by default)
     int final_sel = 0;                        // IGX_FINAL: 0 default, 1 q, 2 valu, 3 mfma (any choice implies the stage kernels)
     int entries_thread = 0;                   // IGX_ENTRIES=thread: one thread per entry (the reference's summation order)
-    int poison = 0;                           // IGX_DEBUG_POISON: NaN-fill the CSR values before an assembly (tests)
+    int poison = 0;                           // IGX_DEBUG_POISON: NaN-fill the CSR values before an assembly and the fields before a field kernel (tests)
     int bf = 0;                               // IGX_BF=2: symmetric 3D forms through k_bf2 + the mirror pass (the chain of rounds 3-4) instead of k_bf3
     int no_twin = 0;                          // IGX_NO_TWIN: no twin patch (repeated knots on the last axis: the stage kernels, as before round 6)
     int no_diag_skip = 0;                     // IGX_NO_DIAG_SKIP: k_geoA writes and k_bf3 reads the K1 slices that diagonal outer pairs duplicate (A/B runs)
@@ -253,8 +253,14 @@ int launch_basis_tables(hipStream_t st, const double *d_kv, int nk, int p, const
                         long long *d_spans /* or null */, int o0 = 0, int o1 = 1 /* derivative orders of the two V slots */);
 int launch_pi_tables(hipStream_t st, const double *d_V, int G, int P, double *d_PI);
 int launch_geo_fields(hipStream_t st, const igx_patch *pt, int kind, double *d_fields);
+// which field kernel launch_geo_fields runs: line-wise (LPB lines per block, `lds` bytes of line coefficients) or point-wise.
+// One function for the launch and for igx_patch_fields_plan.
+struct GeoFieldsPlan { bool lines; int LPB; size_t lds; };
+GeoFieldsPlan geo_fields_plan(const igx_patch *pt);
 // 2D mass / stiffness in one launch, no intermediates (kern_basis.hip)
 bool single2d_supported(const igx_patch *pt, int kind);
+bool single2d_wanted(const igx_patch *pt, int kind);                 // the plan's choice (sumfact.hip)
+int single2d_plan_query(const igx_patch *pt, int kind, bool whole_patch, int64_t out[9]);   // igx_patch_single2d_plan
 long long single2d_blocks(const igx_patch *pt, int kind, int *tile_rows, bool whole_patch);   // launch grid of the single-launch kernel (-1: no tile fits), rows per tile; for the resident rows or as if the patch were whole
 int launch_single2d(hipStream_t st, igx_patch *pt, int kind, double *d_data);
 int launch_grid_geo(hipStream_t st, int dim, int ncomp_total, bool nurbs, const GeoAxis gax[3],

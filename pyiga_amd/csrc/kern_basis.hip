@@ -192,8 +192,9 @@ int launch_coeff_affine(hipStream_t st, const igx_patch *pt, const double c[4], 
     const int G1 = pd.L1, G2 = dim == 3 ? pd.L2 : 1;
     dim3 grid((unsigned)((total + 127) / 128)), block(128);
     const bool nurbs = pt->geo_kind == IGX_GEO_NURBS;
-    if (dim == 2) k_coeff_affine<2><<<grid, block, 0, st>>>(gv, nurbs, pd.g0_lo, pd.G0_loc, G1, G2, pd.b1, pd.b2, c[0], c[1], c[2], c[3], d_coeff);
-    else k_coeff_affine<3><<<grid, block, 0, st>>>(gv, nurbs, pd.g0_lo, pd.G0_loc, G1, G2, pd.b1, pd.b2, c[0], c[1], c[2], c[3], d_coeff);
+    // (3D only: the coefficient belongs to the convection-diffusion form, and igx_patch_set_coeff_affine refuses 2D patches)
+    if (dim != 3) { set_error("an affine coefficient belongs to the 3D convection-diffusion form"); return IGX_ERR_UNSUPPORTED; }
+    k_coeff_affine<3><<<grid, block, 0, st>>>(gv, nurbs, pd.g0_lo, pd.G0_loc, G1, G2, pd.b1, pd.b2, c[0], c[1], c[2], c[3], d_coeff);
     IGX_HIP(hipGetLastError());
     return IGX_OK;
 }
@@ -329,6 +330,25 @@ __global__ void __launch_bounds__(256) k_geo_fields_lines(GeoView gv, bool nurbs
     }
 }
 
+GeoFieldsPlan geo_fields_plan(const igx_patch *pt)
+{
+    const int dim = pt->dim;
+    GeoFieldsPlan plan{false, 0, 0};
+    if (pt->geo_kind != IGX_GEO_JACOBIAN && !pt->boxed) {      // (a boxed patch is small: the point-wise kernel)
+        const int LN = (dim == 3) ? pt->dev.L2 : pt->dev.L1;
+        if (LN <= 0) return plan;
+        // lines per block: a whole number of 256-thread passes over the block's points where a few lines give one
+        // (576-point lines: 4 lines = 9 passes; one line would leave the third pass a quarter full)
+        int LPB = std::max(1, 256 / LN);
+        if (LN > 256)
+            for (int l = 1; l <= 8; ++l)
+                if ((l * LN) % 256 == 0) { LPB = l; break; }
+        const size_t lds = (size_t)LPB * pt->gax[dim - 1].N * pt->ncomp * dim * sizeof(double);
+        if (lds <= 64 * 1024) { plan.lines = true; plan.LPB = LPB; plan.lds = lds; }
+    }
+    return plan;
+}
+
 int launch_geo_fields(hipStream_t st, const igx_patch *pt, int kind, double *d_fields)
 {
     const int dim = pt->dim;
@@ -340,28 +360,21 @@ int launch_geo_fields(hipStream_t st, const igx_patch *pt, int kind, double *d_f
     fv.c = pt->d_formc;
     for (int k = 0; k < 16; ++k) fv.slot[k] = pt->form_slot[k];
     const int G1 = pd.L1, G2 = (dim == 3) ? pd.L2 : 1;
-    if (pt->geo_kind != IGX_GEO_JACOBIAN && !pt->boxed) {      // (a boxed patch is small: the point-wise kernel)
-        const int LN = (dim == 3) ? G2 : G1;
-        // lines per block: a whole number of 256-thread passes over the block's points where a few lines give one
-        // (576-point lines: 4 lines = 9 passes; one line would leave the third pass a quarter full)
-        int LPB = std::max(1, 256 / LN);
-        if (LN > 256)
-            for (int l = 1; l <= 8; ++l)
-                if ((l * LN) % 256 == 0) { LPB = l; break; }
-        const size_t lds = (size_t)LPB * pt->gax[dim - 1].N * pt->ncomp * dim * sizeof(double);
-        if (lds <= 64 * 1024) {
-            const long long nlines = total / LN;
-            dim3 grid((unsigned)((nlines + LPB - 1) / LPB)), block(256);
-            const bool nurbs = pt->geo_kind == IGX_GEO_NURBS;
+    const GeoFieldsPlan plan = geo_fields_plan(pt);
+    if (plan.lines) {
+        const int LN = (dim == 3) ? G2 : G1, LPB = plan.LPB;
+        const size_t lds = plan.lds;
+        const long long nlines = total / LN;
+        dim3 grid((unsigned)((nlines + LPB - 1) / LPB)), block(256);
+        const bool nurbs = pt->geo_kind == IGX_GEO_NURBS;
 #define LAUNCH_LINES(D_, NC_) do { \
-                if (kind == IGX_FORM) k_geo_fields_lines<D_, NC_, true><<<grid, block, lds, st>>>(gv, nurbs, kind, pt->d_coeff, fv, pd, pd.ax[0].w, pd.ax[1].w, D_ == 3 ? pd.ax[2].w : nullptr, pd.g0_lo, pd.G0_loc, G1, G2, LPB, d_fields); \
-                else k_geo_fields_lines<D_, NC_, false><<<grid, block, lds, st>>>(gv, nurbs, kind, pt->d_coeff, fv, pd, pd.ax[0].w, pd.ax[1].w, D_ == 3 ? pd.ax[2].w : nullptr, pd.g0_lo, pd.G0_loc, G1, G2, LPB, d_fields); } while (0)
-            if (dim == 2) { if (nurbs) LAUNCH_LINES(2, 3); else LAUNCH_LINES(2, 2); }
-            else { if (nurbs) LAUNCH_LINES(3, 4); else LAUNCH_LINES(3, 3); }
+            if (kind == IGX_FORM) k_geo_fields_lines<D_, NC_, true><<<grid, block, lds, st>>>(gv, nurbs, kind, pt->d_coeff, fv, pd, pd.ax[0].w, pd.ax[1].w, D_ == 3 ? pd.ax[2].w : nullptr, pd.g0_lo, pd.G0_loc, G1, G2, LPB, d_fields); \
+            else k_geo_fields_lines<D_, NC_, false><<<grid, block, lds, st>>>(gv, nurbs, kind, pt->d_coeff, fv, pd, pd.ax[0].w, pd.ax[1].w, D_ == 3 ? pd.ax[2].w : nullptr, pd.g0_lo, pd.G0_loc, G1, G2, LPB, d_fields); } while (0)
+        if (dim == 2) { if (nurbs) LAUNCH_LINES(2, 3); else LAUNCH_LINES(2, 2); }
+        else { if (nurbs) LAUNCH_LINES(3, 4); else LAUNCH_LINES(3, 3); }
 #undef LAUNCH_LINES
-            IGX_HIP(hipGetLastError());
-            return IGX_OK;
-        }
+        IGX_HIP(hipGetLastError());
+        return IGX_OK;
     }
     dim3 grid((unsigned)((total + 127) / 128)), block(128);
 #define LAUNCH_PTS(D_, F_) k_geo_fields<D_, F_><<<grid, block, 0, st>>>(gv, pt->geo_kind, pt->d_jac, pt->d_coeff, fv, pd, kind, pd.ax[0].w, pd.ax[1].w, \
@@ -621,6 +634,22 @@ long long single2d_blocks(const igx_patch *pt, int kind, int *tile_rows, bool wh
     if (tile_rows) *tile_rows = A.R0 * A.R1;
     const long long nr0 = whole_patch ? pt->ax[0].N : std::max(pt->r0_hi - pt->r0_lo, 0);
     return ((pt->ax[1].N + A.R1 - 1) / A.R1) * ((nr0 + A.R0 - 1) / A.R0);
+}
+
+// igx_patch_single2d_plan: { supported, wanted, R0, R1, NG0, WIN, NCOL, LDS bytes, blocks } of the tile launch_single2d
+// takes (single2d_plan, the function the launch calls); R0 .. blocks are 0 where unsupported or where no tile fits.
+int single2d_plan_query(const igx_patch *pt, int kind, bool whole_patch, int64_t out[9])
+{
+    for (int k = 0; k < 9; ++k) out[k] = 0;
+    if (!single2d_supported(pt, kind)) return IGX_OK;
+    out[0] = 1;
+    out[1] = single2d_wanted(pt, kind) ? 1 : 0;
+    Single2DArgs A{};
+    size_t bytes = 0;
+    if (!single2d_plan(pt, kind, A, bytes, whole_patch)) return IGX_OK;
+    out[2] = A.R0; out[3] = A.R1; out[4] = A.NG0; out[5] = A.WIN; out[6] = A.NCOL; out[7] = (int64_t)bytes;
+    out[8] = single2d_blocks(pt, kind, nullptr, whole_patch);
+    return IGX_OK;
 }
 
 int launch_single2d(hipStream_t st, igx_patch *pt, int kind, double *d_data)

@@ -811,7 +811,7 @@ static bool geoA_wanted(const igx_patch *pt, int kind, int nslots)
 // the chain -- profiles/r03_single2d.txt)
 constexpr long long SINGLE2D_MAX_BLOCKS = 256;
 constexpr int SINGLE2D_MAX_TILE = 36;
-static bool single2d_wanted(const igx_patch *pt, int kind)
+bool single2d_wanted(const igx_patch *pt, int kind)
 {
     // 2D: the single-launch kernel where the stage kernels are launch-bound (small patches), or on request (IGX_PATH=single)
     if (pt->knobs.final_sel || !single2d_supported(pt, kind)) return false;

@@ -1,7 +1,8 @@
 """Long-double restatement of one matrix entry of the entry-wise kernels (pyiga_amd/csrc/kern_entries.hip), plain numpy: no GPU,
 no library load.
 
-The entry kernels are isolated by taking their two inputs as given (both are tested elsewhere):
+The entry kernels are isolated by taking their two inputs as given (both are tested elsewhere: the fields in
+tests/test_fields_kernels_gpu.py, the basis tables in tests/test_entries_kernels_gpu.py):
 
 - ``fields``: the quadrature fields of the patch, shape (F, G0_loc, L1[, L2]) over the resident window (``DevicePatch.fields``;
   on the host, the oracle's fields brought into the same layout),
@@ -275,19 +276,19 @@ def findspan(kv, p, u):
     return a
 
 
-def active_deriv_single_ld(kv, p, u, numderiv):
-    kv = np.asarray(kv, dtype=np.float64).astype(LD)
-    u = LD(u)
-    NDU = np.zeros((p + 1, p + 1), dtype=LD)
-    result = np.zeros((numderiv + 1, p + 1), dtype=LD)
-    left = np.zeros(p + 1, dtype=LD)
-    right = np.zeros(p + 1, dtype=LD)
+def active_deriv_single_ld(kv, p, u, numderiv, dtype=LD):
+    kv = np.asarray(kv, dtype=np.float64).astype(dtype)
+    u = dtype(u)
+    NDU = np.zeros((p + 1, p + 1), dtype=dtype)
+    result = np.zeros((numderiv + 1, p + 1), dtype=dtype)
+    left = np.zeros(p + 1, dtype=dtype)
+    right = np.zeros(p + 1, dtype=dtype)
     span = findspan(kv, p, u)
     NDU[0, 0] = 1
     for j in range(1, p + 1):
         left[j - 1] = u - kv[span + 1 - j]
         right[j - 1] = kv[span + j] - u
-        saved = LD(0)
+        saved = dtype(0)
         for r in range(j):
             NDU[j, r] = right[r] + left[j - r - 1]
             temp = NDU[r, j - 1] / NDU[j, r]
@@ -295,14 +296,14 @@ def active_deriv_single_ld(kv, p, u, numderiv):
             saved = left[j - r - 1] * temp
         NDU[j, j] = saved
     result[0] = NDU[:, p]
-    a1 = np.zeros(p + 2, dtype=LD)
-    a2 = np.zeros(p + 2, dtype=LD)
+    a1 = np.zeros(p + 2, dtype=dtype)
+    a2 = np.zeros(p + 2, dtype=dtype)
     for r in range(p + 1):
         a1[0] = 1
         fac = p
         for k in range(1, numderiv + 1):
             rk, pk = r - k, p - k
-            d = LD(0)
+            d = dtype(0)
             if pk < 0:
                 result[k, r] = 0
                 continue
@@ -323,12 +324,12 @@ def active_deriv_single_ld(kv, p, u, numderiv):
     return result
 
 
-def active_deriv_ld(kv, u, numderiv):
-    """(numderiv + 1, p + 1, len(u)) long double."""
+def active_deriv_ld(kv, u, numderiv, dtype=LD):
+    """(numderiv + 1, p + 1, len(u)) long double (or the same arithmetic in `dtype`)."""
     u = np.asarray(u, dtype=np.float64)
-    out = np.zeros((numderiv + 1, int(kv.p) + 1, u.shape[0]), dtype=LD)
+    out = np.zeros((numderiv + 1, int(kv.p) + 1, u.shape[0]), dtype=dtype)
     for i in range(u.shape[0]):
-        out[:, :, i] = active_deriv_single_ld(kv.kv, int(kv.p), u[i], numderiv)
+        out[:, :, i] = active_deriv_single_ld(kv.kv, int(kv.p), u[i], numderiv, dtype)
     return out
 
 

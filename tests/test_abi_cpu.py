@@ -170,6 +170,25 @@ def test_fused_stage_offset_guard(lib):
     assert fits(9, 1 << 40, 1 << 40, 1, 1) == 0    # no overflow of the products
 
 
+def test_patch_plan_queries_are_bound_and_reject_null(lib):
+    """igx_patch_fields_plan / igx_patch_single2d_plan (host arithmetic on a patch; tests/test_fields_kernels_gpu.py compares
+    them with the restated launchers): declared, bound with 64-bit outputs, exported, and a null patch or output is an
+    argument error, not a crash.  DevicePatch has a thin method for each."""
+    cdll = lib.load()
+    hdr = open(os.path.join(ROOT, 'include', 'igx.h')).read()
+    assert 'int igx_patch_fields_plan(const igx_patch *patch, int kind, int64_t out[4]);' in hdr
+    assert 'int igx_patch_single2d_plan(const igx_patch *patch, int kind, int whole_patch, int64_t out[9]);' in hdr
+    sym = {name: (res, args) for name, res, args in lib.SYMBOLS}
+    assert sym['igx_patch_fields_plan'] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)])
+    assert sym['igx_patch_single2d_plan'] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)])
+    out4, out9 = (ctypes.c_int64 * 4)(), (ctypes.c_int64 * 9)()
+    IGX_ERR_ARG = int(re.search(r'IGX_ERR_ARG = (\d+),', hdr).group(1))
+    assert cdll.igx_patch_fields_plan(None, lib.IGX_MASS, out4) == IGX_ERR_ARG and b'igx_patch_fields_plan' in cdll.igx_last_error()
+    assert cdll.igx_patch_single2d_plan(None, lib.IGX_MASS, 0, out9) == IGX_ERR_ARG and b'igx_patch_single2d_plan' in cdll.igx_last_error()
+    from pyiga_amd import assemblers
+    assert callable(assemblers.DevicePatch.fields_plan) and callable(assemblers.DevicePatch.single2d_plan)
+
+
 def test_rtc_compile_and_cache(lib, tmp_path, monkeypatch):
     """Run-time compiled coefficient kernels (SURVEY 8 f1 "full": an emitter + an on-disk code-object cache keyed by the
     source hash, the analogue of pyiga/compile.py:58-73,120-132): hiprtc cross-compiles without a GPU.  First call compiles
