@@ -1099,6 +1099,44 @@ int  igx_solver_saddle_residual_d(igx_solver *solver, const double *d_b, const d
 int  igx_solver_saddle_correct_d(igx_solver *solver, double *d_x, double tol, int maxiter, int check_every, int timed,
                                  igx_solve_info *info);
 
+/* --- Hierarchical (HB / THB) spline spaces: the level-coupling contraction (pyiga_amd/hierarchical.py).
+   The entry of the HB matrix between the active function a of level la and the active function b of level k >= la is
+       A[a, b] = sum_i W[i, a] A_k[i, b],      A[b, a] = sum_i A_k[b, i] W[i, a],
+   A_k the tensor-product matrix of level k, W = (x)_axes of the composite two-scale matrices from level la to level k, i over
+   the children of a on level k whose support overlaps that of b.  One block = the work items of one pair of levels.
+   Per axis: d_clo / d_ccnt / d_w[n_coarse][wmax] -- first child, number of children and weights of every coarse function
+   (la == k: clo[a] = a, one child, weight 1); d_first / d_cnt -- per function of level k the first overlapping function of level
+   k and their number; box_lo / box_n -- the range of dof indices the row-slot map covers.
+   d_slot[prod box_n]: the slot of a row of level k, -1 without; the entries of row slot s start at d_rowptr[s] and hold its
+   tensor-product stencil, columns d_first .. + d_cnt per axis, last axis fastest: the order igx_entries_d fills them in.
+   Work item n: d_ia[n], d_ib[n] the ravelled indices of a and b on their levels, d_pos[n] the position of A[a, b] and
+   d_pos2[n] (-1: none) the position of A[b, a] in d_values.  symmetric != 0: A[b, a] is a copy of A[a, b]; else it is summed
+   in the other orientation.  `group` lanes (16 or 64) sum the terms of one item in a fixed order: no atomics, the values are
+   the same bits in every run and for every grid.  max_blocks > 0 caps the grid (0: the library's default).  A term that would
+   read outside the slot map or the entries yields NaN; a position outside [0, nnz) is not written. */
+typedef struct {
+    const int32_t *d_clo, *d_ccnt;
+    const double  *d_w;
+    const int32_t *d_first, *d_cnt;
+    int32_t wmax, n_coarse, n_fine, box_lo, box_n, reserved;
+} igx_hier_axis;
+typedef struct {
+    int32_t dim, symmetric;
+    igx_hier_axis ax[IGX_MAX_DIM];
+    const int32_t *d_slot;
+    const int64_t *d_rowptr;
+    const double  *d_entries;
+    int64_t n_entries;
+    const int32_t *d_ia, *d_ib, *d_pos, *d_pos2;
+    int64_t n_items;
+    int32_t group, max_blocks;
+} igx_hier_block;
+/* *ms (may be NULL): the device time of the kernel from events; the call then waits for it. */
+int  igx_hier_contract_d(igx_ctx *ctx, const igx_hier_block *block, double *d_values, int64_t nnz, float *ms);
+/* d_dst[n] = d_src[d_idx[n]], n < n_idx: the active entries of a level's vector in canonical order (an index outside
+   [0, n_src) yields NaN). */
+int  igx_hier_gather_d(igx_ctx *ctx, const double *d_src, int64_t n_src, const int64_t *d_idx, int64_t n_idx, double *d_dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,3 +41,4 @@ from . import approx          # noqa: F401
 from . import multipatch      # noqa: F401
 from . import operators       # noqa: F401
 from . import solvers         # noqa: F401
+from . import hierarchical    # noqa: F401

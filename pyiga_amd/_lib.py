@@ -155,6 +155,23 @@ class EigInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
 
+class HierAxis(C.Structure):
+    _fields_ = [
+        ('d_clo', C.c_void_p), ('d_ccnt', C.c_void_p), ('d_w', C.c_void_p), ('d_first', C.c_void_p), ('d_cnt', C.c_void_p),
+        ('wmax', C.c_int32), ('n_coarse', C.c_int32), ('n_fine', C.c_int32), ('box_lo', C.c_int32), ('box_n', C.c_int32),
+        ('reserved', C.c_int32),
+    ]
+
+
+class HierBlock(C.Structure):
+    _fields_ = [
+        ('dim', C.c_int32), ('symmetric', C.c_int32), ('ax', HierAxis * 3),
+        ('d_slot', C.c_void_p), ('d_rowptr', C.c_void_p), ('d_entries', C.c_void_p), ('n_entries', C.c_int64),
+        ('d_ia', C.c_void_p), ('d_ib', C.c_void_p), ('d_pos', C.c_void_p), ('d_pos2', C.c_void_p), ('n_items', C.c_int64),
+        ('group', C.c_int32), ('max_blocks', C.c_int32),
+    ]
+
+
 class KronDesc(C.Structure):
     _fields_ = [
         ('dim', C.c_int32), ('m', C.c_int32 * 3), ('n', C.c_int32 * 3), ('d_B', C.c_void_p * 3),
@@ -224,6 +241,8 @@ SYMBOLS = [
     ('igx_rtc_compile_exprs_inputs', C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     ('igx_load_vector_jet_d', C.c_int, [C.c_void_p, C.c_void_p * 4, C.c_void_p]),
     ('igx_patch_gauss_slab', C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ('igx_hier_contract_d', C.c_int, [C.c_void_p, C.POINTER(HierBlock), C.c_void_p, C.c_int64, C.POINTER(C.c_float)]),
+    ('igx_hier_gather_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     ('igx_dev_alloc', C.c_void_p, [C.c_void_p, C.c_size_t]),
     ('igx_dev_free', None, [C.c_void_p, C.c_void_p]),
     ('igx_dev_upload', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -44,12 +44,29 @@ def project_L2(kvs, f, f_physical=False, geo=None):
     load vector is multiplied by ``(x) M_k^-1`` with the device Kronecker apply (trailing value axes of a vector-valued `f`
     allowed).  With `geo` the mass matrix is assembled and solved on the device by CG with the Kronecker product of the 1D
     inverse mass matrices as preconditioner (relative tolerance 1e-12, at most 100 iterations, as the reference).
-    Hierarchical spaces are not supported.
+    A hierarchical space (``hierarchical.HSpace``) as `kvs`: the mass matrix and the load vector are assembled on the device
+    (``HDiscretization``) and the system is solved on the host; the result is the coefficient vector in canonical order.
     """
     import sys
     import scipy.linalg
-    from . import _lib, assemble
+    from . import _lib, assemble, hierarchical
     from .solvers import KronDiagOperator, PatchSystem
+    if isinstance(kvs, hierarchical.HSpace):
+        from . import geometry
+        hs = kvs
+        if f_physical:
+            assert geo is not None, 'Cannot use physical coordinates without geometry'
+        g = geo if geo is not None else geometry.unit_cube(hs.dim)
+        # (a function in parametric coordinates is composed with nothing: without geometry the two coordinates coincide)
+        if geo is not None and not f_physical:
+            raise NotImplementedError('project_L2 into a hierarchical space: f in parametric coordinates together with a geometry')
+        disc = hierarchical.HDiscretization(hs, 'u*v*dx', {'geo': g, 'f': f})
+        try:
+            M = disc.assemble_matrix()
+            rhs = disc.assemble_rhs()
+        finally:
+            disc.close()
+        return scipy.sparse.linalg.spsolve(M.tocsc(), rhs)
     if isinstance(kvs, bspline.KnotVector):
         kvs = (kvs,)
     if not isinstance(kvs, (tuple, list)):
