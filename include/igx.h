@@ -1137,6 +1137,81 @@ int  igx_hier_contract_d(igx_ctx *ctx, const igx_hier_block *block, double *d_va
    [0, n_src) yields NaN). */
 int  igx_hier_gather_d(igx_ctx *ctx, const double *d_src, int64_t n_src, const int64_t *d_idx, int64_t n_idx, double *d_dst);
 
+/* --- Local multigrid for hierarchical spline spaces (pyiga/solvers.py:174-324: local_mg_step,
+   iterative_solve, solve_hmultigrid).  All CSR matrices have int32 pointers and columns.
+   igx_csr_rap_d: the values of C = P^T A P on the given pattern of C (n_c x n_c), everything on the device.  A is n_f x n_f and
+   need not be symmetric; the columns of each of its rows ascend (an entry the bisection does not find is no term).  P is given
+   by its transpose alone, P^T (n_c x n_f, rows in any order): column j of P is row j of P^T.  pt_row_max: the longest row of
+   P^T (it selects the lane group: 4, 16 or 64 lanes own one output entry).  Term t = a |row j| + b of C[i, j] is
+   (P^T[i, k_a] A[k_a, m_b]) P^T[j, m_b], a and b the positions in the rows i and j of P^T; lane l of the group adds the terms
+   l, l + G, .. in ascending order and a shuffle tree of fixed shape adds the lanes: no atomics, the same bits in every run and for
+   every grid.  max_blocks > 0 caps the grid (0: the library's default).  A position of the pattern without terms is written as
+   exactly 0.0; an index outside its array makes the entry NaN instead of a read.  Not waited for. */
+int  igx_csr_rap_d(igx_ctx *ctx, int64_t n_f, int64_t n_c, const int32_t *d_a_indptr, const int32_t *d_a_indices, const double *d_a_vals,
+                   int64_t a_nnz, const int32_t *d_pt_indptr, const int32_t *d_pt_indices, const double *d_pt_vals, int64_t pt_nnz,
+                   int32_t pt_row_max, const int32_t *d_c_indptr, const int32_t *d_c_indices, double *d_c_vals, int64_t c_nnz,
+                   int32_t max_blocks);
+/* d_y = M d_x (accumulate == 0) or d_y += M d_x for a rectangular CSR matrix (nrows x ncols) on the device: a group of lanes per
+   row (its width from row_max, the longest row, as the CSR SpMV of the solvers chooses it), fixed summation order.  A column
+   outside [0, ncols) or a row range outside [0, nnz] makes the row NaN instead of a read.  Not waited for. */
+int  igx_csr_rect_spmv_d(igx_ctx *ctx, int64_t nrows, int64_t ncols, const int32_t *d_indptr, const int32_t *d_indices, const double *d_vals,
+                         int64_t nnz, int32_t row_max, const double *d_x, double *d_y, int accumulate, int32_t max_blocks);
+
+/* The handle that owns a hierarchy: level 0 the coarsest, nlevels - 1 the finest.  Set-up order: igx_hmg_set_matrix for every
+   level (the finest with its values), igx_hmg_set_transfer for the levels > 0, igx_hmg_galerkin from the finest level down,
+   igx_hmg_set_smoother for the levels > 0, igx_hmg_set_inverse, igx_hmg_set_free. */
+typedef struct igx_hmg igx_hmg;
+#define IGX_HMG_MAX_LEVELS 16
+enum { IGX_HMG_GS = 0,            /* forward sweeps before the coarse correction, backward sweeps after it */
+       IGX_HMG_FORWARD_GS = 1, IGX_HMG_BACKWARD_GS = 2,
+       IGX_HMG_SYMMETRIC_GS = 3 };/* a forward and a backward sweep per step, before and after */
+enum { IGX_HMG_ITERATE = 0,       /* x <- cycle(x) until the residual over the free dofs has dropped by tol */
+       IGX_HMG_CG = 1 };          /* CG on the free dofs with one cycle from a zero guess as preconditioner (gs, symmetric_gs) */
+typedef struct {
+    int32_t iterations;           /* cycles (iterate) or CG steps done */
+    int32_t converged;            /* 1 if ratio < tol was reached */
+    double ratio;                 /* final ||(f - A x)[free]|| / ||f[free]|| (CG: of the recurrence residual) */
+    int64_t n_free;
+} igx_hmg_info;
+typedef struct {
+    int32_t levels, launches;     /* kernel launches of one cycle */
+    float total_ms, coarse_ms;    /* device time of one cycle (mean over reps) and of the dense solve of level 0 */
+    float smooth_ms[IGX_HMG_MAX_LEVELS], residual_ms[IGX_HMG_MAX_LEVELS], transfer_ms[IGX_HMG_MAX_LEVELS];   /* per level */
+} igx_hmg_profile;
+typedef struct {
+    int64_t nrows, nnz, nsmooth;  /* nsmooth: rows of the smoothing set (level 0: of the dense inverse) */
+    int32_t ncolours, one_block, group_width, reserved;
+} igx_hmg_level;
+int  igx_hmg_create(igx_ctx *ctx, int nlevels, igx_hmg **out);
+void igx_hmg_destroy(igx_hmg *h);
+/* The pattern of level `level` (host arrays; columns ascending within a row) and its values: d_vals (device, nnz doubles, copied)
+   or NULL for a level whose values igx_hmg_galerkin computes. */
+int  igx_hmg_set_matrix(igx_hmg *h, int level, int64_t n, const int32_t *indptr, const int32_t *indices, const double *d_vals);
+/* The prolongation P of level `level` > 0 from level - 1 (host CSR, n_level x n_c); P^T is formed on the host. */
+int  igx_hmg_set_transfer(igx_hmg *h, int level, int64_t n_c, const int32_t *indptr, const int32_t *indices, const double *vals);
+/* A_{level-1} = P^T A_level P by igx_csr_rap_d's kernel on the pattern level - 1 was given. */
+int  igx_hmg_galerkin(igx_hmg *h, int level, int32_t max_blocks);
+/* The smoothing set of level `level` > 0: rows sorted by (colour, index), colour c = rows[colour_offsets[c] ..
+   colour_offsets[c + 1]).  Two coupled rows of one colour are IGX_ERR_ARG.  A set of at most block_rows rows sweeps in one
+   launch of one block, a larger one with one launch per colour. */
+int  igx_hmg_set_smoother(igx_hmg *h, int level, int32_t ncolours, const int32_t *colour_offsets, const int32_t *rows, int64_t block_rows);
+/* Level 0: x[ind[i]] = sum_j inv[i][j] f[ind[j]], inv the m x m row-major inverse of A_0[ind, ind] (host arrays). */
+int  igx_hmg_set_inverse(igx_hmg *h, const int32_t *ind, int64_t m, const double *inv);
+int  igx_hmg_set_options(igx_hmg *h, int smoother, int smooth_steps);
+/* free_mask[i] != 0: dof i of the finest level counts in the residual norm (the non-Dirichlet dofs). */
+int  igx_hmg_set_free(igx_hmg *h, const uint8_t *free_mask);
+int  igx_hmg_level_values(igx_hmg *h, int level, double *out);        /* the values of a level's matrix, to the host */
+int  igx_hmg_level_info(igx_hmg *h, int level, igx_hmg_level *out);
+/* d_y = [d_b +] sign A d_x with the matrix of the finest level (d_b may be NULL, or d_y); not waited for. */
+int  igx_hmg_spmv_d(igx_hmg *h, const double *d_x, const double *d_b, double sign, double *d_y);
+/* d_x <- one cycle with the right-hand side d_f (the reference's step(x)); one stream, no host round trip; not waited for. */
+int  igx_hmg_cycle_d(igx_hmg *h, const double *d_f, double *d_x);
+/* Solves A x = f from x = 0 (device vectors of the finest level).  IGX_HMG_CG with a smoother other than gs / symmetric_gs:
+   IGX_ERR_UNSUPPORTED. */
+int  igx_hmg_solve_d(igx_hmg *h, int method, const double *d_f, double *d_x, double tol, int maxiter, igx_hmg_info *info);
+/* `reps` cycles on d_x with events after every phase. */
+int  igx_hmg_profile_d(igx_hmg *h, const double *d_f, double *d_x, int reps, igx_hmg_profile *out);
+
 #ifdef __cplusplus
 }
 #endif

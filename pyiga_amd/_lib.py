@@ -172,6 +172,33 @@ class HierBlock(C.Structure):
     ]
 
 
+IGX_HMG_MAX_LEVELS = 16
+HMG_SMOOTHERS = {'gs': 0, 'forward_gs': 1, 'backward_gs': 2, 'symmetric_gs': 3}
+HMG_METHODS = {'iterate': 0, 'cg': 1}
+
+
+class HmgInfo(C.Structure):
+    _fields_ = [('iterations', C.c_int32), ('converged', C.c_int32), ('ratio', C.c_double), ('n_free', C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HmgProfile(C.Structure):
+    _fields_ = [
+        ('levels', C.c_int32), ('launches', C.c_int32), ('total_ms', C.c_float), ('coarse_ms', C.c_float),
+        ('smooth_ms', C.c_float * IGX_HMG_MAX_LEVELS), ('residual_ms', C.c_float * IGX_HMG_MAX_LEVELS),
+        ('transfer_ms', C.c_float * IGX_HMG_MAX_LEVELS),
+    ]
+
+
+class HmgLevel(C.Structure):
+    _fields_ = [
+        ('nrows', C.c_int64), ('nnz', C.c_int64), ('nsmooth', C.c_int64), ('ncolours', C.c_int32), ('one_block', C.c_int32),
+        ('group_width', C.c_int32), ('reserved', C.c_int32),
+    ]
+
+
 class KronDesc(C.Structure):
     _fields_ = [
         ('dim', C.c_int32), ('m', C.c_int32 * 3), ('n', C.c_int32 * 3), ('d_B', C.c_void_p * 3),
@@ -351,6 +378,25 @@ SYMBOLS = [
     ('igx_solver_hide_block', C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ('igx_solver_saddle_residual_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
     ('igx_solver_saddle_correct_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(SolveInfo)]),
+    ('igx_csr_rap_d', C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    ('igx_csr_rect_spmv_d', C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int32]),
+    ('igx_hmg_create', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ('igx_hmg_destroy', None, [C.c_void_p]),
+    ('igx_hmg_set_matrix', C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    ('igx_hmg_set_transfer', C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
+    ('igx_hmg_galerkin', C.c_int, [C.c_void_p, C.c_int, C.c_int32]),
+    ('igx_hmg_set_smoother', C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
+    ('igx_hmg_set_inverse', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64, _dp]),
+    ('igx_hmg_set_options', C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ('igx_hmg_set_free', C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
+    ('igx_hmg_level_values', C.c_int, [C.c_void_p, C.c_int, _dp]),
+    ('igx_hmg_level_info', C.c_int, [C.c_void_p, C.c_int, C.POINTER(HmgLevel)]),
+    ('igx_hmg_spmv_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    ('igx_hmg_cycle_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('igx_hmg_solve_d', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(HmgInfo)]),
+    ('igx_hmg_profile_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(HmgProfile)]),
 ]
 
 _lib = None

@@ -31,5 +31,14 @@ int solver_residual(hipStream_t st, const igx_solver *s, const double *x, const 
 void mg_free(igx_solver *s);                  // the levels' device memory and the links to the neighbouring levels
 int mg_check(const igx_solver *s, const char *what);               // the hierarchy below s is complete and every level's sums are current
 int mg_apply(hipStream_t st, igx_solver *s, const double *r, double *z);   // z = one V-cycle on r (r zero on the fixed dofs)
+// The launchers of the smoother and the dense coarse solve, for any CSR matrix on the device (hmg.hip uses them too).
+// One Gauss-Seidel sweep over the rows d_rows, sorted by (colour, index); colour c holds rows coff[c] .. coff[c + 1] (coff on the
+// host, d_coff its device copy).  one_block: k_csr_gs_block, all colours in one launch of one block; else k_csr_gs, one launch per
+// colour.  backward: the colours in descending order.  *launches (may be null) is advanced by the launches made.
+int csr_gs_sweep(hipStream_t st, int gw, int ncol, const int *coff, const int *d_coff, const int32_t *d_rows, bool one_block,
+                 const int32_t *d_indptr, const int32_t *d_indices, const double *d_vals, double *x, const double *b, bool backward,
+                 int *launches);
+// k_dense_apply: x[d_idx[i]] = sum_j d_inv[i][j] b[d_idx[j]], i < m
+int dense_apply(hipStream_t st, int m, const double *d_inv, const int32_t *d_idx, const double *b, double *x);
 
 } // namespace igx

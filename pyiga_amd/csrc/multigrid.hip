@@ -290,26 +290,8 @@ int sweep(hipStream_t st, igx_solver *s, MgLevel *L, double *x, const double *b,
 {
     const SolverRef R = solver_ref(s);
     const igx_multipatch *m = R.mp;
-    if (L->one_block) {
-        with_gs_kernel(R.gw, [&](auto, auto kb) {
-            kb<<<1, BLOCK_ONE, 0, st>>>(L->ncol, L->d_coff, L->d_rows, m->d_indptr, m->d_indices, m->d_vals, x, b, backward ? 1 : 0);
-        });
-        if (pf) ++pf->launches;
-    } else {
-        const long long groups = BLOCK / R.gw;
-        for (int ci = 0; ci < L->ncol; ++ci) {
-            const int c = backward ? L->ncol - 1 - ci : ci;
-            const long long nr = L->coff[c + 1] - L->coff[c];
-            if (nr == 0) continue;
-            const unsigned nb = (unsigned)std::min<long long>(NB_GS_MAX, (nr + groups - 1) / groups);
-            with_gs_kernel(R.gw, [&](auto k, auto) {
-                k<<<nb, BLOCK, 0, st>>>(nr, L->d_rows + L->coff[c], m->d_indptr, m->d_indices, m->d_vals, x, b);
-            });
-            if (pf) ++pf->launches;
-        }
-    }
-    IGX_HIP(hipGetLastError());
-    return IGX_OK;
+    return csr_gs_sweep(st, R.gw, L->ncol, L->coff.data(), L->d_coff, L->d_rows, L->one_block, m->d_indptr, m->d_indices, m->d_vals, x, b,
+                        backward, pf ? &pf->launches : nullptr);
 }
 
 // rc += P^T W^-1 rf (rf zero on the fixed dofs; rc cleared first)
@@ -342,8 +324,7 @@ int vcycle(hipStream_t st, igx_solver *s, const double *b, double *x, Prof *pf =
     const SolverRef R = solver_ref(s);
     IGX_HIP(hipMemsetAsync(x, 0, (size_t)R.n * sizeof(double), st));
     if (L->d_inv) {
-        if (L->ninv > 0) k_dense_apply<<<(unsigned)L->ninv, BLOCK, 0, st>>>(L->ninv, L->d_inv, L->d_free, b, x);
-        IGX_HIP(hipGetLastError());
+        if (int rc = dense_apply(st, L->ninv, L->d_inv, L->d_free, b, x)) return rc;
         if (pf) ++pf->launches;
         return mark(pf, lvl, PH_COARSE);
     }
@@ -393,6 +374,39 @@ void make_band(const double *M, int nr, int nc, bool transposed, std::vector<int
 } // namespace
 
 namespace igx {
+
+int csr_gs_sweep(hipStream_t st, int gw, int ncol, const int *coff, const int *d_coff, const int32_t *d_rows, bool one_block,
+                 const int32_t *d_indptr, const int32_t *d_indices, const double *d_vals, double *x, const double *b, bool backward,
+                 int *launches)
+{
+    if (one_block) {
+        with_gs_kernel(gw, [&](auto, auto kb) {
+            kb<<<1, BLOCK_ONE, 0, st>>>(ncol, d_coff, d_rows, d_indptr, d_indices, d_vals, x, b, backward ? 1 : 0);
+        });
+        if (launches) ++*launches;
+    } else {
+        const long long groups = BLOCK / gw;
+        for (int ci = 0; ci < ncol; ++ci) {
+            const int c = backward ? ncol - 1 - ci : ci;
+            const long long nr = coff[c + 1] - coff[c];
+            if (nr == 0) continue;
+            const unsigned nb = (unsigned)std::min<long long>(NB_GS_MAX, (nr + groups - 1) / groups);
+            with_gs_kernel(gw, [&](auto k, auto) {
+                k<<<nb, BLOCK, 0, st>>>(nr, d_rows + coff[c], d_indptr, d_indices, d_vals, x, b);
+            });
+            if (launches) ++*launches;
+        }
+    }
+    IGX_HIP(hipGetLastError());
+    return IGX_OK;
+}
+
+int dense_apply(hipStream_t st, int m, const double *d_inv, const int32_t *d_idx, const double *b, double *x)
+{
+    if (m > 0) k_dense_apply<<<(unsigned)m, BLOCK, 0, st>>>(m, d_inv, d_idx, b, x);
+    IGX_HIP(hipGetLastError());
+    return IGX_OK;
+}
 
 void mg_free(igx_solver *s)
 {

@@ -508,6 +508,155 @@ class HSpace:
         assert x.shape[0] == self.numdofs, 'Wrong length of input vector'
         return np.split(x, np.cumsum(self.numactive)[:-1])
 
+    # -- the virtual hierarchy of the local multigrid: smoothing sets and prolongators
+    # Level `lv` of the virtual hierarchy is the space of the active functions of the levels up to `lv` and the deactivated ones
+    # of `lv`.  The four index-set families list, per virtual level and per level, the functions a smoother visits (sorted
+    # multi-index tuples, Dirichlet functions left out), as the reference returns them.
+    def _refinement_mask(self, lv):
+        return self._fact[lv] | self._fdeact[lv]
+
+    def _level_within_disparity(self, i, lv):
+        return lv - self.disparity <= i < lv
+
+    @staticmethod
+    def _sorted_tuples(mask):
+        return [tuple(t) for t in np.argwhere(mask).tolist()]
+
+    def _family(self, coarse_mask):
+        """The index-set family whose entry (lv, lv) is `new_indices` and whose entry (lv, i), i < lv within the disparity, is
+        the active non-Dirichlet functions of level i inside ``coarse_mask(lv, i)``."""
+        out = self.new_indices()
+        for lv in range(self.numlevels):
+            for i in range(lv):
+                if self._level_within_disparity(i, lv):
+                    out[lv][i] = self._sorted_tuples(coarse_mask(lv, i) & self._fact[i] & ~self._boundary_mask(i))
+        return out
+
+    def new_indices(self):
+        """Per virtual level, per level: the functions the level adds (its active, then its deactivated functions)."""
+        out = [[[] for _ in range(self.numlevels)] for _ in range(self.numlevels)]
+        for lv in range(self.numlevels):
+            inner = ~self._boundary_mask(lv)
+            out[lv][lv] = self._sorted_tuples(self._fact[lv] & inner) + self._sorted_tuples(self._fdeact[lv] & inner)
+        return out
+
+    def _pattern_1d(self, lv):
+        """Per axis the 0/1 pattern (fine x coarse) of the two-scale relation from level `lv` to `lv` + 1."""
+        return [scipy.sparse.csr_matrix((scipy.sparse.csr_matrix(P) != 0).astype(np.int32)) for P in self._P[lv]]
+
+    def trunc_indices(self):
+        """`new_indices` and, per coarser level within the disparity, the active functions that the truncation at the virtual
+        level changes: those whose descendants, followed down level by level with the functions of every refinement region
+        taken out on the way, meet the refinement region of the virtual level."""
+        out = self.new_indices()
+        for i in range(self.numlevels - 1):
+            act = np.flatnonzero(self._fact[i])
+            if act.size == 0:
+                continue
+            inner = ~self._boundary_mask(i).ravel()[act]
+            # row n: the descendants of active function n on the current level (ravelled), as a sparse 0/1 matrix
+            M = scipy.sparse.csr_matrix((np.ones(act.size, dtype=np.int32), (np.arange(act.size), act)), shape=(act.size, self.mesh(i).numbf))
+            for lv in range(i + 1, self.numlevels):
+                if not self._level_within_disparity(i, lv):
+                    break
+                pats = self._pattern_1d(lv - 1)
+                K = pats[0]
+                for Pm in pats[1:]:
+                    K = scipy.sparse.kron(K, Pm, format='csr')
+                M = scipy.sparse.csr_matrix(M @ K.T)
+                region = self._refinement_mask(lv).ravel()
+                hit = np.asarray(M @ region.astype(np.int32)).ravel() > 0
+                M = scipy.sparse.csr_matrix(M @ scipy.sparse.diags((~region).astype(np.int32)))
+                M.eliminate_zeros()
+                M.data[:] = 1
+                pick = np.zeros(self.mesh(i).numbf, dtype=bool)
+                pick[act[hit & inner]] = True
+                out[lv][i] = self._sorted_tuples(pick.reshape(self.mesh(i).numdofs))
+        return out
+
+    def func_supp_indices(self):
+        """`new_indices` and, per coarser level, the active ancestors of the active functions of the virtual level."""
+        def ancestors(lv, i):
+            m = self._fact[lv]
+            for l in range(lv - 1, i - 1, -1):
+                m = _apply_axes([Pm.T.tocsr() for Pm in self._pattern_1d(l)], m)
+            return m
+        return self._family(ancestors)
+
+    def cell_supp_indices(self, remove_dirichlet=True):
+        """`new_indices` and, per coarser level, the active functions whose support meets that of the active functions of the
+        virtual level (support extension)."""
+        def extension(lv, i):
+            return self.mesh(i).supported_in_mask(_parents(self.mesh(lv).support_mask(self._fact[lv]), lv - i))
+        if remove_dirichlet:
+            return self._family(extension)
+        out = self.new_indices()
+        for lv in range(self.numlevels):
+            for i in range(lv):
+                if self._level_within_disparity(i, lv):
+                    out[lv][i] = self._sorted_tuples(extension(lv, i) & self._fact[i])
+        return out
+
+    def global_indices(self, vlvl=None):
+        """Per level, all functions of virtual level `vlvl` (its active, then its deactivated functions on the last level);
+        without `vlvl` the list over all virtual levels."""
+        if vlvl is None:
+            return [self.global_indices(vlvl=j) for j in range(self.numlevels)]
+        out = [[] for _ in range(self.numlevels)]
+        for i in range(vlvl + 1):
+            out[i] = self._sorted_tuples(self._fact[i])
+        out[vlvl] = out[vlvl] + self._sorted_tuples(self._fdeact[vlvl])
+        return out
+
+    def indices_to_smooth(self, strategy='func_supp'):
+        """Per virtual level, the matrix indices the smoother of that level visits: strategy ``'new'``, ``'trunc'``,
+        ``'func_supp'`` or ``'cell_supp'``."""
+        assert strategy in ('new', 'trunc', 'func_supp', 'cell_supp'), 'Invalid smoothing strategy'
+        chosen = getattr(self, strategy + '_indices')()
+        return [self.raveled_to_virtual_canonical_indices(lv, self.ravel_indices(chosen[lv])) for lv in range(self.numlevels)]
+
+    def raveled_to_virtual_canonical_indices(self, lv, indices):
+        """Matrix indices on virtual level `lv` of the functions given per level by ravelled tensor-product indices."""
+        avail = self._virtual_indices(lv)
+        out, off = [], 0
+        for l in range(self.numlevels):
+            given = np.asarray(indices[l], dtype=np.int64)
+            if l > lv:
+                if given.size:
+                    raise ValueError('level %d has no functions on virtual level %d' % (l, lv))
+                continue
+            rank = np.full(self.mesh(l).numbf, -1, dtype=np.int64)
+            rank[avail[l]] = np.arange(avail[l].size)
+            if given.size and rank[given].min() < 0:
+                raise ValueError('a function of level %d does not belong to virtual level %d' % (l, lv))
+            out.append(off + rank[given])
+            off += avail[l].size
+        return np.concatenate(out).astype(int) if out else np.zeros(0, dtype=int)
+
+    def virtual_hierarchy_prolongators(self, truncate=None):
+        """The prolongation matrices between consecutive virtual levels (scipy sparse, one per level but the finest): the
+        identity on the functions kept, the two-scale relation from the deactivated functions of the level to the refinement
+        region of the next one, and for THB-splines (``truncate``; default: the attribute) the inverse truncation of that level
+        applied from the left."""
+        if truncate is None:
+            truncate = self.truncate
+        IA, ID = self.active_indices(), self.deactivated_indices()
+        nt = np.cumsum([a.size for a in IA])
+        out = []
+        for lv in range(self.numlevels - 1):
+            IR = np.concatenate((IA[lv + 1], ID[lv + 1]))
+            rank = np.full(self.mesh(lv + 1).numbf, -1, dtype=np.int64)
+            rank[IR] = np.arange(IR.size)
+            tabs = [t[1:] for t in self.composite_tables(lv, lv + 1)]
+            I, J, V = _expand_columns(tabs, np.unravel_index(ID[lv], self.mesh(lv).numdofs), self.mesh(lv + 1).numdofs)
+            keep = rank[I] >= 0
+            P_rd = scipy.sparse.csr_matrix((V[keep], (rank[I][keep], J[keep])), shape=(IR.size, ID[lv].size))
+            P = scipy.sparse.bmat(((scipy.sparse.identity(int(nt[lv])), None), (None, P_rd)), format='csc')
+            if truncate:
+                P = scipy.sparse.csc_matrix(self.truncate_one_level(lv, num_rows=P.shape[0], inverse=True) @ P)
+            out.append(P)
+        return out
+
     # -- evaluation
     def coeffs_to_levelwise_funcs(self, coeffs, truncate=None):
         """One :class:`.BSplineFunc` per level whose sum is the hierarchical spline with the given coefficients (THB-spline

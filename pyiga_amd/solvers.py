@@ -45,6 +45,11 @@ blocks and the preconditioner on the device.
 ``SaddlePointSystem((kvs_u, kvs_p), geo, bcs)`` and ``OseenSystem((kvs_u, kvs_p), geo, bcs, viscosity=nu, w=wind)``: the Stokes
 system ``[[A, B^T], [B, 0]]`` by preconditioned MINRES, and the Oseen system -- the same with a frozen-wind convection term in the
 velocity block -- by right-preconditioned restarted GMRES with a block-diagonal or block-triangular preconditioner.
+
+``solve_hmultigrid(hs, A, f, ...)``, ``local_mg_step(...)`` and ``HierarchicalSystem(hs, problem, rhs, geo=geo)``: the local
+multigrid of the reference for hierarchical (HB / THB) spline spaces (pyiga/solvers.py:174-324) with the level matrices, the
+transfers and the coloured Gauss-Seidel sweeps on the device (``HMultigrid``, csrc/hmg.hip), as a stationary iteration or as the
+preconditioner of CG.
 """
 import ctypes as C
 import math
@@ -3470,3 +3475,539 @@ class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
     def schwarz_setup(self):
         raise ValueError("the Schwarz preconditioner is not offered for eigenproblems: use precond='mg'")
 
+
+
+################################################################################
+# Local multigrid for hierarchical spline spaces (pyiga/solvers.py:174-324; csrc/hmg.hip)
+################################################################################
+
+HMG_SMOOTHERS = ('gs', 'forward_gs', 'backward_gs', 'symmetric_gs')
+_ip32 = C.POINTER(C.c_int32)
+
+
+def _csr32(A):
+    """`A` as scipy CSR with ascending columns in every row and int32 index arrays (explicit zeros stay)."""
+    A = scipy.sparse.csr_matrix(A)
+    if not A.has_sorted_indices:
+        A = A.copy()
+        A.sort_indices()
+    if A.nnz >= 2 ** 31:
+        raise ValueError('matrix with %d entries: int32 positions' % A.nnz)
+    return scipy.sparse.csr_matrix((np.asarray(A.data, dtype=np.float64), A.indices.astype(np.int32), A.indptr.astype(np.int32)), shape=A.shape)
+
+
+def _ones_pattern(indptr, indices, shape):
+    return scipy.sparse.csr_matrix((np.ones(len(indices), dtype=np.int64), indices, indptr), shape=shape)
+
+
+def triple_product_pattern(indptr, indices, P):
+    """``(indptr, indices)`` (int32, ascending columns) of the structural pattern of ``P^T A P``: the product of the 0/1 matrices
+    of the stored entries of `A` (given by its pattern) and `P`, so that no entry is lost to cancellation."""
+    P = scipy.sparse.csr_matrix(P)
+    Pb = _ones_pattern(P.indptr, P.indices, P.shape)
+    Cp = scipy.sparse.csr_matrix(Pb.T @ _ones_pattern(indptr, indices, (P.shape[0], P.shape[0])) @ Pb)
+    Cp.sort_indices()
+    return Cp.indptr.astype(np.int32), Cp.indices.astype(np.int32)
+
+
+def colour_order(indptr, indices, ind):
+    """The rows `ind` of the pattern sorted by (colour, index) and the colour offsets: the first-fit colouring in ascending
+    index order over the pattern restricted to the set (``first_fit_colouring`` with the set as its mask)."""
+    ind = np.asarray(ind, dtype=np.int64)
+    n = len(indptr) - 1
+    mask = np.zeros(n, dtype=np.uint8)
+    mask[ind] = 1
+    if int(mask.sum()) != ind.size:
+        raise ValueError('an index list names a dof twice')
+    colour, nc = first_fit_colouring(indptr, indices, mask)
+    rows = np.flatnonzero(mask)
+    rows = rows[np.argsort(colour[rows], kind='stable')]
+    coff = np.concatenate(([0], np.cumsum(np.bincount(colour[rows], minlength=nc)))).astype(np.int32)
+    return rows.astype(np.int32), coff
+
+
+class _DeviceBytes:
+    """Host arrays of any dtype copied to device memory, freed together."""
+
+    def __init__(self, ctx):
+        self.ctx, self.ptrs = ctx, []
+
+    def alloc(self, nbytes):
+        ptr = _lib.load().igx_dev_alloc(self.ctx.handle, max(int(nbytes), 8))
+        if not ptr:
+            raise _lib.IgxError('igx_dev_alloc failed: ' + _lib.last_error())
+        self.ptrs.append(ptr)
+        return ptr
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a)
+        ptr = self.alloc(a.nbytes)
+        if a.nbytes:
+            _lib.check(_lib.load().igx_dev_upload(self.ctx.handle, ptr, a.ctypes.data, a.nbytes), 'igx_dev_upload')
+        return ptr
+
+    def free(self):
+        if getattr(self.ctx, 'handle', None):
+            _lib.check(_lib.load().igx_sync(self.ctx.handle), 'igx_sync')           # (nothing in flight may read what goes now)
+            for p in self.ptrs:
+                _lib.load().igx_dev_free(self.ctx.handle, p)
+        self.ptrs = []
+
+
+def csr_rap_device(ctx, A, PT, Cpat, d_a_vals=None, max_blocks=None):
+    """The values of ``PT A PT^T`` on the pattern `Cpat` = ``(indptr, indices)``, computed on the device (``igx_csr_rap_d``) and
+    left there: returns ``(buffers, pointer)``; the caller frees `buffers`.  `A`: scipy CSR, or with `d_a_vals` (device values)
+    only its pattern is read.  `PT`: the transposed prolongation as scipy CSR."""
+    A, PT = _csr32(A), _csr32(PT)
+    buf = _DeviceBytes(ctx)
+    try:
+        cip, cix = np.ascontiguousarray(Cpat[0], dtype=np.int32), np.ascontiguousarray(Cpat[1], dtype=np.int32)
+        d_cv = buf.alloc(8 * cix.size)
+        tmax = int(np.diff(PT.indptr).max()) if PT.shape[0] else 0
+        _lib.check(_lib.load().igx_csr_rap_d(
+            ctx.handle, A.shape[0], PT.shape[0], buf.upload(A.indptr), buf.upload(A.indices), d_a_vals or buf.upload(A.data), A.nnz,
+            buf.upload(PT.indptr), buf.upload(PT.indices), buf.upload(PT.data), PT.nnz, tmax, buf.upload(cip), buf.upload(cix), d_cv, cix.size,
+            int(max_blocks or 0)), 'igx_csr_rap_d')
+        _lib.check(_lib.load().igx_sync(ctx.handle), 'igx_sync')
+    except BaseException:
+        buf.free()
+        raise
+    return buf, d_cv
+
+
+def csr_rap(A, P, max_blocks=None, device=None):
+    """``P^T A P`` as scipy CSR with the values computed on the device (``igx_csr_rap_d``) on the structural pattern."""
+    ctx = _lib.context(device)
+    A, P = _csr32(A), scipy.sparse.csr_matrix(P)
+    cip, cix = triple_product_pattern(A.indptr, A.indices, P)
+    buf, d_cv = csr_rap_device(ctx, A, P.T, (cip, cix), max_blocks=max_blocks)
+    try:
+        vals = np.empty(cix.size)
+        if vals.size:
+            _lib.check(_lib.load().igx_dev_download(ctx.handle, vals.ctypes.data, d_cv, vals.nbytes), 'igx_dev_download')
+    finally:
+        buf.free()
+    return scipy.sparse.csr_matrix((vals, cix, cip), shape=(P.shape[1], P.shape[1]))
+
+
+def csr_rect_spmv(M, x, y=None, max_blocks=None, device=None):
+    """``M x`` (or ``y + M x``) for a rectangular sparse matrix, computed on the device (``igx_csr_rect_spmv_d``)."""
+    ctx = _lib.context(device)
+    M = _csr32(M)
+    x = _lib.f64(x)
+    if x.shape != (M.shape[1],):
+        raise ValueError('vector of shape %r for a matrix of shape %r' % (x.shape, M.shape))
+    buf = _DeviceBytes(ctx)
+    try:
+        d_y = buf.upload(np.zeros(M.shape[0]) if y is None else _lib.f64(y))
+        _lib.check(_lib.load().igx_csr_rect_spmv_d(ctx.handle, M.shape[0], M.shape[1], buf.upload(M.indptr), buf.upload(M.indices),
+                                                   buf.upload(M.data), M.nnz, int(np.diff(M.indptr).max()) if M.shape[0] else 0,
+                                                   buf.upload(x), d_y, int(y is not None), int(max_blocks or 0)), 'igx_csr_rect_spmv_d')
+        out = np.empty(M.shape[0])
+        if out.size:
+            _lib.check(_lib.load().igx_dev_download(ctx.handle, out.ctypes.data, d_y, out.nbytes), 'igx_dev_download')
+    finally:
+        buf.free()
+    return out
+
+
+class HMultigrid:
+    """The virtual hierarchy of a hierarchical spline space on the device (``igx_hmg``): per level the Galerkin matrix, the
+    prolongation and its transpose, and the smoothing set as row lists by colour; on level 0 the dense inverse.
+
+    Args:
+        A: the matrix of the finest level, scipy sparse (uploaded once), or a triple ``(indptr, indices, d_values)`` whose values
+            are on the device already (copied there)
+        Ps: the prolongations between consecutive levels, coarsest first (``HSpace.virtual_hierarchy_prolongators``)
+        lv_inds: per level the dofs the smoother visits (level 0: the dofs of the direct solve).  The lists are honoured as
+            sets: a sweep runs in (colour, index) order of the first-fit colouring of the level's matrix restricted to the set,
+            which is a Gauss-Seidel sweep in that order (rows of one colour do not couple)
+        free: the dofs the residual norm of a solve runs over (default: all)
+        smoother: ``'gs'`` (forward sweeps before, backward after the coarse correction), ``'forward_gs'``, ``'backward_gs'``
+            or ``'symmetric_gs'``; ``'exact'`` needs a direct solve per level and raises NotImplementedError
+        coarse_max: level 0 is solved with a dense inverse formed on the host; more dofs than this raise ValueError
+        block_rows: a smoothing set of at most this many rows sweeps in one launch of one block (default ``MG_BLOCK_ROWS``),
+            a larger one with one launch per colour
+        max_blocks: cap of the grid of the triple-product kernel (None: the library's default); the values do not depend on it
+    """
+
+    def __init__(self, A, Ps, lv_inds, free=None, smoother='gs', smooth_steps=2, coarse_max=2048, block_rows=None, max_blocks=None,
+                 device=None):
+        if smoother == 'exact':
+            raise NotImplementedError("smoother='exact' needs a direct solve on every level and is not available on the device; "
+                                      "use 'gs', 'forward_gs', 'backward_gs' or 'symmetric_gs'")
+        if smoother not in HMG_SMOOTHERS:
+            raise ValueError('unknown smoother %r (one of %s)' % (smoother, ', '.join(HMG_SMOOTHERS)))
+        smooth_steps = int(smooth_steps)
+        if not 1 <= smooth_steps <= 16:
+            raise ValueError('smooth_steps must be 1 .. 16')
+        Ps = [_csr32(P) for P in Ps]
+        L = len(Ps) + 1
+        if not 1 <= L <= _lib.IGX_HMG_MAX_LEVELS or len(lv_inds) != L:
+            raise ValueError('%d prolongations and %d index lists: one list per level, at most %d levels' % (len(Ps), len(lv_inds), _lib.IGX_HMG_MAX_LEVELS))
+        if isinstance(A, tuple):
+            indptr, indices, d_vals = A
+            indptr, indices = np.ascontiguousarray(indptr, dtype=np.int32), np.ascontiguousarray(indices, dtype=np.int32)
+            host = None
+        else:
+            host = _csr32(A)
+            if host.shape[0] != host.shape[1]:
+                raise ValueError('the matrix is not square')
+            indptr, indices, d_vals = host.indptr, host.indices, None
+        n = indptr.size - 1
+        inds = [np.asarray(ix, dtype=np.int64).ravel() for ix in lv_inds]
+        if inds[0].size > int(coarse_max):
+            raise ValueError('level 0 keeps %d dofs for the direct solve, more than coarse_max = %d' % (inds[0].size, int(coarse_max)))
+        sizes = [P.shape[1] for P in Ps] + [n]
+        for l, P in enumerate(Ps):
+            if P.shape[0] != sizes[l + 1]:
+                raise ValueError('prolongation %d has %d rows, the level above %d dofs' % (l, P.shape[0], sizes[l + 1]))
+        for l, ix in enumerate(inds):
+            if ix.size and (ix.min() < 0 or ix.max() >= sizes[l]):
+                raise ValueError('an index of level %d is outside its %d dofs' % (l, sizes[l]))
+        # the structural patterns of the Galerkin chain, host
+        pats = [None] * L
+        pats[L - 1] = (indptr, indices)
+        for l in range(L - 1, 0, -1):
+            pats[l - 1] = triple_product_pattern(pats[l][0], pats[l][1], Ps[l - 1])
+        self.n, self.numlevels, self.sizes = n, L, sizes
+        self.smoother, self.smooth_steps = smoother, smooth_steps
+        self.lv_inds, self._pats = inds, pats
+        self._ctx = _lib.context(device)
+        lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(lib.igx_hmg_create(self._ctx.handle, L, C.byref(h)), 'igx_hmg_create')
+        self.handle = h
+        tmp = _DeviceBytes(self._ctx)
+        try:
+            if d_vals is None:
+                d_vals = tmp.upload(host.data)
+            for l in range(L):
+                ip, ix = pats[l]
+                _lib.check(lib.igx_hmg_set_matrix(h, l, sizes[l], ip.ctypes.data_as(_ip32), ix.ctypes.data_as(_ip32), d_vals if l == L - 1 else None),
+                           'igx_hmg_set_matrix')
+            for l in range(1, L):
+                P = Ps[l - 1]
+                _lib.check(lib.igx_hmg_set_transfer(h, l, sizes[l - 1], P.indptr.ctypes.data_as(_ip32), P.indices.ctypes.data_as(_ip32), _lib.dptr(P.data)),
+                           'igx_hmg_set_transfer')
+            for l in range(L - 1, 0, -1):
+                _lib.check(lib.igx_hmg_galerkin(h, l, int(max_blocks or 0)), 'igx_hmg_galerkin')
+            block_rows = MG_BLOCK_ROWS if block_rows is None else int(block_rows)
+            self.colours = [None] * L
+            for l in range(1, L):
+                rows, coff = colour_order(pats[l][0], pats[l][1], inds[l])
+                self.colours[l] = (rows, coff)
+                _lib.check(lib.igx_hmg_set_smoother(h, l, coff.size - 1, coff.ctypes.data_as(_ip32), rows.ctypes.data_as(_ip32), block_rows),
+                           'igx_hmg_set_smoother')
+            # level 0: the matrix on its dofs, inverted on the host
+            A0 = self.level_matrix(0)
+            i0 = inds[0]
+            inv = np.ascontiguousarray(scipy.linalg.inv(A0[i0][:, i0].toarray())) if i0.size else np.zeros((0, 0))
+            i032 = np.ascontiguousarray(i0, dtype=np.int32)
+            _lib.check(lib.igx_hmg_set_inverse(h, i032.ctypes.data_as(_ip32), i0.size, _lib.dptr(inv)), 'igx_hmg_set_inverse')
+            mask = np.ones(n, dtype=np.uint8)
+            if free is not None:
+                mask[:] = 0
+                mask[np.asarray(free, dtype=np.int64)] = 1
+            self.free = np.flatnonzero(mask)
+            _lib.check(lib.igx_hmg_set_free(h, mask.ctypes.data_as(C.POINTER(C.c_uint8))), 'igx_hmg_set_free')
+            _lib.check(lib.igx_hmg_set_options(h, _lib.HMG_SMOOTHERS[smoother], smooth_steps), 'igx_hmg_set_options')
+        except BaseException:
+            self.close()
+            raise
+        finally:
+            tmp.free()
+        self.info = None
+
+    def _live(self):
+        if not getattr(self, 'handle', None):
+            raise _lib.IgxError('the hierarchy was closed')
+        return self.handle
+
+    def close(self):
+        h, self.handle = getattr(self, 'handle', None), None
+        if h and getattr(self._ctx, 'handle', None):
+            _lib.load().igx_hmg_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def level_matrix(self, l):
+        """The matrix of level `l` (0: coarsest), downloaded as scipy CSR on the structural pattern of the Galerkin product."""
+        ip, ix = self._pats[l]
+        vals = np.empty(ix.size)
+        _lib.check(_lib.load().igx_hmg_level_values(self._live(), int(l), _lib.dptr(vals)), 'igx_hmg_level_values')
+        return scipy.sparse.csr_matrix((vals, ix, ip), shape=(self.sizes[l], self.sizes[l]))
+
+    def level_info(self, l):
+        out = _lib.HmgLevel()
+        _lib.check(_lib.load().igx_hmg_level_info(self._live(), int(l), C.byref(out)), 'igx_hmg_level_info')
+        return {k: getattr(out, k) for k, _ in out._fields_ if k != 'reserved'}
+
+    def _vec(self, v, what):
+        v = _lib.f64(v)
+        if v.shape != (self.n,):
+            raise ValueError('%s has shape %r, the finest level %d dofs' % (what, v.shape, self.n))
+        return v
+
+    # -- device vectors in and out (HierarchicalSystem keeps its vectors there)
+    def spmv_d(self, d_x, d_y, d_b=None, sign=1.0):
+        """``d_y = [d_b +] sign A d_x`` on the finest level."""
+        _lib.check(_lib.load().igx_hmg_spmv_d(self._live(), d_x.ptr, None if d_b is None else d_b.ptr, float(sign), d_y.ptr), 'igx_hmg_spmv_d')
+
+    def cycle_d(self, d_f, d_x):
+        _lib.check(_lib.load().igx_hmg_cycle_d(self._live(), d_f.ptr, d_x.ptr), 'igx_hmg_cycle_d')
+
+    def solve_d(self, d_f, d_x, method='iterate', tol=1e-8, maxiter=5000):
+        if method not in _lib.HMG_METHODS:
+            raise ValueError("unknown method %r ('iterate' or 'cg')" % (method,))
+        if method == 'cg' and self.smoother not in ('gs', 'symmetric_gs'):
+            raise ValueError("method='cg' needs a symmetric cycle: smoother 'gs' or 'symmetric_gs', not %r" % self.smoother)
+        info = _lib.HmgInfo()
+        _lib.check(_lib.load().igx_hmg_solve_d(self._live(), _lib.HMG_METHODS[method], d_f.ptr, d_x.ptr, float(tol), int(maxiter), C.byref(info)),
+                   'igx_hmg_solve_d')
+        self.info = dict(info.as_dict(), method=method)
+        return self.info
+
+    # -- host vectors
+    def spmv(self, x):
+        d_x, d_y = DeviceArray.from_host(self._ctx, self._vec(x, 'x')), DeviceArray(self._ctx, self.n)
+        self.spmv_d(d_x, d_y)
+        return d_y.download()
+
+    def cycle(self, f, x=None):
+        """One cycle with the right-hand side `f` from the guess `x` (default: zero): the reference's ``step``."""
+        d_f = DeviceArray.from_host(self._ctx, self._vec(f, 'f'))
+        d_x = DeviceArray.from_host(self._ctx, np.zeros(self.n) if x is None else self._vec(x, 'x'))
+        self.cycle_d(d_f, d_x)
+        return d_x.download()
+
+    def solve(self, f, method='iterate', tol=1e-8, maxiter=5000):
+        """``A x = f`` from ``x = 0``; the statistics are left in ``info``."""
+        d_f, d_x = DeviceArray.from_host(self._ctx, self._vec(f, 'f')), DeviceArray(self._ctx, self.n)
+        self.solve_d(d_f, d_x, method=method, tol=tol, maxiter=maxiter)
+        return d_x.download()
+
+    def profile(self, f, reps=5):
+        """Device time of one cycle by phase (events after every phase; mean over `reps` cycles on a zero guess)."""
+        d_f, d_x = DeviceArray.from_host(self._ctx, self._vec(f, 'f')), DeviceArray.from_host(self._ctx, np.zeros(self.n))
+        out = _lib.HmgProfile()
+        _lib.check(_lib.load().igx_hmg_profile_d(self._live(), d_f.ptr, d_x.ptr, int(reps), C.byref(out)), 'igx_hmg_profile_d')
+        L = self.numlevels
+        return dict(levels=L, launches=out.launches, total_ms=out.total_ms, coarse_ms=out.coarse_ms, smooth_ms=list(out.smooth_ms)[:L],
+                    residual_ms=list(out.residual_ms)[:L], transfer_ms=list(out.transfer_ms)[:L])
+
+
+def _hmg_finest(hs, A, ctx, keep, max_blocks=None):
+    """The matrix of the finest level for `hs` from `A`: a scipy matrix as it is, or an ``HDiscretization`` whose HB values are on
+    the device -- as ``(indptr, indices, d_values)``; for a THB space ``T^T A_hb T`` is formed there (buffers go to `keep`)."""
+    from .hierarchical import HDiscretization
+    if not isinstance(A, HDiscretization):
+        return A
+    if A.hs is not hs:
+        raise ValueError('the discretisation belongs to another space')
+    if not A.values_d:
+        raise ValueError('the discretisation holds no values on the device: call assemble_hb_values() or assemble_matrix() first')
+    if not hs.truncate:
+        return (A.indptr, A.indices, A.values_d)
+    T = _csr32(hs.thb_to_hb())
+    Ahb = scipy.sparse.csr_matrix((np.zeros(A.indices.size), A.indices, A.indptr), shape=(hs.numdofs, hs.numdofs))
+    cip, cix = triple_product_pattern(A.indptr, A.indices, T)
+    buf, d_cv = csr_rap_device(ctx, Ahb, T.T, (cip, cix), d_a_vals=A.values_d, max_blocks=max_blocks)
+    keep.append(buf)
+    return (cip, cix, d_cv)
+
+
+def local_mg_step(hs, A, f, Ps, lv_inds, smoother='symmetric_gs', smooth_steps=2, **kwargs):
+    """A callable ``step(x)`` that performs one cycle of the local multigrid method on the device (pyiga/solvers.py:174-241).
+
+    The index lists `lv_inds` are honoured as sets: every sweep runs in (colour, index) order of the first-fit colouring of the
+    level's Galerkin matrix restricted to the set -- one launch or one barrier per colour is exactly the sequential Gauss-Seidel
+    sweep in that order -- not in the order of the lists.  ``smoother='exact'`` raises NotImplementedError.  The hierarchy is
+    the attribute ``step.hierarchy`` (an :class:`HMultigrid`; ``close()`` frees it).  Keywords: those of :class:`HMultigrid`."""
+    ctx = _lib.context(kwargs.get('device'))
+    keep = []
+    try:
+        if smoother == 'exact':
+            raise NotImplementedError("smoother='exact' needs a direct solve on every level and is not available on the device")
+        H = HMultigrid(_hmg_finest(hs, A, ctx, keep, kwargs.get('max_blocks')), Ps, lv_inds, smoother=smoother, smooth_steps=smooth_steps, **kwargs)
+    finally:
+        for b in keep:
+            b.free()
+    d_f = DeviceArray.from_host(ctx, H._vec(f, 'f'))
+
+    def step(x):
+        d_x = DeviceArray.from_host(ctx, H._vec(x, 'x'))
+        H.cycle_d(d_f, d_x)
+        return d_x.download()
+    step.hierarchy = H
+    return step
+
+
+def solve_hmultigrid(hs, A, f, strategy='cell_supp', smoother='gs', smooth_steps=2, tol=1e-8, maxiter=5000, method='iterate',
+                     coarse_max=2048, max_blocks=None, block_rows=None):
+    """Solves a scalar problem in a hierarchical spline space by local multigrid on the device (pyiga/solvers.py:285-324).
+
+    `A`: the matrix in the basis of `hs`, scipy sparse (uploaded once), or an ``HDiscretization`` of `hs` whose values are on
+    the device.  `strategy`: the smoothing sets, ``'new'``, ``'trunc'``, ``'func_supp'`` or ``'cell_supp'``.  `smoother`: see
+    :class:`HMultigrid`.  ``method='iterate'`` repeats the cycle until the residual over the non-Dirichlet dofs has dropped by
+    `tol`; ``method='cg'`` uses the cycle as the preconditioner of CG (symmetric positive definite matrices, smoother ``'gs'``
+    or ``'symmetric_gs'``; else ValueError).  Returns ``(x, iterations)``, the count ``numpy.inf`` when not converged."""
+    if smoother == 'exact':
+        raise NotImplementedError("smoother='exact' needs a direct solve on every level and is not available on the device")
+    if method not in _lib.HMG_METHODS:
+        raise ValueError("unknown method %r ('iterate' or 'cg')" % (method,))
+    if method == 'cg' and smoother not in ('gs', 'symmetric_gs'):
+        raise ValueError("method='cg' needs a symmetric cycle: smoother 'gs' or 'symmetric_gs', not %r" % (smoother,))
+    ctx = _lib.context(None)
+    keep = []
+    try:
+        H = HMultigrid(_hmg_finest(hs, A, ctx, keep, max_blocks), hs.virtual_hierarchy_prolongators(), hs.indices_to_smooth(strategy),
+                       free=hs.non_dirichlet_dofs(), smoother=smoother, smooth_steps=smooth_steps, coarse_max=coarse_max,
+                       block_rows=block_rows, max_blocks=max_blocks)
+    finally:
+        for b in keep:
+            b.free()
+    try:
+        x = H.solve(f, method=method, tol=tol, maxiter=maxiter)
+        return x, (H.info['iterations'] if H.info['converged'] else np.inf)
+    finally:
+        H.close()
+
+
+class HierarchicalSystem:
+    """The Dirichlet problem of a scalar form over a hierarchical spline space, assembled and solved on the device.
+
+    ``HierarchicalSystem(hs, problem, rhs, geo=geo, lift=None, **inputs)``: `problem` a bilinear form string, `rhs` a linear one
+    (or None for ``'f * v * dx'``), `inputs` the named inputs of both.  The matrix is assembled with ``HDiscretization`` and its
+    values stay in device memory; for a THB space ``T^T A T`` and ``T^T rhs`` are formed there.  The Dirichlet sides are those
+    of ``hs.bdspecs``.  `lift`: canonical coefficients that are non-zero on Dirichlet dofs only; the system solves for
+    ``f - A lift`` (formed on the device) and adds the lift back.  Only the right-hand side goes up and only the solution comes
+    down.  Limits: scalar forms on one patch in 2D or 3D (as ``HDiscretization``); ``method='cg'`` needs a symmetric positive
+    definite matrix; ``smoother='exact'`` is refused; level 0 keeps at most `coarse_max` dofs; the pattern of every triple
+    product is built on the host."""
+
+    def __init__(self, hs, problem, rhs=None, geo=None, lift=None, max_blocks=None, **inputs):
+        from .hierarchical import HDiscretization
+        if geo is None:
+            raise ValueError("required input parameter 'geo' missing")
+        self.hs, self.n = hs, hs.numdofs
+        self.max_blocks = max_blocks
+        self._ctx = _lib.context(None)
+        self._H, self._key = None, None
+        self._bufs = []
+        self.info = None
+        if lift is not None:
+            lift = _lib.f64(lift)
+            if lift.shape != (self.n,):
+                raise ValueError('lift has shape %r, the space %d dofs' % (lift.shape, self.n))
+            if np.any(lift[hs.non_dirichlet_dofs()] != 0.0):
+                raise ValueError('lift must vanish on the non-Dirichlet dofs')
+        self.lift = lift
+        disc = HDiscretization(hs, problem, dict(inputs, geo=geo), max_blocks=max_blocks)
+        try:
+            disc.assemble_hb_values()
+            keep = []
+            self._matrix = _hmg_finest(hs, disc, self._ctx, keep, max_blocks)
+            if keep:                                  # (THB: the product owns its values; the HB values may go)
+                self._bufs += keep
+            else:                                     # (HB: the values change hands)
+                self._owned, disc.values_d = disc.values_d, None
+            # the right-hand side: assembled per level on the device, gathered to canonical order (HB functionals)
+            trunc, disc.truncate = disc.truncate, False
+            try:
+                b = disc.assemble_rhs(rhs)
+            finally:
+                disc.truncate = trunc
+        finally:
+            disc.close()
+        self._d_f = DeviceArray(self._ctx, self.n)
+        if hs.truncate:
+            TT = _csr32(hs.thb_to_hb().T)
+            tmp = _DeviceBytes(self._ctx)
+            try:
+                _lib.check(_lib.load().igx_csr_rect_spmv_d(self._ctx.handle, self.n, self.n, tmp.upload(TT.indptr), tmp.upload(TT.indices), tmp.upload(TT.data),
+                                                           TT.nnz, int(np.diff(TT.indptr).max()), tmp.upload(b), self._d_f.ptr, 0, 0), 'igx_csr_rect_spmv_d')
+            finally:
+                tmp.free()
+        else:
+            self._d_f.upload(b)
+
+    _owned = None
+
+    def _hierarchy(self, strategy, smoother, smooth_steps, coarse_max, block_rows):
+        key = (strategy, smoother, int(smooth_steps), int(coarse_max), block_rows)
+        if self._H is None or self._key != key:
+            if self._H is not None:
+                self._H.close()
+                self._H = None
+            hs = self.hs
+            self._H = HMultigrid(self._matrix, hs.virtual_hierarchy_prolongators(), hs.indices_to_smooth(strategy),
+                                 free=hs.non_dirichlet_dofs(), smoother=smoother, smooth_steps=smooth_steps, coarse_max=coarse_max,
+                                 block_rows=block_rows, max_blocks=self.max_blocks)
+            self._key = key
+        return self._H
+
+    def setup(self, strategy='cell_supp', smoother='gs', smooth_steps=2, coarse_max=2048, block_rows=None):
+        """Builds the hierarchy (kept until other options are asked for); ``solve`` does it on demand."""
+        if self._matrix is None:
+            raise _lib.IgxError('the system was closed')
+        self._hierarchy(strategy, smoother, smooth_steps, coarse_max, block_rows)
+        return self
+
+    def solve(self, strategy='cell_supp', smoother='gs', method='cg', tol=1e-8, maxiter=5000, smooth_steps=2, coarse_max=2048, block_rows=None):
+        """The solution in canonical order (with the lift added back); the statistics are left in ``info``."""
+        if smoother == 'exact':
+            raise NotImplementedError("smoother='exact' needs a direct solve on every level and is not available on the device")
+        if method == 'cg' and smoother not in ('gs', 'symmetric_gs'):
+            raise ValueError("method='cg' needs a symmetric cycle: smoother 'gs' or 'symmetric_gs', not %r" % (smoother,))
+        self.setup(strategy, smoother, smooth_steps, coarse_max, block_rows)
+        H = self._H
+        d_f = self._d_f
+        if self.lift is not None:                     # f - A g: one product on the device
+            d_g, d_f = DeviceArray.from_host(self._ctx, self.lift), DeviceArray(self._ctx, self.n)
+            H.spmv_d(d_g, d_f, d_b=self._d_f, sign=-1.0)
+        d_x = DeviceArray(self._ctx, self.n)
+        self.info = H.solve_d(d_f, d_x, method=method, tol=tol, maxiter=maxiter)
+        x = d_x.download()
+        return x if self.lift is None else x + self.lift
+
+    @property
+    def hierarchy(self):
+        """The :class:`HMultigrid` of the last ``setup`` / ``solve`` (None before)."""
+        return self._H
+
+    def rhs(self):
+        """The right-hand side in the basis of the space, downloaded."""
+        return self._d_f.download()
+
+    def spmv(self, x):
+        return self.setup()._H.spmv(x) if self._H is None else self._H.spmv(x)
+
+    def cycle(self, r):
+        """One cycle from a zero guess on `r` with the hierarchy of the last ``setup`` / ``solve`` (default options else)."""
+        return (self.setup()._H if self._H is None else self._H).cycle(r)
+
+    def level_matrix(self, l):
+        return (self.setup()._H if self._H is None else self._H).level_matrix(l)
+
+    def close(self):
+        if self._H is not None:
+            self._H.close()
+            self._H = None
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+        if self._owned and getattr(self._ctx, 'handle', None):
+            _lib.load().igx_dev_free(self._ctx.handle, self._owned)
+        self._owned = None
+        self._matrix = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
