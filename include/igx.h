@@ -521,7 +521,7 @@ int  igx_multipatch_add_face_host(igx_multipatch *mp, int p, int axis, int side,
 typedef struct igx_solver igx_solver;
 enum { IGX_PRECOND_NONE = 0, IGX_PRECOND_JACOBI = 1, IGX_PRECOND_KRON = 2,
        IGX_PRECOND_SCHWARZ = 3,     /* multipatch solvers only: set up by igx_solver_set_schwarz */
-       IGX_PRECOND_MG = 4 };        /* multipatch solvers, CG only: one V-cycle of the hierarchy set up by igx_solver_set_mg_* */
+       IGX_PRECOND_MG = 4 };        /* multipatch solvers, CG only: one V-cycle of the hierarchy set up by igx_solver_set_[block_]mg_* */
 /* how the per-axis eigenvalues lam_k form the diagonal D of a Kronecker preconditioner  (x)U_k . D^-1 . (x)U_k^T */
 enum { IGX_KRON_SUM = 1,       /* D = sum_k 1 (x) .. (x) lam_k (x) .. (x) 1: fast diagonalization of sum_k K_k (x) M_rest (Sangalli-Tani) */
        IGX_KRON_PRODUCT = 2 }; /* D = (x)_k lam_k: with U_k, lam_k the eigenpairs of M_k this is (x) M_k^-1 */
@@ -720,8 +720,8 @@ int  igx_solver_set_block_kron(igx_solver *solver, int comp, const int32_t *box_
    on a solver made with symmetric = 0 is IGX_ERR_UNSUPPORTED.  The solver reads the pattern of `mp`, which must outlive it, but
    owns its value buffers: restarting the multipatch's sums afterwards leaves it as it is.  igx_solver_solve needs b (host,
    nc * nrows; NULL: IGX_ERR_ARG).  Preconditioners: NONE, JACOBI (the diagonals of the diagonal blocks), SCHWARZ once
-   igx_solver_set_block_schwarz has set every component; IGX_PRECOND_KRON, IGX_PRECOND_MG and the eigen, parabolic, stepping and
-   Newton calls: IGX_ERR_UNSUPPORTED. */
+   igx_solver_set_block_schwarz has set every component, MG once igx_solver_set_block_mg_* have completed a hierarchy (until then
+   IGX_ERR_UNSUPPORTED); IGX_PRECOND_KRON and the eigen, parabolic, stepping and Newton calls: IGX_ERR_UNSUPPORTED. */
 int  igx_solver_create_multipatch_block(igx_multipatch *mp, int ncomp, int symmetric, const int64_t *fixed, int64_t nfixed,
                                         igx_solver **out);
 /* Copies the current sums of the multipatch (after igx_multipatch_zero and the scatters of EVERY patch: the interior rows are
@@ -738,6 +738,27 @@ int  igx_solver_download_multipatch_block(const igx_solver *solver, int p, int q
    IGX_ERR_UNSUPPORTED. */
 int  igx_solver_set_block_schwarz(igx_solver *solver, int comp, const int32_t *box_lo, const int32_t *box_hi,
                                   const double *const *U, const double *const *lam, int lam_mode);
+/* Geometric multigrid for multipatch block solvers: the hierarchy of igx_solver_set_mg_* over a chain of
+   block solvers of the same problem, the lifetime rules included.  These three calls serve solvers of
+   igx_solver_create_multipatch_block only (any other solver: IGX_ERR_UNSUPPORTED), and the scalar igx_solver_set_mg_* calls
+   refuse them (IGX_ERR_UNSUPPORTED).  igx_solver_set_precond(IGX_PRECOND_MG) selects the V-cycle once the chain below the solver
+   is complete; it needs IGX_METHOD_CG and a solver made with symmetric = 1 (else, and until then, IGX_ERR_UNSUPPORTED).
+   igx_solver_mg_info, _colours, _relax_d, _prolong_d, _restrict_d and _profile_d serve such a hierarchy on vectors of
+   ncomp * nrows entries: nrows and nfree of igx_mg_info count blocked dofs, nnz sums the present blocks, the colour lists hold
+   nodes.
+   The smoother is a coloured node-block Gauss-Seidel sweep.  A node is a scalar global dof I with its ncomp components;
+   colour[i] (host, nrows nodes; read on the nodes with a free component) such that no two coupled nodes with a free component
+   share a colour (checked against the pattern: IGX_ERR_ARG names the first pair).  A sweep relaxes colour after colour, one launch
+   per colour; every node solves its free components exactly from its ncomp x ncomp diagonal block, the fixed ones keep their
+   entry: x_F[I] = D_FF^-1 (b_F[I] - sum_{J != I} sum_q A_Fq[I,J] x_q[J] - sum_{q fixed} D_Fq x_q[I]).  A node whose elimination
+   meets a zero or non-finite pivot is left as it is.  smooth_steps (1 .. 16): sweeps before and after the coarse correction. */
+int  igx_solver_set_block_mg_smoother(igx_solver *solver, const int32_t *colour, int smooth_steps);
+/* `coarse` becomes the next level of `solver`: two block solvers with the same number of components and patches and injective
+   maps.  P and mult as in igx_solver_set_mg_coarse (those of the scalar space): every component is transferred with them on its
+   slice of the vectors, under its own mask. */
+int  igx_solver_set_block_mg_coarse(igx_solver *solver, igx_solver *coarse, const double *const *P, const double *mult);
+/* The coarsest level: inv (host, m x m row-major, m = free dofs of `solver` in the blocked numbering, ascending). */
+int  igx_solver_set_block_mg_inverse(igx_solver *solver, const double *inv, int64_t m);
 
 /* --- Parabolic problems: DIRK time stepping on the device (pyiga/solvers.py:366-473: dirk_step with constant steps) ----------
    M u' = f - K u on the free dofs, u = g on the fixed ones, u(t0) = x0; f and g constant in time.  M is the patch's mass matrix,

@@ -73,7 +73,8 @@ IGX_KRON_SUM, IGX_KRON_PRODUCT = 1, 2
 PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'kron': IGX_PRECOND_KRON}
 MP_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ,
                'mg': IGX_PRECOND_MG}
-MPVEC_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ}
+MPVEC_PRECONDS = {None: IGX_PRECOND_NONE, 'none': IGX_PRECOND_NONE, 'jacobi': IGX_PRECOND_JACOBI, 'schwarz': IGX_PRECOND_SCHWARZ,
+                  'mg': IGX_PRECOND_MG}
 IGX_METHOD_CG, IGX_METHOD_BICGSTAB, IGX_METHOD_MINRES = 0, 1, 2
 METHODS = {'cg': IGX_METHOD_CG, 'bicgstab': IGX_METHOD_BICGSTAB}
 SADDLE_METHODS = dict(METHODS, minres=IGX_METHOD_MINRES)      # (MINRES: saddle-point solvers, and only they)
@@ -308,6 +309,9 @@ SYMBOLS = [
     ('igx_solver_set_mg_smoother', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int64]),
     ('igx_solver_set_mg_coarse', C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_dp), _dp]),
     ('igx_solver_set_mg_inverse', C.c_int, [C.c_void_p, _dp, C.c_int64]),
+    ('igx_solver_set_block_mg_smoother', C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    ('igx_solver_set_block_mg_coarse', C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_dp), _dp]),
+    ('igx_solver_set_block_mg_inverse', C.c_int, [C.c_void_p, _dp, C.c_int64]),
     ('igx_solver_mg_info', C.c_int, [C.c_void_p, C.c_int, C.POINTER(MgInfo)]),
     ('igx_solver_mg_colours', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ('igx_solver_mg_profile_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MgProfile)]),

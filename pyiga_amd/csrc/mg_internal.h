@@ -16,7 +16,10 @@ struct SolverRef {
     const uint8_t *d_mask;                    // 1 on the free dofs (device), and
     const uint8_t *h_free;                    // the same on the host
     int precond, method;
-    int ncomp;                                // > 1: a multipatch block solver (no multigrid)
+    int ncomp;                                // > 1: a multipatch block solver (its hierarchy: igx_solver_set_block_mg_*)
+    long long N;                              // scalar global dofs (nodes): n / ncomp
+    const double *blk[9];                     // a block solver's block (p, q) at p * ncomp + q over the CSR pattern, or null (absent)
+    bool symmetric;                           // a block solver made as symmetric
 };
 
 // solve.hip
@@ -38,6 +41,12 @@ int mg_apply(hipStream_t st, igx_solver *s, const double *r, double *z);   // z 
 int csr_gs_sweep(hipStream_t st, int gw, int ncol, const int *coff, const int *d_coff, const int32_t *d_rows, bool one_block,
                  const int32_t *d_indptr, const int32_t *d_indices, const double *d_vals, double *x, const double *b, bool backward,
                  int *launches);
+// multigrid_block.hip: one node-block Gauss-Seidel sweep (k_csr_node_gs, one launch per colour) over the nc x nc blocks blk of a
+// multipatch block solver on the pattern of N scalar rows; d_rows lists the nodes with a free component by (colour, index),
+// d_mask is the mask over the nc * N blocked dofs.  sym: the diagonal blocks' lower triangles are taken from the upper ones.
+int csr_node_gs_sweep(hipStream_t st, int gw, int nc, int ncol, const int *coff, const int32_t *d_rows, long long N,
+                      const int32_t *d_indptr, const int32_t *d_indices, const double *const *blk, const uint8_t *d_mask, bool sym,
+                      double *x, const double *b, bool backward, int *launches);
 // k_dense_apply: x[d_idx[i]] = sum_j d_inv[i][j] b[d_idx[j]], i < m
 int dense_apply(hipStream_t st, int m, const double *d_inv, const int32_t *d_idx, const double *b, double *x);
 

@@ -13,6 +13,10 @@
 //                   local-to-global map, and stores (prolongation: shared dofs get the same value from every patch) or adds
 //                   (restriction) at its global dof.  One launch per patch, in patch order: the result is deterministic.
 //   k_dense_apply   the coarsest level: x = A_c^-1 b with the dense inverse, one block per row, fixed summation tree.
+// A multipatch block solver (a vector-valued form, nc components) hangs the same levels on the same chain
+// through igx_solver_set_block_mg_*: its smoother relaxes nodes (scalar dofs with their nc components: csr_node_gs_sweep of
+// multigrid_block.hip), its transfers are k_mg_transfer launched per patch and component on that component's slice of the
+// vectors and of the mask, its dense inverse acts on the blocked free dofs.
 // The colouring itself (igx_csr_colouring: first fit in ascending dof order) is host code and needs no device.
 #include "mg_internal.h"
 
@@ -188,11 +192,12 @@ struct MgLevel {
     // the smoother
     int ncol = 0;
     std::vector<int> coff;                    // colour c: rows coff[c] .. coff[c + 1] of d_rows
-    int32_t *d_rows = nullptr;                // free dofs sorted by (colour, index)
+    int32_t *d_rows = nullptr;                // free dofs sorted by (colour, index); a block solver: the nodes with a free component
+    long long nnode = 0;                      // entries of d_rows (a scalar solver: nfree)
     int *d_coff = nullptr;
     bool one_block = false;
     int steps = 1;
-    long long nfree = 0;
+    long long nfree = 0;                      // (a block solver: blocked free dofs)
     // the next coarser level, and the finer one that points here
     igx_solver *coarse = nullptr, *parent = nullptr;
     std::vector<Transfer> up, down;           // per patch: prolongation from / restriction to `coarse`
@@ -224,11 +229,19 @@ void drop_transfers(MgLevel *L)
 }
 
 // the level of a multipatch solver, made on first use with its work vectors
-int level_of(igx_solver *s, MgLevel **out, const char *what)
+// (block: the call is one of igx_solver_set_block_mg_*, which serve the multipatch block solvers and no other)
+int level_of(igx_solver *s, MgLevel **out, const char *what, bool block = false)
 {
     const SolverRef R = solver_ref(s);
     if (!R.mp) { set_error("%s: multigrid needs a multipatch solver", what); return IGX_ERR_UNSUPPORTED; }
-    if (R.ncomp > 1) { set_error("%s: no multigrid for multipatch block solvers (vector-valued systems)", what); return IGX_ERR_UNSUPPORTED; }
+    if (R.ncomp > 1 && !block) {
+        set_error("%s: a multipatch block solver (vector-valued system) takes its hierarchy through igx_solver_set_block_mg_*", what);
+        return IGX_ERR_UNSUPPORTED;
+    }
+    if (R.ncomp < 2 && block) {
+        set_error("%s: not a multipatch block solver (igx_solver_create_multipatch_block); a scalar one: igx_solver_set_mg_*", what);
+        return IGX_ERR_UNSUPPORTED;
+    }
     MgLevel *&L = solver_mg(s);
     if (!L) {
         IGX_HIP(hipSetDevice(R.ctx->device));
@@ -290,31 +303,37 @@ int sweep(hipStream_t st, igx_solver *s, MgLevel *L, double *x, const double *b,
 {
     const SolverRef R = solver_ref(s);
     const igx_multipatch *m = R.mp;
+    if (R.ncomp > 1)
+        return csr_node_gs_sweep(st, R.gw, R.ncomp, L->ncol, L->coff.data(), L->d_rows, R.N, m->d_indptr, m->d_indices, R.blk, R.d_mask,
+                                 R.symmetric, x, b, backward, pf ? &pf->launches : nullptr);
     return csr_gs_sweep(st, R.gw, L->ncol, L->coff.data(), L->d_coff, L->d_rows, L->one_block, m->d_indptr, m->d_indices, m->d_vals, x, b,
                         backward, pf ? &pf->launches : nullptr);
 }
 
-// rc += P^T W^-1 rf (rf zero on the fixed dofs; rc cleared first)
+// rc += P^T W^-1 rf (rf zero on the fixed dofs; rc cleared first).  A block solver: I (x) P^T, component after component on its
+// slice of the vectors and of the mask (the transfers and the multiplicities are those of the scalar space)
 int restrict_to(hipStream_t st, igx_solver *s, MgLevel *L, const double *rf, double *rc)
 {
-    const SolverRef C = solver_ref(L->coarse);
+    const SolverRef F = solver_ref(s), C = solver_ref(L->coarse);
     IGX_HIP(hipMemsetAsync(rc, 0, (size_t)C.n * sizeof(double), st));
-    for (const Transfer &T : L->down) {
-        k_mg_transfer<true><<<blocks_of(T.nout), BLOCK, 0, st>>>(T, C.d_mask, L->d_winv, rf, rc);
-        IGX_HIP(hipGetLastError());
-    }
+    for (int c = 0; c < C.ncomp; ++c)
+        for (const Transfer &T : L->down) {
+            k_mg_transfer<true><<<blocks_of(T.nout), BLOCK, 0, st>>>(T, C.d_mask + c * C.N, L->d_winv, rf + c * F.N, rc + c * C.N);
+            IGX_HIP(hipGetLastError());
+        }
     return IGX_OK;
 }
 
 // xf = P xc (xc zero on the fixed dofs)
 int prolong_from(hipStream_t st, igx_solver *s, MgLevel *L, const double *xc, double *xf)
 {
-    const SolverRef F = solver_ref(s);
+    const SolverRef F = solver_ref(s), C = solver_ref(L->coarse);
     IGX_HIP(hipMemsetAsync(xf, 0, (size_t)F.n * sizeof(double), st));
-    for (const Transfer &T : L->up) {
-        k_mg_transfer<false><<<blocks_of(T.nout), BLOCK, 0, st>>>(T, F.d_mask, nullptr, xc, xf);
-        IGX_HIP(hipGetLastError());
-    }
+    for (int c = 0; c < F.ncomp; ++c)
+        for (const Transfer &T : L->up) {
+            k_mg_transfer<false><<<blocks_of(T.nout), BLOCK, 0, st>>>(T, F.d_mask + c * F.N, nullptr, xc + c * C.N, xf + c * F.N);
+            IGX_HIP(hipGetLastError());
+        }
     return IGX_OK;
 }
 
@@ -344,7 +363,7 @@ int vcycle(hipStream_t st, igx_solver *s, const double *b, double *x, Prof *pf =
     if (int rc = mark(pf, lvl, PH_VECTOR)) return rc;
     for (int k = 0; k < L->steps; ++k)
         if (int rc = sweep(st, s, L, x, b, true, pf)) return rc;
-    if (pf) pf->launches += 2 + 2 * (int)L->up.size();          // (the residual, the transfers of every patch, the sum)
+    if (pf) pf->launches += 2 + 2 * R.ncomp * (int)L->up.size();          // (the residual, the transfers of every patch and component, the sum)
     return mark(pf, lvl, PH_SMOOTH);
 }
 
@@ -471,44 +490,57 @@ int igx_csr_colouring(int64_t n, const int32_t *indptr, const int32_t *indices, 
     return IGX_OK;
 }
 
-int igx_solver_set_mg_smoother(igx_solver *s, const int32_t *colour, int smooth_steps, int64_t block_rows)
+} // extern "C"
+
+namespace {
+
+// igx_solver_set_mg_smoother, and igx_solver_set_block_mg_smoother (block): there the colours are those of the nodes, the scalar
+// rows of the pattern, and a node is relaxed if any of its components is free
+int set_smoother(igx_solver *s, const int32_t *colour, int smooth_steps, int64_t block_rows, bool block, const char *what)
 {
-    const char *what = "igx_solver_set_mg_smoother";
     if (!s || !colour) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
     if (smooth_steps < 1 || smooth_steps > 16) { set_error("%s: smooth_steps must be 1 .. 16, not %d", what, smooth_steps); return IGX_ERR_ARG; }
     MgLevel *L = nullptr;
-    if (int rc = level_of(s, &L, what)) return rc;
+    if (int rc = level_of(s, &L, what, block)) return rc;
     const SolverRef R = solver_ref(s);
     const igx_multipatch *m = R.mp;
+    const char *dof = block ? "node" : "dof";
+    auto is_free = [&](long long i) {
+        for (int c = 0; c < R.ncomp; ++c)
+            if (R.h_free[c * R.N + i]) return true;
+        return false;
+    };
     IGX_HIP(hipSetDevice(R.ctx->device));
     hipStream_t st = R.ctx->stream;
     // the pattern, to see that no row has a neighbour of its own colour
-    std::vector<int32_t> ip((size_t)R.n + 1), ix((size_t)m->nnz);
+    std::vector<int32_t> ip((size_t)R.N + 1), ix((size_t)m->nnz);
     IGX_HIP(hipStreamSynchronize(st));
     IGX_HIP(hipMemcpy(ip.data(), m->d_indptr, ip.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (!ix.empty()) IGX_HIP(hipMemcpy(ix.data(), m->d_indices, ix.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     int ncol = 0;
-    for (long long i = 0; i < R.n; ++i) {
-        if (!R.h_free[i]) continue;
-        if (colour[i] < 0) { set_error("%s: free dof %lld has no colour", what, i); return IGX_ERR_ARG; }
+    long long nnode = 0;
+    for (long long i = 0; i < R.N; ++i) {
+        if (!is_free(i)) continue;
+        ++nnode;
+        if (colour[i] < 0) { set_error("%s: free %s %lld has no colour", what, dof, i); return IGX_ERR_ARG; }
         ncol = std::max(ncol, colour[i] + 1);
         for (long long k = ip[i]; k < ip[i + 1]; ++k) {
             const int32_t j = ix[k];
-            if (j != i && R.h_free[j] && colour[j] == colour[i]) {
-                set_error("%s: dofs %lld and %d are coupled and both have colour %d", what, i, j, colour[i]);
+            if (j != i && is_free(j) && colour[j] == colour[i]) {
+                set_error("%s: %ss %lld and %d are coupled and both have colour %d", what, dof, i, j, colour[i]);
                 return IGX_ERR_ARG;
             }
         }
     }
     std::vector<int> coff((size_t)ncol + 1, 0);
-    for (long long i = 0; i < R.n; ++i)
-        if (R.h_free[i]) ++coff[colour[i] + 1];
+    for (long long i = 0; i < R.N; ++i)
+        if (is_free(i)) ++coff[colour[i] + 1];
     for (int c = 0; c < ncol; ++c) coff[c + 1] += coff[c];
-    std::vector<int32_t> rows((size_t)L->nfree);
+    std::vector<int32_t> rows((size_t)nnode);
     {
         std::vector<int> at(coff.begin(), coff.end() - 1);
-        for (long long i = 0; i < R.n; ++i)
-            if (R.h_free[i]) rows[at[colour[i]]++] = (int32_t)i;
+        for (long long i = 0; i < R.N; ++i)
+            if (is_free(i)) rows[at[colour[i]]++] = (int32_t)i;
     }
     (void)hipFree(L->d_rows); (void)hipFree(L->d_coff);
     L->d_rows = nullptr; L->d_coff = nullptr;
@@ -518,21 +550,23 @@ int igx_solver_set_mg_smoother(igx_solver *s, const int32_t *colour, int smooth_
     IGX_HIP(hipMemcpy(L->d_coff, coff.data(), coff.size() * sizeof(int), hipMemcpyHostToDevice));
     L->ncol = ncol;
     L->coff = std::move(coff);
+    L->nnode = nnode;
     L->steps = smooth_steps;
-    L->one_block = L->nfree <= block_rows;
+    L->one_block = !block && L->nfree <= block_rows;            // (the node sweep has no one-block variant)
     return IGX_OK;
 }
 
-int igx_solver_set_mg_coarse(igx_solver *s, igx_solver *coarse, const double *const *P, const double *mult)
+// igx_solver_set_mg_coarse, and igx_solver_set_block_mg_coarse (block): P and mult are those of the scalar space
+int set_coarse(igx_solver *s, igx_solver *coarse, const double *const *P, const double *mult, bool block, const char *what)
 {
-    const char *what = "igx_solver_set_mg_coarse";
     if (!s || !coarse || !P || !mult || s == coarse) { set_error("%s: bad argument", what); return IGX_ERR_ARG; }
     MgLevel *L = nullptr, *LC = nullptr;
-    if (int rc = level_of(s, &L, what)) return rc;
-    if (int rc = level_of(coarse, &LC, what)) return rc;
+    if (int rc = level_of(s, &L, what, block)) return rc;
+    if (int rc = level_of(coarse, &LC, what, block)) return rc;
     const SolverRef F = solver_ref(s), Cc = solver_ref(coarse);
     const igx_multipatch *mf = F.mp, *mc = Cc.mp;
     if (F.ctx != Cc.ctx) { set_error("%s: the two solvers live on different contexts", what); return IGX_ERR_ARG; }
+    if (F.ncomp != Cc.ncomp) { set_error("%s: %d fine and %d coarse components", what, F.ncomp, Cc.ncomp); return IGX_ERR_ARG; }
     if (!mf->injective || !mc->injective) {
         set_error("%s: a local-to-global map is not injective (two dofs of one patch share a global dof): the transfers need "
                   "injective maps", what);
@@ -542,7 +576,7 @@ int igx_solver_set_mg_coarse(igx_solver *s, igx_solver *coarse, const double *co
     if (LC->parent && LC->parent != s) { set_error("%s: the coarse solver is the next level of another solver already", what); return IGX_ERR_ARG; }
     for (igx_solver *c = coarse; c; c = solver_mg(c) ? solver_mg(c)->coarse : nullptr)
         if (c == s) { set_error("%s: the hierarchy would contain a cycle", what); return IGX_ERR_ARG; }
-    for (long long i = 0; i < F.n; ++i)
+    for (long long i = 0; i < F.N; ++i)
         if (!(mult[i] >= 1.0)) { set_error("%s: multiplicity %g of dof %lld", what, mult[i], i); return IGX_ERR_ARG; }
     // the bands of every patch and axis: [P rows | P columns], 2D patches get a one-dof outer axis
     std::vector<int> bi;
@@ -569,8 +603,8 @@ int igx_solver_set_mg_coarse(igx_solver *s, igx_solver *coarse, const double *co
                 bv.insert(bv.end(), v.begin(), v.end());
             }
     }
-    std::vector<double> winv((size_t)F.n);
-    for (long long i = 0; i < F.n; ++i) winv[i] = 1.0 / mult[i];
+    std::vector<double> winv((size_t)F.N);
+    for (long long i = 0; i < F.N; ++i) winv[i] = 1.0 / mult[i];
     IGX_HIP(hipSetDevice(F.ctx->device));
     IGX_HIP(hipStreamSynchronize(F.ctx->stream));
     if (L->coarse && L->coarse != coarse && solver_mg(L->coarse)) solver_mg(L->coarse)->parent = nullptr;
@@ -603,12 +637,12 @@ int igx_solver_set_mg_coarse(igx_solver *s, igx_solver *coarse, const double *co
     return IGX_OK;
 }
 
-int igx_solver_set_mg_inverse(igx_solver *s, const double *inv, int64_t m)
+// igx_solver_set_mg_inverse, and igx_solver_set_block_mg_inverse (block): there the free dofs are blocked, ascending
+int set_inverse(igx_solver *s, const double *inv, int64_t m, bool block, const char *what)
 {
-    const char *what = "igx_solver_set_mg_inverse";
     if (!s || (!inv && m > 0)) { set_error("%s: null argument", what); return IGX_ERR_ARG; }
     MgLevel *L = nullptr;
-    if (int rc = level_of(s, &L, what)) return rc;
+    if (int rc = level_of(s, &L, what, block)) return rc;
     if (m != L->nfree) { set_error("%s: the inverse has %lld rows, the level %lld free dofs", what, (long long)m, L->nfree); return IGX_ERR_ARG; }
     if (m > 8192) { set_error("%s: %lld free dofs are too many for a dense inverse", what, (long long)m); return IGX_ERR_UNSUPPORTED; }
     const SolverRef R = solver_ref(s);
@@ -629,6 +663,40 @@ int igx_solver_set_mg_inverse(igx_solver *s, const double *inv, int64_t m)
     return IGX_OK;
 }
 
+} // namespace
+
+extern "C" {
+
+int igx_solver_set_mg_smoother(igx_solver *s, const int32_t *colour, int smooth_steps, int64_t block_rows)
+{
+    return set_smoother(s, colour, smooth_steps, block_rows, false, "igx_solver_set_mg_smoother");
+}
+
+int igx_solver_set_mg_coarse(igx_solver *s, igx_solver *coarse, const double *const *P, const double *mult)
+{
+    return set_coarse(s, coarse, P, mult, false, "igx_solver_set_mg_coarse");
+}
+
+int igx_solver_set_mg_inverse(igx_solver *s, const double *inv, int64_t m)
+{
+    return set_inverse(s, inv, m, false, "igx_solver_set_mg_inverse");
+}
+
+int igx_solver_set_block_mg_smoother(igx_solver *s, const int32_t *colour, int smooth_steps)
+{
+    return set_smoother(s, colour, smooth_steps, 0, true, "igx_solver_set_block_mg_smoother");
+}
+
+int igx_solver_set_block_mg_coarse(igx_solver *s, igx_solver *coarse, const double *const *P, const double *mult)
+{
+    return set_coarse(s, coarse, P, mult, true, "igx_solver_set_block_mg_coarse");
+}
+
+int igx_solver_set_block_mg_inverse(igx_solver *s, const double *inv, int64_t m)
+{
+    return set_inverse(s, inv, m, true, "igx_solver_set_block_mg_inverse");
+}
+
 int igx_solver_mg_info(igx_solver *s, int level, igx_mg_info *out)
 {
     const char *what = "igx_solver_mg_info";
@@ -641,6 +709,11 @@ int igx_solver_mg_info(igx_solver *s, int level, igx_mg_info *out)
     out->nrows = R.n;
     out->nfree = L->nfree;
     out->nnz = R.mp->nnz;
+    if (R.ncomp > 1) {                            // (the present blocks, each over the whole pattern)
+        int present = 0;
+        for (int k = 0; k < R.ncomp * R.ncomp; ++k) present += R.blk[k] ? 1 : 0;
+        out->nnz *= present;
+    }
     out->ncolours = L->ncol;
     out->one_block = L->one_block ? 1 : 0;
     out->smooth_steps = L->steps;
@@ -660,7 +733,7 @@ int igx_solver_mg_colours(igx_solver *s, int level, int32_t *rows, int32_t *colo
     const SolverRef R = solver_ref(c);
     IGX_HIP(hipSetDevice(R.ctx->device));
     IGX_HIP(hipStreamSynchronize(R.ctx->stream));
-    if (L->nfree > 0) IGX_HIP(hipMemcpy(rows, L->d_rows, (size_t)L->nfree * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (L->nnode > 0) IGX_HIP(hipMemcpy(rows, L->d_rows, (size_t)L->nnode * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int k = 0; k <= L->ncol; ++k) colour_offsets[k] = L->coff[k];
     return IGX_OK;
 }

@@ -977,7 +977,7 @@ int check_values(const igx_solver *s, const char *what)
                           s->mp ? "igx_solver_take_multipatch_block" : "igx_solver_take_block");
                 return IGX_ERR_ARG;
             }
-        return IGX_OK;
+        return s->mp && s->precond == IGX_PRECOND_MG ? mg_check(s, what) : IGX_OK;
     }
     if (s->mp) {
         if (s->mp->generation != s->gen) {
@@ -1476,7 +1476,10 @@ int box_fastdiag_setup(igx_solver *s, long long base, const int32_t *box_lo, con
 // what multigrid.hip sees of a solver (mg_internal.h)
 SolverRef solver_ref(const igx_solver *s)
 {
-    return SolverRef{s->ctx, s->mp, s->n, s->gw, s->d_mask, s->h_free.data(), s->precond, s->method, s->ncomp};
+    SolverRef R{s->ctx, s->mp, s->n, s->gw, s->d_mask, s->h_free.data(), s->precond, s->method, s->ncomp, s->n / s->ncomp, {}, s->symmetric};
+    if (s->mp && s->ncomp > 1)
+        for (int k = 0; k < s->ncomp * s->ncomp; ++k) R.blk[k] = s->block.blk[k];
+    return R;
 }
 
 int refuse_multipatch_block(const igx_solver *s, const char *what)
@@ -1484,7 +1487,7 @@ int refuse_multipatch_block(const igx_solver *s, const char *what)
     if (s && s->saddle) return refuse_saddle(s, what);           // (what a multipatch block solver does not serve, a saddle solver does not either)
     if (!s || !s->mp || s->ncomp < 2) return IGX_OK;
     set_error("%s: a multipatch block solver (igx_solver_create_multipatch_block) serves the linear solves, the SpMV and its "
-              "Jacobi and Schwarz preconditioners only", what);
+              "Jacobi, Schwarz and multigrid (igx_solver_set_block_mg_*) preconditioners only", what);
     return IGX_ERR_UNSUPPORTED;
 }
 
@@ -1498,6 +1501,15 @@ void solver_drop_mg_precond(igx_solver *s)
 int solver_check_sums(const igx_solver *s, const char *what)
 {
     if (!s->mp) { set_error("%s: a multigrid level needs a multipatch solver", what); return IGX_ERR_UNSUPPORTED; }
+    if (s->ncomp > 1) {                       // (a block solver owns its blocks: the sums may restart, the diagonal blocks must be there)
+        for (int c = 0; c < s->ncomp; ++c)
+            if (!s->block.blk[c * s->ncomp + c]) {
+                set_error("%s: diagonal block (%d, %d) of a level of the multigrid hierarchy is missing (igx_solver_take_multipatch_block)",
+                          what, c, c);
+                return IGX_ERR_ARG;
+            }
+        return IGX_OK;
+    }
     if (s->mp->generation != s->gen) {
         set_error("%s: the sums of a multipatch of the multigrid hierarchy were restarted (igx_multipatch_zero) since its solver was "
                   "made: make the solvers again", what);
@@ -1818,8 +1830,16 @@ int igx_solver_set_precond(igx_solver *s, int precond, const int32_t *box_lo, co
         s->precond = precond;
         return IGX_OK;
     }
+    if (precond == IGX_PRECOND_MG && s->mp && s->ncomp > 1) {    // the hierarchy of igx_solver_set_block_mg_*, once it is complete
+        if (!s->symmetric || s->method != IGX_METHOD_CG) {
+            set_error("igx_solver_set_precond: the multigrid preconditioner serves CG on a block solver made as symmetric only");
+            return IGX_ERR_UNSUPPORTED;
+        }
+        if (mg_check(s, "igx_solver_set_precond(IGX_PRECOND_MG)")) return IGX_ERR_UNSUPPORTED;     // (mg_check's message stands)
+        s->precond = precond;
+        return IGX_OK;
+    }
     if (precond == IGX_PRECOND_MG) {
-        if (int rc = refuse_multipatch_block(s, "igx_solver_set_precond(IGX_PRECOND_MG)")) return rc;
         if (!s->mp) { set_error("igx_solver_set_precond: the multigrid preconditioner needs a multipatch solver"); return IGX_ERR_UNSUPPORTED; }
         if (s->method != IGX_METHOD_CG) { set_error("igx_solver_set_precond: the multigrid preconditioner serves CG only"); return IGX_ERR_UNSUPPORTED; }
         if (int rc = mg_check(s, "igx_solver_set_precond")) return rc;

@@ -1587,7 +1587,8 @@ class MultipatchVectorSystem(_DeviceSystem):
     `method`: 'auto' is CG when the coefficient tables of every patch are symmetric (``symmetric``), else BiCGStab; 'cg' on a
     non-symmetric form raises ValueError.  `rhs`: a linear form string in the test function, a vector of ``nc * numdofs``
     entries, or a scalar.  `bcs`: ``(indices, values)`` in the blocked numbering, as ``MP.compute_dirichlet_bcs`` gives them for
-    a vector-valued ``dir_func``.
+    a vector-valued ``dir_func``.  Preconditioners: 'jacobi' (the default), 'schwarz', and 'mg' after ``set_multigrid()``
+    (DESIGN.md section 37).
 
     Constructing the system restarts the sums of `MP`: a ``MultipatchSystem`` made over them before goes stale (its solves
     raise), as after ``MP.assemble_system``.  The system owns copies of its blocks, so a later ``MP.assemble_system`` does not
@@ -1596,6 +1597,7 @@ class MultipatchVectorSystem(_DeviceSystem):
 
     PRECONDS = _lib.MPVEC_PRECONDS
     FACTORED = 'schwarz'
+    _mg = None                                # the hierarchy of set_multigrid(): systems (this one first), smooth_steps, info
 
     def __init__(self, MP, problem, rhs, bcs=None, bfuns=None, args=None, method='auto', **kwargs):
         if method != 'auto':
@@ -1603,6 +1605,7 @@ class MultipatchVectorSystem(_DeviceSystem):
         self.MP = MP
         args = dict(args or {})
         args.update(kwargs)
+        self._problem = (problem, bfuns, dict(args))
         nc, asms, args = MP._vector_assemblers(problem, bfuns, args, 'MultipatchVectorSystem')
         try:
             self.ncomp = nc
@@ -1629,14 +1632,171 @@ class MultipatchVectorSystem(_DeviceSystem):
                 a.patch.close()
 
     def _drop_owner(self):
+        self._drop_multigrid()
         MP = getattr(self, 'MP', None)
         if MP is not None:
             MP._solvers.discard(self)
 
     def set_precond(self, precond):
-        if precond in ('mg', 'kron'):
-            raise ValueError('MultipatchVectorSystem has no %r preconditioner: \'jacobi\', \'schwarz\' or None' % (precond,))
+        if precond == 'kron':
+            raise ValueError('MultipatchVectorSystem has no %r preconditioner: \'jacobi\', \'schwarz\', \'mg\' or None' % (precond,))
+        if precond == 'mg':
+            if self.method != 'cg':
+                raise ValueError("precond='mg' serves method='cg' only")
+            self._live()
+            if self._mg is None:
+                raise ValueError("MultipatchVectorSystem: precond='mg' needs a hierarchy: call set_multigrid() first (it assembles "
+                                 'every block again on every coarse level, so it is not done behind a solve)')
         _DeviceSystem.set_precond(self, precond)
+
+    # -- geometric multigrid: the hierarchy handling of MultipatchSystem on blocked vectors
+    _drop_multigrid = MultipatchSystem._drop_multigrid
+    set_method = MultipatchSystem.set_method
+    _mg_level = MultipatchSystem._mg_level
+    mg_level = MultipatchSystem.mg_level
+    mg_info = MultipatchSystem.mg_info
+    mg_profile = MultipatchSystem.mg_profile
+    relax = MultipatchSystem.relax
+    _transfer = MultipatchSystem._transfer
+    prolong = MultipatchSystem.prolong
+    restrict = MultipatchSystem.restrict
+
+    def _component_fixed(self, c):
+        """The fixed dofs of component `c` in the scalar numbering."""
+        idx = self.bc_indices
+        return idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N
+
+    def _node_free(self):
+        """Per node (scalar global dof): whether any of its components is free."""
+        free = np.ones(self.n, dtype=bool)
+        free[self.bc_indices] = False
+        return free.reshape(self.ncomp, self.N).any(axis=0)
+
+    def _set_smoother(self, smooth_steps):
+        """Colours the nodes with a free component (first fit on the scalar pattern) and hands the colours to the device; returns
+        this level's entry of ``mg_info``."""
+        indptr, indices = self.MP.pattern()
+        nodes = self._node_free()
+        colour, ncol = first_fit_colouring(indptr, indices, nodes.astype(np.uint8))
+        _lib.check(_lib.load().igx_solver_set_block_mg_smoother(self._live(), colour.ctypes.data_as(C.POINTER(C.c_int32)), int(smooth_steps)),
+                   'igx_solver_set_block_mg_smoother')
+        return dict(spans=[tuple(kv.numspans for kv in kvs) for kvs, _ in self.MP.patches], dofs=self.n,
+                    free=int(self.n - self.bc_indices.size), nnz=int(indices.size) * sum(sum(row) for row in self.present),
+                    colours=ncol, nodes=int(nodes.sum()))
+
+    def set_multigrid(self, levels=None, coarse=None, smooth_steps=1, coarse_max=2048):
+        """Sets up the hierarchy of ``precond='mg'``, as ``MultipatchSystem.set_multigrid`` does: a V-cycle with `smooth_steps`
+        coloured node-block Gauss-Seidel sweeps before (forward) and after (backward) the coarse correction -- every node, a scalar
+        dof with its ``nc`` components, solves its free components exactly from its ``nc x nc`` diagonal block --, the transfers
+        of the scalar space applied per component, the coarsest level solved with a dense inverse.
+
+        Every patch's knot vectors are coarsened with :func:`coarsen_knots` and the joins replayed, level after level, until there
+        are `levels` of them (the finest included), a knot vector cannot be coarsened, or a level has at most `coarse_max` free
+        dofs (blocked: all components); `coarse`: the coarser multipatches ``[MP1, MP2, ...]`` instead.  Every coarse level is a
+        ``MultipatchVectorSystem`` of the same form with a zero right-hand side and the same patch sides fixed per component,
+        assembled on the device (``nc^2`` blocks per patch and level: the set-up is an explicit call); the system owns the coarse
+        levels and closes them with itself.  ValueError if the fixed dofs of a component are not a union of whole patch sides
+        (the sides may differ between components), if a local-to-global map is not injective, with ``method='bicgstab'`` or a
+        non-symmetric form, or if the coarsest level keeps more than `coarse_max` free dofs."""
+        from . import bspline
+        from .multipatch import slice_indices
+        if self.method != 'cg' or not self.symmetric:
+            raise ValueError("precond='mg' serves method='cg' on a symmetric form only")
+        self._live()
+        MP = self.MP
+        if not MP.injective:
+            raise ValueError('the multigrid preconditioner needs injective local-to-global maps (two dofs of one patch share a '
+                             'global dof)')
+        smooth_steps = int(smooth_steps)
+        if not 1 <= smooth_steps <= 16:
+            raise ValueError('smooth_steps must be 1 .. 16')
+        if levels is not None and int(levels) < 1:
+            raise ValueError('levels must be >= 1')
+        nc = self.ncomp
+        maps0 = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
+        kvs0 = [kvs for kvs, _ in MP.patches]
+        sides = []
+        for c in range(nc):
+            try:
+                sides.append(fixed_sides(kvs0, maps0, self._component_fixed(c)))
+            except ValueError as e:
+                raise ValueError('component %d: %s' % (c, e)) from None
+        self._drop_multigrid()
+        lib = _lib.load()
+        problem, bfuns, args = self._problem
+        systems, keep = [self], []
+        try:
+            given = None if coarse is None else list(coarse)
+            while True:
+                S = systems[-1]
+                nfree = S.n - S.bc_indices.size
+                if given is not None:
+                    if not given:
+                        break
+                    MPc = given.pop(0)
+                    if MPc.numpatches != MP.numpatches:
+                        raise ValueError('a coarse multipatch has %d patches, the system %d' % (MPc.numpatches, MP.numpatches))
+                else:
+                    if (levels is not None and len(systems) >= int(levels)) or (levels is None and nfree <= coarse_max):
+                        break
+                    try:
+                        patches = [(tuple(coarsen_knots(kv) for kv in kvs), geo) for kvs, geo in S.MP.patches]
+                    except ValueError:
+                        break
+                    MPc = MP.replay_joins(patches)
+                Nc = MPc.numdofs
+                fixed = [c * Nc + MPc.patch_to_global_idx(p)[slice_indices(ax, 0 if side == 0 else -1,
+                                                                           tuple(kv.numdofs for kv in MPc.patches[p][0]), ravel=True)]
+                         for c in range(nc) for p, ax, side in sides[c]]
+                fixed = np.unique(np.concatenate(fixed)) if fixed else np.zeros(0, dtype=np.int64)
+                try:
+                    Sc = MultipatchVectorSystem(MPc, problem, 0.0, (fixed, np.zeros(fixed.size)), bfuns=bfuns, args=args, method='cg')
+                except Exception:
+                    MPc.close()
+                    raise
+                systems.append(Sc)
+            coarsest = systems[-1]
+            m = coarsest.n - coarsest.bc_indices.size
+            if m > coarse_max:
+                raise ValueError('the coarsest level keeps %d free dofs, more than coarse_max = %d' % (m, coarse_max))
+            info = [S._set_smoother(smooth_steps) for S in systems]
+            for F, Cs in zip(systems[:-1], systems[1:]):
+                np_ = MP.numpatches
+                Ps = []
+                for (kf, _), (kc, _) in zip(F.MP.patches, Cs.MP.patches):
+                    Ps += [np.ascontiguousarray(bspline.prolongation(c, f).toarray()) for c, f in zip(kc, kf)] + [None] * (3 - len(kf))
+                keep.append(Ps)
+                mult = np.zeros(F.N)
+                for p in range(np_):
+                    mult += np.bincount(F.MP.patch_to_global_idx(p), minlength=F.N)
+                Pp = (_lib._dp * (3 * np_))(*[None if a is None else _lib.dptr(a) for a in Ps])
+                _lib.check(lib.igx_solver_set_block_mg_coarse(F._live(), Cs._live(), Pp, _lib.dptr(mult)), 'igx_solver_set_block_mg_coarse')
+            # the coarsest matrix on its blocked free dofs, inverted on the host
+            A = coarsest.matrix()
+            fr = np.setdiff1d(np.arange(coarsest.n), coarsest.bc_indices)
+            inv = scipy.linalg.inv(A[fr][:, fr].toarray()) if fr.size else np.zeros((0, 0))
+            inv = np.ascontiguousarray(0.5 * (inv + inv.T))
+            _lib.check(lib.igx_solver_set_block_mg_inverse(coarsest._live(), _lib.dptr(inv), fr.size), 'igx_solver_set_block_mg_inverse')
+        except Exception:
+            for S in systems[1:]:
+                S.close()
+                S.MP.close()
+            raise
+        self._mg = dict(systems=systems, smooth_steps=smooth_steps, info=info)
+        if self._precond == 'mg':
+            self._precond = None                  # (the device dropped it when the hierarchy changed)
+        return self
+
+    def mg_colour_order(self, level=0):
+        """The nodes of `level` with a free component in the order the smoother's forward sweep relaxes them: sorted by
+        (colour, index)."""
+        self._mg_level(level)
+        inf = self._mg['info'][int(level)]
+        rows = np.empty(inf['nodes'], dtype=np.int32)
+        offs = np.empty(inf['colours'] + 1, dtype=np.int32)
+        _lib.check(_lib.load().igx_solver_mg_colours(self._live(), int(level), rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     offs.ctypes.data_as(C.POINTER(C.c_int32))), 'igx_solver_mg_colours')
+        return rows.astype(np.int64)
 
     def schwarz_setup(self):
         """Per component ``(boxes, U, lam, mode)`` of the block-diagonal Schwarz preconditioner (host set-up): the boxes of
@@ -1689,8 +1849,14 @@ class MultipatchVectorSystem(_DeviceSystem):
         """CG or BiCGStab (``method``) to ``||r|| <= tol * ||R (b - A ext(g))||``; returns the blocked global solution vector of
         ``nc * numdofs`` entries (the Dirichlet values included).  `precond`: 'jacobi' (the diagonals of the diagonal blocks),
         'schwarz' (per component the additive Schwarz preconditioner of ``MultipatchSystem``: one fast-diagonalization solve of
-        the Laplacian per patch and component) or None; 'mg' and 'kron' raise ValueError."""
-        return self._solve(self.b, tol, maxiter, precond, x0, check_every, timed)
+        the Laplacian per patch and component), 'mg' (CG only: one V-cycle of the hierarchy of ``set_multigrid()``, which must
+        have been called -- ValueError otherwise; ``info`` then has ``levels`` and ``smooth_steps``) or None; 'kron' raises
+        ValueError.  'mg' takes a few tens of iterations where Jacobi takes hundreds to thousands, each of them a V-cycle of a few
+        hundred short launches."""
+        u = self._solve(self.b, tol, maxiter, precond, x0, check_every, timed)
+        if precond == 'mg':
+            self.info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
+        return u
 
 
 ################################################################################
