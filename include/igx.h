@@ -148,6 +148,7 @@ typedef struct {
 #define IGX_PATH_BOTH   32   /* the fused stage wrote both triangles of a symmetric form itself (k_bf3): no mirror pass; timing.stage1_ms = k_bf3 */
 #define IGX_PATH_BF3    64   /* the fused stage ran as k_bf3 (fused3.hip: entry rings per line, store duty on the sweeper waves) */
 #define IGX_PATH_TWIN  128   /* repeated knots on the last axis: the chain ran on the patch with mid and last axis exchanged, k_bf3 stored to this patch's layout */
+#define IGX_PATH_GEOA_ROT 256 /* k_geoA's pair-product sweep kept its pair window in place and rotated the register names (single interior knots on axis 0) */
 #define IGX_PATH_KRON   16   /* separable geometry: 2D matrices of the cross-section expanded by k_kron3 (igx_assemble_kron3): timing.final_ms */
 
 int         igx_version(void);

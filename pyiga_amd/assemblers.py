@@ -317,6 +317,11 @@ class DevicePatch:
         bits = _lib.load().igx_patch_last_path(self.handle)
         return {name for bit, name in ((1, 'geoA'), (2, 'fused'), (4, 'mirror'), (8, 'single'), (16, 'kron'), (32, 'both'), (64, 'bf3'), (128, 'twin')) if bits & bit}
 
+    def geoa_rotated(self):
+        """Whether k_geoA's pair-product sweep of the last sum-factorised assembly kept its pair window in place and rotated the
+        register names (single interior knots on axis 0; include/igx.h IGX_PATH_GEOA_ROT) instead of moving the window."""
+        return bool(_lib.load().igx_patch_last_path(self.handle) & 256)
+
     def fields_plan(self, kind):
         """The kernel that forms the quadrature fields of `kind` (igx_patch_fields_plan; nothing is launched):
         {'lines': line-wise or point-wise, 'lpb': lines per block, 'lds': bytes of LDS, 'nc': control-net components}."""

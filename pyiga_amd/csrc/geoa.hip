@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <algorithm>
+#include <type_traits>
 #include "geo_device.h"
 
 namespace igx {
@@ -80,6 +81,9 @@ struct GeoAArgs {
     // and 2).  On a DIAGONAL pair (i0 = j0) its slice is the other member's, bit for bit -- one product V_a V_a per plane, the
     // same planes in the same order -- and k_bf3 reads it there: the slice is not written
     int nodiag[GA_MAXS];
+    // pair-product sweep: every span end of axis 0 but the last of the axis retires ONE function (single interior knots) -- the pair
+    // window rotates in register names instead of moving (win_acc); 0: the moving form (the window shifts by a knot's multiplicity)
+    int rot;
 };
 constexpr int GA_NFT = 13;      // fields of a point a table form may keep in LDS: ten for a symmetric table with every entry, thirteen for
                                 // reaction + convection both ways + a symmetric diffusion block (sumfact.hip: form_table_plan)
@@ -95,6 +99,9 @@ typedef int int8v __attribute__((ext_vector_type(8)));
 
 // Diagnostic build (-DIGX_GA_STAMP, never the shipped library): shader cycles per wave in the sections of the loop
 #ifdef IGX_GA_STAMP
+#ifdef GEOA_SYM_TU
+extern
+#endif
 __device__ unsigned long long g_ga_stamp[2048 * 8 * 6];
 #define GA_T(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); st_[i] += n_ - st_t; st_t = n_; } while (0)
 #else
@@ -108,16 +115,35 @@ __device__ __forceinline__ void fmac_rowbc(double &acc, const double pv, const d
 {
     asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(pv), "v"(bv), "n"(M));
 }
-// pair m = a (a + 1) / 2 + b (b <= a) of the lower triangle <-> accumulator acc[a][b]
-template <int P, int A_ = 0, int B_ = 0>
+// Rotating window (phase PH): the functions of the window keep the accumulators of their residue mod P for as long as they are
+// active -- the local functions a >= b of a span are the residues (PH + a) % P and (PH + b) % P, their pair owns acc[larger][smaller]
+// (two active functions never share a residue, so an unordered pair of residues names one live pair).  When the first function
+// leaves, the next one enters on ITS residue: nothing moves, the phase advances by one.  PH = 0 is the plain naming acc[a][b].
+template <int P, int PH>
+__device__ __forceinline__ double &win_acc(double (&acc)[P][P], const int a, const int b)
+{
+    const int r = (PH + a) % P, c = (PH + b) % P;
+    return acc[r > c ? r : c][r > c ? c : r];
+}
+// pair m = a (a + 1) / 2 + b (b <= a) of the lower triangle <-> accumulator win_acc<P, PH>(a, b)
+template <int P, int A_ = 0, int B_ = 0, int PH = 0>
 __device__ __forceinline__ void sweep_lower_rowbc(double (&acc)[P][P], const double (&pv)[(P * (P + 1) / 2 + 15) / 16], const double bv)
 {
     if constexpr (A_ < P) {
         constexpr int m = A_ * (A_ + 1) / 2 + B_;
-        fmac_rowbc<(m & 15)>(acc[A_][B_], pv[m >> 4], bv);
-        if constexpr (B_ < A_) sweep_lower_rowbc<P, A_, B_ + 1>(acc, pv, bv);
-        else sweep_lower_rowbc<P, A_ + 1, 0>(acc, pv, bv);
+        fmac_rowbc<(m & 15)>(win_acc<P, PH>(acc, A_, B_), pv[m >> 4], bv);
+        if constexpr (B_ < A_) sweep_lower_rowbc<P, A_, B_ + 1, PH>(acc, pv, bv);
+        else sweep_lower_rowbc<P, A_ + 1, 0, PH>(acc, pv, bv);
     }
+}
+// f(std::integral_constant<int, phase>): the phase of a rotating window as a compile-time value (phase in [0, P))
+template <int P, int PH = 0, class F>
+__device__ __forceinline__ bool with_phase(const int phase, F &&f)
+{
+    if constexpr (PH + 1 < P) {
+        if (phase != PH) return with_phase<P, PH + 1>(phase, f);
+    }
+    return f(std::integral_constant<int, PH>{});
 }
 
 // the full window of a non-symmetric form: pair m = a P + b <-> acc[a][b], products in NPV registers of 16 pairs each
@@ -147,6 +173,7 @@ __device__ __forceinline__ void sweep_full_rowbc(double (&acc)[P][P], const doub
 constexpr int GA_REC = 42;
 constexpr int GA_ROWS = 16;
 
+#ifndef GEOA_SYM_TU
 __global__ void k_geoa_table(const double *V0s, int P, const double *V0g, const int *fa0g, int P0G, const double *w0, int q,
                              const int *step_ptr, const int *steps, int G0, double *tab, const int *rows, int nonsym)
 {
@@ -184,6 +211,7 @@ __global__ void k_geoa_table(const double *V0s, int P, const double *V0g, const 
         }
     }
 }
+#endif
 
 // Uniform tables (sweep coefficients, axis-0 geometry basis, flush records) are NOT read with scalar loads inside the loop:
 // the scalar cache holds 16 KB, the tables are larger, and a scalar load that misses it queues in the L2 behind the K1
@@ -1125,67 +1153,161 @@ k_geoA(const GeoAArgs A)
         products(0, 0);
         __syncthreads();
         GA_T(0);
-        int it = 0, l = 0, sp = s_begin, rs = 0;
-        for (int gb = g_begin; gb < g_end; gb += NS, ++it) {
-            const int buf = it & 1;
-            const int rn = rs == 2 ? 0 : rs + 1, ra = rn == 2 ? 0 : rn + 1;
-            stage_load(gb + 2 * NS);
-            double pv[1] = {pw[(buf * NS) * 64]};
-            double bv = FLD(buf, 0, fi, lane);
+        // The batches, in the two forms of a span end.  Moving form (ROT = false): the window shifts by one function per flush step
+        // -- any number of steps per span end (repeated knots).  Rotating form (A.rot, decided on the host for the whole axis): one
+        // function leaves at a span end and the window rotates in register names (win_acc); its phase is a scalar that lives across
+        // the batches, and a plane's code exists once per phase -- a plane that ends no span runs on into the next plane of its
+        // phase, a span end jumps to the next phase's.  The products, their order per accumulator and the stored values are the
+        // moving form's: the same bits.
+        auto batches = [&](auto rotc) __attribute__((always_inline)) {
+            constexpr bool ROT = decltype(rotc)::value;
+            int it = 0, l = 0, sp = s_begin, rs = 0, phase = 0;
+            for (int gb = g_begin; gb < g_end; gb += NS, ++it) {
+                const int buf = it & 1;
+                const int rn = rs == 2 ? 0 : rs + 1, ra = rn == 2 ? 0 : rn + 1;
+                stage_load(gb + 2 * NS);
+                // (the batch's operands through two addresses formed here: a plane is a constant offset from them in every copy
+                // of the plane's code)
+                const double *const pwb = pw + (buf * NS) * 64, *const fb = &FLD(buf, 0, fi, lane);
+                double pv[1] = {pwb[0]};
+                double bv = fb[0];
+                // plane j of the batch with the window at phase PH (moving form: always 0)
+                auto sweep_plane = [&](auto phc, const int j) __attribute__((always_inline)) {
+                    constexpr int PH = decltype(phc)::value;
+                    // the operands of the next plane are requested before this plane's arithmetic
+                    const int jn = j + 1 < NS ? j + 1 : j;
+                    const double pvn = pwb[jn * 64], bvn = fb[jn * FST];
+                    asm volatile("" ::: "memory");
+                    if (!GA_OFF(4)) sweep_lower_rowbc<P, 0, 0, PH>(acc, pv, bv);
+                    else acc[0][0] += pv[0] + bv;
 #pragma unroll
-            for (int j = 0; j < NS; ++j) {
-                if (gb + j >= g_end || !live) break;
-                // the operands of the next plane are requested before this plane's arithmetic
-                const int jn = j + 1 < NS ? j + 1 : j;
-                const double pvn = pw[(buf * NS + jn) * 64], bvn = FLD(buf, jn, fi, lane);
-                asm volatile("" ::: "memory");
-                if (!GA_OFF(4)) sweep_lower_rowbc<P>(acc, pv, bv);
-                else acc[0][0] += pv[0] + bv;
+                    for (int a = 0; a < P; ++a)
 #pragma unroll
-                for (int a = 0; a < P; ++a)
-#pragma unroll
-                    for (int b = 0; b <= a; ++b) asm volatile("" : "+v"(acc[a][b]));
-                asm volatile("" ::: "memory");
-                pv[0] = pvn; bv = bvn;
-                GA_T(1);
-                if (++l < q) continue;
-                const bool write = sp >= own_lo && !GA_OFF(2);
-                const int *fr = (const int *)&rec[rs][j][20];
-                const int nst = __builtin_amdgcn_readfirstlane(fr[0]), st0 = __builtin_amdgcn_readfirstlane(fr[1]);
-                for (int st = st0; st < st0 + nst; ++st) {
-                    int pr[P];
-                    if (st == st0) {
+                        for (int b = 0; b <= a; ++b) asm volatile("" : "+v"(acc[a][b]));
+                    asm volatile("" ::: "memory");
+                    pv[0] = pvn; bv = bvn;
+                    GA_T(1);
+                };
+                // ... was the last of its span: the complete pairs go out
+                auto span_end = [&](auto phc, const int j) __attribute__((always_inline)) {
+                    constexpr int PH = decltype(phc)::value;
+                    const bool write = sp >= own_lo && !GA_OFF(2);
+                    const int *fr = (const int *)&rec[rs][j][20];
+                    if constexpr (ROT) {
+                        // (the one step of the span end: pair a is (d + a, d), the column of the leaving function; the function that
+                        // enters takes its residue, so its pairs start in the registers that were just stored.  The further steps of
+                        // the axis' last span follow the loop)
+                        int pr[P];
 #pragma unroll
                         for (int a = 0; a < P; ++a) pr[a] = __builtin_amdgcn_readfirstlane(fr[2 + a]);
-                    } else {                              // (several dofs leave at the end of the axis)
-                        const int8v rec8 = *(const int8v __attribute__((address_space(4))) *)((cip)A.steps + (size_t)st * 8);
+                        if (pr[0] >= 0 && write) k1s.store_diag(out, pr[0], A.stride, win_acc<P, PH>(acc, 0, 0));
 #pragma unroll
-                        for (int a = 0; a < P; ++a) pr[a] = rec8[a];
+                        for (int a = 1; a < P; ++a)
+                            if (pr[a] >= 0 && write) k1s.store(out, pr[a], A.stride, win_acc<P, PH>(acc, a, 0));
+#pragma unroll
+                        for (int a = 0; a < P; ++a) win_acc<P, PH>(acc, a, 0) = 0.0;
+                    } else {
+                        const int nst = __builtin_amdgcn_readfirstlane(fr[0]), st0 = __builtin_amdgcn_readfirstlane(fr[1]);
+                        for (int st = st0; st < st0 + nst; ++st) {
+                            int pr[P];
+                            if (st == st0) {
+#pragma unroll
+                                for (int a = 0; a < P; ++a) pr[a] = __builtin_amdgcn_readfirstlane(fr[2 + a]);
+                            } else {                          // (several dofs leave: repeated knots, the end of the axis)
+                                const int8v rec8 = *(const int8v __attribute__((address_space(4))) *)((cip)A.steps + (size_t)st * 8);
+#pragma unroll
+                                for (int a = 0; a < P; ++a) pr[a] = rec8[a];
+                            }
+                            // (pair a of the step is (d + a, d): a = 0 is the diagonal pair, which the second member of a couple skips)
+                            if (pr[0] >= 0 && write) k1s.store_diag(out, pr[0], A.stride, acc[0][0]);
+#pragma unroll
+                            for (int a = 1; a < P; ++a)
+                                if (pr[a] >= 0 && write) k1s.store(out, pr[a], A.stride, acc[a][0]);
+#pragma unroll
+                            for (int a = 0; a < P - 1; ++a)
+#pragma unroll
+                                for (int b = 0; b <= a; ++b) acc[a][b] = acc[a + 1][b + 1];
+#pragma unroll
+                            for (int b = 0; b < P; ++b) acc[P - 1][b] = 0.0;
+                        }
                     }
-                    // (pair a of the step is (d + a, d): a = 0 is the diagonal pair, which the second member of a couple skips)
-                    if (pr[0] >= 0 && write) k1s.store_diag(out, pr[0], A.stride, acc[0][0]);
+                    l = 0; ++sp;
+                    GA_T(2);
+                };
+                if constexpr (ROT) {
+                    // plane J at phase PH: label ga_PH_J; its ways out are written as jumps, so that no plane asks for the phase
+                    // (a switch per plane costs more scalar instructions than the window moves it would save)
+#define GA_ROT_PLANE(PH, J, PHN, JN) \
+                    ga_##PH##_##J: \
+                    if constexpr (PH < P && J < NS) { \
+                        if (J >= nj) { phase = PH; goto ga_done; } \
+                        sweep_plane(std::integral_constant<int, PH>{}, J); \
+                        if (++l < q) goto ga_##PH##_##JN; \
+                        span_end(std::integral_constant<int, PH>{}, J); \
+                        if constexpr (PH + 1 == P) goto ga_0_##JN; else goto ga_##PHN##_##JN; \
+                    } else if constexpr (PH < P && J == NS) { phase = PH; goto ga_done; }
+#define GA_ROT_ROW(J, JN) GA_ROT_PLANE(0, J, 1, JN) GA_ROT_PLANE(1, J, 2, JN) GA_ROT_PLANE(2, J, 3, JN) GA_ROT_PLANE(3, J, 4, JN) GA_ROT_PLANE(4, J, 0, JN)
+                    static_assert(P <= 5 && NS <= 8, "phases and planes of the table below");
+                    {
+                        const int nj = live ? g_end - gb : 0;       // planes of the batch that this wave sweeps
+                        if (phase == 1) goto ga_1_0;
+                        if (phase == 2) goto ga_2_0;
+                        if (phase == 3) goto ga_3_0;
+                        if (phase == 4) goto ga_4_0;
+                        goto ga_0_0;
+                        GA_ROT_ROW(0, 1) GA_ROT_ROW(1, 2) GA_ROT_ROW(2, 3) GA_ROT_ROW(3, 4)
+                        GA_ROT_ROW(4, 5) GA_ROT_ROW(5, 6) GA_ROT_ROW(6, 7) GA_ROT_ROW(7, 8)
+                        // (behind the last plane of the batch -- label ga_PH_NS, above where NS < 8 -- the phase that the next batch starts in)
+                        ga_0_8: phase = 0; goto ga_done;
+                        ga_1_8: phase = 1; goto ga_done;
+                        ga_2_8: phase = 2; goto ga_done;
+                        ga_3_8: phase = 3; goto ga_done;
+                        ga_4_8: phase = 4;
+                        ga_done:;
+                    }
+#undef GA_ROT_ROW
+#undef GA_ROT_PLANE
+                } else {
 #pragma unroll
-                    for (int a = 1; a < P; ++a)
-                        if (pr[a] >= 0 && write) k1s.store(out, pr[a], A.stride, acc[a][0]);
-#pragma unroll
-                    for (int a = 0; a < P - 1; ++a)
-#pragma unroll
-                        for (int b = 0; b <= a; ++b) acc[a][b] = acc[a + 1][b + 1];
-#pragma unroll
-                    for (int b = 0; b < P; ++b) acc[P - 1][b] = 0.0;
+                    for (int j = 0; j < NS; ++j) {
+                        if (gb + j >= g_end || !live) break;
+                        sweep_plane(std::integral_constant<int, 0>{}, j);
+                        if (++l < q) continue;
+                        span_end(std::integral_constant<int, 0>{}, j);
+                    }
                 }
-                l = 0; ++sp;
-                GA_T(2);
+                GA_T(1);
+                next_batch(gb + NS, rn, buf ^ 1);
+                products(rn, buf ^ 1);
+                GA_T(0);
+                stage_store(ra);
+                rs = rn;
+                __syncthreads();
+                GA_T(3);
             }
-            GA_T(1);
-            next_batch(gb + NS, rn, buf ^ 1);
-            products(rn, buf ^ 1);
-            GA_T(0);
-            stage_store(ra);
-            rs = rn;
-            __syncthreads();
-            GA_T(3);
-        }
+            if constexpr (ROT) {
+                // the last span of the AXIS retires every function it still has: the steps behind the first come from the step table,
+                // once per block, with the phase as a run-time value
+                if (live && g_end > g_begin && own_hi > own_lo && !GA_OFF(2)) {
+                    cip fr = (cip)(const int *)(A.tab + (size_t)g_last * GA_REC + 20);
+                    const int nst = fr[0], st0 = fr[1];
+                    for (int st = st0 + 1; st < st0 + nst; ++st) {
+                        const int8v rec8 = *(const int8v __attribute__((address_space(4))) *)((cip)A.steps + (size_t)st * 8);
+                        with_phase<P>(phase, [&](auto phc) __attribute__((always_inline)) -> bool {
+                            constexpr int PH = decltype(phc)::value;
+                            if (rec8[0] >= 0) k1s.store_diag(out, rec8[0], A.stride, win_acc<P, PH>(acc, 0, 0));
+#pragma unroll
+                            for (int a = 1; a < P; ++a)
+                                if (rec8[a] >= 0) k1s.store(out, rec8[a], A.stride, win_acc<P, PH>(acc, a, 0));
+                            return true;
+                        });
+                        phase = phase + 1 == P ? 0 : phase + 1;
+                    }
+                }
+            }
+        };
+        if (A.rot) batches(std::true_type{});
+        else batches(std::false_type{});
 #ifdef IGX_GA_STAMP
         if (lane == 0 && blockIdx.x < 2048 && blockIdx.y == 0)
             for (int i = 0; i < 4; ++i) g_ga_stamp[(blockIdx.x * 8 + (w & 7)) * 6 + i] = st_[i];
@@ -1338,6 +1460,24 @@ k_geoA(const GeoAArgs A)
 #endif
 }
 
+// The instantiations with the pair-product sweep (symmetric fixed forms, P <= 5, vector sweep; 3D and 2D) are compiled in a unit of
+// their own -- geoa_sym.hip: this file with GEOA_SYM_TU defined -- because the rotating window needs a code-generator option
+// (Makefile: GEOA_SYM_FLAGS) that the other instantiations are better off without (it changes their register allocation).  Here
+// they are declared only; the launches below reach them through the linker.
+#ifdef GEOA_SYM_TU
+#define GEOA_DPS_INST(...) template __global__ void k_geoA<__VA_ARGS__>(const GeoAArgs);
+#else
+#define GEOA_DPS_INST(...) extern template __global__ void k_geoA<__VA_ARGS__>(const GeoAArgs);
+#endif
+#define GEOA_DPS_NC(PV, NSV, GV, NC0, NC1, D2V) GEOA_DPS_INST(PV, NSV, GV, NC0, false, 0, D2V) GEOA_DPS_INST(PV, NSV, GV, NC1, false, 0, D2V)
+#define GEOA_DPS_P(PV) GEOA_DPS_NC(PV, 1, 2, 3, 4, false) GEOA_DPS_NC(PV, 1, 3, 3, 4, false) GEOA_DPS_NC(PV, 8, 2, 3, 4, false) GEOA_DPS_NC(PV, 8, 3, 3, 4, false) \
+                       GEOA_DPS_NC(PV, 1, 2, 2, 3, true) GEOA_DPS_NC(PV, 1, 3, 2, 3, true) GEOA_DPS_NC(PV, 4, 2, 2, 3, true) GEOA_DPS_NC(PV, 4, 3, 2, 3, true)
+GEOA_DPS_P(2) GEOA_DPS_P(3) GEOA_DPS_P(4) GEOA_DPS_P(5)
+#undef GEOA_DPS_P
+#undef GEOA_DPS_NC
+#undef GEOA_DPS_INST
+
+#ifndef GEOA_SYM_TU
 template <int P, int NS, int P0G>
 static int launch_geoA_2d(hipStream_t st, const GeoAArgs &A, int nc, dim3 grid)
 {
@@ -1529,11 +1669,15 @@ int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *
     }
     if (nodiag_mask && (nonsym || form || pt->dim != 3 || !geoA_diag_types_commute(pt))) { set_error("internal: diagonal slices skipped on a sweep that does not repeat them"); return IGX_ERR_UNSUPPORTED; }
     A.nslots = nslots;
+    // pair-product sweep (symmetric fixed forms, at most 16 lower pairs; no other sweep reads this): the rotating window where every
+    // interior knot of axis 0 is single -- decided on the whole axis, so every slab and chunk of a patch agrees
+    A.rot = GA_DPP && A0.simple && !pt->knobs.no_geoa_rot && A0.P * (A0.P + 1) / 2 <= 16;
     for (int x = nslots; x < GA_MAXS; ++x) A.out[x] = A.out[0];  // (waves without an array: never stored through)
     A.ntiles = (int)((A.NPL + 63) / 64);
     dim3 grid((unsigned)((A.ntiles + 7) / 8 * 8), nchunks);     // the kernel permutes the tiles over the XCDs
     const int nc = pt->ncomp, p0g = pt->gax[0].P;
     if (d2) {
+        if (A.rot) pt->last_path |= IGX_PATH_GEOA_ROT;
 #define GEOA_2D(PV) case PV: return nslots == 1 ? (p0g == 2 ? launch_geoA_2d<PV, 1, 2>(st, A, nc, grid) : launch_geoA_2d<PV, 1, 3>(st, A, nc, grid)) \
                                                 : (p0g == 2 ? launch_geoA_2d<PV, 4, 2>(st, A, nc, grid) : launch_geoA_2d<PV, 4, 3>(st, A, nc, grid))
         switch (A0.P) { GEOA_2D(2); GEOA_2D(3); GEOA_2D(4); GEOA_2D(5); }
@@ -1576,6 +1720,7 @@ int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *
     }
     // (mass -- one array -- on the eight-wave block where the pair-product sweep applies (p <= 4): the geometry of eight planes in
     // parallel; the one-wave block of rounds 2-5 above that)
+    if (A.rot) pt->last_path |= IGX_PATH_GEOA_ROT;
 #define GEOA_P(PV) case PV: return (nslots == 1 && !(GA_MASS8 && PV <= 5)) ? launch_geoA_g<PV, 1>(st, A, nc, p0g, grid) : launch_geoA_g<PV, 8>(st, A, nc, p0g, grid)
     switch (A0.P) {
         GEOA_P(2); GEOA_P(3); GEOA_P(4); GEOA_P(5); GEOA_P(6);
@@ -1584,5 +1729,6 @@ int launch_geoA(hipStream_t st, igx_patch *pt, int kind, int nslots, const int *
     set_error("fused geometry + stage A: unsupported degree %d", A0.p);
     return IGX_ERR_UNSUPPORTED;
 }
+#endif
 
 } // namespace igx

@@ -427,6 +427,7 @@ igx_patch *igx_patch_create(igx_ctx *ctx, const igx_patch_desc *d)
         if (const char *e = getenv("IGX_BF")) k.bf = atoi(e);
         k.no_twin = getenv("IGX_NO_TWIN") != nullptr;
         if (const char *e = getenv("IGX_NO_DIAG_SKIP")) k.no_diag_skip = strcmp(e, "0") != 0;
+        if (const char *e = getenv("IGX_NO_GEOA_ROT")) k.no_geoa_rot = strcmp(e, "0") != 0;
         if (const char *e = getenv("IGX_PLACEMENT_TRIES")) k.placement_tries = std::max(1, std::min(16, atoi(e)));
         if (const char *e = getenv("IGX_STAGE_EVENTS")) k.stage_events = strcmp(e, "0") != 0;
     }

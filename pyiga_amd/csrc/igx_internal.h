@@ -124,6 +124,7 @@ struct igx_knobs {
     int bf = 0;                               // IGX_BF=2: symmetric 3D forms through k_bf2 + the mirror pass (the chain of rounds 3-4) instead of k_bf3
     int no_twin = 0;                          // IGX_NO_TWIN: no twin patch (repeated knots on the last axis: the stage kernels, as before round 6)
     int no_diag_skip = 0;                     // IGX_NO_DIAG_SKIP: k_geoA writes and k_bf3 reads the K1 slices that diagonal outer pairs duplicate (A/B runs)
+    int no_geoa_rot = 0;                      // IGX_NO_GEOA_ROT: the pair window of k_geoA's pair-product sweep moves at every span end, as it does on axes with repeated knots (A/B runs)
     int placement_tries = 1;                  // IGX_PLACEMENT_TRIES=n (opt-in, 3D symmetric forms): the CSR value buffer is the fastest of n
                                               // allocations under the mirror pass, timed once at its first assembly
     int stage_events = -1;                    // IGX_STAGE_EVENTS: events between the kernels of a chain (per-kernel device times in
