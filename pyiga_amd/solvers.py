@@ -187,6 +187,13 @@ def _box_args(lo, hi, U, lam):
     return (C.c_int32 * n)(*lo), (C.c_int32 * n)(*hi), ptrs(U), ptrs(lam)
 
 
+def _schwarz_args(boxes, U, lam):
+    """``_box_args`` of the boxes and factors of all patches (``schwarz_boxes``, ``schwarz_factors``): three slots per patch, the
+    slots of a missing third axis 0 / null."""
+    slots = lambda per_patch, fill: [v[k] if k < len(v) else fill for v in per_patch for k in range(3)]
+    return _box_args(slots([b[0] for b in boxes], 0), slots([b[1] for b in boxes], 0), slots(U, None), slots(lam, None))
+
+
 class _DeviceSystem:
     """What the device-resident Dirichlet problems share: the solver handle (``igx_solver_*``) and its lifecycle, the method, the
     preconditioner, the solve and the solver's SpMV and preconditioner alone.
@@ -1236,53 +1243,18 @@ def first_fit_colouring(indptr, indices, free=None):
 MG_BLOCK_ROWS = 1024        # a level of at most this many free dofs runs every sweep in one launch of one block
 
 
-class MultipatchSystem(_DeviceSystem):
-    """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, of the global system of the multipatch `MP`, summed and
-    solved on the device.
+class _MultipatchMultigrid:
+    """The geometric multigrid hierarchy of a system on a multipatch (DESIGN.md sections 17 and 37): built, inspected and dropped
+    here for ``MultipatchSystem`` (and through it ``MultipatchEigenSystem``) and ``MultipatchVectorSystem``.  ``_mg`` is None or
+    ``dict(systems=[self, coarser, ...], smooth_steps=, info=[mg_info entry per level])``.
 
-    `problem`, `rhs`, `args` / `kwargs`: as for ``MP.assemble_system`` (the same per-patch assemblies and scatters; the sums stay
-    on the device).  With ``method='cg'`` (the default) the form must be symmetric: a form whose assembler declares
-    ``_symmetric_form = False`` is refused.  ``method='bicgstab'`` solves any form; Schwarz then uses the stiffness factors.
-    `bcs`: ``(indices, values)`` as ``MP.compute_dirichlet_bcs`` returns them, or None.  `boundary_terms`: ``BoundaryTerm``
-    objects, each with its patch index (``patch=``); with a matrix form among them ``precond='mg'`` raises ValueError (the
-    coarse levels would miss the boundary matrices).  ``solve(...)`` returns the completed
-    global vector and leaves the solver's statistics in ``info``.  The system reads the sums `MP` holds: a later
-    ``MP.assemble_system`` restarts them (a solve then raises), and ``MP.close()`` destroys the system's device solver.
-    """
+    A class supplies ``MP`` and what differs between the systems: ``_refuse_multigrid()`` (ValueError when the system cannot have
+    a hierarchy, before any work), ``_mg_fixed_sides(kvs, maps)``, ``_level_system(MPc, bcs)``, ``_set_smoother(smooth_steps,
+    ...)``, and the names ``_MG_COARSE`` / ``_MG_INVERSE`` / ``_MG_ORDER_KEY``."""
 
-    PRECONDS = _lib.MP_PRECONDS
-    FACTORED = 'schwarz'
-    _inspect_symmetry = True                  # (False: the caller has shown the form to be symmetric before, as
-                                              # MultipatchEigenSystem does for its own levels)
-
-    def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', boundary_terms=None, **kwargs):
-        self.MP = MP
-        _check_method(method)
-        self._problem = (problem, rhs, dict(args or {}), dict(kwargs))
-        self._mg = None
-        kinds = []
-        # boundary terms (DESIGN.md section 29), set up on the host before any device work; their matrices are added to the
-        # sums after the scatters, their loads to the patches' load vectors before theirs
-        terms = MP._boundary_terms(boundary_terms, rhs, args, kwargs, method=method, who=type(self).__name__)
-        self._matrix_terms = any(t.has_matrix for t in terms.values())
-
-        def inspect(p, asm):
-            if self._inspect_symmetry and method == 'cg' and not getattr(asm, '_symmetric_form', True):
-                raise ValueError('MultipatchSystem solves by CG and needs a form known to be symmetric; the assembler of patch %d '
-                                 '(%s) cannot show that its form is (general form strings never can).  Accepted: the built-in '
-                                 "mass and stiffness forms ('u*v*dx', 'inner(grad(u),grad(v))*dx') and assemblers that do not "
-                                 "declare _symmetric_form = False; any other form: method='bicgstab'" % (p, type(asm).__name__))
-            kinds.append(getattr(asm, '_kind', None))
-        h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect, boundary_terms=terms)
-        self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
-        self.n = MP.numdofs
-        self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
-        self._attach('igx_solver_create_multipatch', (h,), bcs, method, 'cg')
-        MP._solvers.add(self)
-
-    def error_norms(self, u, exact, grad_exact=None):
-        """``Multipatch.error_norms`` of the system's multipatch for a global solution vector `u`."""
-        return self.MP.error_norms(u, exact, grad_exact)
+    _mg = None
+    _MG_COARSE, _MG_INVERSE = 'igx_solver_set_mg_coarse', 'igx_solver_set_mg_inverse'      # the C calls of a level's links
+    _MG_ORDER_KEY = 'free'                    # the mg_info entry that counts what the smoother colours (``mg_colour_order``)
 
     def _drop_owner(self):
         self._drop_multigrid()
@@ -1290,9 +1262,8 @@ class MultipatchSystem(_DeviceSystem):
         if MP is not None:
             MP._solvers.discard(self)
 
-    # -- geometric multigrid
     def _drop_multigrid(self):
-        mg, self._mg = getattr(self, '_mg', None), None
+        mg, self._mg = self._mg, None
         if mg:
             for S in mg['systems'][1:]:
                 S.close()
@@ -1303,43 +1274,16 @@ class MultipatchSystem(_DeviceSystem):
     def set_method(self, method):
         if method == 'bicgstab' and getattr(self, '_precond', None) == 'mg':
             raise ValueError("precond='mg' serves method='cg' only")
-        _DeviceSystem.set_method(self, method)
+        super().set_method(method)
 
-    def set_precond(self, precond):
-        if precond == 'mg':
-            if self.method != 'cg':
-                raise ValueError("precond='mg' serves method='cg' only")
-            self._refuse_mg_with_terms()
-            self._live()
-            if self._mg is None:
-                self.set_multigrid()
-        _DeviceSystem.set_precond(self, precond)
-
-    _matrix_terms = False                     # the sums hold boundary matrices (boundary_terms with a matrix form)
-
-    def _refuse_mg_with_terms(self):
-        if self._matrix_terms:
-            raise ValueError("precond='mg' is not available with boundary terms that have a matrix form: the coarse levels assemble "
-                             "`problem` again and would miss the boundary matrices (load-only terms are fine); use 'schwarz', "
-                             "'jacobi' or None")
-
-    def set_multigrid(self, levels=None, coarse=None, smooth_steps=1, coarse_max=2048, block_rows=None):
-        """Sets up the hierarchy of ``precond='mg'``: a V-cycle with `smooth_steps` coloured Gauss-Seidel sweeps before (forward)
-        and after (backward) the coarse correction, the coarsest level solved with a dense inverse.
-
-        Every patch's knot vectors are coarsened with :func:`coarsen_knots` and the joins of the multipatch replayed, level after
-        level, until there are `levels` of them (the finest included), a knot vector cannot be coarsened, or a level has at most
-        `coarse_max` free dofs; `coarse`: the coarser multipatches ``[MP1, MP2, ...]`` instead (needed for a multipatch joined
-        through bare ``join_dofs`` calls).  The same problem is assembled again on every coarse level, on the device, with the same
-        patch sides fixed; the system owns the coarse multipatches and closes them with itself.  `block_rows`: levels of at most
-        this many free dofs sweep in one launch of one block (default ``MG_BLOCK_ROWS``).  ValueError if the fixed dofs are not a
-        union of whole patch sides, if a local-to-global map is not injective, with ``method='bicgstab'``, or if the coarsest
-        level keeps more than `coarse_max` free dofs."""
+    def _build_multigrid(self, levels, coarse, smooth_steps, coarse_max, *smoother_args):
+        """``set_multigrid`` of every system: the coarse multipatches (coarsened and re-joined, or `coarse`) with the same patch
+        sides fixed, their systems, then on the device every level's smoother (``S._set_smoother(smooth_steps,
+        *smoother_args)``, the finest first), the links of every pair of levels and the dense inverse of the coarsest.  A
+        failure closes every coarse level made so far and leaves the system without a hierarchy."""
         from . import bspline
         from .multipatch import slice_indices
-        if self.method != 'cg':
-            raise ValueError("precond='mg' serves method='cg' only")
-        self._refuse_mg_with_terms()
+        self._refuse_multigrid()
         self._live()
         MP = self.MP
         if not MP.injective:
@@ -1350,13 +1294,10 @@ class MultipatchSystem(_DeviceSystem):
             raise ValueError('smooth_steps must be 1 .. 16')
         if levels is not None and int(levels) < 1:
             raise ValueError('levels must be >= 1')
-        block_rows = MG_BLOCK_ROWS if block_rows is None else int(block_rows)
-        maps0 = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
-        sides = fixed_sides([kvs for kvs, _ in MP.patches], maps0, self.bc_indices)
+        sides = self._mg_fixed_sides([kvs for kvs, _ in MP.patches], [MP.patch_to_global_idx(p) for p in range(MP.numpatches)])
         self._drop_multigrid()
         lib = _lib.load()
-        problem, rhs, args, kwargs = self._problem
-        systems, keep = [self], []
+        systems, keep = [self], []                # (keep: the host tables stay referenced until the calls that read them are over)
         try:
             given = None if coarse is None else list(coarse)
             while True:
@@ -1376,11 +1317,14 @@ class MultipatchSystem(_DeviceSystem):
                     except ValueError:
                         break
                     MPc = MP.replay_joins(patches)
-                fixed = [MPc.patch_to_global_idx(p)[slice_indices(ax, 0 if side == 0 else -1, tuple(kv.numdofs for kv in MPc.patches[p][0]),
-                                                                  ravel=True)] for p, ax, side in sides]
+                # the sides of component c, fixed on the coarse multipatch: its scalar dofs numbered from c * Nc
+                Nc = MPc.numdofs
+                fixed = [c * Nc + MPc.patch_to_global_idx(p)[slice_indices(ax, 0 if side == 0 else -1,
+                                                                           tuple(kv.numdofs for kv in MPc.patches[p][0]), ravel=True)]
+                         for c, of_c in enumerate(sides) for p, ax, side in of_c]
                 fixed = np.unique(np.concatenate(fixed)) if fixed else np.zeros(0, dtype=np.int64)
                 try:
-                    Sc = self._level_system(MPc, problem, rhs, (fixed, np.zeros(fixed.size)), args, kwargs)
+                    Sc = self._level_system(MPc, (fixed, np.zeros(fixed.size)))
                 except Exception:
                     MPc.close()
                     raise
@@ -1389,33 +1333,25 @@ class MultipatchSystem(_DeviceSystem):
             m = coarsest.n - coarsest.bc_indices.size
             if m > coarse_max:
                 raise ValueError('the coarsest level keeps %d free dofs, more than coarse_max = %d' % (m, coarse_max))
-            info = []
-            for S in systems:
-                indptr, indices = S.MP.pattern()
-                free = np.ones(S.n, dtype=np.uint8)
-                free[S.bc_indices] = 0
-                colour, nc = first_fit_colouring(indptr, indices, free)
-                _lib.check(lib.igx_solver_set_mg_smoother(S._live(), colour.ctypes.data_as(C.POINTER(C.c_int32)), smooth_steps, block_rows),
-                           'igx_solver_set_mg_smoother')
-                info.append(dict(spans=[tuple(kv.numspans for kv in kvs) for kvs, _ in S.MP.patches], dofs=S.n,
-                                 free=int(S.n - S.bc_indices.size), nnz=int(indices.size), colours=nc))
+            info = [S._set_smoother(smooth_steps, *smoother_args) for S in systems]
             for F, Cs in zip(systems[:-1], systems[1:]):
                 np_ = MP.numpatches
                 Ps = []
                 for (kf, _), (kc, _) in zip(F.MP.patches, Cs.MP.patches):
                     Ps += [np.ascontiguousarray(bspline.prolongation(c, f).toarray()) for c, f in zip(kc, kf)] + [None] * (3 - len(kf))
                 keep.append(Ps)
-                mult = np.zeros(F.n)
+                N = F.MP.numdofs                  # (the multiplicities are those of the scalar dofs, whatever the components)
+                mult = np.zeros(N)
                 for p in range(np_):
-                    mult += np.bincount(F.MP.patch_to_global_idx(p), minlength=F.n)
+                    mult += np.bincount(F.MP.patch_to_global_idx(p), minlength=N)
                 Pp = (_lib._dp * (3 * np_))(*[None if a is None else _lib.dptr(a) for a in Ps])
-                _lib.check(lib.igx_solver_set_mg_coarse(F._live(), Cs._live(), Pp, _lib.dptr(mult)), 'igx_solver_set_mg_coarse')
-            # the coarsest matrix on its free dofs, inverted on the host
+                _lib.check(getattr(lib, self._MG_COARSE)(F._live(), Cs._live(), Pp, _lib.dptr(mult)), self._MG_COARSE)
+            # the coarsest matrix on its free dofs (blocked: of all components), inverted on the host
             A = coarsest.matrix()
             fr = np.setdiff1d(np.arange(coarsest.n), coarsest.bc_indices)
             inv = scipy.linalg.inv(A[fr][:, fr].toarray()) if fr.size else np.zeros((0, 0))
             inv = np.ascontiguousarray(0.5 * (inv + inv.T))
-            _lib.check(lib.igx_solver_set_mg_inverse(coarsest._live(), _lib.dptr(inv), fr.size), 'igx_solver_set_mg_inverse')
+            _lib.check(getattr(lib, self._MG_INVERSE)(coarsest._live(), _lib.dptr(inv), fr.size), self._MG_INVERSE)
         except Exception:
             for S in systems[1:]:
                 S.close()
@@ -1426,9 +1362,10 @@ class MultipatchSystem(_DeviceSystem):
             self._precond = None                  # (the device dropped it when the hierarchy changed)
         return self
 
-    def _level_system(self, MPc, problem, rhs, bcs, args, kwargs):
-        """The system of a coarse level of the hierarchy."""
-        return MultipatchSystem(MPc, problem, rhs, bcs, args=args, **kwargs)
+    def _mg_solve_info(self, precond):
+        """``levels`` and ``smooth_steps`` in ``info`` after a solve preconditioned with `precond` = 'mg'."""
+        if precond == 'mg':
+            self.info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
 
     def _mg_level(self, level):
         self._live()
@@ -1438,21 +1375,6 @@ class MultipatchSystem(_DeviceSystem):
         if not 0 <= int(level) < len(systems):
             raise ValueError('level %r: the hierarchy has %d levels' % (level, len(systems)))
         return systems[int(level)]
-
-    def matrix(self):
-        """The summed matrix the system solves with, downloaded: CSR over all dofs (fixed rows and columns included)."""
-        self._live()
-        indptr, indices = self.MP.pattern()
-        data = np.empty(indices.shape[0])
-        _lib.check(_lib.load().igx_multipatch_download(self.MP._device(), _lib.dptr(data), None), 'igx_multipatch_download')
-        return scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(self.n, self.n))
-
-    def rhs(self):
-        """The summed right-hand side on the device, downloaded (all dofs)."""
-        self._live()
-        b = np.empty(self.n)
-        _lib.check(_lib.load().igx_multipatch_download(self.MP._device(), None, _lib.dptr(b)), 'igx_multipatch_download')
-        return b
 
     def mg_level(self, level):
         """The system of `level` of the hierarchy (0: this one): its ``MP``, ``bc_indices`` and ``matrix()``."""
@@ -1485,10 +1407,11 @@ class MultipatchSystem(_DeviceSystem):
                     smooth_ms=list(pf.smooth_ms)[:nl], residual_ms=list(pf.residual_ms)[:nl], transfer_ms=list(pf.transfer_ms)[:nl])
 
     def mg_colour_order(self, level=0):
-        """The free dofs of `level` in the order the smoother's forward sweep relaxes them: sorted by (colour, index)."""
+        """What the smoother of `level` colours -- the free dofs of a scalar system, the nodes with a free component of a
+        vector-valued one -- in the order its forward sweep relaxes them: sorted by (colour, index)."""
         self._mg_level(level)
         inf = self._mg['info'][int(level)]
-        rows = np.empty(inf['free'], dtype=np.int32)
+        rows = np.empty(inf[self._MG_ORDER_KEY], dtype=np.int32)
         offs = np.empty(inf['colours'] + 1, dtype=np.int32)
         _lib.check(_lib.load().igx_solver_mg_colours(self._live(), int(level), rows.ctypes.data_as(C.POINTER(C.c_int32)),
                                                      offs.ctypes.data_as(C.POINTER(C.c_int32))), 'igx_solver_mg_colours')
@@ -1534,6 +1457,123 @@ class MultipatchSystem(_DeviceSystem):
         F, Cs = self._mg_level(level), self._mg_level(level + 1)
         return self._transfer(_lib.load().igx_solver_mg_restrict_d, 'igx_solver_mg_restrict_d', r, level, F.n, Cs.n)
 
+
+class MultipatchSystem(_MultipatchMultigrid, _DeviceSystem):
+    """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, of the global system of the multipatch `MP`, summed and
+    solved on the device.
+
+    `problem`, `rhs`, `args` / `kwargs`: as for ``MP.assemble_system`` (the same per-patch assemblies and scatters; the sums stay
+    on the device).  With ``method='cg'`` (the default) the form must be symmetric: a form whose assembler declares
+    ``_symmetric_form = False`` is refused.  ``method='bicgstab'`` solves any form; Schwarz then uses the stiffness factors.
+    `bcs`: ``(indices, values)`` as ``MP.compute_dirichlet_bcs`` returns them, or None.  `boundary_terms`: ``BoundaryTerm``
+    objects, each with its patch index (``patch=``); with a matrix form among them ``precond='mg'`` raises ValueError (the
+    coarse levels would miss the boundary matrices).  ``solve(...)`` returns the completed
+    global vector and leaves the solver's statistics in ``info``.  The system reads the sums `MP` holds: a later
+    ``MP.assemble_system`` restarts them (a solve then raises), and ``MP.close()`` destroys the system's device solver.
+    """
+
+    PRECONDS = _lib.MP_PRECONDS
+    FACTORED = 'schwarz'
+    _inspect_symmetry = True                  # (False: the caller has shown the form to be symmetric before, as
+                                              # MultipatchEigenSystem does for its own levels)
+
+    def __init__(self, MP, problem, rhs, bcs=None, args=None, method='cg', boundary_terms=None, **kwargs):
+        self.MP = MP
+        _check_method(method)
+        self._problem = (problem, rhs, dict(args or {}), dict(kwargs))
+        kinds = []
+        # boundary terms (DESIGN.md section 29), set up on the host before any device work; their matrices are added to the
+        # sums after the scatters, their loads to the patches' load vectors before theirs
+        terms = MP._boundary_terms(boundary_terms, rhs, args, kwargs, method=method, who=type(self).__name__)
+        self._matrix_terms = any(t.has_matrix for t in terms.values())
+
+        def inspect(p, asm):
+            if self._inspect_symmetry and method == 'cg' and not getattr(asm, '_symmetric_form', True):
+                raise ValueError('MultipatchSystem solves by CG and needs a form known to be symmetric; the assembler of patch %d '
+                                 '(%s) cannot show that its form is (general form strings never can).  Accepted: the built-in '
+                                 "mass and stiffness forms ('u*v*dx', 'inner(grad(u),grad(v))*dx') and assemblers that do not "
+                                 "declare _symmetric_form = False; any other form: method='bicgstab'" % (p, type(asm).__name__))
+            kinds.append(getattr(asm, '_kind', None))
+        h = MP._sum_system(problem, rhs, args, False, 'csr', 'blocked', kwargs, on_assembler=inspect, boundary_terms=terms)
+        self.kind = kinds[0] if kinds and all(k == kinds[0] for k in kinds) else None
+        self.n = MP.numdofs
+        self._ctx = MP._ctx                       # (the context of the multipatch handle: device vectors of spmv / apply_precond)
+        self._attach('igx_solver_create_multipatch', (h,), bcs, method, 'cg')
+        MP._solvers.add(self)
+
+    def error_norms(self, u, exact, grad_exact=None):
+        """``Multipatch.error_norms`` of the system's multipatch for a global solution vector `u`."""
+        return self.MP.error_norms(u, exact, grad_exact)
+
+    # -- geometric multigrid (DESIGN.md section 17): what _MultipatchMultigrid asks of a scalar system
+    def set_precond(self, precond):
+        if precond == 'mg':
+            self._refuse_multigrid()
+            self._live()
+            if self._mg is None:
+                self.set_multigrid()
+        _DeviceSystem.set_precond(self, precond)
+
+    _matrix_terms = False                     # the sums hold boundary matrices (boundary_terms with a matrix form)
+
+    def _refuse_multigrid(self):
+        if self.method != 'cg':
+            raise ValueError("precond='mg' serves method='cg' only")
+        if self._matrix_terms:
+            raise ValueError("precond='mg' is not available with boundary terms that have a matrix form: the coarse levels assemble "
+                             "`problem` again and would miss the boundary matrices (load-only terms are fine); use 'schwarz', "
+                             "'jacobi' or None")
+
+    def set_multigrid(self, levels=None, coarse=None, smooth_steps=1, coarse_max=2048, block_rows=None):
+        """Sets up the hierarchy of ``precond='mg'``: a V-cycle with `smooth_steps` coloured Gauss-Seidel sweeps before (forward)
+        and after (backward) the coarse correction, the coarsest level solved with a dense inverse.
+
+        Every patch's knot vectors are coarsened with :func:`coarsen_knots` and the joins of the multipatch replayed, level after
+        level, until there are `levels` of them (the finest included), a knot vector cannot be coarsened, or a level has at most
+        `coarse_max` free dofs; `coarse`: the coarser multipatches ``[MP1, MP2, ...]`` instead (needed for a multipatch joined
+        through bare ``join_dofs`` calls).  The same problem is assembled again on every coarse level, on the device, with the same
+        patch sides fixed; the system owns the coarse multipatches and closes them with itself.  `block_rows`: levels of at most
+        this many free dofs sweep in one launch of one block (default ``MG_BLOCK_ROWS``).  ValueError if the fixed dofs are not a
+        union of whole patch sides, if a local-to-global map is not injective, with ``method='bicgstab'``, or if the coarsest
+        level keeps more than `coarse_max` free dofs."""
+        return self._build_multigrid(levels, coarse, smooth_steps, coarse_max, MG_BLOCK_ROWS if block_rows is None else int(block_rows))
+
+    def _mg_fixed_sides(self, kvs, maps):
+        """Per component (a scalar system has one) the wholly fixed patch sides, which stay fixed on every level."""
+        return [fixed_sides(kvs, maps, self.bc_indices)]
+
+    def _level_system(self, MPc, bcs):
+        """The system of a coarse level of the hierarchy: the same problem on `MPc` with the fixed dofs `bcs`."""
+        problem, rhs, args, kwargs = self._problem
+        return MultipatchSystem(MPc, problem, rhs, bcs, args=args, **kwargs)
+
+    def _set_smoother(self, smooth_steps, block_rows):
+        """Colours the free dofs (first fit on the pattern) and hands the colours to the device; returns this level's entry of
+        ``mg_info``."""
+        indptr, indices = self.MP.pattern()
+        free = np.ones(self.n, dtype=np.uint8)
+        free[self.bc_indices] = 0
+        colour, nc = first_fit_colouring(indptr, indices, free)
+        _lib.check(_lib.load().igx_solver_set_mg_smoother(self._live(), colour.ctypes.data_as(C.POINTER(C.c_int32)), smooth_steps, block_rows),
+                   'igx_solver_set_mg_smoother')
+        return dict(spans=[tuple(kv.numspans for kv in kvs) for kvs, _ in self.MP.patches], dofs=self.n,
+                    free=int(self.n - self.bc_indices.size), nnz=int(indices.size), colours=nc)
+
+    def matrix(self):
+        """The summed matrix the system solves with, downloaded: CSR over all dofs (fixed rows and columns included)."""
+        self._live()
+        indptr, indices = self.MP.pattern()
+        data = np.empty(indices.shape[0])
+        _lib.check(_lib.load().igx_multipatch_download(self.MP._device(), _lib.dptr(data), None), 'igx_multipatch_download')
+        return scipy.sparse.csr_matrix((data, indices.copy(), indptr.copy()), shape=(self.n, self.n))
+
+    def rhs(self):
+        """The summed right-hand side on the device, downloaded (all dofs)."""
+        self._live()
+        b = np.empty(self.n)
+        _lib.check(_lib.load().igx_multipatch_download(self.MP._device(), None, _lib.dptr(b)), 'igx_multipatch_download')
+        return b
+
     def schwarz_setup(self):
         """Boxes, factors and mode of the Schwarz preconditioner (host set-up)."""
         MP = self.MP
@@ -1548,10 +1588,7 @@ class MultipatchSystem(_DeviceSystem):
 
     def _set_factors(self, h):
         boxes, U, lam, mode = self.schwarz_setup()
-        slots = lambda per_patch, fill: [v[k] if k < len(v) else fill for v in per_patch for k in range(3)]
-        lo, hi, Up, Lp = _box_args(slots([b[0] for b in boxes], 0), slots([b[1] for b in boxes], 0), slots(U, None),
-                                   slots(lam, None))
-        _lib.check(_lib.load().igx_solver_set_schwarz(h, lo, hi, Up, Lp, mode), 'igx_solver_set_schwarz')
+        _lib.check(_lib.load().igx_solver_set_schwarz(h, *_schwarz_args(boxes, U, lam), mode), 'igx_solver_set_schwarz')
         self._factors_set = True
 
     def solve(self, tol=1e-8, maxiter=1000, precond='jacobi', x0=None, check_every=1, timed=False, b=None):
@@ -1570,12 +1607,11 @@ class MultipatchSystem(_DeviceSystem):
         n = 64: 12 ms against 8 ms; three cubes n = 32: 37 ms against 13 ms), and its set-up (coarse assemblies, colouring, a dense
         inverse) takes 0.1 to 0.4 s on the host."""
         u = self._solve(b, tol, maxiter, precond, x0, check_every, timed)
-        if precond == 'mg':
-            self.info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
+        self._mg_solve_info(precond)
         return u
 
 
-class MultipatchVectorSystem(_DeviceSystem):
+class MultipatchVectorSystem(_MultipatchMultigrid, _DeviceSystem):
     """The Dirichlet problem ``A u = b``, ``u = g`` on the dofs of `bcs`, for a vector-valued form (``bfuns=[('u', nc),
     ('v', nc)]``, nc = 2 or 3: linear elasticity, grad-div, ...) on the multipatch `MP`, summed and solved on the device
     (DESIGN.md section 28).
@@ -1597,7 +1633,6 @@ class MultipatchVectorSystem(_DeviceSystem):
 
     PRECONDS = _lib.MPVEC_PRECONDS
     FACTORED = 'schwarz'
-    _mg = None                                # the hierarchy of set_multigrid(): systems (this one first), smooth_steps, info
 
     def __init__(self, MP, problem, rhs, bcs=None, bfuns=None, args=None, method='auto', **kwargs):
         if method != 'auto':
@@ -1631,12 +1666,6 @@ class MultipatchVectorSystem(_DeviceSystem):
             for a in asms:
                 a.patch.close()
 
-    def _drop_owner(self):
-        self._drop_multigrid()
-        MP = getattr(self, 'MP', None)
-        if MP is not None:
-            MP._solvers.discard(self)
-
     def set_precond(self, precond):
         if precond == 'kron':
             raise ValueError('MultipatchVectorSystem has no %r preconditioner: \'jacobi\', \'schwarz\', \'mg\' or None' % (precond,))
@@ -1649,17 +1678,28 @@ class MultipatchVectorSystem(_DeviceSystem):
                                  'every block again on every coarse level, so it is not done behind a solve)')
         _DeviceSystem.set_precond(self, precond)
 
-    # -- geometric multigrid: the hierarchy handling of MultipatchSystem on blocked vectors
-    _drop_multigrid = MultipatchSystem._drop_multigrid
-    set_method = MultipatchSystem.set_method
-    _mg_level = MultipatchSystem._mg_level
-    mg_level = MultipatchSystem.mg_level
-    mg_info = MultipatchSystem.mg_info
-    mg_profile = MultipatchSystem.mg_profile
-    relax = MultipatchSystem.relax
-    _transfer = MultipatchSystem._transfer
-    prolong = MultipatchSystem.prolong
-    restrict = MultipatchSystem.restrict
+    # -- geometric multigrid: what _MultipatchMultigrid asks of a system on blocked vectors
+    _MG_COARSE, _MG_INVERSE = 'igx_solver_set_block_mg_coarse', 'igx_solver_set_block_mg_inverse'
+    _MG_ORDER_KEY = 'nodes'
+
+    def _refuse_multigrid(self):
+        if self.method != 'cg' or not self.symmetric:
+            raise ValueError("precond='mg' serves method='cg' on a symmetric form only")
+
+    def _mg_fixed_sides(self, kvs, maps):
+        """Per component its wholly fixed patch sides, which stay fixed on every level."""
+        sides = []
+        for c in range(self.ncomp):
+            try:
+                sides.append(fixed_sides(kvs, maps, self._component_fixed(c)))
+            except ValueError as e:
+                raise ValueError('component %d: %s' % (c, e)) from None
+        return sides
+
+    def _level_system(self, MPc, bcs):
+        """The system of a coarse level of the hierarchy: the same form on `MPc` with a zero right-hand side."""
+        problem, bfuns, args = self._problem
+        return MultipatchVectorSystem(MPc, problem, 0.0, bcs, bfuns=bfuns, args=args, method='cg')
 
     def _component_fixed(self, c):
         """The fixed dofs of component `c` in the scalar numbering."""
@@ -1698,105 +1738,7 @@ class MultipatchVectorSystem(_DeviceSystem):
         levels and closes them with itself.  ValueError if the fixed dofs of a component are not a union of whole patch sides
         (the sides may differ between components), if a local-to-global map is not injective, with ``method='bicgstab'`` or a
         non-symmetric form, or if the coarsest level keeps more than `coarse_max` free dofs."""
-        from . import bspline
-        from .multipatch import slice_indices
-        if self.method != 'cg' or not self.symmetric:
-            raise ValueError("precond='mg' serves method='cg' on a symmetric form only")
-        self._live()
-        MP = self.MP
-        if not MP.injective:
-            raise ValueError('the multigrid preconditioner needs injective local-to-global maps (two dofs of one patch share a '
-                             'global dof)')
-        smooth_steps = int(smooth_steps)
-        if not 1 <= smooth_steps <= 16:
-            raise ValueError('smooth_steps must be 1 .. 16')
-        if levels is not None and int(levels) < 1:
-            raise ValueError('levels must be >= 1')
-        nc = self.ncomp
-        maps0 = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
-        kvs0 = [kvs for kvs, _ in MP.patches]
-        sides = []
-        for c in range(nc):
-            try:
-                sides.append(fixed_sides(kvs0, maps0, self._component_fixed(c)))
-            except ValueError as e:
-                raise ValueError('component %d: %s' % (c, e)) from None
-        self._drop_multigrid()
-        lib = _lib.load()
-        problem, bfuns, args = self._problem
-        systems, keep = [self], []
-        try:
-            given = None if coarse is None else list(coarse)
-            while True:
-                S = systems[-1]
-                nfree = S.n - S.bc_indices.size
-                if given is not None:
-                    if not given:
-                        break
-                    MPc = given.pop(0)
-                    if MPc.numpatches != MP.numpatches:
-                        raise ValueError('a coarse multipatch has %d patches, the system %d' % (MPc.numpatches, MP.numpatches))
-                else:
-                    if (levels is not None and len(systems) >= int(levels)) or (levels is None and nfree <= coarse_max):
-                        break
-                    try:
-                        patches = [(tuple(coarsen_knots(kv) for kv in kvs), geo) for kvs, geo in S.MP.patches]
-                    except ValueError:
-                        break
-                    MPc = MP.replay_joins(patches)
-                Nc = MPc.numdofs
-                fixed = [c * Nc + MPc.patch_to_global_idx(p)[slice_indices(ax, 0 if side == 0 else -1,
-                                                                           tuple(kv.numdofs for kv in MPc.patches[p][0]), ravel=True)]
-                         for c in range(nc) for p, ax, side in sides[c]]
-                fixed = np.unique(np.concatenate(fixed)) if fixed else np.zeros(0, dtype=np.int64)
-                try:
-                    Sc = MultipatchVectorSystem(MPc, problem, 0.0, (fixed, np.zeros(fixed.size)), bfuns=bfuns, args=args, method='cg')
-                except Exception:
-                    MPc.close()
-                    raise
-                systems.append(Sc)
-            coarsest = systems[-1]
-            m = coarsest.n - coarsest.bc_indices.size
-            if m > coarse_max:
-                raise ValueError('the coarsest level keeps %d free dofs, more than coarse_max = %d' % (m, coarse_max))
-            info = [S._set_smoother(smooth_steps) for S in systems]
-            for F, Cs in zip(systems[:-1], systems[1:]):
-                np_ = MP.numpatches
-                Ps = []
-                for (kf, _), (kc, _) in zip(F.MP.patches, Cs.MP.patches):
-                    Ps += [np.ascontiguousarray(bspline.prolongation(c, f).toarray()) for c, f in zip(kc, kf)] + [None] * (3 - len(kf))
-                keep.append(Ps)
-                mult = np.zeros(F.N)
-                for p in range(np_):
-                    mult += np.bincount(F.MP.patch_to_global_idx(p), minlength=F.N)
-                Pp = (_lib._dp * (3 * np_))(*[None if a is None else _lib.dptr(a) for a in Ps])
-                _lib.check(lib.igx_solver_set_block_mg_coarse(F._live(), Cs._live(), Pp, _lib.dptr(mult)), 'igx_solver_set_block_mg_coarse')
-            # the coarsest matrix on its blocked free dofs, inverted on the host
-            A = coarsest.matrix()
-            fr = np.setdiff1d(np.arange(coarsest.n), coarsest.bc_indices)
-            inv = scipy.linalg.inv(A[fr][:, fr].toarray()) if fr.size else np.zeros((0, 0))
-            inv = np.ascontiguousarray(0.5 * (inv + inv.T))
-            _lib.check(lib.igx_solver_set_block_mg_inverse(coarsest._live(), _lib.dptr(inv), fr.size), 'igx_solver_set_block_mg_inverse')
-        except Exception:
-            for S in systems[1:]:
-                S.close()
-                S.MP.close()
-            raise
-        self._mg = dict(systems=systems, smooth_steps=smooth_steps, info=info)
-        if self._precond == 'mg':
-            self._precond = None                  # (the device dropped it when the hierarchy changed)
-        return self
-
-    def mg_colour_order(self, level=0):
-        """The nodes of `level` with a free component in the order the smoother's forward sweep relaxes them: sorted by
-        (colour, index)."""
-        self._mg_level(level)
-        inf = self._mg['info'][int(level)]
-        rows = np.empty(inf['nodes'], dtype=np.int32)
-        offs = np.empty(inf['colours'] + 1, dtype=np.int32)
-        _lib.check(_lib.load().igx_solver_mg_colours(self._live(), int(level), rows.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                     offs.ctypes.data_as(C.POINTER(C.c_int32))), 'igx_solver_mg_colours')
-        return rows.astype(np.int64)
+        return self._build_multigrid(levels, coarse, smooth_steps, coarse_max)
 
     def schwarz_setup(self):
         """Per component ``(boxes, U, lam, mode)`` of the block-diagonal Schwarz preconditioner (host set-up): the boxes of
@@ -1806,22 +1748,17 @@ class MultipatchVectorSystem(_DeviceSystem):
         shapes = [tuple(kv.numdofs for kv in kvs) for kvs, _ in MP.patches]
         maps = [MP.patch_to_global_idx(p) for p in range(MP.numpatches)]
         kvs_list = [tuple(kvs) for kvs, _ in MP.patches]
-        idx = self.bc_indices
         out = []
         for c in range(self.ncomp):
-            fixed = idx[(idx >= c * self.N) & (idx < (c + 1) * self.N)] - c * self.N
-            boxes = schwarz_boxes(shapes, maps, fixed)
+            boxes = schwarz_boxes(shapes, maps, self._component_fixed(c))
             U, lam, mode = schwarz_factors(kvs_list, boxes, 'stiffness')
             out.append((boxes, U, lam, mode))
         return out
 
     def _set_factors(self, h):
         lib = _lib.load()
-        slots = lambda per_patch, fill: [v[k] if k < len(v) else fill for v in per_patch for k in range(3)]
         for c, (boxes, U, lam, mode) in enumerate(self.schwarz_setup()):
-            lo, hi, Up, Lp = _box_args(slots([b[0] for b in boxes], 0), slots([b[1] for b in boxes], 0), slots(U, None),
-                                       slots(lam, None))
-            _lib.check(lib.igx_solver_set_block_schwarz(h, c, lo, hi, Up, Lp, mode), 'igx_solver_set_block_schwarz')
+            _lib.check(lib.igx_solver_set_block_schwarz(h, c, *_schwarz_args(boxes, U, lam), mode), 'igx_solver_set_block_schwarz')
         _lib.check(lib.igx_solver_set_precond(h, _lib.IGX_PRECOND_SCHWARZ, None, None, None, None, 0), 'igx_solver_set_precond')
         self._factors_set = True
 
@@ -1854,8 +1791,7 @@ class MultipatchVectorSystem(_DeviceSystem):
         ValueError.  'mg' takes a few tens of iterations where Jacobi takes hundreds to thousands, each of them a V-cycle of a few
         hundred short launches."""
         u = self._solve(self.b, tol, maxiter, precond, x0, check_every, timed)
-        if precond == 'mg':
-            self.info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
+        self._mg_solve_info(precond)
         return u
 
 
@@ -3127,38 +3063,68 @@ def _eig_fixed_dofs(bcs, n):
     return idx
 
 
-def _patch_eig_solve(S, k, tol, maxiter, precond, block, X0, seed, timed):
-    """``solve`` of the one-patch eigen-systems (``EigenSystem``, ``VectorEigenSystem``): ``lobpcg_loop`` on the device session
-    of `S`, which supplies ``n``, ``n_free``, ``_live()`` and ``set_precond``."""
-    k = int(k)
-    m = default_eig_block(max(k, 1)) if block is None else int(block)
-    _check_eig_args(k, m, S.n_free)
-    if X0 is None:
-        X0 = np.random.default_rng(seed).standard_normal((S.n, m))
-    else:
-        X0 = np.asarray(X0, dtype=np.float64)
-        if X0.shape != (S.n, m):
-            raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (S.n, m)))
-    h = S._live()
-    key = S.set_precond(precond)
-    ops = _DeviceEigOps(h, S.n, m, X0, timed)
-    try:
-        lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
-        U = ops.download('X', k)
-        dev = ops.info()
-    finally:
-        ops.end()
-    info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
-    if timed:
-        info.update({name: dev[name] for name in dev if name.endswith('_ms')})
-    S.info = info
-    return lam[:k].copy(), U
-
-
 class _EigBlockPieces:
-    """The block kernels of the eigen-solvers alone, on host arrays of shape ``(n, m)`` (``igx_solver_eig_*_d``): shared by
-    ``EigenSystem``, ``VectorEigenSystem`` and ``MultipatchEigenSystem``, which supply ``_live()``, ``_ctx``, ``n`` and
-    ``_set_eig_precond``."""
+    """What the eigen-solvers share (``EigenSystem``, ``VectorEigenSystem``, ``MultipatchEigenSystem``): the solve, the switch of
+    the preconditioner, and the block kernels alone on host arrays of shape ``(n, m)`` (``igx_solver_eig_*_d``).  A class
+    supplies ``_live()``, ``_ctx``, ``n``, ``n_free``, ``PRECONDS`` and ``set_precond`` (also under the name
+    ``_set_eig_precond``)."""
+
+    def _eig_solve(self, k, tol, maxiter, precond, block, X0, seed, timed):
+        """``solve`` of every eigen-system: ``lobpcg_loop`` on the device session of the system."""
+        k = int(k)
+        m = default_eig_block(max(k, 1)) if block is None else int(block)
+        _check_eig_args(k, m, self.n_free)
+        self._check_solve_precond(precond)
+        if X0 is None:
+            X0 = np.random.default_rng(seed).standard_normal((self.n, m))
+        else:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.shape != (self.n, m):
+                raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (self.n, m)))
+        h = self._live()
+        key = self.set_precond(precond)
+        ops = _DeviceEigOps(h, self.n, m, X0, timed)
+        try:
+            lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
+            U = ops.download('X', k)
+            dev = ops.info()
+        finally:
+            ops.end()
+        info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
+        self.info = info
+        self._eig_solve_info(key)
+        if timed:
+            info.update({name: dev[name] for name in dev if name.endswith('_ms')})
+        return lam[:k].copy(), U
+
+    def _check_solve_precond(self, precond):
+        """Hook of ``_eig_solve``: ValueError for a name `precond` that ``set_precond`` would refuse, before the start block is
+        drawn.  (Nothing for the one-patch systems: their ``set_precond`` refuses it after.)"""
+
+    def _eig_solve_info(self, key):
+        """Hook of ``_eig_solve``: further entries of ``self.info`` after a solve preconditioned with `key`."""
+
+    def _precond_key(self, precond):
+        """The name of `precond` ('none' for None, 'auto' as it is), or ValueError: before any device work."""
+        key = precond if precond is not None else 'none'
+        if key != 'auto' and key not in self.PRECONDS:
+            raise ValueError('unknown preconditioner %r' % (precond,))
+        return key
+
+    def _auto_precond(self):
+        return self.default_precond
+
+    def _switch_eig_precond(self, precond, install):
+        """``set_precond`` of every eigen-system: checks the name, resolves 'auto' (``_auto_precond``) and, unless it is the one
+        in place, has ``install(handle, key)`` hand the preconditioner to the device; returns its name."""
+        key = self._precond_key(precond)
+        h = self._live()
+        if key == 'auto':
+            key = self._auto_precond()
+        if key != self._eig_precond:
+            install(h, key)
+            self._eig_precond = key
+        return key
 
     # -- the pieces alone, on host arrays of shape (n, m)
     def _upload_block(self, A):
@@ -3325,25 +3291,17 @@ class EigenSystem(_PatchErrorNorms, _EigBlockPieces, _DeviceSystem):
 
     def set_precond(self, precond):
         """The preconditioner of ``solve`` and ``apply_precond``: 'auto', 'kron', 'jacobi' or None."""
-        if precond == 'auto':
-            precond = self.default_precond
-        key = precond if precond is not None else 'none'
-        if key not in self.PRECONDS:
-            raise ValueError('unknown preconditioner %r' % (precond,))
-        h = self._live()
-        if key == self._eig_precond:
-            return key
-        lib = _lib.load()
-        if key == 'kron':
-            if self.box is None:
-                raise ValueError("precond='kron' needs the fixed dofs to be a union of whole sides of the patch")
-            U, lam, mode = self._kron_factors()
-            lo, hi, Up, Lp = _box_args(self.box[0], self.box[1], U, lam)
-            _lib.check(lib.igx_solver_eig_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_eig_set_precond')
-        else:
-            _lib.check(lib.igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
-        self._eig_precond = key
-        return key
+        def install(h, key):
+            lib = _lib.load()
+            if key == 'kron':
+                if self.box is None:
+                    raise ValueError("precond='kron' needs the fixed dofs to be a union of whole sides of the patch")
+                U, lam, mode = self._kron_factors()
+                lo, hi, Up, Lp = _box_args(self.box[0], self.box[1], U, lam)
+                _lib.check(lib.igx_solver_eig_set_precond(h, _lib.IGX_PRECOND_KRON, lo, hi, Up, Lp, mode), 'igx_solver_eig_set_precond')
+            else:
+                _lib.check(lib.igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
+        return self._switch_eig_precond(precond, install)
 
     _set_eig_precond = set_precond
 
@@ -3351,7 +3309,7 @@ class EigenSystem(_PatchErrorNorms, _EigBlockPieces, _DeviceSystem):
         """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i M x_i|| <= tol ||K x_i||`` for the k lowest pairs.  `block`: the
         columns iterated (default ``k + max(2, k // 2)``, at most 16); `X0`: a start block of shape ``(n, block)``, else normal
         deviates of ``numpy.random.default_rng(seed)``.  Deterministic: the same inputs give the same bits."""
-        return _patch_eig_solve(self, k, tol, maxiter, precond, block, X0, seed, timed)
+        return self._eig_solve(k, tol, maxiter, precond, block, X0, seed, timed)
 
     def spmv(self, x):
         raise NotImplementedError('EigenSystem holds two matrices: block_products(X) or block_product(X, which)')
@@ -3431,27 +3389,20 @@ class VectorEigenSystem(_VectorBlocks, _EigBlockPieces, _DeviceSystem):
 
     def set_precond(self, precond):
         """The preconditioner of ``solve`` and ``apply_precond``: 'auto', 'kron', 'jacobi' or None."""
-        if precond == 'auto':
-            precond = self.default_precond
-        key = precond if precond is not None else 'none'
-        if key not in self.PRECONDS:
-            raise ValueError('unknown preconditioner %r' % (precond,))
-        h = self._live()
-        if key == self._eig_precond:
-            return key
-        if key == 'kron' and not self._factors_set:
-            self._set_block_kron(h)                                  # (ValueError when a component has no free box)
-            self._factors_set = True
-        _lib.check(_lib.load().igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
-        self._eig_precond = key
-        return key
+        def install(h, key):
+            if key == 'kron' and not self._factors_set:
+                self._set_block_kron(h)                              # (ValueError when a component has no free box)
+                self._factors_set = True
+            _lib.check(_lib.load().igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0),
+                       'igx_solver_eig_set_precond')
+        return self._switch_eig_precond(precond, install)
 
     _set_eig_precond = set_precond
 
     def solve(self, k=6, tol=1e-8, maxiter=200, precond='auto', block=None, X0=None, seed=0, timed=False):
         """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i (I (x) M) x_i|| <= tol ||K x_i||`` for the k lowest pairs;
         arguments, ``info`` and determinism as ``EigenSystem.solve`` (`X0` of shape ``(nc * N, block)``)."""
-        return _patch_eig_solve(self, k, tol, maxiter, precond, block, X0, seed, timed)
+        return self._eig_solve(k, tol, maxiter, precond, block, X0, seed, timed)
 
     def spmv(self, x):
         raise NotImplementedError('VectorEigenSystem holds two matrices: block_products(X) or block_product(X, which)')
@@ -3498,15 +3449,7 @@ class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
                     raise ValueError('MultipatchEigenSystem: %r is not known to be symmetric (the built-in stiffness and mass '
                                      'forms are, and a form string whose traced coefficient table is)' % (problem,))
         self.n = MP.numdofs
-        if bcs is None:
-            idx = np.zeros(0, dtype=np.int64)
-        elif isinstance(bcs, tuple) and len(bcs) == 2 and np.ndim(bcs[0]) >= 1:
-            idx = np.asarray(bcs[0], dtype=np.int64).ravel()
-        else:
-            idx = np.asarray(bcs, dtype=np.int64).ravel()
-        idx = np.unique(idx)
-        if idx.size and (idx[0] < 0 or idx[-1] >= self.n):
-            raise ValueError('fixed dof out of range')
+        idx = _eig_fixed_dofs(bcs, self.n)
         if _form_kind(problem) == 'stiffness' and idx.size == 0:
             raise ValueError('MultipatchEigenSystem: the stiffness matrix without any fixed dof is singular (the constants), and '
                              "the relative stopping rule ||r|| <= tol ||K x|| has no scale there.  Shift instead: "
@@ -3514,7 +3457,6 @@ class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
         self.n_free = self.n - idx.size
         form = STIFFNESS_FORM if problem is None else problem
         self._problem = (form, None, args, {})
-        self._mg = None
         self._eig_precond = False                                    # (no preconditioner of the eigen pieces set yet)
         lib = _lib.load()
         kinds = []
@@ -3536,7 +3478,8 @@ class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
             raise
         MP._solvers.add(self)
 
-    def _level_system(self, MPc, problem, rhs, bcs, args, kwargs):
+    def _level_system(self, MPc, bcs):
+        problem, rhs, args, kwargs = self._problem
         return _SymmetricLevelSystem(MPc, problem, rhs, bcs, args=args, **kwargs)
 
     def set_method(self, method):
@@ -3545,14 +3488,16 @@ class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
         _DeviceSystem.set_method(self, method)
 
     def _precond_key(self, precond):
-        """The name of `precond` ('none' for None), or ValueError: before any device work."""
         if precond == 'schwarz':
             raise ValueError("the Schwarz preconditioner is not offered for eigenproblems (in the host model it takes as many "
                              "iterations as Jacobi): use precond='mg'")
-        key = precond if precond is not None else 'none'
-        if key != 'auto' and key not in self.PRECONDS:
-            raise ValueError('unknown preconditioner %r' % (precond,))
-        return key
+        return super()._precond_key(precond)
+
+    def _check_solve_precond(self, precond):
+        self._precond_key(precond)
+
+    def _eig_solve_info(self, key):
+        self._mg_solve_info(key)
 
     def _auto_precond(self):
         """'mg' if a hierarchy of at least two levels is set up or ``set_multigrid()`` makes one, else 'jacobi'."""
@@ -3570,63 +3515,32 @@ class MultipatchEigenSystem(_EigBlockPieces, MultipatchSystem):
         """The preconditioner of ``solve`` and of ``apply_precond`` on blocks: 'auto', 'mg', 'jacobi' or None.  'auto' is 'mg' when
         ``set_multigrid()`` succeeds with at least one coarser level (the fixed dofs a union of whole patch sides, injective
         maps), else 'jacobi'; 'mg' alone calls ``set_multigrid()`` with its defaults if no hierarchy is set up."""
-        key = self._precond_key(precond)
-        h = self._live()
-        if key == 'auto':
-            key = self._auto_precond()
-        elif key == 'mg' and self._mg is None:
-            self.set_multigrid()
-        if key == self._eig_precond:
-            return key
-        _lib.check(_lib.load().igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0), 'igx_solver_eig_set_precond')
-        self._eig_precond = key
-        return key
+        def install(h, key):
+            if key == 'mg' and self._mg is None:
+                self.set_multigrid()
+            _lib.check(_lib.load().igx_solver_eig_set_precond(h, self.PRECONDS[key], None, None, None, None, 0),
+                       'igx_solver_eig_set_precond')
+        return self._switch_eig_precond(precond, install)
 
     _set_eig_precond = set_precond
 
     def _drop_multigrid(self):
-        MultipatchSystem._drop_multigrid(self)
+        super()._drop_multigrid()
         if getattr(self, '_eig_precond', None) == 'mg':
             self._eig_precond = False
 
-    def set_multigrid(self, *args, **kwargs):
-        MultipatchSystem.set_multigrid(self, *args, **kwargs)
+    def set_multigrid(self, levels=None, coarse=None, smooth_steps=1, coarse_max=2048, block_rows=None):
+        # (documented by MultipatchSystem.set_multigrid, which inspect.getdoc and help() show for it)
+        super().set_multigrid(levels, coarse, smooth_steps, coarse_max, block_rows)
         if self._eig_precond == 'mg':
             self._eig_precond = False             # (checked again against the new hierarchy)
         return self
-
-    set_multigrid.__doc__ = MultipatchSystem.set_multigrid.__doc__
 
     def solve(self, k=6, tol=1e-8, maxiter=200, precond='auto', block=None, X0=None, seed=0, timed=False):
         """Block LOBPCG (``lobpcg_loop``) to ``||K x_i - lam_i M x_i|| <= tol ||K x_i||`` for the k lowest pairs; arguments and
         ``info`` as ``EigenSystem.solve``.  `precond`: see ``set_precond``.  The V-cycle is applied column by column (`block`
         cycles per iteration).  Deterministic on injective maps: the same inputs give the same bits."""
-        k = int(k)
-        m = default_eig_block(max(k, 1)) if block is None else int(block)
-        _check_eig_args(k, m, self.n_free)
-        self._precond_key(precond)
-        if X0 is None:
-            X0 = np.random.default_rng(seed).standard_normal((self.n, m))
-        else:
-            X0 = np.asarray(X0, dtype=np.float64)
-            if X0.shape != (self.n, m):
-                raise ValueError('X0 of shape %r, expected %r' % (X0.shape, (self.n, m)))
-        h = self._live()
-        key = self.set_precond(precond)
-        ops = _DeviceEigOps(h, self.n, m, X0, timed)
-        try:
-            lam, info = lobpcg_loop(ops, m, k, float(tol), int(maxiter))
-            U = ops.download('X', k)
-            dev = ops.info()
-        finally:
-            ops.end()
-        info.update(precond=key, block_products=dev['products'], n_free=dev['n_free'], width=dev['mb'])
-        if key == 'mg':
-            info.update(levels=len(self._mg['systems']), smooth_steps=self._mg['smooth_steps'])
-        if timed:
-            info.update({name: dev[name] for name in dev if name.endswith('_ms')})
-        self.info = info
-        return lam[:k].copy(), U
+        return self._eig_solve(k, tol, maxiter, precond, block, X0, seed, timed)
 
     def vcycle(self, r):
         """One V-cycle of the hierarchy on the vector `r` of all dofs (``MultipatchSystem.apply_precond(r, 'mg')``)."""
