@@ -387,6 +387,13 @@ int igx_patch_quad_sums_d(igx_patch *patch, int nf, const double *const *d_f, do
    only).  d_elem: NULL or [1 + want_grad][nelem]. */
 int igx_patch_error_sums_d(igx_patch *patch, const double *d_coeffs, int want_grad, const double *const d_exact[4],
                            double *d_elem, double out[2]);
+/* Element residual sums of u_h (as above) for the Poisson problem -Lap u = f:  out[0] = sum W (f + Lap u_h)^2, Lap the PHYSICAL
+   Laplacian (second derivatives of u_h and of the geometry map at the Gauss points), out[1] = sum W.  d_f: the right-hand side at
+   the resident Gauss points or NULL (= 0).  d_elem: NULL or [2][nelem] with the same two sums per element.  A geometry given as
+   Jacobian arrays, a row slab or a span box: IGX_ERR_UNSUPPORTED, before anything is launched; a last axis whose line buffers
+   ((3 in 2D, 6 in 3D) * ndofs + 2 * ngauss doubles) exceed 64 KB: IGX_ERR_UNSUPPORTED.  Any space is taken: where u_h is not C^1
+   the sums are those of the element interiors (no jump terms). */
+int igx_patch_residual_sums_d(igx_patch *patch, const double *d_coeffs, const double *d_f, double *d_elem, double out[2]);
 
 /* Precomputed fields (W or upper triangle of B) of the owned Gauss slab: out has shape
    (F, G0_local, G1[, G2]) (structure-of-arrays).  For tests of precompute_fields. */

@@ -265,6 +265,7 @@ SYMBOLS = [
     ('igx_patch_eval_spline_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p * 4]),
     ('igx_patch_quad_sums_d', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, _dp]),
     ('igx_patch_error_sums_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p * 4, C.c_void_p, _dp]),
+    ('igx_patch_residual_sums_d', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
     ('igx_patch_eval_exprs_inputs_d', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_int)]),
     ('igx_rtc_compile_exprs_inputs', C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     ('igx_load_vector_jet_d', C.c_int, [C.c_void_p, C.c_void_p * 4, C.c_void_p]),

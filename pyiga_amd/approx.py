@@ -187,3 +187,46 @@ def error_norms(kvs, geo, u, exact=None, grad_exact=None, f_physical=True, eleme
     if elementwise:
         return res[1][0], (res[1][1] if want_grad else None)
     return float(np.sqrt(res[0])), (float(np.sqrt(res[1])) if want_grad else None)
+
+
+def eta2_of_sums(sums, dim):
+    """``eta_K^2 = h_K^2 sum_K W (f + Lap u_h)^2`` with ``h_K = (sum_K W)^(1/dim)`` from the two element sums of
+    ``DevicePatch.residual_sums`` (arrays of any one shape)."""
+    return np.power(sums[1], 2.0 / dim) * sums[0]
+
+
+def residual_estimator(kvs, geo, u, f=None, patch=None):
+    """The squared element indicators ``eta_K^2 = h_K^2 ||f + Lap u_h||^2_K`` (shape ``numspans``) of the residual-based
+    a-posteriori estimator of the Poisson problem ``-Lap u = f`` for the spline `u_h` of the tensor-product space `kvs` over the
+    geometry `geo` (None: the parameter domain); ``h_K = |K|^(1/dim)``.
+
+    `u` as in :func:`error_norms`; `f` is taken as that function takes `exact` (physical coordinates): a traceable callable is
+    evaluated by a generated kernel, anything else is sampled on the host and uploaded; None is zero.  One fused device pass
+    (``igx_patch_residual_sums_d``: second derivatives of `u_h` and of the geometry map at the Gauss points).  Interior
+    residuals only: the jump terms of a space that is not C^1, and Neumann terms, are not included.  2D and 3D.
+    """
+    from . import assemblers, geometry
+    from .operators import DeviceArray
+    if isinstance(kvs, bspline.KnotVector):
+        kvs = (kvs,)
+    kvs = tuple(kvs)
+    dim = len(kvs)
+    assert dim in (2, 3), 'residual_estimator: 2D and 3D patches'
+    ndofs = tuple(kv.numdofs for kv in kvs)
+    n = int(np.prod(ndofs))
+    if isinstance(u, DeviceArray):
+        size, c = u.n, None
+    else:
+        c = np.asarray(u.coeffs if hasattr(u, 'coeffs') else u, dtype=np.float64)
+        size = c.size
+    if size != n:
+        raise ValueError('residual_estimator: %d dofs, the space has %d' % (size, n))
+    P = patch if patch is not None else assemblers.DevicePatch(kvs, geo if geo is not None else geometry.unit_cube(dim))
+    try:
+        d_u = u.ptr if c is None else P.upload_dofs(c.reshape(ndofs), buf='_d_qdofs')
+        d_f = _exact_arrays(P, geo, f, None, True)
+        _, elem = P.residual_sums(d_u, None if d_f is None else d_f[0], elementwise=True)
+    finally:
+        if patch is None:
+            P.close()
+    return eta2_of_sums(elem, dim)

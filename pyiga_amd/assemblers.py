@@ -613,6 +613,16 @@ class DevicePatch:
         out = out[:n].copy()
         return (out, self._elem_result(d_elem, n)) if elementwise else out
 
+    def residual_sums(self, coeffs, f_d=None, elementwise=False):
+        """``sum W (f + Lap u_h)^2`` and ``sum W`` for the spline u_h with the device dof vector `coeffs`, Lap the physical
+        Laplacian (igx_patch_residual_sums_d).  `f_d`: device pointer of the right-hand side over the
+        resident Gauss points, or None (= 0).  Returns the array of the 2 sums, or with `elementwise` (sums, per-element sums of
+        shape ``(2,) + numspans``)."""
+        out = np.empty(2)
+        d_elem = self._dev_buffer('_d_qelem', 8 * 2 * int(np.prod(self.numspans))) if elementwise else None
+        _lib.check(_lib.load().igx_patch_residual_sums_d(self.handle, coeffs, f_d, d_elem, _lib.dptr(out)), 'igx_patch_residual_sums_d')
+        return (out, self._elem_result(d_elem, 2)) if elementwise else out
+
     def eval_exprs_inputs(self, exprs, d_inputs, to_host=False, buf='_d_tab'):
         """out[k] = exprs[k](x, y, z, pi, f0, f1, ..) at the resident Gauss points, f_j read from the device array d_inputs[j]
         (igx_patch_eval_exprs_inputs_d: compiled at run time, cached).  Returns (device pointers of the len(exprs) arrays, cache

@@ -156,6 +156,196 @@ __device__ __forceinline__ void physical_gradient(const GeoView &gv, bool nurbs,
     }
 }
 
+// Second-derivative tables of the geometry basis at the grid nodes, beside the GeoView (igx_patch_residual_sums_d): the tables
+// of launch_basis_tables' plain output, D2[k][l * G[k] + g] = second derivative of active function l of axis k at node g.
+struct GeoView2 {
+    const double *D2[3];
+    int G[3];
+};
+
+// geometry up to second order at one grid point: per component c (homogeneous: the weight is component DIM of a NURBS map)
+//   val[c], d1[c][k] = d / d xi_k, d2[c][.] = d^2 / d xi_a d xi_b in the order (00, 01, 11) / (00, 01, 02, 11, 12, 22), GRID axes.
+// One component at a time: 19 partial sums live instead of 19 per component.
+template <int DIM>
+__device__ inline void eval_geo2(const GeoView &gv, const GeoView2 &g2, bool nurbs, const int g[3], double val[DIM + 1], double d1[DIM + 1][3],
+                                 double d2[DIM + 1][6])
+{
+    const int nc = gv.nc;
+    const double *V0 = gv.V[0] + (size_t)g[0] * gv.P[0] * 2, *V1 = gv.V[1] + (size_t)g[1] * gv.P[1] * 2;
+    const double *D0 = g2.D2[0] + g[0], *D1 = g2.D2[1] + g[1];
+    const int f0 = gv.fa[0][g[0]], f1 = gv.fa[1][g[1]];
+#pragma unroll
+    for (int c = 0; c <= DIM; ++c) {
+        if (c == DIM && !nurbs) {
+            val[c] = 1.0;
+            for (int k = 0; k < 3; ++k) d1[c][k] = 0.0;
+            for (int k = 0; k < 6; ++k) d2[c][k] = 0.0;
+            continue;
+        }
+        if (DIM == 2) {
+            double v = 0.0, a0 = 0.0, a1 = 0.0, h00 = 0.0, h01 = 0.0, h11 = 0.0;
+            for (int i0 = 0; i0 < gv.P[0]; ++i0) {
+                const double *row = gv.ctrl + ((size_t)(f0 + i0) * gv.N[1] + f1) * nc + c;
+                double sv = 0.0, sd = 0.0, sdd = 0.0;
+                for (int i1 = 0; i1 < gv.P[1]; ++i1) {
+                    const double cf = row[(size_t)i1 * nc];
+                    sv = fma(V1[i1 * 2], cf, sv);
+                    sd = fma(V1[i1 * 2 + 1], cf, sd);
+                    sdd = fma(D1[(size_t)i1 * g2.G[1]], cf, sdd);
+                }
+                const double n0 = V0[i0 * 2], e0 = V0[i0 * 2 + 1], ee0 = D0[(size_t)i0 * g2.G[0]];
+                v = fma(n0, sv, v);
+                a0 = fma(e0, sv, a0);
+                a1 = fma(n0, sd, a1);
+                h00 = fma(ee0, sv, h00);
+                h01 = fma(e0, sd, h01);
+                h11 = fma(n0, sdd, h11);
+            }
+            val[c] = v;
+            d1[c][0] = a0; d1[c][1] = a1; d1[c][2] = 0.0;
+            d2[c][0] = h00; d2[c][1] = h01; d2[c][2] = h11; d2[c][3] = d2[c][4] = d2[c][5] = 0.0;
+        } else {
+            const double *V2 = gv.V[2] + (size_t)g[2] * gv.P[2] * 2, *D2 = g2.D2[2] + g[2];
+            const int f2 = gv.fa[2][g[2]];
+            double v = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0, h00 = 0.0, h01 = 0.0, h02 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0;
+            for (int i0 = 0; i0 < gv.P[0]; ++i0) {
+                double tv = 0.0, t1 = 0.0, t2 = 0.0, t11 = 0.0, t12 = 0.0, t22 = 0.0;
+                for (int i1 = 0; i1 < gv.P[1]; ++i1) {
+                    const double *row = gv.ctrl + (((size_t)(f0 + i0) * gv.N[1] + (f1 + i1)) * gv.N[2] + f2) * nc + c;
+                    double sv = 0.0, sd = 0.0, sdd = 0.0;
+                    for (int i2 = 0; i2 < gv.P[2]; ++i2) {
+                        const double cf = row[(size_t)i2 * nc];
+                        sv = fma(V2[i2 * 2], cf, sv);
+                        sd = fma(V2[i2 * 2 + 1], cf, sd);
+                        sdd = fma(D2[(size_t)i2 * g2.G[2]], cf, sdd);
+                    }
+                    const double n1 = V1[i1 * 2], e1 = V1[i1 * 2 + 1], ee1 = D1[(size_t)i1 * g2.G[1]];
+                    tv = fma(n1, sv, tv);
+                    t1 = fma(e1, sv, t1);
+                    t2 = fma(n1, sd, t2);
+                    t11 = fma(ee1, sv, t11);
+                    t12 = fma(e1, sd, t12);
+                    t22 = fma(n1, sdd, t22);
+                }
+                const double n0 = V0[i0 * 2], e0 = V0[i0 * 2 + 1], ee0 = D0[(size_t)i0 * g2.G[0]];
+                v = fma(n0, tv, v);
+                a0 = fma(e0, tv, a0);
+                a1 = fma(n0, t1, a1);
+                a2 = fma(n0, t2, a2);
+                h00 = fma(ee0, tv, h00);
+                h01 = fma(e0, t1, h01);
+                h02 = fma(e0, t2, h02);
+                h11 = fma(n0, t11, h11);
+                h12 = fma(n0, t12, h12);
+                h22 = fma(n0, t22, h22);
+            }
+            val[c] = v;
+            d1[c][0] = a0; d1[c][1] = a1; d1[c][2] = a2;
+            d2[c][0] = h00; d2[c][1] = h01; d2[c][2] = h02; d2[c][3] = h11; d2[c][4] = h12; d2[c][5] = h22;
+        }
+    }
+}
+
+// index of the pair (a, b), a <= b, in the packed upper triangle of eval_geo2
+template <int DIM>
+__device__ __forceinline__ constexpr int sym_index(int a, int b)
+{
+    return DIM == 2 ? a + b : (a == 0 ? b : a + b + 1);
+}
+
+// The coefficients of the physical Laplacian in parametric derivatives at one point:
+//     Lap u = sum_{c <= d} K[cd] D_c D_d u^ (off-diagonal entries doubled by the caller) + sum_c b[c] D_c u^
+// with JI = J^-1 (JI[c][r] = d xi_c / d x_r), K = JI JI^t and b_c = -sum_m JI[c][m] sum_{e,u} H2[m][e][u] K[e][u], H2 the second
+// parametric derivatives of the map (the trace of pyiga/vform.py:609-625's Christoffel term).  All parametric indices in JET
+// order: c = 0 is the LAST grid axis.  NURBS: second-order quotient rule with ONE reciprocal,
+//     x = A / w,  x_a = (A_a - w_a x) / w,  x_ab = (A_ab - w_a x_b - w_b x_a - w_ab x) / w.
+// K packed as eval_geo2 packs (00, 01[, 02], 11[, 12, 22]).
+template <int DIM>
+__device__ inline void laplace_coefficients(const GeoView &gv, const GeoView2 &g2, bool nurbs, const int gi[3], double K[6], double b[3])
+{
+    double val[DIM + 1], d1[DIM + 1][3], d2[DIM + 1][6];
+    eval_geo2<DIM>(gv, g2, nurbs, gi, val, d1, d2);
+    // physical first / second derivatives along GRID axes
+    double X1[DIM][DIM], X2[DIM][DIM * (DIM + 1) / 2];
+    if (nurbs) {
+        const double iw = 1.0 / val[DIM];
+#pragma unroll
+        for (int r = 0; r < DIM; ++r) {
+            const double x = val[r] * iw;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) X1[r][a] = (d1[r][a] - d1[DIM][a] * x) * iw;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a)
+#pragma unroll
+                for (int bb = a; bb < DIM; ++bb) {
+                    const int t = sym_index<DIM>(a, bb);
+                    X2[r][t] = (((d2[r][t] - d1[DIM][a] * X1[r][bb]) - d1[DIM][bb] * X1[r][a]) - d2[DIM][t] * x) * iw;
+                }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < DIM; ++r) {
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) X1[r][a] = d1[r][a];
+#pragma unroll
+            for (int t = 0; t < DIM * (DIM + 1) / 2; ++t) X2[r][t] = d2[r][t];
+        }
+    }
+    // jet order: parametric index c <-> grid axis DIM - 1 - c
+    double JI[DIM][DIM];
+    if (DIM == 2) {
+        const double J00 = X1[0][1], J01 = X1[0][0], J10 = X1[1][1], J11 = X1[1][0];
+        const double inv = 1.0 / (J00 * J11 - J01 * J10);
+        JI[0][0] = inv * J11; JI[0][1] = inv * -J01;
+        JI[1][0] = inv * -J10; JI[1][1] = inv * J00;
+    } else {
+        const double t[9] = {X1[0][2], X1[0][1], X1[0][0], X1[1][2], X1[1][1], X1[1][0], X1[2][2], X1[2][1], X1[2][0]};
+        const double t3 = t[4] * t[8] - t[5] * t[7];
+        const double t4 = t[3] * t[8] - t[5] * t[6];
+        const double t5 = t[3] * t[7] - t[4] * t[6];
+        const double inv = 1.0 / ((t[0] * t3 - t[1] * t4) + t[2] * t5);
+        JI[0][0] = inv * t3;
+        JI[0][1] = inv * -(t[1] * t[8] - t[2] * t[7]);
+        JI[0][2] = inv * (t[1] * t[5] - t[2] * t[4]);
+        JI[1][0] = inv * -t4;
+        JI[1][1] = inv * (t[0] * t[8] - t[2] * t[6]);
+        JI[1][2] = inv * -(t[0] * t[5] - t[2] * t[3]);
+        JI[2][0] = inv * t5;
+        JI[2][1] = inv * -(t[0] * t[7] - t[1] * t[6]);
+        JI[2][2] = inv * (t[0] * t[4] - t[1] * t[3]);
+    }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c)
+#pragma unroll
+        for (int d = c; d < DIM; ++d) {
+            double s = 0.0;
+#pragma unroll
+            for (int r = 0; r < DIM; ++r) s = fma(JI[c][r], JI[d][r], s);
+            K[sym_index<DIM>(c, d)] = s;
+        }
+    // s_m = sum_{e,u} H2[m][e][u] K[e][u]; jet pair (e, u) is grid pair (DIM-1-u, DIM-1-e)
+    double sm[DIM];
+#pragma unroll
+    for (int m = 0; m < DIM; ++m) {
+        double s = 0.0;
+#pragma unroll
+        for (int e = 0; e < DIM; ++e)
+#pragma unroll
+            for (int u = e; u < DIM; ++u) {
+                const double h = X2[m][sym_index<DIM>(DIM - 1 - u, DIM - 1 - e)], k = K[sym_index<DIM>(e, u)];
+                s = fma(e == u ? h : 2.0 * h, k, s);
+            }
+        sm[m] = s;
+    }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < DIM; ++m) s = fma(JI[c][m], sm[m], s);
+        b[c] = -s;
+    }
+}
+
 // quadrature fields of one point from its Jacobian (row-major t[]): f[0] = W for the mass form, the upper
 // triangle of  W * JacInv JacInv^T  (row-major) for the stiffness form.  Returns the number of fields.
 template <int DIM>

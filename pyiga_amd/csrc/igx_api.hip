@@ -407,6 +407,7 @@ void igx_patch_destroy(igx_patch *pt)
     (void)hipFree(pt->d_lv_f); (void)hipFree(pt->d_lv_t1); (void)hipFree(pt->d_lv_t2); (void)hipFree(pt->d_lv_o);
     (void)hipFree(pt->d_sp_ws);
     (void)hipFree(pt->d_q_ws);
+    for (int k = 0; k < 3; ++k) { (void)hipFree(pt->d_tab2[k]); (void)hipFree(pt->d_gtab2[k]); }
     delete pt;
 }
 
@@ -1594,6 +1595,29 @@ int igx_patch_error_sums_d(igx_patch *pt, const double *d_coeffs, int want_grad,
     (void)hipEventRecord(pt->ctx->ev[7], st);
     if (rc) return rc;
     return quad_done(pt, st, d_tot, nk, out, nl);
+}
+
+// sum W (f + Lap u_h)^2 and sum W, total and per element (k_res12, kern_quad.hip)
+int igx_patch_residual_sums_d(igx_patch *pt, const double *d_coeffs, const double *d_f, double *d_elem, double out[2])
+{
+    if (!pt || !d_coeffs || !out) { set_error("igx_patch_residual_sums_d: null argument"); return IGX_ERR_ARG; }
+    if (int rcp = quad_patch_ok(pt, "igx_patch_residual_sums_d")) return rcp;
+    if (pt->geo_kind == IGX_GEO_JACOBIAN) { set_error("igx_patch_residual_sums_d: the Laplacian needs a spline geometry (second derivatives of the map)"); return IGX_ERR_UNSUPPORTED; }
+    if (int rcb = basis_orders_ok(pt, IGX_MASS, "igx_patch_residual_sums_d")) return rcb;
+    IGX_HIP(hipSetDevice(pt->ctx->device));
+    hipStream_t st = pt->ctx->stream;
+    int rc = ensure_fields(pt, IGX_MASS);
+    if (rc) return rc;
+    if ((rc = residual_tables(st, pt))) return rc;
+    if ((rc = ws_reserve(&pt->d_sp_ws, &pt->sp_ws_cap, residual_spline_workspace(pt), "spline evaluation workspace"))) return rc;
+    if ((rc = ws_reserve(&pt->d_q_ws, &pt->q_ws_cap, quad_workspace(pt, 2), "quadrature workspace"))) return rc;
+    double *d_tot = nullptr;
+    int nl = 0;
+    (void)hipEventRecord(pt->ctx->ev[6], st);
+    rc = launch_residual_sums(st, pt, d_coeffs, d_f, pt->d_fields, d_elem, pt->d_sp_ws, pt->d_q_ws, &d_tot, &nl);
+    (void)hipEventRecord(pt->ctx->ev[7], st);
+    if (rc) return rc;
+    return quad_done(pt, st, d_tot, 2, out, nl);
 }
 
 // out[k * npts + i] = expr_k(x, y, z, pi, f0 .. f{m-1}) at the resident points, f_j = d_in[j][i]

@@ -227,6 +227,10 @@ struct igx_patch {
     size_t sp_ws_cap = 0;
     double *d_q_ws = nullptr;                 // partial lines, element sums and totals of igx_patch_quad_sums_d / _error_sums_d (kern_quad.hip), grow-only
     size_t q_ws_cap = 0;
+    // igx_patch_residual_sums_d: derivative tables (orders 0, 1, 2: [3][P][G], launch_basis_tables' plain output) of the solution
+    // space and of the geometry space per axis, made on first use and kept; the kernels read the order-2 part [P][G]
+    double *d_tab2[3] = {nullptr, nullptr, nullptr}, *d_gtab2[3] = {nullptr, nullptr, nullptr};
+    bool tab2_ready = false;
     // fused sweep + final stage (fused.hip)
     long long nnz_ext = 0;                    // values of the owned rows + the p0 halo planes above them (mirror sources)
     double *d_zeros = nullptr;                // a row of zeros: input of absent sweep slots
@@ -309,6 +313,13 @@ int launch_quad_sums(hipStream_t st, const igx_patch *pt, int nf, const double *
                      double **d_tot, int *n_launches);
 int launch_error_sums(hipStream_t st, const igx_patch *pt, const double *d_coeffs, int want_grad, const double *const d_exact[4], const double *d_W,
                       double *d_elem, double *d_sp_ws, double *d_ws, double **d_tot, int *n_launches);
+// element residual sums  sum W (f + Lap u_h)^2, sum W  of a spline (kern_quad.hip: k_res12); the axis-0 pre-pass with the second
+// derivative (kern_spline.hip)
+int launch_spline_axis0_d2(hipStream_t st, const igx_patch *pt, const double *d_coeffs, const double *d_d2, double *d_ws);
+size_t residual_spline_workspace(const igx_patch *pt);
+int residual_tables(hipStream_t st, igx_patch *pt);
+int launch_residual_sums(hipStream_t st, const igx_patch *pt, const double *d_coeffs, const double *d_f, const double *d_W,
+                         double *d_elem, double *d_sp_ws, double *d_ws, double **d_tot, int *n_launches);
 // coefficient expressions that also read device arrays f0 .. f{m-1} at the thread's point (rtc.hip)
 int launch_form_exprs_inputs(hipStream_t st, igx_patch *pt, int n_expr, const char *const *expr, int m, const double *const *d_in, double *d_out, int *cache_hit);
 int rtc_compile_form_inputs(int n_expr, const char *const *expr, int m, const char *arch, char *path_out, int path_len, int *cache_hit);

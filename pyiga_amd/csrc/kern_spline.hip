@@ -37,6 +37,42 @@ __global__ void __launch_bounds__(256) k_spline_axis0(const double *__restrict__
     if (ND == 2) t[total + idx] = r1;
 }
 
+// The same with the second derivative along axis 0 as a third array, for the residual sums (kern_quad.hip): d2 is the axis'
+// second-derivative table [P][G0] (launch_basis_tables' plain output).  A sibling, so that k_spline_axis0 keeps its code.
+__global__ void __launch_bounds__(256) k_spline_axis0_d2(const double *__restrict__ c, double *__restrict__ t, const AxisDev a0,
+                                                         const double *__restrict__ d2, int g0_lo, int G0, long long B)
+{
+    const long long total = (long long)G0 * B;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int g = (int)(idx / B);
+    const long long j = idx - (long long)g * B;
+    const int gg = g0_lo + g, P = a0.P;
+    const double *V = a0.V + (size_t)gg * P * 2;
+    const double *src = c + (long long)a0.fa[gg / a0.q] * B + j;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    for (int l = 0; l < P; ++l) {
+        const double x = src[(long long)l * B];
+        r0 = fma(V[2 * l], x, r0);
+        r1 = fma(V[2 * l + 1], x, r1);
+        r2 = fma(d2[(size_t)l * a0.G + gg], x, r2);
+    }
+    t[idx] = r0;
+    t[total + idx] = r1;
+    t[2 * total + idx] = r2;
+}
+
+// 3D: value, first and second axis-0 derivative planes of the dofs into d_ws (3 G0 N1 N2 doubles); 2D: nothing to do
+int launch_spline_axis0_d2(hipStream_t st, const igx_patch *pt, const double *d_coeffs, const double *d_d2, double *d_ws)
+{
+    const PatchDev &pd = pt->dev;
+    if (pd.dim != 3) return IGX_OK;
+    const long long B = (long long)pd.ax[1].N * pd.ax[2].N, total = (long long)pd.G0_loc * B;
+    k_spline_axis0_d2<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(d_coeffs, d_ws, pd.ax[0], d_d2, pd.g0_lo, pd.G0_loc, B);
+    IGX_HIP(hipGetLastError());
+    return IGX_OK;
+}
+
 struct SplineOut { double *o[4]; };
 
 // Mid and last axis of a grid line.  A WAVE owns `lpw` consecutive lines (plane, Gauss index gm of the mid axis).  Per line:

@@ -477,6 +477,21 @@ class HSpace:
         R.eliminate_zeros()
         return R
 
+    def level_restriction(self, lv):
+        """The CSR matrix (``mesh(lv).numbf x numdofs``) that maps canonical **HB** coefficients to the coefficients of the
+        tensor-product spline of level `lv` that equals the hierarchical function on the active cells of level `lv` (THB
+        coefficients go through :meth:`thb_to_hb` first).
+
+        On an active cell of level `lv` only functions of the levels up to `lv` are non-zero, so this is
+        ``represent_fine(lv, truncate=False)`` on the rows of the functions whose support meets an active cell of the level,
+        restricted to the columns of the active functions of the levels up to `lv` and padded with zero columns."""
+        assert 0 <= lv < self.numlevels, 'Invalid level.'
+        m = self.mesh(lv)
+        rows = np.flatnonzero(m.supported_in_mask(self._cact[lv]))
+        n_lv = int(sum(self.numactive[:lv + 1]))
+        R = scipy.sparse.csr_matrix(self.represent_fine(lv, truncate=False, rows=rows)[:, :n_lv])
+        return scipy.sparse.csr_matrix((R.data, R.indices, R.indptr), shape=(m.numbf, self.numdofs))
+
     def truncate_one_level(self, k, num_rows=None, inverse=False):
         """The matrix of the truncation from level `k` to `k` + 1 (``inverse=True``: of its inverse)."""
         nt = np.cumsum(self.numactive)
@@ -722,6 +737,37 @@ class HSplineFunc:
         return float(np.asarray(self.grid_eval(grid)).ravel()[0])
 
     __call__ = eval
+
+
+def mark(hs, eta2, theta=0.5, strategy='dorfler'):
+    """The cells to refine from the squared indicators `eta2` (one per active cell, in the order of
+    ``hs.active_cells(flat=True)``): ``{level: set of cell tuples}``, ready for ``hs.refine``.
+
+    ``'dorfler'``: the cells sorted by `eta2` descending (ties: canonical position ascending), the shortest prefix whose sum is at
+    least ``theta * sum(eta2)``, summed in that order.  ``'max'``: the cells with ``eta2 >= theta^2 max(eta2)``."""
+    eta2 = np.asarray(eta2, dtype=np.float64).ravel()
+    cells = hs.active_cells(flat=True)
+    if eta2.size != len(cells):
+        raise ValueError('mark: %d indicators for %d active cells' % (eta2.size, len(cells)))
+    if not (0.0 < theta <= 1.0):
+        raise ValueError('mark: theta = %r, expected 0 < theta <= 1' % (theta,))
+    if not np.all(eta2 >= 0.0):
+        raise ValueError('mark: squared indicators are not negative (or NaN)')
+    if strategy == 'dorfler':
+        order = np.argsort(-eta2, kind='stable')
+        csum = np.cumsum(eta2[order])
+        # (all indicators zero: the empty prefix already reaches theta * 0)
+        n = int(np.searchsorted(csum, theta * csum[-1], side='left')) + 1 if eta2.size and csum[-1] > 0.0 else 0
+        picked = order[:min(n, eta2.size)]
+    elif strategy == 'max':
+        picked = np.flatnonzero(eta2 >= theta * theta * eta2.max()) if eta2.size else np.zeros(0, dtype=np.int64)
+    else:
+        raise ValueError("mark: unknown strategy %r ('dorfler' or 'max')" % (strategy,))
+    out = {}
+    for i in picked.tolist():
+        lv, c = cells[i]
+        out.setdefault(lv, set()).add(c)
+    return out
 
 
 ################################################################################

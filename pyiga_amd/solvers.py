@@ -3987,6 +3987,7 @@ class HierarchicalSystem:
             if np.any(lift[hs.non_dirichlet_dofs()] != 0.0):
                 raise ValueError('lift must vanish on the non-Dirichlet dofs')
         self.lift = lift
+        self.geo, self.problem, self.rhs_form, self.inputs = geo, problem, rhs, dict(inputs)     # (read by error_norms / estimate)
         disc = HDiscretization(hs, problem, dict(inputs, geo=geo), max_blocks=max_blocks)
         try:
             disc.assemble_hb_values()
@@ -4074,6 +4075,140 @@ class HierarchicalSystem:
     def level_matrix(self, l):
         return (self.setup()._H if self._H is None else self._H).level_matrix(l)
 
+    # -- error norms and the residual estimator, level by level on the device
+    def _level_sums(self, u, nk, sums):
+        """The per-cell sums of `nk` quantities over the active cells, ``(nk, total_active_cells)`` in the order of
+        ``hs.active_cells(flat=True)``: per level with active cells one ``DevicePatch`` on the level's knot vectors, the level
+        coefficients ``level_restriction(lv) u_hb`` formed on the device, ``sums(patch, d_coeffs, d_elem)`` writing the
+        ``(nk, numspans)`` element sums of the whole level to `d_elem`, and the gather of the active cells.  Only the dofs go up
+        (unless `u` is a ``DeviceArray``) and only the per-cell array comes down."""
+        from .assemblers import DevicePatch
+        hs, ctx, lib = self.hs, self._ctx, _lib.load()
+        if isinstance(u, DeviceArray):
+            if u.n != self.n:
+                raise ValueError('%d coefficients, the space has %d dofs' % (u.n, self.n))
+            d_u = u
+        else:
+            c = _lib.f64(u.coeffs if hasattr(u, 'coeffs') else u)
+            if c.shape != (self.n,):
+                raise ValueError('coefficients of shape %r, the space has %d dofs' % (c.shape, self.n))
+            d_u = DeviceArray.from_host(ctx, c)
+        ncells = hs.total_active_cells
+        d_out = DeviceArray(ctx, nk * ncells)
+        tmp = _DeviceBytes(ctx)
+        own = [d_out] + ([] if d_u is u else [d_u])          # freed below, not left to the collector
+
+        def spmv(M, d_x, d_y):
+            M = _csr32(M)
+            _lib.check(lib.igx_csr_rect_spmv_d(ctx.handle, M.shape[0], M.shape[1], tmp.upload(M.indptr), tmp.upload(M.indices), tmp.upload(M.data),
+                                               M.nnz, int(np.diff(M.indptr).max()) if M.shape[0] else 0, d_x, d_y, 0, int(self.max_blocks or 0)),
+                       'igx_csr_rect_spmv_d')
+        try:
+            if hs.truncate:                               # THB coefficients -> HB coefficients of the same function
+                d_hb = DeviceArray(ctx, self.n)
+                own.append(d_hb)
+                spmv(hs.thb_to_hb(), d_u.ptr, d_hb.ptr)
+                d_u = d_hb
+            off = 0
+            for lv in range(hs.numlevels):
+                act = np.flatnonzero(hs._cact[lv])
+                if not act.size:
+                    continue
+                kvs = hs.knotvectors(lv)
+                nelem = hs.mesh(lv).numel
+                patch = DevicePatch(kvs, self.geo)
+                try:
+                    d_c = tmp.alloc(8 * hs.mesh(lv).numbf)
+                    spmv(hs.level_restriction(lv), d_u.ptr, d_c)
+                    d_elem = patch._dev_buffer('_d_qelem', 8 * nk * nelem)
+                    sums(patch, d_c, d_elem)
+                    d_idx = tmp.upload(act.astype(np.int64))
+                    for k in range(nk):
+                        _lib.check(lib.igx_hier_gather_d(ctx.handle, C.c_void_p(d_elem + 8 * k * nelem), nelem, d_idx, act.size,
+                                                         C.c_void_p(d_out.ptr + 8 * (k * ncells + off))), 'igx_hier_gather_d')
+                    _lib.check(lib.igx_sync(ctx.handle), 'igx_sync')        # (the gather reads what the patch frees next)
+                finally:
+                    patch.close()
+                off += act.size
+            return d_out.download().reshape(nk, ncells)
+        finally:
+            tmp.free()                                    # (waits for the stream first)
+            for d in own:
+                d.free()
+
+    def error_norms(self, u, exact=None, grad_exact=None, elementwise=False):
+        """``(l2, h1)`` of ``u_h - exact`` for the hierarchical spline with the canonical coefficients `u` (a host array, an
+        ``HSplineFunc`` or a ``DeviceArray``; THB coefficients for a THB space), as :func:`approx.error_norms`: `exact` and
+        `grad_exact` in physical coordinates, `h1` None when `exact` comes without `grad_exact`.  ``elementwise=True``: the flat
+        arrays of the squared contributions of the active cells in the order of ``hs.active_cells(flat=True)``; the totals are
+        the sums over those cells in that order."""
+        from . import approx
+        if grad_exact is not None and exact is None:
+            raise ValueError('error_norms: grad_exact without exact')
+        if self._matrix is None:
+            raise _lib.IgxError('the system was closed')
+        want_grad = exact is None or grad_exact is not None
+        nk = 2 if want_grad else 1
+        out = np.empty(2)
+
+        def sums(patch, d_c, d_elem):
+            d_exact = approx._exact_arrays(patch, self.geo, exact, grad_exact, True)
+            ptrs = (C.c_void_p * 4)()
+            for r, e in enumerate(d_exact or ()):
+                if e is not None:
+                    ptrs[r] = e
+            _lib.check(_lib.load().igx_patch_error_sums_d(patch.handle, d_c, 1 if want_grad else 0, ptrs, d_elem, _lib.dptr(out)),
+                       'igx_patch_error_sums_d')
+        cells = self._level_sums(u, nk, sums)
+        if elementwise:
+            return cells[0], (cells[1] if want_grad else None)
+        return float(np.sqrt(cells[0].sum())), (float(np.sqrt(cells[1].sum())) if want_grad else None)
+
+    def _check_estimate(self):
+        from . import assemble
+        if self.problem is None or not isinstance(self.problem, str) or self.rhs_form is not None or \
+                assemble._normalise_form(self.problem) != assemble._normalise_form('inner(grad(u),grad(v))*dx'):
+            raise ValueError("estimate: the residual estimator eta_K = h_K ||f + Lap u_h||_K belongs to the Poisson problem: the system must be built "
+                             "with the form 'inner(grad(u),grad(v))*dx' and the default right-hand side 'f * v * dx'")
+        for lv in range(self.hs.numlevels):
+            if not self.hs._cact[lv].any():
+                continue
+            for kv in self.hs.knotvectors(lv):
+                kn = np.asarray(kv.kv)
+                mult = np.unique(kn[kv.p + 1:len(kn) - kv.p - 1], return_counts=True)[1]
+                if kv.p < 2 or (mult.size and int(mult.max()) >= kv.p):
+                    raise ValueError('estimate: the space of level %d is not C^1 (degree %d, largest interior knot multiplicity %d): the jump terms '
+                                     'of the normal derivative across its cell faces would be missing from the estimator'
+                                     % (lv, kv.p, int(mult.max()) if mult.size else 0))
+
+    def estimate(self, u, f=None):
+        """``(eta, eta2)``: the residual-based a-posteriori estimator of the Poisson problem for the canonical coefficients `u`
+        (as :meth:`error_norms`) and its squared cell indicators ``eta_K^2 = h_K^2 ||f + Lap u_h||^2_K``, ``h_K = |K|^(1/dim)``,
+        over the active cells in the order of ``hs.active_cells(flat=True)``; ``eta = sqrt(sum(eta2))``.  `f`: the right-hand
+        side, a callable of the physical coordinates (default: the system's own input ``f``; anything else: TypeError), taken as
+        ``error_norms`` takes `exact`; without one it is zero.
+
+        ValueError unless the system was built with ``inner(grad(u),grad(v))*dx`` and the default right-hand side, and every
+        level's space is C^1 (degree >= 2, no interior knot of multiplicity >= p): otherwise jump terms would be missing."""
+        from . import approx
+        self._check_estimate()
+        if self._matrix is None:
+            raise _lib.IgxError('the system was closed')
+        if f is None:
+            f = self.inputs.get('f')
+        if f is not None and not callable(f):
+            raise TypeError('estimate: the right-hand side f is a callable of the physical coordinates (or None for zero), not %r; '
+                            'wrap a constant as  lambda *x: c' % type(f).__name__)
+        out = np.empty(2)
+
+        def sums(patch, d_c, d_elem):
+            d_f = approx._exact_arrays(patch, self.geo, f, None, True)
+            _lib.check(_lib.load().igx_patch_residual_sums_d(patch.handle, d_c, None if d_f is None else d_f[0], d_elem, _lib.dptr(out)),
+                       'igx_patch_residual_sums_d')
+        cells = self._level_sums(u, 2, sums)
+        eta2 = approx.eta2_of_sums(cells, self.hs.dim)
+        return float(np.sqrt(eta2.sum())), eta2
+
     def close(self):
         if self._H is not None:
             self._H.close()
@@ -4091,3 +4226,45 @@ class HierarchicalSystem:
             self.close()
         except Exception:
             pass
+
+
+def adaptive_solve(hs, geo, f, theta=0.5, strategy='dorfler', max_rounds=10, max_dofs=None, tol=None, lift=None, inplace=False,
+                   solve_tol=None, **solve_options):
+    """The adaptive loop solve -> estimate -> mark -> refine for the Poisson problem ``-Lap u = f`` with the Dirichlet sides of
+    ``hs.bdspecs`` over the hierarchical space `hs`.
+
+    Per round a :class:`HierarchicalSystem` is built and solved (`solve_options`: the keywords of its ``solve``, whose own `tol`
+    is given as `solve_tol` here: `tol` is the estimator's), the residual estimator is evaluated (``estimate``), and unless
+    ``eta <= tol``, the space has reached `max_dofs` dofs or this was round
+    `max_rounds`, the cells picked by ``hierarchical.mark(hs, eta2, theta, strategy)`` are refined with
+    ``hs.refine(marked, truncate=hs.truncate)``.  `lift`: None or a callable ``hs -> lift array`` (inhomogeneous Dirichlet data).
+    The loop works on ``hs.copy()`` unless `inplace`.  Only the dofs and the per-cell indicators cross the bus.
+
+    Returns ``(hs, u, history)``: the final space, the solution on it (canonical coefficients) and one dict per round with
+    ``dofs``, ``cells`` (active cells per level), ``eta``, ``eta2``, ``iterations`` and ``marked`` (the dict given to ``refine``;
+    empty in the last round).  Limits: no coarsening; nothing of a round's assembly or solution is reused in the next."""
+    from .hierarchical import mark
+    if max_rounds < 1:
+        raise ValueError('adaptive_solve: max_rounds = %r' % (max_rounds,))
+    if solve_tol is not None:
+        solve_options = dict(solve_options, tol=solve_tol)
+    if not inplace:
+        hs = hs.copy()
+    history, u = [], None
+    for rnd in range(int(max_rounds)):
+        S = HierarchicalSystem(hs, 'inner(grad(u),grad(v))*dx', None, geo=geo, lift=None if lift is None else lift(hs), f=f)
+        try:
+            u = S.solve(**solve_options)
+            eta, eta2 = S.estimate(u)
+            rec = dict(dofs=hs.numdofs, cells=tuple(int(m.sum()) for m in hs._cact), eta=eta, eta2=eta2, iterations=S.info['iterations'], marked={})
+        finally:
+            S.close()
+        history.append(rec)
+        if (tol is not None and eta <= tol) or (max_dofs is not None and hs.numdofs >= max_dofs) or rnd == max_rounds - 1:
+            break
+        marked = mark(hs, eta2, theta, strategy)
+        if not marked:
+            break
+        rec['marked'] = marked
+        hs.refine(marked, truncate=hs.truncate)
+    return hs, u, history
